@@ -12,6 +12,7 @@ so `--steps K` times K such frames whatever K is (the samples per frame are `--s
 Inputs (scene, BVH, camera) are resident in HBM before the timed region.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed frame as DIR/*.npy, for comparing two builds
   python bench.py --gpus N ...            # no launcher needed: starts its N ranks itself (torch.distributed.run, as a child)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
@@ -89,7 +90,36 @@ def parse(argv=None):
     ap.add_argument("--force-rccl", action="store_true",
                     help="N = 1: run the RCCL branch anyway (unique id -> comm_init -> gather -> gathered) with a one-rank communicator")
     ap.add_argument("--dump", default=None, help="write the tone-mapped frame (PPM) here (rank 0)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0): the accumulated frame (float32, "
+                         "width*height x 3) and, on one GPU, the per-bounce (rays_in, hits, misses, shaded) table of the last sample (float64)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, frame, table):
+    """--dump-outputs: the arrays the timed path hands its caller, as .npy files. A frame too large for DUMP_LIMIT_BYTES is written as a
+    fixed, seeded sample of its pixels (accumulated.npy) with their indices (accumulated_pixels.npy), the same sample on every run."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"accumulated": np.ascontiguousarray(frame, np.float32).reshape(-1, 3)}
+    if table is not None:
+        arrays["bounce_table"] = np.asarray(table, np.float64).reshape(-1, 4)
+    n = arrays["accumulated"].shape[0]
+    room = DUMP_LIMIT_BYTES - (1 << 20)  # 1 MB kept for the small arrays and the .npy headers
+    if arrays["accumulated"].nbytes > room:
+        keep = room // (3 * 4 + 8)  # a sampled pixel costs its float32 RGB and its float64 index
+        pixels = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays["accumulated"] = arrays["accumulated"][pixels]
+        arrays["accumulated_pixels"] = pixels.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def self_launch(args):
@@ -387,6 +417,12 @@ def main():
             frame = pt.gathered()  # outside the timed region: the frame crosses PCIe only for the dump / the check
     elif world == 1:
         frame = pt.accumulated()
+    # --dump-outputs: what the last timed step computed, taken here because the passes below render again
+    dumped_frame = last_table = None
+    if args.dump_outputs and frame is not None:
+        dumped_frame = np.array(frame.cpu().numpy() if hasattr(frame, "cpu") else frame, np.float32)
+        if world == 1:
+            last_table = pt.bounce_table()  # the frame's last sample
     # ---- where an N > 1 figure comes from ("scaling factor, gather time"), all OUTSIDE the timed region:
     #   rank_ms_per_step         every rank's own wall time per step of the timed loop (its renders + its leg of the gather)
     #   rank_render_ms_per_step  the same K frames once more WITHOUT the gather, every rank timing itself: what the slab costs
@@ -682,6 +718,8 @@ def main():
         with open(args.dump, "wb") as f:
             f.write(b"P6\n%d %d\n255\n" % (args.width, args.height))
             f.write(rgb.tobytes())
+    if dumped_frame is not None:
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, dumped_frame, last_table)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -52,3 +52,37 @@ def test_cpu_share_reads_quota_and_affinity(orc):
     orc.set_num_threads(2)
     assert orc.lib().orc_num_threads() == 2
     orc.set_num_threads(min(s["granted"], 16))
+
+
+def test_dump_outputs_writes_the_frame_and_table(tmp_path):
+    import numpy as np
+    frame = np.arange(200 * 120 * 3, dtype=np.float32).reshape(-1, 3)
+    table = np.array([[100, 60, 40, 1], [60, 30, 30, 0]], np.uint32)
+    shapes = bench.dump_outputs(str(tmp_path / "out"), frame, table)
+    assert shapes == {"accumulated": [200 * 120, 3], "bounce_table": [2, 4]}
+    got = np.load(tmp_path / "out" / "accumulated.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    t = np.load(tmp_path / "out" / "bounce_table.npy")
+    assert t.dtype == np.float64 and np.array_equal(t, table)
+
+
+def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path):
+    import numpy as np
+    n = 3840 * 2160 * 2  # 199 MB of float32 RGB: more than the dump may hold
+    frame = np.broadcast_to(np.arange(n, dtype=np.float32)[:, None], (n, 3))
+    bench.dump_outputs(str(tmp_path / "a"), frame, None)
+    bench.dump_outputs(str(tmp_path / "b"), frame, None)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= bench.DUMP_LIMIT_BYTES
+    a, idx = np.load(tmp_path / "a" / "accumulated.npy"), np.load(tmp_path / "a" / "accumulated_pixels.npy")
+    assert a.dtype == np.float32 and idx.dtype == np.float64 and len(a) == len(idx) > 1000000
+    assert np.all(np.diff(idx) > 0) and np.array_equal(a[:, 0], idx.astype(np.float32))  # each row is the pixel its index names
+    assert np.array_equal(a, np.load(tmp_path / "b" / "accumulated.npy"))
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "accumulated_pixels.npy"))
+
+
+def test_steps_sets_the_timed_steps():
+    import pytest
+    assert bench.parse(["--steps", "7"]).steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

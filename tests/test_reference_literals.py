@@ -5,7 +5,8 @@ sources (numeric literals and struct field orders only, with file:line). These t
 (oracle/orc_math.h, oracle/wfpt_oracle.c), the device code (csrc/wfpt_device_math.h, csrc/wfpt_kernels.hip), the host
 restatement (csrc/wfpt_host.cpp), the boundary header (include/wfpt.h) and the host mirrors carry exactly those values.
 Floating-point results of WGSL built-ins remain "parity unpinned" (DESIGN.md section 2); this shrinks the unpinned
-surface to them. No GPU needed; /root/reference is only touched by the staleness check, which is skipped without it.
+surface to them. No GPU needed, and nothing outside the repository is read: after a change to the reference, re-run the extractor
+by hand and commit its output.
 """
 import inspect
 import json
@@ -14,7 +15,6 @@ import re
 
 import numpy as np
 import struct
-import subprocess
 import sys
 
 import pytest
@@ -59,17 +59,6 @@ def both(entries):
     values = [e["value"] for e in entries]
     assert len(set(map(str, values))) == 1, f"the reference's two copies differ: {entries}"
     return values[0]
-
-
-def test_committed_json_is_current(tmp_path):
-    """With the reference present (build container), re-extract into a scratch file and compare with the committed one."""
-    if not os.path.isdir("/root/reference/gpu_wavefront_pt/shaders"):
-        pytest.skip("/root/reference is not present on this box; the committed extraction is used as is")
-    fresh = str(tmp_path / "fresh.json")
-    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "extract_reference_literals.py"), "/root/reference", fresh],
-                   check=True, stdout=subprocess.DEVNULL)
-    with open(fresh) as f:
-        assert json.load(f) == json.load(open(GOLD)), "reference_literals.json is stale: re-run the extractor and commit"
 
 
 @pytest.mark.parametrize("path,prefix", [(("oracle", "orc_math.h"), "orc_"), (("wavefront_path_tracer_amd", "csrc", "wfpt_device_math.h"), "")])
