@@ -197,7 +197,7 @@ enum {
                                         is the default in both RNG modes since the end of round 5 (rounds 4-5 binned contexts of at
                                         least 3/4 Mpixel in WFPT_RNG_PIXEL by default); the flag is accepted and wins over
                                         WFPT_FLAG_BINNING. */
-    WFPT_FLAG_BINNING = 1u << 8      /* WFPT_RNG_PIXEL, scenes in LDS: the class-binned loop -- every segment's hits stored sorted by cost
+    WFPT_FLAG_BINNING = 1u << 8,     /* WFPT_RNG_PIXEL, scenes in LDS: the class-binned loop -- every segment's hits stored sorted by cost
                                         class (the dominant primitive | lambertian | metal | dielectric), a work item = 512 hits of ONE
                                         class: 32.8 instead of 29.0 of 64 lanes per vector instruction, and level with the thread-ordered
                                         loop end to end at 1920x1080 (behind it on smaller slabs), hence opt-in. Same images bit for bit. With
@@ -207,6 +207,10 @@ enum {
                                         flag per ray, a rank table per wavefront -- measured it 5.8 % slower than the thread-ordered loop
                                         and round 5 removed it; so was the two-chain experiment, WFPT_FLAG_TWO_CHAINS, bit 9:
                                         profiles/r04_rejected_experiments.txt.) */
+    /* bit 9 is retired (WFPT_FLAG_TWO_CHAINS, above) and stays unused */
+    WFPT_FLAG_AOV = 1u << 10         /* first-hit feature buffers (AOVs) for denoisers, see "AOVs" below: every sample wfpt_render* renders
+                                        also traces its primary ray once more (aov_kernel) and adds the first hit's albedo, normal and
+                                        depth to per-pixel sums. Without the flag nothing is allocated or launched. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -402,6 +406,49 @@ float wfpt_progress(const wfpt_ctx *ctx, uint32_t spp); /* PathTracer::progress 
 int wfpt_render_sample_timed(wfpt_ctx *ctx, float *stage_ms, uint32_t *stage_launches);
 /* n_samples with the same batching as wfpt_render, timed per launch the same way. */
 int wfpt_render_timed(wfpt_ctx *ctx, uint32_t n_samples, float *stage_ms, uint32_t *stage_launches);
+
+/* ------------------------------------------------------------------ AOVs (WFPT_FLAG_AOV): first-hit feature buffers
+ * On a context created with WFPT_FLAG_AOV every sample rendered by wfpt_render, wfpt_render_sample, wfpt_render_timed and
+ * wfpt_render_sample_timed -- whatever the loop (fused, stage kernels, split shade, binned, refill), primitive kind, RNG mode or
+ * sharding -- also adds to per-pixel AOV sums. Sample k's primary ray is exactly the ray its beauty pass traces (same primary_ray,
+ * frame number, sample_number and true-size padding), traced with the same traversal the first extend would use, so t and the
+ * primitive are the first extend's, bit for bit. Per sample and pixel:
+ *   hit:  albedo = the material albedo (rgb) of the primitive hit; normal = the normal shade scatters about (spheres:
+ *         normalize3(p - centre), p = o + t d as shade computes it; triangles: the stored normalize(cross(e1, e2))); depth = t (primary
+ *         directions are unit length, so t is the distance); hits += 1.
+ *   miss: albedo = miss_kernel's sky colour for the direction (a = 0.5 (dy + 1), (1 - a) * 1 + a * (0.5, 0.7, 1.0)); normal = 0.
+ * Sums are added in ascending sample order, so every batch size and loop kind gives the same bits. Read-back resolves them with one
+ * IEEE f32 division each; n = wfpt_accumulated_samples:
+ *   WFPT_AOV_ALBEDO       sum / n                                3 floats per pixel
+ *   WFPT_AOV_NORMAL       sum / n (not renormalised)             3 floats per pixel
+ *   WFPT_AOV_DEPTH        sum of t / hits, 0 where hits == 0     1 float per pixel
+ *   WFPT_AOV_COVERAGE     hits / n                               1 float per pixel
+ *   WFPT_AOV_PRIM_ID      primitive of the first sample since the last reset, 0xffffffff on a miss    1 u32 per pixel
+ *   WFPT_AOV_MATERIAL_ID  that sample's material_idx, 0xffffffff on a miss                           1 u32 per pixel
+ * With n == 0 the float AOVs read 0 and the ids 0xffffffff. Pixels are row-major like wfpt_read_accumulated; a sharded context holds
+ * its own bands. Whatever zeroes `accumulated` (wfpt_reset_accumulated, wfpt_reset_progress, a camera / size / scene change) zeroes the
+ * sums too. Out of scope: the stage API (wfpt_kernel_run), wfpt_render_chunked*, a gather of AOVs, and specular chains (only the first
+ * hit counts, as stored, for metal and dielectric too). On a context without the flag, or with an unknown `which`, these functions
+ * return WFPT_ERR_INVALID_ARGUMENT. */
+typedef enum wfpt_aov {
+    WFPT_AOV_ALBEDO = 0,
+    WFPT_AOV_NORMAL = 1,
+    WFPT_AOV_DEPTH = 2,
+    WFPT_AOV_COVERAGE = 3,
+    WFPT_AOV_PRIM_ID = 4,
+    WFPT_AOV_MATERIAL_ID = 5,
+    WFPT_AOV_COUNT = 6
+} wfpt_aov;
+/* components per pixel of an AOV (3 or 1), 0 for an unknown one */
+int wfpt_aov_channels(int which);
+/* the resolved AOV, wfpt_aov_channels(which) * n_pixels elements of 4 bytes (float, or uint32_t for the ids); n_elems may be less (blocking) */
+int wfpt_read_aov(wfpt_ctx *ctx, int which, void *out, size_t n_elems);
+/* the same values resolved on the device (aov_resolve_kernel, the same bits as wfpt_read_aov) into a caller's device buffer of n_bytes
+ * (at most the whole AOV); ordered on the context's stream, returns when they are written */
+int wfpt_copy_aov_to_device(wfpt_ctx *ctx, int which, void *device_ptr, size_t n_bytes);
+/* time of the AOV launches of every timed render since wfpt_create (hipEvent pairs, not part of stage_ms) and their count; either
+ * pointer may be NULL */
+int wfpt_aov_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

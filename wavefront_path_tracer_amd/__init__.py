@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -33,7 +33,12 @@ SPF = 1   # wavefront_common/src/parameters.rs:5
 RNG_DISPATCH, RNG_PIXEL = 0, 1
 LOOP_KINDS = ("stages", "fused", "fused_binned", "refill")  # wfpt_loop_kind
 FLAG_SPLIT_SHADE, FLAG_NO_GRAPH, FLAG_UNFUSED, FLAG_BINARY_BVH, FLAG_NO_REFILL, FLAG_NO_LDS_SCENE, FLAG_EXACT_TRAVERSAL, FLAG_NO_BINNING, FLAG_BINNING = 1, 2, 4, 8, 16, 32, 64, 128, 256
+FLAG_AOV = 1 << 10  # first-hit AOVs (include/wfpt.h "AOVs"); bit 9 is the retired WFPT_FLAG_TWO_CHAINS
 INACTIVE_PIXEL = 0xFFFFFFFF
+# wfpt_aov: name -> (value, channels, numpy dtype of the resolved values)
+AOV_ALBEDO, AOV_NORMAL, AOV_DEPTH, AOV_COVERAGE, AOV_PRIM_ID, AOV_MATERIAL_ID = 0, 1, 2, 3, 4, 5
+AOVS = {"albedo": (AOV_ALBEDO, 3, "<f4"), "normal": (AOV_NORMAL, 3, "<f4"), "depth": (AOV_DEPTH, 1, "<f4"),
+        "coverage": (AOV_COVERAGE, 1, "<f4"), "prim_id": (AOV_PRIM_ID, 1, "<u4"), "material_id": (AOV_MATERIAL_ID, 1, "<u4")}
 # kernel.rs:32 loads shaders/{name}.wgsl; these are the stage names (path_tracer.rs:162,167,175,180,185)
 STAGES = {"generate_rays": 0, "extend": 1, "shade": 2, "miss_kernel": 3, "accumulate": 4,
           "shade_lambertian": 5, "shade_metal": 6, "shade_dielectric": 7, "scan": 8,
@@ -274,6 +279,10 @@ def lib():
         "wfpt_debug_read_stamps": (i32, [vp, vp, i32]),
         "wfpt_debug_read_stamps_ex": (i32, [vp, i32, vp, i32]),
         "wfpt_debug_bvh4": (i32, [vp, u32, vp]),
+        "wfpt_aov_channels": (i32, [i32]),
+        "wfpt_read_aov": (i32, [vp, i32, vp, sz]),
+        "wfpt_copy_aov_to_device": (i32, [vp, i32, vp, sz]),
+        "wfpt_aov_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -863,6 +872,45 @@ class PathTracer:
 
     def synchronize(self):
         self._check(lib().wfpt_synchronize(self.handle))
+
+    # ---- first-hit AOVs (contexts created with FLAG_AOV)
+    def _aov_shape(self, name):
+        if name not in AOVS:
+            raise ValueError(f"unknown AOV {name!r}: one of {sorted(AOVS)}")
+        which, ch, dtype = AOVS[name]
+        rows = self.n_pixels // self.width
+        return which, ((rows, self.width, 3) if ch == 3 else (rows, self.width)), dtype
+
+    def aov(self, name):
+        """The resolved AOV `name` (see AOVS) as (h, w, 3) or (h, w): float32, uint32 for the ids. A sharded context holds its own bands."""
+        which, shape, dtype = self._aov_shape(name)
+        a = np.zeros(shape, dtype)
+        self._check(lib().wfpt_read_aov(self.handle, which, _p(a), a.size))
+        return a
+
+    def aov_to_tensor(self, name, tensor):
+        """Writes AOV `name` into a caller's contiguous device tensor (torch float32 or int32 / uint32 for the ids, as many elements as
+        aov(name) has) on the context's device, resolved by the GPU (the same bits as aov(name)). Returns the tensor."""
+        which, shape, dtype = self._aov_shape(name)
+        n = int(np.prod(shape))
+        want = ("float32",) if dtype == "<f4" else ("int32", "uint32")
+        dt = str(getattr(tensor, "dtype", "")).replace("torch.", "")
+        if dt not in want:
+            raise TypeError(f"aov_to_tensor({name!r}): tensor dtype {dt or type(tensor).__name__} is not {' or '.join(want)}")
+        if tensor.numel() != n:
+            raise ValueError(f"aov_to_tensor({name!r}): tensor has {tensor.numel()} elements, the AOV {n} {shape}")
+        if not tensor.is_contiguous():
+            raise ValueError(f"aov_to_tensor({name!r}): tensor is not contiguous")
+        if getattr(tensor, "device", None) is None or tensor.device.type != "cuda" or tensor.device.index != self._params.device:
+            raise ValueError(f"aov_to_tensor({name!r}): tensor must live on this context's device (cuda:{self._params.device})")
+        self._check(lib().wfpt_copy_aov_to_device(self.handle, which, C.c_void_p(tensor.data_ptr()), 4 * n))
+        return tensor
+
+    def aov_timing(self):
+        """(milliseconds, launches) of the AOV launches of every timed render since creation (apart from render_timed's stage times)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_aov_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     # ---- read-back
     def accumulated(self):

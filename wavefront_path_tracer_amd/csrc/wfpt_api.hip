@@ -93,6 +93,9 @@ struct wfpt_ctx {
     uint32_t bounce_blocks_per_cu = 1;
     bool fused = true;
     float *image = nullptr, *accumulated = nullptr;
+    float *aov_sums = nullptr;  // WFPT_FLAG_AOV: [kAovPlanes][pixel_capacity] first-hit sums (wfpt_kernels.h), null without the flag
+    double aov_ms = 0.0;        // AOV launches of the timed renders since wfpt_create (wfpt_aov_timing_ms)
+    uint32_t aov_launches = 0;
     Control *ctl = nullptr;
     CameraDev *camera = nullptr;
     wfpt_gpu_camera h_camera{};      // host copy (the conservative traversal's range check, wfpt_update_scene)
@@ -514,6 +517,27 @@ int enqueue_fused_chain(wfpt_ctx *c, Timed &timed, uint32_t nb, uint32_t first, 
     return WFPT_OK;
 }
 
+// The AOV launch's entry in an event record: not a wfpt_stage (WFPT_STAGE_COUNT and the stage_ms arrays callers size by it stay as they
+// are); wfpt_render_timed books it into wfpt_ctx::aov_ms.
+constexpr int kStageAov = WFPT_STAGE_COUNT;
+AovArgs aov_args(wfpt_ctx *c, uint32_t nb) {
+    AovArgs a{};
+    a.n = nb;
+    a.sums = c->aov_sums;
+    a.plane = c->pixel_capacity;
+    a.ctl = c->ctl;
+    a.camera = c->camera;
+    a.gx = c->tiles_x;
+    a.gy = c->tiles_y_local;
+    a.tile = c->tile;
+    a.scene = c->scene;
+    return a;
+}
+uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend's grid (the four-wide walk's spill area is sized for that)
+    const uint64_t items = (static_cast<uint64_t>(c->tiles_x) * c->tiles_y_local * 64u + kExtendThreads - 1) / kExtendThreads;
+    return static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu));
+}
+
 int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     size_t next_event = 0;
     auto timed = [&](int stage, auto &&launch) -> hipError_t {
@@ -538,6 +562,8 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     };
     c->cur = 0;
     const bool split = (c->p.flags & WFPT_FLAG_SPLIT_SHADE) != 0;
+    if (c->aov_sums) // first in the batch, serially on the stream: it sees the batch's first frame, before accumulate advances it
+        WFPT_HIP(c, timed(kStageAov, [&] { return launch_aov(aov_args(c, nb), aov_grid(c), c->stream); }));
     if (c->fused) {
         if (int r = enqueue_fused_chain(c, timed, nb, 0, c->stream); r != WFPT_OK) return r;
         WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] {
@@ -574,6 +600,12 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] {
                  return launch_accumulate(accumulate_args(c, c->n_pixels, true, nb), c->accumulate_grid, c->stream);
              }));
+    return WFPT_OK;
+}
+
+// whatever zeroes `accumulated` zeroes the AOV sums with it (include/wfpt.h "AOVs")
+int reset_aov(wfpt_ctx *c) {
+    if (c->aov_sums) WFPT_HIP(c, hipMemsetAsync(c->aov_sums, 0, sizeof(float) * kAovPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
     return WFPT_OK;
 }
 
@@ -947,6 +979,7 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
 
     int blocks_per_cu = 1;
     WFPT_HIP(c, extend_blocks_per_cu(c->scene, &blocks_per_cu));
+    if (c->p.flags & WFPT_FLAG_AOV) WFPT_HIP(c, aov_prepare(c->scene));
     c->blocks_per_cu = static_cast<uint32_t>(std::max(blocks_per_cu, 1));
     if (c->bin_capable && lds_scene) {
         int bb = 1;
@@ -1193,6 +1226,10 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         }
     }
     CREATE_HIP(hipMemsetAsync(c->accumulated, 0, sizeof(float) * c->acc_floats, c->stream));         // pt:60-65
+    if (params->flags & WFPT_FLAG_AOV) {
+        CREATE_HIP(dmalloc(&c->aov_sums, kAovPlanes * static_cast<size_t>(c->pixel_capacity)));
+        CREATE_HIP(hipMemsetAsync(c->aov_sums, 0, sizeof(float) * kAovPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
+    }
     CREATE_HIP(dmalloc(&c->ctl, kMaxBatch));
     CREATE_HIP(hipMemsetAsync(c->ctl, 0, sizeof(Control) * kMaxBatch, c->stream));
     CREATE_HIP(dmalloc(&c->camera, 1));
@@ -1268,6 +1305,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV); // AOVs of chunked renders are out of scope (include/wfpt.h): nothing to allocate
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1322,7 +1360,7 @@ void wfpt_destroy(wfpt_ctx *c) {
                     c->f_chunk_miss[0], c->f_chunk_miss[1], c->first_seg, c->f_cls[0], c->f_cls[1], c->first_seg_cls, c->plan, c->cls_table,
                     c->ray_mem[0], c->ray_mem[1], c->hit_mem, c->hit_rec, c->miss_mem, c->chunk_hits,
                     c->chunk_miss, c->chunk_hit_base, c->chunk_miss_base, c->mat_list, c->chunk_mat, c->image, c->accumulated, c->ctl,
-                    c->camera, c->d_stamps};
+                    c->camera, c->d_stamps, c->aov_sums};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1358,6 +1396,7 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
     std::memcpy(cam.view, view, sizeof cam.view);
     WFPT_HIP(c, hipMemcpy(c->camera, &cam, sizeof cam, hipMemcpyHostToDevice));       // pt:259-272
     WFPT_HIP(c, hipMemsetAsync(c->accumulated, 0, sizeof(float) * c->acc_floats, c->stream)); // pt:248-250
+    if (int r = reset_aov(c); r != WFPT_OK) return r;
     c->progress_frame = 0;      // RenderProgress::reset, pt:276
     c->accumulated_samples = 0;
     c->dev_frame_valid = false;
@@ -1438,13 +1477,14 @@ int wfpt_reset_accumulated(wfpt_ctx *c) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipMemsetAsync(c->accumulated, 0, sizeof(float) * 3 * static_cast<size_t>(c->pixel_capacity), c->stream));
-    return WFPT_OK;
+    return reset_aov(c);
 }
 
 int wfpt_reset_progress(wfpt_ctx *c) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipMemsetAsync(c->accumulated, 0, sizeof(float) * 3 * static_cast<size_t>(c->pixel_capacity), c->stream)); // pt:248-250
+    if (int r = reset_aov(c); r != WFPT_OK) return r;
     c->progress_frame = 0; // RenderProgress::reset, pt:276
     c->accumulated_samples = 0;
     c->dev_frame_valid = false;
@@ -1560,6 +1600,11 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
         for (const EventRec &e : ev) {
             float ms = 0.0f;
             WFPT_HIP(c, hipEventElapsedTime(&ms, e.start, e.stop));
+            if (e.stage == kStageAov) {
+                c->aov_ms += ms;
+                c->aov_launches += 1;
+                continue;
+            }
             stage_ms[e.stage] += ms;
             if (stage_launches) stage_launches[e.stage] += 1;
         }
@@ -1626,6 +1671,48 @@ int wfpt_copy_accumulated_to_device(wfpt_ctx *c, void *device_ptr, size_t n_byte
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipMemcpyAsync(device_ptr, c->accumulated, n_bytes, hipMemcpyDeviceToDevice, c->stream));
     WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    return WFPT_OK;
+}
+
+int wfpt_aov_channels(int which) { return which >= 0 ? static_cast<int>(aov_channels(static_cast<uint32_t>(which))) : 0; }
+
+static int check_aov(wfpt_ctx *c, int which, const void *p, const char *who) {
+    if (!c || !p) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (!c->aov_sums) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_AOV");
+    if (wfpt_aov_channels(which) == 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown AOV " + std::to_string(which));
+    return WFPT_OK;
+}
+
+int wfpt_read_aov(wfpt_ctx *c, int which, void *out, size_t n_elems) {
+    if (int r = check_aov(c, which, out, "wfpt_read_aov"); r != WFPT_OK) return r;
+    const size_t ch = static_cast<size_t>(wfpt_aov_channels(which));
+    if (n_elems > ch * c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_aov: n_elems exceeds the AOV");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t plane = c->pixel_capacity;
+    std::vector<float> sums(kAovPlanes * plane);
+    WFPT_HIP(c, hipMemcpy(sums.data(), c->aov_sums, sizeof(float) * sums.size(), hipMemcpyDeviceToHost));
+    uint32_t *o = static_cast<uint32_t *>(out);
+    for (size_t k = 0; k < n_elems; ++k) o[k] = aov_resolve_word(sums.data(), plane, static_cast<uint32_t>(which), k, c->accumulated_samples);
+    return WFPT_OK;
+}
+
+int wfpt_copy_aov_to_device(wfpt_ctx *c, int which, void *device_ptr, size_t n_bytes) {
+    if (int r = check_aov(c, which, device_ptr, "wfpt_copy_aov_to_device"); r != WFPT_OK) return r;
+    if (n_bytes > sizeof(float) * static_cast<size_t>(wfpt_aov_channels(which)) * c->n_pixels)
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_copy_aov_to_device: n_bytes exceeds the AOV");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, launch_aov_resolve(c->aov_sums, c->pixel_capacity, static_cast<uint32_t>(which), c->accumulated_samples,
+                                   static_cast<uint32_t *>(device_ptr), n_bytes / sizeof(float), c->stream));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    return WFPT_OK;
+}
+
+int wfpt_aov_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_aov_timing_ms: null context");
+    if (!c->aov_sums) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_aov_timing_ms: the context was created without WFPT_FLAG_AOV");
+    if (ms_total) *ms_total = static_cast<float>(c->aov_ms);
+    if (launches) *launches = c->aov_launches;
     return WFPT_OK;
 }
 

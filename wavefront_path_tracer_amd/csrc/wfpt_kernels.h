@@ -385,6 +385,56 @@ struct AccumulateArgs {
     uint32_t bookkeeping; // fused loop: fold the bounce table into totals, frame += 1
 };
 
+// ---- first-hit AOVs (WFPT_FLAG_AOV; include/wfpt.h "AOVs"). The per-pixel sums are kAovPlanes planes of `plane` elements (the context's
+// pixel capacity) behind one base pointer, indexed by the pixel's slot in this context's slab. All zero = nothing accumulated (the reset state).
+// The id planes hold 0 until the first sample since the reset has run, then primitive / material_idx + 1 for a hit, kAovMissWord for a miss.
+enum : uint32_t {
+    kAovAlbedo = 0,   // 3 planes: sum of the first hit's albedo (rgb), or of the sky colour on a miss
+    kAovNormal = 3,   // 3 planes: sum of the first hit's normal (xyz)
+    kAovDepth = 6,    // sum of t over the hits
+    kAovHits = 7,     // u32: samples that hit
+    kAovPrim = 8,     // u32: see above
+    kAovMaterial = 9, // u32
+    kAovPlanes = 10
+};
+constexpr uint32_t kAovMissWord = 0xffffffffu;
+
+struct AovArgs {
+    uint32_t n;             // samples of this batch: frames ctl->frame.frame + 0 .. n - 1, added in that order
+    float *sums;
+    Stride32 plane;
+    const Control *ctl;     // ctl->frame: the batch's first frame (read on the device: graph replays freeze arguments)
+    const CameraDev *camera;
+    uint32_t gx, gy;        // tiles of this context (gy counts this rank's bands)
+    Tiling tile;
+    SceneDev scene;
+};
+
+// Resolved element k of AOV `which` (k < channels * pixels) from the sums, n = samples accumulated. Compiled for the host
+// (wfpt_read_aov) and the device (aov_resolve_kernel) from this one definition: the same IEEE f32 operations, the same bits.
+__host__ __device__ inline uint32_t aov_resolve_word(const float *sums, size_t plane, uint32_t which, size_t k, uint32_t n) {
+    auto as_u32 = [](float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; };
+    auto word = [&](uint32_t p, size_t px) { return as_u32(sums[p * plane + px]); };
+    const float nf = static_cast<float>(n);
+    switch (which) {
+    case WFPT_AOV_ALBEDO:
+    case WFPT_AOV_NORMAL: {
+        const uint32_t p = (which == WFPT_AOV_ALBEDO ? kAovAlbedo : kAovNormal) + static_cast<uint32_t>(k % 3u);
+        return n ? as_u32(sums[p * plane + k / 3u] / nf) : 0u;
+    }
+    case WFPT_AOV_DEPTH: {
+        const uint32_t hits = word(kAovHits, k);
+        return hits ? as_u32(sums[kAovDepth * plane + k] / static_cast<float>(hits)) : 0u;
+    }
+    case WFPT_AOV_COVERAGE: return n ? as_u32(static_cast<float>(word(kAovHits, k)) / nf) : 0u;
+    default: { // ids
+        const uint32_t w = word(which == WFPT_AOV_PRIM_ID ? kAovPrim : kAovMaterial, k);
+        return (w == 0u || w == kAovMissWord) ? 0xffffffffu : w - 1u;
+    }
+    }
+}
+__host__ __device__ inline uint32_t aov_channels(uint32_t which) { return which < 2u ? 3u : which < WFPT_AOV_COUNT ? 1u : 0u; }
+
 hipError_t launch_generate(const GenerateArgs &a, hipStream_t s);
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per sample
@@ -409,6 +459,12 @@ hipError_t launch_band_scatter(float *frame, const float *slab, size_t n_valid, 
 // AoS <-> SoA converters for the read-back / injection paths
 hipError_t launch_rays_to_aos(const RayQueue &q, wfpt_ray *out, uint32_t n, hipStream_t s);
 hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t n, hipStream_t s);
+// AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
+// sized for it)
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s);
+uint32_t aov_lds_bytes(const SceneDev &scene);
+hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
+hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
 hipError_t launch_selftest_math(int op, const float *a, const float *b, float *out, size_t n, hipStream_t s);
 // Occupancy of the extend kernel for a given dynamic LDS size (workgroups per CU); also raises the
 // kernel's dynamic-LDS limit when the scene needs more than the default 64 KiB.

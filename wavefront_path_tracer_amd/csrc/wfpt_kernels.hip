@@ -2932,6 +2932,135 @@ __global__ void rays_from_aos_kernel(RayQueue q, const wfpt_ray *in, uint32_t n)
     q.pixel()[i] = r.pixel_idx;
 }
 
+// ================================================================================================
+// first-hit AOVs (WFPT_FLAG_AOV; include/wfpt.h "AOVs")
+// ================================================================================================
+// One thread per pixel slot in generate_rays' 8x8-tile order (a wave = one tile), persistent workgroups of kExtendThreads that stage the
+// scene in LDS as extend_kernel does. A thread walks the batch's samples in order: each sample's primary ray (primary_ray with that
+// sample's frame, the true-size rule of generate_rays: padding lanes trace nothing) is traced with extend_kernel's choice of walk -- so t
+// and the primitive are what the first extend reports -- and its albedo, normal and depth are added to the pixel's sums in registers.
+// Sample order per pixel, no atomics: the sums do not depend on the batch size or on anything else that runs beside this kernel.
+// (No min-waves launch bound: capped at 64 vector registers like extend_kernel, every variant spills 96-164 bytes to scratch; unbounded
+// it takes 86-110 and runs 4 waves per SIMD.)
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT>
+__global__ __launch_bounds__(kExtendThreads) void aov_kernel(AovArgs a) {
+    extern __shared__ float4 lds[];
+    constexpr uint32_t kGeomWords = PRIM == 0 ? 1u : 3u; // float4 per primitive
+    const uint32_t n_slots = a.gx * a.gy * 64u;
+    const uint32_t n_items = (n_slots + kExtendThreads - 1u) / kExtendThreads;
+    if (blockIdx.x >= n_items) return; // nothing to do: skip the LDS staging too
+    float4 *s_nodes = lds;
+    float4 *s_geom = lds + (LDS_SCENE ? 2u * a.scene.n_nodes : 0u);
+    const uint32_t parent_words = LDS_SCENE ? ((a.scene.n_nodes / 2u + 1u) + 7u) / 8u : 0u; // uint4 words of 8 u16 entries
+    const uint32_t geom_words = LDS_SCENE ? kGeomWords * a.scene.n_spheres : 0u;
+    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_geom + geom_words);
+    uint32_t *s_stack = reinterpret_cast<uint32_t *>(s_geom + geom_words + parent_words); // HBM-resident scenes: the walk's stack columns
+    const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
+    if (LDS_SCENE) {
+        const float4 *g_staged = EXACT ? g_nodes : a.scene.nodes_ch;
+        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];
+        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_geom[i] = a.scene.prim_geom[i];
+        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);
+        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);
+        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];
+        __syncthreads();
+    }
+    const float4 *geom = LDS_SCENE ? s_geom : a.scene.prim_geom;
+    wfpt_frame_buffer fb0 = a.ctl->frame; // the batch's first frame (accumulate advances it after the batch)
+    fb0.width = uniform(fb0.width); fb0.height = uniform(fb0.height); fb0.frame = uniform(fb0.frame); fb0.sample_number = uniform(fb0.sample_number);
+    const size_t plane = a.plane;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t idx = item * kExtendThreads + threadIdx.x;
+        const uint32_t workgroup_index = idx >> 6, local_index = idx & 63u; // gr:42-57, as generate_rays_kernel
+        const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
+        const uint32_t id_x = wx * 8u + (local_index & 7u);
+        const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
+        if (idx >= n_slots || id_x >= fb0.width || id_y >= fb0.height) continue; // padding lane of a partial tile
+        const uint32_t px = local_pixel(id_x + id_y * fb0.width, fb0.width, a.tile);
+        float alb_r = a.sums[kAovAlbedo * plane + px], alb_g = a.sums[(kAovAlbedo + 1u) * plane + px], alb_b = a.sums[(kAovAlbedo + 2u) * plane + px];
+        float nrm_x = a.sums[kAovNormal * plane + px], nrm_y = a.sums[(kAovNormal + 1u) * plane + px], nrm_z = a.sums[(kAovNormal + 2u) * plane + px];
+        float depth = a.sums[kAovDepth * plane + px];
+        uint32_t *words = reinterpret_cast<uint32_t *>(a.sums);
+        uint32_t hits = words[kAovHits * plane + px], prim_w = words[kAovPrim * plane + px], mat_w = words[kAovMaterial * plane + px];
+        for (uint32_t smp = 0; smp < a.n; ++smp) {
+            wfpt_frame_buffer fb = fb0;
+            fb.frame += smp;
+            const PrimaryRay r = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
+            float t = 0.0f;
+            uint32_t prim = 0;
+            bool hit;
+            if (LDS_SCENE && EXACT) { // the selection of extend_kernel
+                hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_geom, s_parent, nullptr, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                                                a.scene.n_nodes, t, prim);
+            } else if (LDS_SCENE) {
+                prim = kHandOver;
+                hit = false;
+                if (!far_origin(a.scene, r.ox, r.oy, r.oz)) {
+#if WFPT_STAMPS
+                    uint32_t dbg[3] = {0, 0, 0};
+#endif
+                    hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                                                        a.scene.n_nodes, t, prim WFPT_DBG_ARG);
+                }
+                if (prim == kHandOver)
+                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, a.scene.n_nodes,
+                                                                   t, prim);
+            } else if (!EXACT && a.scene.nodes4) {
+                Stack4 st;
+                st.init(WFPT_LDS_BYTES(lds, s_stack), a.scene.stack_spill, a.scene.spill_stride);
+                prim = kHandOver;
+                hit = false;
+                if (!far_origin(a.scene, r.ox, r.oy, r.oz))
+                    hit = trace_ray4<PRIM>(a.scene.nodes4, a.scene.prim_geom, st, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, a.scene.n_nodes,
+                                           a.scene.root_leaf != 0, t, prim);
+                if (prim == kHandOver)
+                    hit = retrace_reference<Trail, PRIM, uint32_t>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, r.ox, r.oy, r.oz, r.dx, r.dy,
+                                                                   r.dz, a.scene.n_nodes, t, prim);
+            } else {
+                hit = trace_ray<Trail, PRIM, uint32_t, kStackDepth, EXACT>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32,
+                                                                            s_stack + threadIdx.x, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
+                                                                            a.scene.n_nodes, t, prim);
+            }
+            if (hit) {
+                const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u];
+                // the normal scatter() uses: spheres normalize3(p - centre) with p = o + t d (extend's path record, sh:91), triangles the stored one
+                float3_ n = {rec0.x, rec0.y, rec0.z};
+                if (PRIM == 0) n = normalize3({(r.ox + t * r.dx) - rec0.x, (r.oy + t * r.dy) - rec0.y, (r.oz + t * r.dz) - rec0.z});
+                alb_r += rec1.x; alb_g += rec1.y; alb_b += rec1.z;
+                nrm_x += n.x; nrm_y += n.y; nrm_z += n.z;
+                depth += t;
+                hits += 1u;
+                if (prim_w == 0u) {
+                    prim_w = prim + 1u;
+                    mat_w = 1u + (PRIM == 0 ? a.scene.spheres[prim].material_idx : __float_as_uint(geom[3u * prim].w));
+                }
+            } else { // miss_kernel's sky colour (mk:32-33)
+                const float sky = 0.5f * (r.dy + 1.0f);
+                const float om = 1.0f - sky;
+                alb_r += om * 1.0f + sky * 0.5f;
+                alb_g += om * 1.0f + sky * 0.7f;
+                alb_b += om * 1.0f + sky * 1.0f;
+                nrm_x += 0.0f; nrm_y += 0.0f; nrm_z += 0.0f; // a miss adds its zero normal like any other sample
+                if (prim_w == 0u) {
+                    prim_w = kAovMissWord;
+                    mat_w = kAovMissWord;
+                }
+            }
+        }
+        a.sums[kAovAlbedo * plane + px] = alb_r; a.sums[(kAovAlbedo + 1u) * plane + px] = alb_g; a.sums[(kAovAlbedo + 2u) * plane + px] = alb_b;
+        a.sums[kAovNormal * plane + px] = nrm_x; a.sums[(kAovNormal + 1u) * plane + px] = nrm_y; a.sums[(kAovNormal + 2u) * plane + px] = nrm_z;
+        a.sums[kAovDepth * plane + px] = depth;
+        words[kAovHits * plane + px] = hits; words[kAovPrim * plane + px] = prim_w; words[kAovMaterial * plane + px] = mat_w;
+    }
+}
+
+// sums -> resolved AOV words (aov_resolve_word, shared with the host read-back)
+__global__ __launch_bounds__(256) void aov_resolve_kernel(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out,
+                                                          size_t n_words) {
+    for (size_t k = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; k < n_words; k += static_cast<size_t>(gridDim.x) * blockDim.x)
+        out[k] = aov_resolve_word(sums, plane, which, k, n_samples);
+}
+
 __global__ void selftest_math_kernel(int op, const float *a, const float *b, float *out, size_t n) {
     const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
     if (i >= n) return;
@@ -3195,6 +3324,50 @@ hipError_t launch_rays_to_aos(const RayQueue &q, wfpt_ray *out, uint32_t n, hipS
 hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(rays_from_aos_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, q, in, n);
+    return hipGetLastError();
+}
+
+namespace {
+using AovFn = void (*)(AovArgs);
+template <int PRIM, bool EXACT> AovFn aov_pick(bool lds_scene, bool deep) {
+    if (!lds_scene) return aov_kernel<unsigned long long, PRIM, false, EXACT>;
+    return deep ? aov_kernel<unsigned long long, PRIM, true, EXACT> : aov_kernel<uint32_t, PRIM, true, EXACT>;
+}
+AovFn aov_variant(const SceneDev &sc, bool exact) {
+    const bool lds = sc.lds_scene != 0, deep = sc.depth > 31u; // as extend_variant
+    if (sc.prim_kind == 0) return exact ? aov_pick<0, true>(lds, deep) : aov_pick<0, false>(lds, deep);
+    return exact ? aov_pick<1, true>(lds, deep) : aov_pick<1, false>(lds, deep);
+}
+} // namespace
+
+uint32_t aov_lds_bytes(const SceneDev &sc) {
+    if (!sc.lds_scene) return 4u * 2u * kStackDepth * kExtendThreads; // the binary walk's stack columns (the four-wide walk uses the first half)
+    const uint32_t parent_words = ((sc.n_nodes / 2u + 1u) + 7u) / 8u;
+    return 32u * sc.n_nodes + 16u * (sc.prim_kind == 0 ? 1u : 3u) * sc.n_spheres + 16u * parent_words;
+}
+
+hipError_t aov_prepare(const SceneDev &scene) {
+    const uint32_t bytes = aov_lds_bytes(scene);
+    if (bytes <= 64u * 1024u) return hipSuccess;
+    for (int exact = 0; exact < 2; ++exact) { // both box tests: the context may switch between them later (decide_exact)
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(aov_variant(scene, exact != 0)),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0 || a.n == 0 || a.gx * a.gy == 0) return hipSuccess;
+    hipLaunchKernelGGL(aov_variant(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s) {
+    if (n_words == 0) return hipSuccess;
+    const size_t blocks = (n_words + 255) / 256;
+    hipLaunchKernelGGL(aov_resolve_kernel, dim3(static_cast<uint32_t>(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, sums, plane, which,
+                       n_samples, out, n_words);
     return hipGetLastError();
 }
 
