@@ -208,9 +208,12 @@ enum {
                                         and round 5 removed it; so was the two-chain experiment, WFPT_FLAG_TWO_CHAINS, bit 9:
                                         profiles/r04_rejected_experiments.txt.) */
     /* bit 9 is retired (WFPT_FLAG_TWO_CHAINS, above) and stays unused */
-    WFPT_FLAG_AOV = 1u << 10         /* first-hit feature buffers (AOVs) for denoisers, see "AOVs" below: every sample wfpt_render* renders
+    WFPT_FLAG_AOV = 1u << 10,        /* first-hit feature buffers (AOVs) for denoisers, see "AOVs" below: every sample wfpt_render* renders
                                         also traces its primary ray once more (aov_kernel) and adds the first hit's albedo, normal and
                                         depth to per-pixel sums. Without the flag nothing is allocated or launched. */
+    WFPT_FLAG_DENOISE = 1u << 11     /* the on-device denoiser, see "Denoiser" below: implies WFPT_FLAG_AOV, and every rendered batch also adds
+                                        each sample's luminance and its square to per-pixel moments (accumulate_moments_kernel in place
+                                        of accumulate_kernel). Without the flag nothing is allocated or launched. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -449,6 +452,50 @@ int wfpt_copy_aov_to_device(wfpt_ctx *ctx, int which, void *device_ptr, size_t n
 /* time of the AOV launches of every timed render since wfpt_create (hipEvent pairs, not part of stage_ms) and their count; either
  * pointer may be NULL */
 int wfpt_aov_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
+
+/* ------------------------------------------------------------------ Denoiser (WFPT_FLAG_DENOISE): edge-avoiding a-trous wavelet filter
+ * A context created with WFPT_FLAG_DENOISE keeps the AOVs above (the flag implies WFPT_FLAG_AOV: wfpt_read_aov and wfpt_aov_timing_ms work
+ * on it) and two more per-pixel sums over the samples k that wfpt_render* adds to `accumulated`: S1 = sum of L_k and S2 = sum of L_k * L_k,
+ * L_k = (0.2126 r + 0.7152 g) + 0.0722 b of the value sample k adds, in ascending sample order (the same bits for every batch size and
+ * loop kind). They are reset with the AOV sums, and out of scope in the same places (stage API, wfpt_render_chunked*).
+ * wfpt_read_variance resolves them, n = wfpt_accumulated_samples, with one IEEE f32 division each in this order:
+ *   mu = S1 / n;  v = max(0, S2 / n - mu * mu) / n        the variance of the n-sample mean's luminance, 0 where n == 0
+ * wfpt_denoise filters the mean colour c = accumulated / n with the spatial part of SVGF (Schied et al. 2017) on Dammertz et al. 2010:
+ *   prepare     guides per pixel from the read-back values: the normalised normal, depth, albedo, the depth gradient (per axis the
+ *               smaller step to an existing neighbour) and v; for n < 4, v is the population variance of L(c) over the 7x7 window
+ *   pass i      (i < iterations) a 5x5 a-trous tap set at step 2^i, taps outside the image skipped; the weight of tap q for pixel p is
+ *               h(dx) h(dy) exp(-|L_p - L_q| / (sigma_luminance sqrt(g3(v)_p) + 1e-10) - |z_p - z_q| / (sigma_depth |grad z_p| 2^i |(dx, dy)| + 1e-3)
+ *                                 - |A_p - A_q|^2 / sigma_albedo^2) * max(0, dot(N_p, N_q))^sigma_normal
+ *               (the normal term is 1 where both normals are 0 and 0 where one is), h = (1, 4, 6, 4, 1) / 16, g3 = 3x3 binomial blur of
+ *               v; c' = sum w c_q / sum w, v' = sum w^2 v_q / (sum w)^2
+ * The result is the last pass's c, a mean colour (not a sum): 3 floats per pixel, stride 12, row-major. No atomics and a fixed order
+ * of every sum: repeated calls, every batch size and every loop kind give the same bits. A call reads the sums and writes only its own
+ * buffers (allocated on the first call): the next render continues as if it had not happened. With n == 0 the outputs are 0.
+ * WFPT_ERR_INVALID_ARGUMENT without the flag, for a bad parameter or too large a size; WFPT_ERR_UNSUPPORTED from the two denoise calls on
+ * a band-sharded context (tile_world > 1: the filter needs the other ranks' bands). */
+typedef struct wfpt_denoise_params {
+    uint32_t iterations;      /* a-trous passes, 0..8; 0 = c = accumulated / n unfiltered */
+    float sigma_luminance;    /* each sigma > 0 and finite */
+    float sigma_normal;
+    float sigma_depth;
+    float sigma_albedo;
+    uint32_t _reserved[3];    /* must be 0 */
+} wfpt_denoise_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_denoise_params) == 32 && offsetof(wfpt_denoise_params, sigma_luminance) == 4 &&
+                       offsetof(wfpt_denoise_params, sigma_normal) == 8 && offsetof(wfpt_denoise_params, sigma_depth) == 12 &&
+                       offsetof(wfpt_denoise_params, sigma_albedo) == 16 && offsetof(wfpt_denoise_params, _reserved) == 20,
+                   "wfpt_denoise_params: 32 bytes");
+/* iterations 5, sigma_luminance 4, sigma_normal 128, sigma_depth 1 (SVGF's), sigma_albedo 0.5 (tuned: DESIGN.md 9c); _reserved zeroed */
+void wfpt_denoise_params_default(wfpt_denoise_params *p);
+/* the denoised mean colour, 3 * n_pixels floats at most (blocking) */
+int wfpt_denoise(wfpt_ctx *ctx, const wfpt_denoise_params *p, float *rgb, size_t n_floats);
+/* the same bits written into a caller's device buffer of n_bytes (at most 12 * n_pixels); returns when they are written */
+int wfpt_denoise_to_device(wfpt_ctx *ctx, const wfpt_denoise_params *p, void *device_ptr, size_t n_bytes);
+/* the per-pixel variance v above, n_pixels floats at most (blocking); a sharded context holds its own bands */
+int wfpt_read_variance(wfpt_ctx *ctx, float *out, size_t n_elems);
+/* time of the last denoise call's launches (a hipEvent pair around them) and the number of calls since wfpt_create; either pointer may
+ * be NULL */
+int wfpt_denoise_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *calls);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

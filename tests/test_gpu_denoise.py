@@ -1,0 +1,241 @@
+"""The on-device denoiser (WFPT_FLAG_DENOISE, include/wfpt.h "Denoiser") on the GPU.
+
+The luminance moments are restated in numpy float32 from each sample's own image, in sample order, and compared bit for bit. The
+filter is compared with tests/denoise_ref.py, a restatement in the kernels' operation order fed with the library's read-backs.
+"""
+import numpy as np
+import pytest
+
+import denoise_ref as R
+from helpers import make_mesh_tracer, make_tracer
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+AOV_NAMES = ("albedo", "normal", "depth", "coverage", "prim_id", "material_id")
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def assert_bits(got, want, what):
+    g, w = bits(got), bits(np.asarray(want, got.dtype))
+    assert g.shape == w.shape, (what, g.shape, w.shape)
+    bad = g != w
+    if bad.ndim == 3:
+        bad = bad.any(axis=2)
+    assert not bad.any(), f"{what}: {int(bad.sum())} pixels differ, first at {np.argwhere(bad)[0]}"
+
+
+def moments_by_sample(pt, n):
+    """Renders n samples one at a time and restates S1, S2 from each sample's image; returns the expected variance (h, w)."""
+    s1 = np.zeros(pt.n_pixels, F)
+    s2 = np.zeros(pt.n_pixels, F)
+    for _ in range(n):
+        pt.render_sample()
+        L = R.luma(pt.image())
+        s1 = s1 + L
+        s2 = s2 + L * L
+    return R.variance_resolve(s1, s2, n).reshape(-1, pt.width)
+
+
+@pytest.mark.parametrize("rng_mode", [0, 1])
+def test_moments_match_the_samples_bit_for_bit(gpu, rng_mode):
+    W = gpu
+    pt = make_tracer(W, "shirley", 100, 60, rng_mode=rng_mode, max_wavefronts=6, batch=1, flags=W.FLAG_DENOISE)
+    want = moments_by_sample(pt, 6)
+    got = pt.variance()
+    assert_bits(got, want, f"variance, rng {rng_mode}")
+    assert got.max() > 0.0
+    pt.close()
+
+
+def test_moments_of_a_mesh_beyond_lds(gpu):
+    W = gpu
+    pt = make_mesh_tracer(W, 128, 96, 20000, edge_scale=5.0, max_wavefronts=3, batch=1, flags=W.FLAG_DENOISE)
+    assert pt.loop_kind == "refill"
+    want = moments_by_sample(pt, 3)
+    assert_bits(pt.variance(), want, "variance, mesh")
+    pt.close()
+
+
+def render(W, w, h, spp, **kw):
+    pt = make_tracer(W, "shirley", w, h, max_wavefronts=4, **kw)
+    pt.render(spp)
+    return pt
+
+
+def test_moments_and_denoise_are_the_same_for_every_loop_and_batch(gpu):
+    W = gpu
+    w, h, spp = 100, 60, 20  # partial tiles; batches of 16 leave a remainder
+    ref = render(W, w, h, spp, rng_mode=1, flags=W.FLAG_DENOISE)
+    ref_var, ref_dn = ref.variance(), ref.denoise()
+    assert_bits(ref.denoise(), ref_dn, "a repeated call")
+    ref.close()
+    for flag, batch in (("UNFUSED", 0), ("SPLIT_SHADE", 0), ("NO_GRAPH", 0), ("BINNING", 0), (None, 1), (None, 16), (None, 64)):
+        fl = W.FLAG_DENOISE | (getattr(W, "FLAG_" + flag) if flag else 0)
+        pt = render(W, w, h, spp, rng_mode=1, flags=fl, batch=batch)
+        assert_bits(pt.variance(), ref_var, f"variance, flag {flag} batch {batch}")
+        assert_bits(pt.denoise(), ref_dn, f"denoise, flag {flag} batch {batch}")
+        pt.close()
+
+
+def test_denoise_to_tensor_gives_the_same_bits(gpu):
+    torch = pytest.importorskip("torch")
+    W = gpu
+    pt = render(W, 100, 60, 5, flags=W.FLAG_DENOISE)
+    for it in (0, 3, 5):
+        host = pt.denoise(iterations=it)
+        t = torch.full(host.shape, -7.0, dtype=torch.float32, device="cuda:0")
+        pt.denoise_to_tensor(t, iterations=it)
+        assert np.array_equal(t.cpu().numpy().view(np.uint32), host.view(np.uint32)), it
+    with pytest.raises(TypeError):
+        pt.denoise_to_tensor(torch.zeros((60, 100, 3), dtype=torch.float64, device="cuda:0"))
+    with pytest.raises(ValueError):
+        pt.denoise_to_tensor(torch.zeros((60, 100), dtype=torch.float32, device="cuda:0"))
+    # a partial buffer: only its floats are written
+    L = W.lib()
+    t = torch.full((7,), -7.0, dtype=torch.float32, device="cuda:0")
+    p = pt._denoise_params({})
+    import ctypes as C
+    assert L.wfpt_denoise_to_device(pt.handle, C.byref(p), C.c_void_p(t.data_ptr()), 4 * 5) == 0
+    got = t.cpu().numpy()
+    assert np.array_equal(got[:5].view(np.uint32), pt.denoise().reshape(-1)[:5].view(np.uint32)) and (got[5:] == -7.0).all()
+    pt.close()
+
+
+def test_flag_changes_nothing_else(gpu):
+    """A flagged context's image and AOVs are an FLAG_AOV context's, and a denoise call changes nothing the next render reads."""
+    W = gpu
+    for flags in (0, W.FLAG_UNFUSED):
+        a = render(W, 120, 80, 4, flags=flags | W.FLAG_AOV)
+        d = render(W, 120, 80, 4, flags=flags | W.FLAG_DENOISE)
+        assert_bits(d.accumulated(), a.accumulated(), f"accumulated, flags {flags}")
+        assert np.array_equal(d.bounce_table(), a.bounce_table())
+        for k in AOV_NAMES:
+            assert_bits(d.aov(k), a.aov(k), f"{k}, flags {flags}")
+        d.denoise()
+        d.denoise(iterations=8)
+        a.render(4)
+        d.render(4)
+        assert_bits(d.accumulated(), a.accumulated(), f"accumulated after a denoise call, flags {flags}")
+        for k in AOV_NAMES:
+            assert_bits(d.aov(k), a.aov(k), f"{k} after a denoise call, flags {flags}")
+        a.close(); d.close()
+    # and the denoised result after it is that of a context that never denoised in between
+    x = render(W, 120, 80, 4, flags=W.FLAG_DENOISE)
+    y = render(W, 120, 80, 4, flags=W.FLAG_DENOISE)
+    x.denoise()
+    x.render(3); y.render(3)
+    assert_bits(x.variance(), y.variance(), "variance after a denoise call")
+    assert_bits(x.denoise(), y.denoise(), "denoise after a denoise call")
+    x.close(); y.close()
+
+
+def test_zero_iterations_is_accumulated_over_n(gpu):
+    W = gpu
+    pt = render(W, 100, 60, 7, flags=W.FLAG_DENOISE)
+    want = (pt.accumulated() / F(7)).astype(F).reshape(60, 100, 3)
+    assert_bits(pt.denoise(iterations=0), want, "iterations=0")
+    pt.close()
+
+
+def inputs_of(pt, n):
+    h, w = pt.height, pt.width
+    c = (pt.accumulated() / F(n)).astype(F).reshape(h, w, 3)
+    return c, pt.aov("albedo"), pt.aov("normal"), pt.aov("depth"), pt.variance()
+
+
+@pytest.mark.parametrize("n", [1, 2, 4, 64])
+def test_denoise_matches_the_restatement(gpu, n):
+    W = gpu
+    pt = render(W, 320, 180, n, flags=W.FLAG_DENOISE)
+    args = inputs_of(pt, n)
+    for it in (1, 5):
+        got = pt.denoise(iterations=it)
+        want = R.denoise(*args, n, iterations=it)
+        np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-6, err_msg=f"n {n} iterations {it}")
+    pt.close()
+
+
+def rel_mse(x, ref):
+    return float(np.mean((x.astype(np.float64) - ref) ** 2 / (ref.astype(np.float64) ** 2 + 1e-2)))
+
+
+def test_denoised_8spp_is_closer_to_the_converged_image(gpu):
+    """relMSE against a 1024-spp render of the same view: the 8-spp denoise against the 8-spp mean it starts from. Measured on an
+    MI355X: 0.531 of the noisy relMSE at the default parameters, hence the bound 0.6."""
+    W = gpu
+    w, h = 320, 180
+    ref_pt = make_tracer(W, "shirley", w, h, max_wavefronts=8)
+    ref_pt.render(1024)
+    ref = (ref_pt.accumulated() / F(1024)).reshape(h, w, 3)
+    ref_pt.close()
+    pt = make_tracer(W, "shirley", w, h, max_wavefronts=8, flags=W.FLAG_DENOISE)
+    pt.render(8)
+    noisy = rel_mse(pt.denoise(iterations=0), ref)
+    denoised = rel_mse(pt.denoise(), ref)
+    print(f"relMSE 8 spp: noisy {noisy:.5f}, denoised {denoised:.5f}, ratio {denoised / noisy:.3f}")
+    assert denoised <= 0.6 * noisy, (noisy, denoised)
+    pt.close()
+
+
+def test_errors_and_edge_cases(gpu):
+    import ctypes as C
+    W = gpu
+    L = W.lib()
+    buf = np.zeros(64 * 48 * 3, "<f4")
+    # n == 0: zeros
+    pt = make_tracer(W, "shirley", 64, 48, max_wavefronts=3, flags=W.FLAG_DENOISE)
+    assert not bits(pt.variance()).any() and not bits(pt.denoise()).any()
+    pt.render(2)
+    assert pt.variance().max() > 0 and pt.denoise().max() > 0
+    L.wfpt_reset_progress(pt.handle)
+    assert not bits(pt.variance()).any() and not bits(pt.denoise()).any()
+    pt.render(1)
+    ms, calls = pt.denoise_timing()
+    pt.denoise()
+    ms, calls2 = pt.denoise_timing()
+    assert calls2 == calls + 1 and ms > 0.0
+    # out-of-range parameters
+    for bad in ({"iterations": 9}, {"sigma_luminance": 0.0}, {"sigma_normal": -1.0}, {"sigma_depth": float("nan")},
+                {"sigma_albedo": float("inf")}):
+        with pytest.raises(W.WfptError):
+            pt.denoise(**bad)
+    with pytest.raises(TypeError):
+        pt.denoise(sigma_colour=1.0)
+    p = pt._denoise_params({})
+    p._reserved[1] = 1
+    assert L.wfpt_denoise(pt.handle, C.byref(p), W._p(buf), 3) == -1
+    p = pt._denoise_params({})
+    assert L.wfpt_denoise(pt.handle, C.byref(p), W._p(buf), 64 * 48 * 3 + 1) == -1
+    assert L.wfpt_read_variance(pt.handle, W._p(buf), 64 * 48 + 1) == -1
+    assert L.wfpt_denoise_to_device(pt.handle, C.byref(p), W._p(buf), 4 * (64 * 48 * 3 + 1)) == -1
+    assert L.wfpt_denoise(pt.handle, None, W._p(buf), 3) == -1
+    pt.close()
+    # no flag (FLAG_AOV alone is not enough)
+    plain = make_tracer(W, "shirley", 64, 48, max_wavefronts=3, flags=W.FLAG_AOV)
+    plain.render(1)
+    with pytest.raises(W.WfptError, match="WFPT_FLAG_DENOISE"):
+        plain.denoise()
+    with pytest.raises(W.WfptError, match="WFPT_FLAG_DENOISE"):
+        plain.variance()
+    assert L.wfpt_denoise_timing_ms(plain.handle, None, None) == -1
+    plain.close()
+    # band-sharded: the moments are there, the filter is not
+    sh = make_tracer(W, "shirley", 64, 48, max_wavefronts=3, flags=W.FLAG_DENOISE, tile_rank=1, tile_world=2)
+    sh.render(2)
+    assert sh.variance().shape == (sh.n_pixels // 64, 64)
+    p = sh._denoise_params({})
+    assert L.wfpt_denoise(sh.handle, C.byref(p), W._p(buf), 3) == -4
+    assert L.wfpt_denoise_to_device(sh.handle, C.byref(p), W._p(buf), 12) == -4
+    sh.close()
+    # the flag implies the AOVs
+    d = make_tracer(W, "shirley", 64, 48, max_wavefronts=3, flags=W.FLAG_DENOISE)
+    d.render(1)
+    assert d.aov("coverage").max() > 0
+    d.render_timed(2)
+    assert d.aov_timing()[1] >= 1
+    d.close()

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -34,6 +34,9 @@ RNG_DISPATCH, RNG_PIXEL = 0, 1
 LOOP_KINDS = ("stages", "fused", "fused_binned", "refill")  # wfpt_loop_kind
 FLAG_SPLIT_SHADE, FLAG_NO_GRAPH, FLAG_UNFUSED, FLAG_BINARY_BVH, FLAG_NO_REFILL, FLAG_NO_LDS_SCENE, FLAG_EXACT_TRAVERSAL, FLAG_NO_BINNING, FLAG_BINNING = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_AOV = 1 << 10  # first-hit AOVs (include/wfpt.h "AOVs"); bit 9 is the retired WFPT_FLAG_TWO_CHAINS
+FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
+# wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
 INACTIVE_PIXEL = 0xFFFFFFFF
 # wfpt_aov: name -> (value, channels, numpy dtype of the resolved values)
 AOV_ALBEDO, AOV_NORMAL, AOV_DEPTH, AOV_COVERAGE, AOV_PRIM_ID, AOV_MATERIAL_ID = 0, 1, 2, 3, 4, 5
@@ -76,6 +79,11 @@ class _Params(C.Structure):
                 ("max_wavefronts", C.c_uint32), ("miss_floor", C.c_uint32), ("rng_mode", C.c_uint32),
                 ("flags", C.c_uint32), ("tile_rank", C.c_uint32), ("tile_world", C.c_uint32),
                 ("device", C.c_int32), ("batch", C.c_uint32)]
+
+
+class _DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("_reserved", C.c_uint32 * 3)]
 
 
 class GPUFrameBuffer(C.Structure):
@@ -283,6 +291,11 @@ def lib():
         "wfpt_read_aov": (i32, [vp, i32, vp, sz]),
         "wfpt_copy_aov_to_device": (i32, [vp, i32, vp, sz]),
         "wfpt_aov_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_denoise_params_default": (None, [C.POINTER(_DenoiseParams)]),
+        "wfpt_denoise": (i32, [vp, C.POINTER(_DenoiseParams), vp, sz]),
+        "wfpt_denoise_to_device": (i32, [vp, C.POINTER(_DenoiseParams), vp, sz]),
+        "wfpt_read_variance": (i32, [vp, vp, sz]),
+        "wfpt_denoise_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -910,6 +923,51 @@ class PathTracer:
         """(milliseconds, launches) of the AOV launches of every timed render since creation (apart from render_timed's stage times)."""
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_aov_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    # ---- denoiser (contexts created with FLAG_DENOISE)
+    def variance(self):
+        """(h, w) float32: the variance of each pixel's n-sample mean luminance, from the per-pixel moments (0 before any sample)."""
+        a = np.zeros((self.n_pixels // self.width, self.width), "<f4")
+        self._check(lib().wfpt_read_variance(self.handle, _p(a), a.size))
+        return a
+
+    @staticmethod
+    def _denoise_params(params):
+        unknown = set(params) - set(DENOISE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown denoise parameter(s) {sorted(unknown)}: one of {sorted(DENOISE_DEFAULTS)}")
+        v = {**DENOISE_DEFAULTS, **params}
+        return _DenoiseParams(int(v["iterations"]), v["sigma_luminance"], v["sigma_normal"], v["sigma_depth"], v["sigma_albedo"])
+
+    def denoise(self, **params):
+        """(h, w, 3) float32: the denoised mean colour (not a sum). Parameters as DENOISE_DEFAULTS; iterations=0 gives accumulated / n."""
+        p = self._denoise_params(params)
+        a = np.zeros((self.n_pixels // self.width, self.width, 3), "<f4")
+        self._check(lib().wfpt_denoise(self.handle, C.byref(p), _p(a), a.size))
+        return a
+
+    def denoise_to_tensor(self, tensor, **params):
+        """Writes denoise(**params) into a caller's contiguous float32 device tensor of h * w * 3 elements on the context's device (the
+        same bits as denoise()). Returns the tensor."""
+        p = self._denoise_params(params)
+        n = self.n_pixels * 3
+        dt = str(getattr(tensor, "dtype", "")).replace("torch.", "")
+        if dt != "float32":
+            raise TypeError(f"denoise_to_tensor: tensor dtype {dt or type(tensor).__name__} is not float32")
+        if tensor.numel() != n:
+            raise ValueError(f"denoise_to_tensor: tensor has {tensor.numel()} elements, the image {n}")
+        if not tensor.is_contiguous():
+            raise ValueError("denoise_to_tensor: tensor is not contiguous")
+        if getattr(tensor, "device", None) is None or tensor.device.type != "cuda" or tensor.device.index != self._params.device:
+            raise ValueError(f"denoise_to_tensor: tensor must live on this context's device (cuda:{self._params.device})")
+        self._check(lib().wfpt_denoise_to_device(self.handle, C.byref(p), C.c_void_p(tensor.data_ptr()), 4 * n))
+        return tensor
+
+    def denoise_timing(self):
+        """(milliseconds of the last denoise call's launches, denoise calls since creation)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_denoise_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     # ---- read-back

@@ -96,6 +96,13 @@ struct wfpt_ctx {
     float *aov_sums = nullptr;  // WFPT_FLAG_AOV: [kAovPlanes][pixel_capacity] first-hit sums (wfpt_kernels.h), null without the flag
     double aov_ms = 0.0;        // AOV launches of the timed renders since wfpt_create (wfpt_aov_timing_ms)
     uint32_t aov_launches = 0;
+    float *moments = nullptr;   // WFPT_FLAG_DENOISE: [kMomentPlanes][pixel_capacity] luminance moments, null without the flag
+    // the denoiser's buffers, [pixel_capacity] each, allocated by the first wfpt_denoise*: guides (normal, depth), (albedo, |grad z|) and
+    // the passes' ping-pong (c, v)
+    float4 *dn_nz = nullptr, *dn_ag = nullptr, *dn_cv[2] = {nullptr, nullptr};
+    hipEvent_t dn_ev[2] = {nullptr, nullptr};
+    float dn_ms = 0.0f;         // the last denoise call's launches (wfpt_denoise_timing_ms)
+    uint32_t dn_calls = 0;
     Control *ctl = nullptr;
     CameraDev *camera = nullptr;
     wfpt_gpu_camera h_camera{};      // host copy (the conservative traversal's range check, wfpt_update_scene)
@@ -538,6 +545,13 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
     return static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu));
 }
 
+// The batch's accumulate launch: with the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way)
+hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
+    const AccumulateArgs a = accumulate_args(c, c->n_pixels, true, nb);
+    if (c->moments) return launch_accumulate_moments(a, c->moments, c->pixel_capacity, c->accumulate_grid, c->stream);
+    return launch_accumulate(a, c->accumulate_grid, c->stream);
+}
+
 int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     size_t next_event = 0;
     auto timed = [&](int stage, auto &&launch) -> hipError_t {
@@ -566,9 +580,7 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
         WFPT_HIP(c, timed(kStageAov, [&] { return launch_aov(aov_args(c, nb), aov_grid(c), c->stream); }));
     if (c->fused) {
         if (int r = enqueue_fused_chain(c, timed, nb, 0, c->stream); r != WFPT_OK) return r;
-        WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] {
-                     return launch_accumulate(accumulate_args(c, c->n_pixels, true, nb), c->accumulate_grid, c->stream);
-                 }));
+        WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] { return launch_batch_accumulate(c, nb); }));
         return WFPT_OK;
     }
     WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS,
@@ -597,15 +609,14 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
                      return launch_miss(miss_args(c, qi, &c->ctl->miss_n, c->capacity, nb), consumer_grid(c, nb), c->stream);
                  }));
     }
-    WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] {
-                 return launch_accumulate(accumulate_args(c, c->n_pixels, true, nb), c->accumulate_grid, c->stream);
-             }));
+    WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] { return launch_batch_accumulate(c, nb); }));
     return WFPT_OK;
 }
 
-// whatever zeroes `accumulated` zeroes the AOV sums with it (include/wfpt.h "AOVs")
+// whatever zeroes `accumulated` zeroes the AOV sums and the luminance moments with it (include/wfpt.h "AOVs", "Denoiser")
 int reset_aov(wfpt_ctx *c) {
     if (c->aov_sums) WFPT_HIP(c, hipMemsetAsync(c->aov_sums, 0, sizeof(float) * kAovPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
+    if (c->moments) WFPT_HIP(c, hipMemsetAsync(c->moments, 0, sizeof(float) * kMomentPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
     return WFPT_OK;
 }
 
@@ -1099,6 +1110,7 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
     }
     auto *c = new wfpt_ctx();
     c->p = *params;
+    if (c->p.flags & WFPT_FLAG_DENOISE) c->p.flags |= WFPT_FLAG_AOV; // the denoiser's guides are the AOVs
     c->device = params->device;
     c->tile.world = params->tile_world == 0 ? 1u : params->tile_world;
     c->tile.rank = params->tile_world == 0 ? 0u : params->tile_rank;
@@ -1226,9 +1238,13 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         }
     }
     CREATE_HIP(hipMemsetAsync(c->accumulated, 0, sizeof(float) * c->acc_floats, c->stream));         // pt:60-65
-    if (params->flags & WFPT_FLAG_AOV) {
+    if (c->p.flags & WFPT_FLAG_AOV) {
         CREATE_HIP(dmalloc(&c->aov_sums, kAovPlanes * static_cast<size_t>(c->pixel_capacity)));
         CREATE_HIP(hipMemsetAsync(c->aov_sums, 0, sizeof(float) * kAovPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
+    }
+    if (c->p.flags & WFPT_FLAG_DENOISE) {
+        CREATE_HIP(dmalloc(&c->moments, kMomentPlanes * static_cast<size_t>(c->pixel_capacity)));
+        CREATE_HIP(hipMemsetAsync(c->moments, 0, sizeof(float) * kMomentPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
     }
     CREATE_HIP(dmalloc(&c->ctl, kMaxBatch));
     CREATE_HIP(hipMemsetAsync(c->ctl, 0, sizeof(Control) * kMaxBatch, c->stream));
@@ -1305,7 +1321,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV); // AOVs of chunked renders are out of scope (include/wfpt.h): nothing to allocate
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE); // AOVs / denoising of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1355,12 +1371,14 @@ void wfpt_destroy(wfpt_ctx *c) {
         if (t.stop) (void)hipEventDestroy(t.stop);
     }
     for (auto e : c->sample_events) (void)hipEventDestroy(e);
+    for (auto e : c->dn_ev)
+        if (e) (void)hipEventDestroy(e);
     free_scene(c);
     void *bufs[] = {c->rec_dense, c->rec_mem[0], c->rec_mem[1], c->f_miss_mem[0], c->f_miss_mem[1], c->f_chunk_hits[0], c->f_chunk_hits[1],
                     c->f_chunk_miss[0], c->f_chunk_miss[1], c->first_seg, c->f_cls[0], c->f_cls[1], c->first_seg_cls, c->plan, c->cls_table,
                     c->ray_mem[0], c->ray_mem[1], c->hit_mem, c->hit_rec, c->miss_mem, c->chunk_hits,
                     c->chunk_miss, c->chunk_hit_base, c->chunk_miss_base, c->mat_list, c->chunk_mat, c->image, c->accumulated, c->ctl,
-                    c->camera, c->d_stamps, c->aov_sums};
+                    c->camera, c->d_stamps, c->aov_sums, c->moments, c->dn_nz, c->dn_ag, c->dn_cv[0], c->dn_cv[1]};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1713,6 +1731,126 @@ int wfpt_aov_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (!c->aov_sums) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_aov_timing_ms: the context was created without WFPT_FLAG_AOV");
     if (ms_total) *ms_total = static_cast<float>(c->aov_ms);
     if (launches) *launches = c->aov_launches;
+    return WFPT_OK;
+}
+
+void wfpt_denoise_params_default(wfpt_denoise_params *p) {
+    if (!p) return;
+    *p = wfpt_denoise_params{};
+    p->iterations = 5;
+    p->sigma_luminance = 4.0f; // SVGF's (Schied et al. 2017)
+    p->sigma_normal = 128.0f;
+    p->sigma_depth = 1.0f;
+    p->sigma_albedo = 0.5f;    // chosen with tests/test_gpu_denoise.py's quality test
+}
+
+static int check_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, const void *out, const char *who) {
+    if (!c || !p || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_DENOISE");
+    if (c->tile.world > 1)
+        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": a band-sharded context holds only its own bands (the filter needs its neighbours')");
+    auto sigma_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
+    if (p->iterations > 8u || !sigma_ok(p->sigma_luminance) || !sigma_ok(p->sigma_normal) || !sigma_ok(p->sigma_depth) ||
+        !sigma_ok(p->sigma_albedo) || p->_reserved[0] || p->_reserved[1] || p->_reserved[2])
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": iterations must be 0..8, every sigma > 0 and finite, _reserved 0");
+    return WFPT_OK;
+}
+
+// Enqueues prepare and the passes; the result is c in dn_cv[iterations & 1] and, when out is not null, its first out_floats floats.
+static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out, size_t out_floats) {
+    const size_t cap = c->pixel_capacity;
+    if (!c->dn_nz) {
+        WFPT_HIP(c, dmalloc(&c->dn_nz, cap));
+        WFPT_HIP(c, dmalloc(&c->dn_ag, cap));
+        WFPT_HIP(c, dmalloc(&c->dn_cv[0], cap));
+        WFPT_HIP(c, dmalloc(&c->dn_cv[1], cap));
+    }
+    for (auto &e : c->dn_ev)
+        if (!e) WFPT_HIP(c, hipEventCreate(&e));
+    DenoiseArgs a{};
+    a.width = c->width;
+    a.height = c->height;
+    a.n = c->accumulated_samples;
+    a.accumulated = c->accumulated;
+    a.aov_sums = c->aov_sums;
+    a.moments = c->moments;
+    a.plane = cap;
+    a.guide_nz = c->dn_nz;
+    a.guide_ag = c->dn_ag;
+    a.sigma_l = p->sigma_luminance;
+    a.sigma_n = p->sigma_normal;
+    a.sigma_z = p->sigma_depth;
+    a.sigma_a2 = p->sigma_albedo * p->sigma_albedo;
+    WFPT_HIP(c, hipEventRecord(c->dn_ev[0], c->stream));
+    a.cv_in = nullptr;
+    a.cv_out = c->dn_cv[0];
+    a.out = p->iterations == 0 ? out : nullptr;
+    a.out_floats = out_floats;
+    WFPT_HIP(c, launch_denoise_prepare(a, c->stream));
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        a.cv_in = c->dn_cv[i & 1u];
+        a.cv_out = c->dn_cv[(i + 1u) & 1u];
+        a.step = 1u << i;
+        a.out = i + 1u == p->iterations ? out : nullptr;
+        WFPT_HIP(c, launch_denoise_atrous(a, c->stream));
+    }
+    WFPT_HIP(c, hipEventRecord(c->dn_ev[1], c->stream));
+    WFPT_HIP(c, hipEventSynchronize(c->dn_ev[1]));
+    WFPT_HIP(c, hipEventElapsedTime(&c->dn_ms, c->dn_ev[0], c->dn_ev[1]));
+    c->dn_calls += 1;
+    return WFPT_OK;
+}
+
+int wfpt_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *rgb, size_t n_floats) {
+    if (int r = check_denoise(c, p, rgb, "wfpt_denoise"); r != WFPT_OK) return r;
+    if (n_floats > 3 * static_cast<size_t>(c->n_pixels)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise: n_floats exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    if (c->accumulated_samples == 0) {
+        std::fill(rgb, rgb + n_floats, 0.0f);
+        return WFPT_OK;
+    }
+    if (int r = enqueue_denoise(c, p, nullptr, 0); r != WFPT_OK) return r;
+    const size_t n_px = (n_floats + 2) / 3;
+    std::vector<float4> cv(n_px);
+    WFPT_HIP(c, hipMemcpy(cv.data(), c->dn_cv[p->iterations & 1u], sizeof(float4) * n_px, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_floats; ++k) {
+        const float4 &v = cv[k / 3];
+        rgb[k] = k % 3 == 0 ? v.x : k % 3 == 1 ? v.y : v.z;
+    }
+    return WFPT_OK;
+}
+
+int wfpt_denoise_to_device(wfpt_ctx *c, const wfpt_denoise_params *p, void *device_ptr, size_t n_bytes) {
+    if (int r = check_denoise(c, p, device_ptr, "wfpt_denoise_to_device"); r != WFPT_OK) return r;
+    if (n_bytes > sizeof(float) * 3 * static_cast<size_t>(c->n_pixels))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_to_device: n_bytes exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    if (c->accumulated_samples == 0) {
+        WFPT_HIP(c, hipMemsetAsync(device_ptr, 0, n_bytes, c->stream));
+        WFPT_HIP(c, hipStreamSynchronize(c->stream));
+        return WFPT_OK;
+    }
+    return enqueue_denoise(c, p, static_cast<float *>(device_ptr), n_bytes / sizeof(float));
+}
+
+int wfpt_read_variance(wfpt_ctx *c, float *out, size_t n_elems) {
+    if (!c || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: null argument");
+    if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: the context was created without WFPT_FLAG_DENOISE");
+    if (n_elems > c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: n_elems exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t plane = c->pixel_capacity;
+    std::vector<float> m(kMomentPlanes * plane);
+    WFPT_HIP(c, hipMemcpy(m.data(), c->moments, sizeof(float) * m.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_elems; ++k) out[k] = variance_resolve(m[k], m[plane + k], c->accumulated_samples);
+    return WFPT_OK;
+}
+
+int wfpt_denoise_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *calls) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: null context");
+    if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: the context was created without WFPT_FLAG_DENOISE");
+    if (ms_last) *ms_last = c->dn_ms;
+    if (calls) *calls = c->dn_calls;
     return WFPT_OK;
 }
 

@@ -435,6 +435,39 @@ __host__ __device__ inline uint32_t aov_resolve_word(const float *sums, size_t p
 }
 __host__ __device__ inline uint32_t aov_channels(uint32_t which) { return which < 2u ? 3u : which < WFPT_AOV_COUNT ? 1u : 0u; }
 
+// ---- denoiser (WFPT_FLAG_DENOISE; include/wfpt.h "Denoiser"). The luminance moments are two planes of `plane` floats (the pixel capacity)
+// behind one base pointer, indexed like `accumulated`: S1 = sum of L_k, then S2 = sum of L_k * L_k, over the samples k since the last reset.
+constexpr uint32_t kMomentPlanes = 2;
+__host__ __device__ inline float denoise_luma(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// The variance of the n-sample mean's luminance from the moments (wfpt_read_variance on the host, denoise_prepare_kernel on the device):
+// one IEEE f32 division per step, in this order.
+__host__ __device__ inline float variance_resolve(float s1, float s2, uint32_t n) {
+    if (n == 0u) return 0.0f;
+    const float nf = static_cast<float>(n);
+    const float mu = s1 / nf;
+    const float d = s2 / nf - mu * mu;
+    return (d > 0.0f ? d : 0.0f) / nf;
+}
+
+// One launch of the filter chain over a width x height row-major image (an unsharded context: pixel slot = x + y * width).
+struct DenoiseArgs {
+    uint32_t width, height;
+    uint32_t n;                 // samples accumulated (>= 1)
+    const float *accumulated;   // stride 3
+    const float *aov_sums;      // kAovPlanes planes of `plane`
+    const float *moments;       // kMomentPlanes planes of `plane`
+    Stride32 plane;
+    float4 *guide_nz;           // (normalised normal, depth): written by prepare, read by the passes
+    float4 *guide_ag;           // (albedo, |grad z|)
+    const float4 *cv_in;        // (c, v) of the previous pass
+    float4 *cv_out;             // (c, v) this launch writes (prepare: pass 0's input)
+    float *out;                 // when not null: also c, stride 3, the first out_floats floats (the caller's buffer)
+    size_t out_floats;
+    uint32_t step;              // a-trous pass: 2^i
+    float sigma_l, sigma_n, sigma_z, sigma_a2; // sigma_a2 = sigma_albedo * sigma_albedo
+};
+constexpr uint32_t kDenoiseTile = 16; // a workgroup = 16 x 16 pixels, each of its four waves an 8 x 8 block
+
 hipError_t launch_generate(const GenerateArgs &a, hipStream_t s);
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per sample
@@ -465,6 +498,10 @@ hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s);
 uint32_t aov_lds_bytes(const SceneDev &scene);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
+// accumulate_kernel's work plus the luminance moments (WFPT_FLAG_DENOISE contexts, in its place)
+hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, size_t plane, uint32_t grid, hipStream_t s);
+hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);
+hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_selftest_math(int op, const float *a, const float *b, float *out, size_t n, hipStream_t s);
 // Occupancy of the extend kernel for a given dynamic LDS size (workgroups per CU); also raises the
 // kernel's dynamic-LDS limit when the scene needs more than the default 64 KiB.

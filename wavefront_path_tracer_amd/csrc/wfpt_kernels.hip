@@ -3061,6 +3061,210 @@ __global__ __launch_bounds__(256) void aov_resolve_kernel(const float *sums, siz
         out[k] = aov_resolve_word(sums, plane, which, k, n_samples);
 }
 
+// ================================================================================================
+// denoiser (WFPT_FLAG_DENOISE; include/wfpt.h "Denoiser")
+// ================================================================================================
+// accumulate_kernel's adds in the same order -- `accumulated` gets the same bits -- plus the luminance moments of each sample's value.
+// Runs in place of accumulate_kernel on flagged contexts only (that kernel stays as it is: profiles and the resource tests key on it).
+// Four samples' loads in flight per trip: the moments' two extra planes read and written once per batch cost 8 B of 28 per pixel.
+__global__ __launch_bounds__(256) void accumulate_moments_kernel(AccumulateArgs a, float *moments, Stride32 plane) {
+    const size_t stride4 = a.batch.image_stride / 4u;
+    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
+    float *s2p = moments + static_cast<size_t>(plane);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n_pixels; i += gridDim.x * blockDim.x) {
+        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
+        float s1 = moments[i], s2 = s2p[i];
+        const float4 *im0 = image4 + i;
+        uint32_t smp = 0;
+        for (; smp + 4u <= a.batch.n; smp += 4u) {
+            float4 p[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) p[k] = im0[(smp + k) * stride4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) {
+                r += p[k].x; g += p[k].y; b += p[k].z;
+                const float l = denoise_luma(p[k].x, p[k].y, p[k].z);
+                s1 += l; s2 += l * l;
+            }
+        }
+        for (; smp < a.batch.n; ++smp) {
+            const float4 p = im0[smp * stride4];
+            r += p.x; g += p.y; b += p.z;
+            const float l = denoise_luma(p.x, p.y, p.z);
+            s1 += l; s2 += l * l;
+        }
+        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
+        moments[i] = s1; s2p[i] = s2;
+    }
+    if (blockIdx.x == 0 && a.bookkeeping) { // the end of accumulate_kernel, restated: the batch's bounce rows -> totals, frame += n
+        __shared__ unsigned long long s_rows[kMaxRows][2];
+        for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += blockDim.x) (&s_rows[0][0])[k] = 0ull;
+        __syncthreads();
+        for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += blockDim.x) {
+            const Control *c = a.ctl + smp;
+            const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
+            for (uint32_t b = 0; b < rows; ++b) {
+                if (c->rows[b][0] == 0) continue;
+                atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
+                atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
+            }
+        }
+        __syncthreads();
+        Control *c0 = a.ctl;
+        if (threadIdx.x < kMaxRows) {
+            const uint32_t b = threadIdx.x;
+            const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
+            if (h + m) {
+                c0->wave_totals[b][0] += h + m;
+                c0->wave_totals[b][1] += h;
+                c0->wave_totals[b][2] += m;
+            }
+        }
+        if (threadIdx.x == 0) {
+            unsigned long long h = 0, m = 0;
+            for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
+            c0->totals[0] += h + m;
+            c0->totals[1] += h;
+            c0->totals[2] += m;
+            c0->totals[3] += a.batch.n;
+            c0->samples += a.batch.n;
+            c0->ticket = 0;
+            c0->frame.frame += a.batch.n;
+        }
+    }
+}
+
+// The filter's pixel of this thread: a workgroup covers a kDenoiseTile^2 block, each wave an 8 x 8 block of it (2-D locality for the taps,
+// as generate_rays_kernel's tiles). False for the padding lanes of partial blocks.
+__device__ inline bool denoise_pixel(const DenoiseArgs &a, uint32_t &x, uint32_t &y) {
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+    x = blockIdx.x * kDenoiseTile + (wave & 1u) * 8u + (t & 7u);
+    y = blockIdx.y * kDenoiseTile + (wave >> 1) * 8u + ((t >> 3) & 7u);
+    return x < a.width && y < a.height;
+}
+
+// Guides and pass 0's (c, v) from the read-back values (the resolve functions wfpt_read_accumulated / _aov / _variance share, so every
+// input is bit-equal to what the host reads).
+__global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a) {
+    uint32_t x, y;
+    if (!denoise_pixel(a, x, y)) return;
+    const size_t w = a.width, p = y * w + x, plane = a.plane;
+    const float nf = static_cast<float>(a.n);
+    auto word = [&](uint32_t which, size_t k) { return __uint_as_float(aov_resolve_word(a.aov_sums, plane, which, k, a.n)); };
+    auto luma_of = [&](size_t q) { return denoise_luma(a.accumulated[3u * q] / nf, a.accumulated[3u * q + 1u] / nf, a.accumulated[3u * q + 2u] / nf); };
+    const float cr = a.accumulated[3u * p] / nf, cg = a.accumulated[3u * p + 1u] / nf, cb = a.accumulated[3u * p + 2u] / nf;
+    float nx = word(WFPT_AOV_NORMAL, 3u * p), ny = word(WFPT_AOV_NORMAL, 3u * p + 1u), nz = word(WFPT_AOV_NORMAL, 3u * p + 2u);
+    const float dot = (nx * nx + ny * ny) + nz * nz;
+    if (dot != 0.0f) {
+        const float inv = 1.0f / sqrtf(dot);
+        nx *= inv; ny *= inv; nz *= inv;
+    } else {
+        nx = ny = nz = 0.0f;
+    }
+    const float z = word(WFPT_AOV_DEPTH, p);
+    // per axis the smaller step to an existing neighbour (0 without one)
+    float gx = 0.0f, gy = 0.0f;
+    if (x > 0u) gx = fabsf(word(WFPT_AOV_DEPTH, p - 1u) - z);
+    if (x + 1u < a.width) { const float d = fabsf(word(WFPT_AOV_DEPTH, p + 1u) - z); gx = x > 0u ? fminf(gx, d) : d; }
+    if (y > 0u) gy = fabsf(word(WFPT_AOV_DEPTH, p - w) - z);
+    if (y + 1u < a.height) { const float d = fabsf(word(WFPT_AOV_DEPTH, p + w) - z); gy = y > 0u ? fminf(gy, d) : d; }
+    const float grad = sqrtf(gx * gx + gy * gy);
+    float v;
+    if (a.n >= 4u) {
+        v = variance_resolve(a.moments[p], a.moments[plane + p], a.n);
+    } else { // short history: the population variance of L(c) over the 7x7 window, clipped to the image
+        float s1 = 0.0f, s2 = 0.0f, m = 0.0f;
+        for (int dy = -3; dy <= 3; ++dy) {
+            const int yq = static_cast<int>(y) + dy;
+            if (yq < 0 || yq >= static_cast<int>(a.height)) continue;
+            for (int dx = -3; dx <= 3; ++dx) {
+                const int xq = static_cast<int>(x) + dx;
+                if (xq < 0 || xq >= static_cast<int>(a.width)) continue;
+                const float l = luma_of(static_cast<size_t>(yq) * w + static_cast<size_t>(xq));
+                s1 += l; s2 += l * l; m += 1.0f;
+            }
+        }
+        const float mu = s1 / m;
+        const float d = s2 / m - mu * mu;
+        v = d > 0.0f ? d : 0.0f;
+    }
+    a.guide_nz[p] = make_float4(nx, ny, nz, z);
+    a.guide_ag[p] = make_float4(word(WFPT_AOV_ALBEDO, 3u * p), word(WFPT_AOV_ALBEDO, 3u * p + 1u), word(WFPT_AOV_ALBEDO, 3u * p + 2u), grad);
+    a.cv_out[p] = make_float4(cr, cg, cb, v);
+    if (a.out) {
+        if (3u * p < a.out_floats) a.out[3u * p] = cr;
+        if (3u * p + 1u < a.out_floats) a.out[3u * p + 1u] = cg;
+        if (3u * p + 2u < a.out_floats) a.out[3u * p + 2u] = cb;
+    }
+}
+
+// One a-trous pass at step a.step: the 5x5 taps p + step (dx, dy), dy outer, dx inner, taps outside the image skipped. The taps come from
+// L1 / L2: at step 16 an 8 x 8 block's apron is 64 pixels wide, and a tile of it in LDS would be read once.
+__global__ __launch_bounds__(256) void denoise_atrous_kernel(DenoiseArgs a) {
+    uint32_t x, y;
+    if (!denoise_pixel(a, x, y)) return;
+    const size_t w = a.width, p = y * w + x;
+    const float4 cp = a.cv_in[p], np = a.guide_nz[p], ap = a.guide_ag[p];
+    const float lp = denoise_luma(cp.x, cp.y, cp.z);
+    // g3: the 3x3 binomial blur of v at step 1, taps outside skipped and the weights renormalised
+    constexpr float k3[3] = {0.25f, 0.5f, 0.25f};
+    float gs = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int yq = static_cast<int>(y) + dy;
+        if (yq < 0 || yq >= static_cast<int>(a.height)) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int xq = static_cast<int>(x) + dx;
+            if (xq < 0 || xq >= static_cast<int>(a.width)) continue;
+            const float k = k3[dy + 1] * k3[dx + 1];
+            gs += k * a.cv_in[static_cast<size_t>(yq) * w + static_cast<size_t>(xq)].w;
+            gw += k;
+        }
+    }
+    const float den_l = a.sigma_l * sqrtf(gs / gw) + 1e-10f;
+    const float zscale = (a.sigma_z * ap.w) * static_cast<float>(a.step);
+    const bool p_normal = np.x != 0.0f || np.y != 0.0f || np.z != 0.0f;
+    constexpr float h[5] = {1.0f / 16.0f, 0.25f, 0.375f, 0.25f, 1.0f / 16.0f};
+    const int s = static_cast<int>(a.step);
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yq = static_cast<int>(y) + dy * s;
+        if (yq < 0 || yq >= static_cast<int>(a.height)) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int xq = static_cast<int>(x) + dx * s;
+            if (xq < 0 || xq >= static_cast<int>(a.width)) continue;
+            const size_t q = static_cast<size_t>(yq) * w + static_cast<size_t>(xq);
+            const float4 cq = a.cv_in[q], nq = a.guide_nz[q], aq = a.guide_ag[q];
+            const float dl = fabsf(lp - denoise_luma(cq.x, cq.y, cq.z));
+            const float dz = fabsf(np.w - nq.w);
+            const float ar = ap.x - aq.x, ag = ap.y - aq.y, ab = ap.z - aq.z;
+            const float da = (ar * ar + ag * ag) + ab * ab;
+            const float den_z = zscale * sqrtf(static_cast<float>(dx * dx + dy * dy)) + 1e-3f;
+            const float e = (-(dl / den_l) - dz / den_z) - da / a.sigma_a2;
+            const bool q_normal = nq.x != 0.0f || nq.y != 0.0f || nq.z != 0.0f;
+            float wn = p_normal == q_normal ? 1.0f : 0.0f;
+            if (p_normal && q_normal) {
+                const float nd = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+                wn = powf(nd > 0.0f ? nd : 0.0f, a.sigma_n);
+            }
+            const float wt = ((h[dx + 2] * h[dy + 2]) * expf(e)) * wn;
+            sw += wt;
+            sr += wt * cq.x; sg += wt * cq.y; sb += wt * cq.z;
+            sv += (wt * wt) * cq.w;
+        }
+    }
+    const float cr = sr / sw, cg = sg / sw, cb = sb / sw;
+    a.cv_out[p] = make_float4(cr, cg, cb, sv / (sw * sw));
+    if (a.out) {
+        if (3u * p < a.out_floats) a.out[3u * p] = cr;
+        if (3u * p + 1u < a.out_floats) a.out[3u * p + 1u] = cg;
+        if (3u * p + 2u < a.out_floats) a.out[3u * p + 2u] = cb;
+    }
+}
+
 __global__ void selftest_math_kernel(int op, const float *a, const float *b, float *out, size_t n) {
     const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
     if (i >= n) return;
@@ -3368,6 +3572,27 @@ hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, u
     const size_t blocks = (n_words + 255) / 256;
     hipLaunchKernelGGL(aov_resolve_kernel, dim3(static_cast<uint32_t>(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, sums, plane, which,
                        n_samples, out, n_words);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, size_t plane, uint32_t grid, hipStream_t s) {
+    Stride32 pl{};
+    pl = plane;
+    hipLaunchKernelGGL(accumulate_moments_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, moments, pl);
+    return hipGetLastError();
+}
+
+static dim3 denoise_grid(const DenoiseArgs &a) { return dim3((a.width + kDenoiseTile - 1) / kDenoiseTile, (a.height + kDenoiseTile - 1) / kDenoiseTile); }
+
+hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s) {
+    if (a.width == 0 || a.height == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_prepare_kernel, denoise_grid(a), dim3(kDenoiseTile * kDenoiseTile), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s) {
+    if (a.width == 0 || a.height == 0) return hipSuccess;
+    hipLaunchKernelGGL(denoise_atrous_kernel, denoise_grid(a), dim3(kDenoiseTile * kDenoiseTile), 0, s, a);
     return hipGetLastError();
 }
 
