@@ -401,6 +401,13 @@ int wfpt_render_sample(wfpt_ctx *ctx);
 int wfpt_render(wfpt_ctx *ctx, uint32_t n_samples);
 int wfpt_synchronize(wfpt_ctx *ctx);
 uint32_t wfpt_frame(const wfpt_ctx *ctx);               /* RenderProgress.frame */
+/* RNG frame offset of the device-resident loop (wfpt_render*, default 0): the frame uniform it writes becomes
+ * {width, height, wfpt_frame() + 1 + offset, 0} (uint32 wrap-around), so the samples after a reset continue the random streams of
+ * earlier epochs instead of replaying frames 1, 2, ... (a temporal blend of repeated streams gains nothing). wfpt_frame()
+ * keeps its meaning. Setting it takes effect at the next rendered batch; no reset, camera change or scene change clears it. The stage
+ * API (wfpt_set_frame / wfpt_kernel_run, PathTracer.run) sets the frame itself and ignores the offset, as does wfpt_render_chunked*. */
+int wfpt_set_frame_offset(wfpt_ctx *ctx, uint32_t offset);
+uint32_t wfpt_frame_offset(const wfpt_ctx *ctx);
 uint32_t wfpt_accumulated_samples(const wfpt_ctx *ctx); /* RenderProgress.accumulated_samples */
 float wfpt_progress(const wfpt_ctx *ctx, uint32_t spp); /* PathTracer::progress (path_tracer.rs:219-221) */
 /* Same loop with hipEvent pairs around every stage launch; adds the elapsed milliseconds per stage
@@ -496,6 +503,63 @@ int wfpt_read_variance(wfpt_ctx *ctx, float *out, size_t n_elems);
 /* time of the last denoise call's launches (a hipEvent pair around them) and the number of calls since wfpt_create; either pointer may
  * be NULL */
 int wfpt_denoise_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *calls);
+
+/* ------------------------------------------------------------------ Temporal denoiser (WFPT_FLAG_DENOISE): reprojected history
+ * wfpt_denoise_temporal is wfpt_denoise with temporal_prepare_kernel in place of prepare: it carries the samples of earlier camera poses
+ * into the current one (the temporal part of SVGF, Schied et al. 2017), then runs the same a-trous passes. Any WFPT_FLAG_DENOISE context.
+ * Epochs: an epoch is the span between two resets of the accumulation (every camera change, wfpt_reset_progress, wfpt_reset_accumulated).
+ * The context keeps two history slots, live and sealed (allocated by the first call): per pixel the blended colour c and history length L,
+ * the per-sample moments (m1, m2), the guides (normalised normal and depth as prepare makes them, coverage, material id), plus the epoch
+ * and the camera (position, view, inv_proj, viewport) they were written under. A call first seals: when the live slot was written in
+ * another epoch, live and sealed swap. Then, n = wfpt_accumulated_samples, S / S1 / S2 the sums, per pixel p = (x, y):
+ *   ray         the centre ray of primary_ray (jitter (0, 0), no lens) from the camera position o; X = (o + z d, 1) where coverage > 0
+ *               (a hit), else the direction (d, 0)
+ *   project     q = M X, M = inverse(inv_proj_s) inverse(view_s) of the sealed camera (double on the host, rounded to f32); q.w <= 0: no
+ *               history; else x' = ((q.x / q.w + 1) 0.5) W, y' = (1 - (q.y / q.w + 1) 0.5) H (pixel centres at integers),
+ *               z' = |X - o_s| for hits (0 for misses)
+ *   taps        (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), x0 = floor(x'), bilinear weights; a tap inside the image is accepted when
+ *               for a hit: its coverage > 0, the same material id, |z_t - z'| <= depth_tolerance z' and dot(N_p, N_t) >= normal_cos;
+ *               for a miss: its coverage is 0. Wsum = sum of the accepted weights in tap order
+ *   no history (no projection, Wsum < 0.01 or history_cap == 0): prepare's outputs, bit for bit; the slot gets c = S / n, L = n and the
+ *               moments (S1 / n, S2 / n)
+ *   history     H = sum w value_t / Wsum over the accepted taps for c, m1, m2 and L; h = min(H_L, history_cap), L = h + n;
+ *               c = (h H_c + S) / L, m1 = (h H_m1 + S1) / L, m2 = (h H_m2 + S2) / L, v = max(0, m2 - m1 m1) / L (for L < 4 prepare's
+ *               7x7 variance times n / L instead)
+ * (c, v) is pass 0's input. Each call is a pure function of the sealed slot, the sums and the parameters: repeated calls give the same
+ * bits, and it changes nothing a render, wfpt_denoise or the AOV read-backs see. The next call has no history after wfpt_reset_history,
+ * wfpt_update_scene* (there are no object motion vectors), a viewport size change, and on the first call. With n == 0 the call writes
+ * zeros and leaves both slots untouched. WFPT_ERR_INVALID_ARGUMENT without the flag, for a bad parameter or too large a size;
+ * WFPT_ERR_UNSUPPORTED on a band-sharded context. Out of scope: object motion, the stage API, wfpt_render_chunked*. */
+typedef struct wfpt_temporal_params {
+    wfpt_denoise_params spatial;  /* the a-trous passes, checked as wfpt_denoise checks them */
+    float history_cap;            /* >= 0, finite: samples of history a pixel may carry; 0 = none (the call equals wfpt_denoise) */
+    float depth_tolerance;        /* > 0, finite, relative */
+    float normal_cos;             /* in [-1, 1] */
+    uint32_t _reserved[5];        /* must be 0 */
+} wfpt_temporal_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_temporal_params) == 64 && offsetof(wfpt_temporal_params, history_cap) == 32 &&
+                       offsetof(wfpt_temporal_params, depth_tolerance) == 36 && offsetof(wfpt_temporal_params, normal_cos) == 40 &&
+                       offsetof(wfpt_temporal_params, _reserved) == 44,
+                   "wfpt_temporal_params: 64 bytes");
+/* spatial = wfpt_denoise_params_default, history_cap 32 (chosen by a sweep: DESIGN.md 9d), depth_tolerance 0.05, normal_cos 0.9 */
+void wfpt_temporal_params_default(wfpt_temporal_params *p);
+/* the denoised mean colour, 3 * n_pixels floats at most (blocking) */
+int wfpt_denoise_temporal(wfpt_ctx *ctx, const wfpt_temporal_params *p, float *rgb, size_t n_floats);
+/* the same bits written into a caller's device buffer of n_bytes (at most 12 * n_pixels); returns when they are written */
+int wfpt_denoise_temporal_to_device(wfpt_ctx *ctx, const wfpt_temporal_params *p, void *device_ptr, size_t n_bytes);
+/* per-pixel state of the last temporal call (channels per pixel in the comment) */
+typedef enum wfpt_temporal_out {
+    WFPT_TEMPORAL_COLOR = 0,   /* 3: c before the passes */
+    WFPT_TEMPORAL_MOMENTS = 1, /* 2: (m1, m2) */
+    WFPT_TEMPORAL_LENGTH = 2,  /* 1: L */
+    WFPT_TEMPORAL_MOTION = 3   /* 3: (x', y', z'); (-1e30, -1e30, 0) where there was no projection */
+} wfpt_temporal_out;
+/* channels * n_pixels floats at most (blocking); WFPT_ERR_INVALID_ARGUMENT when no call has run since the history was dropped */
+int wfpt_read_temporal(wfpt_ctx *ctx, int which, float *out, size_t n_elems);
+/* drops both history slots: the next temporal call has no history */
+int wfpt_reset_history(wfpt_ctx *ctx);
+/* time of the last temporal call's launches and the number of calls since wfpt_create; either pointer may be NULL */
+int wfpt_temporal_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *calls);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

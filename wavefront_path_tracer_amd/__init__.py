@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -37,6 +37,11 @@ FLAG_AOV = 1 << 10  # first-hit AOVs (include/wfpt.h "AOVs"); bit 9 is the retir
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
+# wfpt_temporal_params_default: the spatial passes above plus the history (include/wfpt.h "Temporal denoiser"); history_cap chosen by a
+# quality sweep, the rejection thresholds SVGF-style
+TEMPORAL_DEFAULTS = {**DENOISE_DEFAULTS, "history_cap": 32.0, "depth_tolerance": 0.05, "normal_cos": 0.9}
+# wfpt_temporal_out: name -> (value, channels)
+TEMPORAL_OUTPUTS = {"color": (0, 3), "moments": (1, 2), "length": (2, 1), "motion": (3, 3)}
 INACTIVE_PIXEL = 0xFFFFFFFF
 # wfpt_aov: name -> (value, channels, numpy dtype of the resolved values)
 AOV_ALBEDO, AOV_NORMAL, AOV_DEPTH, AOV_COVERAGE, AOV_PRIM_ID, AOV_MATERIAL_ID = 0, 1, 2, 3, 4, 5
@@ -84,6 +89,11 @@ class _Params(C.Structure):
 class _DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
                 ("sigma_albedo", C.c_float), ("_reserved", C.c_uint32 * 3)]
+
+
+class _TemporalParams(C.Structure):
+    _fields_ = [("spatial", _DenoiseParams), ("history_cap", C.c_float), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float),
+                ("_reserved", C.c_uint32 * 5)]
 
 
 class GPUFrameBuffer(C.Structure):
@@ -296,6 +306,14 @@ def lib():
         "wfpt_denoise_to_device": (i32, [vp, C.POINTER(_DenoiseParams), vp, sz]),
         "wfpt_read_variance": (i32, [vp, vp, sz]),
         "wfpt_denoise_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_set_frame_offset": (i32, [vp, u32]),
+        "wfpt_frame_offset": (u32, [vp]),
+        "wfpt_temporal_params_default": (None, [C.POINTER(_TemporalParams)]),
+        "wfpt_denoise_temporal": (i32, [vp, C.POINTER(_TemporalParams), vp, sz]),
+        "wfpt_denoise_temporal_to_device": (i32, [vp, C.POINTER(_TemporalParams), vp, sz]),
+        "wfpt_read_temporal": (i32, [vp, i32, vp, sz]),
+        "wfpt_reset_history": (i32, [vp]),
+        "wfpt_temporal_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -968,6 +986,72 @@ class PathTracer:
         """(milliseconds of the last denoise call's launches, denoise calls since creation)."""
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_denoise_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    # ---- temporal denoiser (contexts created with FLAG_DENOISE; include/wfpt.h "Temporal denoiser")
+    def set_frame_offset(self, offset):
+        """The device-resident loop's RNG frame offset: the next samples render frames wfpt_frame() + 1 + offset, ... (uint32). An
+        interactive host sets it to the samples rendered so far after each camera move, so a new pose does not replay the random streams
+        of the last one. No reset clears it; run() (the stage API) ignores it."""
+        self._check(lib().wfpt_set_frame_offset(self.handle, int(offset) & 0xFFFFFFFF))
+
+    @property
+    def frame_offset(self):
+        return int(lib().wfpt_frame_offset(self.handle))
+
+    @staticmethod
+    def _temporal_params(params):
+        unknown = set(params) - set(TEMPORAL_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown temporal denoise parameter(s) {sorted(unknown)}: one of {sorted(TEMPORAL_DEFAULTS)}")
+        v = {**TEMPORAL_DEFAULTS, **params}
+        spatial = PathTracer._denoise_params({k: v[k] for k in DENOISE_DEFAULTS})
+        return _TemporalParams(spatial, v["history_cap"], v["depth_tolerance"], v["normal_cos"])
+
+    def denoise_temporal(self, **params):
+        """(h, w, 3) float32: the denoised mean colour with the reprojected history of earlier epochs blended in. Parameters as
+        TEMPORAL_DEFAULTS; history_cap=0 gives denoise()'s bits."""
+        p = self._temporal_params(params)
+        a = np.zeros((self.n_pixels // self.width, self.width, 3), "<f4")
+        self._check(lib().wfpt_denoise_temporal(self.handle, C.byref(p), _p(a), a.size))
+        return a
+
+    def denoise_temporal_to_tensor(self, tensor, **params):
+        """Writes denoise_temporal(**params) into a caller's contiguous float32 device tensor of h * w * 3 elements on the context's device
+        (the same bits). Returns the tensor."""
+        p = self._temporal_params(params)
+        n = self.n_pixels * 3
+        dt = str(getattr(tensor, "dtype", "")).replace("torch.", "")
+        if dt != "float32":
+            raise TypeError(f"denoise_temporal_to_tensor: tensor dtype {dt or type(tensor).__name__} is not float32")
+        if tensor.numel() != n:
+            raise ValueError(f"denoise_temporal_to_tensor: tensor has {tensor.numel()} elements, the image {n}")
+        if not tensor.is_contiguous():
+            raise ValueError("denoise_temporal_to_tensor: tensor is not contiguous")
+        if getattr(tensor, "device", None) is None or tensor.device.type != "cuda" or tensor.device.index != self._params.device:
+            raise ValueError(f"denoise_temporal_to_tensor: tensor must live on this context's device (cuda:{self._params.device})")
+        self._check(lib().wfpt_denoise_temporal_to_device(self.handle, C.byref(p), C.c_void_p(tensor.data_ptr()), 4 * n))
+        return tensor
+
+    def temporal(self, name):
+        """State of the last temporal call, float32: "color" (h, w, 3) c before the passes, "moments" (h, w, 2) (m1, m2), "length" (h, w)
+        the history length L, "motion" (h, w, 3) (x', y', z'), (-1e30, -1e30, 0) where there was no projection."""
+        if name not in TEMPORAL_OUTPUTS:
+            raise KeyError(f"unknown temporal output {name!r}: one of {sorted(TEMPORAL_OUTPUTS)}")
+        which, ch = TEMPORAL_OUTPUTS[name]
+        h = self.n_pixels // self.width
+        a = np.zeros((h, self.width, ch) if ch > 1 else (h, self.width), "<f4")
+        self._check(lib().wfpt_read_temporal(self.handle, which, _p(a), a.size))
+        return a
+
+    def reset_history(self):
+        """The next denoise_temporal() call has no history."""
+        self._check(lib().wfpt_reset_history(self.handle))
+
+    def temporal_timing(self):
+        """(milliseconds of the last temporal call's launches, temporal calls since creation)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_temporal_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     # ---- read-back

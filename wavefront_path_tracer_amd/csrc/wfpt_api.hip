@@ -103,9 +103,27 @@ struct wfpt_ctx {
     hipEvent_t dn_ev[2] = {nullptr, nullptr};
     float dn_ms = 0.0f;         // the last denoise call's launches (wfpt_denoise_timing_ms)
     uint32_t dn_calls = 0;
+    // the temporal denoiser (include/wfpt.h "Temporal denoiser"): two history slots, tp[tp_live] and tp[tp_live ^ 1] (sealed), and the
+    // motion plane, allocated by the first wfpt_denoise_temporal*; `epoch` counts the resets of the accumulation (reset_aov)
+    struct History {
+        TemporalSlot s{};
+        bool valid = false;     // written by a call since the history was last dropped
+        uint64_t epoch = 0;
+        float pos[3] = {0, 0, 0}, view[16] = {}, inv_proj[16] = {};
+        uint32_t width = 0, height = 0;
+    } tp[2];
+    int tp_live = 0;
+    float4 *tp_motion = nullptr;
+    bool tp_read_ok = false;    // a call has run since the history was dropped (wfpt_read_temporal)
+    uint64_t epoch = 0;
+    hipEvent_t tp_ev[2] = {nullptr, nullptr};
+    float tp_ms = 0.0f;
+    uint32_t tp_calls = 0;
+    uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     Control *ctl = nullptr;
     CameraDev *camera = nullptr;
     wfpt_gpu_camera h_camera{};      // host copy (the conservative traversal's range check, wfpt_update_scene)
+    float h_inv_proj[16] = {}, h_view[16] = {}; // host copies of the matrices (the temporal denoiser's sealed camera)
     wfpt_bvh_node *d_nodes = nullptr;
     float4 *d_sphere_geom = nullptr;
     uint16_t *d_pair_parent = nullptr;
@@ -613,16 +631,24 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     return WFPT_OK;
 }
 
-// whatever zeroes `accumulated` zeroes the AOV sums and the luminance moments with it (include/wfpt.h "AOVs", "Denoiser")
+// whatever zeroes `accumulated` zeroes the AOV sums and the luminance moments with it (include/wfpt.h "AOVs", "Denoiser") and starts a new
+// epoch of the temporal denoiser
 int reset_aov(wfpt_ctx *c) {
+    c->epoch += 1;
     if (c->aov_sums) WFPT_HIP(c, hipMemsetAsync(c->aov_sums, 0, sizeof(float) * kAovPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
     if (c->moments) WFPT_HIP(c, hipMemsetAsync(c->moments, 0, sizeof(float) * kMomentPlanes * static_cast<size_t>(c->pixel_capacity), c->stream));
     return WFPT_OK;
 }
 
+// the next temporal call has no history (include/wfpt.h "Temporal denoiser")
+void drop_history(wfpt_ctx *c) {
+    c->tp[0].valid = c->tp[1].valid = false;
+    c->tp_read_ok = false;
+}
+
 int ensure_device_frame(wfpt_ctx *c) {
     if (c->dev_frame_valid) return WFPT_OK;
-    const wfpt_frame_buffer f{c->width, c->height, c->progress_frame + 1u, 0u}; // parameters.rs:78-83; pt:296
+    const wfpt_frame_buffer f{c->width, c->height, c->progress_frame + 1u + c->frame_offset, 0u}; // parameters.rs:78-83; pt:296 (+ the offset)
     WFPT_HIP(c, launch_set_frame(c->ctl, f, c->stream)); // on the stream: frames can be queued back to back without a host sync
     c->dev_frame_valid = true;
     return WFPT_OK;
@@ -1258,6 +1284,8 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
     const uint32_t cus = c->cus;
     // scene upload (pt:120-128) plus the traversal's own copies of it
     c->h_camera = *camera;
+    std::memcpy(c->h_inv_proj, inv_proj, sizeof c->h_inv_proj);
+    std::memcpy(c->h_view, view, sizeof c->h_view);
     if (upload_scene(c, spheres, triangles, n_spheres, materials, n_materials, nodes, n_nodes, pair_parent, static_cast<uint32_t>(bvh_depth),
                      camera) != WFPT_OK) {
         g_last_error = c->err;
@@ -1373,12 +1401,16 @@ void wfpt_destroy(wfpt_ctx *c) {
     for (auto e : c->sample_events) (void)hipEventDestroy(e);
     for (auto e : c->dn_ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto e : c->tp_ev)
+        if (e) (void)hipEventDestroy(e);
     free_scene(c);
     void *bufs[] = {c->rec_dense, c->rec_mem[0], c->rec_mem[1], c->f_miss_mem[0], c->f_miss_mem[1], c->f_chunk_hits[0], c->f_chunk_hits[1],
                     c->f_chunk_miss[0], c->f_chunk_miss[1], c->first_seg, c->f_cls[0], c->f_cls[1], c->first_seg_cls, c->plan, c->cls_table,
                     c->ray_mem[0], c->ray_mem[1], c->hit_mem, c->hit_rec, c->miss_mem, c->chunk_hits,
                     c->chunk_miss, c->chunk_hit_base, c->chunk_miss_base, c->mat_list, c->chunk_mat, c->image, c->accumulated, c->ctl,
-                    c->camera, c->d_stamps, c->aov_sums, c->moments, c->dn_nz, c->dn_ag, c->dn_cv[0], c->dn_cv[1]};
+                    c->camera, c->d_stamps, c->aov_sums, c->moments, c->dn_nz, c->dn_ag, c->dn_cv[0], c->dn_cv[1],
+                    c->tp[0].s.cl, c->tp[0].s.m, c->tp[0].s.nz, c->tp[0].s.cm, c->tp[1].s.cl, c->tp[1].s.m, c->tp[1].s.nz, c->tp[1].s.cm,
+                    c->tp_motion};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1407,6 +1439,7 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
     if (probe.n_pixels > c->pixel_capacity || slots > c->capacity)
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "viewport exceeds the capacity given at wfpt_create (max_pixels)");
     WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    if (width != c->width || height != c->height) drop_history(c); // the history's pixels belong to another viewport
     set_viewport(c, width, height);
     CameraDev cam{};
     cam.cam = *camera;
@@ -1420,6 +1453,8 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
     c->dev_frame_valid = false;
     destroy_graph(c); // grid shapes (and the kernel variant) are baked into the captured graph
     c->h_camera = *camera;
+    std::memcpy(c->h_inv_proj, inv_proj, sizeof c->h_inv_proj);
+    std::memcpy(c->h_view, view, sizeof c->h_view);
     float reach[3];
     camera_reach(*camera, reach);
     decide_exact(c, reach); // a camera far outside the scene leaves the conservative box test's error bound
@@ -1454,6 +1489,7 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
                              static_cast<uint32_t>(depth), &c->h_camera);
         r != WFPT_OK)
         return r;
+    drop_history(c); // no object motion vectors: the history shows the old scene
     return wfpt_reset_progress(c);
 }
 
@@ -1653,6 +1689,13 @@ int wfpt_synchronize(wfpt_ctx *c) {
 }
 
 uint32_t wfpt_frame(const wfpt_ctx *c) { return c ? c->progress_frame : 0; }
+int wfpt_set_frame_offset(wfpt_ctx *c, uint32_t offset) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
+    c->frame_offset = offset;
+    c->dev_frame_valid = false; // the next rendered batch rewrites the frame uniform with it
+    return WFPT_OK;
+}
+uint32_t wfpt_frame_offset(const wfpt_ctx *c) { return c ? c->frame_offset : 0; }
 uint32_t wfpt_accumulated_samples(const wfpt_ctx *c) { return c ? c->accumulated_samples : 0; }
 float wfpt_progress(const wfpt_ctx *c, uint32_t spp) {
     return (c && spp) ? static_cast<float>(c->accumulated_samples) / static_cast<float>(spp) : 0.0f;
@@ -1756,8 +1799,9 @@ static int check_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, const void *
     return WFPT_OK;
 }
 
-// Enqueues prepare and the passes; the result is c in dn_cv[iterations & 1] and, when out is not null, its first out_floats floats.
-static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out, size_t out_floats) {
+// Enqueues prepare (temporal_prepare with t) and the passes; the result is c in dn_cv[iterations & 1] and, when out is not null, its first
+// out_floats floats. Blocks until they are done and records the launches' time as the denoise (temporal with t) call's.
+static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out, size_t out_floats, const TemporalArgs *t = nullptr) {
     const size_t cap = c->pixel_capacity;
     if (!c->dn_nz) {
         WFPT_HIP(c, dmalloc(&c->dn_nz, cap));
@@ -1765,8 +1809,9 @@ static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out
         WFPT_HIP(c, dmalloc(&c->dn_cv[0], cap));
         WFPT_HIP(c, dmalloc(&c->dn_cv[1], cap));
     }
-    for (auto &e : c->dn_ev)
-        if (!e) WFPT_HIP(c, hipEventCreate(&e));
+    hipEvent_t *ev = t ? c->tp_ev : c->dn_ev;
+    for (int k = 0; k < 2; ++k)
+        if (!ev[k]) WFPT_HIP(c, hipEventCreate(&ev[k]));
     DenoiseArgs a{};
     a.width = c->width;
     a.height = c->height;
@@ -1781,12 +1826,12 @@ static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out
     a.sigma_n = p->sigma_normal;
     a.sigma_z = p->sigma_depth;
     a.sigma_a2 = p->sigma_albedo * p->sigma_albedo;
-    WFPT_HIP(c, hipEventRecord(c->dn_ev[0], c->stream));
+    WFPT_HIP(c, hipEventRecord(ev[0], c->stream));
     a.cv_in = nullptr;
     a.cv_out = c->dn_cv[0];
     a.out = p->iterations == 0 ? out : nullptr;
     a.out_floats = out_floats;
-    WFPT_HIP(c, launch_denoise_prepare(a, c->stream));
+    WFPT_HIP(c, t ? launch_temporal_prepare(a, *t, c->stream) : launch_denoise_prepare(a, c->stream));
     for (uint32_t i = 0; i < p->iterations; ++i) {
         a.cv_in = c->dn_cv[i & 1u];
         a.cv_out = c->dn_cv[(i + 1u) & 1u];
@@ -1794,10 +1839,22 @@ static int enqueue_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *out
         a.out = i + 1u == p->iterations ? out : nullptr;
         WFPT_HIP(c, launch_denoise_atrous(a, c->stream));
     }
-    WFPT_HIP(c, hipEventRecord(c->dn_ev[1], c->stream));
-    WFPT_HIP(c, hipEventSynchronize(c->dn_ev[1]));
-    WFPT_HIP(c, hipEventElapsedTime(&c->dn_ms, c->dn_ev[0], c->dn_ev[1]));
-    c->dn_calls += 1;
+    WFPT_HIP(c, hipEventRecord(ev[1], c->stream));
+    WFPT_HIP(c, hipEventSynchronize(ev[1]));
+    WFPT_HIP(c, hipEventElapsedTime(t ? &c->tp_ms : &c->dn_ms, ev[0], ev[1]));
+    (t ? c->tp_calls : c->dn_calls) += 1;
+    return WFPT_OK;
+}
+
+// c's first n_floats floats from (c, v) planes on the device
+static int read_cv(wfpt_ctx *c, const float4 *cv_dev, float *rgb, size_t n_floats) {
+    const size_t n_px = (n_floats + 2) / 3;
+    std::vector<float4> cv(n_px);
+    WFPT_HIP(c, hipMemcpy(cv.data(), cv_dev, sizeof(float4) * n_px, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_floats; ++k) {
+        const float4 &v = cv[k / 3];
+        rgb[k] = k % 3 == 0 ? v.x : k % 3 == 1 ? v.y : v.z;
+    }
     return WFPT_OK;
 }
 
@@ -1810,14 +1867,7 @@ int wfpt_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, float *rgb, size_t n
         return WFPT_OK;
     }
     if (int r = enqueue_denoise(c, p, nullptr, 0); r != WFPT_OK) return r;
-    const size_t n_px = (n_floats + 2) / 3;
-    std::vector<float4> cv(n_px);
-    WFPT_HIP(c, hipMemcpy(cv.data(), c->dn_cv[p->iterations & 1u], sizeof(float4) * n_px, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_floats; ++k) {
-        const float4 &v = cv[k / 3];
-        rgb[k] = k % 3 == 0 ? v.x : k % 3 == 1 ? v.y : v.z;
-    }
-    return WFPT_OK;
+    return read_cv(c, c->dn_cv[p->iterations & 1u], rgb, n_floats);
 }
 
 int wfpt_denoise_to_device(wfpt_ctx *c, const wfpt_denoise_params *p, void *device_ptr, size_t n_bytes) {
@@ -1851,6 +1901,176 @@ int wfpt_denoise_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *calls) {
     if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: the context was created without WFPT_FLAG_DENOISE");
     if (ms_last) *ms_last = c->dn_ms;
     if (calls) *calls = c->dn_calls;
+    return WFPT_OK;
+}
+
+void wfpt_temporal_params_default(wfpt_temporal_params *p) {
+    if (!p) return;
+    *p = wfpt_temporal_params{};
+    wfpt_denoise_params_default(&p->spatial);
+    p->history_cap = 32.0f;     // chosen with tests/test_gpu_temporal.py's quality sweep
+    p->depth_tolerance = 0.05f; // SVGF-style rejection thresholds
+    p->normal_cos = 0.9f;
+}
+
+static int check_temporal(wfpt_ctx *c, const wfpt_temporal_params *p, const void *out, const char *who) {
+    if (!c || !p || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (int r = check_denoise(c, &p->spatial, out, who); r != WFPT_OK) return r;
+    bool reserved = false;
+    for (uint32_t r : p->_reserved) reserved = reserved || r != 0u;
+    if (!std::isfinite(p->history_cap) || !(p->history_cap >= 0.0f) || !std::isfinite(p->depth_tolerance) || !(p->depth_tolerance > 0.0f) ||
+        !(p->normal_cos >= -1.0f && p->normal_cos <= 1.0f) || reserved)
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": history_cap must be >= 0 and finite, depth_tolerance > 0 and finite, "
+                                                                      "normal_cos in [-1, 1], _reserved 0");
+    return WFPT_OK;
+}
+
+// M = inverse(inv_proj) inverse(view) in double, rounded to f32 (column-major 4x4, as mat_mul reads it)
+static bool invert4(const double *m, double *out) { // Gauss-Jordan with partial pivoting
+    double a[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) {
+            a[r][k] = m[k * 4 + r];
+            a[r][4 + k] = r == k ? 1.0 : 0.0;
+        }
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r)
+            if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
+        if (a[piv][col] == 0.0) return false;
+        if (piv != col)
+            for (int k = 0; k < 8; ++k) std::swap(a[col][k], a[piv][k]);
+        const double d = a[col][col];
+        for (int k = 0; k < 8; ++k) a[col][k] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = a[r][col];
+            for (int k = 0; k < 8; ++k) a[r][k] -= f * a[col][k];
+        }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int k = 0; k < 4; ++k) out[k * 4 + r] = a[r][4 + k];
+    return true;
+}
+
+static bool world_to_clip(const float inv_proj[16], const float view[16], float out[16]) {
+    double ip[16], vw[16], p[16], v[16];
+    for (int k = 0; k < 16; ++k) { ip[k] = inv_proj[k]; vw[k] = view[k]; }
+    if (!invert4(ip, p) || !invert4(vw, v)) return false;
+    for (int col = 0; col < 4; ++col)
+        for (int r = 0; r < 4; ++r) {
+            double acc = 0.0;
+            for (int k = 0; k < 4; ++k) acc += p[k * 4 + r] * v[col * 4 + k];
+            out[col * 4 + r] = static_cast<float>(acc);
+        }
+    return true;
+}
+
+static int temporal_call(wfpt_ctx *c, const wfpt_temporal_params *p, float *out, size_t out_floats) {
+    const size_t cap = c->pixel_capacity;
+    if (!c->tp_motion) {
+        for (auto &h : c->tp) {
+            WFPT_HIP(c, dmalloc(&h.s.cl, cap));
+            WFPT_HIP(c, dmalloc(&h.s.m, cap));
+            WFPT_HIP(c, dmalloc(&h.s.nz, cap));
+            WFPT_HIP(c, dmalloc(&h.s.cm, cap));
+        }
+        WFPT_HIP(c, dmalloc(&c->tp_motion, cap));
+    }
+    // seal: the live slot of another epoch becomes the sealed one (a pointer swap)
+    if (!c->tp[c->tp_live].valid || c->tp[c->tp_live].epoch != c->epoch) c->tp_live ^= 1;
+    wfpt_ctx::History &live = c->tp[c->tp_live];
+    const wfpt_ctx::History &sealed = c->tp[c->tp_live ^ 1];
+    TemporalArgs t{};
+    t.camera = c->camera;
+    t.has_sealed = sealed.valid && sealed.width == c->width && sealed.height == c->height &&
+                   world_to_clip(sealed.inv_proj, sealed.view, t.m) ? 1u : 0u;
+    std::memcpy(t.pos_s, sealed.pos, sizeof t.pos_s);
+    t.history_cap = p->history_cap;
+    t.depth_tolerance = p->depth_tolerance;
+    t.normal_cos = p->normal_cos;
+    t.sealed = sealed.s;
+    t.live = live.s;
+    t.motion = c->tp_motion;
+    live.valid = false; // until the launches below succeed
+    if (int r = enqueue_denoise(c, &p->spatial, out, out_floats, &t); r != WFPT_OK) return r;
+    live.valid = true;
+    live.epoch = c->epoch;
+    std::memcpy(live.pos, c->h_camera.position, sizeof live.pos);
+    std::memcpy(live.view, c->h_view, sizeof live.view);
+    std::memcpy(live.inv_proj, c->h_inv_proj, sizeof live.inv_proj);
+    live.width = c->width;
+    live.height = c->height;
+    c->tp_read_ok = true;
+    return WFPT_OK;
+}
+
+int wfpt_denoise_temporal(wfpt_ctx *c, const wfpt_temporal_params *p, float *rgb, size_t n_floats) {
+    if (int r = check_temporal(c, p, rgb, "wfpt_denoise_temporal"); r != WFPT_OK) return r;
+    if (n_floats > 3 * static_cast<size_t>(c->n_pixels)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_temporal: n_floats exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    if (c->accumulated_samples == 0) {
+        std::fill(rgb, rgb + n_floats, 0.0f);
+        return WFPT_OK;
+    }
+    if (int r = temporal_call(c, p, nullptr, 0); r != WFPT_OK) return r;
+    return read_cv(c, c->dn_cv[p->spatial.iterations & 1u], rgb, n_floats);
+}
+
+int wfpt_denoise_temporal_to_device(wfpt_ctx *c, const wfpt_temporal_params *p, void *device_ptr, size_t n_bytes) {
+    if (int r = check_temporal(c, p, device_ptr, "wfpt_denoise_temporal_to_device"); r != WFPT_OK) return r;
+    if (n_bytes > sizeof(float) * 3 * static_cast<size_t>(c->n_pixels))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_temporal_to_device: n_bytes exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    if (c->accumulated_samples == 0) {
+        WFPT_HIP(c, hipMemsetAsync(device_ptr, 0, n_bytes, c->stream));
+        WFPT_HIP(c, hipStreamSynchronize(c->stream));
+        return WFPT_OK;
+    }
+    return temporal_call(c, p, static_cast<float *>(device_ptr), n_bytes / sizeof(float));
+}
+
+int wfpt_read_temporal(wfpt_ctx *c, int which, float *out, size_t n_elems) {
+    if (!c || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: null argument");
+    if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: the context was created without WFPT_FLAG_DENOISE");
+    if (which < WFPT_TEMPORAL_COLOR || which > WFPT_TEMPORAL_MOTION) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: unknown output");
+    if (!c->tp_read_ok) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: no temporal call since the history was dropped");
+    const size_t ch = which == WFPT_TEMPORAL_COLOR || which == WFPT_TEMPORAL_MOTION ? 3u : which == WFPT_TEMPORAL_MOMENTS ? 2u : 1u;
+    if (n_elems > ch * c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: n_elems exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t n_px = (n_elems + ch - 1) / ch;
+    const TemporalSlot &s = c->tp[c->tp_live].s;
+    if (which == WFPT_TEMPORAL_MOMENTS) {
+        std::vector<float2> m(n_px);
+        WFPT_HIP(c, hipMemcpy(m.data(), s.m, sizeof(float2) * n_px, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < n_elems; ++k) out[k] = k % 2 == 0 ? m[k / 2].x : m[k / 2].y;
+        return WFPT_OK;
+    }
+    std::vector<float4> v(n_px);
+    WFPT_HIP(c, hipMemcpy(v.data(), which == WFPT_TEMPORAL_MOTION ? c->tp_motion : s.cl, sizeof(float4) * n_px, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_elems; ++k) {
+        if (which == WFPT_TEMPORAL_LENGTH) {
+            out[k] = v[k].w;
+            continue;
+        }
+        const float4 &e = v[k / 3];
+        out[k] = k % 3 == 0 ? e.x : k % 3 == 1 ? e.y : e.z;
+    }
+    return WFPT_OK;
+}
+
+int wfpt_reset_history(wfpt_ctx *c) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
+    drop_history(c);
+    return WFPT_OK;
+}
+
+int wfpt_temporal_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *calls) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_temporal_timing_ms: null context");
+    if (!c->moments) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_temporal_timing_ms: the context was created without WFPT_FLAG_DENOISE");
+    if (ms_last) *ms_last = c->tp_ms;
+    if (calls) *calls = c->tp_calls;
     return WFPT_OK;
 }
 

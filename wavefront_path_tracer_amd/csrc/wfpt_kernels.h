@@ -468,6 +468,26 @@ struct DenoiseArgs {
 };
 constexpr uint32_t kDenoiseTile = 16; // a workgroup = 16 x 16 pixels, each of its four waves an 8 x 8 block
 
+// ---- temporal denoiser (include/wfpt.h "Temporal denoiser"). A history slot: four SoA planes of `plane` pixels.
+struct TemporalSlot {
+    float4 *cl;  // (blended colour, history length L)
+    float2 *m;   // per-sample moments (m1, m2)
+    float4 *nz;  // (normalised normal, depth) as prepare makes them
+    float2 *cm;  // (coverage, material id as its u32 bits)
+};
+constexpr float kNoMotion = -1e30f; // x', y' of a pixel without a projection
+// temporal_prepare_kernel's launch beside the DenoiseArgs of the chain (cv_out, guides, out as prepare's)
+struct TemporalArgs {
+    const CameraDev *camera; // the current camera (the context's device copy)
+    float m[16];             // world -> clip of the sealed camera, column-major (mat_mul's layout)
+    float pos_s[3];          // the sealed camera's position
+    uint32_t has_sealed;     // 0: no projection at all (first call, dropped history, another viewport)
+    float history_cap, depth_tolerance, normal_cos;
+    TemporalSlot sealed;     // read
+    TemporalSlot live;       // written
+    float4 *motion;          // (x', y', z', 0)
+};
+
 hipError_t launch_generate(const GenerateArgs &a, hipStream_t s);
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per sample
@@ -502,6 +522,7 @@ hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, u
 hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, size_t plane, uint32_t grid, hipStream_t s);
 hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s);
+hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, hipStream_t s);
 hipError_t launch_selftest_math(int op, const float *a, const float *b, float *out, size_t n, hipStream_t s);
 // Occupancy of the extend kernel for a given dynamic LDS size (workgroups per CU); also raises the
 // kernel's dynamic-LDS limit when the scene needs more than the default 64 KiB.

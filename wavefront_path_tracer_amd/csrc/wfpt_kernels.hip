@@ -3143,16 +3143,20 @@ __device__ inline bool denoise_pixel(const DenoiseArgs &a, uint32_t &x, uint32_t
     return x < a.width && y < a.height;
 }
 
-// Guides and pass 0's (c, v) from the read-back values (the resolve functions wfpt_read_accumulated / _aov / _variance share, so every
-// input is bit-equal to what the host reads).
-__global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a) {
-    uint32_t x, y;
-    if (!denoise_pixel(a, x, y)) return;
+// Prepare's values of one pixel from the read-back values (the resolve functions wfpt_read_accumulated / _aov / _variance share, so every
+// input is bit-equal to what the host reads): shared by denoise_prepare_kernel and temporal_prepare_kernel.
+struct PreparedPixel {
+    float cr, cg, cb, v;       // pass 0's (c, v)
+    float nx, ny, nz, z;       // guide_nz
+    float ar, ag, ab, grad;    // guide_ag
+};
+__device__ inline PreparedPixel denoise_prepare_pixel(const DenoiseArgs &a, uint32_t x, uint32_t y) {
     const size_t w = a.width, p = y * w + x, plane = a.plane;
     const float nf = static_cast<float>(a.n);
     auto word = [&](uint32_t which, size_t k) { return __uint_as_float(aov_resolve_word(a.aov_sums, plane, which, k, a.n)); };
     auto luma_of = [&](size_t q) { return denoise_luma(a.accumulated[3u * q] / nf, a.accumulated[3u * q + 1u] / nf, a.accumulated[3u * q + 2u] / nf); };
-    const float cr = a.accumulated[3u * p] / nf, cg = a.accumulated[3u * p + 1u] / nf, cb = a.accumulated[3u * p + 2u] / nf;
+    PreparedPixel o;
+    o.cr = a.accumulated[3u * p] / nf; o.cg = a.accumulated[3u * p + 1u] / nf; o.cb = a.accumulated[3u * p + 2u] / nf;
     float nx = word(WFPT_AOV_NORMAL, 3u * p), ny = word(WFPT_AOV_NORMAL, 3u * p + 1u), nz = word(WFPT_AOV_NORMAL, 3u * p + 2u);
     const float dot = (nx * nx + ny * ny) + nz * nz;
     if (dot != 0.0f) {
@@ -3168,10 +3172,9 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a) {
     if (x + 1u < a.width) { const float d = fabsf(word(WFPT_AOV_DEPTH, p + 1u) - z); gx = x > 0u ? fminf(gx, d) : d; }
     if (y > 0u) gy = fabsf(word(WFPT_AOV_DEPTH, p - w) - z);
     if (y + 1u < a.height) { const float d = fabsf(word(WFPT_AOV_DEPTH, p + w) - z); gy = y > 0u ? fminf(gy, d) : d; }
-    const float grad = sqrtf(gx * gx + gy * gy);
-    float v;
+    o.grad = sqrtf(gx * gx + gy * gy);
     if (a.n >= 4u) {
-        v = variance_resolve(a.moments[p], a.moments[plane + p], a.n);
+        o.v = variance_resolve(a.moments[p], a.moments[plane + p], a.n);
     } else { // short history: the population variance of L(c) over the 7x7 window, clipped to the image
         float s1 = 0.0f, s2 = 0.0f, m = 0.0f;
         for (int dy = -3; dy <= 3; ++dy) {
@@ -3186,16 +3189,127 @@ __global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a) {
         }
         const float mu = s1 / m;
         const float d = s2 / m - mu * mu;
-        v = d > 0.0f ? d : 0.0f;
+        o.v = d > 0.0f ? d : 0.0f;
     }
-    a.guide_nz[p] = make_float4(nx, ny, nz, z);
-    a.guide_ag[p] = make_float4(word(WFPT_AOV_ALBEDO, 3u * p), word(WFPT_AOV_ALBEDO, 3u * p + 1u), word(WFPT_AOV_ALBEDO, 3u * p + 2u), grad);
+    o.nx = nx; o.ny = ny; o.nz = nz; o.z = z;
+    o.ar = word(WFPT_AOV_ALBEDO, 3u * p); o.ag = word(WFPT_AOV_ALBEDO, 3u * p + 1u); o.ab = word(WFPT_AOV_ALBEDO, 3u * p + 2u);
+    return o;
+}
+
+// Writes pass 0's input, the guides and (a.out) the caller's copy of c for pixel p.
+__device__ inline void denoise_prepare_store(const DenoiseArgs &a, size_t p, const PreparedPixel &o, float cr, float cg, float cb, float v) {
+    a.guide_nz[p] = make_float4(o.nx, o.ny, o.nz, o.z);
+    a.guide_ag[p] = make_float4(o.ar, o.ag, o.ab, o.grad);
     a.cv_out[p] = make_float4(cr, cg, cb, v);
     if (a.out) {
         if (3u * p < a.out_floats) a.out[3u * p] = cr;
         if (3u * p + 1u < a.out_floats) a.out[3u * p + 1u] = cg;
         if (3u * p + 2u < a.out_floats) a.out[3u * p + 2u] = cb;
     }
+}
+
+// Guides and pass 0's (c, v).
+__global__ __launch_bounds__(256) void denoise_prepare_kernel(DenoiseArgs a) {
+    uint32_t x, y;
+    if (!denoise_pixel(a, x, y)) return;
+    const PreparedPixel o = denoise_prepare_pixel(a, x, y);
+    denoise_prepare_store(a, static_cast<size_t>(y) * a.width + x, o, o.cr, o.cg, o.cb, o.v);
+}
+
+// The temporal head of the chain (include/wfpt.h "Temporal denoiser"), in place of denoise_prepare_kernel: prepare's pixel, its centre ray
+// reprojected into the sealed camera, up to four bilinear taps of the sealed history accepted by coverage / material / depth / normal, and
+// the count-weighted blend. Every sum runs in tap order; no atomics. The taps of a near-identity reprojection are the pixel's own and its
+// neighbours' 16 / 8-byte elements, which the wave's neighbours load too: L2 serves them, no LDS staging.
+__global__ __launch_bounds__(256) void temporal_prepare_kernel(DenoiseArgs a, TemporalArgs t) {
+    uint32_t x, y;
+    if (!denoise_pixel(a, x, y)) return;
+    const size_t w = a.width, p = static_cast<size_t>(y) * w + x, plane = a.plane;
+    const PreparedPixel o = denoise_prepare_pixel(a, x, y);
+    const float nf = static_cast<float>(a.n);
+    const float cov = __uint_as_float(aov_resolve_word(a.aov_sums, plane, WFPT_AOV_COVERAGE, p, a.n));
+    const uint32_t mat = aov_resolve_word(a.aov_sums, plane, WFPT_AOV_MATERIAL_ID, p, a.n);
+    const bool hit = cov > 0.0f;
+    float mx = kNoMotion, my = kNoMotion, mz = 0.0f;
+    float wsum = 0.0f, hr = 0.0f, hg = 0.0f, hb = 0.0f, hl = 0.0f, hm1 = 0.0f, hm2 = 0.0f;
+    if (t.has_sealed) {
+        // the centre ray: primary_ray with the jitter (0, 0) and without the lens, from the camera position
+        const CameraDev &cam = *t.camera;
+        float ndc_x = static_cast<float>(x) / static_cast<float>(a.width);
+        float ndc_y = 1.0f - static_cast<float>(y) / static_cast<float>(a.height);
+        ndc_x = 2.0f * ndc_x - 1.0f;
+        ndc_y = 2.0f * ndc_y - 1.0f;
+        float4_ pp = mat_mul(cam.inv_proj, {ndc_x, ndc_y, 1.0f, 1.0f});
+        const float pw = pp.w;
+        pp = {pp.x / pw, pp.y / pw, pp.z / pw, pp.w / pw};
+        const float4_ rd = mat_mul(cam.view, {pp.x, pp.y, pp.z, 0.0f});
+        const float inv_len = 1.0f / sqrt_(((rd.x * rd.x + rd.y * rd.y) + rd.z * rd.z) + rd.w * rd.w);
+        const float dx = rd.x * inv_len, dy = rd.y * inv_len, dz = rd.z * inv_len;
+        const float4_ X = hit ? float4_{cam.cam.position[0] + o.z * dx, cam.cam.position[1] + o.z * dy, cam.cam.position[2] + o.z * dz, 1.0f}
+                              : float4_{dx, dy, dz, 0.0f};
+        const float4_ q = mat_mul(t.m, X);
+        if (q.w > 0.0f) {
+            mx = ((q.x / q.w + 1.0f) * 0.5f) * static_cast<float>(a.width);
+            my = (1.0f - (q.y / q.w + 1.0f) * 0.5f) * static_cast<float>(a.height);
+            if (hit) {
+                const float ex = X.x - t.pos_s[0], ey = X.y - t.pos_s[1], ez = X.z - t.pos_s[2];
+                mz = sqrtf((ex * ex + ey * ey) + ez * ez);
+            }
+            const float fx0 = floorf(mx), fy0 = floorf(my);
+            // taps exist only for x0 in [-1, W) and y0 in [-1, H): this also keeps the int conversion in range (and drops NaN)
+            if (fx0 >= -1.0f && fx0 < static_cast<float>(a.width) && fy0 >= -1.0f && fy0 < static_cast<float>(a.height)) {
+                const float fx = mx - fx0, fy = my - fy0;
+                const int x0 = static_cast<int>(fx0), y0 = static_cast<int>(fy0);
+                const float wt[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int xt = x0 + (k & 1), yt = y0 + (k >> 1);
+                    if (xt < 0 || xt >= static_cast<int>(a.width) || yt < 0 || yt >= static_cast<int>(a.height)) continue;
+                    const size_t q_ = static_cast<size_t>(yt) * w + static_cast<size_t>(xt);
+                    const float2 cm = t.sealed.cm[q_];
+                    bool ok;
+                    if (hit) {
+                        ok = cm.x > 0.0f && __float_as_uint(cm.y) == mat;
+                        if (ok) {
+                            const float4 nzt = t.sealed.nz[q_];
+                            ok = fabsf(nzt.w - mz) <= t.depth_tolerance * mz &&
+                                 ((o.nx * nzt.x + o.ny * nzt.y) + o.nz * nzt.z) >= t.normal_cos;
+                        }
+                    } else {
+                        ok = cm.x == 0.0f;
+                    }
+                    if (!ok) continue;
+                    const float4 cl = t.sealed.cl[q_];
+                    const float2 mm = t.sealed.m[q_];
+                    wsum += wt[k];
+                    hr += wt[k] * cl.x; hg += wt[k] * cl.y; hb += wt[k] * cl.z; hl += wt[k] * cl.w;
+                    hm1 += wt[k] * mm.x; hm2 += wt[k] * mm.y;
+                }
+            }
+        }
+    }
+    const float s1 = a.moments[p], s2 = a.moments[plane + p];
+    float cr = o.cr, cg = o.cg, cb = o.cb, v = o.v, len = nf, m1 = s1 / nf, m2 = s2 / nf;
+    if (wsum >= 0.01f && t.history_cap > 0.0f) {
+        const float h = fminf(hl / wsum, t.history_cap);
+        len = h + nf;
+        cr = (h * (hr / wsum) + a.accumulated[3u * p]) / len;
+        cg = (h * (hg / wsum) + a.accumulated[3u * p + 1u]) / len;
+        cb = (h * (hb / wsum) + a.accumulated[3u * p + 2u]) / len;
+        m1 = (h * (hm1 / wsum) + s1) / len;
+        m2 = (h * (hm2 / wsum) + s2) / len;
+        if (len < 4.0f) {
+            v = o.v * (nf / len); // o.v is prepare's 7x7 variance here (L < 4 means n < 4)
+        } else {
+            const float d = m2 - m1 * m1;
+            v = (d > 0.0f ? d : 0.0f) / len;
+        }
+    }
+    denoise_prepare_store(a, p, o, cr, cg, cb, v);
+    t.live.cl[p] = make_float4(cr, cg, cb, len);
+    t.live.m[p] = make_float2(m1, m2);
+    t.live.nz[p] = make_float4(o.nx, o.ny, o.nz, o.z);
+    t.live.cm[p] = make_float2(cov, __uint_as_float(mat));
+    t.motion[p] = make_float4(mx, my, mz, 0.0f);
 }
 
 // One a-trous pass at step a.step: the 5x5 taps p + step (dx, dy), dy outer, dx inner, taps outside the image skipped. The taps come from
@@ -3593,6 +3707,12 @@ hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s) {
 hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s) {
     if (a.width == 0 || a.height == 0) return hipSuccess;
     hipLaunchKernelGGL(denoise_atrous_kernel, denoise_grid(a), dim3(kDenoiseTile * kDenoiseTile), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, hipStream_t s) {
+    if (a.width == 0 || a.height == 0) return hipSuccess;
+    hipLaunchKernelGGL(temporal_prepare_kernel, denoise_grid(a), dim3(kDenoiseTile * kDenoiseTile), 0, s, a, t);
     return hipGetLastError();
 }
 
