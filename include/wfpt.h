@@ -211,9 +211,12 @@ enum {
     WFPT_FLAG_AOV = 1u << 10,        /* first-hit feature buffers (AOVs) for denoisers, see "AOVs" below: every sample wfpt_render* renders
                                         also traces its primary ray once more (aov_kernel) and adds the first hit's albedo, normal and
                                         depth to per-pixel sums. Without the flag nothing is allocated or launched. */
-    WFPT_FLAG_DENOISE = 1u << 11     /* the on-device denoiser, see "Denoiser" below: implies WFPT_FLAG_AOV, and every rendered batch also adds
+    WFPT_FLAG_DENOISE = 1u << 11,    /* the on-device denoiser, see "Denoiser" below: implies WFPT_FLAG_AOV, and every rendered batch also adds
                                         each sample's luminance and its square to per-pixel moments (accumulate_moments_kernel in place
                                         of accumulate_kernel). Without the flag nothing is allocated or launched. */
+    WFPT_FLAG_ENVIRONMENT = 1u << 12 /* misses lit by an HDR environment map, see "Environment map" below: the miss queues carry the full
+                                        direction (two more planes). Without a map set the context renders the gradient sky, bit for bit;
+                                        without the flag nothing is allocated or launched. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -561,6 +564,41 @@ int wfpt_reset_history(wfpt_ctx *ctx);
 /* time of the last temporal call's launches and the number of calls since wfpt_create; either pointer may be NULL */
 int wfpt_temporal_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *calls);
 
+/* ------------------------------------------------------------------ Environment map (WFPT_FLAG_ENVIRONMENT): image-based lighting of misses
+ * With a map set, every miss that miss_kernel would colour with the gradient sky (image[pixel] *= sky(d)) is multiplied by the map's value
+ * in its direction d instead, per channel: thr.r * c.r, thr.g * c.g, thr.b * c.b. The lookup (wfpt_device_math.h env_lookup), IEEE f32
+ * add / sub / mul / div / sqrt, comparisons and floor only, no fma:
+ *   n = normalize3(d);  phi = atan2_(n.x, -n.z);  theta = atan2_(sqrt(n.x n.x + n.z n.z), n.y)
+ *   u = phi / 2pi + (0.5 + rotation), u <- u - floor(u);  v = theta / pi      (row 0 of the map = +y, column w/2 faces -z)
+ *   x = u w - 0.5, x0 = floor(x), fx = x - x0 (the same for y); columns wrap modulo w, rows clamp to [0, h - 1]
+ *   c = (((t00 (1-fx)(1-fy) + t10 fx (1-fy)) + t01 (1-fx) fy) + t11 fx fy) * intensity
+ * atan2_ is the library's own (Cephes atanf with a fixed operation order, within 2 ulp; wfpt_selftest_math op 8). A context with
+ * WFPT_FLAG_AOV adds the map's value of the primary direction to the albedo sum of a primary miss, in place of the sky colour.
+ * wfpt_set_environment and wfpt_clear_environment act like a scene update: the accumulation and the frame counter restart, the temporal
+ * history is dropped, and so are the captured graphs. wfpt_update_scene* and viewport changes keep the map. A refused call leaves the
+ * context as it was, its map included. WFPT_ERR_INVALID_ARGUMENT without the flag and for a bad size, texel or parameter; WFPT_ERR_UNSUPPORTED
+ * while wfpt_loop_kind_of reports WFPT_LOOP_FUSED_BINNED (the opt-in class-binned loop measures level with the default one and is not
+ * extended: WFPT_FLAG_BINNING contexts keep the gradient sky). Out of scope: wfpt_render_chunked* (the flag is masked off there), importance
+ * sampling of the map and next-event estimation (this chain traces no shadow rays). */
+typedef struct wfpt_environment_params {
+    float intensity;        /* >= 0, finite: multiplies every texel */
+    float rotation;         /* in [0, 1): turns added to u (the map turns about +y) */
+    uint32_t _reserved[6];  /* must be 0 */
+} wfpt_environment_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_environment_params) == 32 && offsetof(wfpt_environment_params, rotation) == 4 &&
+                       offsetof(wfpt_environment_params, _reserved) == 8,
+                   "wfpt_environment_params: 32 bytes");
+/* intensity 1, rotation 0, _reserved zeroed */
+void wfpt_environment_params_default(wfpt_environment_params *p);
+/* rgb: h rows of w texels, 3 floats each (row-major, row 0 = up), finite and >= 0; 1 <= w <= 16384, 1 <= h <= 8192. Stored on the device
+ * as float4 texels; replaces any earlier map. p may be NULL (the defaults). Blocking. */
+int wfpt_set_environment(wfpt_ctx *ctx, const float *rgb, uint32_t w, uint32_t h, const wfpt_environment_params *p);
+/* back to the gradient sky */
+int wfpt_clear_environment(wfpt_ctx *ctx);
+/* the lookup above on the device for n caller directions (xyz, 3 floats each) into rgb_out (3 floats each); WFPT_ERR_INVALID_ARGUMENT when
+ * no map is set. Blocking. */
+int wfpt_sample_environment(wfpt_ctx *ctx, const float *dirs, size_t n, float *rgb_out);
+
 /* ------------------------------------------------------------------ read-back (blocking) */
 
 uint32_t wfpt_n_pixels(const wfpt_ctx *ctx);  /* pixels held by this context (whole 8-row bands when sharded) */
@@ -627,7 +665,7 @@ int wfpt_write_png_rgb8(const char *path, const uint8_t *rgb, uint32_t width, ui
 
 /* ------------------------------------------------------------------ diagnostics */
 /* Runs the device math primitives over arrays (op: 0 sqrt(a), 1 a/b, 2 sin(a), 3 cos(a), 4 pow(a,b),
- * 5 f32(u32 bits of a)*2^-32, 6 min(a,b), 7 max(a,b)); used by the parity tests to prove the device
+ * 5 f32(u32 bits of a)*2^-32, 6 min(a,b), 7 max(a,b), 8 atan2_(a, b)); used by the parity tests to prove the device
  * arithmetic matches the oracle's bit for bit. */
 int wfpt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n);
 /* Workgroups of the extend kernel that fit one CU when each declares `lds_bytes` of dynamic LDS (occupancy query;

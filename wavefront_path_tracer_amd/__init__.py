@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -34,6 +34,7 @@ RNG_DISPATCH, RNG_PIXEL = 0, 1
 LOOP_KINDS = ("stages", "fused", "fused_binned", "refill")  # wfpt_loop_kind
 FLAG_SPLIT_SHADE, FLAG_NO_GRAPH, FLAG_UNFUSED, FLAG_BINARY_BVH, FLAG_NO_REFILL, FLAG_NO_LDS_SCENE, FLAG_EXACT_TRAVERSAL, FLAG_NO_BINNING, FLAG_BINNING = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_AOV = 1 << 10  # first-hit AOVs (include/wfpt.h "AOVs"); bit 9 is the retired WFPT_FLAG_TWO_CHAINS
+FLAG_ENVIRONMENT = 1 << 12  # misses lit by an HDR environment map (include/wfpt.h "Environment map")
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -89,6 +90,10 @@ class _Params(C.Structure):
 class _DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
                 ("sigma_albedo", C.c_float), ("_reserved", C.c_uint32 * 3)]
+
+
+class _EnvironmentParams(C.Structure):
+    _fields_ = [("intensity", C.c_float), ("rotation", C.c_float), ("_reserved", C.c_uint32 * 6)]
 
 
 class _TemporalParams(C.Structure):
@@ -314,6 +319,10 @@ def lib():
         "wfpt_read_temporal": (i32, [vp, i32, vp, sz]),
         "wfpt_reset_history": (i32, [vp]),
         "wfpt_temporal_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_environment_params_default": (None, [C.POINTER(_EnvironmentParams)]),
+        "wfpt_set_environment": (i32, [vp, vp, u32, u32, C.POINTER(_EnvironmentParams)]),
+        "wfpt_clear_environment": (i32, [vp]),
+        "wfpt_sample_environment": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -384,6 +393,78 @@ def write_png(path, rgb8, width, height):
     st = lib().wfpt_write_png_rgb8(os.fsencode(path), _p(a), width, height)
     if st != 0:
         raise WfptError(st, f"cannot write {path}")
+
+
+def load_environment(path):
+    """An HDR environment map as an (h, w, 3) float32 array, row 0 = top: Radiance .hdr (RGBE, "-Y h +X w", flat or new-style RLE
+    scanlines) or .pfm (colour "PF", either byte order; PFM stores rows bottom-up)."""
+    data = open(path, "rb").read()
+    if data[:2] in (b"PF", b"Pf"):
+        return _read_pfm(data)
+    if data[:2] == b"#?":
+        return _read_hdr(data)
+    raise ValueError(f"load_environment: {path} is neither a Radiance .hdr nor a .pfm file")
+
+
+def _read_pfm(data):
+    fields, pos = [], 0
+    while len(fields) < 4:  # "PF", width, height, scale, separated by whitespace
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        end = pos
+        while not data[end:end + 1].isspace():
+            end += 1
+        fields.append(data[pos:end].decode("ascii"))
+        pos = end
+    pos += 1  # the single whitespace character before the raster
+    if fields[0] != "PF":
+        raise ValueError("load_environment: only colour PFM (PF) maps are supported")
+    w, h, scale = int(fields[1]), int(fields[2]), float(fields[3])
+    a = np.frombuffer(data, "<f4" if scale < 0 else ">f4", count=w * h * 3, offset=pos)
+    return np.ascontiguousarray(a.reshape(h, w, 3)[::-1].astype("<f4"))
+
+
+def _read_hdr(data):
+    pos = 0
+    while True:  # header lines up to the empty one
+        end = data.index(b"\n", pos)
+        line = data[pos:end].strip()
+        pos = end + 1
+        if not line:
+            break
+        if line.startswith(b"FORMAT=") and line != b"FORMAT=32-bit_rle_rgbe":
+            raise ValueError(f"load_environment: unsupported .hdr format {line!r}")
+    end = data.index(b"\n", pos)
+    res = data[pos:end].split()
+    pos = end + 1
+    if len(res) != 4 or res[0] != b"-Y" or res[2] != b"+X":
+        raise ValueError(f"load_environment: only '-Y h +X w' .hdr maps are supported, not {data[pos:end]!r}")
+    h, w = int(res[1]), int(res[3])
+    buf = np.frombuffer(data, np.uint8, offset=pos)
+    rgbe = np.zeros((h, w, 4), np.uint8)
+    i = 0
+    for y in range(h):
+        if 8 <= w < 32768 and buf[i] == 2 and buf[i + 1] == 2 and (int(buf[i + 2]) << 8 | int(buf[i + 3])) == w and not buf[i + 2] & 0x80:
+            i += 4  # new-style RLE: four channel runs, each packed as (count > 128: a run of count - 128 copies | count: literals)
+            for ch in range(4):
+                x = 0
+                while x < w:
+                    n = int(buf[i])
+                    i += 1
+                    if n > 128:
+                        n -= 128
+                        rgbe[y, x:x + n, ch] = buf[i]
+                        i += 1
+                    else:
+                        rgbe[y, x:x + n, ch] = buf[i:i + n]
+                        i += n
+                    x += n
+        else:  # flat scanline
+            rgbe[y] = buf[i:i + 4 * w].reshape(w, 4)
+            i += 4 * w
+    e = rgbe[..., 3].astype(np.int32)
+    scale = np.where(e > 0, np.ldexp(1.0, e - 136), 0.0)  # mantissa / 256 * 2^(e - 128)
+    return (rgbe[..., :3].astype(np.float64) * scale[..., None]).astype("<f4")
 
 
 def selftest_math(op, a, b=None, device=0):
@@ -1053,6 +1134,27 @@ class PathTracer:
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_temporal_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
+
+    # ---- environment map (contexts created with FLAG_ENVIRONMENT; include/wfpt.h "Environment map")
+    def set_environment(self, rgb, intensity=1.0, rotation=0.0):
+        """Lights every miss with the map `rgb`, an (h, w, 3) float32 array (row 0 = up, column w/2 faces -z; finite, >= 0), times
+        `intensity`, turned by `rotation` (in turns, [0, 1)). Restarts the accumulation like a scene update."""
+        a = np.ascontiguousarray(rgb, "<f4")
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"set_environment: expected an (h, w, 3) array, got shape {a.shape}")
+        p = _EnvironmentParams(float(intensity), float(rotation))
+        self._check(lib().wfpt_set_environment(self.handle, _p(a), a.shape[1], a.shape[0], C.byref(p)))
+
+    def clear_environment(self):
+        """Back to the gradient sky (restarts the accumulation)."""
+        self._check(lib().wfpt_clear_environment(self.handle))
+
+    def sample_environment(self, dirs):
+        """(n, 3) float32: the map's value (with its intensity) in each of the (n, 3) directions, looked up on the device."""
+        d = np.ascontiguousarray(dirs, "<f4").reshape(-1, 3)
+        out = np.zeros_like(d)
+        self._check(lib().wfpt_sample_environment(self.handle, _p(d), d.shape[0], _p(out)))
+        return out
 
     # ---- read-back
     def accumulated(self):

@@ -18,7 +18,7 @@
 namespace wfpt {
 
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ float sqrt_(float x) { return __builtin_sqrtf(x); }
+__host__ __device__ __forceinline__ float sqrt_(float x) { return __builtin_sqrtf(x); }
 // minNum / maxNum (v_min_f32 / v_max_f32): a NaN operand yields the other operand
 __device__ __forceinline__ float min_(float a, float b) { return __builtin_fminf(a, b); }
 __device__ __forceinline__ float max_(float a, float b) { return __builtin_fmaxf(a, b); }
@@ -124,13 +124,75 @@ __device__ __forceinline__ float pow_(float x, float y) { // sh:120 (y = 0.33333
 
 // ---------------- small vectors: fixed association order, no contraction ----------------
 struct float3_ { float x, y, z; };
-__device__ __forceinline__ float dot3(float3_ a, float3_ b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__host__ __device__ __forceinline__ float dot3(float3_ a, float3_ b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 // WGSL normalize(v): the built-in's accuracy is that of v / length(v) (2.5 ULP per component); the definition fixed here since round 4
 // is v * (1 / length(v)): one IEEE division and three products instead of three divisions (a correctly rounded division is ~11
 // instructions, most of them half rate), at most 1.5 ULP from the quotient form. Rounds 1-3 divided each component.
-__device__ __forceinline__ float3_ normalize3(float3_ a) {
+__host__ __device__ __forceinline__ float3_ normalize3(float3_ a) {
     const float inv = 1.0f / sqrt_(dot3(a, a));
     return {a.x * inv, a.y * inv, a.z * inv};
+}
+
+// ---------------- environment map (WFPT_FLAG_ENVIRONMENT; include/wfpt.h "Environment map") ----------------
+// Only IEEE f32 add / sub / mul / div / sqrt, comparisons, selects and floor, no fma: numpy float32 restates every step bit for bit
+// (tests/environment_ref.py).
+//
+// atan2_(y, x): a Cephes atanf (Moshier) polynomial on a reduced ratio of lo = min(|x|, |y|) and hi = max(|x|, |y|), then the octant and
+// quadrant fix-ups. Constants that are not floats are carried as hi + lo pairs:
+//   t = lo / hi (0 when hi == 0);  r = t, base = 0            when t <= tan(pi/8)
+//                                  r = (2 lo - hi) / (2 hi + lo), base = atan(1/2)   otherwise (the ratio's exact difference form of
+//                                  (t - 1/2) / (1 + t/2): 2 lo - hi is exact there, so r carries two roundings, not four)
+//   z = r r;  p = (((c3 z - c2) z + c1) z - c0) z;  a = base_hi + (base_lo + (p r + r))    (a = p r + r when base = 0)
+//   |y| > |x|:  a <- pi/2_hi + (pi/2_lo - a);    x < 0:  a <- pi_hi + (pi_lo - a);    y < 0:  a <- -a
+// The signs are read by comparisons, so a zero of either sign counts as positive: atan2_(+-0, +-0) = 0, atan2_(+-0, x < 0) = pi,
+// atan2_(+-0, x > 0) = 0, atan2_(y > 0, +-0) = pi/2, atan2_(y < 0, +-0) = -pi/2. Finite inputs below 2^126 in magnitude are within 2 ulp of
+// the true atan2 (1.8 measured; tests/test_environment_host.py).
+__host__ __device__ __forceinline__ float atan2_(float y, float x) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const float hi = ax > ay ? ax : ay, lo = ax > ay ? ay : ax;
+    const float t = hi > 0.0f ? lo / hi : 0.0f;
+    const bool big = t > 0.41421356f;
+    const float r = big ? (2.0f * lo - hi) / (2.0f * hi + lo) : t;
+    const float z = r * r;
+    const float p = (((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f) * z;
+    float a = p * r + r;
+    if (big) a = 4.636476040e-01f + (5.012158688e-09f + a);
+    if (ay > ax) a = 1.570796371e+00f + (-4.371138829e-08f - a);
+    if (x < 0.0f) a = 3.141592741e+00f + (-8.742277657e-08f - a);
+    return y < 0.0f ? -a : a;
+}
+
+// The map's value in direction d (not necessarily unit length): a w x h equirectangular map of float4 texels (rgb, unused), row 0 = +y,
+// column w/2 faces -z, `rotation` in turns added to u, bilinear with texel centres at half-integers, columns wrapping and rows clamped.
+//   n = normalize3(d);  phi = atan2_(n.x, -n.z);  theta = atan2_(sqrt(n.x n.x + n.z n.z), n.y)
+//   u = phi / 2pi + (0.5 + rotation), u <- u - floor(u);  v = theta / pi
+//   x = u w - 0.5, x0 = floor(x), fx = x - x0 (the same for y); column x0 mod w and x0 + 1 mod w, rows clamp(y0), clamp(y0 + 1)
+//   c = (((t00 (1-fx)(1-fy) + t10 fx (1-fy)) + t01 (1-fx) fy) + t11 fx fy) * intensity      (each weight one product)
+// x0 and y0 are clamped to the map (as floats) before they become indices: a NaN direction reads texel 0 and yields NaN, never an address
+// outside the map.
+__host__ __device__ __forceinline__ float3_ env_lookup(const float4 *tex, uint32_t w, uint32_t h, float intensity, float rotation, float dx,
+                                                       float dy, float dz) {
+    const float3_ n = normalize3({dx, dy, dz});
+    const float phi = atan2_(n.x, -n.z);
+    const float theta = atan2_(sqrt_(n.x * n.x + n.z * n.z), n.y);
+    float u = phi * 0.15915494f + (0.5f + rotation);
+    u = u - __builtin_floorf(u);
+    const float v = theta * 0.31830988f;
+    const float fw = static_cast<float>(w), fh = static_cast<float>(h);
+    const float x = u * fw - 0.5f, y = v * fh - 0.5f;
+    const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    const int i0 = static_cast<int>(__builtin_fminf(__builtin_fmaxf(x0, -1.0f), fw - 1.0f)); // -1 .. w-1
+    const uint32_t c0 = i0 < 0 ? w - 1u : static_cast<uint32_t>(i0);
+    const uint32_t c1 = static_cast<uint32_t>(i0 + 1) >= w ? 0u : static_cast<uint32_t>(i0 + 1);
+    const size_t r0 = static_cast<size_t>(__builtin_fminf(__builtin_fmaxf(y0, 0.0f), fh - 1.0f)) * w;
+    const size_t r1 = static_cast<size_t>(__builtin_fminf(__builtin_fmaxf(y0 + 1.0f, 0.0f), fh - 1.0f)) * w;
+    const float4 t00 = tex[r0 + c0], t10 = tex[r0 + c1], t01 = tex[r1 + c0], t11 = tex[r1 + c1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+    return {(((t00.x * w00 + t10.x * w10) + t01.x * w01) + t11.x * w11) * intensity,
+            (((t00.y * w00 + t10.y * w10) + t01.y * w01) + t11.y * w11) * intensity,
+            (((t00.z * w00 + t10.z * w10) + t01.z * w01) + t11.z * w11) * intensity};
 }
 
 } // namespace wfpt

@@ -62,12 +62,25 @@ struct HitQueue {
     __host__ __device__ uint32_t *prim() const { return base + static_cast<size_t>(plane); }
     __host__ __device__ uint32_t *ridx() const { return base + 2u * static_cast<size_t>(plane); }
 };
+// WFPT_FLAG_ENVIRONMENT contexts allocate two more planes, direction.x and direction.z (the map is looked up in the full direction); the
+// environment variants of the kernels write and read them, the others never touch them.
 struct MissQueue {
     uint32_t *base;
     Stride32 plane;
     __host__ __device__ uint32_t *ridx() const { return base; }
     __host__ __device__ float *dy() const { return reinterpret_cast<float *>(base + static_cast<size_t>(plane)); }
     __host__ __device__ uint32_t *pixel() const { return base + 2u * static_cast<size_t>(plane); }
+    __host__ __device__ float *dx() const { return reinterpret_cast<float *>(base + 3u * static_cast<size_t>(plane)); }
+    __host__ __device__ float *dz() const { return reinterpret_cast<float *>(base + 4u * static_cast<size_t>(plane)); }
+};
+constexpr uint32_t kMissPlanes = 3, kMissPlanesEnv = 5;
+
+// The environment map a miss is lit by (WFPT_FLAG_ENVIRONMENT, include/wfpt.h "Environment map"): w x h float4 texels (rgb, 0), row 0 = +y.
+// Passed by value as the last argument of the environment variants of the kernels (a captured graph bakes it in: setting a map drops them).
+struct EnvDev {
+    const float4 *texels;
+    uint32_t w, h;
+    float intensity, rotation;
 };
 
 // Device-resident control block. `counters` is the reference's counter_buffer (extend.wgsl:41).
@@ -489,9 +502,11 @@ struct TemporalArgs {
 };
 
 hipError_t launch_generate(const GenerateArgs &a, hipStream_t s);
-hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s, bool env_dirs = false); // env_dirs: also write the miss queue's dx, dz planes
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per sample
-hipError_t launch_bounce(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s);
+// env_dirs: the variant of WFPT_FLAG_ENVIRONMENT contexts with a map: misses carry direction.x and .z, no miss items (launch_miss with the
+// map lights them)
+hipError_t launch_bounce(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s, bool env_dirs = false);
 hipError_t launch_bounce_binned(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s); // LDS-resident scenes only
 hipError_t launch_scan_binned(const ScanBinnedArgs &a, hipStream_t s);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t s);
@@ -499,11 +514,11 @@ hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s, bool preshaded = false);
 hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s);
 hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array (WFPT_PRESHADE)
-hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s);
+hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 uint32_t bounce_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
-hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_fill(float *p, float v, size_t n, hipStream_t s);
 hipError_t launch_set_frame(Control *ctl, const wfpt_frame_buffer &f, hipStream_t s); // ctl->frame = f, ordered on the stream
@@ -514,7 +529,7 @@ hipError_t launch_rays_to_aos(const RayQueue &q, wfpt_ray *out, uint32_t n, hipS
 hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t n, hipStream_t s);
 // AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
 // sized for it)
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
 uint32_t aov_lds_bytes(const SceneDev &scene);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
@@ -523,6 +538,8 @@ hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, si
 hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, hipStream_t s);
+// env_lookup of n directions (xyz, stride 3) into rgb (stride 3): wfpt_sample_environment
+hipError_t launch_env_sample(const EnvDev &env, const float *dirs, float *rgb, size_t n, hipStream_t s);
 hipError_t launch_selftest_math(int op, const float *a, const float *b, float *out, size_t n, hipStream_t s);
 // Occupancy of the extend kernel for a given dynamic LDS size (workgroups per CU); also raises the
 // kernel's dynamic-LDS limit when the scene needs more than the default 64 KiB.
