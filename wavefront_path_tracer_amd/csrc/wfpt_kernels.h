@@ -516,7 +516,6 @@ hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t
 hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array (WFPT_PRESHADE)
 hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
-uint32_t bounce_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
@@ -530,7 +529,6 @@ hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t 
 // AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
 // sized for it)
 hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
-uint32_t aov_lds_bytes(const SceneDev &scene);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
 // accumulate_kernel's work plus the luminance moments (WFPT_FLAG_DENOISE contexts, in its place)

@@ -211,23 +211,6 @@ __device__ __forceinline__ float hit_bvh_node(float4 bmin, float4 bmax, float ox
     return (tmin > tmax || tmax <= 0.0f || tmin > nearest) ? (EXACT ? 1e30f : kBoxMiss) : tmin;
 }
 
-// measurement-only switches (tools/build_variant.sh): what each safety layer of the free walks costs. NOT for use: without them
-// the walks are no longer equivalent to the reference's (tests/test_traversal_model.py holds the counter-examples).
-#ifndef WFPT_EXP_NO_TIE
-#define WFPT_EXP_NO_TIE 0     // 1: no near-tie watch, no probe of failed leaves, no far-origin hand-over
-#endif
-#ifndef WFPT_EXP_NO_LEAFBOX
-#define WFPT_EXP_NO_LEAFBOX 0 // 1: leaf boxes are not re-tested with the reference's arithmetic
-#endif
-#ifndef WFPT_VISIT4_PK
-#define WFPT_VISIT4_PK 0 // 1: visit4's plane distances two children at a time with v_pk_fma_f32
-#endif
-#ifndef WFPT_VISIT4_PARTIAL_SORT
-#define WFPT_VISIT4_PARTIAL_SORT 0 // 1: visit4 brings only the nearest child to the front (measured: profiles/r04_rejected_experiments.txt)
-#endif
-#ifndef WFPT_LEAF_BOX_FUSED
-#define WFPT_LEAF_BOX_FUSED 1 // visit_leaf_in_place gathers the leaf's box in the loop that tests its primitives (one fetch of each)
-#endif
 #ifndef WFPT_LEAF_LANES
 #define WFPT_LEAF_LANES 8 // refill_kernel: lanes that have to wait at a leaf before the wave runs the leaf code
 #endif
@@ -250,9 +233,6 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 #define WFPT_STAMP(var)
 #define WFPT_DBG_PARAM
 #define WFPT_DBG_ARG
-#endif
-#ifndef WFPT_BUDGET_INNER
-#define WFPT_BUDGET_INNER 0 // 1: count the step budget down on every inner visit as well (costs 3 instructions per visit)
 #endif
 
 // Marks all four components of loaded float4s as used, so each load stays one ds_read_b128 (hipcc otherwise
@@ -340,7 +320,7 @@ struct Traversal {
 // which its walk meets them (the first of two bit-equal hits wins, ex:190-207's strict `<`; a box whose entry distance lies a
 // rounding error beyond a hit inside it is skipped or not depending on what was found before). The walks that are free in
 // their visit order (trace_ray_conservative, trace_ray4) watch for this and hand such a ray to the reference's own walk.
-__device__ __forceinline__ bool near_tie(float t, float nearest) { return !WFPT_EXP_NO_TIE && __builtin_fabsf(t - nearest) <= nearest * 3.8146973e-6f; }
+__device__ __forceinline__ bool near_tie(float t, float nearest) { return __builtin_fabsf(t - nearest) <= nearest * 3.8146973e-6f; }
 // How a free walk marks "hand this ray over": no flag of its own (a lane mask kept alive across the whole loop nest cost the
 // kernel ~40 scalar registers' worth of spills) but a poisoned result: nearest = -1 makes every later box and primitive test
 // fail, so the walk runs out by itself, and best = kHandOver tells the caller why.
@@ -426,7 +406,6 @@ __device__ __forceinline__ void grow_prim_box(const float4 *geom, uint32_t idx, 
 // test's own rounding slack stays inside the boxes' margin). A ray from farther away -- a bounce off the ground sphere hundreds of
 // units out -- is traced by the reference's own walk.
 __device__ __forceinline__ bool far_origin(const SceneDev &sc, float ox, float oy, float oz) {
-    if (WFPT_EXP_NO_TIE) return false;
     const float fx = ox - sc.safe_c[0], fy = oy - sc.safe_c[1], fz = oz - sc.safe_c[2];
     return (fx * fx + fy * fy) + fz * fz > sc.safe_r2;
 }
@@ -466,15 +445,13 @@ __device__ __forceinline__ void visit_leaf(const float4 *geom, uint32_t first, u
 template <int PRIM>
 __device__ __forceinline__ void leaf_box_verdict(const float4 *geom, uint32_t first, uint32_t count, bool box_untested, float ox, float oy, float oz,
                                                  float dx, float dy, float dz, float &nearest, uint32_t &best) {
-    if (best >= kHandOver || box_untested || WFPT_EXP_NO_LEAFBOX) return; // no hit, or handed over already
+    if (best >= kHandOver || box_untested) return; // no hit, or handed over already
     float3_ lo = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
     for (uint32_t i = 0; i < count; ++i) grow_prim_box<PRIM>(geom, first + i, lo, hi);
     const float ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz; // invDirection (gr:87, sh:153)
     float tmin, tmax;
     slab_range(make_float4(lo.x, lo.y, lo.z, 0.0f), make_float4(hi.x, hi.y, hi.z, 0.0f), ox, oy, oz, ix, iy, iz, tmin, tmax);
-    if (tmin > tmax || tmax <= 0.0f || tmin > nearest) { // ex:179 with nearest = the hit's own distance
-        if (!WFPT_EXP_NO_TIE) hand_over(nearest, best);
-    }
+    if (tmin > tmax || tmax <= 0.0f || tmin > nearest) hand_over(nearest, best); // ex:179 with nearest = the hit's own distance
 }
 
 // The same debt paid inside the walk, as round 3 did everywhere: the primitive tests run into a TENTATIVE result and, if that changed
@@ -489,7 +466,6 @@ __device__ __forceinline__ void visit_leaf_in_place(const float4 *geom, uint32_t
                                            float dx, float dy, float dz, float ix, float iy, float iz, float a, float &nearest, uint32_t &best) {
     float n2 = nearest;
     uint32_t b2 = best;
-#if WFPT_LEAF_BOX_FUSED
     // (round 5) the leaf's box is gathered while its primitives are in registers for their tests: with ~9 lanes in a leaf round some lane
     // accepts a primitive in nearly every round, so the wave ran the second loop -- the primitives fetched again, a dependent round trip --
     // nearly always anyway
@@ -498,18 +474,11 @@ __device__ __forceinline__ void visit_leaf_in_place(const float4 *geom, uint32_t
         hit_prim<PRIM, true>(geom, first + i, ox, oy, oz, dx, dy, dz, a, n2, b2);
         grow_prim_box<PRIM>(geom, first + i, lo, hi);
     }
-#else
-    for (uint32_t i = 0; i < count; ++i) hit_prim<PRIM, true>(geom, first + i, ox, oy, oz, dx, dy, dz, a, n2, b2);
-#endif
     // The box's verdict only matters if something changed (a primitive accepted, or a near-tie poisoned the window: n2 = -1):
     // most leaf visits end here, without the box ever being tested.
     if (n2 < nearest) {
-        bool enter = box_untested || WFPT_EXP_NO_LEAFBOX;
+        bool enter = box_untested;
         if (!enter) {
-#if !WFPT_LEAF_BOX_FUSED
-            float3_ lo = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-            for (uint32_t i = 0; i < count; ++i) grow_prim_box<PRIM>(geom, first + i, lo, hi);
-#endif
             float tmin, tmax;
             if (LAZY_INV) { ix = 1.0f / dx; iy = 1.0f / dy; iz = 1.0f / dz; } // invDirection (gr:87, sh:153)
             slab_range(make_float4(lo.x, lo.y, lo.z, 0.0f), make_float4(hi.x, hi.y, hi.z, 0.0f), ox, oy, oz, ix, iy, iz, tmin, tmax);
@@ -518,7 +487,7 @@ __device__ __forceinline__ void visit_leaf_in_place(const float4 *geom, uint32_t
         if (enter) {
             nearest = n2;
             best = b2;
-        } else if (!WFPT_EXP_NO_TIE) {
+        } else {
             hand_over(nearest, best);
         }
     }
@@ -547,7 +516,6 @@ __device__ __forceinline__ bool trace_ray(const float4 *nodes, const float4 *pri
     while (alive) {
         // ---- inner nodes (ex:105-138)
         while (alive && tr.prim_count == 0) {
-            if (WFPT_BUDGET_INNER && budget-- == 0) { alive = false; break; }
             const float4 *pair = nodes + 2u * tr.left_first;
             const float4 lmin = pair[0], lmax = pair[1], rmin = pair[2], rmax = pair[3];
             keep4(lmin, lmax, rmin, rmax);
@@ -859,9 +827,6 @@ __device__ __forceinline__ bool trace_ray_conservative(const float4 *nodes_ch, c
             trail = static_cast<Trail>(trail32);
         } else
         while (prim_count == 0u) { // inner nodes (ex:105-138)
-#if WFPT_BUDGET_INNER
-            if (budget-- == 0) { prim_count = kWalkDone; break; }
-#endif
 #if WFPT_STAMPS
             dbg[0] = __builtin_amdgcn_readfirstlane(dbg[0]) + 1u;
             dbg[2] += 1u;
@@ -1012,39 +977,17 @@ __device__ __forceinline__ Visit4 visit4(const float4 a, const float4 b, const f
     Visit4 v;
     v.w0 = __float_as_uint(c.z); v.w1 = __float_as_uint(c.w); v.w2 = __float_as_uint(d.x); v.w3 = __float_as_uint(d.y);
     float t[4];
-#if WFPT_VISIT4_PK
-    // two children per instruction: v_pk_fma_f32 issues two fp32 FMAs in the slot of one (tools/microbench_valu.hip)
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 sx = {spx, spx}, sy = {spy, spy}, sz = {spz, spz}, bx = {opx, opx}, by = {opy, opy}, bz = {opz, opz};
-#pragma unroll
-    for (int k = 0; k < 4; k += 2) {
-        const f2 inx = __builtin_elementwise_fma(f2{ubyte(nx, k), ubyte(nx, k + 1)}, sx, bx), iny = __builtin_elementwise_fma(f2{ubyte(ny, k), ubyte(ny, k + 1)}, sy, by),
-                 inz = __builtin_elementwise_fma(f2{ubyte(nz, k), ubyte(nz, k + 1)}, sz, bz);
-        const f2 outx = __builtin_elementwise_fma(f2{ubyte(fx, k), ubyte(fx, k + 1)}, sx, bx), outy = __builtin_elementwise_fma(f2{ubyte(fy, k), ubyte(fy, k + 1)}, sy, by),
-                 outz = __builtin_elementwise_fma(f2{ubyte(fz, k), ubyte(fz, k + 1)}, sz, bz);
-        const float t_in0 = max_(max_(inx.x, iny.x), inz.x), t_in1 = max_(max_(inx.y, iny.y), inz.y);
-        const float t_out0 = min_(min_(outx.x, outy.x), outz.x), t_out1 = min_(min_(outx.y, outy.y), outz.y);
-        t[k] = (max_(t_in0, 0.0f) <= min_(t_out0, nearest)) ? t_in0 : 2e30f;
-        t[k + 1] = (max_(t_in1, 0.0f) <= min_(t_out1, nearest)) ? t_in1 : 2e30f;
-    }
-#else
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float t_in = max_(max_(fma_(ubyte(nx, k), spx, opx), fma_(ubyte(ny, k), spy, opy)), fma_(ubyte(nz, k), spz, opz));
         const float t_out = min_(min_(fma_(ubyte(fx, k), spx, opx), fma_(ubyte(fy, k), spy, opy)), fma_(ubyte(fz, k), spz, opz));
         t[k] = (max_(t_in, 0.0f) <= min_(t_out, nearest)) ? t_in : 2e30f;
     }
-#endif
     // (an absent child has an inverted box, qlo = 255 > qhi = 0 on every axis, so it is not entered; should rounding ever make its
     // two plane distances meet, its word is a leaf of no primitives: nothing to guard here)
     v.t0 = t[0]; v.t1 = t[1]; v.t2 = t[2]; v.t3 = t[3];
-#if WFPT_VISIT4_PARTIAL_SORT
-    // only the nearest child is brought to the front (three compare-exchanges instead of five); the others are pushed in slot order
-    order2(v.t0, v.w0, v.t1, v.w1); order2(v.t2, v.w2, v.t3, v.w3); order2(v.t0, v.w0, v.t2, v.w2);
-#else
     order2(v.t0, v.w0, v.t1, v.w1); order2(v.t2, v.w2, v.t3, v.w3); order2(v.t0, v.w0, v.t2, v.w2); order2(v.t1, v.w1, v.t3, v.w3);
     order2(v.t1, v.w1, v.t2, v.w2);
-#endif
     return v;
 }
 // the node's four 16-byte quarters: from the LDS copy of the top of the tree (tile, nodes [0, tile_n)) or from global memory
@@ -1070,9 +1013,6 @@ __device__ __forceinline__ bool trace_ray4(const float4 *nodes4, const float4 *p
     uint32_t cur = 0; // node 0 is the root's four-wide node (the root's own box is never tested, ex:84)
     bool alive = true;
     uint32_t budget = max_steps; // every node is visited at most once on a valid tree
-#ifdef WFPT_DEBUG_BUDGET
-    budget = WFPT_DEBUG_BUDGET;
-#endif
     while (alive) {
         while (alive && !(cur & kLeafFlag)) {
             if (budget-- == 0) { alive = false; break; }
@@ -1101,16 +1041,79 @@ __device__ __forceinline__ bool trace_ray4(const float4 *nodes4, const float4 *p
     return nearest < 1e30f;
 }
 
+// ---- what the tracing kernels (extend, bounce, bounce_binned, aov) share: the scene staged in LDS and the choice of walk.
+// Macros, not forceinline functions: the compiler optimizes a function on its own before it inlines it, and written as a struct and a
+// function these three changed the machine code of 132 of the 139 tracing kernels, the register counts of 15 of them. They name the
+// kernel's `a` (a.scene: its SceneDev), `lds` (its dynamic LDS) and its template parameters PRIM, EXACT (WFPT_TRACE_ANY: also Trail,
+// LDS_SCENE, the kernel's hit / t / prim and, in WFPT_STAMPS builds, its `dbg` counters).
+//
+// uint4 words of the u16 parent table (8 entries each) of a tree of n_nodes nodes; scene_lds_bytes counts the same words on the host
+__host__ __device__ constexpr uint32_t parent_lds_words(uint32_t n_nodes) { return ((n_nodes / 2u + 1u) + 7u) / 8u; }
+// The scene at the start of the dynamic LDS: s_nodes (two float4 per node: the reference's boxes, or SceneDev::nodes_ch's centre /
+// half-extent boxes), s_geom (geom_words float4 of primitive geometry), s_parent (parent_words uint4 of the u16 parent table); `end` is
+// the first word after it, where the kernel carves its own area. STAGED false (HBM-resident scenes, launches that trace nothing): the
+// three are empty and `end` is the start of the dynamic LDS.
+#define WFPT_SCENE_LDS(STAGED, end)                                                                                                    \
+    float4 *s_nodes = lds;                                                                                                             \
+    float4 *s_geom = lds + ((STAGED) ? 2u * a.scene.n_nodes : 0u);                                                                     \
+    const uint32_t parent_words = (STAGED) ? parent_lds_words(a.scene.n_nodes) : 0u;                                                   \
+    const uint32_t geom_words = (STAGED) ? (PRIM == 0 ? 1u : 3u) * a.scene.n_spheres : 0u;                                             \
+    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_geom + geom_words);                                                            \
+    uint32_t *end = reinterpret_cast<uint32_t *>(s_geom + geom_words + parent_words)
+// The copy of the scene into LDS by the whole workgroup (g_nodes: a.scene.nodes); each kernel issues its own barrier after it.
+#define WFPT_STAGE_SCENE(g_nodes)                                                                                                      \
+    {                                                                                                                                  \
+        const float4 *g_staged = EXACT ? (g_nodes) : a.scene.nodes_ch;                                                                 \
+        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];                        \
+        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_geom[i] = a.scene.prim_geom[i];                          \
+        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);                                                     \
+        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);                                                                           \
+        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];                                    \
+    }
+// One ray's closest hit into the kernel's `hit`, `t` and `prim`, by the walk the scene and the flags select:
+//   * LDS + exact: the reference's walk (trace_ray) on the staged reference boxes;
+//   * LDS: the free walk on conservative boxes (trace_ray_conservative);
+//   * HBM + four-wide nodes: trace_ray4, its stack in the kernel's stack columns (spilling to SceneDev::stack_spill);
+//   * HBM: the reference's walk on the binary tree, the last kStackDepth pushes in the kernel's stack columns.
+// A free walk hands the ray over (prim = kHandOver) on a near-tie, a failed leaf-box verdict or an origin farther than sqrt(safe_r2) from
+// safe_c: the reference's own walk (retrace_reference, its boxes read from global memory; this is rare) then decides, which keeps every
+// result bit-equal to the reference's. g_nodes: a.scene.nodes; stack: the kernel's stack area in its dynamic LDS,
+// [2 * kStackDepth][kExtendThreads] words (HBM-resident scenes only).
+#define WFPT_TRACE_ANY(g_nodes, stack, ox, oy, oz, dx, dy, dz)                                                                         \
+    {                                                                                                                                  \
+        if (LDS_SCENE && EXACT)                                                                                                        \
+            hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_geom, s_parent, nullptr, ox, oy, oz, dx, dy, dz, a.scene.n_nodes,  \
+                                                            t, prim);                                                                  \
+        else if (LDS_SCENE) {                                                                                                          \
+            prim = kHandOver;                                                                                                          \
+            if (!far_origin(a.scene, ox, oy, oz))                                                                                      \
+                hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes,  \
+                                                                    t, prim WFPT_DBG_ARG);                                             \
+            if (prim == kHandOver)                                                                                                     \
+                hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t,  \
+                                                               prim);                                                                  \
+        } else if (!EXACT && a.scene.nodes4) {                                                                                         \
+            Stack4 st;                                                                                                                 \
+            st.init(WFPT_LDS_BYTES(lds, stack), a.scene.stack_spill, a.scene.spill_stride);                                            \
+            prim = kHandOver;                                                                                                          \
+            if (!far_origin(a.scene, ox, oy, oz))                                                                                      \
+                hit = trace_ray4<PRIM>(a.scene.nodes4, a.scene.prim_geom, st, ox, oy, oz, dx, dy, dz, a.scene.n_nodes,                 \
+                                       a.scene.root_leaf != 0, t, prim);                                                               \
+            if (prim == kHandOver)                                                                                                     \
+                hit = retrace_reference<Trail, PRIM, uint32_t>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, ox, oy, oz, dx, dy,  \
+                                                               dz, a.scene.n_nodes, t, prim);                                          \
+        } else                                                                                                                         \
+            hit = trace_ray<Trail, PRIM, uint32_t, kStackDepth, EXACT>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32,              \
+                                                                        (stack) + threadIdx.x, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, \
+                                                                        t, prim);                                                      \
+    }
+
 // The eight waves' hit and miss counts of a work item -> this wave's offsets. `cnt` = [16] words in LDS: hits of waves 0-7, misses of waves
 // 0-7 (written by lane 0 of every wave before the item's barrier). One ds_read per lane of the first row, an inclusive scan over the row with
 // four DPP adds, four v_readlane: where the obvious loop over the waves -- (w < wave) ? count : 0 -- compiled to 16 v_readfirstlane and, because
 // hipcc keeps the eight `w < wave` booleans as lane masks in scalar registers it then has to spill, ~32 v_readlane and ~40 scalar instructions.
-#ifndef WFPT_DPP_PREFIX
-#define WFPT_DPP_PREFIX 1
-#endif
 __device__ __forceinline__ void wave_offsets(const uint32_t *cnt, uint32_t wave, uint32_t lane, uint32_t &hit_before, uint32_t &hit_total,
                                              uint32_t &miss_before, uint32_t &miss_total) {
-#if WFPT_DPP_PREFIX
     static_assert(kExtendWaves == 8, "the sixteen counts are one DPP row");
     uint32_t v = lane < 16u ? cnt[lane] : 0u;
     // row_shr:n within the row of 16 lanes, zero shifted in (bound_ctrl): inclusive prefix sums of the row
@@ -1126,17 +1129,6 @@ __device__ __forceinline__ void wave_offsets(const uint32_t *cnt, uint32_t wave,
     hit_before = wave ? h_incl : 0u;
     miss_before = m_incl - hit_total;
     miss_total = all - hit_total;
-#else
-    hit_before = miss_before = hit_total = miss_total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kExtendWaves; ++w) {
-        const uint32_t hc = uniform(cnt[w]), mc = uniform(cnt[kExtendWaves + w]);
-        hit_before += (w < wave) ? hc : 0u;
-        miss_before += (w < wave) ? mc : 0u;
-        hit_total += hc;
-        miss_total += mc;
-    }
-#endif
 }
 
 // Persistent workgroups of 512 threads (8 waves): stage the scene in LDS once, then trace queue
@@ -1153,13 +1145,7 @@ __device__ __forceinline__ void wave_offsets(const uint32_t *cnt, uint32_t wave,
 template <bool HAS_INACTIVE, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV = false>
 __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void extend_kernel(ExtendArgs a) {
     extern __shared__ float4 lds[];
-    constexpr uint32_t kGeomWords = PRIM == 0 ? 1u : 3u; // float4 per primitive
-    float4 *s_nodes = lds;
-    float4 *s_sphere = lds + (LDS_SCENE ? 2u * a.scene.n_nodes : 0u);
-    const uint32_t parent_words = LDS_SCENE ? ((a.scene.n_nodes / 2u + 1u) + 7u) / 8u : 0u; // uint4 words of 8 u16 entries
-    const uint32_t geom_words = LDS_SCENE ? kGeomWords * a.scene.n_spheres : 0u;
-    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_sphere + geom_words);
-    uint32_t *s_misc = reinterpret_cast<uint32_t *>(s_sphere + geom_words + parent_words);
+    WFPT_SCENE_LDS(LDS_SCENE, s_misc);
     // s_misc: [2][2][kExtendWaves] wave counts, [2] next work item, [kMaxBatchClassic] rays per sample,
     //         [kMaxBatchClassic + 1] first work item of each sample
     uint32_t *s_next = s_misc + 4 * kExtendWaves;
@@ -1186,12 +1172,7 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void extend_
     if (item >= n_items) return; // nothing to do: skip the LDS staging too
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
     if (LDS_SCENE) {
-        const float4 *g_staged = EXACT ? g_nodes : a.scene.nodes_ch; // reference boxes, or conservative centre / half-extent boxes
-        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];
-        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_sphere[i] = a.scene.prim_geom[i];
-        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);
-        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);
-        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];
+        WFPT_STAGE_SCENE(g_nodes);
         __syncthreads();
     }
 
@@ -1219,33 +1200,10 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void extend_
         uint32_t prim = 0;
         bool hit = false;
         if (live) {
-            if (LDS_SCENE && EXACT)
-                hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_sphere, s_parent, nullptr, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t,
-                                                                prim);
-            else if (LDS_SCENE) {
-                prim = kHandOver;
-                if (!far_origin(a.scene, ox, oy, oz))
-                {
 #if WFPT_STAMPS
-                    uint32_t dbg[3] = {0, 0, 0};
+            uint32_t dbg[3] = {0, 0, 0};
 #endif
-                    hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_sphere, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim WFPT_DBG_ARG);
-                }
-                if (prim == kHandOver) // near-tie, probe or far origin: the reference's own walk decides (its boxes are read from global memory: this is rare)
-                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_sphere, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-            } else if (!EXACT && a.scene.nodes4) {
-                Stack4 st;
-                st.init(WFPT_LDS_BYTES(lds, s_stack), a.scene.stack_spill, a.scene.spill_stride);
-                prim = kHandOver;
-                if (!far_origin(a.scene, ox, oy, oz))
-                    hit = trace_ray4<PRIM>(a.scene.nodes4, a.scene.prim_geom, st, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, a.scene.root_leaf != 0, t, prim);
-                if (prim == kHandOver)
-                    hit = retrace_reference<Trail, PRIM, uint32_t>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, ox, oy, oz, dx, dy, dz,
-                                                                    a.scene.n_nodes, t, prim);
-            } else
-                hit = trace_ray<Trail, PRIM, uint32_t, kStackDepth, EXACT>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32,
-                                                                            s_stack + threadIdx.x, ox, oy, oz, dx, dy, dz,
-                                                                            a.scene.n_nodes, t, prim);
+            WFPT_TRACE_ANY(g_nodes, s_stack, ox, oy, oz, dx, dy, dz);
         }
         const bool miss = live && !hit;
         const unsigned long long hit_mask = __ballot(hit), miss_mask = __ballot(miss);
@@ -1817,14 +1775,8 @@ template <int MODE, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool E
 __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     extern __shared__ float4 lds[];
     constexpr bool TRACE = MODE != kBounceLast;
-    constexpr uint32_t kGeomWords = PRIM == 0 ? 1u : 3u;
     const bool stage_scene = TRACE && LDS_SCENE;
-    float4 *s_nodes = lds;
-    float4 *s_geom = lds + (stage_scene ? 2u * a.scene.n_nodes : 0u);
-    const uint32_t parent_words = stage_scene ? ((a.scene.n_nodes / 2u + 1u) + 7u) / 8u : 0u;
-    const uint32_t geom_words = stage_scene ? kGeomWords * a.scene.n_spheres : 0u;
-    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_geom + geom_words);
-    uint32_t *s_misc = reinterpret_cast<uint32_t *>(s_geom + geom_words + parent_words);
+    WFPT_SCENE_LDS(stage_scene, s_misc);
     BounceLds L;
     L.cnt = s_misc;
     L.next = L.cnt + 4 * kExtendWaves;
@@ -1863,12 +1815,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     uint32_t item = tickets.item_of(ticket);
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
     if (stage_scene) {
-        const float4 *g_staged = EXACT ? g_nodes : a.scene.nodes_ch; // reference boxes, or conservative centre / half-extent boxes
-        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];
-        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_geom[i] = a.scene.prim_geom[i];
-        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);
-        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);
-        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];
+        WFPT_STAGE_SCENE(g_nodes);
         __syncthreads();
     }
     wfpt_frame_buffer fb0 = a.ctl->frame; // the same for every lane: kept in scalar registers
@@ -1969,28 +1916,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         float t = 0.0f;
         uint32_t prim = 0;
         bool hit = false;
-        if (live) {
-            if (LDS_SCENE && EXACT)
-                hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_geom, s_parent, nullptr, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-            else if (LDS_SCENE) {
-                prim = kHandOver;
-                if (!far_origin(a.scene, ox, oy, oz))
-                    hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim WFPT_DBG_ARG);
-                if (prim == kHandOver) // near-tie, probe or far origin: the reference's own walk decides (its boxes are read from global memory: this is rare)
-                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-            } else if (!EXACT && a.scene.nodes4) {
-                Stack4 st;
-                st.init(WFPT_LDS_BYTES(lds, L.stack), a.scene.stack_spill, a.scene.spill_stride);
-                prim = kHandOver;
-                if (!far_origin(a.scene, ox, oy, oz))
-                    hit = trace_ray4<PRIM>(a.scene.nodes4, a.scene.prim_geom, st, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, a.scene.root_leaf != 0, t, prim);
-                if (prim == kHandOver)
-                    hit = retrace_reference<Trail, PRIM, uint32_t>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, ox, oy, oz, dx, dy, dz,
-                                                                    a.scene.n_nodes, t, prim);
-            } else
-                hit = trace_ray<Trail, PRIM, uint32_t, kStackDepth, EXACT>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, L.stack + threadIdx.x,
-                                                                            ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-        }
+        if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
         WFPT_STAMP(t_traced);
         const bool miss = live && !hit;
         const unsigned long long hit_mask = __ballot(hit), miss_mask = __ballot(miss);
@@ -2084,13 +2010,8 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
     extern __shared__ float4 lds[];
     constexpr bool TRACE = MODE != kBounceLast;
     constexpr int NW = ClsPack<K>::kWords;
-    constexpr uint32_t kGeomWords = PRIM == 0 ? 1u : 3u;
-    float4 *s_nodes = lds;
-    float4 *s_geom = lds + (TRACE ? 2u * a.scene.n_nodes : 0u);
-    const uint32_t parent_words = TRACE ? ((a.scene.n_nodes / 2u + 1u) + 7u) / 8u : 0u;
-    const uint32_t geom_words = TRACE ? kGeomWords * a.scene.n_spheres : 0u;
-    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_geom + geom_words);
-    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_geom + geom_words + parent_words); // [2][kExtendWaves][NW] packed per-wave counts
+    constexpr bool LDS_SCENE = true; // LDS-resident scenes only (WFPT_TRACE_ANY)
+    WFPT_SCENE_LDS(TRACE, s_cnt);                                                        // [2][kExtendWaves][NW] packed per-wave counts
     uint32_t *s_next = s_cnt + 2 * kExtendWaves * NW;                                    // [2] next work item
     uint8_t *s_cls = reinterpret_cast<uint8_t *>(s_next + 2);                            // [n_prims] ShadeRec::cost_class of each primitive
 
@@ -2111,12 +2032,7 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
     uint32_t item = tickets.item_of(ticket);
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
     if (TRACE) {
-        const float4 *g_staged = EXACT ? g_nodes : a.scene.nodes_ch; // reference boxes, or conservative centre / half-extent boxes
-        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];
-        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_geom[i] = a.scene.prim_geom[i];
-        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);
-        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);
-        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];
+        WFPT_STAGE_SCENE(g_nodes);
         for (uint32_t i = threadIdx.x; i < a.scene.n_spheres; i += kExtendThreads)
             s_cls[i] = static_cast<uint8_t>(umin(__float_as_uint(a.scene.shade_rec[3u * i + 2u].y), static_cast<uint32_t>(K - 1)));
         __syncthreads();
@@ -2244,17 +2160,7 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
         float t = 0.0f;
         uint32_t prim = 0;
         bool hit = false;
-        if (live) {
-            if (EXACT)
-                hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_geom, s_parent, nullptr, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-            else {
-                prim = kHandOver;
-                if (!far_origin(a.scene, ox, oy, oz))
-                    hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim WFPT_DBG_ARG);
-                if (prim == kHandOver) // near-tie, failed verdict or far origin: the reference's own walk decides (its boxes are read from global memory: this is rare)
-                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
-            }
-        }
+        if (live) WFPT_TRACE_ANY(g_nodes, static_cast<uint32_t *>(nullptr), ox, oy, oz, dx, dy, dz);
         const bool miss = live && !hit;
         // ---------------- compaction, class by class: K ballots, per-wave counts as packed fields, one LDS exchange
         const float hx = ox + t * dx, hy = oy + t * dy, hz = oz + t * dz; // the hit point shade will read: p = origin + t * direction (sh:91)
@@ -2279,7 +2185,6 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
         }
         __syncthreads();
         uint32_t before[NW], total[NW];
-#if WFPT_DPP_PREFIX
 #pragma unroll
         for (int j = 0; j < NW; ++j) { // lane w < 8 holds wave w's packed counts; inclusive scan over the row (see wave_offsets)
             uint32_t v = lane < kExtendWaves ? s_cnt[(buf * kExtendWaves + lane) * NW + j] : 0u; // fields of at most 512 each: no carries between them
@@ -2290,19 +2195,6 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
             const uint32_t incl = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), static_cast<int>((wave + 15u) & 15u)));
             before[j] = wave ? incl : 0u;
         }
-#else
-#pragma unroll
-        for (int j = 0; j < NW; ++j) { before[j] = 0; total[j] = 0; }
-#pragma unroll
-        for (uint32_t w = 0; w < kExtendWaves; ++w) {
-#pragma unroll
-            for (int j = 0; j < NW; ++j) {
-                const uint32_t v = uniform(s_cnt[(buf * kExtendWaves + w) * NW + j]);
-                before[j] += (w < wave) ? v : 0u; // fields of at most 512 each: no carries between them
-                total[j] += v;
-            }
-        }
-#endif
         // where class k starts inside the segment: the totals of the classes before it (packed like the counts)
         uint32_t coff[NW];
 #pragma unroll
@@ -2664,12 +2556,6 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
         { const unsigned long long vm = __ballot(alive && (cur & kLeafFlag) == 0); if (vm) { st_n[2] += 1; st_n[3] += static_cast<unsigned long long>(__popcll(vm)); } }
 #endif
         if (alive && (cur & kLeafFlag) == 0) {
-#if WFPT_BUDGET_INNER
-            if (budget-- == 0) {
-                fin = true;
-            } else
-#endif
-            {
             // (no step budget on node visits, as in the LDS walk's inner loop: wfpt_create / wfpt_update_scene reject a tree with a cycle
             // (validate_bvh), the four-wide nodes are collapsed from it, and a walk over a tree visits a node once; leaves keep theirs)
             const Visit4 v = visit4_at(nodes4, s_tile, tile_n, cur, r4, nearest);
@@ -2690,7 +2576,6 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
                     if (v.t1 < 2e30f) st.push(v.w1);
                 }
                 cur = v.w0;
-            }
             }
         }
         // A lane that has just arrived at a leaf goes on into the leaf code of the same iteration. The leaf code runs when enough
@@ -2973,24 +2858,13 @@ __global__ void rays_from_aos_kernel(RayQueue q, const wfpt_ray *in, uint32_t n)
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV>
 __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
     extern __shared__ float4 lds[];
-    constexpr uint32_t kGeomWords = PRIM == 0 ? 1u : 3u; // float4 per primitive
     const uint32_t n_slots = a.gx * a.gy * 64u;
     const uint32_t n_items = (n_slots + kExtendThreads - 1u) / kExtendThreads;
     if (blockIdx.x >= n_items) return; // nothing to do: skip the LDS staging too
-    float4 *s_nodes = lds;
-    float4 *s_geom = lds + (LDS_SCENE ? 2u * a.scene.n_nodes : 0u);
-    const uint32_t parent_words = LDS_SCENE ? ((a.scene.n_nodes / 2u + 1u) + 7u) / 8u : 0u; // uint4 words of 8 u16 entries
-    const uint32_t geom_words = LDS_SCENE ? kGeomWords * a.scene.n_spheres : 0u;
-    uint16_t *s_parent = reinterpret_cast<uint16_t *>(s_geom + geom_words);
-    uint32_t *s_stack = reinterpret_cast<uint32_t *>(s_geom + geom_words + parent_words); // HBM-resident scenes: the walk's stack columns
+    WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
     if (LDS_SCENE) {
-        const float4 *g_staged = EXACT ? g_nodes : a.scene.nodes_ch;
-        for (uint32_t i = threadIdx.x; i < 2u * a.scene.n_nodes; i += kExtendThreads) s_nodes[i] = g_staged[i];
-        for (uint32_t i = threadIdx.x; i < geom_words; i += kExtendThreads) s_geom[i] = a.scene.prim_geom[i];
-        const uint4 *g_par = reinterpret_cast<const uint4 *>(a.scene.pair_parent);
-        uint4 *s_par4 = reinterpret_cast<uint4 *>(s_parent);
-        for (uint32_t i = threadIdx.x; i < parent_words; i += kExtendThreads) s_par4[i] = g_par[i];
+        WFPT_STAGE_SCENE(g_nodes);
         __syncthreads();
     }
     const float4 *geom = LDS_SCENE ? s_geom : a.scene.prim_geom;
@@ -3016,39 +2890,11 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
             const PrimaryRay r = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
             float t = 0.0f;
             uint32_t prim = 0;
-            bool hit;
-            if (LDS_SCENE && EXACT) { // the selection of extend_kernel
-                hit = trace_ray<Trail, PRIM, uint16_t, 0, true>(s_nodes, s_geom, s_parent, nullptr, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                a.scene.n_nodes, t, prim);
-            } else if (LDS_SCENE) {
-                prim = kHandOver;
-                hit = false;
-                if (!far_origin(a.scene, r.ox, r.oy, r.oz)) {
 #if WFPT_STAMPS
-                    uint32_t dbg[3] = {0, 0, 0};
+            uint32_t dbg[3] = {0, 0, 0};
 #endif
-                    hit = trace_ray_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                        a.scene.n_nodes, t, prim WFPT_DBG_ARG);
-                }
-                if (prim == kHandOver)
-                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, a.scene.n_nodes,
-                                                                   t, prim);
-            } else if (!EXACT && a.scene.nodes4) {
-                Stack4 st;
-                st.init(WFPT_LDS_BYTES(lds, s_stack), a.scene.stack_spill, a.scene.spill_stride);
-                prim = kHandOver;
-                hit = false;
-                if (!far_origin(a.scene, r.ox, r.oy, r.oz))
-                    hit = trace_ray4<PRIM>(a.scene.nodes4, a.scene.prim_geom, st, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz, a.scene.n_nodes,
-                                           a.scene.root_leaf != 0, t, prim);
-                if (prim == kHandOver)
-                    hit = retrace_reference<Trail, PRIM, uint32_t>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32, r.ox, r.oy, r.oz, r.dx, r.dy,
-                                                                   r.dz, a.scene.n_nodes, t, prim);
-            } else {
-                hit = trace_ray<Trail, PRIM, uint32_t, kStackDepth, EXACT>(g_nodes, a.scene.prim_geom, a.scene.pair_parent32,
-                                                                            s_stack + threadIdx.x, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz,
-                                                                            a.scene.n_nodes, t, prim);
-            }
+            bool hit = false;
+            WFPT_TRACE_ANY(g_nodes, s_stack, r.ox, r.oy, r.oz, r.dx, r.dy, r.dz);
             if (hit) {
                 const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u];
                 // the normal scatter() uses: spheres normalize3(p - centre) with p = o + t d (extend's path record, sh:91), triangles the stored one
@@ -3456,135 +3302,117 @@ __global__ void selftest_math_kernel(int op, const float *a, const float *b, flo
 // ================================================================================================
 // launchers
 // ================================================================================================
-uint32_t extend_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene) {
-    const uint32_t misc = 4u * (4u * kExtendWaves + 2u + 2u * kMaxBatchClassic + 1u + 6u * kExtendWaves) + 16u;
-    if (!lds_scene) return misc + 4u * 2u * kStackDepth * kExtendThreads; // a stack entry is (node, packed fields)
-    const uint32_t parent_words = ((n_nodes / 2u + 1u) + 7u) / 8u;
-    return 32u * n_nodes + 16u * (prim_kind == 0 ? 1u : 3u) * n_prims + 16u * parent_words + misc;
+namespace {
+// The staged scene of WFPT_SCENE_LDS: nodes, primitive geometry, the u16 parent table. Each kernel adds its own area after it.
+uint32_t scene_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind) {
+    return 32u * n_nodes + 16u * (prim_kind == 0 ? 1u : 3u) * n_prims + 16u * parent_lds_words(n_nodes);
+}
+// HBM-resident scenes instead: the walk's stack columns (a binary-walk entry is (node, packed fields); the four-wide walk uses the first half)
+constexpr uint32_t kStackColumnBytes = 4u * 2u * kStackDepth * kExtendThreads;
+
+// The variant of a tracing kernel family for a scene: F::get<Trail, PRIM, LDS_SCENE, EXACT>() picked by (prim_kind, lds_scene,
+// depth > 31, exact). F names the family and its other template parameters (miss payload, launch mode).
+template <typename F, int PRIM, bool EXACT> auto pick_walk(bool lds_scene, bool deep) {
+    if (!lds_scene) return F::template get<unsigned long long, PRIM, false, EXACT>();
+    return deep ? F::template get<unsigned long long, PRIM, true, EXACT>() : F::template get<uint32_t, PRIM, true, EXACT>();
+}
+template <typename F> auto pick_variant(const SceneDev &sc, bool exact, bool lds_scene) {
+    const bool deep = sc.depth > 31u; // a 32-bit trail covers trees up to 31 levels deep
+    if (sc.prim_kind == 0) return exact ? pick_walk<F, 0, true>(lds_scene, deep) : pick_walk<F, 0, false>(lds_scene, deep);
+    return exact ? pick_walk<F, 1, true>(lds_scene, deep) : pick_walk<F, 1, false>(lds_scene, deep);
+}
+// A kernel may use more than 64 KiB of dynamic LDS only once that is allowed for it: for every variant the context may switch to
+template <typename... Fn> hipError_t allow_dynamic_lds(uint32_t bytes, Fn... fns) {
+    if (bytes <= 64u * 1024u) return hipSuccess;
+    for (const void *fn : {reinterpret_cast<const void *>(fns)...}) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
-namespace {
 using ExtendFn = void (*)(ExtendArgs);
-template <bool INACT, int PRIM, bool EXACT, bool ENV> ExtendFn extend_pick(bool lds_scene, bool deep) {
-    if (!lds_scene) return extend_kernel<INACT, unsigned long long, PRIM, false, EXACT, ENV>;
-    return deep ? extend_kernel<INACT, unsigned long long, PRIM, true, EXACT, ENV> : extend_kernel<INACT, uint32_t, PRIM, true, EXACT, ENV>;
-}
-template <bool EXACT, bool ENV> ExtendFn extend_variant_of(const SceneDev &sc, bool has_inactive) {
-    const bool lds = sc.lds_scene != 0, deep = sc.depth > 31u; // a 32-bit trail covers trees up to 31 levels deep
-    if (sc.prim_kind == 0) return has_inactive ? extend_pick<true, 0, EXACT, ENV>(lds, deep) : extend_pick<false, 0, EXACT, ENV>(lds, deep);
-    return has_inactive ? extend_pick<true, 1, EXACT, ENV>(lds, deep) : extend_pick<false, 1, EXACT, ENV>(lds, deep);
-}
-ExtendFn extend_variant(const SceneDev &sc, bool has_inactive, bool env = false) {
-    if (!env) return sc.exact ? extend_variant_of<true, false>(sc, has_inactive) : extend_variant_of<false, false>(sc, has_inactive);
-    return sc.exact ? extend_variant_of<true, true>(sc, has_inactive) : extend_variant_of<false, true>(sc, has_inactive);
+template <bool INACT, bool ENV> struct ExtendK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ExtendFn get() { return extend_kernel<INACT, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+};
+ExtendFn extend_variant(const SceneDev &sc, bool exact, bool has_inactive, bool env = false) {
+    const bool lds = sc.lds_scene != 0;
+    if (env) return has_inactive ? pick_variant<ExtendK<true, true>>(sc, exact, lds) : pick_variant<ExtendK<false, true>>(sc, exact, lds);
+    return has_inactive ? pick_variant<ExtendK<true, false>>(sc, exact, lds) : pick_variant<ExtendK<false, false>>(sc, exact, lds);
 }
 } // namespace
 
-hipError_t extend_blocks_per_cu(const SceneDev &scene, int *blocks) {
-    hipError_t e = hipSuccess;
-    if (scene.lds_bytes > 64u * 1024u) {
-        for (int v = 0; v < 8; ++v) { // both box tests (the context may switch between them later: decide_exact), both miss payloads
-            SceneDev sc = scene;
-            sc.exact = (v >> 1) & 1;
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(extend_variant(sc, (v & 1) != 0, (v >> 2) != 0)),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(scene.lds_bytes));
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, extend_variant(scene, false), kExtendThreads, scene.lds_bytes);
+uint32_t extend_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene) {
+    const uint32_t misc = 4u * (4u * kExtendWaves + 2u + 2u * kMaxBatchClassic + 1u + 6u * kExtendWaves) + 16u;
+    return misc + (lds_scene ? scene_lds_bytes(n_nodes, n_prims, prim_kind) : kStackColumnBytes);
 }
 
-uint32_t bounce_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene) {
-    const uint32_t misc = 4u * kBounceMiscWords;
-    if (!lds_scene) return misc + 4u * 2u * kStackDepth * kExtendThreads;
-    const uint32_t parent_words = ((n_nodes / 2u + 1u) + 7u) / 8u;
-    return 32u * n_nodes + 16u * (prim_kind == 0 ? 1u : 3u) * n_prims + 16u * parent_words + misc;
+hipError_t extend_blocks_per_cu(const SceneDev &scene, int *blocks) {
+    for (bool exact : {false, true}) { // both box tests (the context may switch between them later: decide_exact), both miss payloads
+        const hipError_t e = allow_dynamic_lds(scene.lds_bytes, extend_variant(scene, exact, false), extend_variant(scene, exact, true),
+                                               extend_variant(scene, exact, false, true), extend_variant(scene, exact, true, true));
+        if (e != hipSuccess) return e;
+    }
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, extend_variant(scene, scene.exact != 0, false), kExtendThreads, scene.lds_bytes);
 }
 
 namespace {
 using BounceFn = void (*)(BounceArgs);
-template <int MODE, int PRIM, bool EXACT, bool ENV> BounceFn bounce_pick(bool lds_scene, bool deep) {
-    if (!lds_scene) return bounce_kernel<MODE, unsigned long long, PRIM, false, EXACT, ENV>;
-    return deep ? bounce_kernel<MODE, unsigned long long, PRIM, true, EXACT, ENV> : bounce_kernel<MODE, uint32_t, PRIM, true, EXACT, ENV>;
-}
-template <bool EXACT, bool ENV> BounceFn bounce_variant_of(const SceneDev &sc, int mode) {
-    const bool lds = sc.lds_scene != 0, deep = sc.depth > 31u;
-    if (sc.prim_kind == 0) return mode == kBounceFirst ? bounce_pick<kBounceFirst, 0, EXACT, ENV>(lds, deep) : bounce_pick<kBounceMiddle, 0, EXACT, ENV>(lds, deep);
-    return mode == kBounceFirst ? bounce_pick<kBounceFirst, 1, EXACT, ENV>(lds, deep) : bounce_pick<kBounceMiddle, 1, EXACT, ENV>(lds, deep);
-}
+template <int MODE, bool ENV> struct BounceK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_kernel<MODE, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+};
 // env: the variant of WFPT_FLAG_ENVIRONMENT contexts with a map (bounce_kernel's ENV)
-BounceFn bounce_variant(const SceneDev &sc, int mode, bool env = false) {
-    if (!env) {
-        if (mode == kBounceLast) return bounce_kernel<kBounceLast, uint32_t, 0, false, false>; // no traversal: one variant
-        return sc.exact ? bounce_variant_of<true, false>(sc, mode) : bounce_variant_of<false, false>(sc, mode);
-    }
-    if (mode == kBounceLast) return bounce_kernel<kBounceLast, uint32_t, 0, false, false, true>;
-    return sc.exact ? bounce_variant_of<true, true>(sc, mode) : bounce_variant_of<false, true>(sc, mode);
+BounceFn bounce_variant(const SceneDev &sc, bool exact, int mode, bool env = false) {
+    const bool lds = sc.lds_scene != 0;
+    if (mode == kBounceLast) // no traversal: one variant
+        return env ? bounce_kernel<kBounceLast, uint32_t, 0, false, false, true> : bounce_kernel<kBounceLast, uint32_t, 0, false, false>;
+    if (env) return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, true>>(sc, exact, lds);
+    return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, false>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, false>>(sc, exact, lds);
 }
 uint32_t bounce_dynamic_lds(const SceneDev &sc, int mode) {
-    return mode == kBounceLast ? 4u * kBounceMiscWords : bounce_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind, sc.lds_scene != 0);
+    const uint32_t misc = 4u * kBounceMiscWords;
+    if (mode == kBounceLast) return misc;
+    return misc + (sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes);
 }
 } // namespace
 
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks) {
-    hipError_t e = hipSuccess;
     const uint32_t bytes = bounce_dynamic_lds(scene, kBounceMiddle);
-    if (bytes > 64u * 1024u) {
-        for (int exact = 0; exact < 2; ++exact)
-            for (int mode : {kBounceFirst, kBounceMiddle}) {
-                SceneDev sc = scene;
-                sc.exact = static_cast<uint32_t>(exact);
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(bounce_variant(sc, mode)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-                if (e != hipSuccess) return e;
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(bounce_variant(sc, mode, true)),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-                if (e != hipSuccess) return e;
-            }
+    for (bool exact : {false, true}) { // both box tests, the first and the middle launches, both miss payloads
+        const hipError_t e = allow_dynamic_lds(bytes, bounce_variant(scene, exact, kBounceFirst), bounce_variant(scene, exact, kBounceMiddle),
+                                               bounce_variant(scene, exact, kBounceFirst, true), bounce_variant(scene, exact, kBounceMiddle, true));
+        if (e != hipSuccess) return e;
     }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_variant(scene, kBounceMiddle), kExtendThreads, bytes);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
 }
 
 // ---- class-binned loop
 namespace {
 uint32_t bounce_binned_lds(const SceneDev &sc, int mode) {
     const uint32_t misc = 4u * (2u * kExtendWaves * ClsPack<kBinClasses>::kWords + 2u + 2u) + ((sc.n_spheres + 15u) & ~15u);
-    if (mode == kBounceLast) return misc;
-    const uint32_t parent_words = ((sc.n_nodes / 2u + 1u) + 7u) / 8u;
-    return 32u * sc.n_nodes + 16u * (sc.prim_kind == 0 ? 1u : 3u) * sc.n_spheres + 16u * parent_words + misc;
+    return mode == kBounceLast ? misc : misc + scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind);
 }
-template <int MODE, int PRIM, bool EXACT> BounceFn bounce_binned_pick(bool deep) {
-    return deep ? bounce_binned_kernel<MODE, unsigned long long, PRIM, EXACT, kBinClasses> : bounce_binned_kernel<MODE, uint32_t, PRIM, EXACT, kBinClasses>;
-}
-template <bool EXACT> BounceFn bounce_binned_variant_of(const SceneDev &sc, int mode) {
-    const bool deep = sc.depth > 31u;
-    if (sc.prim_kind == 0) return mode == kBounceFirst ? bounce_binned_pick<kBounceFirst, 0, EXACT>(deep) : bounce_binned_pick<kBounceMiddle, 0, EXACT>(deep);
-    return mode == kBounceFirst ? bounce_binned_pick<kBounceFirst, 1, EXACT>(deep) : bounce_binned_pick<kBounceMiddle, 1, EXACT>(deep);
-}
-BounceFn bounce_binned_variant(const SceneDev &sc, int mode) {
+template <int MODE> struct BinnedK { // LDS-resident scenes only: no LDS_SCENE parameter
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_binned_kernel<MODE, Trail, PRIM, EXACT, kBinClasses>; }
+};
+BounceFn bounce_binned_variant(const SceneDev &sc, bool exact, int mode) {
     if (mode == kBounceLast) return bounce_binned_kernel<kBounceLast, uint32_t, 0, false, kBinClasses>; // no traversal: one variant
-    return sc.exact ? bounce_binned_variant_of<true>(sc, mode) : bounce_binned_variant_of<false>(sc, mode);
+    return mode == kBounceFirst ? pick_variant<BinnedK<kBounceFirst>>(sc, exact, true) : pick_variant<BinnedK<kBounceMiddle>>(sc, exact, true);
 }
 } // namespace
 
 hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks) {
     const uint32_t bytes = bounce_binned_lds(scene, kBounceMiddle);
-    if (bytes > 64u * 1024u) {
-        for (int exact = 0; exact < 2; ++exact)
-            for (int mode : {kBounceFirst, kBounceMiddle}) {
-                SceneDev sc = scene;
-                sc.exact = static_cast<uint32_t>(exact);
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bounce_binned_variant(sc, mode)),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-                if (e != hipSuccess) return e;
-            }
+    for (bool exact : {false, true}) {
+        const hipError_t e = allow_dynamic_lds(bytes, bounce_binned_variant(scene, exact, kBounceFirst), bounce_binned_variant(scene, exact, kBounceMiddle));
+        if (e != hipSuccess) return e;
     }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_binned_variant(scene, kBounceMiddle), kExtendThreads, bytes);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_binned_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
 }
 
 hipError_t launch_bounce_binned(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(bounce_binned_variant(a.scene, mode), dim3(grid), dim3(kExtendThreads), bounce_binned_lds(a.scene, mode), s, a);
+    hipLaunchKernelGGL(bounce_binned_variant(a.scene, a.scene.exact != 0, mode), dim3(grid), dim3(kExtendThreads), bounce_binned_lds(a.scene, mode), s, a);
     return hipGetLastError();
 }
 
@@ -3600,7 +3428,7 @@ hipError_t launch_plan(const PlanArgs &a, hipStream_t s) {
 
 hipError_t launch_bounce(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s, bool env_dirs) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(bounce_variant(a.scene, mode, env_dirs), dim3(grid), dim3(kExtendThreads), bounce_dynamic_lds(a.scene, mode), s, a);
+    hipLaunchKernelGGL(bounce_variant(a.scene, a.scene.exact != 0, mode, env_dirs), dim3(grid), dim3(kExtendThreads), bounce_dynamic_lds(a.scene, mode), s, a);
     return hipGetLastError();
 }
 
@@ -3648,7 +3476,7 @@ hipError_t launch_generate(const GenerateArgs &a, hipStream_t s) {
 
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s, bool env_dirs) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(extend_variant(a.scene, a.has_inactive != 0, env_dirs), dim3(grid), dim3(kExtendThreads), a.scene.lds_bytes, s, a);
+    hipLaunchKernelGGL(extend_variant(a.scene, a.scene.exact != 0, a.has_inactive != 0, env_dirs), dim3(grid), dim3(kExtendThreads), a.scene.lds_bytes, s, a);
     return hipGetLastError();
 }
 
@@ -3719,33 +3547,13 @@ template <bool ENV> struct AovK {
 template <> struct AovK<true> {
     template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovEnvFn get() { return aov_env_kernel<Trail, PRIM, LDS_SCENE, EXACT>; }
 };
-template <int PRIM, bool EXACT, bool ENV> auto aov_pick(bool lds_scene, bool deep) {
-    using K = AovK<ENV>;
-    if (!lds_scene) return K::template get<unsigned long long, PRIM, false, EXACT>();
-    return deep ? K::template get<unsigned long long, PRIM, true, EXACT>() : K::template get<uint32_t, PRIM, true, EXACT>();
-}
-template <bool ENV = false> auto aov_variant(const SceneDev &sc, bool exact) {
-    const bool lds = sc.lds_scene != 0, deep = sc.depth > 31u; // as extend_variant
-    if (sc.prim_kind == 0) return exact ? aov_pick<0, true, ENV>(lds, deep) : aov_pick<0, false, ENV>(lds, deep);
-    return exact ? aov_pick<1, true, ENV>(lds, deep) : aov_pick<1, false, ENV>(lds, deep);
-}
+template <bool ENV = false> auto aov_variant(const SceneDev &sc, bool exact) { return pick_variant<AovK<ENV>>(sc, exact, sc.lds_scene != 0); }
+uint32_t aov_lds_bytes(const SceneDev &sc) { return sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes; }
 } // namespace
 
-uint32_t aov_lds_bytes(const SceneDev &sc) {
-    if (!sc.lds_scene) return 4u * 2u * kStackDepth * kExtendThreads; // the binary walk's stack columns (the four-wide walk uses the first half)
-    const uint32_t parent_words = ((sc.n_nodes / 2u + 1u) + 7u) / 8u;
-    return 32u * sc.n_nodes + 16u * (sc.prim_kind == 0 ? 1u : 3u) * sc.n_spheres + 16u * parent_words;
-}
-
 hipError_t aov_prepare(const SceneDev &scene) {
-    const uint32_t bytes = aov_lds_bytes(scene);
-    if (bytes <= 64u * 1024u) return hipSuccess;
-    for (int exact = 0; exact < 2; ++exact) { // both box tests: the context may switch between them later (decide_exact)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(aov_variant(scene, exact != 0)),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(aov_variant<true>(scene, exact != 0)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(bytes));
+    for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
+        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), aov_variant(scene, exact), aov_variant<true>(scene, exact));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
