@@ -42,8 +42,8 @@ KERNELS = {  # mangled fragment: (what it is, scratch bytes allowed)
     "bounce_kernelILi0EjLi0ELb1ELb0E": ("bounce_kernel<first>", 24),
     "bounce_binned_kernelILi1EjLi0ELb0ELi4E": ("bounce_binned_kernel<middle>", 0),
     "extend_kernelILb0EjLi0ELb1ELb0E": ("extend_kernel, spheres in LDS, default walk", 0),
-    "refill_kernelILi0ELi1ELb1E": ("refill_kernel<first>, triangles, rays from the dense array", 16),
-    "refill_kernelILi1ELi1ELb1E": ("refill_kernel<middle>, triangles, rays from the dense array", 16),
+    "refill_kernelILi0ELi1EE": ("refill_kernel<first>, triangles, rays from the dense array", 16),
+    "refill_kernelILi1ELi1EE": ("refill_kernel<middle>, triangles, rays from the dense array", 16),
 }
 
 

@@ -362,20 +362,18 @@ ExtendArgs extend_args(wfpt_ctx *c, int qi, const uint32_t *n_in, uint32_t limit
     a.scene = c->scene;
     return a;
 }
-// `first`: the first sample of the launch's slices (0: a batch is one chain of launches)
-ScanArgs scan_args(wfpt_ctx *c, const uint32_t *n_in, uint32_t limit, bool fused, uint32_t bounce, uint32_t nb = 1, int fused_parity = -1, uint32_t first = 0) {
+ScanArgs scan_args(wfpt_ctx *c, const uint32_t *n_in, uint32_t limit, bool fused, uint32_t bounce, uint32_t nb = 1, int fused_parity = -1) {
     ScanArgs a{};
     a.batch = batch_of(c, nb);
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max;
-    a.chunk_hits = c->chunk_hits.get() + co; a.chunk_miss = c->chunk_miss.get() + co;
+    a.chunk_hits = c->chunk_hits.get(); a.chunk_miss = c->chunk_miss.get();
     if (fused_parity >= 0) { // counts written by the fused bounce kernel of this wavefront
-        a.chunk_hits = c->f_chunk_hits[fused_parity].get() + co;
-        a.chunk_miss = c->f_chunk_miss[fused_parity].get() + co;
-        a.first_seg = c->first_seg.get() + co;
+        a.chunk_hits = c->f_chunk_hits[fused_parity].get();
+        a.chunk_miss = c->f_chunk_miss[fused_parity].get();
+        a.first_seg = c->first_seg.get();
     }
-    a.chunk_hit_base = c->chunk_hit_base.get() + co; a.chunk_miss_base = c->chunk_miss_base.get() + co;
-    a.ctl = c->ctl.get() + first;
-    a.n_in = n_in + static_cast<size_t>(first) * a.batch.ctl_stride;
+    a.chunk_hit_base = c->chunk_hit_base.get(); a.chunk_miss_base = c->chunk_miss_base.get();
+    a.ctl = c->ctl.get();
+    a.n_in = n_in;
     a.limit = std::min(limit, c->capacity);
     a.fused = fused ? 1u : 0u;
     a.miss_floor = c->p.miss_floor;
@@ -435,32 +433,30 @@ AccumulateArgs accumulate_args(wfpt_ctx *c, uint32_t n_pixels, bool bookkeeping,
 }
 
 constexpr uint32_t kPlanWords = kMaxBatch * (kBinClasses + 2) + 8; // work-item plan of the class-binned loop
-BounceArgs bounce_args(wfpt_ctx *c, int in_parity, int out_parity, uint32_t nb, uint32_t first = 0) {
+BounceArgs bounce_args(wfpt_ctx *c, int in_parity, int out_parity, uint32_t nb) {
     BounceArgs a{};
     a.batch = batch_of(c, nb);
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max, qo = static_cast<size_t>(first) * c->capacity;
     a.stamps = c->d_stamps.get();
-    a.rec_in = c->rec_mem[in_parity].get() + 2 * qo;
-    a.rec_out = c->rec_mem[out_parity].get() + 2 * qo;
-    a.in_hits = c->f_chunk_hits[in_parity].get() + co;
-    a.in_miss = c->f_chunk_miss[in_parity].get() + co;
-    a.in_hit_base = c->chunk_hit_base.get() + co;
-    a.in_first_seg = c->first_seg.get() + co;
-    a.out_hits = c->f_chunk_hits[out_parity].get() + co;
-    a.out_miss = c->f_chunk_miss[out_parity].get() + co;
-    a.mq_in = c->f_mq[in_parity]; a.mq_in.base += qo;
-    a.mq_out = c->f_mq[out_parity]; a.mq_out.base += qo;
+    a.rec_in = c->rec_mem[in_parity].get();
+    a.rec_out = c->rec_mem[out_parity].get();
+    a.in_hits = c->f_chunk_hits[in_parity].get();
+    a.in_miss = c->f_chunk_miss[in_parity].get();
+    a.in_hit_base = c->chunk_hit_base.get();
+    a.in_first_seg = c->first_seg.get();
+    a.out_hits = c->f_chunk_hits[out_parity].get();
+    a.out_miss = c->f_chunk_miss[out_parity].get();
+    a.mq_in = c->f_mq[in_parity];
+    a.mq_out = c->f_mq[out_parity];
     if (c->bin_capable) {
-        constexpr size_t kWords = ClsPack<kBinClasses>::kWords;
         a.plan = c->plan.get();
         a.plan_seg_off = nb * kBinClasses + 1u;
         a.plan_miss_off = a.plan_seg_off + nb + 1u;
-        a.cls_table = c->cls_table.get() + co * kBinClasses;
-        a.first_seg_cls = c->first_seg_cls.get() + co * kBinClasses;
-        a.out_cls = c->f_cls[out_parity].get() + co * kWords;
+        a.cls_table = c->cls_table.get();
+        a.first_seg_cls = c->first_seg_cls.get();
+        a.out_cls = c->f_cls[out_parity].get();
     }
-    a.image = c->image.get() + static_cast<size_t>(first) * c->image_floats;
-    a.ctl = c->ctl.get() + first;
+    a.image = c->image.get();
+    a.ctl = c->ctl.get();
     a.camera = c->camera.get();
     a.gx = c->tiles_x;
     a.gy = c->tiles_y_local;
@@ -471,18 +467,17 @@ BounceArgs bounce_args(wfpt_ctx *c, int in_parity, int out_parity, uint32_t nb, 
     a.scene = c->scene;
     return a;
 }
-RefillArgs refill_args(wfpt_ctx *c, int in_parity, uint32_t nb, uint32_t first = 0) {
+RefillArgs refill_args(wfpt_ctx *c, int in_parity, uint32_t nb) {
     RefillArgs a{};
     a.batch = batch_of(c, nb);
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max, qo = static_cast<size_t>(first) * c->capacity;
     a.stamps = c->d_stamps.get();
-    a.rec_in = c->rec_mem[in_parity].get() + 2 * qo;
-    a.dense_out = c->rec_dense.get() + 2 * qo;
-    a.in_hits = c->f_chunk_hits[in_parity].get() + co;
-    a.in_hit_base = c->chunk_hit_base.get() + co;
-    a.in_first_seg = c->first_seg.get() + co;
-    a.image = c->image.get() + static_cast<size_t>(first) * c->image_floats;
-    a.ctl = c->ctl.get() + first;
+    a.rec_in = c->rec_mem[in_parity].get();
+    a.dense_out = c->rec_dense.get();
+    a.in_hits = c->f_chunk_hits[in_parity].get();
+    a.in_hit_base = c->chunk_hit_base.get();
+    a.in_first_seg = c->first_seg.get();
+    a.image = c->image.get();
+    a.ctl = c->ctl.get();
     a.camera = c->camera.get();
     a.gx = c->tiles_x;
     a.gy = c->tiles_y_local;
@@ -493,64 +488,62 @@ RefillArgs refill_args(wfpt_ctx *c, int in_parity, uint32_t nb, uint32_t first =
     a.scene = c->scene;
     return a;
 }
-CompactArgs compact_args(wfpt_ctx *c, int out_parity, uint32_t nb, uint32_t first = 0) {
+CompactArgs compact_args(wfpt_ctx *c, int out_parity, uint32_t nb) {
     CompactArgs a{};
     a.batch = batch_of(c, nb);
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max, qo = static_cast<size_t>(first) * c->capacity;
-    a.dense_in = c->rec_dense.get() + 2 * qo;
-    a.rec_out = c->rec_mem[out_parity].get() + 2 * qo;
-    a.mq_out = c->f_mq[out_parity]; a.mq_out.base += qo;
-    a.out_hits = c->f_chunk_hits[out_parity].get() + co;
-    a.out_miss = c->f_chunk_miss[out_parity].get() + co;
-    a.ctl = c->ctl.get() + first;
+    a.dense_in = c->rec_dense.get();
+    a.rec_out = c->rec_mem[out_parity].get();
+    a.mq_out = c->f_mq[out_parity];
+    a.out_hits = c->f_chunk_hits[out_parity].get();
+    a.out_miss = c->f_chunk_miss[out_parity].get();
+    a.ctl = c->ctl.get();
     a.capacity = c->capacity;
     return a;
 }
-MissArgs fused_miss_args(wfpt_ctx *c, int parity, uint32_t nb, uint32_t first = 0) { // miss_kernel over the fused loop's miss queue of one wavefront
+MissArgs fused_miss_args(wfpt_ctx *c, int parity, uint32_t nb) { // miss_kernel over the fused loop's miss queue of one wavefront
     MissArgs a = miss_args(c, 0, &c->ctl.get()->miss_n, c->capacity, nb);
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max, qo = static_cast<size_t>(first) * c->capacity;
-    a.mq = c->f_mq[parity]; a.mq.base += qo;
-    a.chunk_miss = c->f_chunk_miss[parity].get() + co;
-    a.chunk_miss_base = c->chunk_miss_base.get() + co;
-    a.image = c->image.get() + static_cast<size_t>(first) * c->image_floats;
-    a.ctl = c->ctl.get() + first;
-    a.n_miss = &c->ctl.get()[first].miss_n;
+    a.mq = c->f_mq[parity];
+    a.chunk_miss = c->f_chunk_miss[parity].get();
     return a;
 }
-ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity, uint32_t first = 0) {
+ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
     ScanBinnedArgs a{};
     a.batch = batch_of(c, nb);
-    constexpr size_t kWords = ClsPack<kBinClasses>::kWords;
-    const size_t co = static_cast<size_t>(first) * c->n_chunks_max;
-    a.chunk_hits = c->f_chunk_hits[parity].get() + co;
-    a.chunk_miss = c->f_chunk_miss[parity].get() + co;
-    a.chunk_cls = c->f_cls[parity].get() + co * kWords;
-    a.cls_table = c->cls_table.get() + co * kBinClasses;
-    a.first_seg_cls = c->first_seg_cls.get() + co * kBinClasses;
-    a.ctl = c->ctl.get() + first;
-    a.n_in = &c->ctl.get()[first].n_in;
+    a.chunk_hits = c->f_chunk_hits[parity].get();
+    a.chunk_miss = c->f_chunk_miss[parity].get();
+    a.chunk_cls = c->f_cls[parity].get();
+    a.cls_table = c->cls_table.get();
+    a.first_seg_cls = c->first_seg_cls.get();
+    a.ctl = c->ctl.get();
+    a.n_in = &c->ctl.get()->n_in;
     a.limit = c->capacity;
     a.miss_floor = c->p.miss_floor;
     a.bounce = bounce;
     return a;
 }
-PlanArgs plan_args(wfpt_ctx *c, uint32_t nb, bool last, uint32_t first = 0) {
+PlanArgs plan_args(wfpt_ctx *c, uint32_t nb, bool last) {
     PlanArgs a{};
     a.batch = batch_of(c, nb);
-    a.ctl = c->ctl.get() + first;
+    a.ctl = c->ctl.get();
     a.plan = c->plan.get();
     a.plan_seg_off = nb * kBinClasses + 1u;
     a.plan_miss_off = a.plan_seg_off + nb + 1u;
     a.last = last ? 1u : 0u;
     return a;
 }
-// the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
-// the record's 16 bits
 // the map the kernels light misses with, null for the gradient sky: selects the environment variants (and the miss launches of the fused loops)
 const EnvDev *env_of(const wfpt_ctx *c) { return c->env_tex.get() ? &c->env : nullptr; }
+// the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
+// the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
     return c->bin_capable && !c->env_tex.get() && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
+}
+// The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
+wfpt_loop_kind loop_of(const wfpt_ctx *c) {
+    if (!c->fused) return WFPT_LOOP_STAGES;
+    if (c->rec_dense.get() && !c->scene.exact) return WFPT_LOOP_REFILL;
+    return use_binned(c) ? WFPT_LOOP_FUSED_BINNED : WFPT_LOOP_FUSED;
 }
 uint32_t bounce_grid(const wfpt_ctx *c, uint32_t n) {
     // hit items + miss items never exceed 1.25 work items per segment
@@ -558,73 +551,104 @@ uint32_t bounce_grid(const wfpt_ctx *c, uint32_t n) {
     return static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->bounce_blocks_per_cu));
 }
 
-// One batch of fused samples on the stream (pt:291-368). `ev`: optional (stage, start, stop) event recorder.
+// One batch of nb samples on the stream (pt:291-368). `ev`: optional (stage, start, stop) event recorder.
 struct EventRec { int stage; hipEvent_t start, stop; };
 
-// The wavefront chain of the samples [first, first + nb) of a batch on `st`, up to (not including) accumulate. Returns false if this
-// context's loop is not one of the fused ones (the stage kernels one by one: enqueue_batch).
+// The wavefront chain of a batch up to (not including) accumulate, one function per loop (loop_of). `timed(stage, launch)` runs a launch
+// and records its events.
+
+// WFPT_LOOP_STAGES: generate | (extend | scan | shade | miss) x max_wavefronts, the reference's stages one by one
 template <typename Timed>
-int enqueue_fused_chain(wfpt_ctx *c, Timed &timed, uint32_t nb, uint32_t first, hipStream_t st) {
-    if (c->fused && c->rec_dense.get() && !c->scene.exact) {
-        // HBM-resident scene: traversal with dynamic lane refill. Per wavefront: (miss_kernel of the previous one) |
-        // refill-trace into dense per-ray records | compact into the queues | scan; then shade+miss of the last one.
-        const uint32_t grid = c->cus * c->bounce_blocks_per_cu;
-        if (WFPT_PRESHADE) // generate_rays at full waves into the dense array, then the traversal refills from it
-            WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate_dense(refill_args(c, 1, nb, first), st); }));
-        WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_refill(refill_args(c, 1, nb, first), kBounceFirst, grid, st, WFPT_PRESHADE != 0); }));
-        const EnvDev *env = env_of(c);
-        for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
-            const int par = static_cast<int>(b & 1u);
-            WFPT_HIP(c, timed(WFPT_STAGE_COMPACT, [&] { return launch_compact(compact_args(c, par, nb, first), c->n_chunks_max, st, env != nullptr); }));
-            WFPT_HIP(c, timed(WFPT_STAGE_SCAN,
-                              [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par, first), st); }));
-            if (b + 1 < c->p.max_wavefronts) {
-                WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb, first), consumer_grid(c, nb), st, env); }));
-                if (WFPT_PRESHADE) // shade at full waves into the dense array, then the traversal refills from it
-                    WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb, first), c->n_chunks_max, st); }));
-                WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb, first), kBounceMiddle, grid, st, WFPT_PRESHADE != 0); }));
-            } else {
-                if (env) // the last launch's miss items, as a launch of their own with the map
-                    WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb, first), consumer_grid(c, nb), st, env); }));
-                WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
-                                  [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb, first), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
-            }
-        }
-        return WFPT_OK;
+int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
+    const hipStream_t st = c->stream.get();
+    const bool split = (c->p.flags & WFPT_FLAG_SPLIT_SHADE) != 0;
+    const EnvDev *env = env_of(c);
+    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate(generate_args(c, c->tiles_x, c->tiles_y_local, true, nb), st); }));
+    for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
+        const int qi = static_cast<int>(b & 1u);
+        WFPT_HIP(c, timed(WFPT_STAGE_EXTEND, [&] {
+                     return launch_extend(extend_args(c, qi, &c->ctl.get()->n_in, c->capacity, nb, split), extend_grid(c, nb), st, env != nullptr);
+                 }));
+        WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), st); }));
+        // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
+        WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
+                     ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
+                     sa.rec_in = c->hit_rec.get(); // this wavefront's extend has just written them
+                     return launch_shade(sa, consumer_grid(c, nb), st);
+                 }));
+        WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] {
+                     return launch_miss(miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb), st, env);
+                 }));
     }
-    if (use_binned(c)) {
-        // the same chain with the hit queue binned by cost class: generate+extend | scan, plan | (shade+extend+miss | scan, plan) x (max - 1) | shade+miss
-        const uint64_t items = (static_cast<uint64_t>(c->n_chunks_max) * 5u / 4u + 1u) * nb;
-        const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->bounce_binned_blocks_per_cu));
-        WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_bounce_binned(bounce_args(c, 1, 0, nb, first), kBounceFirst, grid, st); }));
-        for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
-            const int par = static_cast<int>(b & 1u);
-            const bool last = b + 1 >= c->p.max_wavefronts;
-            WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] {
-                         hipError_t e = launch_scan_binned(scan_binned_args(c, b, nb, par, first), st);
-                         return e != hipSuccess ? e : launch_plan(plan_args(c, nb, last, first), st);
-                     }));
-            WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE,
-                              [&] { return launch_bounce_binned(bounce_args(c, par, par ^ 1, nb, first), last ? kBounceLast : kBounceMiddle, grid, st); }));
-        }
-        return WFPT_OK;
-    }
-    // generate+extend | scan | (shade+extend+miss | scan) x (max_wavefronts - 1) | shade+miss
-    // With an environment map the bounce launches carry no miss items: a miss launch with the map precedes each of them (after the scan that
-    // decides whether the loop goes on, as the miss items would)
+    return WFPT_OK;
+}
+
+// WFPT_LOOP_FUSED: generate+extend | scan | (shade+extend+miss | scan) x (max_wavefronts - 1) | shade+miss
+// With an environment map the bounce launches carry no miss items: a miss launch with the map precedes each of them (after the scan that
+// decides whether the loop goes on, as the miss items would)
+template <typename Timed>
+int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
+    const hipStream_t st = c->stream.get();
     const uint32_t grid = bounce_grid(c, nb);
     const EnvDev *env = env_of(c);
-    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_bounce(bounce_args(c, 1, 0, nb, first), kBounceFirst, grid, st, env != nullptr); }));
+    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_bounce(bounce_args(c, 1, 0, nb), kBounceFirst, grid, st, env != nullptr); }));
     for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
         const int par = static_cast<int>(b & 1u);
-        WFPT_HIP(c, timed(WFPT_STAGE_SCAN,
-                          [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par, first), st); }));
-        if (env)
-            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb, first), consumer_grid(c, nb), st, env); }));
-        if (b + 1 < c->p.max_wavefronts)
-            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb, first), kBounceMiddle, grid, st, env != nullptr); }));
-        else
-            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST, [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb, first), kBounceLast, grid, st, env != nullptr); }));
+        const bool last = b + 1 >= c->p.max_wavefronts;
+        WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
+        if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+        WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
+                     return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
+                 }));
+    }
+    return WFPT_OK;
+}
+
+// WFPT_LOOP_FUSED_BINNED: the fused chain with the hit queue binned by cost class:
+// generate+extend | scan, plan | (shade+extend+miss | scan, plan) x (max_wavefronts - 1) | shade+miss
+template <typename Timed>
+int enqueue_fused_binned(wfpt_ctx *c, Timed &timed, uint32_t nb) {
+    const hipStream_t st = c->stream.get();
+    const uint64_t items = (static_cast<uint64_t>(c->n_chunks_max) * 5u / 4u + 1u) * nb;
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->bounce_binned_blocks_per_cu));
+    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_bounce_binned(bounce_args(c, 1, 0, nb), kBounceFirst, grid, st); }));
+    for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
+        const int par = static_cast<int>(b & 1u);
+        const bool last = b + 1 >= c->p.max_wavefronts;
+        WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] {
+                     hipError_t e = launch_scan_binned(scan_binned_args(c, b, nb, par), st);
+                     return e != hipSuccess ? e : launch_plan(plan_args(c, nb, last), st);
+                 }));
+        WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE,
+                          [&] { return launch_bounce_binned(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st); }));
+    }
+    return WFPT_OK;
+}
+
+// WFPT_LOOP_REFILL: HBM-resident scene, traversal with dynamic lane refill. generate_rays at full waves into the dense array, then the
+// traversal refills from it; per wavefront: compact into the queues | scan | (miss_kernel | shade at full waves into the dense array |
+// refill-trace into dense per-ray records); then shade+miss of the last one.
+template <typename Timed>
+int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
+    const hipStream_t st = c->stream.get();
+    const uint32_t grid = c->cus * c->bounce_blocks_per_cu;
+    const EnvDev *env = env_of(c);
+    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate_dense(refill_args(c, 1, nb), st); }));
+    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_refill(refill_args(c, 1, nb), kBounceFirst, grid, st); }));
+    for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
+        const int par = static_cast<int>(b & 1u);
+        WFPT_HIP(c, timed(WFPT_STAGE_COMPACT, [&] { return launch_compact(compact_args(c, par, nb), c->n_chunks_max, st, env != nullptr); }));
+        WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
+        if (b + 1 < c->p.max_wavefronts) {
+            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
+        } else {
+            if (env) // the last launch's miss items, as a launch of their own with the map
+                WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
+                              [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
+        }
     }
     return WFPT_OK;
 }
@@ -671,40 +695,16 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
         return hipEventRecord(p.stop.get(), c->stream.get());
     };
     c->cur = 0;
-    const bool split = (c->p.flags & WFPT_FLAG_SPLIT_SHADE) != 0;
     if (c->aov_sums.get()) // first in the batch, serially on the stream: it sees the batch's first frame, before accumulate advances it
         WFPT_HIP(c, timed(kStageAov, [&] { return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c)); }));
-    if (c->fused) {
-        if (int r = enqueue_fused_chain(c, timed, nb, 0, c->stream.get()); r != WFPT_OK) return r;
-        WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] { return launch_batch_accumulate(c, nb); }));
-        return WFPT_OK;
+    int r = WFPT_OK;
+    switch (loop_of(c)) {
+    case WFPT_LOOP_STAGES: r = enqueue_stages(c, timed, nb); break;
+    case WFPT_LOOP_FUSED: r = enqueue_fused(c, timed, nb); break;
+    case WFPT_LOOP_FUSED_BINNED: r = enqueue_fused_binned(c, timed, nb); break;
+    case WFPT_LOOP_REFILL: r = enqueue_refill(c, timed, nb); break;
     }
-    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS,
-                      [&] { return launch_generate(generate_args(c, c->tiles_x, c->tiles_y_local, true, nb), c->stream.get()); }));
-    for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
-        const int qi = static_cast<int>(b & 1u);
-        WFPT_HIP(c, timed(WFPT_STAGE_EXTEND, [&] {
-                     return launch_extend(extend_args(c, qi, &c->ctl.get()->n_in, c->capacity, nb, split), extend_grid(c, nb), c->stream.get(), env_of(c) != nullptr);
-                 }));
-        WFPT_HIP(c, timed(WFPT_STAGE_SCAN,
-                          [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), c->stream.get()); }));
-        if (split) { // one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
-            WFPT_HIP(c, timed(WFPT_STAGE_SHADE_LAMBERTIAN, [&] {
-                         ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
-                         sa.rec_in = c->hit_rec.get(); // this wavefront's extend has just written them
-                         return launch_shade(sa, consumer_grid(c, nb), c->stream.get());
-                     }));
-        } else {
-            WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] {
-                         ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
-                         sa.rec_in = c->hit_rec.get(); // this wavefront's extend has just written them
-                         return launch_shade(sa, consumer_grid(c, nb), c->stream.get());
-                     }));
-        }
-        WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] {
-                     return launch_miss(miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb), c->stream.get(), env_of(c));
-                 }));
-    }
+    if (r != WFPT_OK) return r;
     WFPT_HIP(c, timed(WFPT_STAGE_ACCUMULATE, [&] { return launch_batch_accumulate(c, nb); }));
     return WFPT_OK;
 }
@@ -1175,9 +1175,7 @@ const char *wfpt_build_info(void) {
 
 int wfpt_loop_kind_of(const wfpt_ctx *c) {
     if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_loop_kind_of: null context");
-    if (!c->fused) return WFPT_LOOP_STAGES;
-    if (c->rec_dense.get() && !c->scene.exact) return WFPT_LOOP_REFILL;
-    return use_binned(c) ? WFPT_LOOP_FUSED_BINNED : WFPT_LOOP_FUSED;
+    return loop_of(c);
 }
 
 int wfpt_device_count(void) {

@@ -300,34 +300,23 @@ struct PlanArgs {
 // ---- HBM-resident scenes: traversal with dynamic lane refill. Rays of such scenes take very
 // different numbers of steps (1M-triangle soup: mean 188, p99 650), so a wave that keeps its 64 rays until the longest one
 // ends runs at 13-17 % lane utilisation. Here every wave is an independent worker: a lane that finishes its ray takes
-// the next ray index from a global cursor (in groups, one atomic per group), sets the ray up itself (generate_rays, or
-// shade of hit h of the previous wavefront) and traces it. Results go to a DENSE per-ray array; `compact_kernel` then
-// builds the segment-compacted path-record / miss queues in ray order, so everything downstream (scan, RNG keying by
+// the next ray index from a global cursor (in groups, one atomic per group), reads the ray that generate_dense_kernel or
+// shade_rays_kernel left at full waves in a DENSE per-ray array, and traces it. Results go to the same array; `compact_kernel`
+// then builds the segment-compacted path-record / miss queues in ray order, so everything downstream (scan, RNG keying by
 // queue position, the next wavefront) sees exactly the queues the fused bounce kernel would have written.
 constexpr uint32_t kDenseMiss = 0xffffffffu, kDenseInactive = 0xfffffffeu; // primitive word of a dense record that is not a hit
-#ifndef WFPT_REFILL_IDLE
-#define WFPT_REFILL_IDLE 40
-#endif
-#ifndef WFPT_REFILL_IDLE_FIRST
-#define WFPT_REFILL_IDLE_FIRST 16
-#endif
-// refill when at least this many lanes of a wave are idle: what a refill costs (shade: ~550 instructions; generate_rays of the
-// first wavefront: ~250) against the idle lanes the traversal drags along until then
 #ifndef WFPT_TICKET_BLOCK
 #define WFPT_TICKET_BLOCK 64
 #endif
 constexpr uint32_t kTicketBlock = WFPT_TICKET_BLOCK; // ray indices a wave of the refill traversal reserves per atomic
+// refill when at least this many lanes of a wave are idle: a refill reads a ready ray, so waves refill early
 #ifndef WFPT_REFILL_IDLE_PRESHADED
-#define WFPT_REFILL_IDLE_PRESHADED 24
+#define WFPT_REFILL_IDLE_PRESHADED 24 // middle wavefronts: extension rays from shade_rays_kernel
 #endif
 #ifndef WFPT_REFILL_IDLE_FIRST_PRE
-#define WFPT_REFILL_IDLE_FIRST_PRE 16 // first wavefront with pre-generated primary rays (generate_dense_kernel)
+#define WFPT_REFILL_IDLE_FIRST_PRE 16 // first wavefront: primary rays from generate_dense_kernel
 #endif
-#ifndef WFPT_PRESHADE
-#define WFPT_PRESHADE 1 // middle wavefronts of the refill traversal: shade in a kernel of its own (shade_rays_kernel), rays through the dense array
-#endif
-constexpr uint32_t kRefillIdle = WFPT_REFILL_IDLE, kRefillIdleFirst = WFPT_REFILL_IDLE_FIRST, kRefillIdlePreshaded = WFPT_REFILL_IDLE_PRESHADED,
-                   kRefillIdleFirstPre = WFPT_REFILL_IDLE_FIRST_PRE;
+constexpr uint32_t kRefillIdlePreshaded = WFPT_REFILL_IDLE_PRESHADED, kRefillIdleFirstPre = WFPT_REFILL_IDLE_FIRST_PRE;
 
 struct RefillArgs {
     Batch batch;
@@ -511,9 +500,9 @@ hipError_t launch_bounce_binned(const BounceArgs &a, int mode, uint32_t grid, hi
 hipError_t launch_scan_binned(const ScanBinnedArgs &a, hipStream_t s);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t s);
 hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks);
-hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s, bool preshaded = false);
+hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s);
 hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s);
-hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array (WFPT_PRESHADE)
+hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array
 hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);

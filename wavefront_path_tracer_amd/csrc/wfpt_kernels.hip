@@ -127,6 +127,38 @@ __device__ __forceinline__ PrimaryRay primary_ray(const CameraDev &cam, uint32_t
     return {origin.x, origin.y, origin.z, rd.x * inv_len, rd.y * inv_len, rd.z * inv_len};
 }
 
+// generate_rays' pixel of a ray slot (gr:42-57): slot = tile * 64 + local, one 8x8 tile per 64 slots, gx tiles per row, the rows of
+// tiles this context's bands. `tile_index` is slot >> 6, passed in so that a caller whose waves hold one tile can make it a scalar.
+struct TilePixel { uint32_t x, y; };
+__device__ __forceinline__ TilePixel tile_pixel(uint32_t tile_index, uint32_t slot, uint32_t gx, Tiling tile) {
+    const uint32_t local_index = slot & 63u;
+    const uint32_t wx = tile_index % gx, wy = tile_index / gx;
+    return {wx * 8u + (local_index & 7u), (wy * tile.world + tile.rank) * 8u + (local_index >> 3)};
+}
+
+// The fused loops' generate_rays (gr:42-91) of pixel p inside the image: the kernel's pixel_idx and the primary ray `pr`, then the
+// statements USE that take the ray, then the throughput starts at 1 (pt:305-306 folded in). A macro, for the reason given at
+// WFPT_SCENE_LDS; USE keeps each kernel's stores in their order. It names the kernel's `a` (a.camera, a.tile) and pixel_idx.
+#define WFPT_START_PATH(pr, p, fb, image, ...)                                                                                         \
+    pixel_idx = (p).x + (p).y * (fb).width; /* gr:57 */                                                                                \
+    const PrimaryRay pr = primary_ray(*a.camera, (p).x, (p).y, (fb).width, (fb).height, fb);                                           \
+    __VA_ARGS__;                                                                                                                       \
+    *pixel_of(image, local_pixel(pixel_idx, (fb).width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f)
+
+// The frame of a batch's first sample, the same for every lane: kept in scalar registers
+__device__ __forceinline__ wfpt_frame_buffer uniform_frame(const Control *ctl) {
+    wfpt_frame_buffer fb = ctl->frame;
+    fb.width = uniform(fb.width); fb.height = uniform(fb.height); fb.frame = uniform(fb.frame); fb.sample_number = uniform(fb.sample_number);
+    return fb;
+}
+
+// miss_kernel's gradient sky (mk:32-33) in direction.y, which is not normalised after bounce 0
+__device__ __forceinline__ float3_ sky(float dy) {
+    const float t = 0.5f * (dy + 1.0f);
+    const float om = 1.0f - t;
+    return {om * 1.0f + t * 0.5f, om * 1.0f + t * 0.7f, om * 1.0f + t * 1.0f};
+}
+
 // ================================================================================================
 // generate_rays (gr:42-91): one thread per queue slot, slot = tile*64 + local (8x8-tile order), so a
 // wave is one 8x8 pixel tile and the SoA stores are fully coalesced.
@@ -138,24 +170,21 @@ __global__ __launch_bounds__(256) void generate_rays_kernel(GenerateArgs a) {
     const uint32_t sample = blockIdx.y; // batch slice; renders frame (base frame + sample)
     a.q = slice(a.q, sample * a.batch.ray_stride);
     a.image += sample * a.batch.image_stride;
-    const uint32_t workgroup_index = idx >> 6, local_index = idx & 63u;
-    const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-    const uint32_t id_x = wx * 8u + (local_index & 7u);
-    const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
+    const TilePixel p = tile_pixel(idx >> 6, idx, a.gx, a.tile);
     wfpt_frame_buffer fb = a.ctl->frame;
     fb.frame += sample;
     if (a.set_n_in && idx == 0) a.ctl[sample].n_in = n_threads; // pt:313-316: counter[2] = rays for the first extend
     const uint32_t width = a.true_size ? fb.width : a.gx * 8u;   // gr:55-56
     const uint32_t height = a.true_size ? fb.height : a.gy * 8u;
 
-    if (a.true_size && (id_x >= width || id_y >= height)) { // padding lane of a partial tile
+    if (a.true_size && (p.x >= width || p.y >= height)) { // padding lane of a partial tile
         a.q.ox()[idx] = 0.0f; a.q.oy()[idx] = 0.0f; a.q.oz()[idx] = 0.0f;
         a.q.dx()[idx] = 0.0f; a.q.dy()[idx] = 0.0f; a.q.dz()[idx] = 0.0f;
         a.q.pixel()[idx] = WFPT_INACTIVE_PIXEL;
         return;
     }
-    const uint32_t pixel_idx = id_x + id_y * width; // gr:57
-    const PrimaryRay pr = primary_ray(*a.camera, id_x, id_y, width, height, fb);
+    const uint32_t pixel_idx = p.x + p.y * width; // gr:57
+    const PrimaryRay pr = primary_ray(*a.camera, p.x, p.y, width, height, fb);
 
     a.q.ox()[idx] = pr.ox; a.q.oy()[idx] = pr.oy; a.q.oz()[idx] = pr.oz;
     a.q.dx()[idx] = pr.dx; a.q.dy()[idx] = pr.dy; a.q.dz()[idx] = pr.dz;
@@ -1602,9 +1631,7 @@ __global__ __launch_bounds__(kConsumerThreads) void shade_kernel(ShadeArgs a) {
 template <bool ENV>
 __device__ __forceinline__ float3_ miss_factor(const EnvDev &env, const MissQueue &mq, size_t slot, float dy) {
     if (ENV) return env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, mq.dx()[slot], dy, mq.dz()[slot]);
-    const float t = 0.5f * (dy + 1.0f); // mk:32: the direction is not normalised after bounce 0
-    const float om = 1.0f - t;
-    return {om * 1.0f + t * 0.5f, om * 1.0f + t * 0.7f, om * 1.0f + t * 1.0f}; // mk:33
+    return sky(dy);
 }
 
 template <bool ENV>
@@ -1653,7 +1680,7 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_env_kernel(MissArgs a, 
 // segment is the last one whose first hit is not after h, searched between the segments that hold the first hit of
 // this run of kChunk hits and of the next run: scan's first_seg table), multiply the pixel's throughput by the albedo
 // (sh:84-87) and, if SCATTER, produce the extension ray (origin = hit point, direction NOT normalised, sh:153-155).
-// Shared by the fused bounce kernel and the refill traversal.
+// Shared by the fused bounce kernel and the refill traversal's shade_rays_kernel.
 struct HitSource {
     const float4 *rec_in;
     const uint32_t *in_hit_base, *in_first_seg;
@@ -1683,20 +1710,20 @@ __device__ __forceinline__ void shade_record(const HitSource &s, float4 ra, floa
     }
     *px = make_float4(thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z, thr.w); // sh:84-87: throughput *= albedo, for every material type
 }
-// WAVE_RUN: every lane of the wave shades a hit of the same run of kChunk hits and the same sample (the fused bounce kernel), so the
-// run's segment bounds and the sample's counters are scalars.
+// Every lane of the wave shades a hit of the same run of kChunk hits and the same sample, so the run's segment bounds and the sample's
+// counters are scalars.
 #if WFPT_STAMPS
 #define WFPT_SHADE_STAMPS_PARAM , unsigned long long *shade_stamps = nullptr
 #else
 #define WFPT_SHADE_STAMPS_PARAM
 #endif
-template <bool SCATTER, bool WAVE_RUN = false>
+template <bool SCATTER>
 __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32_t n_hits, wfpt_frame_buffer fb, float &ox, float &oy,
                                           float &oz, float &dx, float &dy, float &dz, uint32_t &pixel_idx WFPT_SHADE_STAMPS_PARAM) {
-    const uint32_t run = WAVE_RUN ? uniform(h / kChunk) : h / kChunk, n_runs = (n_hits + kChunk - 1) / kChunk;
+    const uint32_t run = uniform(h / kChunk), n_runs = (n_hits + kChunk - 1) / kChunk;
     uint32_t lo = s.in_first_seg[s.co + run];
     uint32_t hi = run + 1 < n_runs ? s.in_first_seg[s.co + run + 1] : (umin(s.ctl->seg_n, s.capacity) + kChunk - 1) / kChunk - 1u;
-    if (WAVE_RUN) { lo = uniform(lo); hi = uniform(hi); }
+    lo = uniform(lo); hi = uniform(hi);
     while (lo < hi) {
         const uint32_t mid = (lo + hi + 1u) >> 1;
         if (s.in_hit_base[s.co + mid] <= h) lo = mid; else hi = mid - 1u;
@@ -1709,7 +1736,7 @@ __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32
 #if WFPT_STAMPS
     if (shade_stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); shade_stamps[1] = stamp_now(); } // the record has arrived
 #endif
-    shade_record<SCATTER, WAVE_RUN, WAVE_RUN>(s, ra, rb, __float_as_uint(rb.w), h, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
+    shade_record<SCATTER, true, true>(s, ra, rb, __float_as_uint(rb.w), h, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
 }
 
 // ================================================================================================
@@ -1766,6 +1793,31 @@ struct BounceLds {
 constexpr uint32_t kBounceMiscWords = 4u * kExtendWaves + 2u + 2u + kMaxBatch; // the two u16 tables take kMaxBatch words
 static_assert(kBounceMiscWords % 4u == 0, "the stack column area stays 16-byte aligned");
 
+// miss_kernel (mk:13-38), as a miss item of the fused loops: kMissSegsPerItem segments of sample SMP's miss queue of the previous
+// wavefront from segment FIRST_SEG on (N_SEGS: the wavefront's segments). One segment per wave at a time: the eight waves keep eight
+// independent load -> read-modify-write chains in flight. A macro, for the reason given at WFPT_SCENE_LDS; it names the kernel's `a`,
+// `wave` and `lane`.
+#define WFPT_MISS_ITEM(SMP, FIRST_SEG, N_SEGS)                                                                                         \
+    {                                                                                                                                  \
+        const uint32_t smp = (SMP), first_seg = (FIRST_SEG), n_segs = (N_SEGS);                                                        \
+        const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;                                                 \
+        float *image = a.image + smp * a.batch.image_stride;                                                                           \
+        for (uint32_t k = wave; k < kMissSegsPerItem; k += kExtendWaves) {                                                             \
+            const uint32_t seg = first_seg + k;                                                                                        \
+            if (seg >= n_segs) break;                                                                                                  \
+            const uint32_t count = uniform(a.in_miss[co + seg]);                                                                       \
+            for (uint32_t r = lane; r < count; r += 64u) {                                                                             \
+                const size_t slot = qo + static_cast<size_t>(seg) * kChunk + r;                                                        \
+                const float dy = a.mq_in.dy()[slot]; /* ray_buffer[miss_buffer[idx]].direction.y, mk:28-32 */                          \
+                const uint32_t pixel_idx = a.mq_in.pixel()[slot];                                                                      \
+                const float3_ c = sky(dy);                                                                                             \
+                float4 *px = pixel_of(image, local_pixel(pixel_idx, a.image_width, a.tile));                                           \
+                const float4 thr = *px;                                                                                                \
+                *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w); /* mk:35-37 */                                        \
+            }                                                                                                                          \
+        }                                                                                                                              \
+    }
+
 #ifndef WFPT_BOUNCE_ATTR
 #define WFPT_BOUNCE_ATTR __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES)
 #endif
@@ -1818,8 +1870,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         WFPT_STAGE_SCENE(g_nodes);
         __syncthreads();
     }
-    wfpt_frame_buffer fb0 = a.ctl->frame; // the same for every lane: kept in scalar registers
-    fb0.width = uniform(fb0.width); fb0.height = uniform(fb0.height); fb0.frame = uniform(fb0.frame); fb0.sample_number = uniform(fb0.sample_number);
+    const wfpt_frame_buffer fb0 = uniform_frame(a.ctl);
     const uint32_t lane = lane_id(), wave = uniform(threadIdx.x >> 6); // (a scalar: what is selected or summed per wave below runs on the scalar unit)
     uint32_t iter = 0;
 #if WFPT_STAMPS
@@ -1830,32 +1881,8 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         const uint32_t buf = iter & 1u;
         if (threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
         if (!ENV && item >= n_hit_items) {
-            // ---------------- miss_kernel (mk:13-38) for kMissSegsPerItem segments of the previous wavefront's miss queue
             while (item >= first_m + uniform(L.items_m[smp_m])) first_m += uniform(L.items_m[smp_m++]);
-            const uint32_t smp = smp_m;
-            const uint32_t first_seg = (item - first_m) * kMissSegsPerItem;
-            const uint32_t n_segs = (uniform(umin(a.ctl[smp].seg_n, a.capacity)) + kChunk - 1) / kChunk;
-            const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
-            float *image = a.image + smp * a.batch.image_stride;
-            // one segment per wave at a time: the eight waves keep eight independent load -> read-modify-write chains in flight
-            for (uint32_t k = wave; k < kMissSegsPerItem; k += kExtendWaves) {
-                const uint32_t seg = first_seg + k;
-                if (seg >= n_segs) break;
-                const uint32_t count = uniform(a.in_miss[co + seg]);
-                for (uint32_t r = lane; r < count; r += 64u) {
-                    const size_t slot = qo + static_cast<size_t>(seg) * kChunk + r;
-                    const float dy = a.mq_in.dy()[slot]; // ray_buffer[miss_buffer[idx]].direction.y, mk:28-32
-                    const uint32_t pixel_idx = a.mq_in.pixel()[slot];
-                    const float t = 0.5f * (dy + 1.0f); // mk:32: the direction is not normalised after bounce 0
-                    const float om = 1.0f - t;
-                    const float cr = om * 1.0f + t * 0.5f; // mk:33
-                    const float cg = om * 1.0f + t * 0.7f;
-                    const float cb = om * 1.0f + t * 1.0f;
-                    float4 *px = pixel_of(image, local_pixel(pixel_idx, a.image_width, a.tile));
-                    const float4 thr = *px;
-                    *px = make_float4(thr.x * cr, thr.y * cg, thr.z * cb, thr.w); // mk:35-37
-                }
-            }
+            WFPT_MISS_ITEM(smp_m, (item - first_m) * kMissSegsPerItem, (uniform(umin(a.ctl[smp_m].seg_n, a.capacity)) + kChunk - 1) / kChunk);
             __syncthreads(); // L.next[buf] is visible
             ticket = uniform(L.next[buf]);
             item = tickets.item_of(ticket);
@@ -1878,16 +1905,10 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         uint32_t pixel_idx = 0;
         if (MODE == kBounceFirst) {
             // ---------------- generate_rays (gr:42-91), true-size semantics: lanes outside the image emit nothing
-            const uint32_t workgroup_index = uniform(h >> 6), local_index = h & 63u; // one wave = one 8x8 tile of generate_rays
-            const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-            const uint32_t id_x = wx * 8u + (local_index & 7u);
-            const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
-            live = live && id_x < fb.width && id_y < fb.height;
+            const TilePixel p = tile_pixel(uniform(h >> 6), h, a.gx, a.tile); // one wave = one 8x8 tile of generate_rays
+            live = live && p.x < fb.width && p.y < fb.height;
             if (live) {
-                pixel_idx = id_x + id_y * fb.width; // gr:57
-                const PrimaryRay pr = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
-                ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz;
-                *pixel_of(image, local_pixel(pixel_idx, fb.width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f); // pt:305-306 folded in: throughput starts at 1
+                WFPT_START_PATH(pr, p, fb, image, ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz);
             }
         } else if (live) {
             // ---------------- shade (sh:56-156) of hit h of the previous wavefront
@@ -1895,10 +1916,10 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
                                 a.capacity, a.rng_mode, a.image_width, a.scene.prim_kind, a.tile};
 #if WFPT_STAMPS
             unsigned long long sst[2] = {t_item, t_item};
-            shade_hit<TRACE, true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, sst);
+            shade_hit<TRACE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, sst);
             if (MODE == kBounceMiddle) { acc_search += sst[0] - t_item; acc_record += sst[1] - sst[0]; }
 #else
-            shade_hit<TRACE, true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
+            shade_hit<TRACE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
 #endif
         }
         if (!TRACE) {
@@ -2037,8 +2058,7 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
             s_cls[i] = static_cast<uint8_t>(umin(__float_as_uint(a.scene.shade_rec[3u * i + 2u].y), static_cast<uint32_t>(K - 1)));
         __syncthreads();
     }
-    wfpt_frame_buffer fb0 = a.ctl->frame; // the same for every lane: kept in scalar registers
-    fb0.width = uniform(fb0.width); fb0.height = uniform(fb0.height); fb0.frame = uniform(fb0.frame); fb0.sample_number = uniform(fb0.sample_number);
+    const wfpt_frame_buffer fb0 = uniform_frame(a.ctl);
     const uint32_t lane = lane_id(), wave = uniform(threadIdx.x >> 6);
     uint32_t idx_h = 0, idx_m = 0; // a workgroup's tickets only grow: the plan is searched on from where the previous item was found
     uint32_t iter = 0;
@@ -2046,31 +2066,8 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
         const uint32_t buf = iter & 1u;
         if (threadIdx.x == 0) s_next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
         if (item >= n_hit_items) {
-            // ---------------- miss_kernel (mk:13-38) for kMissSegsPerItem segments of the previous wavefront's miss queue
             while (item >= uniform(plan_m[idx_m + 1])) ++idx_m;
-            const uint32_t smp = idx_m;
-            const uint32_t first_seg = (item - uniform(plan_m[idx_m])) * kMissSegsPerItem;
-            const uint32_t n_segs = uniform(a.ctl[smp].n_segs);
-            const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
-            float *image = a.image + smp * a.batch.image_stride;
-            for (uint32_t k = wave; k < kMissSegsPerItem; k += kExtendWaves) { // one segment per wave at a time
-                const uint32_t seg = first_seg + k;
-                if (seg >= n_segs) break;
-                const uint32_t count = uniform(a.in_miss[co + seg]);
-                for (uint32_t r = lane; r < count; r += 64u) {
-                    const size_t slot = qo + static_cast<size_t>(seg) * kChunk + r;
-                    const float dy = a.mq_in.dy()[slot]; // ray_buffer[miss_buffer[idx]].direction.y, mk:28-32
-                    const uint32_t pixel_idx = a.mq_in.pixel()[slot];
-                    const float t = 0.5f * (dy + 1.0f); // mk:32: the direction is not normalised after bounce 0
-                    const float om = 1.0f - t;
-                    const float cr = om * 1.0f + t * 0.5f; // mk:33
-                    const float cg = om * 1.0f + t * 0.7f;
-                    const float cb = om * 1.0f + t * 1.0f;
-                    float4 *px = pixel_of(image, local_pixel(pixel_idx, a.image_width, a.tile));
-                    const float4 thr = *px;
-                    *px = make_float4(thr.x * cr, thr.y * cg, thr.z * cb, thr.w); // mk:35-37
-                }
-            }
+            WFPT_MISS_ITEM(idx_m, (item - uniform(plan_m[idx_m])) * kMissSegsPerItem, uniform(a.ctl[idx_m].n_segs));
             __syncthreads(); // s_next[buf] is visible
             ticket = uniform(s_next[buf]);
             item = tickets.item_of(ticket);
@@ -2101,16 +2098,10 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES) void bounce_
         if (MODE == kBounceFirst) {
             // ---------------- generate_rays (gr:42-91), true-size semantics: lanes outside the image emit nothing
             const uint32_t h = seg_out * kChunk + threadIdx.x;
-            const uint32_t workgroup_index = uniform(h >> 6), local_index = h & 63u; // one wave = one 8x8 tile of generate_rays
-            const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-            const uint32_t id_x = wx * 8u + (local_index & 7u);
-            const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
-            live = h < n_first && id_x < fb.width && id_y < fb.height;
+            const TilePixel p = tile_pixel(uniform(h >> 6), h, a.gx, a.tile); // one wave = one 8x8 tile of generate_rays
+            live = h < n_first && p.x < fb.width && p.y < fb.height;
             if (live) {
-                pixel_idx = id_x + id_y * fb.width; // gr:57
-                const PrimaryRay pr = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
-                ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz;
-                *pixel_of(image, local_pixel(pixel_idx, fb.width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f); // pt:305-306 folded in: throughput starts at 1
+                WFPT_START_PATH(pr, p, fb, image, ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz);
             }
         } else {
             // ---------------- the hit record of the previous wavefront this lane shades
@@ -2394,16 +2385,15 @@ __global__ __launch_bounds__(kPlanThreads) void plan_kernel(PlanArgs a) {
 
 // ================================================================================================
 // HBM-resident scenes: four-wide traversal with dynamic lane refill + dense results + compaction (see RefillArgs).
-// MODE kBounceFirst: ray G is slot G of generate_rays' numbering; kBounceMiddle: ray G is the extension ray of hit G of
-// the previous wavefront (shade runs at refill time, by the lane that takes the ray).
+// MODE kBounceFirst: ray G is primary ray G of generate_rays' numbering (generate_dense_kernel); kBounceMiddle: ray G is the
+// extension ray of hit G of the previous wavefront (shade_rays_kernel). Both wait in the dense array at their ray's slot,
+// (o | pixel), (d | -); a lane that takes ray g reads its 32 bytes, traces, and leaves the result in the same slot. A refill
+// then costs next to nothing, so waves refill early.
 // ================================================================================================
 #ifndef WFPT_REFILL_MIN_WAVES
 #define WFPT_REFILL_MIN_WAVES 8
 #endif
-// PRESHADED (middle wavefronts): the extension rays were produced by shade_rays_kernel -- shade at 64 lanes per wave instead of at
-// the 24-40 idle lanes of a refill -- and wait in the dense array at their ray's slot, (o | pixel), (d | -); a lane that takes ray g
-// reads its 32 bytes, traces, and leaves the result in the same slot. A refill then costs next to nothing, so waves refill early.
-template <int MODE, int PRIM, bool PRESHADED = false>
+template <int MODE, int PRIM>
 __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_kernel(RefillArgs a) {
     extern __shared__ float4 lds[];
     uint32_t *s_n = reinterpret_cast<uint32_t *>(lds);   // [kMaxBatch] rays of this wavefront per sample
@@ -2434,8 +2424,6 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
         for (uint32_t i = threadIdx.x; i < 4u * tile_n; i += kExtendThreads) tile_w[i] = a.scene.nodes4[i];
         __syncthreads();
     }
-    wfpt_frame_buffer fb0 = a.ctl->frame; // the same for every lane: kept in scalar registers
-    fb0.width = uniform(fb0.width); fb0.height = uniform(fb0.height); fb0.frame = uniform(fb0.frame); fb0.sample_number = uniform(fb0.sample_number);
     const uint32_t lane = lane_id();
     uint32_t smp_cur = 0; // sample of the last group's first ray: a wave's tickets only grow, so the search goes on from there
     Stack4 st;
@@ -2465,7 +2453,7 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
         // ---------------- refill: idle lanes take the next rays
         const unsigned long long idle = __ballot(!alive);
         const uint32_t n_idle = static_cast<uint32_t>(__popcll(idle));
-        if ((more || cur_ray < end_ray) && (n_idle >= (PRESHADED ? (MODE == kBounceFirst ? kRefillIdleFirstPre : kRefillIdlePreshaded) : (MODE == kBounceFirst ? kRefillIdleFirst : kRefillIdle)))) {
+        if ((more || cur_ray < end_ray) && n_idle >= (MODE == kBounceFirst ? kRefillIdleFirstPre : kRefillIdlePreshaded)) {
             // idle lane number `rank` takes ray `g`: first what is left of the wave's block, then (one atomic) the head of the next one,
             // so that every idle lane is served in this pass
             const uint32_t rank = mbcnt(idle);
@@ -2498,43 +2486,16 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
                 smp = smp_cur;
                 while (g >= s_first[smp + 1]) ++smp; // a group rarely straddles samples
                 ray = g - s_first[smp];
-                float *image = a.image + smp * a.batch.image_stride;
-                wfpt_frame_buffer fb = fb0;
-                fb.frame += smp;
-                bool ok = true;
-                float ox = 0, oy = 0, oz = 0;
-                if (PRESHADED) { // the ray waits in the dense array: the extension ray of hit `ray` (shade_rays_kernel), or primary ray `ray` (generate_dense_kernel)
-                    const size_t slot = smp * a.batch.queue_stride + ray;
-                    const float4 ra = a.dense_out[2u * slot], rb = a.dense_out[2u * slot + 1u];
-                    ox = ra.x; oy = ra.y; oz = ra.z; pixel_idx = __float_as_uint(ra.w);
-                    dx = rb.x; dy = rb.y; dz = rb.z;
-                    if (MODE == kBounceFirst) ok = __float_as_uint(rb.w) != kDenseInactive; // a lane outside the image: neither hit nor miss, the marker stays
-                } else if (MODE == kBounceFirst) { // generate_rays (gr:42-91), true-size semantics
-                    const uint32_t workgroup_index = ray >> 6, local_index = ray & 63u;
-                    const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-                    const uint32_t id_x = wx * 8u + (local_index & 7u);
-                    const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
-                    ok = id_x < fb.width && id_y < fb.height;
-                    if (ok) {
-                        pixel_idx = id_x + id_y * fb.width;
-                        const PrimaryRay pr = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
-                        ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz;
-                        *pixel_of(image, local_pixel(pixel_idx, fb.width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-                    } else { // a lane outside the image: neither hit nor miss
-                        const size_t slot = smp * a.batch.queue_stride + ray;
-                        a.dense_out[2u * slot + 1u] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kDenseInactive));
-                    }
-                } else { // shade (sh:56-156) of hit `ray` of the previous wavefront
-                    const HitSource src{a.rec_in, a.in_hit_base, a.in_first_seg, a.ctl + smp, image, a.scene.shade_rec,
-                                        smp * a.batch.queue_stride, smp * a.batch.chunk_stride, a.capacity, a.rng_mode, a.image_width,
-                                        a.scene.prim_kind, a.tile};
-                    shade_hit<true>(src, ray, s_n[smp], fb, ox, oy, oz, dx, dy, dz, pixel_idx);
-                }
-                if (ok) {
-                    r4 = make_ray4(ox, oy, oz, dx, dy, dz);
+                // the ray waits in the dense array: the extension ray of hit `ray` (shade_rays_kernel), or primary ray `ray` (generate_dense_kernel)
+                const size_t slot = smp * a.batch.queue_stride + ray;
+                const float4 ra = a.dense_out[2u * slot], rb = a.dense_out[2u * slot + 1u];
+                pixel_idx = __float_as_uint(ra.w);
+                dx = rb.x; dy = rb.y; dz = rb.z;
+                if (MODE != kBounceFirst || __float_as_uint(rb.w) != kDenseInactive) { // (a lane outside the image: neither hit nor miss, the marker stays)
+                    r4 = make_ray4(ra.x, ra.y, ra.z, dx, dy, dz);
                     nearest = 1e30f; best = 0xffffffffu; cur = 0; st.reset(); budget = a.scene.n_nodes;
                     alive = true;
-                    if (far_origin(a.scene, ox, oy, oz)) hand_over(nearest, best); // (the walk then runs out at once; the re-trace at its end decides)
+                    if (far_origin(a.scene, ra.x, ra.y, ra.z)) hand_over(nearest, best); // (the walk then runs out at once; the re-trace at its end decides)
                 }
             }
         }
@@ -2631,8 +2592,8 @@ __global__ __launch_bounds__(kExtendThreads) void shade_rays_kernel(RefillArgs a
     const uint32_t smp = blockIdx.y;
     const uint32_t n = uniform(umin(a.ctl[smp].shade_n, a.capacity));
     if (blockIdx.x * kChunk >= n) return;
-    wfpt_frame_buffer fb = a.ctl->frame;
-    fb.width = uniform(fb.width); fb.height = uniform(fb.height); fb.frame = uniform(fb.frame) + smp; fb.sample_number = uniform(fb.sample_number);
+    wfpt_frame_buffer fb = uniform_frame(a.ctl);
+    fb.frame += smp;
     const uint32_t h = blockIdx.x * kChunk + threadIdx.x;
     if (h >= n) return;
     const HitSource src{a.rec_in, a.in_hit_base, a.in_first_seg, a.ctl + smp, a.image + smp * a.batch.image_stride, a.scene.shade_rec,
@@ -2640,7 +2601,7 @@ __global__ __launch_bounds__(kExtendThreads) void shade_rays_kernel(RefillArgs a
                         a.scene.prim_kind, a.tile};
     float ox, oy, oz, dx, dy, dz;
     uint32_t pixel_idx;
-    shade_hit<true, true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
+    shade_hit<true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
     const size_t slot = smp * a.batch.queue_stride + h;
     a.dense_out[2u * slot] = make_float4(ox, oy, oz, __uint_as_float(pixel_idx));
     a.dense_out[2u * slot + 1u] = make_float4(dx, dy, dz, 0.0f);
@@ -2654,19 +2615,15 @@ __global__ __launch_bounds__(256) void generate_dense_kernel(RefillArgs a) {
     const uint32_t n = umin(a.gx * a.gy * 64u, a.capacity);
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
-    wfpt_frame_buffer fb = a.ctl->frame;
-    fb.width = uniform(fb.width); fb.height = uniform(fb.height); fb.frame = uniform(fb.frame) + smp; fb.sample_number = uniform(fb.sample_number);
-    const uint32_t workgroup_index = g >> 6, local_index = g & 63u; // one wave = one 8x8 tile of generate_rays
-    const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-    const uint32_t id_x = wx * 8u + (local_index & 7u);
-    const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
+    wfpt_frame_buffer fb = uniform_frame(a.ctl);
+    fb.frame += smp;
+    const TilePixel p = tile_pixel(g >> 6, g, a.gx, a.tile); // one wave = one 8x8 tile of generate_rays
     const size_t slot = smp * a.batch.queue_stride + g;
-    if (id_x < fb.width && id_y < fb.height) {
-        const uint32_t pixel_idx = id_x + id_y * fb.width; // gr:57
-        const PrimaryRay pr = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
-        a.dense_out[2u * slot] = make_float4(pr.ox, pr.oy, pr.oz, __uint_as_float(pixel_idx));
-        a.dense_out[2u * slot + 1u] = make_float4(pr.dx, pr.dy, pr.dz, 0.0f);
-        *pixel_of(a.image + smp * a.batch.image_stride, local_pixel(pixel_idx, fb.width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f); // pt:305-306 folded in
+    if (p.x < fb.width && p.y < fb.height) {
+        uint32_t pixel_idx;
+        WFPT_START_PATH(pr, p, fb, a.image + smp * a.batch.image_stride,
+                        a.dense_out[2u * slot] = make_float4(pr.ox, pr.oy, pr.oz, __uint_as_float(pixel_idx));
+                        a.dense_out[2u * slot + 1u] = make_float4(pr.dx, pr.dy, pr.dz, 0.0f));
     } else {
         a.dense_out[2u * slot + 1u] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kDenseInactive));
     }
@@ -2868,17 +2825,13 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
         __syncthreads();
     }
     const float4 *geom = LDS_SCENE ? s_geom : a.scene.prim_geom;
-    wfpt_frame_buffer fb0 = a.ctl->frame; // the batch's first frame (accumulate advances it after the batch)
-    fb0.width = uniform(fb0.width); fb0.height = uniform(fb0.height); fb0.frame = uniform(fb0.frame); fb0.sample_number = uniform(fb0.sample_number);
+    const wfpt_frame_buffer fb0 = uniform_frame(a.ctl); // the batch's first frame (accumulate advances it after the batch)
     const size_t plane = a.plane;
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const uint32_t idx = item * kExtendThreads + threadIdx.x;
-        const uint32_t workgroup_index = idx >> 6, local_index = idx & 63u; // gr:42-57, as generate_rays_kernel
-        const uint32_t wx = workgroup_index % a.gx, wy = workgroup_index / a.gx;
-        const uint32_t id_x = wx * 8u + (local_index & 7u);
-        const uint32_t id_y = (wy * a.tile.world + a.tile.rank) * 8u + (local_index >> 3);
-        if (idx >= n_slots || id_x >= fb0.width || id_y >= fb0.height) continue; // padding lane of a partial tile
-        const uint32_t px = local_pixel(id_x + id_y * fb0.width, fb0.width, a.tile);
+        const TilePixel p = tile_pixel(idx >> 6, idx, a.gx, a.tile); // gr:42-57, as generate_rays_kernel
+        if (idx >= n_slots || p.x >= fb0.width || p.y >= fb0.height) continue; // padding lane of a partial tile
+        const uint32_t px = local_pixel(p.x + p.y * fb0.width, fb0.width, a.tile);
         float alb_r = a.sums[kAovAlbedo * plane + px], alb_g = a.sums[(kAovAlbedo + 1u) * plane + px], alb_b = a.sums[(kAovAlbedo + 2u) * plane + px];
         float nrm_x = a.sums[kAovNormal * plane + px], nrm_y = a.sums[(kAovNormal + 1u) * plane + px], nrm_z = a.sums[(kAovNormal + 2u) * plane + px];
         float depth = a.sums[kAovDepth * plane + px];
@@ -2887,7 +2840,7 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
         for (uint32_t smp = 0; smp < a.n; ++smp) {
             wfpt_frame_buffer fb = fb0;
             fb.frame += smp;
-            const PrimaryRay r = primary_ray(*a.camera, id_x, id_y, fb.width, fb.height, fb);
+            const PrimaryRay r = primary_ray(*a.camera, p.x, p.y, fb.width, fb.height, fb);
             float t = 0.0f;
             uint32_t prim = 0;
 #if WFPT_STAMPS
@@ -2917,11 +2870,8 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
                     mat_w = kAovMissWord;
                 }
             } else { // miss_kernel's sky colour (mk:32-33)
-                const float sky = 0.5f * (r.dy + 1.0f);
-                const float om = 1.0f - sky;
-                alb_r += om * 1.0f + sky * 0.5f;
-                alb_g += om * 1.0f + sky * 0.7f;
-                alb_b += om * 1.0f + sky * 1.0f;
+                const float3_ c = sky(r.dy);
+                alb_r += c.x; alb_g += c.y; alb_b += c.z;
                 nrm_x += 0.0f; nrm_y += 0.0f; nrm_z += 0.0f; // a miss adds its zero normal like any other sample
                 if (prim_w == 0u) {
                     prim_w = kAovMissWord;
@@ -3436,13 +3386,11 @@ namespace {
 constexpr uint32_t kRefillLdsFixed = 4u * (2u * kMaxBatch + 4u + kStack4Lds * kExtendThreads); // + 64 B per staged node
 }
 
-hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s, bool preshaded) {
+hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
     using Fn = void (*)(RefillArgs);
     Fn fn;
-    if (mode == kBounceFirst && preshaded) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceFirst, 0, true> : refill_kernel<kBounceFirst, 1, true>;
-    else if (mode == kBounceFirst) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceFirst, 0> : refill_kernel<kBounceFirst, 1>;
-    else if (preshaded) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceMiddle, 0, true> : refill_kernel<kBounceMiddle, 1, true>;
+    if (mode == kBounceFirst) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceFirst, 0> : refill_kernel<kBounceFirst, 1>;
     else fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceMiddle, 0> : refill_kernel<kBounceMiddle, 1>;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kExtendThreads), kRefillLdsFixed + 64u * a.scene.tile_n, s, a);
     return hipGetLastError();
