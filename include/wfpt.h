@@ -65,7 +65,8 @@ typedef struct wfpt_triangle {
     float e1[3];
     uint32_t material_type;
     float e2[3];
-    uint32_t _pad;
+    uint32_t _pad;          /* WFPT_FLAG_TEXTURES: the triangle's row in the context's UV table (wfpt_set_triangle_uvs); 0 otherwise. The
+                               BVH builders move a triangle whole, so the row follows it when they reorder. */
 } wfpt_triangle;
 
 /* wavefront_common/src/camera_controller.rs:161-185 == generate_rays.wgsl:13-19 */
@@ -216,7 +217,11 @@ enum {
                                         of accumulate_kernel). Without the flag nothing is allocated or launched. */
     WFPT_FLAG_ENVIRONMENT = 1u << 12 /* misses lit by an HDR environment map, see "Environment map" below: the miss queues carry the full
                                         direction (two more planes). Without a map set the context renders the gradient sky, bit for bit;
-                                        without the flag nothing is allocated or launched. */
+                                        without the flag nothing is allocated or launched. */,
+    WFPT_FLAG_TEXTURES = 1u << 13    /* image textures on spheres and triangle meshes, see "Textures" below: up to WFPT_MAX_TEXTURES slots, a
+                                        material bound to a slot multiplies the throughput of its hits by the texture as well as by its
+                                        albedo. With nothing bound the context renders bit for bit as without the flag, and launches the
+                                        same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -272,6 +277,11 @@ int wfpt_build_bvh_triangles_device(wfpt_triangle *triangles, uint32_t n_triangl
  * WFPT_ERR_INVALID_ARGUMENT for an unreadable file, a bad index or too small a capacity. */
 int wfpt_load_obj(const char *path, wfpt_triangle *triangles, uint32_t capacity, uint32_t *n_triangles,
                   uint32_t material_idx, uint32_t material_type);
+/* wfpt_load_obj plus texture coordinates (WFPT_FLAG_TEXTURES): also reads `vt u v [w]` records, and writes triangle i of the file (in file
+ * order, after fan triangulation) with _pad = i and row i of uv6 (6 floats: u0 v0 u1 v1 u2 v2) from its corners' `t` indices (1-based or
+ * negative); corners without one get (0, 0). uv6 holds `capacity` rows; both NULL only counts. */
+int wfpt_load_obj_uv(const char *path, wfpt_triangle *triangles, float *uv6, uint32_t capacity, uint32_t *n_triangles,
+                     uint32_t material_idx, uint32_t material_type);
 /* BASELINE config 5: seeded triangle soup -- centres U[-10,10]^3, edges U[-0.05,0.05]^3, material i % 3 over
  * {Lambertian 0.7, Metal 0.8 fuzz 0.1, Dielectric 1.5}. Writes n triangles and 3 materials; returns 3. */
 uint32_t wfpt_scene_random_mesh(uint64_t seed, uint32_t n_triangles, wfpt_triangle *triangles, wfpt_material *materials);
@@ -598,6 +608,55 @@ int wfpt_clear_environment(wfpt_ctx *ctx);
 /* the lookup above on the device for n caller directions (xyz, 3 floats each) into rgb_out (3 floats each); WFPT_ERR_INVALID_ARGUMENT when
  * no map is set. Blocking. */
 int wfpt_sample_environment(wfpt_ctx *ctx, const float *dirs, size_t n, float *rgb_out);
+
+/* ------------------------------------------------------------------ Textures (WFPT_FLAG_TEXTURES): image textures on surfaces
+ * A context created with WFPT_FLAG_TEXTURES holds WFPT_MAX_TEXTURES texture slots, and a material can be bound to a slot. Every hit on a
+ * primitive whose material is bound is shaded, for every material type, with
+ *   thr <- (thr * tex) * albedo      per channel, two IEEE f32 multiplies (unbound materials: thr <- thr * albedo, as without the flag)
+ * where tex is the texture's value at the hit's UV (wfpt_device_math.h, IEEE f32 operations only, no fma):
+ *   spheres:   n = normalize3(p - centre);  u = atan2_(-n.z, n.x) / 2pi + 0.5;  v = atan2_(sqrt(n.x n.x + n.z n.z), -n.y) / pi
+ *   triangles: w = p - v0; d00 = e1.e1, d01 = e1.e2, d11 = e2.e2, d20 = w.e1, d21 = w.e2; den = d00 d11 - d01 d01;
+ *              b1 = b2 = 0 unless den > 0, else b1 = (d11 d20 - d01 d21) / den, b2 = (d00 d21 - d01 d20) / den (one reciprocal, two products);
+ *              b0 = (1 - b1) - b2;  uv = (uv0 b0 + uv1 b1) + uv2 b2 with the corner UVs of the triangle's row (_pad) of the UV table,
+ *              (0, 0) at every corner when no table is set
+ *   lookup:    u' = u scale.u + offset.u, u' <- u' - floor(u') (the same for v'): both axes repeat; row 0 of the image is the top (v' = 1)
+ *              bilinear: x = u' w - 0.5, y = (1 - v') h - 0.5, texel centres at half-integers, columns wrap modulo w and rows modulo h,
+ *                        ((t00 w00 + t10 w10) + t01 w01) + t11 w11 with w00 = (1-fx)(1-fy), w10 = fx (1-fy), w01 = (1-fx) fy, w11 = fx fy
+ *              nearest:  column min(floor(u' w), w - 1), row min(floor((1 - v') h), h - 1)
+ * Textures change no scattering, RNG, traversal, miss or exit decision. With WFPT_FLAG_AOV a primary hit adds tex * albedo to the albedo sum.
+ * wfpt_set_texture, wfpt_clear_texture, wfpt_bind_texture and wfpt_set_triangle_uvs act like wfpt_set_environment: the accumulation and the
+ * frame counter restart, the temporal history and the captured graphs are dropped. wfpt_update_scene* and viewport changes keep the slots,
+ * the bindings and the UV table. A refused call leaves the context as it was. WFPT_ERR_INVALID_ARGUMENT without the flag, for a slot out of
+ * range, a binding to an empty slot, a bad size, texel or parameter, a UV that is not finite, and a triangle whose row is >= the rows of a set
+ * UV table (checked by wfpt_set_triangle_uvs and wfpt_update_scene_mesh); WFPT_ERR_UNSUPPORTED for a call that would texture a
+ * WFPT_LOOP_FUSED_BINNED context (a context with a binding never runs the class-binned loop). wfpt_render_chunked* masks the flag off.
+ * Out of scope: mip-mapping, normal / bump / roughness maps, per-vertex normals, .mtl files. */
+#define WFPT_MAX_TEXTURES 64u
+typedef enum wfpt_texture_filter { WFPT_TEXTURE_BILINEAR = 0, WFPT_TEXTURE_NEAREST = 1 } wfpt_texture_filter;
+typedef struct wfpt_texture_params {
+    float scale[2];            /* finite; default (1, 1) */
+    float offset[2];           /* finite; default (0, 0) */
+    uint32_t filter;           /* a wfpt_texture_filter: WFPT_TEXTURE_BILINEAR (default) or WFPT_TEXTURE_NEAREST */
+    uint32_t _reserved[3];     /* must be 0 */
+} wfpt_texture_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_texture_params) == 32 && offsetof(wfpt_texture_params, offset) == 8 &&
+                       offsetof(wfpt_texture_params, filter) == 16 && offsetof(wfpt_texture_params, _reserved) == 20,
+                   "wfpt_texture_params: 32 bytes");
+/* scale (1, 1), offset (0, 0), bilinear, _reserved zeroed */
+void wfpt_texture_params_default(wfpt_texture_params *p);
+/* rgb: h rows of w texels, 3 floats each (linear, row-major, row 0 = the top), finite and >= 0; 1 <= w, h <= 16384. Stored on the device as
+ * float4 texels in slot `slot`, replacing what it held (its bindings stay). p may be NULL (the defaults). Blocking. */
+int wfpt_set_texture(wfpt_ctx *ctx, uint32_t slot, const float *rgb, uint32_t w, uint32_t h, const wfpt_texture_params *p);
+/* empties the slot and unbinds the materials bound to it */
+int wfpt_clear_texture(wfpt_ctx *ctx, uint32_t slot);
+/* binds material material_idx (< the scene's materials) to slot (which must hold a texture); slot -1 unbinds */
+int wfpt_bind_texture(wfpt_ctx *ctx, uint32_t material_idx, int32_t slot);
+/* the UV table: n_rows rows of u0 v0 u1 v1 u2 v2 (finite), row r for the triangles whose _pad is r; NULL / 0 clears it */
+int wfpt_set_triangle_uvs(wfpt_ctx *ctx, const float *uv6, uint32_t n_rows);
+/* the lookup above on the device for n caller UVs (2 floats each) into rgb_out (3 floats each); the slot must hold a texture. Blocking. */
+int wfpt_sample_texture(wfpt_ctx *ctx, uint32_t slot, const float *uv, size_t n, float *rgb_out);
+/* the texture launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
+int wfpt_texture_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -35,6 +35,9 @@ LOOP_KINDS = ("stages", "fused", "fused_binned", "refill")  # wfpt_loop_kind
 FLAG_SPLIT_SHADE, FLAG_NO_GRAPH, FLAG_UNFUSED, FLAG_BINARY_BVH, FLAG_NO_REFILL, FLAG_NO_LDS_SCENE, FLAG_EXACT_TRAVERSAL, FLAG_NO_BINNING, FLAG_BINNING = 1, 2, 4, 8, 16, 32, 64, 128, 256
 FLAG_AOV = 1 << 10  # first-hit AOVs (include/wfpt.h "AOVs"); bit 9 is the retired WFPT_FLAG_TWO_CHAINS
 FLAG_ENVIRONMENT = 1 << 12  # misses lit by an HDR environment map (include/wfpt.h "Environment map")
+FLAG_TEXTURES = 1 << 13  # image textures on spheres and triangles (include/wfpt.h "Textures")
+MAX_TEXTURES = 64  # WFPT_MAX_TEXTURES
+TEXTURE_FILTERS = {"bilinear": 0, "nearest": 1}
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -94,6 +97,10 @@ class _DenoiseParams(C.Structure):
 
 class _EnvironmentParams(C.Structure):
     _fields_ = [("intensity", C.c_float), ("rotation", C.c_float), ("_reserved", C.c_uint32 * 6)]
+
+
+class _TextureParams(C.Structure):
+    _fields_ = [("scale", C.c_float * 2), ("offset", C.c_float * 2), ("filter", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
 
 
 class _TemporalParams(C.Structure):
@@ -323,6 +330,14 @@ def lib():
         "wfpt_set_environment": (i32, [vp, vp, u32, u32, C.POINTER(_EnvironmentParams)]),
         "wfpt_clear_environment": (i32, [vp]),
         "wfpt_sample_environment": (i32, [vp, vp, sz, vp]),
+        "wfpt_texture_params_default": (None, [C.POINTER(_TextureParams)]),
+        "wfpt_set_texture": (i32, [vp, u32, vp, u32, u32, C.POINTER(_TextureParams)]),
+        "wfpt_clear_texture": (i32, [vp, u32]),
+        "wfpt_bind_texture": (i32, [vp, u32, C.c_int32]),
+        "wfpt_set_triangle_uvs": (i32, [vp, vp, u32]),
+        "wfpt_sample_texture": (i32, [vp, u32, vp, sz, vp]),
+        "wfpt_texture_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_load_obj_uv": (i32, [C.c_char_p, vp, vp, u32, C.POINTER(u32), u32, u32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -467,6 +482,94 @@ def _read_hdr(data):
     return (rgbe[..., :3].astype(np.float64) * scale[..., None]).astype("<f4")
 
 
+def load_texture(path):
+    """A texture image as an (h, w, 3) float32 array of linear RGB, row 0 = the top: 8-bit PNG (grey, RGB or RGBA, non-interlaced) or binary
+    PPM (P6), decoded from sRGB; or PFM / Radiance .hdr, linear as stored (the environment map's readers)."""
+    data = open(path, "rb").read()
+    if data[:8] == b"\x89PNG\r\n\x1a\n":
+        return _srgb_to_linear(_read_png(data))
+    if data[:2] == b"P6":
+        return _srgb_to_linear(_read_ppm(data))
+    if data[:2] in (b"PF", b"Pf"):
+        return _read_pfm(data)
+    if data[:2] == b"#?":
+        return _read_hdr(data)
+    raise ValueError(f"load_texture: {path} is not a PNG, PPM (P6), PFM or Radiance .hdr file")
+
+
+def _srgb_to_linear(rgb8):
+    c = rgb8.astype(np.float64) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype("<f4")
+
+
+def _read_ppm(data):
+    fields, pos = [], 0
+    while len(fields) < 4:  # "P6", width, height, maxval; comments run to the end of their line
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        if data[pos:pos + 1] == b"#":
+            pos = data.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        fields.append(data[pos:end].decode("ascii"))
+        pos = end
+    pos += 1
+    w, h, maxval = int(fields[1]), int(fields[2]), int(fields[3])
+    if maxval != 255:
+        raise ValueError("load_texture: only 8-bit PPM files (maxval 255) are supported")
+    return np.frombuffer(data, np.uint8, count=w * h * 3, offset=pos).reshape(h, w, 3)
+
+
+def _png_unfilter(raw, w, ch):
+    """The five scanline filters of PNG (spec 9.2) undone for a whole image: raw (h, 1 + w * ch) uint8 -> (h, w, ch) uint8. A pixel depends
+    on its reconstructed left, upper and upper-left neighbours only, so every anti-diagonal x + y = d depends on earlier diagonals alone:
+    the image is reconstructed one diagonal at a time, each as one vector step over its pixels (h + w steps, not h * w * ch)."""
+    h = raw.shape[0]
+    filt = raw[:, 0].astype(np.int32)
+    if (filt > 4).any():
+        raise ValueError(f"load_texture: unknown PNG filter type {int(filt.max())}")
+    line = raw[:, 1:].reshape(h, w, ch).astype(np.int32)
+    rec = np.zeros((h + 1, w + 1, ch), np.int32)  # row 0 and column 0: the zero neighbours outside the image
+    for d in range(h + w - 1):
+        y = np.arange(max(0, d - w + 1), min(h, d + 1))
+        x = d - y
+        a, b, c = rec[y + 1, x], rec[y, x + 1], rec[y, x]  # left, up, upper left
+        pa, pb, pc = np.abs(b - c), np.abs(a - c), np.abs(a + b - 2 * c)
+        paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+        f = filt[y][:, None]
+        pred = np.where(f == 1, a, np.where(f == 2, b, np.where(f == 3, (a + b) >> 1, np.where(f == 4, paeth, 0))))
+        rec[y + 1, x + 1] = (line[y, x] + pred) & 255
+    return rec[1:, 1:].astype(np.uint8)
+
+
+def _read_png(data):
+    import struct
+    import zlib
+    pos, idat, w = 8, [], None
+    while pos < len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        pos += 12 + n
+        if kind == b"IHDR":
+            w, h, depth, ctype, _, _, interlace = struct.unpack(">IIBBBBB", body)
+            if depth != 8 or ctype not in (0, 2, 6) or interlace:
+                raise ValueError("load_texture: only 8-bit, non-interlaced grey, RGB or RGBA PNG files are supported")
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+    if w is None:
+        raise ValueError("load_texture: PNG without IHDR")
+    ch = {0: 1, 2: 3, 6: 4}[ctype]
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(h, 1 + w * ch)
+    img = _png_unfilter(raw, w, ch)
+    if ch == 1:
+        img = np.repeat(img, 3, axis=2)
+    return np.ascontiguousarray(img[..., :3])
+
+
 def selftest_math(op, a, b=None, device=0):
     a = np.ascontiguousarray(a, "<f4")
     out = np.zeros_like(a)
@@ -506,6 +609,27 @@ class Scene:
         if st != 0:
             raise WfptError(st, f"cannot read triangles from {path}")
         return cls(np.zeros(0, SPHERE), materials, triangles=tris)
+
+    @classmethod
+    def load_obj(cls, path, materials=None, material_idx=0, uvs=False):
+        """from_obj; with uvs=True returns (scene, uv) -- the (n, 6) float32 UV rows u0 v0 u1 v1 u2 v2 of the triangles in file order (each
+        triangle's _pad names its row), for PathTracer.set_triangle_uvs."""
+        if not uvs:
+            return cls.from_obj(path, materials, material_idx)
+        if materials is None:
+            materials = np.zeros(1, MATERIAL)
+            materials["albedo"][0] = (0.7, 0.7, 0.7, 1.0)
+        materials = np.ascontiguousarray(materials, MATERIAL)
+        n = C.c_uint32()
+        st = lib().wfpt_load_obj_uv(os.fsencode(path), None, None, 0, C.byref(n), 0, 0)
+        if st != 0 or n.value == 0:
+            raise WfptError(st or ERR_INVALID_ARGUMENT, f"cannot read triangles from {path}")
+        tris, uv = np.zeros(n.value, TRIANGLE), np.zeros((n.value, 6), "<f4")
+        mtype = int(materials["material_type"][material_idx])
+        st = lib().wfpt_load_obj_uv(os.fsencode(path), _p(tris), _p(uv), len(tris), C.byref(n), material_idx, mtype)
+        if st != 0:
+            raise WfptError(st, f"cannot read triangles from {path}")
+        return cls(np.zeros(0, SPHERE), materials, triangles=tris), uv
 
     @classmethod
     def random_mesh(cls, n_triangles, seed=1):
@@ -1155,6 +1279,47 @@ class PathTracer:
         out = np.zeros_like(d)
         self._check(lib().wfpt_sample_environment(self.handle, _p(d), d.shape[0], _p(out)))
         return out
+
+    # ---- textures (contexts created with FLAG_TEXTURES; include/wfpt.h "Textures")
+    def set_texture(self, slot, rgb, scale=(1.0, 1.0), offset=(0.0, 0.0), filter="bilinear"):
+        """Puts the (h, w, 3) float32 image `rgb` (linear, row 0 = the top; finite, >= 0) in texture slot `slot`, with the UV transform
+        u' = u * scale + offset and the filter "bilinear" or "nearest". Restarts the accumulation like a scene update."""
+        a = np.ascontiguousarray(rgb, "<f4")
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"set_texture: expected an (h, w, 3) array, got shape {a.shape}")
+        if filter not in TEXTURE_FILTERS:
+            raise ValueError(f"set_texture: filter must be one of {sorted(TEXTURE_FILTERS)}")
+        p = _TextureParams((C.c_float * 2)(*scale), (C.c_float * 2)(*offset), TEXTURE_FILTERS[filter])
+        self._check(lib().wfpt_set_texture(self.handle, slot, _p(a), a.shape[1], a.shape[0], C.byref(p)))
+
+    def clear_texture(self, slot):
+        """Empties the slot and unbinds the materials bound to it."""
+        self._check(lib().wfpt_clear_texture(self.handle, slot))
+
+    def bind_texture(self, material_idx, slot):
+        """Material `material_idx` is textured by slot `slot` (which must hold a texture); None or -1 unbinds it."""
+        self._check(lib().wfpt_bind_texture(self.handle, material_idx, -1 if slot is None else slot))
+
+    def set_triangle_uvs(self, uv):
+        """The UV table: (n, 6) rows u0 v0 u1 v1 u2 v2; a triangle uses the row its _pad names. None clears it."""
+        if uv is None:
+            self._check(lib().wfpt_set_triangle_uvs(self.handle, None, 0))
+            return
+        a = np.ascontiguousarray(uv, "<f4").reshape(-1, 6)
+        self._check(lib().wfpt_set_triangle_uvs(self.handle, _p(a), a.shape[0]))
+
+    def sample_texture(self, slot, uv):
+        """(n, 3) float32: the texture of slot `slot` at each of the (n, 2) UVs, looked up on the device."""
+        a = np.ascontiguousarray(uv, "<f4").reshape(-1, 2)
+        out = np.zeros((a.shape[0], 3), "<f4")
+        self._check(lib().wfpt_sample_texture(self.handle, slot, _p(a), a.shape[0], _p(out)))
+        return out
+
+    def texture_timing(self):
+        """(milliseconds, launches) of the texture launches of every timed render since creation (apart from render_timed's stage times)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_texture_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     # ---- read-back
     def accumulated(self):

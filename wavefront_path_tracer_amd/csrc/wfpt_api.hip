@@ -110,6 +110,12 @@ struct DenoiseBuffers {
 
 // The temporal denoiser's two history slots and the motion plane, [pixel_capacity] each, allocated whole by the first
 // wfpt_denoise_temporal*
+// The texture tables the kernels read (wfpt_ctx::tex_desc, tex_prim), built for a candidate state and then committed whole
+struct TextureTables {
+    DeviceBuffer<TexDev> desc;
+    DeviceBuffer<uint2> prim;
+};
+
 struct HistoryBuffers {
     struct Slot {
         DeviceBuffer<float4> cl, nz;
@@ -209,6 +215,19 @@ struct wfpt_ctx {
     // WFPT_FLAG_ENVIRONMENT (include/wfpt.h "Environment map"): the map set by wfpt_set_environment, null = the gradient sky
     DeviceBuffer<float4> env_tex;
     EnvDev env{};
+    // WFPT_FLAG_TEXTURES (include/wfpt.h "Textures"): the slots' texels and descriptors, the bindings per material (-1 = none), the UV table,
+    // and what build_texture_tables makes of them for the kernels -- the descriptor array and the per-primitive {slot, row} table (null while
+    // no material is bound: nothing is launched then)
+    DeviceBuffer<float4> tex_texels[WFPT_MAX_TEXTURES];
+    TexDev tex_dev[WFPT_MAX_TEXTURES] = {};
+    std::vector<int32_t> tex_bind;
+    DeviceBuffer<float> tex_uv;
+    uint32_t tex_uv_rows = 0;
+    DeviceBuffer<TexDev> tex_desc;
+    DeviceBuffer<uint2> tex_prim;
+    std::vector<uint32_t> h_prim_mat_idx, h_prim_row; // material_idx and _pad per primitive (textured contexts)
+    double tex_ms = 0.0;        // texture launches of the timed renders since wfpt_create (wfpt_texture_timing_ms)
+    uint32_t tex_launches = 0;
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -506,6 +525,41 @@ MissArgs fused_miss_args(wfpt_ctx *c, int parity, uint32_t nb) { // miss_kernel 
     a.chunk_miss = c->f_chunk_miss[parity].get();
     return a;
 }
+// a material is bound to a texture: the texture passes run before the shade steps and the AOV kernel takes the textured variant
+bool textured(const wfpt_ctx *c) { return c->tex_prim.get() != nullptr; }
+TexScene tex_scene(const wfpt_ctx *c) { return TexScene{c->tex_prim.get(), c->tex_desc.get(), c->tex_uv.get()}; }
+// the texture pass before a shade step: over the fused loops' path records of wavefront `parity` (parity >= 0), or over the stage queues
+// (parity < 0: hit queue, ray queue qi, *n_hits capped at limit, material class `material` or all)
+TextureArgs texture_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
+                         uint32_t material = 0xffffffffu) {
+    TextureArgs a{};
+    a.batch = batch_of(c, nb);
+    if (parity >= 0) {
+        a.rec_in = c->rec_mem[parity].get();
+        a.in_hits = c->f_chunk_hits[parity].get();
+    } else {
+        a.in_hits = c->chunk_hits.get();
+        a.q = c->q[qi];
+        a.hq = c->hq;
+        a.n_hits = n_hits;
+        a.limit = std::min(limit, c->capacity);
+    }
+    a.in_hit_base = c->chunk_hit_base.get();
+    a.material = material;
+    a.capacity = c->capacity;
+    a.image = c->image.get();
+    a.ctl = c->ctl.get();
+    a.image_width = c->width;
+    a.tile = c->tile;
+    a.prim_geom = c->scene.prim_geom;
+    a.shade_rec = c->scene.shade_rec;
+    a.prim_kind = c->scene.prim_kind;
+    a.ts = tex_scene(c);
+    return a;
+}
+// The texture launches' entry in an event record (not a wfpt_stage, like the AOV launch's): booked into wfpt_ctx::tex_ms
+constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
+
 ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
     ScanBinnedArgs a{};
     a.batch = batch_of(c, nb);
@@ -536,7 +590,7 @@ const EnvDev *env_of(const wfpt_ctx *c) { return c->env_tex.get() ? &c->env : nu
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
-    return c->bin_capable && !c->env_tex.get() && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
+    return c->bin_capable && !c->env_tex.get() && !textured(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
 }
 // The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
@@ -570,6 +624,10 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      return launch_extend(extend_args(c, qi, &c->ctl.get()->n_in, c->capacity, nb, split), extend_grid(c, nb), st, env != nullptr);
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), st); }));
+        if (textured(c))
+            WFPT_HIP(c, timed(kStageTexture, [&] {
+                         return launch_texture(texture_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st);
+                     }));
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
                      ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
@@ -597,6 +655,8 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const bool last = b + 1 >= c->p.max_wavefronts;
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+        if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
+            WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
                  }));
@@ -641,11 +701,15 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (b + 1 < c->p.max_wavefronts) {
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+            if (textured(c))
+                WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
         } else {
             if (env) // the last launch's miss items, as a launch of their own with the map
                 WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+            if (textured(c))
+                WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
                               [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
         }
@@ -696,7 +760,10 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     };
     c->cur = 0;
     if (c->aov_sums.get()) // first in the batch, serially on the stream: it sees the batch's first frame, before accumulate advances it
-        WFPT_HIP(c, timed(kStageAov, [&] { return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c)); }));
+        WFPT_HIP(c, timed(kStageAov, [&] {
+                     const TexScene ts = tex_scene(c);
+                     return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c), textured(c) ? &ts : nullptr);
+                 }));
     int r = WFPT_OK;
     switch (loop_of(c)) {
     case WFPT_LOOP_STAGES: r = enqueue_stages(c, timed, nb); break;
@@ -1116,6 +1183,14 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
     c->far_rays = false;
     c->depth4 = depth4;
     c->h_prim_mat_type = std::move(mat_type);
+    if (c->p.flags & WFPT_FLAG_TEXTURES) { // what build_texture_tables needs of the primitives (in the order the device holds them)
+        c->h_prim_mat_idx.resize(n_spheres);
+        c->h_prim_row.resize(n_spheres);
+        for (uint32_t i = 0; i < n_spheres; ++i) {
+            c->h_prim_mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
+            c->h_prim_row[i] = spheres ? 0u : triangles[i]._pad;
+        }
+    }
     c->blocks_per_cu = static_cast<uint32_t>(blocks);
     c->bounce_blocks_per_cu = static_cast<uint32_t>(bounce_blocks);
     c->bounce_binned_blocks_per_cu = static_cast<uint32_t>(std::max(binned_blocks, 1));
@@ -1408,7 +1483,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT); // AOVs / denoising / maps of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES); // AOVs / denoising / maps / textures of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1497,6 +1572,9 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
 // context's device by the device builder (byte-identical to bvh.rs:147-210, so the oracle chain stays the checker), the
 // traversal's derived data (shade records, conservative boxes or four-wide nodes, parent table) re-derived, and the
 // accumulation reset as update_buffers does for a parameter change (pt:240-277): the next sample is frame 1 again.
+static int build_texture_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mat_idx,
+                                const std::vector<uint32_t> &row, TextureTables &out);
+static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
     if (!c || !(spheres || triangles) || !materials || n_prims == 0 || n_materials == 0)
@@ -1504,6 +1582,10 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     for (uint32_t i = 0; i < n_prims; ++i)
         if ((spheres ? spheres[i].material_idx : triangles[i].material_idx) >= n_materials)
             return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: primitive material_idx out of range");
+    if (triangles && (c->p.flags & WFPT_FLAG_TEXTURES) && c->tex_uv_rows)
+        for (uint32_t i = 0; i < n_prims; ++i)
+            if (triangles[i]._pad >= c->tex_uv_rows)
+                return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene_mesh: a triangle's UV row (_pad) is beyond the UV table");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old scene
     std::vector<wfpt_bvh_node> nodes(2 * static_cast<size_t>(n_prims));
@@ -1515,10 +1597,20 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     std::vector<uint32_t> pair_parent;
     const int depth = validate_bvh(c, nodes.data(), n_nodes, n_prims, pair_parent);
     if (depth < 0) return depth;
+    TextureTables tables; // the texture tables of the new primitive order, built before anything is replaced
+    if (c->p.flags & WFPT_FLAG_TEXTURES) {
+        std::vector<uint32_t> mat_idx(n_prims), row(n_prims);
+        for (uint32_t i = 0; i < n_prims; ++i) {
+            mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
+            row[i] = spheres ? 0u : triangles[i]._pad;
+        }
+        if (int r = build_texture_tables(c, c->tex_dev, c->tex_bind, mat_idx, row, tables); r != WFPT_OK) return r;
+    }
     if (int r = upload_scene(c, spheres, triangles, n_prims, materials, n_materials, nodes.data(), n_nodes, pair_parent,
                              static_cast<uint32_t>(depth), &c->h_camera);
         r != WFPT_OK)
-        return r; // the context keeps its old scene, graphs and accumulation
+        return r; // the context keeps its old scene, graphs, texture tables and accumulation
+    if (c->p.flags & WFPT_FLAG_TEXTURES) commit_texture_tables(c, std::move(tables));
     return scene_changed(c); // (no object motion vectors: the history shows the old scene)
 }
 
@@ -1618,12 +1710,18 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         c->hit_rec_valid = true; // shade may stream extend's path records until the host touches the ray queue (generate_rays, write, swap, clear)
         break;
     case WFPT_STAGE_SHADE:
+        if (textured(c))
+            WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx, 0xffffffffu, true),
                                  consumer_grid(c, 1), c->stream.get()));
         break;
     case WFPT_STAGE_SHADE_LAMBERTIAN:
     case WFPT_STAGE_SHADE_METAL:
     case WFPT_STAGE_SHADE_DIELECTRIC:
+        if (textured(c))
+            WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
+                                                    static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
+                                       consumer_grid(c, 1), c->stream.get()));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx,
                                             static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN), true),
                                  consumer_grid(c, 1), c->stream.get()));
@@ -1684,6 +1782,11 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
             if (e.stage == kStageAov) {
                 c->aov_ms += ms;
                 c->aov_launches += 1;
+                continue;
+            }
+            if (e.stage == kStageTexture) {
+                c->tex_ms += ms;
+                c->tex_launches += 1;
                 continue;
             }
             stage_ms[e.stage] += ms;
@@ -2560,6 +2663,176 @@ int wfpt_sample_environment(wfpt_ctx *c, const float *dirs, size_t n, float *rgb
     if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
     if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment");
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- textures (include/wfpt.h "Textures")
+// The kernels' view of the slots, bindings and scene: the descriptor array and the per-primitive {slot, row} table (both null while no
+// material is bound). Built whole for a CANDIDATE state -- descriptors `dev`, bindings `bind`, and per primitive its material_idx and UV
+// row -- without touching the context; the caller commits it with everything else only once every step has succeeded (a failed
+// allocation or copy leaves the context, its tables and its graphs as they were).
+static int build_texture_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mat_idx,
+                                const std::vector<uint32_t> &row, TextureTables &out) {
+    bool any = false;
+    for (int32_t b : bind) any = any || b >= 0;
+    if (!any) return WFPT_OK;
+    const size_t n = mat_idx.size();
+    std::vector<uint2> t(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t slot = mat_idx[i] < bind.size() ? bind[mat_idx[i]] : -1;
+        t[i] = make_uint2(slot >= 0 ? static_cast<uint32_t>(slot) : kNoTexture, row[i]);
+    }
+    WFPT_HIP(c, out.desc.alloc(WFPT_MAX_TEXTURES));
+    WFPT_HIP(c, out.prim.alloc(n));
+    WFPT_HIP(c, hipMemcpy(out.desc.get(), dev, sizeof(TexDev) * WFPT_MAX_TEXTURES, hipMemcpyHostToDevice));
+    WFPT_HIP(c, hipMemcpy(out.prim.get(), t.data(), sizeof(uint2) * n, hipMemcpyHostToDevice));
+    return WFPT_OK;
+}
+// the new tables replace the old ones (the stream is idle: the caller synchronised it)
+static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t) {
+    c->tex_desc = std::move(t.desc);
+    c->tex_prim = std::move(t.prim);
+}
+
+static int texture_check(wfpt_ctx *c, const char *who) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_TEXTURES))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_TEXTURES");
+    if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
+        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no textures");
+    return WFPT_OK;
+}
+
+void wfpt_texture_params_default(wfpt_texture_params *p) {
+    if (!p) return;
+    *p = wfpt_texture_params{};
+    p->scale[0] = p->scale[1] = 1.0f;
+}
+
+int wfpt_set_texture(wfpt_ctx *c, uint32_t slot, const float *rgb, uint32_t w, uint32_t h, const wfpt_texture_params *p) {
+    if (int r = texture_check(c, "wfpt_set_texture"); r != WFPT_OK) return r;
+    wfpt_texture_params dp;
+    wfpt_texture_params_default(&dp);
+    if (!p) p = &dp;
+    if (slot >= WFPT_MAX_TEXTURES) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: slot out of range");
+    if (!rgb) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: null texels");
+    if (w < 1 || w > 16384 || h < 1 || h > 16384)
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: the texture must be 1..16384 x 1..16384 texels");
+    for (float v : {p->scale[0], p->scale[1], p->offset[0], p->offset[1]})
+        if (!std::isfinite(v)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: scale and offset must be finite");
+    if (p->filter > static_cast<uint32_t>(WFPT_TEXTURE_NEAREST)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: unknown filter");
+    for (uint32_t r : p->_reserved)
+        if (r != 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: _reserved must be 0");
+    const size_t n = static_cast<size_t>(w) * h;
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!(rgb[i] >= 0.0f && rgb[i] <= FLT_MAX)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: texels must be finite and >= 0");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float4> tex;
+    WFPT_HIP(c, tex.alloc(n));
+    constexpr size_t kPiece = 1u << 20; // float4 per texel, converted in pieces (as wfpt_set_environment)
+    std::vector<float4> piece(std::min(n, kPiece));
+    for (size_t i0 = 0; i0 < n; i0 += kPiece) {
+        const size_t m = std::min(kPiece, n - i0);
+        for (size_t i = 0; i < m; ++i) {
+            const float *t = rgb + 3 * (i0 + i);
+            piece[i] = make_float4(t[0], t[1], t[2], 0.0f);
+        }
+        if (const hipError_t e = hipMemcpy(tex.get() + i0, piece.data(), sizeof(float4) * m, hipMemcpyHostToDevice); e != hipSuccess)
+            return hip_fail(c, e, "wfpt_set_texture: upload");
+    }
+    TexDev dev[WFPT_MAX_TEXTURES];
+    std::copy(c->tex_dev, c->tex_dev + WFPT_MAX_TEXTURES, dev);
+    dev[slot] = TexDev{tex.get(), w, h, p->scale[0], p->scale[1], p->offset[0], p->offset[1], p->filter, 0u};
+    TextureTables tables;
+    if (int r = build_texture_tables(c, dev, c->tex_bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old texels
+    c->tex_texels[slot] = std::move(tex);               // (frees the old texels: the old tables that named them go with them)
+    std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
+    commit_texture_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_clear_texture(wfpt_ctx *c, uint32_t slot) {
+    if (int r = texture_check(c, "wfpt_clear_texture"); r != WFPT_OK) return r;
+    if (slot >= WFPT_MAX_TEXTURES) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_clear_texture: slot out of range");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    TexDev dev[WFPT_MAX_TEXTURES];
+    std::copy(c->tex_dev, c->tex_dev + WFPT_MAX_TEXTURES, dev);
+    dev[slot] = TexDev{};
+    std::vector<int32_t> bind = c->tex_bind;
+    for (int32_t &b : bind)
+        if (b == static_cast<int32_t>(slot)) b = -1;
+    TextureTables tables;
+    if (int r = build_texture_tables(c, dev, bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    c->tex_texels[slot].release();
+    std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
+    c->tex_bind = std::move(bind);
+    commit_texture_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_bind_texture(wfpt_ctx *c, uint32_t material_idx, int32_t slot) {
+    if (int r = texture_check(c, "wfpt_bind_texture"); r != WFPT_OK) return r;
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_bind_texture: material_idx out of range");
+    if (slot < -1 || slot >= static_cast<int32_t>(WFPT_MAX_TEXTURES)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_bind_texture: slot out of range");
+    if (slot >= 0 && !c->tex_texels[slot].get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_bind_texture: the slot holds no texture");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> bind = c->tex_bind;
+    if (bind.size() <= material_idx) bind.resize(material_idx + 1u, -1);
+    bind[material_idx] = slot;
+    TextureTables tables;
+    if (int r = build_texture_tables(c, c->tex_dev, bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    c->tex_bind = std::move(bind);
+    commit_texture_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_set_triangle_uvs(wfpt_ctx *c, const float *uv6, uint32_t n_rows) {
+    if (int r = texture_check(c, "wfpt_set_triangle_uvs"); r != WFPT_OK) return r;
+    if (!uv6) n_rows = 0;
+    for (size_t i = 0; i < 6 * static_cast<size_t>(n_rows); ++i)
+        if (!std::isfinite(uv6[i])) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_triangle_uvs: UVs must be finite");
+    if (n_rows && c->scene.prim_kind == 1)
+        for (uint32_t row : c->h_prim_row)
+            if (row >= n_rows) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_triangle_uvs: a triangle's UV row (_pad) is beyond the table");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> uv;
+    if (n_rows) {
+        WFPT_HIP(c, uv.alloc(6 * static_cast<size_t>(n_rows)));
+        WFPT_HIP(c, hipMemcpy(uv.get(), uv6, sizeof(float) * 6 * n_rows, hipMemcpyHostToDevice));
+    }
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    c->tex_uv = std::move(uv); // (the kernels take it from the context at each launch; the graphs that hold the old one are dropped)
+    c->tex_uv_rows = n_rows;
+    return scene_changed(c);
+}
+
+int wfpt_sample_texture(wfpt_ctx *c, uint32_t slot, const float *uv, size_t n, float *rgb_out) {
+    if (int r = texture_check(c, "wfpt_sample_texture"); r != WFPT_OK) return r;
+    if (slot >= WFPT_MAX_TEXTURES || !c->tex_texels[slot].get())
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_texture: the slot holds no texture");
+    if ((!uv || !rgb_out) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_texture: null argument");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_uv, d_rgb;
+    hipError_t e = d_uv.alloc(2 * n);
+    if (e == hipSuccess) e = d_rgb.alloc(3 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_uv.get(), uv, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) e = launch_tex_sample(c->tex_dev[slot], d_uv.get(), d_rgb.get(), n, c->stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_texture");
+    return WFPT_OK;
+}
+
+int wfpt_texture_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_texture_timing_ms: null context");
+    if (!(c->p.flags & WFPT_FLAG_TEXTURES))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_texture_timing_ms: the context was created without WFPT_FLAG_TEXTURES");
+    if (ms_total) *ms_total = static_cast<float>(c->tex_ms);
+    if (launches) *launches = c->tex_launches;
     return WFPT_OK;
 }
 

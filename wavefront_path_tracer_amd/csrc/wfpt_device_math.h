@@ -195,4 +195,76 @@ __host__ __device__ __forceinline__ float3_ env_lookup(const float4 *tex, uint32
             (((t00.z * w00 + t10.z * w10) + t01.z * w01) + t11.z * w11) * intensity};
 }
 
+// ---------------- surface textures (WFPT_FLAG_TEXTURES; include/wfpt.h "Textures") ----------------
+// The same rules as the environment map: IEEE f32 add / sub / mul / div / sqrt, comparisons, selects and floor, no fma; restated bit for bit
+// by tests/texture_ref.py.
+//
+// A texture as the kernels see it: w x h float4 texels (rgb, 0), row 0 = the top (v = 1), the UV transform and the filter.
+struct TexDev {
+    const float4 *texels;
+    uint32_t w, h;
+    float scale_u, scale_v, offset_u, offset_v;
+    uint32_t filter; // WFPT_TEXTURE_BILINEAR 0, WFPT_TEXTURE_NEAREST 1
+    uint32_t _pad;
+};
+
+// (u, v) of the point with unit outward normal n on a sphere (Shirley book 2's get_sphere_uv, v = 0 at the -y pole)
+__host__ __device__ __forceinline__ void sphere_uv(float3_ n, float &u, float &v) {
+    u = atan2_(-n.z, n.x) * 0.15915494f + 0.5f;
+    v = atan2_(sqrt_(n.x * n.x + n.z * n.z), -n.y) * 0.31830988f;
+}
+
+// (u, v) of point p on the triangle (v0, e1, e2) with corner UVs uv[0..5] = u0 v0 u1 v1 u2 v2: barycentrics from the normal equations
+__host__ __device__ __forceinline__ void triangle_uv(float3_ p, float3_ v0, float3_ e1, float3_ e2, const float *uv, float &u, float &v) {
+    const float3_ w = {p.x - v0.x, p.y - v0.y, p.z - v0.z};
+    const float d00 = dot3(e1, e1), d01 = dot3(e1, e2), d11 = dot3(e2, e2), d20 = dot3(w, e1), d21 = dot3(w, e2);
+    const float den = d00 * d11 - d01 * d01;
+    float b1 = 0.0f, b2 = 0.0f;
+    if (den > 0.0f) {
+        const float inv = 1.0f / den;
+        b1 = (d11 * d20 - d01 * d21) * inv;
+        b2 = (d00 * d21 - d01 * d20) * inv;
+    }
+    const float b0 = (1.0f - b1) - b2;
+    u = (uv[0] * b0 + uv[2] * b1) + uv[4] * b2;
+    v = (uv[1] * b0 + uv[3] * b1) + uv[5] * b2;
+}
+
+// index of a texel coordinate c0 (floor of a float, expected in -1 .. n-1) and of c0 + 1, both wrapped into 0 .. n-1; NaN reads index n-1
+__host__ __device__ __forceinline__ void wrap_pair(float c0, float fn, uint32_t n, uint32_t &i0, uint32_t &i1) {
+    const int k = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c0, -1.0f), fn - 1.0f)); // -1 .. n-1
+    i0 = k < 0 ? n - 1u : static_cast<uint32_t>(k);
+    i1 = static_cast<uint32_t>(k + 1) >= n ? 0u : static_cast<uint32_t>(k + 1);
+}
+
+// The texture's value at (u, v): u' = u * scale + offset, wrapped into [0, 1] by u' - floor(u'), the same for v'; then
+//   bilinear: x = u' w - 0.5, y = (1 - v') h - 0.5, texel centres at half-integers, columns and rows wrapping, weights combined in
+//             env_lookup's order ((t00 w00 + t10 w10) + t01 w01) + t11 w11
+//   nearest:  column min(floor(u' w), w - 1), row min(floor((1 - v') h), h - 1)
+__host__ __device__ __forceinline__ float3_ tex_lookup(const TexDev &t, float u, float v) {
+    float uu = u * t.scale_u + t.offset_u, vv = v * t.scale_v + t.offset_v;
+    uu = uu - __builtin_floorf(uu);
+    vv = vv - __builtin_floorf(vv);
+    const float fw = static_cast<float>(t.w), fh = static_cast<float>(t.h);
+    const float ry = 1.0f - vv;
+    if (t.filter == 1u) { // WFPT_TEXTURE_NEAREST
+        const uint32_t cx = static_cast<uint32_t>(__builtin_fminf(__builtin_fmaxf(__builtin_floorf(uu * fw), 0.0f), fw - 1.0f));
+        const uint32_t cy = static_cast<uint32_t>(__builtin_fminf(__builtin_fmaxf(__builtin_floorf(ry * fh), 0.0f), fh - 1.0f));
+        const float4 c = t.texels[static_cast<size_t>(cy) * t.w + cx];
+        return {c.x, c.y, c.z};
+    }
+    const float x = uu * fw - 0.5f, y = ry * fh - 0.5f;
+    const float x0 = __builtin_floorf(x), y0 = __builtin_floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    uint32_t c0, c1, r0, r1;
+    wrap_pair(x0, fw, t.w, c0, c1);
+    wrap_pair(y0, fh, t.h, r0, r1);
+    const size_t o0 = static_cast<size_t>(r0) * t.w, o1 = static_cast<size_t>(r1) * t.w;
+    const float4 t00 = t.texels[o0 + c0], t10 = t.texels[o0 + c1], t01 = t.texels[o1 + c0], t11 = t.texels[o1 + c1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+    return {((t00.x * w00 + t10.x * w10) + t01.x * w01) + t11.x * w11, ((t00.y * w00 + t10.y * w10) + t01.y * w01) + t11.y * w11,
+            ((t00.z * w00 + t10.z * w10) + t01.z * w01) + t11.z * w11};
+}
+
 } // namespace wfpt

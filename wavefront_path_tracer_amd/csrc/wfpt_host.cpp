@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <limits>
 #include <vector>
 
@@ -471,13 +472,16 @@ int wfpt_build_bvh_triangles(wfpt_triangle *tris, uint32_t n, wfpt_bvh_node *nod
     return WFPT_OK;
 }
 
-int wfpt_load_obj(const char *path, wfpt_triangle *tris, uint32_t capacity, uint32_t *n_tris, uint32_t material_idx,
-                  uint32_t material_type) {
+// The OBJ reader behind wfpt_load_obj and wfpt_load_obj_uv. uvs: also read `vt` records and the faces' texture indices into uv6 (when
+// triangles are written), and number each triangle's row in _pad.
+static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool uvs, uint32_t capacity, uint32_t *n_tris,
+                         uint32_t material_idx, uint32_t material_type) {
     if (!path || !n_tris) return WFPT_ERR_INVALID_ARGUMENT;
     std::FILE *f = std::fopen(path, "r");
     if (!f) return WFPT_ERR_INVALID_ARGUMENT;
     std::vector<Vec3> verts;
-    std::vector<long long> face;
+    std::vector<std::pair<float, float>> tex;
+    std::vector<long long> face, face_t; // face_t: -1 = no texture index
     uint32_t count = 0;
     int status = WFPT_OK;
     char line[4096];
@@ -488,21 +492,38 @@ int wfpt_load_obj(const char *path, wfpt_triangle *tris, uint32_t capacity, uint
             Vec3 v{0.0f, 0.0f, 0.0f};
             if (std::sscanf(p + 1, "%f %f %f", &v.x, &v.y, &v.z) != 3) status = WFPT_ERR_INVALID_ARGUMENT;
             verts.push_back(v);
+        } else if (uvs && p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t')) { // vt u v [w]
+            float u = 0.0f, v = 0.0f;
+            if (std::sscanf(p + 2, "%f %f", &u, &v) != 2) status = WFPT_ERR_INVALID_ARGUMENT;
+            tex.emplace_back(u, v);
         } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
             face.clear();
+            face_t.clear();
             char *q = const_cast<char *>(p + 1);
             for (;;) {
                 while (*q == ' ' || *q == '\t') ++q;
                 if (*q == 0 || *q == '\n' || *q == '\r' || *q == '#') break;
                 char *end = nullptr;
-                long long idx = std::strtoll(q, &end, 10); // the vertex index; "/t/n" parts are skipped
+                long long idx = std::strtoll(q, &end, 10); // the vertex index; "/t/n" parts are skipped unless uvs
                 if (end == q) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
+                long long tidx = -1;
+                if (uvs && *end == '/' && end[1] != '/') { // i/t or i/t/n
+                    char *tend = nullptr;
+                    long long t = std::strtoll(end + 1, &tend, 10);
+                    if (tend == end + 1) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
+                    if (t < 0) t += static_cast<long long>(tex.size());
+                    else t -= 1;
+                    if (t < 0 || t >= static_cast<long long>(tex.size())) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
+                    tidx = t;
+                    end = tend;
+                }
                 while (*end && *end != ' ' && *end != '\t' && *end != '\n' && *end != '\r') ++end;
                 q = end;
                 if (idx < 0) idx += static_cast<long long>(verts.size()); // relative to the vertices read so far
                 else idx -= 1;
                 if (idx < 0 || idx >= static_cast<long long>(verts.size())) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
                 face.push_back(idx);
+                face_t.push_back(tidx);
             }
             for (size_t k = 2; status == WFPT_OK && k < face.size(); ++k) { // fan around the first vertex
                 if (tris) {
@@ -514,7 +535,14 @@ int wfpt_load_obj(const char *path, wfpt_triangle *tris, uint32_t capacity, uint
                     t.e2[0] = c.x - a.x; t.e2[1] = c.y - a.y; t.e2[2] = c.z - a.z;
                     t.material_idx = material_idx;
                     t.material_type = material_type;
-                    t._pad = 0;
+                    t._pad = uvs ? count : 0u;
+                    if (uvs && uv6) {
+                        const long long corner[3] = {face_t[0], face_t[k - 1], face_t[k]};
+                        for (int j = 0; j < 3; ++j) {
+                            uv6[6 * static_cast<size_t>(count) + 2 * j] = corner[j] >= 0 ? tex[corner[j]].first : 0.0f;
+                            uv6[6 * static_cast<size_t>(count) + 2 * j + 1] = corner[j] >= 0 ? tex[corner[j]].second : 0.0f;
+                        }
+                    }
                 }
                 count += 1;
             }
@@ -523,6 +551,17 @@ int wfpt_load_obj(const char *path, wfpt_triangle *tris, uint32_t capacity, uint
     std::fclose(f);
     *n_tris = count;
     return status;
+}
+
+int wfpt_load_obj(const char *path, wfpt_triangle *tris, uint32_t capacity, uint32_t *n_tris, uint32_t material_idx,
+                  uint32_t material_type) {
+    return load_obj_impl(path, tris, nullptr, false, capacity, n_tris, material_idx, material_type);
+}
+
+int wfpt_load_obj_uv(const char *path, wfpt_triangle *tris, float *uv6, uint32_t capacity, uint32_t *n_tris, uint32_t material_idx,
+                     uint32_t material_type) {
+    if (tris && !uv6) return WFPT_ERR_INVALID_ARGUMENT;
+    return load_obj_impl(path, tris, uv6, true, capacity, n_tris, material_idx, material_type);
 }
 
 uint32_t wfpt_scene_random_mesh(uint64_t seed, uint32_t n, wfpt_triangle *tris, wfpt_material *mt) {

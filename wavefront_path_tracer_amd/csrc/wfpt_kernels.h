@@ -7,6 +7,7 @@
 
 #include "wfpt.h"
 #include "wfpt_bvh4.h"
+#include "wfpt_device_math.h"
 
 namespace wfpt {
 
@@ -81,6 +82,17 @@ struct EnvDev {
     const float4 *texels;
     uint32_t w, h;
     float intensity, rotation;
+};
+
+// Surface textures (WFPT_FLAG_TEXTURES, include/wfpt.h "Textures"), as the texture pass and the AOV kernel read them: the per-primitive table
+// the host resolves from the bindings, the scene and the UV table -- {texture slot or kNoTexture, UV row} -- the WFPT_MAX_TEXTURES
+// descriptors (TexDev, wfpt_device_math.h) and the UV rows (u0 v0 u1 v1 u2 v2; null = (0, 0) at every corner). Passed by value (a captured
+// graph bakes it in: every change drops the graphs).
+constexpr uint32_t kNoTexture = 0xffffffffu;
+struct TexScene {
+    const uint2 *prim_tex;
+    const TexDev *tex;
+    const float *uv6;
 };
 
 // Device-resident control block. `counters` is the reference's counter_buffer (extend.wgsl:41).
@@ -378,6 +390,33 @@ struct MissArgs {
     Tiling tile;
 };
 
+// The texture pass (texture_kernel): before a shade step, the throughput of every hit that step will shade is multiplied by the texture of
+// the primitive hit, so that shade's own `*= albedo` makes (thr * tex) * albedo. Two forms, as the shade steps read their hits:
+//   records (rec_in != null): the fused loops' path records of the previous wavefront -- segment c holds in_hits[c] records, its first one
+//            shade's hit in_hit_base[c]; the hits shaded are h < ctl->shade_n (0 once the loop has exited), as bounce_kernel and
+//            shade_rays_kernel shade them;
+//   queues  (rec_in == null): shade_kernel's hit queue (t, primitive, ray index) and ray queue: hits h < min(*n_hits, limit), of material
+//            class `material` only unless it is 0xffffffff (the per-material shade stages).
+struct TextureArgs {
+    Batch batch;
+    const float4 *rec_in;
+    const uint32_t *in_hits, *in_hit_base;
+    RayQueue q;
+    HitQueue hq;
+    const uint32_t *n_hits;
+    uint32_t limit;
+    uint32_t material;
+    uint32_t capacity;
+    float *image;
+    const Control *ctl;
+    uint32_t image_width;
+    Tiling tile;
+    const float4 *prim_geom;  // triangles: the wfpt_triangle array (v0, e1, e2)
+    const float4 *shade_rec;  // spheres: the centre; the material class
+    uint32_t prim_kind;
+    TexScene ts;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -507,6 +546,7 @@ hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
+hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_fill(float *p, float v, size_t n, hipStream_t s);
 hipError_t launch_set_frame(Control *ctl, const wfpt_frame_buffer &f, hipStream_t s); // ctl->frame = f, ordered on the stream
@@ -517,7 +557,7 @@ hipError_t launch_rays_to_aos(const RayQueue &q, wfpt_ray *out, uint32_t n, hipS
 hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t n, hipStream_t s);
 // AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
 // sized for it)
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const TexScene *tex = nullptr);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
 // accumulate_kernel's work plus the luminance moments (WFPT_FLAG_DENOISE contexts, in its place)
@@ -527,6 +567,8 @@ hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, hipStream_t s);
 // env_lookup of n directions (xyz, stride 3) into rgb (stride 3): wfpt_sample_environment
 hipError_t launch_env_sample(const EnvDev &env, const float *dirs, float *rgb, size_t n, hipStream_t s);
+// tex_lookup of n UVs (stride 2) into rgb (stride 3): wfpt_sample_texture
+hipError_t launch_tex_sample(const TexDev &tex, const float *uv, float *rgb, size_t n, hipStream_t s);
 hipError_t launch_selftest_math(int op, const float *a, const float *b, float *out, size_t n, hipStream_t s);
 // Occupancy of the extend kernel for a given dynamic LDS size (workgroups per CU); also raises the
 // kernel's dynamic-LDS limit when the scene needs more than the default 64 KiB.

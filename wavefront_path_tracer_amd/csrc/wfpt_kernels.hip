@@ -1676,6 +1676,79 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_kernel(MissArgs a) {
 }
 __global__ __launch_bounds__(kConsumerThreads) void miss_env_kernel(MissArgs a, EnvDev env) { miss_body<true>(a, env); }
 
+// ================================================================================================
+// texture pass (WFPT_FLAG_TEXTURES; include/wfpt.h "Textures")
+// ================================================================================================
+// The texture's value at point p of primitive `prim`, or false when the primitive's material is bound to none. Spheres: sphere_uv of the
+// normal scatter() uses; triangles: triangle_uv with the corner UVs of the primitive's row.
+__device__ __forceinline__ bool texture_factor(const TexScene &ts, const float4 *prim_geom, const float4 *shade_rec, uint32_t prim_kind,
+                                               uint32_t prim, float3_ p, float3_ &c) {
+    const uint2 e = ts.prim_tex[prim];
+    if (e.x == kNoTexture) return false;
+    float u, v;
+    if (prim_kind == 0) {
+        const float4 rec0 = shade_rec[3u * prim];
+        sphere_uv(normalize3({p.x - rec0.x, p.y - rec0.y, p.z - rec0.z}), u, v);
+    } else {
+        const float4 g0 = prim_geom[3u * prim], g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+        float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (ts.uv6) {
+            const float2 *row = reinterpret_cast<const float2 *>(ts.uv6 + 6u * static_cast<size_t>(e.y));
+            const float2 q0 = row[0], q1 = row[1], q2 = row[2];
+            uv[0] = q0.x; uv[1] = q0.y; uv[2] = q1.x; uv[3] = q1.y; uv[4] = q2.x; uv[5] = q2.y;
+        }
+        triangle_uv(p, {g0.x, g0.y, g0.z}, {g1.x, g1.y, g1.z}, {g2.x, g2.y, g2.z}, uv, u, v);
+    }
+    c = tex_lookup(ts.tex[e.x], u, v);
+    return true;
+}
+
+// One launch before a shade step (TextureArgs): walks the segments that step walks, one segment per workgroup at a time, and multiplies the
+// pixel's throughput of every textured hit by the texture. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
+__global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a) {
+    const uint32_t smp = blockIdx.y;
+    const Control *ctl = a.ctl + smp;
+    const bool records = a.rec_in != nullptr;
+    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
+    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
+    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
+    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.in_hits[co + chunk];
+        const uint32_t base = a.in_hit_base[co + chunk];
+        if (base >= n) break; // bases ascend with the segment index
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n) break;
+            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
+            float3_ p;
+            uint32_t prim, pixel_idx;
+            if (records) {
+                const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
+                p = {ra.x, ra.y, ra.z};
+                pixel_idx = __float_as_uint(ra.w);
+                prim = __float_as_uint(rb.w);
+            } else {
+                const float t = a.hq.t()[slot];
+                const uint32_t ridx = a.hq.ridx()[slot];
+                prim = a.hq.prim()[slot];
+                p = {q.ox()[ridx] + t * q.dx()[ridx], q.oy()[ridx] + t * q.dy()[ridx], q.oz()[ridx] + t * q.dz()[ridx]}; // sh:91
+                pixel_idx = q.pixel()[ridx];
+            }
+            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
+                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
+                if (m > 2u) m = 0u;
+                if (m != a.material) continue;
+            }
+            float3_ c;
+            if (!texture_factor(a.ts, a.prim_geom, a.shade_rec, a.prim_kind, prim, p, c)) continue;
+            float4 *px = pixel_of(image, local_pixel(pixel_idx, a.image_width, a.tile));
+            const float4 thr = *px;
+            *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+        }
+    }
+}
+
 // shade (sh:56-156) of hit h of the previous wavefront, as the fused loop runs it: find the hit's path record (its
 // segment is the last one whose first hit is not after h, searched between the segments that hold the first hit of
 // this run of kChunk hits and of the next run: scan's first_seg table), multiply the pixel's throughput by the albedo
@@ -2812,8 +2885,8 @@ __global__ void rays_from_aos_kernel(RayQueue q, const wfpt_ray *in, uint32_t n)
 // Sample order per pixel, no atomics: the sums do not depend on the batch size or on anything else that runs beside this kernel.
 // (No min-waves launch bound: capped at 64 vector registers like extend_kernel, every variant spills 96-164 bytes to scratch; unbounded
 // it takes 86-110 and runs 4 waves per SIMD.)
-template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV>
-__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX = false>
+__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, const TexScene &ts = TexScene{}) {
     extern __shared__ float4 lds[];
     const uint32_t n_slots = a.gx * a.gy * 64u;
     const uint32_t n_items = (n_slots + kExtendThreads - 1u) / kExtendThreads;
@@ -2853,7 +2926,13 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env) {
                 // the normal scatter() uses: spheres normalize3(p - centre) with p = o + t d (extend's path record, sh:91), triangles the stored one
                 float3_ n = {rec0.x, rec0.y, rec0.z};
                 if (PRIM == 0) n = normalize3({(r.ox + t * r.dx) - rec0.x, (r.oy + t * r.dy) - rec0.y, (r.oz + t * r.dz) - rec0.z});
-                alb_r += rec1.x; alb_g += rec1.y; alb_b += rec1.z;
+                float3_ tc;
+                if (TEX && texture_factor(ts, a.scene.prim_geom, a.scene.shade_rec, PRIM, prim,
+                                          {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, tc)) { // the textured albedo tex * albedo
+                    alb_r += tc.x * rec1.x; alb_g += tc.y * rec1.y; alb_b += tc.z * rec1.z;
+                } else {
+                    alb_r += rec1.x; alb_g += rec1.y; alb_b += rec1.z;
+                }
                 nrm_x += n.x; nrm_y += n.y; nrm_z += n.z;
                 depth += t;
                 hits += 1u;
@@ -2893,6 +2972,12 @@ __global__ __launch_bounds__(kExtendThreads) void aov_kernel(AovArgs a) {
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT>
 __global__ __launch_bounds__(kExtendThreads) void aov_env_kernel(AovArgs a, EnvDev env) {
     aov_body<Trail, PRIM, LDS_SCENE, EXACT, true>(a, env);
+}
+
+// WFPT_FLAG_TEXTURES with a binding: a primary hit adds its textured albedo (both ENV cases)
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV>
+__global__ __launch_bounds__(kExtendThreads) void aov_tex_kernel(AovArgs a, EnvDev env, TexScene ts) {
+    aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, true>(a, env, ts);
 }
 
 // sums -> resolved AOV words (aov_resolve_word, shared with the host read-back)
@@ -3227,6 +3312,13 @@ __global__ __launch_bounds__(256) void env_sample_kernel(EnvDev env, const float
     rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 
+__global__ __launch_bounds__(256) void tex_sample_kernel(TexDev tex, const float *uv, float *rgb, size_t n) {
+    const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
+    if (i >= n) return;
+    const float3_ c = tex_lookup(tex, uv[2 * i], uv[2 * i + 1]);
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+
 __global__ void selftest_math_kernel(int op, const float *a, const float *b, float *out, size_t n) {
     const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
     if (i >= n) return;
@@ -3449,6 +3541,12 @@ hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const En
     return hipGetLastError();
 }
 
+hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(texture_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s) {
     hipLaunchKernelGGL(accumulate_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -3496,20 +3594,31 @@ template <> struct AovK<true> {
     template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovEnvFn get() { return aov_env_kernel<Trail, PRIM, LDS_SCENE, EXACT>; }
 };
 template <bool ENV = false> auto aov_variant(const SceneDev &sc, bool exact) { return pick_variant<AovK<ENV>>(sc, exact, sc.lds_scene != 0); }
+using AovTexFn = void (*)(AovArgs, EnvDev, TexScene);
+template <bool ENV> struct AovTexK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovTexFn get() { return aov_tex_kernel<Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+};
+AovTexFn aov_tex_variant(const SceneDev &sc, bool exact, bool env) {
+    return env ? pick_variant<AovTexK<true>>(sc, exact, sc.lds_scene != 0) : pick_variant<AovTexK<false>>(sc, exact, sc.lds_scene != 0);
+}
 uint32_t aov_lds_bytes(const SceneDev &sc) { return sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes; }
 } // namespace
 
 hipError_t aov_prepare(const SceneDev &scene) {
     for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
-        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), aov_variant(scene, exact), aov_variant<true>(scene, exact));
+        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), aov_variant(scene, exact), aov_variant<true>(scene, exact),
+                                               aov_tex_variant(scene, exact, false), aov_tex_variant(scene, exact, true));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env) {
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex) {
     if (grid == 0 || a.n == 0 || a.gx * a.gy == 0) return hipSuccess;
-    if (env)
+    if (tex)
+        hipLaunchKernelGGL(aov_tex_variant(a.scene, a.scene.exact != 0, env != nullptr), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s,
+                           a, env ? *env : EnvDev{}, *tex);
+    else if (env)
         hipLaunchKernelGGL(aov_variant<true>(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a, *env);
     else
         hipLaunchKernelGGL(aov_variant(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
@@ -3554,6 +3663,12 @@ hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, 
 hipError_t launch_env_sample(const EnvDev &env, const float *dirs, float *rgb, size_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(env_sample_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, env, dirs, rgb, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_tex_sample(const TexDev &tex, const float *uv, float *rgb, size_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(tex_sample_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, tex, uv, rgb, n);
     return hipGetLastError();
 }
 

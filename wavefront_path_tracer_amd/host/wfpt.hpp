@@ -322,6 +322,33 @@ class PathTracer {
         check(wfpt_read_accumulated(ctx_, a.data(), a.size()));
         return a;
     }
+    // Textures (WFPT_FLAG_TEXTURES, include/wfpt.h "Textures"): rgb = h rows of w linear texels, 3 floats each, row 0 = the top.
+    void set_texture(uint32_t slot, const std::vector<float> &rgb, uint32_t w, uint32_t h, std::array<float, 2> scale = {1.0f, 1.0f},
+                     std::array<float, 2> offset = {0.0f, 0.0f}, uint32_t filter = WFPT_TEXTURE_BILINEAR) {
+        if (rgb.size() != 3 * static_cast<size_t>(w) * h) throw Error(WFPT_ERR_INVALID_ARGUMENT, "set_texture: rgb must hold w * h * 3 floats");
+        wfpt_texture_params p;
+        wfpt_texture_params_default(&p);
+        p.scale[0] = scale[0]; p.scale[1] = scale[1];
+        p.offset[0] = offset[0]; p.offset[1] = offset[1];
+        p.filter = filter;
+        check(wfpt_set_texture(ctx_, slot, rgb.data(), w, h, &p));
+    }
+    void clear_texture(uint32_t slot) { check(wfpt_clear_texture(ctx_, slot)); }
+    void bind_texture(uint32_t material_idx, int32_t slot) { check(wfpt_bind_texture(ctx_, material_idx, slot)); } // slot -1 unbinds
+    void set_triangle_uvs(const std::vector<float> &uv6) { // rows of u0 v0 u1 v1 u2 v2; empty clears
+        check(wfpt_set_triangle_uvs(ctx_, uv6.empty() ? nullptr : uv6.data(), static_cast<uint32_t>(uv6.size() / 6)));
+    }
+    std::vector<float> sample_texture(uint32_t slot, const std::vector<float> &uv) { // (u, v) pairs -> rgb triples
+        std::vector<float> rgb(3 * (uv.size() / 2));
+        check(wfpt_sample_texture(ctx_, slot, uv.data(), uv.size() / 2, rgb.data()));
+        return rgb;
+    }
+    std::pair<float, uint32_t> texture_timing() {
+        float ms = 0.0f;
+        uint32_t n = 0;
+        check(wfpt_texture_timing_ms(ctx_, &ms, &n));
+        return {ms, n};
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
