@@ -28,7 +28,13 @@ extern "C" {
 
 /* ------------------------------------------------------------------ data model (wavefront_common) */
 
-/* wavefront_common/src/sphere.rs:3-11 == extend.wgsl:10-15. center.w is 1.0 (sphere.rs:18-20). */
+/* wavefront_common/src/sphere.rs:3-11 == extend.wgsl:10-15. center.w is 1.0 (sphere.rs:18-20).
+ * radius may be 0 or negative; wfpt_create accepts both and the kernels do what the reference's text does. extend.wgsl:193 squares the radius
+ * and shade.wgsl:93 normalises p - centre without dividing by it, so a negative radius is the sphere of |radius| with an OUTWARD normal (not
+ * Shirley's hollow sphere); its box (sphere.rs:23-24) is inverted, which the slab test reads like the proper box but which does not widen the
+ * boxes of its ancestors, so the sphere is only seen where those cover it anyway (e.g. inside another sphere). A sphere of radius 0 is hit
+ * only where the discriminant rounds to exactly 0. Materials are not validated either: any fuzz, albedo and refraction index, non-finite ones
+ * included, go through scatter() as the shader text has them (tests/test_gpu_shade_edges.py). */
 typedef struct wfpt_sphere {
     float center[4];
     float radius;

@@ -150,6 +150,9 @@ def lib(serial=False):
     L.orc_probe_advance.argtypes = [u32, u32]
     L.orc_probe_sincos.argtypes = [vp, vp, vp, C.c_size_t]
     L.orc_probe_pow.argtypes = [vp, vp, vp, C.c_size_t]
+    L.orc_probe_min.argtypes = [vp, vp, vp, C.c_size_t]
+    L.orc_probe_max.argtypes = [vp, vp, vp, C.c_size_t]
+    L.orc_probe_shade_rb.argtypes = [u32, u32, u32, u32, u32, vp]
     L.orc_set_frame.argtypes = [vp, C.POINTER(FrameBuffer)]
     L.orc_set_counters.argtypes = [vp, vp]
     L.orc_get_counters.argtypes = [vp, vp]
@@ -381,6 +384,22 @@ class Oracle:
         out = np.zeros(1, HIT)
         h = self.L.orc_trace_bvh(self.h, _p(r), _p(out))
         return bool(h), out[0]
+
+
+def probe_shade_rb(px, py, res_x, frame, sample_number=0):
+    """shade's first draw for the hit keyed by (px, py): normalize(rng_next_vec3in_unit_sphere(state)) (sh:104, sh:111)."""
+    out = np.zeros(3, "<f4")
+    lib().orc_probe_shade_rb(px, py, res_x, frame, sample_number, _p(out))
+    return out
+
+
+def probe_minmax(a, b):
+    """(orc_min(a, b), orc_max(a, b)) element by element."""
+    a, b = np.ascontiguousarray(a, "<f4"), np.ascontiguousarray(b, "<f4")
+    mn, mx = np.zeros_like(a), np.zeros_like(a)
+    lib().orc_probe_min(_p(a), _p(b), _p(mn), a.size)
+    lib().orc_probe_max(_p(a), _p(b), _p(mx), a.size)
+    return mn, mx
 
 
 def tonemap_rgb8(acc, n_samples):

@@ -24,9 +24,15 @@ static inline uint32_t orc_f2u(float f)    { uint32_t u; memcpy(&u, &f, 4); retu
 
 static inline float orc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 static inline float orc_sqrt(float x)                  { return __builtin_sqrtf(x); }
-/* minNum/maxNum: a NaN operand yields the other operand (WGSL leaves this case open). */
-static inline float orc_min(float a, float b) { return (a != a) ? b : ((b != b) ? a : (b < a ? b : a)); }
-static inline float orc_max(float a, float b) { return (a != a) ? b : ((b != b) ? a : (b > a ? b : a)); }
+/* minNum/maxNum: a NaN operand yields the other operand (WGSL leaves this case open). Zeros are ordered -0 < +0 (IEEE 754-2019
+ * minimumNumber / maximumNumber), which is what v_min_f32 / v_max_f32 return; WGSL allows either zero. No result of the chain depends on it:
+ * the slab test only compares its min / max chain, and the dielectric clamp is min(dot, 1). */
+static inline float orc_min(float a, float b) {
+    return (a != a) ? b : ((b != b) ? a : ((b < a || (b == a && (orc_f2u(b) >> 31))) ? b : a));
+}
+static inline float orc_max(float a, float b) {
+    return (a != a) ? b : ((b != b) ? a : ((b > a || (b == a && !(orc_f2u(b) >> 31))) ? b : a));
+}
 
 /* ---- integer RNG: generate_rays.wgsl:138-181 (identical copies in shade.wgsl:228-266) ---- */
 

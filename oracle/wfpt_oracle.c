@@ -472,6 +472,12 @@ void orc_probe_sincos(const float *x, float *s, float *c, size_t n) {
 void orc_probe_pow(const float *x, const float *y, float *out, size_t n) {
     for (size_t i = 0; i < n; i++) out[i] = orc_pow(x[i], y[i]);
 }
+void orc_probe_min(const float *a, const float *b, float *out, size_t n) {
+    for (size_t i = 0; i < n; i++) out[i] = orc_min(a[i], b[i]);
+}
+void orc_probe_max(const float *a, const float *b, float *out, size_t n) {
+    for (size_t i = 0; i < n; i++) out[i] = orc_max(a[i], b[i]);
+}
 
 /* ------------------------------------------------------------------------------------------------
  * context
@@ -1317,6 +1323,13 @@ static v3 rng_next_vec3in_unit_sphere(uint32_t *state) {
     float y = r * sin_theta * sphi;
     float z = r * cos_theta;
     return v3_make(x, y, z);
+}
+/* test probe: the rb of sh:104 / sh:111 for the state sh:71-73 gives the hit keyed by (px, py) */
+void orc_probe_shade_rb(uint32_t px, uint32_t py, uint32_t res_x, uint32_t frame, uint32_t sample_number, float out3[3]) {
+    uint32_t rng_state = orc_init_rng(px, py, res_x, frame);
+    orc_advance(&rng_state, sample_number * 10u);
+    v3 rb = v3_normalize(rng_next_vec3in_unit_sphere(&rng_state));
+    out3[0] = rb.x; out3[1] = rb.y; out3[2] = rb.z;
 }
 /* sh:158-162 */
 static float schlick(float cosine, float refraction_index) {

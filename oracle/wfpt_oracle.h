@@ -89,6 +89,10 @@ float    orc_probe_next_float(uint32_t *state);
 uint32_t orc_probe_advance(uint32_t state, uint32_t n);
 void     orc_probe_sincos(const float *x, float *s, float *c, size_t n);
 void     orc_probe_pow(const float *x, const float *y, float *out, size_t n);
+void     orc_probe_min(const float *a, const float *b, float *out, size_t n); /* orc_min, the slab test's and the dielectric clamp's */
+void     orc_probe_max(const float *a, const float *b, float *out, size_t n);
+/* shade's first draw for the hit whose RNG key is (px, py): normalize(rng_next_vec3in_unit_sphere(state)) for the state orc_shade starts from */
+void     orc_probe_shade_rb(uint32_t px, uint32_t py, uint32_t res_x, uint32_t frame, uint32_t sample_number, float out3[3]);
 
 /* ---- the kernel chain ---- */
 orc_ctx *orc_create(const orc_params *p,

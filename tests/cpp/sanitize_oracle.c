@@ -39,6 +39,11 @@ int main(void) {
     orc_render_sample(c); orc_render_sample(c);
     uint64_t t[3]; orc_totals(c, t); printf("mesh rays %llu\n", (unsigned long long)t[0]);
     orc_destroy(c);
+    /* probes of the shade-edge tests */
+    float rb[3], in2[4] = {0.0f, -0.0f, 1.0f, -1.0f}, mnmx[4];
+    orc_probe_shade_rb(5, 7, 128, 2, 0, rb);
+    orc_probe_min(in2, in2 + 1, mnmx, 3); orc_probe_max(in2, in2 + 1, mnmx, 3);
+    printf("rb %g %g %g max %g\n", rb[0], rb[1], rb[2], mnmx[2]);
     free(nodes); free(tr); free(mn);
     puts("ok");
     return 0;

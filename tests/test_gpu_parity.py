@@ -44,6 +44,67 @@ def test_device_math_matches_oracle(gpu, orc):
     assert_bit_equal(gpu.selftest_math(5, k.view("<f4")), ref, "u32->unit float")
 
 
+def _ieee_specials():
+    f = np.float32
+    tiny, big = f(1.1754944e-38), f(3.4028235e38)  # FLT_MIN, FLT_MAX
+    v = [0.0, -0.0, np.inf, -np.inf, np.nan, tiny, np.nextafter(tiny, f(0)), np.nextafter(tiny, f(1)), f(1e-45), f(1e-40), big,
+         np.nextafter(big, f(0)), 1.0, -1.0, 3.0, f(2.0 ** 126), f(2.0 ** -126), f(2.0 ** 127)]
+    for e in range(-74, 64, 3):  # powers of 4 and their neighbours: exact square roots and the roundings either side
+        p = f(4.0 ** e)
+        v += [p, np.nextafter(p, f(0)), np.nextafter(p, f(np.inf))]
+    v = np.array(v, "<f4")
+    return np.concatenate([v, -v])
+
+
+def test_device_sqrt_and_divide_over_all_bit_patterns(gpu):
+    """sqrt and / are IEEE-754 correctly rounded on the device over the WHOLE format, not only the ranges the scenes produce: operands
+    drawn uniformly over bit patterns (every exponent, denormals, both signs, inf and NaN), every pair of a fixed list (+-0, +-inf, NaN,
+    FLT_MIN and its neighbours, FLT_MAX, powers of 4 +- 1 ulp; its quotients round to denormals, to FLT_MAX and past it) and 1 / x over
+    every exponent. Reference: numpy float32. A result may be NaN by IEEE rule only: the numpy side is asserted to be NaN for exactly a
+    negative radicand, 0/0, inf/inf or a NaN operand; everything else is compared bit for bit, NaNs as NaNs."""
+    from helpers import assert_bits_or_nan
+    rng = np.random.default_rng(11)
+    n = 1 << 22
+    sp = _ieee_specials()
+    a = np.concatenate([rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype("<u4").view("<f4"), np.repeat(sp, len(sp))])
+    b = np.concatenate([rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype("<u4").view("<f4"), np.tile(sp, len(sp))])
+    with np.errstate(all="ignore"):
+        want_sqrt, want_div = np.sqrt(a), a / b
+    assert np.array_equal(np.isnan(want_sqrt), np.isnan(a) | ((a < 0) & (a != 0)))
+    assert np.array_equal(np.isnan(want_div), np.isnan(a) | np.isnan(b) | ((a == 0) & (b == 0)) | (np.isinf(a) & np.isinf(b)))
+    assert (np.abs(want_div[np.isfinite(want_div)]) < 1.1754944e-38).sum() > 1000 and np.isinf(want_div[np.isfinite(a) & (b != 0)]).sum() > 1000
+    assert_bits_or_nan(gpu.selftest_math(0, a), want_sqrt, "sqrt over all bit patterns")
+    assert_bits_or_nan(gpu.selftest_math(1, a, b), want_div, "a / b over all bit patterns")
+    x = np.concatenate([(np.arange(1, 255, dtype=np.uint32)[:, None] << 23 | rng.integers(0, 1 << 23, (254, 4096), dtype=np.uint64).astype(np.uint32)).ravel(),
+                        rng.integers(1, 1 << 23, 1 << 16, dtype=np.uint64).astype(np.uint32)]).view("<f4")  # every exponent, and denormals
+    x = np.concatenate([x, -x])
+    with np.errstate(all="ignore"):
+        want = np.float32(1.0) / x
+    assert not np.isnan(want).any()
+    assert_bit_equal(gpu.selftest_math(1, np.ones_like(x), x), want, "1 / x over every exponent")
+
+
+def test_device_min_max_match_oracle(gpu, orc):
+    """Selftest ops 6 and 7 (min_, max_) against the oracle's orc_min / orc_max on all pairs from {NaN, +-0, +-inf, +-1, denormal, FLT_MAX}:
+    a NaN with a number gives the number on both sides (what the slab test and the dielectric clamp min(dot, 1) rely on), NaN with NaN
+    gives NaN. The pairs (+0, -0) and (-0, +0) are compared like all others: see DESIGN.md for what either side returns there."""
+    from helpers import assert_bits_or_nan
+    v = np.array([np.nan, 0.0, -0.0, np.inf, -np.inf, 1.0, -1.0, 1e-40, -1e-40, 3.4028235e38], "<f4")
+    a, b = np.repeat(v, len(v)), np.tile(v, len(v))
+    mn, mx = orc.probe_minmax(a, b)
+    one_nan = np.isnan(a) ^ np.isnan(b)
+    number = np.where(np.isnan(a), b, a)
+    assert_bit_equal(mn[one_nan], number[one_nan], "orc_min(NaN, x) = x")
+    assert_bit_equal(mx[one_nan], number[one_nan], "orc_max(NaN, x) = x")
+    both = np.isnan(a) & np.isnan(b)
+    assert np.isnan(mn[both]).all() and not np.isnan(mn[~both]).any()
+    g_mn, g_mx = gpu.selftest_math(6, a, b), gpu.selftest_math(7, a, b)
+    assert_bit_equal(g_mn[~both], mn[~both], "min_")
+    assert_bit_equal(g_mx[~both], mx[~both], "max_")
+    assert_bits_or_nan(g_mn[both], mn[both], "min_(NaN, NaN)")
+    assert_bits_or_nan(g_mx[both], mx[both], "max_(NaN, NaN)")
+
+
 # ------------------------------------------------------------------ stage-wise parity (Kernel::run API)
 @pytest.mark.parametrize("kind,w,h", [("simple", 64, 64), ("simple", 128, 72), ("shirley", 400, 224)])
 @pytest.mark.parametrize("rng_mode", [0, 1])

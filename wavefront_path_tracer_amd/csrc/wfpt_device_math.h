@@ -168,8 +168,10 @@ __host__ __device__ __forceinline__ float atan2_(float y, float x) {
 //   u = phi / 2pi + (0.5 + rotation), u <- u - floor(u);  v = theta / pi
 //   x = u w - 0.5, x0 = floor(x), fx = x - x0 (the same for y); column x0 mod w and x0 + 1 mod w, rows clamp(y0), clamp(y0 + 1)
 //   c = (((t00 (1-fx)(1-fy) + t10 fx (1-fy)) + t01 (1-fx) fy) + t11 fx fy) * intensity      (each weight one product)
-// x0 and y0 are clamped to the map (as floats) before they become indices: a NaN direction reads texel 0 and yields NaN, never an address
-// outside the map.
+// x0 and y0 are clamped to the map (as floats) before they become indices, so no direction reads outside the map. A zero, NaN or infinite
+// direction normalises to NaN components; atan2_'s comparisons are all false for them, so phi = theta = 0 and the lookup is the ordinary one at
+// u = 0.5 + rotation, v = 0. A direction whose squared length underflows normalises to +-inf components; atan2_ then divides inf by inf, x0 and
+// y0 are NaN, fmax(NaN, -1) = -1 and fmax(NaN, 0) = 0 pick columns w - 1 and 0 of row 0, and the NaN weights make the result NaN.
 __host__ __device__ __forceinline__ float3_ env_lookup(const float4 *tex, uint32_t w, uint32_t h, float intensity, float rotation, float dx,
                                                        float dy, float dz) {
     const float3_ n = normalize3({dx, dy, dz});
