@@ -227,7 +227,10 @@ enum {
     WFPT_FLAG_TEXTURES = 1u << 13    /* image textures on spheres and triangle meshes, see "Textures" below: up to WFPT_MAX_TEXTURES slots, a
                                         material bound to a slot multiplies the throughput of its hits by the texture as well as by its
                                         albedo. With nothing bound the context renders bit for bit as without the flag, and launches the
-                                        same kernels. */
+                                        same kernels. */,
+    WFPT_FLAG_EMISSION = 1u << 14    /* emissive materials, see "Emission" below: a material given a non-zero emission colour lights the scene
+                                        and ends the paths that hit it. With no emitter set the context renders bit for bit as without the
+                                        flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -663,6 +666,42 @@ int wfpt_set_triangle_uvs(wfpt_ctx *ctx, const float *uv6, uint32_t n_rows);
 int wfpt_sample_texture(wfpt_ctx *ctx, uint32_t slot, const float *uv, size_t n, float *rgb_out);
 /* the texture launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
 int wfpt_texture_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
+
+/* ------------------------------------------------------------------ Emission (WFPT_FLAG_EMISSION): materials that light the scene
+ * A context created with WFPT_FLAG_EMISSION holds one emission colour per material, all zero at creation. A material with a non-zero colour
+ * is an emitter -- Shirley's diffuse_light: it emits and does not scatter.
+ * The per-sample image holds the path throughput thr per pixel: 1 when the primary ray is generated, times the albedo at every hit, times
+ * the sky (or the environment map) at a miss. A context with an emitter keeps a second per-sample plane `emitted` of the same shape, 0
+ * wherever the image is set to 1. Before every shade step of every loop, an emission pass visits the hits that step will shade; for each hit
+ * on an emitter of colour e, per channel, with IEEE f32 operations and no fma:
+ *   emitted[pixel] <- emitted[pixel] + thr * e      (one multiply, one add)
+ *   thr            <- +0.0                          (the path is dead)
+ * Shade then runs unchanged: it scatters the dead path, which keeps travelling with zero throughput and adds +0 wherever it ends (0 * e = +0
+ * at another emitter). With WFPT_FLAG_TEXTURES the emission pass runs after the texture pass of the same step, so an emitter's bound texture
+ * modulates its light: emitted += (thr * tex) * e.
+ * Accumulation adds image_k + emitted_k per sample, in ascending sample order: one f32 add per channel for the sample's value, then the add
+ * into `accumulated`; every batch size and loop gives the same bits. On a WFPT_FLAG_DENOISE context the luminance moments take L of that
+ * same value. The AOVs are unchanged: a primary hit on an emitter adds its material albedo (times its texture) to the albedo sum.
+ * What does not change:
+ *   - the loop exit `misses < miss_floor`: a closed room lit by emitters alone has no misses, so it needs miss_floor = 0 to be traced at all;
+ *   - dead paths stay in the queues: they cost their bounces until they miss or max_wavefronts ends them (DESIGN.md 9g has the price);
+ *   - no next-event estimation and no shadow rays: emitters are found by path hits only.
+ * With no emitter set, a flagged context launches exactly the kernels a context without the flag launches and renders the same bits; the
+ * second plane is allocated with the first emitter.
+ * wfpt_set_emission and wfpt_clear_emission act like wfpt_bind_texture: the accumulation and the frame counter restart, the temporal
+ * history and the captured graphs are dropped. wfpt_update_scene* keeps the colours of the material indices below the new material count;
+ * the colours of indices at or beyond it are dropped (a later scene with more materials finds them zero). Viewport changes keep everything.
+ * A refused call leaves the context as it was. WFPT_ERR_INVALID_ARGUMENT without the flag, for a material index out of range and for a
+ * colour that is not finite or is negative; WFPT_ERR_UNSUPPORTED for a set or clear on a WFPT_LOOP_FUSED_BINNED context (a context with an
+ * emitter never runs the class-binned loop). wfpt_render_chunked* masks the flag off. wfpt_read_image returns thr alone. */
+/* rgb: finite and >= 0; all zeros makes the material an ordinary one again */
+int wfpt_set_emission(wfpt_ctx *ctx, uint32_t material_idx, const float rgb[3]);
+int wfpt_get_emission(wfpt_ctx *ctx, uint32_t material_idx, float rgb[3]);
+/* every material's colour back to zero */
+int wfpt_clear_emission(wfpt_ctx *ctx);
+/* the emission launches of every timed render since wfpt_create -- the passes and the zeroing of the second plane at the start of each
+ * batch (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
+int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

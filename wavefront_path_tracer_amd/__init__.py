@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -38,6 +38,7 @@ FLAG_ENVIRONMENT = 1 << 12  # misses lit by an HDR environment map (include/wfpt
 FLAG_TEXTURES = 1 << 13  # image textures on spheres and triangles (include/wfpt.h "Textures")
 MAX_TEXTURES = 64  # WFPT_MAX_TEXTURES
 TEXTURE_FILTERS = {"bilinear": 0, "nearest": 1}
+FLAG_EMISSION = 1 << 14  # emissive materials (include/wfpt.h "Emission")
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -338,6 +339,10 @@ def lib():
         "wfpt_sample_texture": (i32, [vp, u32, vp, sz, vp]),
         "wfpt_texture_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
         "wfpt_load_obj_uv": (i32, [C.c_char_p, vp, vp, u32, C.POINTER(u32), u32, u32]),
+        "wfpt_set_emission": (i32, [vp, u32, C.POINTER(f32)]),
+        "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
+        "wfpt_clear_emission": (i32, [vp]),
+        "wfpt_emission_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -568,6 +573,23 @@ def _read_png(data):
     if ch == 1:
         img = np.repeat(img, 3, axis=2)
     return np.ascontiguousarray(img[..., :3])
+
+
+def _emission_colour(rgb):
+    """rgb as the (3 x c_float) array wfpt_set_emission takes; ValueError unless it is three finite floats >= 0 (what the library accepts)."""
+    a = np.asarray(rgb, "<f4")
+    if a.shape != (3,):
+        raise ValueError(f"set_emission: expected 3 floats (r, g, b), got shape {a.shape}")
+    if not (np.isfinite(a).all() and (a >= 0).all()):
+        raise ValueError(f"set_emission: the colour must be finite and >= 0, got {a.tolist()}")
+    return (C.c_float * 3)(*a.tolist())
+
+
+def _material_index(material_idx):
+    m = int(material_idx)
+    if m != material_idx or not 0 <= m < 2 ** 32:
+        raise ValueError(f"material_idx must be an integer in 0..2^32-1, got {material_idx!r}")
+    return m
 
 
 def selftest_math(op, a, b=None, device=0):
@@ -1319,6 +1341,30 @@ class PathTracer:
         """(milliseconds, launches) of the texture launches of every timed render since creation (apart from render_timed's stage times)."""
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_texture_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    # ---- emission (contexts created with FLAG_EMISSION; include/wfpt.h "Emission")
+    def set_emission(self, material_idx, rgb):
+        """Material `material_idx` emits the colour `rgb` (3 floats, finite, >= 0) and ends the paths that hit it; all zeros makes it an
+        ordinary material again. Restarts the accumulation like a scene update."""
+        self._check(lib().wfpt_set_emission(self.handle, _material_index(material_idx), _emission_colour(rgb)))
+        self.render_progress.reset()
+
+    def emission(self, material_idx):
+        """The (3,) float32 emission colour of material `material_idx` (zeros: not an emitter)."""
+        out = (C.c_float * 3)()
+        self._check(lib().wfpt_get_emission(self.handle, _material_index(material_idx), out))
+        return np.array(out[:], "<f4")
+
+    def clear_emission(self):
+        """No material emits."""
+        self._check(lib().wfpt_clear_emission(self.handle))
+        self.render_progress.reset()
+
+    def emission_timing(self):
+        """(milliseconds, launches) of the emission launches of every timed render since creation (apart from render_timed's stage times)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_emission_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     # ---- read-back

@@ -116,6 +116,12 @@ struct TextureTables {
     DeviceBuffer<uint2> prim;
 };
 
+// The emission tables the kernels read (wfpt_ctx::em_prim, em_mat), built for a candidate state and then committed whole
+struct EmissionTables {
+    DeviceBuffer<uint32_t> prim;
+    DeviceBuffer<float4> mat;
+};
+
 struct HistoryBuffers {
     struct Slot {
         DeviceBuffer<float4> cl, nz;
@@ -228,6 +234,16 @@ struct wfpt_ctx {
     std::vector<uint32_t> h_prim_mat_idx, h_prim_row; // material_idx and _pad per primitive (textured contexts)
     double tex_ms = 0.0;        // texture launches of the timed renders since wfpt_create (wfpt_texture_timing_ms)
     uint32_t tex_launches = 0;
+    // WFPT_FLAG_EMISSION (include/wfpt.h "Emission"): the colour per material (3 floats each, all zero = no emitter), what
+    // build_emission_tables makes of them for the kernels -- per primitive its material_idx or kNoEmission, and the colours as float4 (both
+    // null while no material emits: nothing new is launched then) -- and the second per-sample plane, image's shape, allocated with the
+    // first emitter and kept
+    std::vector<float> em_rgb;
+    DeviceBuffer<uint32_t> em_prim;
+    DeviceBuffer<float4> em_mat;
+    DeviceBuffer<float> emitted;
+    double em_ms = 0.0;         // emission launches of the timed renders since wfpt_create (wfpt_emission_timing_ms)
+    uint32_t em_launches = 0;
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -565,6 +581,36 @@ TextureArgs texture_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const
 // The texture launches' entry in an event record (not a wfpt_stage, like the AOV launch's): booked into wfpt_ctx::tex_ms
 constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
 
+// a material emits: the emission passes run before the shade steps (after their texture passes) and accumulate takes the second plane
+bool emitting(const wfpt_ctx *c) { return c->em_prim.get() != nullptr; }
+// the emission pass before a shade step: the hits texture_args names, in its two forms
+EmissionArgs emission_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
+                           uint32_t material = 0xffffffffu) {
+    const TextureArgs t = texture_args(c, parity, nb, qi, n_hits, limit, material);
+    EmissionArgs a{};
+    a.batch = t.batch;
+    a.rec_in = t.rec_in;
+    a.in_hits = t.in_hits;
+    a.in_hit_base = t.in_hit_base;
+    a.q = t.q;
+    a.hq = t.hq;
+    a.n_hits = t.n_hits;
+    a.limit = t.limit;
+    a.material = t.material;
+    a.capacity = t.capacity;
+    a.image = t.image;
+    a.emitted = c->emitted.get();
+    a.ctl = t.ctl;
+    a.image_width = t.image_width;
+    a.tile = t.tile;
+    a.shade_rec = t.shade_rec;
+    a.prim_em = c->em_prim.get();
+    a.em = c->em_mat.get();
+    return a;
+}
+// The emission launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::em_ms
+constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
+
 ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
     ScanBinnedArgs a{};
     a.batch = batch_of(c, nb);
@@ -595,7 +641,7 @@ const EnvDev *env_of(const wfpt_ctx *c) { return c->env_tex.get() ? &c->env : nu
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
-    return c->bin_capable && !c->env_tex.get() && !textured(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
+    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
 }
 // The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
@@ -633,6 +679,10 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             WFPT_HIP(c, timed(kStageTexture, [&] {
                          return launch_texture(texture_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st);
                      }));
+        if (emitting(c))
+            WFPT_HIP(c, timed(kStageEmission, [&] {
+                         return launch_emission(emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st);
+                     }));
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
                      ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
@@ -662,6 +712,8 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
         if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
             WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
+        if (emitting(c)) // after the texture pass: a textured emitter's light is (thr * tex) * e
+            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
                  }));
@@ -708,6 +760,8 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
+            if (emitting(c))
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
         } else {
@@ -715,6 +769,8 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                 WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
+            if (emitting(c))
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
                               [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
         }
@@ -746,6 +802,8 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
 // The batch's accumulate launch: with the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way)
 hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
     const AccumulateArgs a = accumulate_args(c, c->n_pixels, true, nb);
+    if (emitting(c)) // each sample's value is image + emitted (the same kernels with the second plane)
+        return launch_accumulate_emission(a, c->emitted.get(), c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
     if (c->moments.get()) return launch_accumulate_moments(a, c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
     return launch_accumulate(a, c->accumulate_grid, c->stream.get());
 }
@@ -768,6 +826,10 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
         WFPT_HIP(c, timed(kStageAov, [&] {
                      const TexScene ts = tex_scene(c);
                      return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c), textured(c) ? &ts : nullptr);
+                 }));
+    if (emitting(c)) // the loops' first kernel sets every slice of `image` to 1: `emitted` starts at 0 with it
+        WFPT_HIP(c, timed(kStageEmission, [&] {
+                     return hipMemsetAsync(c->emitted.get(), 0, sizeof(float) * nb * c->image_floats, c->stream.get());
                  }));
     int r = WFPT_OK;
     switch (loop_of(c)) {
@@ -1188,7 +1250,7 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
     c->far_rays = false;
     c->depth4 = depth4;
     c->h_prim_mat_type = std::move(mat_type);
-    if (c->p.flags & WFPT_FLAG_TEXTURES) { // what build_texture_tables needs of the primitives (in the order the device holds them)
+    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION)) { // what build_texture_tables and build_emission_tables need of the primitives (in the order the device holds them)
         c->h_prim_mat_idx.resize(n_spheres);
         c->h_prim_row.resize(n_spheres);
         for (uint32_t i = 0; i < n_spheres; ++i) {
@@ -1489,7 +1551,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES); // AOVs / denoising / maps / textures of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION); // AOVs / denoising / maps / textures / emitters of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1583,6 +1645,8 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
 static int build_texture_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mat_idx,
                                 const std::vector<uint32_t> &row, TextureTables &out);
 static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t);
+static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out);
+static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
     if (!c || !(spheres || triangles) || !materials || n_prims == 0 || n_materials == 0)
@@ -1614,11 +1678,24 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         }
         if (int r = build_texture_tables(c, c->tex_dev, c->tex_bind, mat_idx, row, tables); r != WFPT_OK) return r;
     }
+    EmissionTables em_tables; // likewise; the colours of materials the new scene no longer has are dropped
+    std::vector<float> em_rgb;
+    if (c->p.flags & WFPT_FLAG_EMISSION) {
+        em_rgb = c->em_rgb;
+        em_rgb.resize(3 * static_cast<size_t>(n_materials), 0.0f);
+        std::vector<uint32_t> mat_idx(n_prims);
+        for (uint32_t i = 0; i < n_prims; ++i) mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
+        if (int r = build_emission_tables(c, em_rgb, mat_idx, em_tables); r != WFPT_OK) return r;
+    }
     if (int r = upload_scene(c, spheres, triangles, n_prims, materials, n_materials, nodes.data(), n_nodes, pair_parent,
                              static_cast<uint32_t>(depth), &c->h_camera);
         r != WFPT_OK)
         return r; // the context keeps its old scene, graphs, texture tables and accumulation
     if (c->p.flags & WFPT_FLAG_TEXTURES) commit_texture_tables(c, std::move(tables));
+    if (c->p.flags & WFPT_FLAG_EMISSION) {
+        c->em_rgb = std::move(em_rgb);
+        commit_emission_tables(c, std::move(em_tables));
+    }
     return scene_changed(c); // (no object motion vectors: the history shows the old scene)
 }
 
@@ -1653,6 +1730,7 @@ int wfpt_reset_image(wfpt_ctx *c) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, launch_fill(c->image.get(), 1.0f, c->image_floats, c->stream.get()));
+    if (c->emitted.get()) WFPT_HIP(c, hipMemsetAsync(c->emitted.get(), 0, sizeof(float) * c->image_floats, c->stream.get())); // 0 where image is 1
     return WFPT_OK;
 }
 
@@ -1720,6 +1798,8 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
     case WFPT_STAGE_SHADE:
         if (textured(c))
             WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
+        if (emitting(c))
+            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx, 0xffffffffu, true),
                                  consumer_grid(c, 1), c->stream.get()));
         break;
@@ -1730,6 +1810,10 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
             WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
                                                     static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
                                        consumer_grid(c, 1), c->stream.get()));
+        if (emitting(c))
+            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
+                                                      static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
+                                        consumer_grid(c, 1), c->stream.get()));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx,
                                             static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN), true),
                                  consumer_grid(c, 1), c->stream.get()));
@@ -1738,7 +1822,10 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         WFPT_HIP(c, launch_miss(miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1), c->stream.get(), env_of(c)));
         break;
     case WFPT_STAGE_ACCUMULATE:
-        WFPT_HIP(c, launch_accumulate(accumulate_args(c, threads, false), c->accumulate_grid, c->stream.get()));
+        if (emitting(c))
+            WFPT_HIP(c, launch_accumulate_emission(accumulate_args(c, threads, false), c->emitted.get(), nullptr, 0, c->accumulate_grid, c->stream.get()));
+        else
+            WFPT_HIP(c, launch_accumulate(accumulate_args(c, threads, false), c->accumulate_grid, c->stream.get()));
         break;
     default: break;
     }
@@ -1795,6 +1882,11 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
             if (e.stage == kStageTexture) {
                 c->tex_ms += ms;
                 c->tex_launches += 1;
+                continue;
+            }
+            if (e.stage == kStageEmission) {
+                c->em_ms += ms;
+                c->em_launches += 1;
                 continue;
             }
             stage_ms[e.stage] += ms;
@@ -2841,6 +2933,99 @@ int wfpt_texture_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_texture_timing_ms: the context was created without WFPT_FLAG_TEXTURES");
     if (ms_total) *ms_total = static_cast<float>(c->tex_ms);
     if (launches) *launches = c->tex_launches;
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- emission (include/wfpt.h "Emission")
+// The kernels' view of the colours and the scene: per primitive its material_idx when that material emits, kNoEmission otherwise, and the
+// colours as float4 (both null while no material emits). Built whole for a CANDIDATE state -- colours `rgb` (3 per material) and per
+// primitive its material_idx -- without touching the context, like build_texture_tables.
+static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out) {
+    const size_t n_mat = rgb.size() / 3;
+    std::vector<float4> mat(n_mat);
+    bool any = false;
+    for (size_t m = 0; m < n_mat; ++m) {
+        mat[m] = make_float4(rgb[3 * m], rgb[3 * m + 1], rgb[3 * m + 2], 0.0f);
+        any = any || rgb[3 * m] != 0.0f || rgb[3 * m + 1] != 0.0f || rgb[3 * m + 2] != 0.0f;
+    }
+    if (!any) return WFPT_OK;
+    const size_t n = mat_idx.size();
+    std::vector<uint32_t> t(n);
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t m = mat_idx[i];
+        const bool emits = m < n_mat && (mat[m].x != 0.0f || mat[m].y != 0.0f || mat[m].z != 0.0f);
+        t[i] = emits ? m : kNoEmission;
+    }
+    WFPT_HIP(c, out.prim.alloc(n));
+    WFPT_HIP(c, out.mat.alloc(n_mat));
+    WFPT_HIP(c, hipMemcpy(out.prim.get(), t.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    WFPT_HIP(c, hipMemcpy(out.mat.get(), mat.data(), sizeof(float4) * n_mat, hipMemcpyHostToDevice));
+    return WFPT_OK;
+}
+// the new tables replace the old ones (the stream is idle: the caller synchronised it)
+static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t) {
+    c->em_prim = std::move(t.prim);
+    c->em_mat = std::move(t.mat);
+}
+
+static int emission_check(wfpt_ctx *c, const char *who, bool changes) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_EMISSION))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_EMISSION");
+    if (changes && wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
+        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no emitters");
+    return WFPT_OK;
+}
+
+// The candidate colours replace the context's: tables first, then the second plane if this is the first emitter, and only then the commit
+static int apply_emission(wfpt_ctx *c, std::vector<float> &&rgb) {
+    WFPT_HIP(c, hipSetDevice(c->device));
+    EmissionTables tables;
+    if (int r = build_emission_tables(c, rgb, c->h_prim_mat_idx, tables); r != WFPT_OK) return r;
+    DeviceBuffer<float> plane;
+    if (tables.prim.get() && !c->emitted.get()) {
+        WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
+        WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
+    }
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
+    if (plane.get()) c->emitted = std::move(plane);
+    c->em_rgb = std::move(rgb);
+    commit_emission_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_set_emission(wfpt_ctx *c, uint32_t material_idx, const float rgb[3]) {
+    if (int r = emission_check(c, "wfpt_set_emission", true); r != WFPT_OK) return r;
+    if (!rgb) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_emission: null colour");
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_emission: material_idx out of range");
+    for (int k = 0; k < 3; ++k)
+        if (!(rgb[k] >= 0.0f && rgb[k] <= FLT_MAX)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_emission: the colour must be finite and >= 0");
+    std::vector<float> cand = c->em_rgb;
+    cand.resize(3 * static_cast<size_t>(c->scene.n_materials), 0.0f);
+    for (int k = 0; k < 3; ++k) cand[3 * static_cast<size_t>(material_idx) + k] = rgb[k] + 0.0f; // (-0 -> +0)
+    return apply_emission(c, std::move(cand));
+}
+
+int wfpt_get_emission(wfpt_ctx *c, uint32_t material_idx, float rgb[3]) {
+    if (int r = emission_check(c, "wfpt_get_emission", false); r != WFPT_OK) return r;
+    if (!rgb) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_emission: null colour");
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_emission: material_idx out of range");
+    for (int k = 0; k < 3; ++k) {
+        const size_t i = 3 * static_cast<size_t>(material_idx) + k;
+        rgb[k] = i < c->em_rgb.size() ? c->em_rgb[i] : 0.0f;
+    }
+    return WFPT_OK;
+}
+
+int wfpt_clear_emission(wfpt_ctx *c) {
+    if (int r = emission_check(c, "wfpt_clear_emission", true); r != WFPT_OK) return r;
+    return apply_emission(c, std::vector<float>(3 * static_cast<size_t>(c->scene.n_materials), 0.0f));
+}
+
+int wfpt_emission_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
+    if (int r = emission_check(c, "wfpt_emission_timing_ms", false); r != WFPT_OK) return r;
+    if (ms_total) *ms_total = static_cast<float>(c->em_ms);
+    if (launches) *launches = c->em_launches;
     return WFPT_OK;
 }
 

@@ -417,6 +417,34 @@ struct TextureArgs {
     TexScene ts;
 };
 
+// The emission pass (emission_kernel; WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): before a shade step -- and after that step's texture
+// pass -- every hit the step will shade that lies on an emitter adds thr * e to the pixel's `emitted` and leaves thr = +0 (one multiply and
+// one add per channel, no fma); shade then scatters the dead path as any other. It visits the hits exactly as texture_kernel does (the
+// records and queues forms of TextureArgs, the same per-material class filter) but reads no hit point: the pixel and the primitive only.
+// The table: prim_em[primitive] is the primitive's material_idx when that material emits and kNoEmission otherwise, in the order the
+// device holds the primitives, and em[material_idx] its colour (w unused). An index per primitive rather than a float4: the pass reads
+// 4 bytes for every hit and the colour for emitter hits only, out of a table of a few materials that stays in cache.
+constexpr uint32_t kNoEmission = 0xffffffffu;
+struct EmissionArgs {
+    Batch batch;
+    const float4 *rec_in;
+    const uint32_t *in_hits, *in_hit_base;
+    RayQueue q;
+    HitQueue hq;
+    const uint32_t *n_hits;
+    uint32_t limit;
+    uint32_t material;
+    uint32_t capacity;
+    float *image;
+    float *emitted;           // the second per-sample plane: image's shape and strides
+    const Control *ctl;
+    uint32_t image_width;
+    Tiling tile;
+    const float4 *shade_rec;  // the material class (the per-material shade stages' filter)
+    const uint32_t *prim_em;
+    const float4 *em;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -547,7 +575,10 @@ hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
+// accumulate_kernel / accumulate_moments_kernel with the second plane: each sample's value is image_k + emitted_k (moments: null = none)
+hipError_t launch_accumulate_emission(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s);
 hipError_t launch_fill(float *p, float v, size_t n, hipStream_t s);
 hipError_t launch_set_frame(Control *ctl, const wfpt_frame_buffer &f, hipStream_t s); // ctl->frame = f, ordered on the stream
 // frame band (j * world + rank) <- slab band j for the first n_valid floats of a slab: the root of the multi-GPU gather

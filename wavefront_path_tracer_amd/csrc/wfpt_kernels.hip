@@ -1749,6 +1749,48 @@ __global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a
     }
 }
 
+// ================================================================================================
+// emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
+// ================================================================================================
+// One launch before a shade step, after that step's texture pass (EmissionArgs): walks the hits texture_kernel walks -- the walk is
+// restated here, that kernel stays as it is -- and for every hit on an emitter adds thr * e to the pixel's `emitted` and leaves the
+// throughput +0: the path is dead, shade scatters it all the same. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
+__global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
+    const uint32_t smp = blockIdx.y;
+    const Control *ctl = a.ctl + smp;
+    const bool records = a.rec_in != nullptr;
+    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
+    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
+    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
+    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
+    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.in_hits[co + chunk];
+        const uint32_t base = a.in_hit_base[co + chunk];
+        if (base >= n) break; // bases ascend with the segment index
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n) break;
+            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
+            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
+            const uint32_t m_idx = a.prim_em[prim];
+            if (m_idx == kNoEmission) continue;
+            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
+                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
+                if (m > 2u) m = 0u;
+                if (m != a.material) continue;
+            }
+            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
+            const float4 e = a.em[m_idx];
+            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
+            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
+            const float4 thr = *px, had = *out;
+            *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
+            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+        }
+    }
+}
+
 // shade (sh:56-156) of hit h of the previous wavefront, as the fused loop runs it: find the hit's path record (its
 // segment is the last one whose first hit is not after h, searched between the segments that hold the first hit of
 // this run of kChunk hits and of the next run: scan's first_seg table), multiply the pixel's throughput by the albedo
@@ -3060,6 +3102,89 @@ __global__ __launch_bounds__(256) void accumulate_moments_kernel(AccumulateArgs 
     }
 }
 
+// ---- accumulate with the second per-sample plane (WFPT_FLAG_EMISSION contexts that hold an emitter; include/wfpt.h "Emission")
+// The end of accumulate_kernel and accumulate_moments_kernel, restated for the two kernels below (those two stay as they are): the
+// batch's bounce rows -> the context's totals, frame += n.
+__device__ __forceinline__ void accumulate_bookkeeping(const AccumulateArgs &a) {
+    __shared__ unsigned long long s_rows[kMaxRows][2]; // hits, misses per wavefront over the batch
+    for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += blockDim.x) (&s_rows[0][0])[k] = 0ull;
+    __syncthreads();
+    for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += blockDim.x) {
+        const Control *c = a.ctl + smp;
+        const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
+        for (uint32_t b = 0; b < rows; ++b) {
+            if (c->rows[b][0] == 0) continue;
+            atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
+            atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
+        }
+    }
+    __syncthreads();
+    Control *c0 = a.ctl;
+    if (threadIdx.x < kMaxRows) {
+        const uint32_t b = threadIdx.x;
+        const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
+        if (h + m) {
+            c0->wave_totals[b][0] += h + m;
+            c0->wave_totals[b][1] += h;
+            c0->wave_totals[b][2] += m;
+        }
+    }
+    if (threadIdx.x == 0) {
+        unsigned long long h = 0, m = 0;
+        for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
+        c0->totals[0] += h + m;
+        c0->totals[1] += h;
+        c0->totals[2] += m;
+        c0->totals[3] += a.batch.n;
+        c0->samples += a.batch.n;
+        c0->ticket = 0;
+        c0->frame.frame += a.batch.n;
+    }
+}
+
+// accumulated += (image_k + emitted_k) in sample order: one add for the sample's value, one into the sum (MOMENTS: the luminance moments
+// take L of that same value). TRIP samples a trip, two loads each: 8 for the plain kernel -- accumulate_kernel's sixteen loads in flight
+// -- and 4 with the moments, accumulate_moments_kernel's trip.
+template <bool MOMENTS, uint32_t TRIP>
+__device__ __forceinline__ void accumulate_emission_body(const AccumulateArgs &a, const float *emitted, float *moments, Stride32 plane) {
+    const size_t stride4 = a.batch.image_stride / 4u;
+    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
+    const float4 *emit4 = reinterpret_cast<const float4 *>(emitted);
+    float *s2p = MOMENTS ? moments + static_cast<size_t>(plane) : nullptr;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n_pixels; i += gridDim.x * blockDim.x) {
+        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
+        float s1 = 0.0f, s2 = 0.0f;
+        if (MOMENTS) { s1 = moments[i]; s2 = s2p[i]; }
+        auto add = [&](const float4 &p, const float4 &e) {
+            const float vr = p.x + e.x, vg = p.y + e.y, vb = p.z + e.z;
+            r += vr; g += vg; b += vb;
+            if (MOMENTS) {
+                const float l = denoise_luma(vr, vg, vb);
+                s1 += l; s2 += l * l;
+            }
+        };
+        const float4 *im0 = image4 + i, *em0 = emit4 + i;
+        uint32_t smp = 0;
+        for (; smp + TRIP <= a.batch.n; smp += TRIP) {
+            float4 p[TRIP], e[TRIP];
+#pragma unroll
+            for (uint32_t k = 0; k < TRIP; ++k) { p[k] = im0[(smp + k) * stride4]; e[k] = em0[(smp + k) * stride4]; }
+#pragma unroll
+            for (uint32_t k = 0; k < TRIP; ++k) add(p[k], e[k]);
+        }
+        for (; smp < a.batch.n; ++smp) add(im0[smp * stride4], em0[smp * stride4]);
+        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
+        if (MOMENTS) { moments[i] = s1; s2p[i] = s2; }
+    }
+    if (blockIdx.x == 0 && a.bookkeeping) accumulate_bookkeeping(a);
+}
+__global__ __launch_bounds__(256) void accumulate_emission_kernel(AccumulateArgs a, const float *emitted) {
+    accumulate_emission_body<false, 8u>(a, emitted, nullptr, Stride32{});
+}
+__global__ __launch_bounds__(256) void accumulate_emission_moments_kernel(AccumulateArgs a, const float *emitted, float *moments, Stride32 plane) {
+    accumulate_emission_body<true, 4u>(a, emitted, moments, plane);
+}
+
 // The filter's pixel of this thread: a workgroup covers a kDenoiseTile^2 block, each wave an 8 x 8 block of it (2-D locality for the taps,
 // as generate_rays_kernel's tiles). False for the padding lanes of partial blocks.
 __device__ inline bool denoise_pixel(const DenoiseArgs &a, uint32_t &x, uint32_t &y) {
@@ -3547,6 +3672,12 @@ hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(emission_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s) {
     hipLaunchKernelGGL(accumulate_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -3637,6 +3768,16 @@ hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, si
     Stride32 pl{};
     pl = plane;
     hipLaunchKernelGGL(accumulate_moments_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, moments, pl);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_emission(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s) {
+    Stride32 pl{};
+    pl = plane;
+    if (moments)
+        hipLaunchKernelGGL(accumulate_emission_moments_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, emitted, moments, pl);
+    else
+        hipLaunchKernelGGL(accumulate_emission_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, emitted);
     return hipGetLastError();
 }
 

@@ -349,6 +349,20 @@ class PathTracer {
         check(wfpt_texture_timing_ms(ctx_, &ms, &n));
         return {ms, n};
     }
+    // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
+    void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
+    std::array<float, 3> emission(uint32_t material_idx) {
+        std::array<float, 3> rgb{};
+        check(wfpt_get_emission(ctx_, material_idx, rgb.data()));
+        return rgb;
+    }
+    void clear_emission() { check(wfpt_clear_emission(ctx_)); }
+    std::pair<float, uint32_t> emission_timing() {
+        float ms = 0.0f;
+        uint32_t n = 0;
+        check(wfpt_emission_timing_ms(ctx_, &ms, &n));
+        return {ms, n};
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
