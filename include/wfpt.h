@@ -230,7 +230,10 @@ enum {
                                         same kernels. */,
     WFPT_FLAG_EMISSION = 1u << 14    /* emissive materials, see "Emission" below: a material given a non-zero emission colour lights the scene
                                         and ends the paths that hit it. With no emitter set the context renders bit for bit as without the
-                                        flag, and launches the same kernels. */
+                                        flag, and launches the same kernels. */,
+    WFPT_FLAG_NEE = 1u << 15         /* next-event estimation, see "Next-event estimation" below: every diffuse hit sends one shadow ray to a
+                                        sampled point of an emitter. Needs WFPT_FLAG_EMISSION. With no emitter set the context renders bit
+                                        for bit as without the flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -685,7 +688,7 @@ int wfpt_texture_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * What does not change:
  *   - the loop exit `misses < miss_floor`: a closed room lit by emitters alone has no misses, so it needs miss_floor = 0 to be traced at all;
  *   - dead paths stay in the queues: they cost their bounces until they miss or max_wavefronts ends them (DESIGN.md 9g has the price);
- *   - no next-event estimation and no shadow rays: emitters are found by path hits only.
+ *   - without WFPT_FLAG_NEE ("Next-event estimation" below) there are no shadow rays: emitters are found by path hits only.
  * With no emitter set, a flagged context launches exactly the kernels a context without the flag launches and renders the same bits; the
  * second plane is allocated with the first emitter.
  * wfpt_set_emission and wfpt_clear_emission act like wfpt_bind_texture: the accumulation and the frame counter restart, the temporal
@@ -702,6 +705,57 @@ int wfpt_clear_emission(wfpt_ctx *ctx);
 /* the emission launches of every timed render since wfpt_create -- the passes and the zeroing of the second plane at the start of each
  * batch (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
 int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
+
+/* ------------------------------------------------------------------ Next-event estimation (WFPT_FLAG_NEE): shadow rays to the emitters
+ * wfpt_create* accepts WFPT_FLAG_NEE only together with WFPT_FLAG_EMISSION (WFPT_ERR_INVALID_ARGUMENT otherwise). A flagged context with
+ * an emitter keeps a light list: the indices of all primitives whose material emits, in the order the device holds the primitives,
+ * resolved wherever the emission table is (wfpt_set_emission, wfpt_clear_emission, wfpt_update_scene*). Before every shade step of every
+ * loop the passes run in the order texture, emission, connect, shade. Each pixel has a connected flag, 0 wherever the image is set to 1.
+ * The connect pass visits the hits the step will shade. For hit h of wavefront b (b = 0 for the primary hits; the stage API counts the
+ * extend stages since the last generate_rays stage):
+ *  1. The hit is diffuse when its material class is Lambertian (mat_type 0 or above 2) and its material does not emit. A diffuse hit sets
+ *     the pixel's flag to 1 and goes on; every other hit (metal, dielectric, emitter) clears it to 0 and does nothing else.
+ *  2. Three draws u0 u1 u2 from a stream of the pass's own, keyed by the pixel in both RNG modes (shade's stream is not touched):
+ *       s = init_rng((x, y), (W, H), frame) = jenkins_hash((x + y W) ^ jenkins_hash(frame)), frame the sample's frame (no advance by
+ *       sample_number);  s <- jenkins_hash(s ^ (0x9E3779B9 * (b + 1)))  (u32 arithmetic);  then three rng_next_float(s).
+ *  3. With n_l lights, nf = f32(n_l): light i = min(floor(u0 * nf), n_l - 1), its primitive's material emits e. A point q on it, uniform by
+ *     area, its normal nl and its area A. All operations are IEEE f32 add, sub, mul, div, sqrt in the order written, no fma; sin and cos
+ *     are the library's own (wfpt_selftest_math), pi = 3.1415927f, 2 pi and 4 pi its exact doubles:
+ *       sphere (c, radius):  ra = |radius|;  z = 1 - 2 u1;  r = sqrt(max(0, 1 - z z));  phi = (2 pi) u2;
+ *                            q = c + ra * (r cos phi, r sin phi, z)   (per component: the product in the parentheses, times ra, plus c);
+ *                            nl = (q - c) / ra   (three divisions);  A = (4 pi) * (ra ra)
+ *       triangle (v0, e1, e2):  su = sqrt(u1);  b1 = 1 - su;  b2 = u2 su;  q = (v0 + b1 e1) + b2 e2;
+ *                            nl = the stored normalize(cross(e1, e2));  cr = cross(e1, e2), each component one difference of two products
+ *                            (e1.y e2.z - e1.z e2.y, ...);  A = 0.5 * sqrt((cr.x cr.x + cr.y cr.y) + cr.z cr.z)
+ *     Lights emit from both sides.
+ *  4. p = o + t d as shade computes it (shade.wgsl:91), n the normal shade scatters about (never flipped):
+ *       v = q - p;  dist2 = (v.x v.x + v.y v.y) + v.z v.z;  dist = sqrt(dist2);  w = v / dist   (three divisions);
+ *       cos_s = (n.x w.x + n.y w.y) + n.z w.z;  cos_l = |(nl.x w.x + nl.y w.y) + nl.z w.z|
+ *     The sample contributes only if A > 0, dist2 > 0, cos_s > 0 and cos_l > 0 (a NaN fails each test). Then the ray (p, w) is traced with
+ *     the context's own traversal (t_min = 0.001, extend.wgsl:90); the sample is occluded iff the closest hit has t < dist * 0.999.
+ *  5. An unoccluded sample adds, per channel, emitted[pixel] += ((thr * albedo) * e_q) * G with
+ *       G = (((cos_s * cos_l) * A) * nf) / (pi * dist2)
+ *     thr the pixel's throughput after the texture and emission passes of this step, albedo the one shade will multiply in, e_q = e, or
+ *     e * tex per channel where the light's material is bound to a texture (the texture pass's lookup at q).
+ * The emission pass of such a context still leaves thr = +0 at a hit on an emitter, but adds thr * e only where the pixel's connected flag
+ * is 0: at primary hits and after a metal or dielectric bounce. After a diffuse bounce the connect pass has already counted that light
+ * (next-event estimation without multiple importance sampling).
+ * Shade, the tracing kernels, miss, the loop exit, the AOVs, accumulation (image + emitted in sample order) and the luminance moments are
+ * unchanged, and dead paths keep travelling. Every batch size, loop, RNG mode's queue order and band sharding gives the same connect
+ * samples: the stream is keyed by the pixel.
+ * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
+ * context with the flag and an emitter never runs the class-binned loop (set and clear on such a context are refused, see "Emission");
+ * wfpt_render_chunked* masks the flag off. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag.
+ * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, importance sampling of
+ * the environment map, retiring dead or fully shadowed paths, contact shadows thinner than the 0.001 / 0.1 % windows. */
+/* the number of emitting primitives (the light list's length), 0 with none; negative: a wfpt_status */
+int wfpt_nee_light_count(wfpt_ctx *ctx);
+/* the connect launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
+int wfpt_nee_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
+/* Steps 3 and 4 for n caller-supplied receivers on the device. in9: n rows of (p.xyz, n.xyz, u0, u1, u2); out8: n rows of (q.xyz, the
+ * light's primitive index as a float, the unoccluded factor e_q * G per channel -- 0 where the sample contributes nothing --, 1.0 if the
+ * sample is occluded and 0.0 otherwise). WFPT_ERR_INVALID_ARGUMENT while no primitive emits. */
+int wfpt_sample_lights(wfpt_ctx *ctx, const float *in9, size_t n, float *out8);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -39,6 +39,7 @@ FLAG_TEXTURES = 1 << 13  # image textures on spheres and triangles (include/wfpt
 MAX_TEXTURES = 64  # WFPT_MAX_TEXTURES
 TEXTURE_FILTERS = {"bilinear": 0, "nearest": 1}
 FLAG_EMISSION = 1 << 14  # emissive materials (include/wfpt.h "Emission")
+FLAG_NEE = 1 << 15  # shadow rays from diffuse hits to the emitters (include/wfpt.h "Next-event estimation"); needs FLAG_EMISSION
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -343,6 +344,9 @@ def lib():
         "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_clear_emission": (i32, [vp]),
         "wfpt_emission_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_nee_light_count": (i32, [vp]),
+        "wfpt_nee_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_sample_lights": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -1366,6 +1370,30 @@ class PathTracer:
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_emission_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
+
+    # ---- next-event estimation (contexts created with FLAG_EMISSION | FLAG_NEE; include/wfpt.h "Next-event estimation")
+    def nee_light_count(self):
+        """The number of emitting primitives (the light list the connect pass samples), 0 with none."""
+        n = lib().wfpt_nee_light_count(self.handle)
+        if n < 0:
+            self._check(n)
+        return int(n)
+
+    def nee_timing(self):
+        """(milliseconds, launches) of the connect launches of every timed render since creation (apart from render_timed's stage times)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_nee_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def sample_lights(self, rows):
+        """The connect pass's light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 of (p.xyz, n.xyz,
+        u0, u1, u2); returns (n, 8) float32 of (q.xyz, the light's primitive index, the unoccluded factor e_q * G per channel, occluded 0/1)."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != 9:
+            raise ValueError(f"sample_lights: expected rows of 9 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 8), "<f4")
+        self._check(lib().wfpt_sample_lights(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
 
     # ---- read-back
     def accumulated(self):

@@ -120,6 +120,8 @@ struct TextureTables {
 struct EmissionTables {
     DeviceBuffer<uint32_t> prim;
     DeviceBuffer<float4> mat;
+    DeviceBuffer<uint32_t> lights; // WFPT_FLAG_NEE contexts: the primitives whose material emits, in primitive order
+    uint32_t n_lights = 0;
 };
 
 struct HistoryBuffers {
@@ -244,6 +246,13 @@ struct wfpt_ctx {
     DeviceBuffer<float> emitted;
     double em_ms = 0.0;         // emission launches of the timed renders since wfpt_create (wfpt_emission_timing_ms)
     uint32_t em_launches = 0;
+    // WFPT_FLAG_NEE (include/wfpt.h "Next-event estimation"): the light list build_emission_tables resolves with the tables above (null
+    // while no material emits: nothing new is launched then), and the stage API's wavefront counter (extends since the last generate_rays)
+    DeviceBuffer<uint32_t> nee_lights;
+    uint32_t n_lights = 0;
+    uint32_t stage_extends = 0;
+    double nee_ms = 0.0;        // connect launches of the timed renders since wfpt_create (wfpt_nee_timing_ms)
+    uint32_t nee_launches = 0;
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -611,6 +620,46 @@ EmissionArgs emission_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, con
 // The emission launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::em_ms
 constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
 
+// a WFPT_FLAG_NEE context holds an emitter: the connect passes run before the shade steps (after their emission passes, which then add a
+// hit light only where the pixel's connected flag is 0)
+bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr; }
+// the connect pass before a shade step of wavefront `wavefront`: the hits emission_args names, in its two forms
+ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
+                         uint32_t material = 0xffffffffu) {
+    const EmissionArgs e = emission_args(c, parity, nb, qi, n_hits, limit, material);
+    ConnectArgs a{};
+    a.batch = e.batch;
+    a.rec_in = e.rec_in;
+    a.in_hits = e.in_hits;
+    a.in_hit_base = e.in_hit_base;
+    a.q = e.q;
+    a.hq = e.hq;
+    a.n_hits = e.n_hits;
+    a.limit = e.limit;
+    a.material = e.material;
+    a.capacity = e.capacity;
+    a.image = e.image;
+    a.emitted = e.emitted;
+    a.ctl = e.ctl;
+    a.image_width = e.image_width;
+    a.tile = e.tile;
+    a.n_chunks_max = c->n_chunks_max;
+    a.wavefront = wavefront;
+    a.prim_em = e.prim_em;
+    a.em = e.em;
+    a.lights = c->nee_lights.get();
+    a.n_lights = c->n_lights;
+    a.ts = tex_scene(c);
+    a.scene = c->scene;
+    return a;
+}
+// persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
+hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
+    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c));
+}
+// The connect launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::nee_ms
+constexpr int kStageConnect = WFPT_STAGE_COUNT + 3;
+
 ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
     ScanBinnedArgs a{};
     a.batch = batch_of(c, nb);
@@ -681,7 +730,11 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      }));
         if (emitting(c))
             WFPT_HIP(c, timed(kStageEmission, [&] {
-                         return launch_emission(emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st);
+                         return launch_emission(emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st, connecting(c));
+                     }));
+        if (connecting(c))
+            WFPT_HIP(c, timed(kStageConnect, [&] {
+                         return launch_connect_pass(c, connect_args(c, b, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), nb);
                      }));
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
@@ -713,7 +766,9 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
             WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
         if (emitting(c)) // after the texture pass: a textured emitter's light is (thr * tex) * e
-            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
+            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+        if (connecting(c)) // after the emission pass, which reads the flag the previous step's connect pass left
+            WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
                  }));
@@ -761,7 +816,9 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+            if (connecting(c))
+                WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
         } else {
@@ -770,7 +827,9 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st); }));
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+            if (connecting(c))
+                WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
                               [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
         }
@@ -1228,6 +1287,7 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
     int blocks = 1, bounce_blocks = 1, binned_blocks = static_cast<int>(c->bounce_binned_blocks_per_cu);
     WFPT_HIP(c, extend_blocks_per_cu(sc, &blocks));
     if (c->p.flags & WFPT_FLAG_AOV) WFPT_HIP(c, aov_prepare(sc));
+    if (c->p.flags & WFPT_FLAG_NEE) WFPT_HIP(c, connect_prepare(sc));
     if (c->bin_capable && lds_scene) WFPT_HIP(c, bounce_binned_blocks_per_cu(sc, &binned_blocks));
     WFPT_HIP(c, bounce_blocks_per_cu(sc, &bounce_blocks));
     blocks = std::max(blocks, 1);
@@ -1340,6 +1400,10 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
     if ((params->flags & WFPT_FLAG_BINNING) != 0 && params->rng_mode != WFPT_RNG_PIXEL) {
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_BINNING needs WFPT_RNG_PIXEL (the class-binned loop reorders the hit queue, which "
                                                  "shade.wgsl:72's RNG key, the dispatch's thread index, does not allow)");
+        return nullptr;
+    }
+    if ((params->flags & WFPT_FLAG_NEE) != 0 && (params->flags & WFPT_FLAG_EMISSION) == 0) {
+        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
         return nullptr;
     }
     if (params->max_wavefronts == 0 || params->max_wavefronts > static_cast<uint32_t>(kMaxRows)) {
@@ -1551,7 +1615,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION); // AOVs / denoising / maps / textures / emitters of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1766,6 +1830,9 @@ int wfpt_swap_ray_queues(wfpt_ctx *c) {
     return WFPT_OK;
 }
 
+// The stage API's wavefront index: a shade stage shades the hits of the last extend, extends are counted since the last generate_rays
+static uint32_t stage_wavefront(const wfpt_ctx *c) { return c->stage_extends ? c->stage_extends - 1u : 0u; }
+
 int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "null context");
     if (stage < 0 || stage >= WFPT_STAGE_SCAN) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_kernel_run: unknown stage");
@@ -1788,18 +1855,22 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
     switch (stage) {
     case WFPT_STAGE_GENERATE_RAYS:
         c->hit_rec_valid = false;
+        c->stage_extends = 0;
         WFPT_HIP(c, launch_generate(generate_args(c, gx, gy, false), c->stream.get()));
         break;
     case WFPT_STAGE_EXTEND:
         WFPT_HIP(c, launch_extend(extend_args(c, c->cur, &c->ctl.get()->counters[2], threads), extend_grid(c, 1), c->stream.get(), env_of(c) != nullptr));
         WFPT_HIP(c, launch_scan(scan_args(c, &c->ctl.get()->counters[2], threads, false, 0), c->stream.get()));
+        c->stage_extends += 1;   // the connect pass of the shade stages that follow keys its stream by the wavefront, stage_wavefront()
         c->hit_rec_valid = true; // shade may stream extend's path records until the host touches the ray queue (generate_rays, write, swap, clear)
         break;
     case WFPT_STAGE_SHADE:
         if (textured(c))
             WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
         if (emitting(c))
-            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
+            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get(), connecting(c)));
+        if (connecting(c))
+            WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads), 1));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx, 0xffffffffu, true),
                                  consumer_grid(c, 1), c->stream.get()));
         break;
@@ -1813,7 +1884,10 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         if (emitting(c))
             WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
                                                       static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
-                                        consumer_grid(c, 1), c->stream.get()));
+                                        consumer_grid(c, 1), c->stream.get(), connecting(c)));
+        if (connecting(c)) // the Lambertian stage connects, the other two only clear the pixels' connected flags
+            WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
+                                                            static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)), 1));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx,
                                             static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN), true),
                                  consumer_grid(c, 1), c->stream.get()));
@@ -1887,6 +1961,11 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
             if (e.stage == kStageEmission) {
                 c->em_ms += ms;
                 c->em_launches += 1;
+                continue;
+            }
+            if (e.stage == kStageConnect) {
+                c->nee_ms += ms;
+                c->nee_launches += 1;
                 continue;
             }
             stage_ms[e.stage] += ms;
@@ -2960,12 +3039,24 @@ static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, con
     WFPT_HIP(c, out.mat.alloc(n_mat));
     WFPT_HIP(c, hipMemcpy(out.prim.get(), t.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     WFPT_HIP(c, hipMemcpy(out.mat.get(), mat.data(), sizeof(float4) * n_mat, hipMemcpyHostToDevice));
+    if (c->p.flags & WFPT_FLAG_NEE) { // the light list: every primitive whose material emits, in primitive order (at least one: `any`
+        std::vector<uint32_t> lights;  // may hold for a material no primitive uses, and then there is nothing to connect to)
+        for (size_t i = 0; i < n; ++i)
+            if (t[i] != kNoEmission) lights.push_back(static_cast<uint32_t>(i));
+        if (!lights.empty()) {
+            WFPT_HIP(c, out.lights.alloc(lights.size()));
+            WFPT_HIP(c, hipMemcpy(out.lights.get(), lights.data(), sizeof(uint32_t) * lights.size(), hipMemcpyHostToDevice));
+            out.n_lights = static_cast<uint32_t>(lights.size());
+        }
+    }
     return WFPT_OK;
 }
 // the new tables replace the old ones (the stream is idle: the caller synchronised it)
 static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t) {
     c->em_prim = std::move(t.prim);
     c->em_mat = std::move(t.mat);
+    c->nee_lights = std::move(t.lights);
+    c->n_lights = t.n_lights;
 }
 
 static int emission_check(wfpt_ctx *c, const char *who, bool changes) {
@@ -3026,6 +3117,51 @@ int wfpt_emission_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = emission_check(c, "wfpt_emission_timing_ms", false); r != WFPT_OK) return r;
     if (ms_total) *ms_total = static_cast<float>(c->em_ms);
     if (launches) *launches = c->em_launches;
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- next-event estimation (include/wfpt.h "Next-event estimation")
+static int nee_check(wfpt_ctx *c, const char *who) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_NEE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_NEE");
+    return WFPT_OK;
+}
+
+int wfpt_nee_light_count(wfpt_ctx *c) {
+    if (int r = nee_check(c, "wfpt_nee_light_count"); r != WFPT_OK) return r;
+    return static_cast<int>(c->n_lights);
+}
+
+int wfpt_nee_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
+    if (int r = nee_check(c, "wfpt_nee_timing_ms"); r != WFPT_OK) return r;
+    if (ms_total) *ms_total = static_cast<float>(c->nee_ms);
+    if (launches) *launches = c->nee_launches;
+    return WFPT_OK;
+}
+
+int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
+    if (int r = nee_check(c, "wfpt_sample_lights"); r != WFPT_OK) return r;
+    if (!connecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
+    if ((!in9 || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(9 * n);
+    if (e == hipSuccess) e = d_out.alloc(8 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) {
+        ConnectArgs a = connect_args(c, 0, -1, 1);
+        a.sample_in = d_in.get();
+        a.sample_out = d_out.get();
+        a.sample_n = static_cast<uint32_t>(n);
+        const uint64_t items = (n + kChunk - 1) / kChunk;
+        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
+                           textured(c));
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights");
     return WFPT_OK;
 }
 

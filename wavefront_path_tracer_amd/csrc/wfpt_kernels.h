@@ -445,6 +445,42 @@ struct EmissionArgs {
     const float4 *em;
 };
 
+// The connect pass (connect_kernel; WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): before a shade step, after that step's texture
+// and emission passes, every hit the step will shade either sends one shadow ray to a sampled point of a light and adds the unoccluded
+// sample to the pixel's `emitted` (a diffuse hit: the pixel's connected flag, emitted.w, becomes 1) or only clears the flag (every other
+// hit). It visits the hits as emission_kernel does (both forms, the same class filter) and traces with the context's own walk
+// (WFPT_TRACE_ANY), so it carries the scene like the other tracing kernels. `lights`: the primitives whose material emits, in primitive
+// order. `wavefront`: the index b of the wavefront whose hits these are (the key of the pass's own random stream).
+// The sampler form (sample_in != null; wfpt_sample_lights): sample_n rows of (point, normal, u0 u1 u2) instead of hits, one row of
+// (q, light primitive, e_q G, occluded) each out; nothing else is read or written.
+struct ConnectArgs {
+    Batch batch;
+    const float4 *rec_in;
+    const uint32_t *in_hits, *in_hit_base;
+    RayQueue q;
+    HitQueue hq;
+    const uint32_t *n_hits;
+    uint32_t limit;
+    uint32_t material;
+    uint32_t capacity;
+    float *image;
+    float *emitted;
+    const Control *ctl;
+    uint32_t image_width;
+    Tiling tile;
+    uint32_t n_chunks_max;    // segments per sample: the work items are (sample, segment) pairs, sample-major
+    uint32_t wavefront;
+    const uint32_t *prim_em;
+    const float4 *em;
+    const uint32_t *lights;
+    uint32_t n_lights;
+    const float *sample_in;
+    float *sample_out;
+    uint32_t sample_n;
+    TexScene ts;              // the textures of the lights (the TEX variants only)
+    SceneDev scene;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -575,7 +611,11 @@ hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s);
+// nee: the variant of contexts that connect (WFPT_FLAG_NEE with an emitter): adds thr * e only where the pixel's connected flag is 0
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee = false);
+// grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured);
+hipError_t connect_prepare(const SceneDev &scene); // raises the connect kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
 // accumulate_kernel / accumulate_moments_kernel with the second plane: each sample's value is image_k + emitted_k (moments: null = none)
 hipError_t launch_accumulate_emission(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s);

@@ -901,6 +901,96 @@ __device__ __forceinline__ bool trace_ray_conservative(const float4 *nodes_ch, c
     return nearest < 1e30f; // ex:157
 }
 
+// ---- the occlusion walk of the connect pass (WFPT_FLAG_NEE) for scenes in LDS: trace_ray_conservative's walk started with
+// nearest = `window` and ended at the first primitive the exact test accepts inside (0.001, window). What it answers is "does the
+// reference's closest hit lie inside the window", in three values:
+//   kOccNone       nothing accepted: the walk reaches every leaf the reference enters (see above; a box pruned by `window` holds nothing
+//                  nearer than it), so the reference tests no primitive with t < window either;
+//   kOccHit        primitive b accepted and its leaf's box passes the reference's test with entry distance <= t(b) (leaf_box_verdict):
+//                  then the reference tests b too (the argument at visit_leaf), so its closest hit is at most t(b) < window. Which
+//                  primitive wins does not matter, so no near-tie watch is needed;
+//   kOccUndecided  b's leaf fails that verdict (a false positive of the exact test outside its box): the caller asks the closest-hit
+//                  walk, as it does for origins beyond the safe radius.
+// The inner-node loop is descend_asm (or the compiler's loop), unchanged: `nearest` is an input there.
+constexpr uint32_t kOccNone = 0u, kOccHit = 1u, kOccUndecided = 2u;
+template <typename Trail, int PRIM, typename ParentT>
+__device__ __forceinline__ uint32_t occluded_conservative(const float4 *nodes_ch, const float4 *prim_geom, const ParentT *pair_parent, float ox,
+                                                          float oy, float oz, float dx, float dy, float dz, uint32_t max_steps,
+                                                          float window WFPT_DBG_PARAM) {
+    const float a = (dx * dx + dy * dy) + dz * dz;
+    const float bx = min_(max_(1.0f / dx, -1e30f), 1e30f), by = min_(max_(1.0f / dy, -1e30f), 1e30f), bz = min_(max_(1.0f / dz, -1e30f), 1e30f);
+    const float nox = -(ox * bx), noy = -(oy * by), noz = -(oz * bz);
+    const float ax = __builtin_fabsf(bx), ay = __builtin_fabsf(by), az = __builtin_fabsf(bz);
+    uint32_t node = 0;
+    uint32_t left_first = __float_as_uint(nodes_ch[0].w), prim_count = __float_as_uint(nodes_ch[1].w);
+    Trail trail = 0;
+    const bool root_leaf = prim_count != 0u;
+    uint32_t budget = max_steps, verdict = kOccNone;
+    const uint32_t nodes_lds = uniform(lds_offset(nodes_ch)), parent_lds = uniform(lds_offset(pair_parent));
+#define WFPT_OCC_POP()                                                                                                                 \
+    do {                                                                                                                               \
+        if (trail == 0) {                                                                                                              \
+            prim_count = kWalkDone;                                                                                                    \
+        } else {                                                                                                                       \
+            const uint32_t up = (sizeof(Trail) == 8) ? static_cast<uint32_t>(__ffsll(static_cast<long long>(trail)) - 1)              \
+                                                     : static_cast<uint32_t>(__ffs(static_cast<int>(trail)) - 1);                      \
+            trail = (trail >> up) & ~static_cast<Trail>(1);                                                                            \
+            for (uint32_t k = 0; k < up; ++k) node = pair_parent[node >> 1];                                                           \
+            node ^= 1u;                                                                                                                \
+            left_first = __float_as_uint(nodes_ch[2u * node].w);                                                                       \
+            prim_count = __float_as_uint(nodes_ch[2u * node + 1u].w);                                                                  \
+        }                                                                                                                              \
+    } while (0)
+    while (prim_count != kWalkDone) {
+        if (WFPT_WALK_ASM && sizeof(Trail) == 4 && sizeof(ParentT) == 2) {
+            uint32_t trail32 = static_cast<uint32_t>(trail);
+            descend_asm(nodes_lds, parent_lds, bx, by, bz, nox, noy, noz, window, node, left_first, prim_count, trail32 WFPT_DBG_ARG);
+            trail = static_cast<Trail>(trail32);
+        } else
+        while (prim_count == 0u) {
+            const float4 *pair = nodes_ch + 2u * left_first;
+            const float4 lc = pair[0], lh = pair[1], rc = pair[2], rh = pair[3];
+            keep4(lc, lh, rc, rh);
+            const float lcx = fma_(lc.x, bx, nox), lcy = fma_(lc.y, by, noy), lcz = fma_(lc.z, bz, noz);
+            const float l_in = max_(max_(fma_(lh.x, -ax, lcx), fma_(lh.y, -ay, lcy)), fma_(lh.z, -az, lcz));
+            const float l_out = min_(min_(fma_(lh.x, ax, lcx), fma_(lh.y, ay, lcy)), fma_(lh.z, az, lcz));
+            const float rcx = fma_(rc.x, bx, nox), rcy = fma_(rc.y, by, noy), rcz = fma_(rc.z, bz, noz);
+            const float r_in = max_(max_(fma_(rh.x, -ax, rcx), fma_(rh.y, -ay, rcy)), fma_(rh.z, -az, rcz));
+            const float r_out = min_(min_(fma_(rh.x, ax, rcx), fma_(rh.y, ay, rcy)), fma_(rh.z, az, rcz));
+            const bool hit_l = max_(l_in, 0.0f) <= min_(l_out, window);
+            const bool hit_r = max_(r_in, 0.0f) <= min_(r_out, window);
+            const bool go_right = hit_r && (!hit_l || l_in > r_in);
+            if (hit_l || hit_r) {
+                node = left_first + (go_right ? 1u : 0u);
+                trail = (trail << 1) | static_cast<Trail>((hit_l && hit_r) ? 1u : 0u);
+                left_first = __float_as_uint(go_right ? rc.w : lc.w);
+                prim_count = __float_as_uint(go_right ? rh.w : lh.w);
+            } else {
+                WFPT_OCC_POP();
+            }
+        }
+        if (prim_count != kWalkDone) { // leaf
+            if (budget-- == 0) {
+                verdict = kOccUndecided;
+                prim_count = kWalkDone;
+            } else {
+                float t = window;
+                uint32_t b = 0xffffffffu;
+                for (uint32_t i = 0; i < prim_count; ++i) hit_prim<PRIM>(prim_geom, left_first + i, ox, oy, oz, dx, dy, dz, a, t, b);
+                if (b != 0xffffffffu) { // the first accepted primitive ends the walk: its leaf's box decides between "hit" and "ask again"
+                    leaf_box_verdict<PRIM>(prim_geom, left_first, prim_count, root_leaf, ox, oy, oz, dx, dy, dz, t, b);
+                    verdict = b == kHandOver ? kOccUndecided : kOccHit;
+                    prim_count = kWalkDone;
+                } else {
+                    WFPT_OCC_POP();
+                }
+            }
+        }
+    }
+#undef WFPT_OCC_POP
+    return verdict;
+}
+
 // ---- four-wide traversal for HBM-resident scenes (build extension) ----------------------------
 // The closest hit does not depend on the order in which nodes are visited (only on which primitives pass the exact
 // test; equal-t ties between different primitives aside), so for scenes whose tree lives in HBM / Infinity Cache the
@@ -1755,6 +1845,7 @@ __global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a
 // One launch before a shade step, after that step's texture pass (EmissionArgs): walks the hits texture_kernel walks -- the walk is
 // restated here, that kernel stays as it is -- and for every hit on an emitter adds thr * e to the pixel's `emitted` and leaves the
 // throughput +0: the path is dead, shade scatters it all the same. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
+// (emission_nee_kernel below is this kernel's twin with one condition added: a change here belongs there too.)
 __global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
     const uint32_t smp = blockIdx.y;
     const Control *ctl = a.ctl + smp;
@@ -1786,6 +1877,47 @@ __global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs
             float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
             const float4 thr = *px, had = *out;
             *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
+            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+        }
+    }
+}
+
+// The emission pass of a context that connects (WFPT_FLAG_NEE with an emitter; include/wfpt.h "Next-event estimation"): emission_kernel
+// restated with one difference: thr * e is added only where the pixel's connected flag (emitted.w, set by the previous step's connect
+// pass) is 0. After a diffuse bounce the connect pass has already counted this light. A copy and not a `template <bool NEE>` body shared
+// by the two: instantiated from such a body, emission_kernel's own instructions change (the scalar address arithmetic at its head is
+// scheduled differently; tools/isa_compare.py), and contexts without the flag must run the kernel they ran before.
+__global__ __launch_bounds__(kConsumerThreads) void emission_nee_kernel(EmissionArgs a) {
+    const uint32_t smp = blockIdx.y;
+    const Control *ctl = a.ctl + smp;
+    const bool records = a.rec_in != nullptr;
+    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
+    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
+    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
+    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
+    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.in_hits[co + chunk];
+        const uint32_t base = a.in_hit_base[co + chunk];
+        if (base >= n) break; // bases ascend with the segment index
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n) break;
+            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
+            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
+            const uint32_t m_idx = a.prim_em[prim];
+            if (m_idx == kNoEmission) continue;
+            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
+                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
+                if (m > 2u) m = 0u;
+                if (m != a.material) continue;
+            }
+            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
+            const float4 e = a.em[m_idx];
+            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
+            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
+            const float4 thr = *px, had = *out;
+            if (had.w == 0.0f) *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
             *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
         }
     }
@@ -3022,6 +3154,188 @@ __global__ __launch_bounds__(kExtendThreads) void aov_tex_kernel(AovArgs a, EnvD
     aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, true>(a, env, ts);
 }
 
+// ================================================================================================
+// connect pass (WFPT_FLAG_NEE; include/wfpt.h "Next-event estimation")
+// ================================================================================================
+// One light sample for the receiver at p with normal n (steps 3 and 4 of the header's section, in its operation order: IEEE f32
+// add / sub / mul / div / sqrt, sincos_, no fma; tests/nee_ref.py restates it). False: no contribution (the comparisons are written so that
+// a NaN fails them). q, the light's primitive and the shadow ray's direction w and length dist are set either way.
+struct LightSample {
+    float3_ q, w, e; // e: the light's emission colour at q (times its texture)
+    float dist, G;
+    uint32_t prim;
+};
+template <int PRIM, bool TEX>
+__device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, float3_ n, float u0, float u1, float u2, LightSample &s) {
+    const float nl_f = static_cast<float>(a.n_lights);
+    // (max_ first: a NaN or negative u0 of a caller's row picks light 0, and no float outside the u32 range is converted)
+    const uint32_t i = umin(static_cast<uint32_t>(min_(max_(__builtin_floorf(u0 * nl_f), 0.0f), nl_f)), a.n_lights - 1u);
+    const uint32_t prim = a.lights[i];
+    s.prim = prim;
+    float3_ nl;
+    float area;
+    if (PRIM == 0) {
+        const float4 g = a.scene.prim_geom[prim]; // (centre, radius)
+        const float ra = __builtin_fabsf(g.w);
+        const float z = 1.0f - 2.0f * u1;
+        const float r = sqrt_(max_(0.0f, 1.0f - z * z));
+        float sn, cs;
+        sincos_((2.0f * kPi) * u2, sn, cs);
+        s.q = {g.x + ra * (r * cs), g.y + ra * (r * sn), g.z + ra * z};
+        nl = {(s.q.x - g.x) / ra, (s.q.y - g.y) / ra, (s.q.z - g.z) / ra};
+        area = (4.0f * kPi) * (ra * ra);
+    } else {
+        const float4 g0 = a.scene.prim_geom[3u * prim], g1 = a.scene.prim_geom[3u * prim + 1u], g2 = a.scene.prim_geom[3u * prim + 2u];
+        const float su = sqrt_(u1);
+        const float b1 = 1.0f - su, b2 = u2 * su;
+        s.q = {(g0.x + b1 * g1.x) + b2 * g2.x, (g0.y + b1 * g1.y) + b2 * g2.y, (g0.z + b1 * g1.z) + b2 * g2.z};
+        const float4 rec0 = a.scene.shade_rec[3u * prim]; // the stored normalize(cross(e1, e2))
+        nl = {rec0.x, rec0.y, rec0.z};
+        const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
+        area = 0.5f * sqrt_(dot3(cr, cr));
+    }
+    const float3_ v = {s.q.x - p.x, s.q.y - p.y, s.q.z - p.z};
+    const float dist2 = dot3(v, v);
+    s.dist = sqrt_(dist2);
+    s.w = {v.x / s.dist, v.y / s.dist, v.z / s.dist};
+    const float cos_s = dot3(n, s.w), cos_l = __builtin_fabsf(dot3(nl, s.w));
+    s.G = (((cos_s * cos_l) * area) * nl_f) / (kPi * dist2);
+    const float4 e = a.em[a.prim_em[prim]];
+    s.e = {e.x, e.y, e.z};
+    float3_ tc;
+    if (TEX && texture_factor(a.ts, a.scene.prim_geom, a.scene.shade_rec, PRIM, prim, s.q, tc)) s.e = {e.x * tc.x, e.y * tc.y, e.z * tc.z};
+    return area > 0.0f && dist2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;
+}
+
+// Persistent workgroups of kExtendThreads threads over the (sample, segment) items of the hits a shade step will shade, one hit per thread:
+// the scene is staged once per workgroup, at its first item that holds a hit (a workgroup without one stages nothing). Each pixel has at
+// most one hit per wavefront: no two lanes touch one pixel. The closest hit decides the occlusion (WFPT_TRACE_ANY, then t against
+// dist * 0.999): by construction the oracle's answer for every scene kind and flag; scenes in LDS ask occluded_conservative first.
+// (No min-waves launch bound, as aov_body.)
+#ifndef WFPT_NEE_EARLY_OUT
+#define WFPT_NEE_EARLY_OUT 1 // 0: every shadow ray takes the closest-hit walk (the first version; tools/bench_nee.py's shirley:nee@closest leg builds it)
+#endif
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX>
+__global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
+    extern __shared__ float4 lds[];
+    WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
+    const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
+    const bool sampler = a.sample_in != nullptr, records = a.rec_in != nullptr;
+    const uint32_t per_smp = sampler ? (a.sample_n + kChunk - 1u) / kChunk : a.n_chunks_max;
+    const uint32_t n_items = sampler ? per_smp : per_smp * a.batch.n;
+    const uint32_t frame0 = sampler ? 0u : uniform(a.ctl->frame.frame); // the batch's first frame, as shade_kernel and aov_body take it
+    bool staged = false;
+    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const uint32_t smp = sampler ? 0u : item / per_smp, chunk = item - smp * per_smp;
+        uint32_t count;
+        if (sampler) {
+            count = umin(static_cast<uint32_t>(kChunk), a.sample_n - chunk * kChunk);
+        } else { // the segment's hits among those the step shades, as emission_kernel finds them (all block-uniform)
+            const Control *ctl = a.ctl + smp;
+            const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
+            if (chunk >= (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk) continue;
+            const size_t co = smp * static_cast<size_t>(a.batch.chunk_stride);
+            const uint32_t base = a.in_hit_base[co + chunk];
+            if (base >= n) continue;
+            count = umin(umin(a.in_hits[co + chunk], static_cast<uint32_t>(kChunk)), n - base);
+        }
+        count = uniform(count);
+        if (count == 0u) continue;
+        if (LDS_SCENE && !staged) {
+            WFPT_STAGE_SCENE(g_nodes);
+            __syncthreads();
+            staged = true;
+        }
+        bool live = threadIdx.x < count;
+        float3_ p = {0.0f, 0.0f, 0.0f}, n = p;
+        float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f;
+        float4 *px = nullptr, *out = nullptr;
+        float4 rec1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (live && sampler) {
+            const float *row = a.sample_in + 9u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
+            p = {row[0], row[1], row[2]};
+            n = {row[3], row[4], row[5]};
+            u0 = row[6]; u1 = row[7]; u2 = row[8];
+        } else if (live) {
+            const size_t slot = smp * static_cast<size_t>(a.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk + threadIdx.x;
+            uint32_t prim, pixel_idx;
+            if (records) {
+                const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
+                p = {ra.x, ra.y, ra.z};
+                pixel_idx = __float_as_uint(ra.w);
+                prim = __float_as_uint(rb.w);
+            } else {
+                const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
+                const float t = a.hq.t()[slot];
+                const uint32_t ridx = a.hq.ridx()[slot];
+                prim = a.hq.prim()[slot];
+                p = {q.ox()[ridx] + t * q.dx()[ridx], q.oy()[ridx] + t * q.dy()[ridx], q.oz()[ridx] + t * q.dz()[ridx]}; // sh:91
+                pixel_idx = q.pixel()[ridx];
+            }
+            const float4 rec0 = a.scene.shade_rec[3u * prim];
+            rec1 = a.scene.shade_rec[3u * prim + 1u];
+            uint32_t m = __float_as_uint(a.scene.shade_rec[3u * prim + 2u].x); // `case 0u, default` folds > 2 into 0
+            if (m > 2u) m = 0u;
+            if (a.material != 0xffffffffu && m != a.material) {
+                live = false; // one per-material shade stage: its class only
+            } else {
+                const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
+                out = pixel_of(a.emitted + smp * static_cast<size_t>(a.batch.image_stride), lp);
+                if (m != 0u || a.prim_em[prim] != kNoEmission) { // metal, dielectric, emitter: the flag is cleared, nothing else
+                    out->w = 0.0f;
+                    live = false;
+                } else {
+                    px = pixel_of(a.image + smp * static_cast<size_t>(a.batch.image_stride), lp);
+                    // the normal scatter() uses, never flipped
+                    n = PRIM == 0 ? normalize3({p.x - rec0.x, p.y - rec0.y, p.z - rec0.z}) : float3_{rec0.x, rec0.y, rec0.z};
+                    uint32_t rng = jenkins_hash(pixel_idx ^ jenkins_hash(frame0 + smp)); // init_rng((x, y), (W, H), frame): x + y W is the pixel
+                    rng = jenkins_hash(rng ^ (0x9E3779B9u * (a.wavefront + 1u)));
+                    u0 = rng_next_float(rng);
+                    u1 = rng_next_float(rng);
+                    u2 = rng_next_float(rng);
+                }
+            }
+        }
+        LightSample s;
+        bool lit = false, occluded = false;
+        if (live) lit = sample_light<PRIM, TEX>(a, p, n, u0, u1, u2, s);
+        if (lit) {
+#if WFPT_STAMPS
+            uint32_t dbg[3] = {0, 0, 0};
+#endif
+            const float window = s.dist * 0.999f;
+            uint32_t verdict = kOccUndecided;
+            // scenes in LDS, conservative boxes: the early-out walk answers most rays (3.4 % of a Shirley frame, same booleans)
+            if (WFPT_NEE_EARLY_OUT && LDS_SCENE && !EXACT && !far_origin(a.scene, p.x, p.y, p.z))
+                verdict = occluded_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z,
+                                                                      a.scene.n_nodes, window WFPT_DBG_ARG);
+            if (verdict == kOccUndecided) { // every other scene kind, and the rays that walk hands back: the closest hit decides
+                float t = 0.0f;
+                uint32_t prim = 0;
+                bool hit = false;
+                WFPT_TRACE_ANY(g_nodes, s_stack, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z);
+                occluded = hit && t < window;
+            } else {
+                occluded = verdict == kOccHit;
+            }
+        }
+        if (live && sampler) {
+            float *row = a.sample_out + 8u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
+            row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
+            row[3] = static_cast<float>(s.prim);
+            row[4] = lit ? s.e.x * s.G : 0.0f; row[5] = lit ? s.e.y * s.G : 0.0f; row[6] = lit ? s.e.z * s.G : 0.0f;
+            row[7] = occluded ? 1.0f : 0.0f;
+        } else if (live) {
+            const float4 thr = *px, had = *out;
+            if (lit && !occluded)
+                *out = make_float4(had.x + ((thr.x * rec1.x) * s.e.x) * s.G, had.y + ((thr.y * rec1.y) * s.e.y) * s.G,
+                                   had.z + ((thr.z * rec1.z) * s.e.z) * s.G, 1.0f);
+            else
+                out->w = 1.0f;
+        }
+    }
+}
+
 // sums -> resolved AOV words (aov_resolve_word, shared with the host read-back)
 __global__ __launch_bounds__(256) void aov_resolve_kernel(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out,
                                                           size_t n_words) {
@@ -3672,9 +3986,12 @@ hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s) {
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(emission_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    if (nee)
+        hipLaunchKernelGGL(emission_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    else
+        hipLaunchKernelGGL(emission_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -3753,6 +4070,30 @@ hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvD
         hipLaunchKernelGGL(aov_variant<true>(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a, *env);
     else
         hipLaunchKernelGGL(aov_variant(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+    return hipGetLastError();
+}
+
+namespace {
+using ConnectFn = void (*)(ConnectArgs);
+template <bool TEX> struct ConnectK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX>; }
+};
+ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex) {
+    return tex ? pick_variant<ConnectK<true>>(sc, exact, sc.lds_scene != 0) : pick_variant<ConnectK<false>>(sc, exact, sc.lds_scene != 0);
+}
+} // namespace
+
+hipError_t connect_prepare(const SceneDev &scene) {
+    for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
+        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured) {
+    if (grid == 0 || a.n_lights == 0) return hipSuccess;
+    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }
 

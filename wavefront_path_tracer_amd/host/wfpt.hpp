@@ -363,6 +363,24 @@ class PathTracer {
         check(wfpt_emission_timing_ms(ctx_, &ms, &n));
         return {ms, n};
     }
+    // Next-event estimation (WFPT_FLAG_EMISSION | WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): shadow rays from diffuse hits to the emitters.
+    uint32_t nee_light_count() {
+        const int n = wfpt_nee_light_count(ctx_);
+        if (n < 0) check(n);
+        return static_cast<uint32_t>(n);
+    }
+    std::pair<float, uint32_t> nee_timing() {
+        float ms = 0.0f;
+        uint32_t n = 0;
+        check(wfpt_nee_timing_ms(ctx_, &ms, &n));
+        return {ms, n};
+    }
+    // rows of (p.xyz, n.xyz, u0, u1, u2) -> rows of (q.xyz, light primitive, e_q G rgb, occluded)
+    std::vector<float> sample_lights(const std::vector<float> &in9) {
+        std::vector<float> out(in9.size() / 9 * 8);
+        check(wfpt_sample_lights(ctx_, in9.data(), in9.size() / 9, out.data()));
+        return out;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
