@@ -233,7 +233,11 @@ enum {
                                         flag, and launches the same kernels. */,
     WFPT_FLAG_NEE = 1u << 15         /* next-event estimation, see "Next-event estimation" below: every diffuse hit sends one shadow ray to a
                                         sampled point of an emitter. Needs WFPT_FLAG_EMISSION. With no emitter set the context renders bit
-                                        for bit as without the flag, and launches the same kernels. */
+                                        for bit as without the flag, and launches the same kernels. */,
+    WFPT_FLAG_ENV_NEE = 1u << 16     /* the environment map as one more light of the connect pass, sampled in proportion to its radiance, see
+                                        "Environment next-event estimation" below. Needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and
+                                        WFPT_FLAG_NEE. With no map set (or a black one) the context renders bit for bit as without the
+                                        flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -600,8 +604,8 @@ int wfpt_temporal_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *calls);
  * history is dropped, and so are the captured graphs. wfpt_update_scene* and viewport changes keep the map. A refused call leaves the
  * context as it was, its map included. WFPT_ERR_INVALID_ARGUMENT without the flag and for a bad size, texel or parameter; WFPT_ERR_UNSUPPORTED
  * while wfpt_loop_kind_of reports WFPT_LOOP_FUSED_BINNED (the opt-in class-binned loop measures level with the default one and is not
- * extended: WFPT_FLAG_BINNING contexts keep the gradient sky). Out of scope: wfpt_render_chunked* (the flag is masked off there), importance
- * sampling of the map and next-event estimation (this chain traces no shadow rays). */
+ * extended: WFPT_FLAG_BINNING contexts keep the gradient sky). Out of scope: wfpt_render_chunked* (the flag is masked off there). Importance
+ * sampling of the map by shadow rays: WFPT_FLAG_ENV_NEE ("Environment next-event estimation" below). */
 typedef struct wfpt_environment_params {
     float intensity;        /* >= 0, finite: multiplies every texel */
     float rotation;         /* in [0, 1): turns added to u (the map turns about +y) */
@@ -746,8 +750,8 @@ int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
  * context with the flag and an emitter never runs the class-binned loop (set and clear on such a context are refused, see "Emission");
  * wfpt_render_chunked* masks the flag off. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag.
- * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, importance sampling of
- * the environment map, retiring dead or fully shadowed paths, contact shadows thinner than the 0.001 / 0.1 % windows. */
+ * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, retiring dead or fully
+ * shadowed paths, contact shadows thinner than the 0.001 / 0.1 % windows. (Importance sampling of the environment map: WFPT_FLAG_ENV_NEE.) */
 /* the number of emitting primitives (the light list's length), 0 with none; negative: a wfpt_status */
 int wfpt_nee_light_count(wfpt_ctx *ctx);
 /* the connect launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
@@ -756,6 +760,65 @@ int wfpt_nee_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * light's primitive index as a float, the unoccluded factor e_q * G per channel -- 0 where the sample contributes nothing --, 1.0 if the
  * sample is occluded and 0.0 otherwise). WFPT_ERR_INVALID_ARGUMENT while no primitive emits. */
 int wfpt_sample_lights(wfpt_ctx *ctx, const float *in9, size_t n, float *out8);
+
+/* ------------------------------------------------------------------ Environment next-event estimation (WFPT_FLAG_ENV_NEE)
+ * wfpt_create* accepts WFPT_FLAG_ENV_NEE only together with WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and WFPT_FLAG_NEE
+ * (WFPT_ERR_INVALID_ARGUMENT otherwise). On such a context the map is one of the lights the connect pass can pick, sampled in proportion
+ * to its radiance; its sample lands in the `emitted` plane, under the same connected flag (emitted.w).
+ *
+ * The sampling distribution is built by wfpt_set_environment and dropped by wfpt_clear_environment; wfpt_update_scene* and viewport
+ * changes keep it. It is made of integers, so every build order gives the same tables. For a map of w x h texels (r, g, b):
+ *   L(x, y)  = (0.2126 r + 0.7152 g) + 0.0722 b of the stored texel (f32, the luminance moments' order; `intensity` is not applied)
+ *   Lm(x, y) = the maximum of L over columns x - 1, x, x + 1 (modulo w) and rows y - 1, y, y + 1 (clamped to [0, h - 1]): the texels the
+ *              bilinear taps of a lookup inside texel (x, y) can reach, so a direction with radiance never has probability zero
+ *   s_y      = the sine the library's sincos gives for pi * ((f32(y) + 0.5) / f32(h))
+ *   f = Lm * s_y;  M = the maximum of f over the map
+ *   k(x, y)  = u32(ceil((f / M) * 65535.0)), in [0, 65535], and 1 where f > 0 and the quotient underflows to 0
+ *   row[y][x] = the inclusive prefix sum of k along row y (u32);  marg[y] = the inclusive prefix sum of the row totals (u64)
+ *   total = marg[h - 1]
+ * If M is not a finite number above 0 (a black map) there is no distribution, and for this flag the context behaves as with no map.
+ *
+ * With a distribution the context connects even with no emitter: the `emitted` plane and the connect launches exist from
+ * wfpt_set_environment on. Steps 1 and 2 of "Next-event estimation" are unchanged (u0 u1 u2 as there). Then, with p the effective share
+ * -- 1 when the light list is empty, the context's environment share (wfpt_set_environment_share, default 0.5) otherwise:
+ *   p = 1:            the environment branch, without a comparison (a draw of exactly 1.0 never reaches an empty light list)
+ *   p < 1, u0 >= p:   the emitter branch: q = 1 - p;  steps 3-5 with u0' = (u0 - p) / q in place of u0, and the value step 5 adds is
+ *                     divided by q as its last operation: emitted += (((thr * albedo) * e_q) * G) / q
+ *   p < 1, u0 < p:    the environment branch
+ * The environment branch draws two more floats u3 u4 from the same stream (only this branch draws them). All operations are IEEE f32 in
+ * the order written, no fma, f64 only where said; pi = 3.1415927f, 2 pi its exact double, 2 pi^2 = 19.739209f:
+ *   row:      T = u64(floor(f64(u1) * f64(total))), at most total - 1;  y = the first row with marg[y] > T
+ *   column:   R = row[y][w - 1];  C = u32(floor(f64(u2) * f64(R))), at most R - 1;  x = the first column with row[y][x] > C
+ *             (a NaN or negative product of a caller's row selects 0);  k = row[y][x] - row[y][x - 1] (row[y][-1] = 0), > 0 by construction
+ *   direction: u = (f32(x) + u3) / f32(w);  v = (f32(y) + u4) / f32(h);  theta = pi * v;  phi = (2 pi) * ((u - 0.5) - rotation);
+ *             (st, ct) = sincos(theta);  (sp, cp) = sincos(phi);  wdir = (st * sp, ct, -(st * cp))
+ *             -- the inverse of the lookup's phi = atan2(n.x, -n.z), theta = atan2(hypot(n.x, n.z), n.y), u = phi / 2 pi + 0.5 + rotation
+ *   probability: P = f32(k) / f32(total) (u64 -> f32 rounds to nearest even);  pdf = ((P * f32(w)) * f32(h)) / ((2 pi^2) * st)
+ *             cos_s = (n.x wdir.x + n.y wdir.y) + n.z wdir.z;  e = the map's lookup in direction wdir, with intensity and rotation
+ * The sample contributes only if st > 0, cos_s > 0 and pdf > 0 (a NaN fails each test). Then the ray (p_hit, wdir) is traced with the
+ * context's own traversal (t_min = 0.001); it is occluded iff the walk reports any hit. An unoccluded sample adds, per channel,
+ *   emitted[pixel] += ((thr * albedo) * e) * Genv,   Genv = (cos_s / pi) / (pdf * p)
+ * Either branch sets the pixel's connected flag to 1, as a diffuse hit does without this flag; metal, dielectric and emitter hits clear
+ * it. The miss pass leaves thr = +0 where the pixel's connected flag is 1 -- the connect pass of the bounce before has already counted
+ * the map -- and multiplies by the map where it is 0: primary misses and misses after a metal or dielectric bounce. The emission pass
+ * gates emitter hits by the same flag, as before. AOVs, shade, the tracing kernels, the loop exit, accumulation and the moments are
+ * untouched. Such a context never runs the class-binned loop while a map is set; wfpt_render_chunked* masks the flag off.
+ * With no map set, or a black one, a flagged context launches exactly the kernels a context with the three other flags launches and
+ * renders the same bits, with and without emitters. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag; the
+ * connect launches stay under wfpt_nee_timing_ms.
+ * Not done: multiple importance sampling between the map and the scatter, a distribution that accounts for the receiver's normal or for
+ * visibility, a coarser importance grid or an alias table for very large maps, the class-binned loop and wfpt_render_chunked*, object
+ * lights selected by power, retiring dead paths. */
+/* the environment share: finite, in (0, 1]. Acts like wfpt_set_emission: the accumulation restarts, the graphs and the history are dropped */
+int wfpt_set_environment_share(wfpt_ctx *ctx, float share);
+float wfpt_environment_share(const wfpt_ctx *ctx); /* 0 on a context without the flag */
+/* the tables of the map's distribution: row_wh w * h words (row-major), marg_h h words; either may be NULL. WFPT_ERR_INVALID_ARGUMENT
+ * while no map with a distribution is set */
+int wfpt_read_environment_distribution(wfpt_ctx *ctx, uint32_t *row_wh, uint64_t *marg_h);
+/* The environment branch with p = 1 for n caller-supplied receivers on the device. in10: n rows of (p.xyz, n.xyz, u1, u2, u3, u4); out8: n
+ * rows of (wdir.xyz, f32(y * w + x), e * Genv per channel -- 0 where the sample contributes nothing --, 1.0 if the sample is occluded and
+ * 0.0 otherwise). WFPT_ERR_INVALID_ARGUMENT while no map with a distribution is set */
+int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, float *out8);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

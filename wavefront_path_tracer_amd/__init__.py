@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -40,6 +40,9 @@ MAX_TEXTURES = 64  # WFPT_MAX_TEXTURES
 TEXTURE_FILTERS = {"bilinear": 0, "nearest": 1}
 FLAG_EMISSION = 1 << 14  # emissive materials (include/wfpt.h "Emission")
 FLAG_NEE = 1 << 15  # shadow rays from diffuse hits to the emitters (include/wfpt.h "Next-event estimation"); needs FLAG_EMISSION
+# the environment map as one more light of the connect pass (include/wfpt.h "Environment next-event estimation"); needs FLAG_ENVIRONMENT,
+# FLAG_EMISSION and FLAG_NEE
+FLAG_ENV_NEE = 1 << 16
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -347,6 +350,10 @@ def lib():
         "wfpt_nee_light_count": (i32, [vp]),
         "wfpt_nee_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
         "wfpt_sample_lights": (i32, [vp, vp, sz, vp]),
+        "wfpt_set_environment_share": (i32, [vp, f32]),
+        "wfpt_environment_share": (f32, [vp]),
+        "wfpt_read_environment_distribution": (i32, [vp, vp, vp]),
+        "wfpt_sample_environment_light": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -1294,10 +1301,12 @@ class PathTracer:
             raise ValueError(f"set_environment: expected an (h, w, 3) array, got shape {a.shape}")
         p = _EnvironmentParams(float(intensity), float(rotation))
         self._check(lib().wfpt_set_environment(self.handle, _p(a), a.shape[1], a.shape[0], C.byref(p)))
+        self._env_shape = (a.shape[0], a.shape[1])
 
     def clear_environment(self):
         """Back to the gradient sky (restarts the accumulation)."""
         self._check(lib().wfpt_clear_environment(self.handle))
+        self._env_shape = None
 
     def sample_environment(self, dirs):
         """(n, 3) float32: the map's value (with its intensity) in each of the (n, 3) directions, looked up on the device."""
@@ -1393,6 +1402,34 @@ class PathTracer:
             raise ValueError(f"sample_lights: expected rows of 9 floats, got shape {a.shape}")
         out = np.zeros((a.shape[0], 8), "<f4")
         self._check(lib().wfpt_sample_lights(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
+
+    # ---- environment next-event estimation (contexts created with FLAG_ENVIRONMENT | FLAG_EMISSION | FLAG_NEE | FLAG_ENV_NEE)
+    def set_environment_share(self, share):
+        """The probability, in (0, 1], with which a diffuse hit connects to the map rather than to an emitter (0.5 by default; with no
+        emitter every hit connects to the map). Restarts the accumulation."""
+        self._check(lib().wfpt_set_environment_share(self.handle, float(share)))
+
+    def environment_share(self):
+        return float(lib().wfpt_environment_share(self.handle))
+
+    def environment_distribution(self):
+        """(row, marg) of the map's sampling distribution: row (h, w) uint32, the prefix sums of the integer texel weights along each row,
+        and marg (h,) uint64, the prefix sums of the row totals. Raises while no map with a distribution is set."""
+        h, w = getattr(self, "_env_shape", None) or (1, 1)
+        row, marg = np.zeros((h, w), "<u4"), np.zeros(h, "<u8")
+        self._check(lib().wfpt_read_environment_distribution(self.handle, _p(row), _p(marg)))
+        return row, marg
+
+    def sample_environment_light(self, rows):
+        """The connect pass's sample of the map (its environment branch with p = 1) for caller-supplied receivers, computed on the device.
+        rows: (n, 10) float32 of (p.xyz, n.xyz, u1, u2, u3, u4); returns (n, 8) float32 of (wdir.xyz, the texel index y * w + x, the
+        unoccluded factor e * Genv per channel, occluded 0/1)."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != 10:
+            raise ValueError(f"sample_environment_light: expected rows of 10 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 8), "<f4")
+        self._check(lib().wfpt_sample_environment_light(self.handle, _p(a), a.shape[0], _p(out)))
         return out
 
     # ---- read-back

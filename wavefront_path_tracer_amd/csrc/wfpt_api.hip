@@ -253,6 +253,12 @@ struct wfpt_ctx {
     uint32_t stage_extends = 0;
     double nee_ms = 0.0;        // connect launches of the timed renders since wfpt_create (wfpt_nee_timing_ms)
     uint32_t nee_launches = 0;
+    // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
+    // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
+    DeviceBuffer<uint32_t> env_row;
+    DeviceBuffer<uint64_t> env_marg;
+    uint64_t env_total = 0;
+    float env_share = 0.5f;
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -622,7 +628,11 @@ constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
 
 // a WFPT_FLAG_NEE context holds an emitter: the connect passes run before the shade steps (after their emission passes, which then add a
 // hit light only where the pixel's connected flag is 0)
-bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr; }
+// (or, WFPT_FLAG_ENV_NEE, a map with a sampling distribution: env_connecting)
+bool env_connecting(const wfpt_ctx *c) { return c->env_row.get() != nullptr; }
+bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || env_connecting(c); }
+// the second plane is in use: accumulate adds it, the head of every batch zeroes it
+bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c); }
 // the connect pass before a shade step of wavefront `wavefront`: the hits emission_args names, in its two forms
 ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
                          uint32_t material = 0xffffffffu) {
@@ -651,12 +661,16 @@ ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t n
     a.n_lights = c->n_lights;
     a.ts = tex_scene(c);
     a.scene = c->scene;
+    if (env_connecting(c)) // the effective share: 1 while there is no light to pick instead
+        a.envd = EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f};
     return a;
 }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
-    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c));
+    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c));
 }
+// the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
+const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
 // The connect launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::nee_ms
 constexpr int kStageConnect = WFPT_STAGE_COUNT + 3;
 
@@ -743,7 +757,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      return launch_shade(sa, consumer_grid(c, nb), st);
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] {
-                     return launch_miss(miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb), st, env);
+                     return launch_miss(miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb), st, env, miss_gate(c));
                  }));
     }
     return WFPT_OK;
@@ -762,7 +776,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const int par = static_cast<int>(b & 1u);
         const bool last = b + 1 >= c->p.max_wavefronts;
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
-        if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+        if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
         if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
             WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
         if (emitting(c)) // after the texture pass: a textured emitter's light is (thr * tex) * e
@@ -812,7 +826,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(WFPT_STAGE_COMPACT, [&] { return launch_compact(compact_args(c, par, nb), c->n_chunks_max, st, env != nullptr); }));
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (b + 1 < c->p.max_wavefronts) {
-            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
@@ -823,7 +837,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
         } else {
             if (env) // the last launch's miss items, as a launch of their own with the map
-                WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env); }));
+                WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
@@ -861,7 +875,7 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
 // The batch's accumulate launch: with the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way)
 hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
     const AccumulateArgs a = accumulate_args(c, c->n_pixels, true, nb);
-    if (emitting(c)) // each sample's value is image + emitted (the same kernels with the second plane)
+    if (second_plane(c)) // each sample's value is image + emitted (the same kernels with the second plane)
         return launch_accumulate_emission(a, c->emitted.get(), c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
     if (c->moments.get()) return launch_accumulate_moments(a, c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
     return launch_accumulate(a, c->accumulate_grid, c->stream.get());
@@ -886,7 +900,7 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
                      const TexScene ts = tex_scene(c);
                      return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c), textured(c) ? &ts : nullptr);
                  }));
-    if (emitting(c)) // the loops' first kernel sets every slice of `image` to 1: `emitted` starts at 0 with it
+    if (second_plane(c)) // the loops' first kernel sets every slice of `image` to 1: `emitted` starts at 0 with it
         WFPT_HIP(c, timed(kStageEmission, [&] {
                      return hipMemsetAsync(c->emitted.get(), 0, sizeof(float) * nb * c->image_floats, c->stream.get());
                  }));
@@ -1406,6 +1420,14 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
         return nullptr;
     }
+    if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
+        constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
+        if ((params->flags & need) != need) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_NEE needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+                                                     "(the map is one more light of the connect pass, its sample lands in the emission plane)");
+            return nullptr;
+        }
+    }
     if (params->max_wavefronts == 0 || params->max_wavefronts > static_cast<uint32_t>(kMaxRows)) {
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: max_wavefronts must be in 1..64");
         return nullptr;
@@ -1615,7 +1637,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1893,10 +1915,10 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
                                  consumer_grid(c, 1), c->stream.get()));
         break;
     case WFPT_STAGE_MISS:
-        WFPT_HIP(c, launch_miss(miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1), c->stream.get(), env_of(c)));
+        WFPT_HIP(c, launch_miss(miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1), c->stream.get(), env_of(c), miss_gate(c)));
         break;
     case WFPT_STAGE_ACCUMULATE:
-        if (emitting(c))
+        if (second_plane(c))
             WFPT_HIP(c, launch_accumulate_emission(accumulate_args(c, threads, false), c->emitted.get(), nullptr, 0, c->accumulate_grid, c->stream.get()));
         else
             WFPT_HIP(c, launch_accumulate(accumulate_args(c, threads, false), c->accumulate_grid, c->stream.get()));
@@ -2779,10 +2801,50 @@ static int environment_check(wfpt_ctx *c, const char *who) {
     return WFPT_OK;
 }
 
+// The sampling distribution of a candidate map (WFPT_FLAG_ENV_NEE contexts; include/wfpt.h "Environment next-event estimation"), built on
+// the device without touching the context. A black map has none (its buffers stay null). `plane`: the second plane, allocated here if the
+// context has none yet and the map gets a distribution.
+struct EnvTables {
+    DeviceBuffer<uint32_t> row;
+    DeviceBuffer<uint64_t> marg;
+    uint64_t total = 0;
+    DeviceBuffer<float> plane;
+};
+static int build_env_tables(wfpt_ctx *c, const EnvDev &env, EnvTables &out) {
+    if (!(c->p.flags & WFPT_FLAG_ENV_NEE)) return WFPT_OK;
+    const size_t n = static_cast<size_t>(env.w) * env.h;
+    const hipStream_t st = c->stream.get();
+    DeviceBuffer<float> f;
+    DeviceBuffer<uint32_t> max_bits;
+    WFPT_HIP(c, f.alloc(n));
+    WFPT_HIP(c, max_bits.alloc(1));
+    WFPT_HIP(c, hipMemsetAsync(max_bits.get(), 0, sizeof(uint32_t), st));
+    WFPT_HIP(c, launch_env_weights(env, f.get(), max_bits.get(), st));
+    float M = 0.0f;
+    WFPT_HIP(c, hipMemcpyAsync(&M, max_bits.get(), sizeof(float), hipMemcpyDeviceToHost, st));
+    WFPT_HIP(c, hipStreamSynchronize(st));
+    if (!(M > 0.0f && M <= FLT_MAX)) return WFPT_OK; // a black map (or one whose luminance overflows): no distribution
+    WFPT_HIP(c, out.row.alloc(n));
+    WFPT_HIP(c, out.marg.alloc(env.h));
+    WFPT_HIP(c, launch_env_tables(env, f.get(), M, out.row.get(), out.marg.get(), st));
+    WFPT_HIP(c, hipMemcpyAsync(&out.total, out.marg.get() + (env.h - 1u), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    WFPT_HIP(c, hipStreamSynchronize(st));
+    if (out.total == 0) return fail(c, WFPT_ERR_HIP, "wfpt_set_environment: the sampling distribution of a lit map is empty");
+    if (!c->emitted.get()) {
+        WFPT_HIP(c, out.plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
+        WFPT_HIP(c, hipMemset(out.plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
+    }
+    return WFPT_OK;
+}
+
 // a new map (or none) is a new scene for the accumulation, the temporal history and the captured graphs (whose kernel arguments hold the map)
-static int environment_changed(wfpt_ctx *c, DeviceBuffer<float4> tex, uint32_t w, uint32_t h, float intensity, float rotation) {
+static int environment_changed(wfpt_ctx *c, DeviceBuffer<float4> tex, uint32_t w, uint32_t h, float intensity, float rotation, EnvTables &&t = EnvTables()) {
     c->env_tex = std::move(tex); // frees the old map: the stream is idle, the caller synchronised it
     c->env = EnvDev{c->env_tex.get(), w, h, intensity, rotation};
+    c->env_row = std::move(t.row); // and the old map's distribution
+    c->env_marg = std::move(t.marg);
+    c->env_total = t.total;
+    if (t.plane.get()) c->emitted = std::move(t.plane);
     return scene_changed(c);
 }
 
@@ -2818,7 +2880,9 @@ int wfpt_set_environment(wfpt_ctx *c, const float *rgb, uint32_t w, uint32_t h, 
             return hip_fail(c, e, "wfpt_set_environment: upload");
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old map
-    return environment_changed(c, std::move(tex), w, h, p->intensity, p->rotation);
+    EnvTables tables;
+    if (int r = build_env_tables(c, EnvDev{tex.get(), w, h, p->intensity, p->rotation}, tables); r != WFPT_OK) return r;
+    return environment_changed(c, std::move(tex), w, h, p->intensity, p->rotation, std::move(tables));
 }
 
 int wfpt_clear_environment(wfpt_ctx *c) {
@@ -3141,7 +3205,7 @@ int wfpt_nee_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
 
 int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (int r = nee_check(c, "wfpt_sample_lights"); r != WFPT_OK) return r;
-    if (!connecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
+    if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
     if ((!in9 || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: null argument");
     if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: too many rows");
     if (n == 0) return WFPT_OK;
@@ -3162,6 +3226,65 @@ int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
     if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights");
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- environment next-event estimation (include/wfpt.h)
+static int env_nee_check(const wfpt_ctx *c, const char *who) {
+    if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_ENV_NEE))
+        return fail(const_cast<wfpt_ctx *>(c), WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_ENV_NEE");
+    return WFPT_OK;
+}
+
+int wfpt_set_environment_share(wfpt_ctx *c, float share) {
+    if (int r = env_nee_check(c, "wfpt_set_environment_share"); r != WFPT_OK) return r;
+    if (!(share > 0.0f && share <= 1.0f)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_environment_share: the share must be in (0, 1]");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    c->env_share = share;
+    return scene_changed(c); // the captured graphs hold the share in their kernel arguments
+}
+
+float wfpt_environment_share(const wfpt_ctx *c) {
+    if (env_nee_check(c, "wfpt_environment_share") != WFPT_OK) return 0.0f;
+    return c->env_share;
+}
+
+int wfpt_read_environment_distribution(wfpt_ctx *c, uint32_t *row_wh, uint64_t *marg_h) {
+    if (int r = env_nee_check(c, "wfpt_read_environment_distribution"); r != WFPT_OK) return r;
+    if (!env_connecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_environment_distribution: no map with a distribution is set");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    if (row_wh) WFPT_HIP(c, hipMemcpy(row_wh, c->env_row.get(), sizeof(uint32_t) * c->env.w * c->env.h, hipMemcpyDeviceToHost));
+    if (marg_h) WFPT_HIP(c, hipMemcpy(marg_h, c->env_marg.get(), sizeof(uint64_t) * c->env.h, hipMemcpyDeviceToHost));
+    return WFPT_OK;
+}
+
+int wfpt_sample_environment_light(wfpt_ctx *c, const float *in10, size_t n, float *out8) {
+    if (int r = env_nee_check(c, "wfpt_sample_environment_light"); r != WFPT_OK) return r;
+    if (!env_connecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: no map with a distribution is set");
+    if ((!in10 || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(10 * n);
+    if (e == hipSuccess) e = d_out.alloc(8 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in10, sizeof(float) * 10 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) {
+        ConnectArgs a = connect_args(c, 0, -1, 1);
+        a.envd.share = 1.0f; // the environment branch alone
+        a.sample_in = d_in.get();
+        a.sample_out = d_out.get();
+        a.sample_n = static_cast<uint32_t>(n);
+        const uint64_t items = (n + kChunk - 1) / kChunk;
+        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
+                           textured(c), true);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment_light");
     return WFPT_OK;
 }
 

@@ -445,6 +445,17 @@ struct EmissionArgs {
     const float4 *em;
 };
 
+// The environment map as a light (WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment next-event estimation"): the map and its sampling
+// distribution. row[y * w + x]: the inclusive prefix sum of the integer texel weights k along row y; marg[y]: the inclusive prefix sum of
+// the row totals; total = marg[h - 1] > 0; share: the effective probability p with which a diffuse hit picks the map rather than an emitter (1 with no light).
+struct EnvDist {
+    EnvDev env;
+    const uint32_t *row;
+    const uint64_t *marg;
+    uint64_t total;
+    float share;
+};
+
 // The connect pass (connect_kernel; WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): before a shade step, after that step's texture
 // and emission passes, every hit the step will shade either sends one shadow ray to a sampled point of a light and adds the unoccluded
 // sample to the pixel's `emitted` (a diffuse hit: the pixel's connected flag, emitted.w, becomes 1) or only clears the flag (every other
@@ -453,6 +464,9 @@ struct EmissionArgs {
 // order. `wavefront`: the index b of the wavefront whose hits these are (the key of the pass's own random stream).
 // The sampler form (sample_in != null; wfpt_sample_lights): sample_n rows of (point, normal, u0 u1 u2) instead of hits, one row of
 // (q, light primitive, e_q G, occluded) each out; nothing else is read or written.
+// The ENVS variants (launch_connect's `envs`; WFPT_FLAG_ENV_NEE contexts whose map has a distribution): a diffuse hit picks the map with
+// probability envd.share (always, when n_lights is 0: prim_em may be null then) and an emitter otherwise; their sampler form
+// (wfpt_sample_environment_light) takes rows of (point, normal, u1 u2 u3 u4) and answers (wdir, texel, e Genv, occluded) for the map alone.
 struct ConnectArgs {
     Batch batch;
     const float4 *rec_in;
@@ -479,6 +493,7 @@ struct ConnectArgs {
     uint32_t sample_n;
     TexScene ts;              // the textures of the lights (the TEX variants only)
     SceneDev scene;
+    EnvDist envd;             // the map as a light (the ENVS variants only; below)
 };
 
 struct AccumulateArgs {
@@ -609,12 +624,20 @@ hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the fir
 hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
-hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr);
+// connected: the `emitted` plane of a context that connects to its map (WFPT_FLAG_ENV_NEE): miss_env_nee_kernel, which leaves thr = +0
+// where the pixel's connected flag (emitted.w) is 1
+hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const float *connected = nullptr);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
 // nee: the variant of contexts that connect (WFPT_FLAG_NEE with an emitter): adds thr * e only where the pixel's connected flag is 0
 hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee = false);
 // grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured);
+// envs: the ENVS variants (a.envd holds a distribution)
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false);
+// The sampling distribution of a map (include/wfpt.h "Environment next-event estimation"), built on the device in three launches on `s`:
+// f = Lm * s_y per texel into `f` (w * h floats) and its maximum's bits into *max_bits (zeroed by the caller); then, once the caller has
+// read M back, row (w * h) and the row-total prefix marg (h).
+hipError_t launch_env_weights(const EnvDev &env, float *f, uint32_t *max_bits, hipStream_t s);
+hipError_t launch_env_tables(const EnvDev &env, const float *f, float M, uint32_t *row, uint64_t *marg, hipStream_t s);
 hipError_t connect_prepare(const SceneDev &scene); // raises the connect kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
 // accumulate_kernel / accumulate_moments_kernel with the second plane: each sample's value is image_k + emitted_k (moments: null = none)

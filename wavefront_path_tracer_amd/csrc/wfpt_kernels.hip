@@ -1766,6 +1766,40 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_kernel(MissArgs a) {
 }
 __global__ __launch_bounds__(kConsumerThreads) void miss_env_kernel(MissArgs a, EnvDev env) { miss_body<true>(a, env); }
 
+// The miss pass of a context that connects to its map (WFPT_FLAG_ENV_NEE with a distribution; include/wfpt.h "Environment next-event
+// estimation"): miss_body<true> restated with one difference: where the pixel's connected flag (emitted.w, set by the connect pass of the
+// step that scattered this ray) is 1 the throughput becomes +0 -- the connect pass has already counted the map -- and the map is not read.
+// A copy for emission_nee_kernel's reason: miss_env_kernel keeps its instructions. (A change to miss_body belongs here too.)
+__global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs a, EnvDev env, const float *emitted) {
+    const uint32_t sample = blockIdx.y;
+    a.ctl += sample;
+    a.mq.base += sample * a.batch.queue_stride;
+    a.chunk_miss += sample * a.batch.chunk_stride;
+    a.chunk_miss_base += sample * a.batch.chunk_stride;
+    a.image += sample * a.batch.image_stride;
+    emitted += sample * a.batch.image_stride;
+    const uint32_t n_miss = umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.chunk_miss[chunk];
+        const uint32_t base = a.chunk_miss_base[chunk];
+        if (base >= n_miss) break;
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n_miss) break;
+            const size_t slot = chunk * kChunk + r;
+            const uint32_t lp = local_pixel(a.mq.pixel()[slot], a.image_width, a.tile);
+            float4 *px = pixel_of(a.image, lp);
+            const float4 thr = *px;
+            if (reinterpret_cast<const float4 *>(emitted)[lp].w != 0.0f) {
+                *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+            } else {
+                const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, a.mq.dx()[slot], a.mq.dy()[slot], a.mq.dz()[slot]);
+                *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+            }
+        }
+    }
+}
+
 // ================================================================================================
 // texture pass (WFPT_FLAG_TEXTURES; include/wfpt.h "Textures")
 // ================================================================================================
@@ -3207,6 +3241,52 @@ __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, fl
     return area > 0.0f && dist2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;
 }
 
+// One sample of the environment map for the receiver with normal n (the environment branch of include/wfpt.h "Environment next-event
+// estimation", in its operation order: f64 only in the two selections, no fma; tests/env_nee_ref.py restates it): the texel (y, x) by the
+// two tables, a direction inside it, its probability and the map's value there. Fills s.w (the shadow ray's direction), s.e (env_lookup),
+// s.G (Genv = (cos_s / pi) / (pdf * share)) and s.prim (y * w + x). False: no contribution (a NaN fails each comparison). The selections
+// clamp T and C into their tables (a NaN or negative draw of a caller's row selects 0), so every index read lies inside the tables.
+constexpr float kTwoPiSq = 19.739209f; // 2 pi^2
+__device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1, float u2, float u3, float u4, float share, LightSample &s) {
+    const uint32_t w = d.env.w, h = d.env.h;
+    const double ft = static_cast<double>(d.total);
+    const double tr = __builtin_floor(static_cast<double>(u1) * ft);
+    const uint64_t T = tr >= 0.0 ? (tr < ft ? static_cast<uint64_t>(tr) : d.total - 1u) : 0u;
+    uint32_t lo = 0u, hi = h - 1u; // the first row with marg[y] > T: marg[h - 1] = total > T
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (d.marg[mid] > T) hi = mid; else lo = mid + 1u;
+    }
+    const uint32_t y = lo;
+    const uint32_t *row = d.row + static_cast<size_t>(y) * w;
+    const uint32_t R = row[w - 1u]; // > 0: marg[y] > T >= marg[y - 1]
+    const double fr = static_cast<double>(R);
+    const double tc = __builtin_floor(static_cast<double>(u2) * fr);
+    const uint32_t C = tc >= 0.0 ? (tc < fr ? static_cast<uint32_t>(tc) : R - 1u) : 0u;
+    lo = 0u;
+    hi = w - 1u; // the first column with row[x] > C: row[w - 1] = R > C
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (row[mid] > C) hi = mid; else lo = mid + 1u;
+    }
+    const uint32_t x = lo;
+    const uint32_t k = row[x] - (x ? row[x - 1u] : 0u);
+    s.prim = y * w + x;
+    const float fw = static_cast<float>(w), fh = static_cast<float>(h);
+    const float u = (static_cast<float>(x) + u3) / fw, v = (static_cast<float>(y) + u4) / fh;
+    const float theta = kPi * v, phi = (2.0f * kPi) * ((u - 0.5f) - d.env.rotation);
+    float st, ct, sp, cp;
+    sincos_(theta, st, ct);
+    sincos_(phi, sp, cp);
+    s.w = {st * sp, ct, -(st * cp)};
+    const float P = static_cast<float>(k) / static_cast<float>(d.total);
+    const float pdf = ((P * fw) * fh) / (kTwoPiSq * st);
+    const float cos_s = dot3(n, s.w);
+    s.e = env_lookup(d.env.texels, w, h, d.env.intensity, d.env.rotation, s.w.x, s.w.y, s.w.z);
+    s.G = (cos_s / kPi) / (pdf * share);
+    return st > 0.0f && cos_s > 0.0f && pdf > 0.0f;
+}
+
 // Persistent workgroups of kExtendThreads threads over the (sample, segment) items of the hits a shade step will shade, one hit per thread:
 // the scene is staged once per workgroup, at its first item that holds a hit (a workgroup without one stages nothing). Each pixel has at
 // most one hit per wavefront: no two lanes touch one pixel. The closest hit decides the occlusion (WFPT_TRACE_ANY, then t against
@@ -3215,7 +3295,10 @@ __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, fl
 #ifndef WFPT_NEE_EARLY_OUT
 #define WFPT_NEE_EARLY_OUT 1 // 0: every shadow ray takes the closest-hit walk (the first version; tools/bench_nee.py's shirley:nee@closest leg builds it)
 #endif
-template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX>
+// ENVS (WFPT_FLAG_ENV_NEE contexts whose map has a distribution): a diffuse hit picks the map with probability `share` (sample_env; two more
+// draws; the shadow ray has no far end) and an emitter otherwise, each weighted by the inverse of its probability; the sampler form is the
+// map's alone. With ENVS false the kernel is the one of WFPT_FLAG_NEE.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
     extern __shared__ float4 lds[];
     WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
@@ -3249,13 +3332,20 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
         bool live = threadIdx.x < count;
         float3_ p = {0.0f, 0.0f, 0.0f}, n = p;
         float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f;
+        float u3 = 0.0f, u4 = 0.0f, share = 1.0f; // ENVS: the environment branch's two draws and the probability of the branch taken
+        bool to_env = false;
         float4 *px = nullptr, *out = nullptr;
         float4 rec1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (live && sampler) {
-            const float *row = a.sample_in + 9u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
+            const float *row = a.sample_in + (ENVS ? 10u : 9u) * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
             p = {row[0], row[1], row[2]};
             n = {row[3], row[4], row[5]};
-            u0 = row[6]; u1 = row[7]; u2 = row[8];
+            if (ENVS) {
+                u1 = row[6]; u2 = row[7]; u3 = row[8]; u4 = row[9];
+                to_env = true;
+            } else {
+                u0 = row[6]; u1 = row[7]; u2 = row[8];
+            }
         } else if (live) {
             const size_t slot = smp * static_cast<size_t>(a.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk + threadIdx.x;
             uint32_t prim, pixel_idx;
@@ -3281,7 +3371,8 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
             } else {
                 const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
                 out = pixel_of(a.emitted + smp * static_cast<size_t>(a.batch.image_stride), lp);
-                if (m != 0u || a.prim_em[prim] != kNoEmission) { // metal, dielectric, emitter: the flag is cleared, nothing else
+                // (ENVS: no emission table while no material emits)
+                if (m != 0u || ((!ENVS || a.prim_em) && a.prim_em[prim] != kNoEmission)) { // metal, dielectric, emitter: the flag is cleared, nothing else
                     out->w = 0.0f;
                     live = false;
                 } else {
@@ -3293,17 +3384,32 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
                     u0 = rng_next_float(rng);
                     u1 = rng_next_float(rng);
                     u2 = rng_next_float(rng);
+                    if (ENVS) { // the map with probability envd.share (the effective one: 1 with no light). At 1 there is no comparison:
+                        // u0 = 1.0f must never reach an empty light list, nor a division by 1 - 1
+                        to_env = !(a.envd.share < 1.0f) || u0 < a.envd.share;
+                        if (to_env) {
+                            share = a.envd.share;
+                            u3 = rng_next_float(rng);
+                            u4 = rng_next_float(rng);
+                        } else {
+                            share = 1.0f - a.envd.share;
+                            u0 = (u0 - a.envd.share) / share;
+                        }
+                    }
                 }
             }
         }
         LightSample s;
         bool lit = false, occluded = false;
-        if (live) lit = sample_light<PRIM, TEX>(a, p, n, u0, u1, u2, s);
+        if (ENVS && to_env) lit = sample_env(a.envd, n, u1, u2, u3, u4, share, s);
+        else if (live) lit = sample_light<PRIM, TEX>(a, p, n, u0, u1, u2, s);
         if (lit) {
 #if WFPT_STAMPS
             uint32_t dbg[3] = {0, 0, 0};
 #endif
-            const float window = s.dist * 0.999f;
+            // (the map: any hit occludes. Started with the closest-hit walk's own far end the early-out walk answers "is there a hit": kOccNone
+            // means the reference tests no primitive below 1e30, kOccHit that it accepts one)
+            const float window = (ENVS && to_env) ? 1e30f : s.dist * 0.999f;
             uint32_t verdict = kOccUndecided;
             // scenes in LDS, conservative boxes: the early-out walk answers most rays (3.4 % of a Shirley frame, same booleans)
             if (WFPT_NEE_EARLY_OUT && LDS_SCENE && !EXACT && !far_origin(a.scene, p.x, p.y, p.z))
@@ -3314,20 +3420,24 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
                 uint32_t prim = 0;
                 bool hit = false;
                 WFPT_TRACE_ANY(g_nodes, s_stack, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z);
-                occluded = hit && t < window;
+                occluded = hit && ((ENVS && to_env) || t < window);
             } else {
                 occluded = verdict == kOccHit;
             }
         }
         if (live && sampler) {
             float *row = a.sample_out + 8u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
+            if (ENVS) s.q = s.w;
             row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
             row[3] = static_cast<float>(s.prim);
             row[4] = lit ? s.e.x * s.G : 0.0f; row[5] = lit ? s.e.y * s.G : 0.0f; row[6] = lit ? s.e.z * s.G : 0.0f;
             row[7] = occluded ? 1.0f : 0.0f;
         } else if (live) {
             const float4 thr = *px, had = *out;
-            if (lit && !occluded)
+            if (ENVS && lit && !occluded && !to_env) // an emitter, picked with probability `share` = 1 - envd.share: the last operation
+                *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) / share, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) / share,
+                                   had.z + (((thr.z * rec1.z) * s.e.z) * s.G) / share, 1.0f);
+            else if (lit && !occluded)
                 *out = make_float4(had.x + ((thr.x * rec1.x) * s.e.x) * s.G, had.y + ((thr.y * rec1.y) * s.e.y) * s.G,
                                    had.z + ((thr.z * rec1.z) * s.e.z) * s.G, 1.0f);
             else
@@ -3751,6 +3861,61 @@ __global__ __launch_bounds__(256) void env_sample_kernel(EnvDev env, const float
     rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 
+// ---- the sampling distribution of an environment map (include/wfpt.h "Environment next-event estimation"; not a hot path: three launches
+// per wfpt_set_environment). All-f32 in the header's order; the tables are integers, so the order of the sums does not matter.
+// f = Lm * s_y per texel, and the bits of the map's largest f (f >= 0: the bit patterns order as the floats do) into *max_bits
+__global__ __launch_bounds__(256) void env_weight_kernel(EnvDev env, float *f, uint32_t *max_bits) {
+    const size_t n = static_cast<size_t>(env.w) * env.h, i = blockIdx.x * static_cast<size_t>(256) + threadIdx.x;
+    float v = 0.0f;
+    if (i < n) {
+        const uint32_t y = static_cast<uint32_t>(i / env.w), x = static_cast<uint32_t>(i - static_cast<size_t>(y) * env.w);
+        float lm = 0.0f; // the texels env_lookup's taps reach from inside (x, y): columns wrap, rows clamp
+        for (int dy = -1; dy <= 1; ++dy) {
+            const uint32_t yy = (dy < 0 && y == 0u) ? 0u : (dy > 0 && y + 1u == env.h) ? y : y + dy;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const uint32_t xx = (x + env.w + dx) % env.w;
+                const float4 t = env.texels[static_cast<size_t>(yy) * env.w + xx];
+                lm = max_(lm, denoise_luma(t.x, t.y, t.z));
+            }
+        }
+        float sy, cy;
+        sincos_(kPi * ((static_cast<float>(y) + 0.5f) / static_cast<float>(env.h)), sy, cy);
+        v = lm * sy;
+        f[i] = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) v = max_(v, __shfl_xor(v, off));
+    if ((threadIdx.x & 63u) == 0u && v > 0.0f) atomicMax(max_bits, __float_as_uint(v));
+}
+// One wave per row: k = u32(ceil((f / M) * 65535)), at least 1 where f > 0 (a quotient that underflows), scanned along the row
+__global__ __launch_bounds__(64) void env_row_kernel(EnvDev env, const float *f, float M, uint32_t *row) {
+    const size_t base = static_cast<size_t>(blockIdx.x) * env.w;
+    uint32_t carry = 0u;
+    for (uint32_t x0 = 0; x0 < env.w; x0 += 64u) {
+        const uint32_t x = x0 + threadIdx.x;
+        uint32_t k = 0u;
+        if (x < env.w) {
+            const float fv = f[base + x];
+            k = static_cast<uint32_t>(__builtin_ceilf((fv / M) * 65535.0f));
+            if (fv > 0.0f && k == 0u) k = 1u;
+        }
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t t = __shfl_up(k, off);
+            if (threadIdx.x >= off) k += t;
+        }
+        k += carry;
+        if (x < env.w) row[base + x] = k;
+        carry = __shfl(k, 63);
+    }
+}
+// marg[y] = the sum of the row totals up to row y (one thread: at most 8192 rows, once per map)
+__global__ void env_marg_kernel(const uint32_t *row, uint32_t w, uint32_t h, uint64_t *marg) {
+    uint64_t sum = 0;
+    for (uint32_t y = 0; y < h; ++y) {
+        sum += row[static_cast<size_t>(y) * w + (w - 1u)];
+        marg[y] = sum;
+    }
+}
+
 __global__ __launch_bounds__(256) void tex_sample_kernel(TexDev tex, const float *uv, float *rgb, size_t n) {
     const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
     if (i >= n) return;
@@ -3971,12 +4136,27 @@ hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env) {
+hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const float *connected) {
     if (grid == 0) return hipSuccess;
-    if (env)
+    if (env && connected)
+        hipLaunchKernelGGL(miss_env_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *env, connected);
+    else if (env)
         hipLaunchKernelGGL(miss_env_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *env);
     else
         hipLaunchKernelGGL(miss_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_env_weights(const EnvDev &env, float *f, uint32_t *max_bits, hipStream_t s) {
+    const size_t n = static_cast<size_t>(env.w) * env.h;
+    hipLaunchKernelGGL(env_weight_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, env, f, max_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_env_tables(const EnvDev &env, const float *f, float M, uint32_t *row, uint64_t *marg, hipStream_t s) {
+    hipLaunchKernelGGL(env_row_kernel, dim3(env.h), dim3(64), 0, s, env, f, M, row);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(env_marg_kernel, dim3(1), dim3(1), 0, s, row, env.w, env.h, marg);
     return hipGetLastError();
 }
 
@@ -4075,25 +4255,28 @@ hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvD
 
 namespace {
 using ConnectFn = void (*)(ConnectArgs);
-template <bool TEX> struct ConnectK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX>; }
+template <bool TEX, bool ENVS> struct ConnectK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS>; }
 };
-ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex) {
-    return tex ? pick_variant<ConnectK<true>>(sc, exact, sc.lds_scene != 0) : pick_variant<ConnectK<false>>(sc, exact, sc.lds_scene != 0);
+ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = false) {
+    const bool lds = sc.lds_scene != 0;
+    if (envs) return tex ? pick_variant<ConnectK<true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true>>(sc, exact, lds);
+    return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
 }
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
     for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
-        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true));
+        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true),
+                                               connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured) {
-    if (grid == 0 || a.n_lights == 0) return hipSuccess;
-    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs) {
+    if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
+    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }
 

@@ -381,6 +381,22 @@ class PathTracer {
         check(wfpt_sample_lights(ctx_, in9.data(), in9.size() / 9, out.data()));
         return out;
     }
+    // Environment next-event estimation (the three flags above | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment
+    // next-event estimation"): the map as one more light of the connect pass, sampled in proportion to its radiance.
+    void set_environment_share(float share) { check(wfpt_set_environment_share(ctx_, share)); }
+    float environment_share() const { return wfpt_environment_share(ctx_); }
+    // (row: w * h prefix sums of the texel weights along the rows, marg: h prefix sums of the row totals) of a w x h map
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> environment_distribution(uint32_t w, uint32_t h) {
+        std::pair<std::vector<uint32_t>, std::vector<uint64_t>> t{std::vector<uint32_t>(static_cast<size_t>(w) * h), std::vector<uint64_t>(h)};
+        check(wfpt_read_environment_distribution(ctx_, t.first.data(), t.second.data()));
+        return t;
+    }
+    // rows of (p.xyz, n.xyz, u1, u2, u3, u4) -> rows of (wdir.xyz, texel index, e Genv rgb, occluded)
+    std::vector<float> sample_environment_light(const std::vector<float> &in10) {
+        std::vector<float> out(in10.size() / 10 * 8);
+        check(wfpt_sample_environment_light(ctx_, in10.data(), in10.size() / 10, out.data()));
+        return out;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
