@@ -237,7 +237,11 @@ enum {
     WFPT_FLAG_ENV_NEE = 1u << 16     /* the environment map as one more light of the connect pass, sampled in proportion to its radiance, see
                                         "Environment next-event estimation" below. Needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and
                                         WFPT_FLAG_NEE. With no map set (or a black one) the context renders bit for bit as without the
-                                        flag, and launches the same kernels. */
+                                        flag, and launches the same kernels. */,
+    WFPT_FLAG_MIS = 1u << 17         /* multiple importance sampling, see "Multiple importance sampling" below: the emitter hits of
+                                        scattered rays and the shadow rays of the connect pass are both kept, weighed by the balance
+                                        heuristic. Needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with WFPT_FLAG_ENV_NEE. With no emitter
+                                        set the context renders bit for bit as without the flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -743,7 +747,7 @@ int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  *     e * tex per channel where the light's material is bound to a texture (the texture pass's lookup at q).
  * The emission pass of such a context still leaves thr = +0 at a hit on an emitter, but adds thr * e only where the pixel's connected flag
  * is 0: at primary hits and after a metal or dielectric bounce. After a diffuse bounce the connect pass has already counted that light
- * (next-event estimation without multiple importance sampling).
+ * (next-event estimation without multiple importance sampling; with it: WFPT_FLAG_MIS, "Multiple importance sampling" below).
  * Shade, the tracing kernels, miss, the loop exit, the AOVs, accumulation (image + emitted in sample order) and the luminance moments are
  * unchanged, and dead paths keep travelling. Every batch size, loop, RNG mode's queue order and band sharding gives the same connect
  * samples: the stream is keyed by the pixel.
@@ -819,6 +823,58 @@ int wfpt_read_environment_distribution(wfpt_ctx *ctx, uint32_t *row_wh, uint64_t
  * rows of (wdir.xyz, f32(y * w + x), e * Genv per channel -- 0 where the sample contributes nothing --, 1.0 if the sample is occluded and
  * 0.0 otherwise). WFPT_ERR_INVALID_ARGUMENT while no map with a distribution is set */
 int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, float *out8);
+
+/* ------------------------------------------------------------------ Multiple importance sampling (WFPT_FLAG_MIS)
+ * wfpt_create* accepts WFPT_FLAG_MIS only together with WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, and refuses it together with
+ * WFPT_FLAG_ENV_NEE (WFPT_ERR_INVALID_ARGUMENT either way). The flag combines the two strategies that can find an emitter after a diffuse
+ * bounce -- shade's cosine-distributed Lambertian scatter and the connect pass's area sampling of the light list -- by the balance
+ * heuristic. No ray is added: the emitter hit of a scattered ray, which "Next-event estimation" drops, gets the weight wb, and the shadow
+ * ray's sample, which it takes whole, gets the complementary wl.
+ *
+ * The identity the weights rest on: shade's Lambertian scatter (shade.wgsl:102-108) is d = n + r with r a normalised point of the unit
+ * sphere and d NOT normalised, a cosine distribution about the unflipped n with solid-angle density cos / pi. As |n| = |r| = 1,
+ * |d|^2 = 2 (1 + n.r), so the cosine of d against n is |d| / 2: the density of the scatter that produced a ray is (0.5 |d|) / pi, from
+ * the ray's own direction, without the previous normal. Two caveats: n and r are unit vectors only to rounding, so 0.5 |d| and n.d / |d|
+ * differ by rounding (DESIGN.md 9j measures it); and the scatter's `length < 0.001` fallback d = n gives 0.5 where the cosine is 1, an
+ * event of probability of order 1e-9 that is accepted.
+ *
+ * On a flagged context with an emitter the step order stays texture, emission, connect, shade; the stream, the draws, the light choice,
+ * the point, the occlusion test and the connected flag of "Next-event estimation" are unchanged. All operations are IEEE f32 in the order
+ * written, no fma, pi = 3.1415927f. Two things change:
+ *  1. Connect pass, step 5. For an unoccluded contributing sample
+ *       pb = cos_s / pi;  pl = dist2 / ((cos_l * A) * nf);  wl = pl / (pl + pb)
+ *       emitted[pixel] += (((thr * albedo) * e_q) * G) * wl
+ *     At every diffuse hit, contributing or not, the pass also writes the hit point p (as shade computes it) into a per-sample,
+ *     per-pixel float4 plane `origin`, as (p.x, p.y, p.z, 0). The plane has the shape of `emitted`, is allocated with the first emitter
+ *     and kept, and costs 16 bytes per pixel per sample in flight. It is never zeroed: it is read only where the connected flag is 1.
+ *  2. Emission pass. At a hit on an emitter whose pixel's connected flag is 0, emitted += thr * e as before (primary hits, hits after
+ *     metal or glass). Where the flag is 1, with d the hit's ray direction (not normalised), o the pixel's `origin` entry and ph the hit
+ *     point as shade computes it:
+ *       v = ph - o;  dist2 = (v.x v.x + v.y v.y) + v.z v.z;  dist = sqrt(dist2);  w = v / dist   (three divisions)
+ *       nl, A = the hit primitive's, as step 3 of "Next-event estimation" computes them with q = ph
+ *               (sphere: nl = (ph - c) / ra, A = (4 pi) * (ra ra);  triangle: the stored normal and the cross-product area)
+ *       cos_l = |(nl.x w.x + nl.y w.y) + nl.z w.z|;  len = sqrt((d.x d.x + d.y d.y) + d.z d.z);  pb = (0.5 * len) / pi
+ *       wb = 1 and pl = 0                                     if A > 0, dist2 > 0 or cos_l > 0 fails (a NaN fails each test)
+ *       pl = dist2 / ((cos_l * A) * nf);  wb = pb / (pb + pl)   otherwise
+ *       emitted[pixel] += (thr * e) * wb   per channel (thr already holds the texture where the texture pass applied);  thr <- +0
+ *     wb = 1 on a failed condition because the connect pass can never produce that sample. o equals the origin of the ray that made the
+ *     hit bit for bit (extension_ray.origin = p): a loop that still holds the ray queue may read it there instead; the shipped kernels
+ *     read the plane in every loop.
+ * Every batch size, loop, RNG mode and band sharding gives the same weights: they depend on the path alone.
+ * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
+ * flagged context with an emitter never runs the class-binned loop (see "Emission"); wfpt_render_chunked* masks the flag off. The
+ * launches are booked under wfpt_emission_timing_ms and wfpt_nee_timing_ms. The calls below are blocking and return
+ * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while no primitive emits.
+ * Not done: weighing the environment map against the scatter (WFPT_FLAG_ENV_NEE is refused), the power heuristic, cone sampling of
+ * sphere lights, light selection by power, MIS for fuzzy metal, retiring dead paths, the class-binned loop and wfpt_render_chunked*. */
+/* Steps 3 to 5 with the weight for n caller-supplied receivers on the device. in9: as wfpt_sample_lights; out12: n rows of (q.xyz, the
+ * light's primitive index as a float, ((e_q * G) * wl) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pl, pb, wl, 0) --
+ * the three channels and pl, pb, wl are 0 where the sample contributes nothing. */
+int wfpt_sample_lights_mis(wfpt_ctx *ctx, const float *in9, size_t n, float *out12);
+/* The emission pass's weight for n caller-supplied hits on the device. in8: n rows of (o.xyz, d.xyz, t, the primitive index as the float
+ * of its integer value), with ph = o + t d per component; out4: n rows of (pl, pb, wb, cos_l). A primitive that does not emit or is out
+ * of range (a NaN included) gives (0, pb, 1, 0). */
+int wfpt_mis_hit_weight(wfpt_ctx *ctx, const float *in8, size_t n, float *out4);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""tools/bench_mis.py: what multiple importance sampling costs per frame (WFPT_FLAG_MIS).
+
+Legs, --spp samples per frame: `plain` no flag, `lit` WFPT_FLAG_EMISSION, `nee` EMISSION|NEE, `mis` EMISSION|NEE|MIS:
+  shirley  plain | lit | nee | mis   (the three big spheres emit)                          at --width x --height
+  lamp     lit | nee | mis           (section 9h's small, far emitting sphere over a large Lambertian one, black map, miss_floor = 0)
+  near     lit | nee | mis           (the near-lamp scene of the tests: radius 1, a gap of 0.05 to the radius-1000 ground)
+and, with --parent-tree DIR (a checkout of the parent commit with its library built), the plain Shirley frame of that tree: the kernels a
+context without the flag launches are the parent's, so the two are expected to be equal within the spread reported here.
+
+Method: tools/bench_nee.py's. Every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that drift
+hits them alike. A child warms up (graph capture, first touch), then times --frames frames one by one, each ending in a device
+synchronise. A leg's figure is the median of all its frames; its spread is the range of its per-round medians. The connect and emission
+launches' own times come from wfpt_nee_timing_ms and wfpt_emission_timing_ms over one timed frame (hipEvent pairs around every launch, so
+it is slower than the frame it describes). The lamp legs also report the sum of wfpt_read_variance over the frame (WFPT_FLAG_DENOISE is
+set on them), for the equal-time product variance x frame time. Prints one JSON line per leg and one summary line."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def leg(a):
+    sys.path.insert(0, a.tree)
+    import numpy as np
+    import wavefront_path_tracer_amd as W
+    scene, kind = a.leg.split(":")
+    flags = {"plain": 0, "lit": W.FLAG_EMISSION, "nee": W.FLAG_EMISSION | W.FLAG_NEE}.get(kind)
+    if flags is None:
+        flags = W.FLAG_EMISSION | W.FLAG_NEE | W.FLAG_MIS
+    if scene in ("lamp", "near"):
+        sp, mt = np.zeros(2, W.SPHERE), np.zeros(2, W.MATERIAL)
+        mt["albedo"][:] = (0.5, 0.75, 0.25, 1.0)
+        sp["center"][:, 3] = 1.0
+        far = scene == "lamp"
+        sp["center"][:, :3] = [(0.0, -100.0, 0.0), (0.0, 2.0, 0.0)] if far else [(0.0, -1000.0, 0.0), (0.0, 1.05, 0.0)]
+        sp["radius"] = (100.0, 0.25) if far else (1000.0, 1.0)
+        sp["material_idx"] = (0, 1)
+        cc = W.CameraController(W.Camera((0.0, 6.0, 8.0) if far else (0.0, 5.0, 7.0), (0.0, 0.0, 0.0)), 40.0, 0.0, 10.0, 0.1, 100.0)
+        pt = W.PathTracer(W.Scene(sp, mt), W.RenderParameters(cc, (a.width, a.height)), max_wavefronts=a.bounces, miss_floor=0,
+                          rng_mode=W.RNG_DISPATCH, flags=flags | W.FLAG_ENVIRONMENT | W.FLAG_DENOISE, batch=64)
+        pt.set_environment(np.zeros((1, 1, 3), "<f4"))
+        pt.set_emission(1, (16.0, 8.0, 32.0) if far else (4.0, 2.0, 8.0))
+    elif scene == "shirley":
+        pt = W.shirley_path_tracer(a.width, a.height, max_wavefronts=a.bounces, rng_mode=W.RNG_DISPATCH, flags=flags, batch=64)
+        if kind != "plain":
+            sp = pt.scene.spheres
+            for m, c in zip(sp["material_idx"][sp["radius"] == 1.0], ((4.0, 3.0, 2.0), (0.25, 0.5, 1.5), (1.0, 1.0, 1.0))):
+                pt.set_emission(int(m), c)
+    else:
+        sys.exit(f"bench_mis: unknown scene {scene}")
+    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
+    pt.render(a.spp)
+    pt.synchronize()
+    ms = []
+    for _ in range(a.frames):
+        t0 = time.perf_counter()
+        pt.render(a.spp)
+        pt.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms}
+    if scene in ("lamp", "near"):  # the variance of the last frame's mean, summed over the frame (every leg restarts from the same state)
+        pt.reset_progress()
+        pt.render(a.spp)
+        out.update(variance_sum=float(pt.variance().astype(np.float64).sum()))
+    if kind in ("nee", "mis"):
+        stage_ms, _ = pt.render_timed(a.spp)
+        nee_ms, launches = pt.nee_timing()
+        out.update(lights=pt.nee_light_count(), connect_ms_timed=nee_ms, connect_launches_timed=launches, emission_ms_timed=pt.emission_timing()[0],
+                   stages_ms_timed=float(np.sum(stage_ms)))
+    print(json.dumps(out), flush=True)
+    pt.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=64)
+    ap.add_argument("--bounces", type=int, default=8)
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--scenes", nargs="+", default=["shirley", "lamp", "near"])
+    ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
+    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.leg:
+        return leg(a)
+    legs = []
+    if "shirley" in a.scenes:
+        legs += [("shirley:plain", ROOT), ("shirley:lit", ROOT), ("shirley:nee", ROOT), ("shirley:mis", ROOT)]
+        if a.parent_tree:
+            legs.insert(1, ("shirley:plain@parent", os.path.abspath(a.parent_tree)))
+    for scene in ("lamp", "near"):
+        if scene in a.scenes:
+            legs += [(f"{scene}:lit", ROOT), (f"{scene}:nee", ROOT), (f"{scene}:mis", ROOT)]
+    results = {name: {"rounds": [], "last": None} for name, _ in legs}
+    for _ in range(a.rounds):
+        for name, tree in legs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
+                   str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--frames", str(a.frames)]
+            env = dict(os.environ)
+            env.pop("WFPT_LIB", None)  # each tree loads its own library
+            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
+            if res.returncode != 0:
+                sys.exit(f"bench_mis: leg {name} failed with status {res.returncode}")
+            r = json.loads(res.stdout.strip().splitlines()[-1])
+            results[name]["rounds"].append(r["frame_ms"])
+            results[name]["last"] = r
+            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
+    summary = {}
+    for name, _ in legs:
+        rounds = results[name]["rounds"]
+        med = statistics.median(x for r in rounds for x in r)
+        per_round = [statistics.median(r) for r in rounds]
+        line = {"leg": name, "loop": results[name]["last"]["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces,
+                "frames": a.frames, "rounds": a.rounds, "frame_ms_median": round(med, 3),
+                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3)}
+        for k in ("lights", "variance_sum", "connect_ms_timed", "connect_launches_timed", "emission_ms_timed", "stages_ms_timed"):
+            if k in results[name]["last"]:
+                line[k] = round(results[name]["last"][k], 3) if isinstance(results[name]["last"][k], float) else results[name]["last"][k]
+        summary[name] = line
+        print(json.dumps(line), flush=True)
+    rel = {}
+    for name, base in (("shirley:lit", "shirley:plain"), ("shirley:nee", "shirley:lit"), ("shirley:mis", "shirley:nee"), ("lamp:mis", "lamp:nee"),
+                       ("near:mis", "near:nee"), ("near:mis", "near:lit"), ("shirley:plain", "shirley:plain@parent")):
+        if name in summary and base in summary:
+            rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
+            if "variance_sum" in summary[name] and "variance_sum" in summary[base]:  # equal time: variance x frame time, MIS over the base
+                rel[f"{name} over {base}, variance x time"] = round(
+                    summary[name]["variance_sum"] * summary[name]["frame_ms_median"] / (summary[base]["variance_sum"] * summary[base]["frame_ms_median"]), 4)
+    print(json.dumps({"summary": rel}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

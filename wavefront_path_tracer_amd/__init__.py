@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -43,6 +43,7 @@ FLAG_NEE = 1 << 15  # shadow rays from diffuse hits to the emitters (include/wfp
 # the environment map as one more light of the connect pass (include/wfpt.h "Environment next-event estimation"); needs FLAG_ENVIRONMENT,
 # FLAG_EMISSION and FLAG_NEE
 FLAG_ENV_NEE = 1 << 16
+FLAG_MIS = 1 << 17
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -354,6 +355,8 @@ def lib():
         "wfpt_environment_share": (f32, [vp]),
         "wfpt_read_environment_distribution": (i32, [vp, vp, vp]),
         "wfpt_sample_environment_light": (i32, [vp, vp, sz, vp]),
+        "wfpt_sample_lights_mis": (i32, [vp, vp, sz, vp]),
+        "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -1430,6 +1433,27 @@ class PathTracer:
             raise ValueError(f"sample_environment_light: expected rows of 10 floats, got shape {a.shape}")
         out = np.zeros((a.shape[0], 8), "<f4")
         self._check(lib().wfpt_sample_environment_light(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
+
+    # ---- multiple importance sampling (contexts created with FLAG_EMISSION | FLAG_NEE | FLAG_MIS; include/wfpt.h "Multiple importance sampling")
+    def sample_lights_mis(self, rows):
+        """The connect pass's weighed light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 as for
+        sample_lights; returns (n, 12) float32 of (q.xyz, the light's primitive index, (e_q * G) * wl per channel, occluded 0/1, pl, pb, wl, 0)."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != 9:
+            raise ValueError(f"sample_lights_mis: expected rows of 9 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 12), "<f4")
+        self._check(lib().wfpt_sample_lights_mis(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
+
+    def mis_hit_weight(self, rows):
+        """The emission pass's weight for caller-supplied hits, computed on the device. rows: (n, 8) float32 of (o.xyz, d.xyz, t, the
+        primitive index); returns (n, 4) float32 of (pl, pb, wb, cos_l)."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError(f"mis_hit_weight: expected rows of 8 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 4), "<f4")
+        self._check(lib().wfpt_mis_hit_weight(self.handle, _p(a), a.shape[0], _p(out)))
         return out
 
     # ---- read-back

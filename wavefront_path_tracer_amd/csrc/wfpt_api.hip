@@ -253,6 +253,9 @@ struct wfpt_ctx {
     uint32_t stage_extends = 0;
     double nee_ms = 0.0;        // connect launches of the timed renders since wfpt_create (wfpt_nee_timing_ms)
     uint32_t nee_launches = 0;
+    // WFPT_FLAG_MIS (include/wfpt.h "Multiple importance sampling"): the hit points of the diffuse hits, `emitted`'s shape (one float4 per
+    // pixel per sample in flight), allocated with the first emitter and kept; never zeroed (read only where the connected flag is 1)
+    DeviceBuffer<float4> mis_origin;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
     // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
     DeviceBuffer<uint32_t> env_row;
@@ -633,6 +636,12 @@ bool env_connecting(const wfpt_ctx *c) { return c->env_row.get() != nullptr; }
 bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || env_connecting(c); }
 // the second plane is in use: accumulate adds it, the head of every batch zeroes it
 bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c); }
+// a WFPT_FLAG_MIS context holds an emitter (never with a map's distribution: the flag excludes WFPT_FLAG_ENV_NEE): the connect and
+// emission passes are the MIS variants
+bool weighing(const wfpt_ctx *c) { return c->mis_origin.get() != nullptr && c->n_lights > 0; }
+MisArgs mis_args(const wfpt_ctx *c) {
+    return MisArgs{c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
+}
 // the connect pass before a shade step of wavefront `wavefront`: the hits emission_args names, in its two forms
 ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
                          uint32_t material = 0xffffffffu) {
@@ -661,13 +670,19 @@ ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t n
     a.n_lights = c->n_lights;
     a.ts = tex_scene(c);
     a.scene = c->scene;
+    if (weighing(c)) a.origin = c->mis_origin.get(); // (shares sample_out's slot: the sampler calls set that one after this)
     if (env_connecting(c)) // the effective share: 1 while there is no light to pick instead
         a.envd = EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f};
     return a;
 }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
-    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c));
+    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c));
+}
+// the emission pass of the context's kind: emission_kernel, its connecting twin or its weighing one
+hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
+    const MisArgs m = mis_args(c);
+    return launch_emission(a, grid, c->stream.get(), connecting(c), weighing(c) ? &m : nullptr);
 }
 // the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
 const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
@@ -744,7 +759,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      }));
         if (emitting(c))
             WFPT_HIP(c, timed(kStageEmission, [&] {
-                         return launch_emission(emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st, connecting(c));
+                         return launch_emission_pass(c, emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb));
                      }));
         if (connecting(c))
             WFPT_HIP(c, timed(kStageConnect, [&] {
@@ -780,7 +795,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
             WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
         if (emitting(c)) // after the texture pass: a textured emitter's light is (thr * tex) * e
-            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
         if (connecting(c)) // after the emission pass, which reads the flag the previous step's connect pass left
             WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
@@ -830,7 +845,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
             if (connecting(c))
                 WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
@@ -841,7 +856,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             if (textured(c))
                 WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
             if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission(emission_args(c, par, nb), consumer_grid(c, nb), st, connecting(c)); }));
+                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
             if (connecting(c))
                 WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
@@ -1420,6 +1435,19 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
         return nullptr;
     }
+    if ((params->flags & WFPT_FLAG_MIS) != 0) {
+        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
+        if ((params->flags & need) != need) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_MIS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+                                                     "(it weighs the emission pass's hits against the connect pass's samples)");
+            return nullptr;
+        }
+        if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_MIS does not go with WFPT_FLAG_ENV_NEE "
+                                                     "(the map's samples are not weighed against the scatter yet)");
+            return nullptr;
+        }
+    }
     if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
         constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
         if ((params->flags & need) != need) {
@@ -1637,7 +1665,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1890,7 +1918,7 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         if (textured(c))
             WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
         if (emitting(c))
-            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get(), connecting(c)));
+            WFPT_HIP(c, launch_emission_pass(c, emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1)));
         if (connecting(c))
             WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads), 1));
         WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx, 0xffffffffu, true),
@@ -1904,9 +1932,9 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
                                                     static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
                                        consumer_grid(c, 1), c->stream.get()));
         if (emitting(c))
-            WFPT_HIP(c, launch_emission(emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
-                                                      static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
-                                        consumer_grid(c, 1), c->stream.get(), connecting(c)));
+            WFPT_HIP(c, launch_emission_pass(c, emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
+                                                           static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
+                                             consumer_grid(c, 1)));
         if (connecting(c)) // the Lambertian stage connects, the other two only clear the pixels' connected flags
             WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
                                                             static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)), 1));
@@ -3138,12 +3166,15 @@ static int apply_emission(wfpt_ctx *c, std::vector<float> &&rgb) {
     EmissionTables tables;
     if (int r = build_emission_tables(c, rgb, c->h_prim_mat_idx, tables); r != WFPT_OK) return r;
     DeviceBuffer<float> plane;
+    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS: the hit-point plane comes and stays with the second plane
     if (tables.prim.get() && !c->emitted.get()) {
         WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
         WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
+        if (c->p.flags & WFPT_FLAG_MIS) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
     if (plane.get()) c->emitted = std::move(plane);
+    if (origin.get()) c->mis_origin = std::move(origin);
     c->em_rgb = std::move(rgb);
     commit_emission_tables(c, std::move(tables));
     return scene_changed(c);
@@ -3217,7 +3248,7 @@ int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (e == hipSuccess) {
         ConnectArgs a = connect_args(c, 0, -1, 1);
         a.sample_in = d_in.get();
-        a.sample_out = d_out.get();
+        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
         a.sample_n = static_cast<uint32_t>(n);
         const uint64_t items = (n + kChunk - 1) / kChunk;
         e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
@@ -3226,6 +3257,57 @@ int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
     if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights");
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- multiple importance sampling (include/wfpt.h "Multiple importance sampling")
+static int mis_check(wfpt_ctx *c, const char *who) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_MIS)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_MIS");
+    if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no primitive emits");
+    return WFPT_OK;
+}
+
+int wfpt_sample_lights_mis(wfpt_ctx *c, const float *in9, size_t n, float *out12) {
+    if (int r = mis_check(c, "wfpt_sample_lights_mis"); r != WFPT_OK) return r;
+    if ((!in9 || !out12) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights_mis: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights_mis: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(9 * n);
+    if (e == hipSuccess) e = d_out.alloc(12 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) {
+        ConnectArgs a = connect_args(c, 0, -1, 1);
+        a.sample_in = d_in.get();
+        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
+        a.sample_n = static_cast<uint32_t>(n);
+        const uint64_t items = (n + kChunk - 1) / kChunk;
+        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
+                           textured(c), false, true);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out12, d_out.get(), sizeof(float) * 12 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights_mis");
+    return WFPT_OK;
+}
+
+int wfpt_mis_hit_weight(wfpt_ctx *c, const float *in8, size_t n, float *out4) {
+    if (int r = mis_check(c, "wfpt_mis_hit_weight"); r != WFPT_OK) return r;
+    if ((!in8 || !out4) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_mis_hit_weight: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_mis_hit_weight: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(8 * n);
+    if (e == hipSuccess) e = d_out.alloc(4 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in8, sizeof(float) * 8 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess)
+        e = launch_mis_weight(mis_args(c), c->scene.shade_rec, c->em_prim.get(), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out4, d_out.get(), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_mis_hit_weight");
     return WFPT_OK;
 }
 
@@ -3276,7 +3358,7 @@ int wfpt_sample_environment_light(wfpt_ctx *c, const float *in10, size_t n, floa
         ConnectArgs a = connect_args(c, 0, -1, 1);
         a.envd.share = 1.0f; // the environment branch alone
         a.sample_in = d_in.get();
-        a.sample_out = d_out.get();
+        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
         a.sample_n = static_cast<uint32_t>(n);
         const uint64_t items = (n + kChunk - 1) / kChunk;
         e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),

@@ -489,11 +489,32 @@ struct ConnectArgs {
     const uint32_t *lights;
     uint32_t n_lights;
     const float *sample_in;
-    float *sample_out;
+    union {                   // (one slot: the struct, and with it the kernels of contexts without WFPT_FLAG_MIS, stays as it was)
+        float *sample_out;    // the sampler form: the rows out
+        float4 *origin;       // the MIS variants' render form: the hit points of the diffuse hits, `emitted`'s shape and strides (MisArgs)
+    };
     uint32_t sample_n;
     TexScene ts;              // the textures of the lights (the TEX variants only)
     SceneDev scene;
     EnvDist envd;             // the map as a light (the ENVS variants only; below)
+};
+// sample_out and origin alias: a sampler call on a WFPT_FLAG_MIS context gets `origin` from connect_args and must set sample_out after it
+// (the sampler form never reads `origin`, the render form never sample_out: sample_n tells them apart)
+static_assert(sizeof(float *) == sizeof(float4 *), "ConnectArgs: sample_out and origin share one slot");
+
+// Multiple importance sampling (WFPT_FLAG_MIS with an emitter; include/wfpt.h "Multiple importance sampling"): the balance heuristic
+// between shade's cosine scatter and the connect pass's area sampling. The MIS connect variants weigh their sample by wl and store the
+// hit point of every diffuse hit in `origin` (one float4 per pixel per sample in flight, never zeroed: read only where the connected
+// flag is 1, which the same lane set with it). emission_mis_kernel weighs a hit on an emitter whose pixel's flag is 1 by wb
+// (mis_hit_weight: the distance comes from `origin`, the scatter's density from the length of the ray's direction) instead of dropping it.
+// The sampler forms: the connect variants answer 12 floats a row (wfpt_sample_lights_mis), mis_weight_kernel runs mis_hit_weight on rows
+// of (o, d, t, primitive) (wfpt_mis_hit_weight).
+struct MisArgs {
+    const float4 *prim_geom;
+    const float4 *origin;
+    uint32_t prim_kind;
+    uint32_t n_prims;
+    float nf;                 // f32(n_lights)
 };
 
 struct AccumulateArgs {
@@ -629,10 +650,14 @@ hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const float *connected = nullptr);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
 // nee: the variant of contexts that connect (WFPT_FLAG_NEE with an emitter): adds thr * e only where the pixel's connected flag is 0
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee = false);
+// mis: emission_mis_kernel (the same contexts with WFPT_FLAG_MIS): a hit whose pixel's flag is 1 adds (thr * e) * wb
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee = false, const MisArgs *mis = nullptr);
+// wfpt_mis_hit_weight: n rows of (o.xyz, d.xyz, t, primitive) -> (pl, pb, wb, cos_l), one thread per row
+hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s);
 // grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture
 // envs: the ENVS variants (a.envd holds a distribution)
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false);
+// mis: the MIS variants (a.origin set; never with envs)
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false);
 // The sampling distribution of a map (include/wfpt.h "Environment next-event estimation"), built on the device in three launches on `s`:
 // f = Lm * s_y per texel into `f` (w * h floats) and its maximum's bits into *max_bits (zeroed by the caller); then, once the caller has
 // read M back, row (w * h) and the row-total prefix marg (h).

@@ -1957,6 +1957,129 @@ __global__ __launch_bounds__(kConsumerThreads) void emission_nee_kernel(Emission
     }
 }
 
+// The weight of a scattered ray's hit on emitter `prim` under the balance heuristic (include/wfpt.h "Multiple importance sampling", in its
+// operation order: IEEE f32, no fma; tests/mis_ref.py restates it). o: the point the ray left (the previous diffuse hit), ph: the hit, d: the
+// ray's direction as shade scattered it, not normalised: d = n + r with |n| = |r| = 1, so the cosine of d against n is |d| / 2 and the
+// scatter's density cos / pi needs no normal. pl: the density with which the connect pass at o would have sampled ph (NEE steps 3 and 4
+// with q = ph), 0 where it cannot (A > 0, dist2 > 0 or cos_l > 0 fails, NaN included: the weight is 1 then).
+struct MisWeight {
+    float pl, pb, wb, cos_l;
+};
+__device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, const float4 *shade_rec, uint32_t prim_kind, uint32_t prim, float nf,
+                                                    float3_ o, float3_ ph, float3_ d) {
+    const float3_ v = {ph.x - o.x, ph.y - o.y, ph.z - o.z};
+    const float dist2 = dot3(v, v);
+    const float dist = sqrt_(dist2);
+    const float3_ w = {v.x / dist, v.y / dist, v.z / dist};
+    float3_ nl;
+    float area;
+    if (prim_kind == 0) {
+        const float4 g = prim_geom[prim]; // (centre, radius)
+        const float ra = __builtin_fabsf(g.w);
+        nl = {(ph.x - g.x) / ra, (ph.y - g.y) / ra, (ph.z - g.z) / ra};
+        area = (4.0f * kPi) * (ra * ra);
+    } else {
+        const float4 g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+        const float4 rec0 = shade_rec[3u * prim]; // the stored normalize(cross(e1, e2))
+        nl = {rec0.x, rec0.y, rec0.z};
+        const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
+        area = 0.5f * sqrt_(dot3(cr, cr));
+    }
+    MisWeight m;
+    m.cos_l = __builtin_fabsf(dot3(nl, w));
+    const float len = sqrt_(dot3(d, d));
+    m.pb = (0.5f * len) / kPi;
+    if (area > 0.0f && dist2 > 0.0f && m.cos_l > 0.0f) {
+        m.pl = dist2 / ((m.cos_l * area) * nf);
+        m.wb = m.pb / (m.pb + m.pl);
+    } else {
+        m.pl = 0.0f;
+        m.wb = 1.0f;
+    }
+    return m;
+}
+
+// The emission pass of a context that connects and weighs (WFPT_FLAG_MIS with an emitter; include/wfpt.h "Multiple importance sampling"):
+// emission_nee_kernel restated with one difference: where the pixel's connected flag is 1 the hit is not dropped but adds (thr * e) * wb
+// (mis_hit_weight, with the point the previous step's connect pass stored in `origin` and the direction the ray arrived with). A third
+// copy for emission_nee_kernel's reason. The extra loads happen per hit on an emitter after a diffuse bounce only.
+__global__ __launch_bounds__(kConsumerThreads) void emission_mis_kernel(EmissionArgs a, MisArgs mis) {
+    const uint32_t smp = blockIdx.y;
+    const Control *ctl = a.ctl + smp;
+    const bool records = a.rec_in != nullptr;
+    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
+    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
+    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
+    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
+    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
+    const float4 *origin = mis.origin + smp * static_cast<size_t>(a.batch.image_stride / 4u);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.in_hits[co + chunk];
+        const uint32_t base = a.in_hit_base[co + chunk];
+        if (base >= n) break; // bases ascend with the segment index
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n) break;
+            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
+            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
+            const uint32_t m_idx = a.prim_em[prim];
+            if (m_idx == kNoEmission) continue;
+            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
+                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
+                if (m > 2u) m = 0u;
+                if (m != a.material) continue;
+            }
+            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
+            const float4 e = a.em[m_idx];
+            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
+            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
+            const float4 thr = *px, had = *out;
+            if (had.w == 0.0f) {
+                *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
+            } else {
+                float3_ ph, d;
+                if (records) {
+                    const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
+                    ph = {ra.x, ra.y, ra.z};
+                    d = {rb.x, rb.y, rb.z};
+                } else {
+                    const float t = a.hq.t()[slot];
+                    const uint32_t ridx = a.hq.ridx()[slot];
+                    d = {q.dx()[ridx], q.dy()[ridx], q.dz()[ridx]};
+                    ph = {q.ox()[ridx] + t * d.x, q.oy()[ridx] + t * d.y, q.oz()[ridx] + t * d.z}; // sh:91
+                }
+                const float4 o = origin[lp];
+                const float wb = mis_hit_weight(mis.prim_geom, a.shade_rec, mis.prim_kind, prim, mis.nf, {o.x, o.y, o.z}, ph, d).wb;
+                *out = make_float4(had.x + (thr.x * e.x) * wb, had.y + (thr.y * e.y) * wb, had.z + (thr.z * e.z) * wb, had.w);
+            }
+            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+        }
+    }
+}
+
+// wfpt_mis_hit_weight: mis_hit_weight for caller rows (o.xyz, d.xyz, t, the primitive index as a float), one thread per row; a primitive
+// that does not emit or lies outside the scene (a NaN index included) answers (0, pb, 1, 0)
+__global__ __launch_bounds__(256) void mis_weight_kernel(MisArgs mis, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4,
+                                                         uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *row = in8 + 8u * static_cast<size_t>(i);
+    const float3_ o = {row[0], row[1], row[2]}, d = {row[3], row[4], row[5]};
+    const float t = row[6], pf = row[7];
+    const float3_ ph = {o.x + t * d.x, o.y + t * d.y, o.z + t * d.z}; // sh:91
+    MisWeight m;
+    if (pf >= 0.0f && pf < static_cast<float>(mis.n_prims) && prim_em[static_cast<uint32_t>(pf)] != kNoEmission) {
+        m = mis_hit_weight(mis.prim_geom, shade_rec, mis.prim_kind, static_cast<uint32_t>(pf), mis.nf, o, ph, d);
+    } else {
+        m.pl = 0.0f;
+        m.pb = (0.5f * sqrt_(dot3(d, d))) / kPi;
+        m.wb = 1.0f;
+        m.cos_l = 0.0f;
+    }
+    float *out = out4 + 4u * static_cast<size_t>(i);
+    out[0] = m.pl; out[1] = m.pb; out[2] = m.wb; out[3] = m.cos_l;
+}
+
 // shade (sh:56-156) of hit h of the previous wavefront, as the fused loop runs it: find the hit's path record (its
 // segment is the last one whose first hit is not after h, searched between the segments that hold the first hit of
 // this run of kChunk hits and of the next run: scan's first_seg table), multiply the pixel's throughput by the albedo
@@ -3198,8 +3321,9 @@ struct LightSample {
     float3_ q, w, e; // e: the light's emission colour at q (times its texture)
     float dist, G;
     uint32_t prim;
+    float pl, pb; // MIS only: the solid-angle densities of this sample under the light list's area sampling and under shade's scatter
 };
-template <int PRIM, bool TEX>
+template <int PRIM, bool TEX, bool MIS = false>
 __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, float3_ n, float u0, float u1, float u2, LightSample &s) {
     const float nl_f = static_cast<float>(a.n_lights);
     // (max_ first: a NaN or negative u0 of a caller's row picks light 0, and no float outside the u32 range is converted)
@@ -3234,6 +3358,10 @@ __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, fl
     s.w = {v.x / s.dist, v.y / s.dist, v.z / s.dist};
     const float cos_s = dot3(n, s.w), cos_l = __builtin_fabsf(dot3(nl, s.w));
     s.G = (((cos_s * cos_l) * area) * nl_f) / (kPi * dist2);
+    if (MIS) {
+        s.pb = cos_s / kPi;
+        s.pl = dist2 / ((cos_l * area) * nl_f);
+    }
     const float4 e = a.em[a.prim_em[prim]];
     s.e = {e.x, e.y, e.z};
     float3_ tc;
@@ -3298,7 +3426,10 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // ENVS (WFPT_FLAG_ENV_NEE contexts whose map has a distribution): a diffuse hit picks the map with probability `share` (sample_env; two more
 // draws; the shadow ray has no far end) and an emitter otherwise, each weighted by the inverse of its probability; the sampler form is the
 // map's alone. With ENVS false the kernel is the one of WFPT_FLAG_NEE.
-template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS>
+// MIS (WFPT_FLAG_MIS contexts with an emitter; never with ENVS): the sample is weighed by wl = pl / (pl + pb), and every diffuse hit stores
+// its point in a.origin for the next step's emission_mis_kernel (one 16-byte store next to the `emitted` update of the same pixel); the
+// sampler form answers 12 floats a row. With MIS false the source is the one above.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
     extern __shared__ float4 lds[];
     WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
@@ -3402,7 +3533,7 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
         LightSample s;
         bool lit = false, occluded = false;
         if (ENVS && to_env) lit = sample_env(a.envd, n, u1, u2, u3, u4, share, s);
-        else if (live) lit = sample_light<PRIM, TEX>(a, p, n, u0, u1, u2, s);
+        else if (live) lit = sample_light<PRIM, TEX, MIS>(a, p, n, u0, u1, u2, s);
         if (lit) {
 #if WFPT_STAMPS
             uint32_t dbg[3] = {0, 0, 0};
@@ -3425,7 +3556,26 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
                 occluded = verdict == kOccHit;
             }
         }
-        if (live && sampler) {
+        if (MIS && live && sampler) { // (q, primitive, (e_q G) wl, occluded, pl, pb, wl, 0): zeros where the sample contributes nothing
+            float *row = a.sample_out + 12u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
+            const float wl = lit ? s.pl / (s.pl + s.pb) : 0.0f; // (sample_light sets pl and pb only where it answers true)
+            row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
+            row[3] = static_cast<float>(s.prim);
+            row[4] = lit ? (s.e.x * s.G) * wl : 0.0f; row[5] = lit ? (s.e.y * s.G) * wl : 0.0f; row[6] = lit ? (s.e.z * s.G) * wl : 0.0f;
+            row[7] = occluded ? 1.0f : 0.0f;
+            row[8] = lit ? s.pl : 0.0f; row[9] = lit ? s.pb : 0.0f; row[10] = wl; row[11] = 0.0f;
+        } else if (MIS && live) {
+            const float4 thr = *px, had = *out;
+            const size_t lp4 = static_cast<size_t>(out - reinterpret_cast<float4 *>(a.emitted)); // the pixel's float4 in `emitted`: `origin` has its shape
+            a.origin[lp4] = make_float4(p.x, p.y, p.z, 0.0f);
+            if (lit && !occluded) {
+                const float wl = s.pl / (s.pl + s.pb);
+                *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) * wl, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) * wl,
+                                   had.z + (((thr.z * rec1.z) * s.e.z) * s.G) * wl, 1.0f);
+            } else {
+                out->w = 1.0f;
+            }
+        } else if (live && sampler) {
             float *row = a.sample_out + 8u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
             if (ENVS) s.q = s.w;
             row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
@@ -4166,12 +4316,20 @@ hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee) {
+hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee, const MisArgs *mis) {
     if (grid == 0) return hipSuccess;
-    if (nee)
+    if (nee && mis)
+        hipLaunchKernelGGL(emission_mis_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *mis);
+    else if (nee)
         hipLaunchKernelGGL(emission_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
     else
         hipLaunchKernelGGL(emission_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n);
     return hipGetLastError();
 }
 
@@ -4255,11 +4413,12 @@ hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvD
 
 namespace {
 using ConnectFn = void (*)(ConnectArgs);
-template <bool TEX, bool ENVS> struct ConnectK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS>; }
+template <bool TEX, bool ENVS, bool MIS = false> struct ConnectK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS, MIS>; }
 };
-ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = false) {
+ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = false, bool mis = false) {
     const bool lds = sc.lds_scene != 0;
+    if (mis) return tex ? pick_variant<ConnectK<true, false, true>>(sc, exact, lds) : pick_variant<ConnectK<false, false, true>>(sc, exact, lds);
     if (envs) return tex ? pick_variant<ConnectK<true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true>>(sc, exact, lds);
     return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
 }
@@ -4268,15 +4427,17 @@ ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = 
 hipError_t connect_prepare(const SceneDev &scene) {
     for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
         const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true),
-                                               connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true));
+                                               connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true),
+                                               connect_variant(scene, exact, false, false, true), connect_variant(scene, exact, true, false, true));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs) {
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis) {
     if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
-    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+    if (mis && (envs || !a.origin)) return hipErrorInvalidValue; // (a.origin: the plane, or the sampler form's rows out)
+    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }
 

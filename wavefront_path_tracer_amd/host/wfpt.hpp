@@ -397,6 +397,20 @@ class PathTracer {
         check(wfpt_sample_environment_light(ctx_, in10.data(), in10.size() / 10, out.data()));
         return out;
     }
+    // Multiple importance sampling (WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_MIS, include/wfpt.h "Multiple importance sampling"): emitter
+    // hits of scattered rays and the connect pass's shadow rays, both weighed by the balance heuristic.
+    // rows of (p.xyz, n.xyz, u0, u1, u2) -> rows of (q.xyz, light primitive, (e_q G) wl rgb, occluded, pl, pb, wl, 0)
+    std::vector<float> sample_lights_mis(const std::vector<float> &in9) {
+        std::vector<float> out(in9.size() / 9 * 12);
+        check(wfpt_sample_lights_mis(ctx_, in9.data(), in9.size() / 9, out.data()));
+        return out;
+    }
+    // rows of (o.xyz, d.xyz, t, primitive) -> rows of (pl, pb, wb, cos_l)
+    std::vector<float> mis_hit_weight(const std::vector<float> &in8) {
+        std::vector<float> out(in8.size() / 8 * 4);
+        check(wfpt_mis_hit_weight(ctx_, in8.data(), in8.size() / 8, out.data()));
+        return out;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
