@@ -706,3 +706,16 @@ def degenerate_radius_rays(W, spheres, n=256, seed=4):
         rays["inv_direction"] = (np.float32(1.0) / rays["direction"][:, :3]).astype("<f4")
     rays["pixel_idx"] = np.arange(n, dtype="<u4")
     return rays
+
+
+def assert_second_trips(W, pt, batch_with, batch_without):
+    """The premise of the second-trip tests, from the library's own numbers: `pt`'s segment count (its ray capacity over the segment size
+    wfpt_build_info reports) is above the workgroups a segment-walking pass launches per sample at `batch_with`, so some workgroup walks
+    a second segment, and within those at `batch_without`, so none does. The grid is consumer_grid's rule (csrc/wfpt_api.hip):
+    min(segments, max(64, ceil(8 CUs / batch)))."""
+    info = dict(kv.split("=") for kv in W.lib().wfpt_build_info().decode().split(";"))
+    segments = pt.ray_capacity // int(info["chunk"])
+    cus = W.device_info(0)["compute_units"]
+    grid = {b: min(segments, max(64, -(-cus * 8 // b))) for b in (batch_with, batch_without)}
+    assert segments > 64 and grid[batch_with] < segments == grid[batch_without], \
+        f"{segments} segments, {grid} workgroups per sample: the premise of this test is gone"

@@ -10,7 +10,7 @@ import denoise_ref as R
 import emission_ref as E
 import env_nee_ref as V
 import nee_ref as N
-from helpers import assert_bits_or_nan, make_oracle, make_tracer, simple_inputs
+from helpers import assert_bits_or_nan, assert_second_trips, make_oracle, make_tracer, simple_inputs
 from test_env_nee_host import maps
 from test_gpu_nee import assert_bits, bits, compare, light, mesh_inputs, mesh_tracer, sphere_tracer
 
@@ -154,6 +154,21 @@ def test_same_bits_across_batches_and_loops(W, O):
         else:
             assert_bits(got, base, f"loop {loop} batch {batch}")
         pt.close()
+
+
+def test_second_trips_through_the_segment_loop(W, O):
+    """68 segments: at batch 128 the miss launches (and the stage loop's emission pass) run 64 workgroups per sample, so four of them walk
+    a second segment; at batch 16 they run 68 and none does. Same bits, and the stage loop's at batch 128 as well."""
+    w, h, spp = 256, 136, 128
+    got = {}
+    for loop, batch in (("", 128), ("", 16), ("UNFUSED", 128)):
+        pt = lamp_scene(W, O, w, h, rng_mode=W.RNG_PIXEL, flags=flags_of(W, loop), batch=batch)
+        assert_second_trips(W, pt, 128, 16)
+        pt.render(spp)
+        got[loop, batch] = pt.accumulated()
+        pt.close()
+    assert_bits(got["", 128], got["", 16], "batch 128 against batch 16")
+    assert_bits(got["UNFUSED", 128], got["", 128], "the stage loop against the fused one, batch 128")
 
 
 def test_stage_loops_equal_render(W, O):

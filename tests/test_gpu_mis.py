@@ -10,7 +10,7 @@ import emission_ref as E
 import mis_ref as M
 import nee_ref as N
 import texture_ref as T
-from helpers import closed_room_inputs, make_oracle
+from helpers import assert_second_trips, closed_room_inputs, make_oracle
 from mis_ref import NEAR
 from nee_ref import LAMP
 from test_gpu_nee import (assert_bits, bits, compare, lamp_tracer, light, mesh_inputs, mesh_tracer, random_tex, sampler_rows, shirley_scene,
@@ -212,6 +212,25 @@ def test_same_bits_across_batches_stage_loops_and_shards(W, O):
             y0 = (j * 2 + r) * 8
             full[y0:y0 + 8] = b[j][:max(0, min(8, h - y0))]
     assert_bits(full.reshape(-1, 3), base, "two band-sharded contexts")
+
+
+def test_second_trips_through_the_segment_loop(W, O):
+    """68 segments: at batch 128 the texture and emission passes launch 64 workgroups per sample, so four of them walk a second segment;
+    at batch 16 they launch 68 and none does. Same bits."""
+    w, h, spp = 256, 136, 128
+    _, _, colours = shirley_scene(O)
+    lamps = sorted(colours)
+    got = {}
+    for batch in (128, 16):
+        pt = W.shirley_path_tracer(w, h, max_wavefronts=5, miss_floor=0, rng_mode=W.RNG_PIXEL, flags=flags_of(W, "TEXTURES"), batch=batch)
+        assert_second_trips(W, pt, 128, 16)
+        pt.set_texture(0, random_tex(64, 32, 1), scale=(3.0, 2.0), offset=(0.25, -0.5))
+        light(pt, colours)
+        pt.bind_texture(lamps[0], 0)
+        pt.render(spp)
+        got[batch] = pt.accumulated()
+        pt.close()
+    assert_bits(got[128], got[16], "batch 128 against batch 16")
 
 
 @pytest.mark.parametrize("three", [False, True])

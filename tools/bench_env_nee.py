@@ -7,8 +7,9 @@ sphere of directions, 50 000 times brighter):
   shirley:off      WFPT_FLAG_ENVIRONMENT | EMISSION | NEE, no emitter: the flag off
   shirley:env      WFPT_FLAG_ENVIRONMENT only
   shirley:env_nee  the three flags | WFPT_FLAG_ENV_NEE
-and, with --parent-tree DIR (a checkout of the parent commit with its library built), shirley:off in that tree: the kernels a context
-without the flag launches are the parent's, so the two are expected to agree within the spread reported here.
+and, with --parent-tree DIR (a checkout of the parent commit with its library built), every leg once more in that tree, named
+`<leg>@parent` and run right after its twin: the kernels a context without the flag launches are the parent's, so the off pair is
+expected to agree within the spread reported here, and the other pairs say what a change to the feature's own kernels costs.
 
 Method (tools/bench_nee.py's): every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that
 drift hits them alike. A child warms up, then times --frames frames one by one, each ending in a device synchronise. A leg's figure is
@@ -98,7 +99,7 @@ def main():
         return leg(a)
     legs = [("shirley:off", ROOT), ("shirley:env", ROOT), ("shirley:env_nee", ROOT)]
     if a.parent_tree:
-        legs.insert(1, ("shirley:off@parent", os.path.abspath(a.parent_tree)))
+        legs = [x for name, tree in legs for x in ((name, tree), (name + "@parent", os.path.abspath(a.parent_tree)))]
     results = {name: {"rounds": [], "last": None} for name, _ in legs}
     for _ in range(a.rounds):
         for name, tree in legs:
@@ -127,7 +128,8 @@ def main():
         summary[name] = line
         print(json.dumps(line), flush=True)
     rel = {}
-    for name, base in (("shirley:off", "shirley:off@parent"), ("shirley:off", "shirley:env"), ("shirley:env_nee", "shirley:env")):
+    twins = [(name, name + "@parent") for name, _ in legs if not name.endswith("@parent")]
+    for name, base in twins + [("shirley:off", "shirley:env"), ("shirley:env_nee", "shirley:env")]:
         if name in summary and base in summary:
             rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
     if "variance_sum" in summary.get("shirley:env_nee", {}) and "variance_sum" in summary.get("shirley:env", {}):

@@ -5,8 +5,9 @@ Legs, --spp samples per frame: `plain` no flag, `lit` WFPT_FLAG_EMISSION, `nee` 
   shirley  plain | lit | nee | mis   (the three big spheres emit)                          at --width x --height
   lamp     lit | nee | mis           (section 9h's small, far emitting sphere over a large Lambertian one, black map, miss_floor = 0)
   near     lit | nee | mis           (the near-lamp scene of the tests: radius 1, a gap of 0.05 to the radius-1000 ground)
-and, with --parent-tree DIR (a checkout of the parent commit with its library built), the plain Shirley frame of that tree: the kernels a
-context without the flag launches are the parent's, so the two are expected to be equal within the spread reported here.
+and, with --parent-tree DIR (a checkout of the parent commit with its library built), every leg once more in that tree, named
+`<leg>@parent` and run right after its twin: the kernels a context without the flag launches are the parent's, so the plain pair is
+expected to be equal within the spread reported here, and the other pairs say what a change to the feature's own kernels costs.
 
 Method: tools/bench_nee.py's. Every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that drift
 hits them alike. A child warms up (graph capture, first touch), then times --frames frames one by one, each ending in a device
@@ -95,11 +96,11 @@ def main():
     legs = []
     if "shirley" in a.scenes:
         legs += [("shirley:plain", ROOT), ("shirley:lit", ROOT), ("shirley:nee", ROOT), ("shirley:mis", ROOT)]
-        if a.parent_tree:
-            legs.insert(1, ("shirley:plain@parent", os.path.abspath(a.parent_tree)))
     for scene in ("lamp", "near"):
         if scene in a.scenes:
             legs += [(f"{scene}:lit", ROOT), (f"{scene}:nee", ROOT), (f"{scene}:mis", ROOT)]
+    if a.parent_tree:
+        legs = [x for name, tree in legs for x in ((name, tree), (name + "@parent", os.path.abspath(a.parent_tree)))]
     results = {name: {"rounds": [], "last": None} for name, _ in legs}
     for _ in range(a.rounds):
         for name, tree in legs:
@@ -128,8 +129,9 @@ def main():
         summary[name] = line
         print(json.dumps(line), flush=True)
     rel = {}
-    for name, base in (("shirley:lit", "shirley:plain"), ("shirley:nee", "shirley:lit"), ("shirley:mis", "shirley:nee"), ("lamp:mis", "lamp:nee"),
-                       ("near:mis", "near:nee"), ("near:mis", "near:lit"), ("shirley:plain", "shirley:plain@parent")):
+    twins = [(name, name + "@parent") for name, _ in legs if not name.endswith("@parent")]
+    for name, base in [("shirley:lit", "shirley:plain"), ("shirley:nee", "shirley:lit"), ("shirley:mis", "shirley:nee"), ("lamp:mis", "lamp:nee"),
+                       ("near:mis", "near:nee"), ("near:mis", "near:lit")] + twins:
         if name in summary and base in summary:
             rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
             if "variance_sum" in summary[name] and "variance_sum" in summary[base]:  # equal time: variance x frame time, MIS over the base

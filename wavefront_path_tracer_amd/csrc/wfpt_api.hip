@@ -567,64 +567,42 @@ MissArgs fused_miss_args(wfpt_ctx *c, int parity, uint32_t nb) { // miss_kernel 
 // a material is bound to a texture: the texture passes run before the shade steps and the AOV kernel takes the textured variant
 bool textured(const wfpt_ctx *c) { return c->tex_prim.get() != nullptr; }
 TexScene tex_scene(const wfpt_ctx *c) { return TexScene{c->tex_prim.get(), c->tex_desc.get(), c->tex_uv.get()}; }
-// the texture pass before a shade step: over the fused loops' path records of wavefront `parity` (parity >= 0), or over the stage queues
-// (parity < 0: hit queue, ray queue qi, *n_hits capped at limit, material class `material` or all)
-TextureArgs texture_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
-                         uint32_t material = 0xffffffffu) {
-    TextureArgs a{};
-    a.batch = batch_of(c, nb);
+// the hits a shade step will shade, for the passes that precede it: the fused loops' path records of wavefront `parity` (parity >= 0), or
+// the stage queues (parity < 0: hit queue, ray queue qi, *n_hits capped at limit, material class `material` or all)
+HitWalk hit_walk(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
+                 uint32_t material = 0xffffffffu) {
+    HitWalk w{};
+    w.batch = batch_of(c, nb);
     if (parity >= 0) {
-        a.rec_in = c->rec_mem[parity].get();
-        a.in_hits = c->f_chunk_hits[parity].get();
+        w.rec_in = c->rec_mem[parity].get();
+        w.in_hits = c->f_chunk_hits[parity].get();
     } else {
-        a.in_hits = c->chunk_hits.get();
-        a.q = c->q[qi];
-        a.hq = c->hq;
-        a.n_hits = n_hits;
-        a.limit = std::min(limit, c->capacity);
+        w.in_hits = c->chunk_hits.get();
+        w.q = c->q[qi];
+        w.hq = c->hq;
+        w.n_hits = n_hits;
+        w.limit = std::min(limit, c->capacity);
     }
-    a.in_hit_base = c->chunk_hit_base.get();
-    a.material = material;
-    a.capacity = c->capacity;
-    a.image = c->image.get();
-    a.ctl = c->ctl.get();
-    a.image_width = c->width;
-    a.tile = c->tile;
-    a.prim_geom = c->scene.prim_geom;
-    a.shade_rec = c->scene.shade_rec;
-    a.prim_kind = c->scene.prim_kind;
-    a.ts = tex_scene(c);
-    return a;
+    w.in_hit_base = c->chunk_hit_base.get();
+    w.material = material;
+    w.capacity = c->capacity;
+    w.image = c->image.get();
+    w.ctl = c->ctl.get();
+    w.image_width = c->width;
+    w.tile = c->tile;
+    w.shade_rec = c->scene.shade_rec;
+    return w;
 }
+TextureArgs texture_args(wfpt_ctx *c, const HitWalk &w) { return TextureArgs{w, c->scene.prim_geom, c->scene.prim_kind, tex_scene(c)}; }
 // The texture launches' entry in an event record (not a wfpt_stage, like the AOV launch's): booked into wfpt_ctx::tex_ms
 constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
 
 // a material emits: the emission passes run before the shade steps (after their texture passes) and accumulate takes the second plane
 bool emitting(const wfpt_ctx *c) { return c->em_prim.get() != nullptr; }
-// the emission pass before a shade step: the hits texture_args names, in its two forms
-EmissionArgs emission_args(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
-                           uint32_t material = 0xffffffffu) {
-    const TextureArgs t = texture_args(c, parity, nb, qi, n_hits, limit, material);
-    EmissionArgs a{};
-    a.batch = t.batch;
-    a.rec_in = t.rec_in;
-    a.in_hits = t.in_hits;
-    a.in_hit_base = t.in_hit_base;
-    a.q = t.q;
-    a.hq = t.hq;
-    a.n_hits = t.n_hits;
-    a.limit = t.limit;
-    a.material = t.material;
-    a.capacity = t.capacity;
-    a.image = t.image;
-    a.emitted = c->emitted.get();
-    a.ctl = t.ctl;
-    a.image_width = t.image_width;
-    a.tile = t.tile;
-    a.shade_rec = t.shade_rec;
-    a.prim_em = c->em_prim.get();
-    a.em = c->em_mat.get();
-    return a;
+// (the last four fields: the weighing kind's alone)
+EmissionArgs emission_args(wfpt_ctx *c, const HitWalk &w) {
+    return EmissionArgs{w, c->emitted.get(), c->em_prim.get(), c->em_mat.get(), c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind,
+                        static_cast<float>(c->n_lights)};
 }
 // The emission launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::em_ms
 constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
@@ -639,50 +617,39 @@ bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c); 
 // a WFPT_FLAG_MIS context holds an emitter (never with a map's distribution: the flag excludes WFPT_FLAG_ENV_NEE): the connect and
 // emission passes are the MIS variants
 bool weighing(const wfpt_ctx *c) { return c->mis_origin.get() != nullptr && c->n_lights > 0; }
-MisArgs mis_args(const wfpt_ctx *c) {
-    return MisArgs{c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
-}
-// the connect pass before a shade step of wavefront `wavefront`: the hits emission_args names, in its two forms
-ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, int parity, uint32_t nb, int qi = 0, const uint32_t *n_hits = nullptr, uint32_t limit = 0,
-                         uint32_t material = 0xffffffffu) {
-    const EmissionArgs e = emission_args(c, parity, nb, qi, n_hits, limit, material);
+// the connect pass before a shade step of wavefront `wavefront`
+ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w) {
     ConnectArgs a{};
-    a.batch = e.batch;
-    a.rec_in = e.rec_in;
-    a.in_hits = e.in_hits;
-    a.in_hit_base = e.in_hit_base;
-    a.q = e.q;
-    a.hq = e.hq;
-    a.n_hits = e.n_hits;
-    a.limit = e.limit;
-    a.material = e.material;
-    a.capacity = e.capacity;
-    a.image = e.image;
-    a.emitted = e.emitted;
-    a.ctl = e.ctl;
-    a.image_width = e.image_width;
-    a.tile = e.tile;
+    a.w = w;
+    a.emitted = c->emitted.get();
     a.n_chunks_max = c->n_chunks_max;
     a.wavefront = wavefront;
-    a.prim_em = e.prim_em;
-    a.em = e.em;
+    a.prim_em = c->em_prim.get();
+    a.em = c->em_mat.get();
     a.lights = c->nee_lights.get();
     a.n_lights = c->n_lights;
+    a.origin = c->mis_origin.get();
     a.ts = tex_scene(c);
     a.scene = c->scene;
-    if (weighing(c)) a.origin = c->mis_origin.get(); // (shares sample_out's slot: the sampler calls set that one after this)
     if (env_connecting(c)) // the effective share: 1 while there is no light to pick instead
         a.envd = EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f};
+    return a;
+}
+// the sampler form of the connect pass (no hits: the caller's rows)
+ConnectArgs sampler_args(wfpt_ctx *c, const float *in, float *out, size_t n) {
+    ConnectArgs a = connect_args(c, 0, hit_walk(c, -1, 1));
+    a.sample_in = in;
+    a.sample_out = out;
+    a.sample_n = static_cast<uint32_t>(n);
     return a;
 }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
     return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c));
 }
-// the emission pass of the context's kind: emission_kernel, its connecting twin or its weighing one
+// the emission pass of the context's kind
 hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
-    const MisArgs m = mis_args(c);
-    return launch_emission(a, grid, c->stream.get(), connecting(c), weighing(c) ? &m : nullptr);
+    return launch_emission(a, !connecting(c) ? kEmitAll : weighing(c) ? kEmitWeighed : kEmitGated, grid, c->stream.get());
 }
 // the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
 const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
@@ -740,6 +707,19 @@ struct EventRec { int stage; hipEvent_t start, stop; };
 // The wavefront chain of a batch up to (not including) accumulate, one function per loop (loop_of). `timed(stage, launch)` runs a launch
 // and records its events.
 
+// The passes that precede a shade step of wavefront b over the hits `w` names, each where the context has it: the texture pass; the
+// emission pass after it (a textured emitter's light is (thr * tex) * e); the connect pass after that, which the emission pass must not
+// see (it reads the flag the previous step's connect pass left). In the loops they follow the scan that decides whether the loop goes on
+// (shade_n = 0 once it has exited), as the shade they precede.
+template <typename Timed>
+int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const HitWalk &w) {
+    const uint32_t grid = consumer_grid(c, nb);
+    if (textured(c)) WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
+    if (emitting(c)) WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
+    if (connecting(c)) WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, w), nb); }));
+    return WFPT_OK;
+}
+
 // WFPT_LOOP_STAGES: generate | (extend | scan | shade | miss) x max_wavefronts, the reference's stages one by one
 template <typename Timed>
 int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
@@ -753,18 +733,8 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      return launch_extend(extend_args(c, qi, &c->ctl.get()->n_in, c->capacity, nb, split), extend_grid(c, nb), st, env != nullptr);
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), st); }));
-        if (textured(c))
-            WFPT_HIP(c, timed(kStageTexture, [&] {
-                         return launch_texture(texture_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb), st);
-                     }));
-        if (emitting(c))
-            WFPT_HIP(c, timed(kStageEmission, [&] {
-                         return launch_emission_pass(c, emission_args(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), consumer_grid(c, nb));
-                     }));
-        if (connecting(c))
-            WFPT_HIP(c, timed(kStageConnect, [&] {
-                         return launch_connect_pass(c, connect_args(c, b, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity), nb);
-                     }));
+        const HitWalk w = hit_walk(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity);
+        if (int r = enqueue_pre_shade(c, timed, b, nb, w); r != WFPT_OK) return r;
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
                      ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
@@ -792,12 +762,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const bool last = b + 1 >= c->p.max_wavefronts;
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
-        if (textured(c)) // after the scan that decides whether the loop goes on (shade_n = 0 once it has exited), as the shade it precedes
-            WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
-        if (emitting(c)) // after the texture pass: a textured emitter's light is (thr * tex) * e
-            WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
-        if (connecting(c)) // after the emission pass, which reads the flag the previous step's connect pass left
-            WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
+        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
                  }));
@@ -840,25 +805,14 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const int par = static_cast<int>(b & 1u);
         WFPT_HIP(c, timed(WFPT_STAGE_COMPACT, [&] { return launch_compact(compact_args(c, par, nb), c->n_chunks_max, st, env != nullptr); }));
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
-        if (b + 1 < c->p.max_wavefronts) {
+        const bool last = b + 1 >= c->p.max_wavefronts;
+        if (!last || env) // (the last launch's miss items: a launch of their own only with the map)
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
-            if (textured(c))
-                WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
-            if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
-            if (connecting(c))
-                WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
+        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
+        if (!last) {
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
         } else {
-            if (env) // the last launch's miss items, as a launch of their own with the map
-                WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
-            if (textured(c))
-                WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, par, nb), consumer_grid(c, nb), st); }));
-            if (emitting(c))
-                WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, par, nb), consumer_grid(c, nb)); }));
-            if (connecting(c))
-                WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, par, nb), nb); }));
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
                               [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
         }
@@ -1915,33 +1869,18 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         c->hit_rec_valid = true; // shade may stream extend's path records until the host touches the ray queue (generate_rays, write, swap, clear)
         break;
     case WFPT_STAGE_SHADE:
-        if (textured(c))
-            WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1), c->stream.get()));
-        if (emitting(c))
-            WFPT_HIP(c, launch_emission_pass(c, emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads), consumer_grid(c, 1)));
-        if (connecting(c))
-            WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads), 1));
-        WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx, 0xffffffffu, true),
-                                 consumer_grid(c, 1), c->stream.get()));
-        break;
     case WFPT_STAGE_SHADE_LAMBERTIAN:
     case WFPT_STAGE_SHADE_METAL:
-    case WFPT_STAGE_SHADE_DIELECTRIC:
-        if (textured(c))
-            WFPT_HIP(c, launch_texture(texture_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
-                                                    static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
-                                       consumer_grid(c, 1), c->stream.get()));
-        if (emitting(c))
-            WFPT_HIP(c, launch_emission_pass(c, emission_args(c, -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
-                                                           static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)),
-                                             consumer_grid(c, 1)));
-        if (connecting(c)) // the Lambertian stage connects, the other two only clear the pixels' connected flags
-            WFPT_HIP(c, launch_connect_pass(c, connect_args(c, stage_wavefront(c), -1, 1, c->cur, &c->ctl.get()->counters[1], threads,
-                                                            static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN)), 1));
-        WFPT_HIP(c, launch_shade(shade_args(c, c->cur, &c->ctl.get()->counters[1], threads, gx,
-                                            static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN), true),
-                                 consumer_grid(c, 1), c->stream.get()));
+    case WFPT_STAGE_SHADE_DIELECTRIC: {
+        // one material class (its connect pass: the Lambertian stage connects, the other two only clear the pixels' connected flags) or all
+        const uint32_t material = stage == WFPT_STAGE_SHADE ? 0xffffffffu : static_cast<uint32_t>(stage - WFPT_STAGE_SHADE_LAMBERTIAN);
+        auto untimed = [](int, auto &&launch) { return launch(); };
+        const uint32_t *n_hits = &c->ctl.get()->counters[1];
+        if (int r = enqueue_pre_shade(c, untimed, stage_wavefront(c), 1, hit_walk(c, -1, 1, c->cur, n_hits, threads, material)); r != WFPT_OK)
+            return r;
+        WFPT_HIP(c, launch_shade(shade_args(c, c->cur, n_hits, threads, gx, material, true), consumer_grid(c, 1), c->stream.get()));
         break;
+    }
     case WFPT_STAGE_MISS:
         WFPT_HIP(c, launch_miss(miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1), c->stream.get(), env_of(c), miss_gate(c)));
         break;
@@ -3246,10 +3185,7 @@ int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (e == hipSuccess) e = d_out.alloc(8 * n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
     if (e == hipSuccess) {
-        ConnectArgs a = connect_args(c, 0, -1, 1);
-        a.sample_in = d_in.get();
-        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
-        a.sample_n = static_cast<uint32_t>(n);
+        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
         const uint64_t items = (n + kChunk - 1) / kChunk;
         e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
                            textured(c));
@@ -3279,10 +3215,7 @@ int wfpt_sample_lights_mis(wfpt_ctx *c, const float *in9, size_t n, float *out12
     if (e == hipSuccess) e = d_out.alloc(12 * n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
     if (e == hipSuccess) {
-        ConnectArgs a = connect_args(c, 0, -1, 1);
-        a.sample_in = d_in.get();
-        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
-        a.sample_n = static_cast<uint32_t>(n);
+        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
         const uint64_t items = (n + kChunk - 1) / kChunk;
         e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
                            textured(c), false, true);
@@ -3303,8 +3236,9 @@ int wfpt_mis_hit_weight(wfpt_ctx *c, const float *in8, size_t n, float *out4) {
     hipError_t e = d_in.alloc(8 * n);
     if (e == hipSuccess) e = d_out.alloc(4 * n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in8, sizeof(float) * 8 * n, hipMemcpyHostToDevice, c->stream.get());
+    const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
     if (e == hipSuccess)
-        e = launch_mis_weight(mis_args(c), c->scene.shade_rec, c->em_prim.get(), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
+        e = launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
     if (e == hipSuccess) e = hipMemcpyAsync(out4, d_out.get(), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
     if (e != hipSuccess) return hip_fail(c, e, "wfpt_mis_hit_weight");
@@ -3355,11 +3289,8 @@ int wfpt_sample_environment_light(wfpt_ctx *c, const float *in10, size_t n, floa
     if (e == hipSuccess) e = d_out.alloc(8 * n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in10, sizeof(float) * 10 * n, hipMemcpyHostToDevice, c->stream.get());
     if (e == hipSuccess) {
-        ConnectArgs a = connect_args(c, 0, -1, 1);
+        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
         a.envd.share = 1.0f; // the environment branch alone
-        a.sample_in = d_in.get();
-        a.sample_out = d_out.get(); // (replaces connect_args' `origin` in the slot they share: the sampler form stores no hit point)
-        a.sample_n = static_cast<uint32_t>(n);
         const uint64_t items = (n + kChunk - 1) / kChunk;
         e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
                            textured(c), true);

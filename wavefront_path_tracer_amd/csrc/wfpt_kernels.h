@@ -390,14 +390,14 @@ struct MissArgs {
     Tiling tile;
 };
 
-// The texture pass (texture_kernel): before a shade step, the throughput of every hit that step will shade is multiplied by the texture of
-// the primitive hit, so that shade's own `*= albedo` makes (thr * tex) * albedo. Two forms, as the shade steps read their hits:
+// The hits a shade step will shade, as the passes that precede the step walk them (for_each_shaded_hit). Two forms, as the shade steps read
+// their hits:
 //   records (rec_in != null): the fused loops' path records of the previous wavefront -- segment c holds in_hits[c] records, its first one
 //            shade's hit in_hit_base[c]; the hits shaded are h < ctl->shade_n (0 once the loop has exited), as bounce_kernel and
 //            shade_rays_kernel shade them;
 //   queues  (rec_in == null): shade_kernel's hit queue (t, primitive, ray index) and ray queue: hits h < min(*n_hits, limit), of material
 //            class `material` only unless it is 0xffffffff (the per-material shade stages).
-struct TextureArgs {
+struct HitWalk {
     Batch batch;
     const float4 *rec_in;
     const uint32_t *in_hits, *in_hit_base;
@@ -411,38 +411,43 @@ struct TextureArgs {
     const Control *ctl;
     uint32_t image_width;
     Tiling tile;
+    const float4 *shade_rec;  // spheres: the centre; the material class (the per-material shade stages' filter)
+};
+
+// The texture pass (texture_kernel): before a shade step, the throughput of every hit that step will shade is multiplied by the texture of
+// the primitive hit, so that shade's own `*= albedo` makes (thr * tex) * albedo.
+struct TextureArgs {
+    HitWalk w;
     const float4 *prim_geom;  // triangles: the wfpt_triangle array (v0, e1, e2)
-    const float4 *shade_rec;  // spheres: the centre; the material class
     uint32_t prim_kind;
     TexScene ts;
 };
 
 // The emission pass (emission_kernel; WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): before a shade step -- and after that step's texture
 // pass -- every hit the step will shade that lies on an emitter adds thr * e to the pixel's `emitted` and leaves thr = +0 (one multiply and
-// one add per channel, no fma); shade then scatters the dead path as any other. It visits the hits exactly as texture_kernel does (the
-// records and queues forms of TextureArgs, the same per-material class filter) but reads no hit point: the pixel and the primitive only.
+// one add per channel, no fma); shade then scatters the dead path as any other. It reads no hit point: the pixel and the primitive only.
 // The table: prim_em[primitive] is the primitive's material_idx when that material emits and kNoEmission otherwise, in the order the
 // device holds the primitives, and em[material_idx] its colour (w unused). An index per primitive rather than a float4: the pass reads
 // 4 bytes for every hit and the colour for emitter hits only, out of a table of a few materials that stays in cache.
+// The kernel's three kinds (launch_emission):
+//   kEmitAll:     the contexts that do not connect;
+//   kEmitGated:   the contexts that connect (WFPT_FLAG_NEE with an emitter, or WFPT_FLAG_ENV_NEE): thr * e is added only where the pixel's
+//                 connected flag (emitted.w, set by the previous step's connect pass) is 0 -- after a diffuse bounce the connect pass
+//                 has already counted this light;
+//   kEmitWeighed: the contexts that connect and weigh (WFPT_FLAG_MIS with an emitter): where the flag is 1 the hit is not dropped but adds
+//                 (thr * e) * wb (mis_hit_weight: the distance comes from `origin`, the scatter's density from the length of the ray's
+//                 direction). The extra loads happen per hit on an emitter after a diffuse bounce only. The last four fields are its alone.
 constexpr uint32_t kNoEmission = 0xffffffffu;
+enum EmissionKind : int { kEmitAll, kEmitGated, kEmitWeighed };
 struct EmissionArgs {
-    Batch batch;
-    const float4 *rec_in;
-    const uint32_t *in_hits, *in_hit_base;
-    RayQueue q;
-    HitQueue hq;
-    const uint32_t *n_hits;
-    uint32_t limit;
-    uint32_t material;
-    uint32_t capacity;
-    float *image;
+    HitWalk w;
     float *emitted;           // the second per-sample plane: image's shape and strides
-    const Control *ctl;
-    uint32_t image_width;
-    Tiling tile;
-    const float4 *shade_rec;  // the material class (the per-material shade stages' filter)
     const uint32_t *prim_em;
     const float4 *em;
+    const float4 *prim_geom;
+    const float4 *origin;     // the hit points the previous step's MIS connect pass stored: `emitted`'s shape and strides
+    uint32_t prim_kind;
+    float nf;                 // f32(n_lights)
 };
 
 // The environment map as a light (WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment next-event estimation"): the map and its sampling
@@ -459,29 +464,21 @@ struct EnvDist {
 // The connect pass (connect_kernel; WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): before a shade step, after that step's texture
 // and emission passes, every hit the step will shade either sends one shadow ray to a sampled point of a light and adds the unoccluded
 // sample to the pixel's `emitted` (a diffuse hit: the pixel's connected flag, emitted.w, becomes 1) or only clears the flag (every other
-// hit). It visits the hits as emission_kernel does (both forms, the same class filter) and traces with the context's own walk
-// (WFPT_TRACE_ANY), so it carries the scene like the other tracing kernels. `lights`: the primitives whose material emits, in primitive
-// order. `wavefront`: the index b of the wavefront whose hits these are (the key of the pass's own random stream).
+// hit). It traces with the context's own walk (WFPT_TRACE_ANY), so it carries the scene like the other tracing kernels. `lights`: the
+// primitives whose material emits, in primitive order. `wavefront`: the index b of the wavefront whose hits these are (the key of the
+// pass's own random stream).
 // The sampler form (sample_in != null; wfpt_sample_lights): sample_n rows of (point, normal, u0 u1 u2) instead of hits, one row of
 // (q, light primitive, e_q G, occluded) each out; nothing else is read or written.
 // The ENVS variants (launch_connect's `envs`; WFPT_FLAG_ENV_NEE contexts whose map has a distribution): a diffuse hit picks the map with
 // probability envd.share (always, when n_lights is 0: prim_em may be null then) and an emitter otherwise; their sampler form
 // (wfpt_sample_environment_light) takes rows of (point, normal, u1 u2 u3 u4) and answers (wdir, texel, e Genv, occluded) for the map alone.
+// The MIS variants (WFPT_FLAG_MIS with an emitter; include/wfpt.h "Multiple importance sampling"): the balance heuristic between shade's
+// cosine scatter and the connect pass's area sampling. They weigh their sample by wl and store the hit point of every diffuse hit in
+// `origin` (one float4 per pixel per sample in flight, never zeroed: read only where the connected flag is 1, which the same lane set
+// with it) for the next step's kEmitWeighed emission pass; their sampler form answers 12 floats a row (wfpt_sample_lights_mis).
 struct ConnectArgs {
-    Batch batch;
-    const float4 *rec_in;
-    const uint32_t *in_hits, *in_hit_base;
-    RayQueue q;
-    HitQueue hq;
-    const uint32_t *n_hits;
-    uint32_t limit;
-    uint32_t material;
-    uint32_t capacity;
-    float *image;
+    HitWalk w;
     float *emitted;
-    const Control *ctl;
-    uint32_t image_width;
-    Tiling tile;
     uint32_t n_chunks_max;    // segments per sample: the work items are (sample, segment) pairs, sample-major
     uint32_t wavefront;
     const uint32_t *prim_em;
@@ -489,29 +486,17 @@ struct ConnectArgs {
     const uint32_t *lights;
     uint32_t n_lights;
     const float *sample_in;
-    union {                   // (one slot: the struct, and with it the kernels of contexts without WFPT_FLAG_MIS, stays as it was)
-        float *sample_out;    // the sampler form: the rows out
-        float4 *origin;       // the MIS variants' render form: the hit points of the diffuse hits, `emitted`'s shape and strides (MisArgs)
-    };
+    float *sample_out;        // the sampler form: the rows out
     uint32_t sample_n;
+    float4 *origin;           // the MIS variants' render form: the hit points of the diffuse hits, `emitted`'s shape and strides
     TexScene ts;              // the textures of the lights (the TEX variants only)
     SceneDev scene;
     EnvDist envd;             // the map as a light (the ENVS variants only; below)
 };
-// sample_out and origin alias: a sampler call on a WFPT_FLAG_MIS context gets `origin` from connect_args and must set sample_out after it
-// (the sampler form never reads `origin`, the render form never sample_out: sample_n tells them apart)
-static_assert(sizeof(float *) == sizeof(float4 *), "ConnectArgs: sample_out and origin share one slot");
 
-// Multiple importance sampling (WFPT_FLAG_MIS with an emitter; include/wfpt.h "Multiple importance sampling"): the balance heuristic
-// between shade's cosine scatter and the connect pass's area sampling. The MIS connect variants weigh their sample by wl and store the
-// hit point of every diffuse hit in `origin` (one float4 per pixel per sample in flight, never zeroed: read only where the connected
-// flag is 1, which the same lane set with it). emission_mis_kernel weighs a hit on an emitter whose pixel's flag is 1 by wb
-// (mis_hit_weight: the distance comes from `origin`, the scatter's density from the length of the ray's direction) instead of dropping it.
-// The sampler forms: the connect variants answer 12 floats a row (wfpt_sample_lights_mis), mis_weight_kernel runs mis_hit_weight on rows
-// of (o, d, t, primitive) (wfpt_mis_hit_weight).
+// wfpt_mis_hit_weight (mis_weight_kernel): mis_hit_weight on caller rows of (o, d, t, primitive)
 struct MisArgs {
     const float4 *prim_geom;
-    const float4 *origin;
     uint32_t prim_kind;
     uint32_t n_prims;
     float nf;                 // f32(n_lights)
@@ -649,9 +634,7 @@ hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 // where the pixel's connected flag (emitted.w) is 1
 hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const float *connected = nullptr);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
-// nee: the variant of contexts that connect (WFPT_FLAG_NEE with an emitter): adds thr * e only where the pixel's connected flag is 0
-// mis: emission_mis_kernel (the same contexts with WFPT_FLAG_MIS): a hit whose pixel's flag is 1 adds (thr * e) * wb
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee = false, const MisArgs *mis = nullptr);
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s);
 // wfpt_mis_hit_weight: n rows of (o.xyz, d.xyz, t, primitive) -> (pl, pb, wb, cos_l), one thread per row
 hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s);
 // grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture

@@ -1769,7 +1769,8 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_env_kernel(MissArgs a, 
 // The miss pass of a context that connects to its map (WFPT_FLAG_ENV_NEE with a distribution; include/wfpt.h "Environment next-event
 // estimation"): miss_body<true> restated with one difference: where the pixel's connected flag (emitted.w, set by the connect pass of the
 // step that scattered this ray) is 1 the throughput becomes +0 -- the connect pass has already counted the map -- and the map is not read.
-// A copy for emission_nee_kernel's reason: miss_env_kernel keeps its instructions. (A change to miss_body belongs here too.)
+// Its own kernel, not a miss_body<ENV, GATED>: the gate sits before the direction is read, so the walk is not pipelined, and folded into
+// miss_body it took more registers than this form.
 __global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs a, EnvDev env, const float *emitted) {
     const uint32_t sample = blockIdx.y;
     a.ctl += sample;
@@ -1827,133 +1828,116 @@ __device__ __forceinline__ bool texture_factor(const TexScene &ts, const float4 
     return true;
 }
 
-// One launch before a shade step (TextureArgs): walks the segments that step walks, one segment per workgroup at a time, and multiplies the
-// pixel's throughput of every textured hit by the texture. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
-__global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a) {
-    const uint32_t smp = blockIdx.y;
-    const Control *ctl = a.ctl + smp;
-    const bool records = a.rec_in != nullptr;
-    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
-    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
-    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
-    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
-    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = a.in_hits[co + chunk];
-        const uint32_t base = a.in_hit_base[co + chunk];
-        if (base >= n) break; // bases ascend with the segment index
-        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
-            if (base + r >= n) break;
-            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
-            float3_ p;
-            uint32_t prim, pixel_idx;
-            if (records) {
-                const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
-                p = {ra.x, ra.y, ra.z};
-                pixel_idx = __float_as_uint(ra.w);
-                prim = __float_as_uint(rb.w);
-            } else {
-                const float t = a.hq.t()[slot];
-                const uint32_t ridx = a.hq.ridx()[slot];
-                prim = a.hq.prim()[slot];
-                p = {q.ox()[ridx] + t * q.dx()[ridx], q.oy()[ridx] + t * q.dy()[ridx], q.oz()[ridx] + t * q.dz()[ridx]}; // sh:91
-                pixel_idx = q.pixel()[ridx];
-            }
-            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
-                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
-                if (m > 2u) m = 0u;
-                if (m != a.material) continue;
-            }
-            float3_ c;
-            if (!texture_factor(a.ts, a.prim_geom, a.shade_rec, a.prim_kind, prim, p, c)) continue;
-            float4 *px = pixel_of(image, local_pixel(pixel_idx, a.image_width, a.tile));
-            const float4 thr = *px;
-            *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+// ---- the walk the texture, emission and connect passes share (HitWalk): the hits the next shade step will shade, segment by segment
+// One sample's share of a walk (block-uniform): the step shades its hits h < n, which lie in the segments below n_chunks
+struct SampleHits {
+    uint32_t n, n_chunks;
+    size_t qo, co; // the sample's first slot in the hit queue / the records, and its first segment in the segment tables
+    RayQueue q;
+    float *image;
+};
+__device__ __forceinline__ SampleHits sample_hits(const HitWalk &w, uint32_t smp) {
+    const Control *ctl = w.ctl + smp;
+    SampleHits s;
+    s.n = w.rec_in ? umin(ctl->shade_n, w.capacity) : umin(w.n_hits[static_cast<size_t>(smp) * w.batch.ctl_stride], w.limit);
+    s.n_chunks = (umin(ctl->seg_n, w.capacity) + kChunk - 1) / kChunk;
+    s.qo = smp * static_cast<size_t>(w.batch.queue_stride);
+    s.co = smp * static_cast<size_t>(w.batch.chunk_stride);
+    s.q = slice(w.q, smp * static_cast<size_t>(w.batch.ray_stride));
+    s.image = w.image + smp * static_cast<size_t>(w.batch.image_stride);
+    return s;
+}
+// The hits of segment `chunk` among those the step shades (block-uniform): its first `count` slots. False: the segment, and every later
+// one, holds none (bases ascend with the segment index).
+__device__ __forceinline__ bool segment_hits(const HitWalk &w, const SampleHits &s, uint32_t chunk, uint32_t &count) {
+    if (chunk >= s.n_chunks) return false;
+    const uint32_t base = w.in_hit_base[s.co + chunk];
+    if (base >= s.n) return false;
+    count = umin(w.in_hits[s.co + chunk], s.n - base);
+    return true;
+}
+// Hit `slot` (s.qo + the segment's first slot + the hit's place in it) from either form: the primitive and the pixel, and with POINT the
+// hit point and the direction the ray arrived with.
+struct Hit {
+    uint32_t prim, pixel_idx;
+    float3_ p, d;
+};
+template <bool POINT>
+__device__ __forceinline__ Hit load_hit(const HitWalk &w, const SampleHits &s, size_t slot) {
+    Hit h;
+    h.p = h.d = {0.0f, 0.0f, 0.0f};
+    if (w.rec_in) {
+        const float4 ra = w.rec_in[2u * slot], rb = w.rec_in[2u * slot + 1u];
+        h.pixel_idx = __float_as_uint(ra.w);
+        h.prim = __float_as_uint(rb.w);
+        if (POINT) {
+            h.p = {ra.x, ra.y, ra.z};
+            h.d = {rb.x, rb.y, rb.z};
         }
+    } else {
+        const float t = POINT ? w.hq.t()[slot] : 0.0f;
+        const uint32_t ridx = w.hq.ridx()[slot];
+        h.prim = w.hq.prim()[slot];
+        if (POINT) {
+            h.d = {s.q.dx()[ridx], s.q.dy()[ridx], s.q.dz()[ridx]};
+            h.p = {s.q.ox()[ridx] + t * h.d.x, s.q.oy()[ridx] + t * h.d.y, s.q.oz()[ridx] + t * h.d.z}; // sh:91
+        }
+        h.pixel_idx = s.q.pixel()[ridx];
     }
+    return h;
+}
+// a primitive's material class as shade switches on it (`case 0u, default` folds > 2 into 0)
+__device__ __forceinline__ uint32_t material_class(const float4 *shade_rec, uint32_t prim) {
+    const uint32_t m = __float_as_uint(shade_rec[3u * prim + 2u].x);
+    return m > 2u ? 0u : m;
+}
+// a per-material shade stage shades hits of its class only
+__device__ __forceinline__ bool in_class(const HitWalk &w, uint32_t prim) {
+    return w.material == 0xffffffffu || material_class(w.shade_rec, prim) == w.material;
+}
+// per_hit(slot, hit) for every hit the step shades in sample blockIdx.y, the hit decoded with or without its POINT: one segment per
+// workgroup at a time, one hit per thread at a time. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
+template <bool POINT, typename F>
+__device__ __forceinline__ void for_each_shaded_hit(const HitWalk &w, const SampleHits &s, F &&per_hit) {
+    uint32_t count;
+    for (uint32_t chunk = blockIdx.x; segment_hits(w, s, chunk, count); chunk += gridDim.x)
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            const size_t slot = s.qo + static_cast<size_t>(chunk) * kChunk + r;
+            const Hit h = load_hit<POINT>(w, s, slot);
+            if (in_class(w, h.prim)) per_hit(slot, h);
+        }
+}
+
+// One launch before a shade step (TextureArgs): multiplies the pixel's throughput of every textured hit by the texture.
+__global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    for_each_shaded_hit<true>(a.w, s, [&](size_t, const Hit &h) {
+        float3_ c;
+        if (!texture_factor(a.ts, a.prim_geom, a.w.shade_rec, a.prim_kind, h.prim, h.p, c)) return;
+        float4 *px = pixel_of(s.image, local_pixel(h.pixel_idx, a.w.image_width, a.w.tile));
+        const float4 thr = *px;
+        *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+    });
 }
 
 // ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
-// One launch before a shade step, after that step's texture pass (EmissionArgs): walks the hits texture_kernel walks -- the walk is
-// restated here, that kernel stays as it is -- and for every hit on an emitter adds thr * e to the pixel's `emitted` and leaves the
-// throughput +0: the path is dead, shade scatters it all the same. Each pixel has at most one hit per wavefront: no two lanes touch one pixel.
-// (emission_nee_kernel below is this kernel's twin with one condition added: a change here belongs there too.)
-__global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
-    const uint32_t smp = blockIdx.y;
-    const Control *ctl = a.ctl + smp;
-    const bool records = a.rec_in != nullptr;
-    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
-    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
-    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
-    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
-    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
-    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = a.in_hits[co + chunk];
-        const uint32_t base = a.in_hit_base[co + chunk];
-        if (base >= n) break; // bases ascend with the segment index
-        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
-            if (base + r >= n) break;
-            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
-            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
-            const uint32_t m_idx = a.prim_em[prim];
-            if (m_idx == kNoEmission) continue;
-            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
-                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
-                if (m > 2u) m = 0u;
-                if (m != a.material) continue;
-            }
-            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
-            const float4 e = a.em[m_idx];
-            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
-            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
-            const float4 thr = *px, had = *out;
-            *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
-            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
-        }
-    }
-}
-
-// The emission pass of a context that connects (WFPT_FLAG_NEE with an emitter; include/wfpt.h "Next-event estimation"): emission_kernel
-// restated with one difference: thr * e is added only where the pixel's connected flag (emitted.w, set by the previous step's connect
-// pass) is 0. After a diffuse bounce the connect pass has already counted this light. A copy and not a `template <bool NEE>` body shared
-// by the two: instantiated from such a body, emission_kernel's own instructions change (the scalar address arithmetic at its head is
-// scheduled differently; tools/isa_compare.py), and contexts without the flag must run the kernel they ran before.
-__global__ __launch_bounds__(kConsumerThreads) void emission_nee_kernel(EmissionArgs a) {
-    const uint32_t smp = blockIdx.y;
-    const Control *ctl = a.ctl + smp;
-    const bool records = a.rec_in != nullptr;
-    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
-    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
-    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
-    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
-    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
-    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = a.in_hits[co + chunk];
-        const uint32_t base = a.in_hit_base[co + chunk];
-        if (base >= n) break; // bases ascend with the segment index
-        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
-            if (base + r >= n) break;
-            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
-            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
-            const uint32_t m_idx = a.prim_em[prim];
-            if (m_idx == kNoEmission) continue;
-            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
-                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
-                if (m > 2u) m = 0u;
-                if (m != a.material) continue;
-            }
-            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
-            const float4 e = a.em[m_idx];
-            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
-            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
-            const float4 thr = *px, had = *out;
-            if (had.w == 0.0f) *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
-            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
-        }
+// The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
+// operation order): what the connect pass's sample and the weight of a scattered ray's hit on the light both measure the light by.
+__device__ __forceinline__ void light_normal_area(const float4 *prim_geom, const float4 *shade_rec, uint32_t prim_kind, uint32_t prim, float3_ q,
+                                                  float3_ &nl, float &area) {
+    if (prim_kind == 0) {
+        const float4 g = prim_geom[prim]; // (centre, radius)
+        const float ra = __builtin_fabsf(g.w);
+        nl = {(q.x - g.x) / ra, (q.y - g.y) / ra, (q.z - g.z) / ra};
+        area = (4.0f * kPi) * (ra * ra);
+    } else {
+        const float4 g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+        const float4 rec0 = shade_rec[3u * prim]; // the stored normalize(cross(e1, e2))
+        nl = {rec0.x, rec0.y, rec0.z};
+        const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
+        area = 0.5f * sqrt_(dot3(cr, cr));
     }
 }
 
@@ -1973,18 +1957,7 @@ __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, con
     const float3_ w = {v.x / dist, v.y / dist, v.z / dist};
     float3_ nl;
     float area;
-    if (prim_kind == 0) {
-        const float4 g = prim_geom[prim]; // (centre, radius)
-        const float ra = __builtin_fabsf(g.w);
-        nl = {(ph.x - g.x) / ra, (ph.y - g.y) / ra, (ph.z - g.z) / ra};
-        area = (4.0f * kPi) * (ra * ra);
-    } else {
-        const float4 g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
-        const float4 rec0 = shade_rec[3u * prim]; // the stored normalize(cross(e1, e2))
-        nl = {rec0.x, rec0.y, rec0.z};
-        const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
-        area = 0.5f * sqrt_(dot3(cr, cr));
-    }
+    light_normal_area(prim_geom, shade_rec, prim_kind, prim, ph, nl, area);
     MisWeight m;
     m.cos_l = __builtin_fabsf(dot3(nl, w));
     const float len = sqrt_(dot3(d, d));
@@ -1999,62 +1972,31 @@ __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, con
     return m;
 }
 
-// The emission pass of a context that connects and weighs (WFPT_FLAG_MIS with an emitter; include/wfpt.h "Multiple importance sampling"):
-// emission_nee_kernel restated with one difference: where the pixel's connected flag is 1 the hit is not dropped but adds (thr * e) * wb
-// (mis_hit_weight, with the point the previous step's connect pass stored in `origin` and the direction the ray arrived with). A third
-// copy for emission_nee_kernel's reason. The extra loads happen per hit on an emitter after a diffuse bounce only.
-__global__ __launch_bounds__(kConsumerThreads) void emission_mis_kernel(EmissionArgs a, MisArgs mis) {
-    const uint32_t smp = blockIdx.y;
-    const Control *ctl = a.ctl + smp;
-    const bool records = a.rec_in != nullptr;
-    const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
-    const uint32_t n_chunks = (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk;
-    const size_t qo = smp * static_cast<size_t>(a.batch.queue_stride), co = smp * static_cast<size_t>(a.batch.chunk_stride);
-    const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
-    float *image = a.image + smp * static_cast<size_t>(a.batch.image_stride);
-    float *emitted = a.emitted + smp * static_cast<size_t>(a.batch.image_stride);
-    const float4 *origin = mis.origin + smp * static_cast<size_t>(a.batch.image_stride / 4u);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = a.in_hits[co + chunk];
-        const uint32_t base = a.in_hit_base[co + chunk];
-        if (base >= n) break; // bases ascend with the segment index
-        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
-            if (base + r >= n) break;
-            const size_t slot = qo + static_cast<size_t>(chunk) * kChunk + r;
-            const uint32_t prim = records ? __float_as_uint(a.rec_in[2u * slot + 1u].w) : a.hq.prim()[slot];
-            const uint32_t m_idx = a.prim_em[prim];
-            if (m_idx == kNoEmission) continue;
-            if (a.material != 0xffffffffu) { // one per-material shade stage: its class only (`case 0u, default` folds > 2 into 0)
-                uint32_t m = __float_as_uint(a.shade_rec[3u * prim + 2u].x);
-                if (m > 2u) m = 0u;
-                if (m != a.material) continue;
-            }
-            const uint32_t pixel_idx = records ? __float_as_uint(a.rec_in[2u * slot].w) : q.pixel()[a.hq.ridx()[slot]];
-            const float4 e = a.em[m_idx];
-            const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
-            float4 *px = pixel_of(image, lp), *out = pixel_of(emitted, lp);
-            const float4 thr = *px, had = *out;
-            if (had.w == 0.0f) {
-                *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
-            } else {
-                float3_ ph, d;
-                if (records) {
-                    const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
-                    ph = {ra.x, ra.y, ra.z};
-                    d = {rb.x, rb.y, rb.z};
-                } else {
-                    const float t = a.hq.t()[slot];
-                    const uint32_t ridx = a.hq.ridx()[slot];
-                    d = {q.dx()[ridx], q.dy()[ridx], q.dz()[ridx]};
-                    ph = {q.ox()[ridx] + t * d.x, q.oy()[ridx] + t * d.y, q.oz()[ridx] + t * d.z}; // sh:91
-                }
-                const float4 o = origin[lp];
-                const float wb = mis_hit_weight(mis.prim_geom, a.shade_rec, mis.prim_kind, prim, mis.nf, {o.x, o.y, o.z}, ph, d).wb;
-                *out = make_float4(had.x + (thr.x * e.x) * wb, had.y + (thr.y * e.y) * wb, had.z + (thr.z * e.z) * wb, had.w);
-            }
-            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+// One launch before a shade step, after that step's texture pass (EmissionArgs, with its three kinds): for every hit on an emitter adds
+// thr * e (gated, or weighed, by the pixel's connected flag) to the pixel's `emitted` and leaves the throughput +0: the path is dead,
+// shade scatters it all the same.
+template <int KIND>
+__global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    float *emitted = a.emitted + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride);
+    const float4 *origin = KIND == kEmitWeighed ? a.origin + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride / 4u) : nullptr;
+    for_each_shaded_hit<false>(a.w, s, [&](size_t slot, const Hit &hit) {
+        const uint32_t m_idx = a.prim_em[hit.prim];
+        if (m_idx == kNoEmission) return;
+        const float4 e = a.em[m_idx];
+        const uint32_t lp = local_pixel(hit.pixel_idx, a.w.image_width, a.w.tile);
+        float4 *px = pixel_of(s.image, lp), *out = pixel_of(emitted, lp);
+        const float4 thr = *px, had = *out;
+        if (KIND == kEmitAll || had.w == 0.0f) {
+            *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
+        } else if (KIND == kEmitWeighed) {
+            const Hit h = load_hit<true>(a.w, s, slot); // the point and the direction: for the hits that are weighed only
+            const float4 o = origin[lp];
+            const float wb = mis_hit_weight(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, a.nf, {o.x, o.y, o.z}, h.p, h.d).wb;
+            *out = make_float4(had.x + (thr.x * e.x) * wb, had.y + (thr.y * e.y) * wb, had.z + (thr.z * e.z) * wb, had.w);
         }
-    }
+        *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+    });
 }
 
 // wfpt_mis_hit_weight: mis_hit_weight for caller rows (o.xyz, d.xyz, t, the primitive index as a float), one thread per row; a primitive
@@ -3340,18 +3282,13 @@ __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, fl
         float sn, cs;
         sincos_((2.0f * kPi) * u2, sn, cs);
         s.q = {g.x + ra * (r * cs), g.y + ra * (r * sn), g.z + ra * z};
-        nl = {(s.q.x - g.x) / ra, (s.q.y - g.y) / ra, (s.q.z - g.z) / ra};
-        area = (4.0f * kPi) * (ra * ra);
     } else {
         const float4 g0 = a.scene.prim_geom[3u * prim], g1 = a.scene.prim_geom[3u * prim + 1u], g2 = a.scene.prim_geom[3u * prim + 2u];
         const float su = sqrt_(u1);
         const float b1 = 1.0f - su, b2 = u2 * su;
         s.q = {(g0.x + b1 * g1.x) + b2 * g2.x, (g0.y + b1 * g1.y) + b2 * g2.y, (g0.z + b1 * g1.z) + b2 * g2.z};
-        const float4 rec0 = a.scene.shade_rec[3u * prim]; // the stored normalize(cross(e1, e2))
-        nl = {rec0.x, rec0.y, rec0.z};
-        const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
-        area = 0.5f * sqrt_(dot3(cr, cr));
     }
+    light_normal_area(a.scene.prim_geom, a.scene.shade_rec, PRIM, prim, s.q, nl, area);
     const float3_ v = {s.q.x - p.x, s.q.y - p.y, s.q.z - p.z};
     const float dist2 = dot3(v, v);
     s.dist = sqrt_(dist2);
@@ -3427,31 +3364,26 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // draws; the shadow ray has no far end) and an emitter otherwise, each weighted by the inverse of its probability; the sampler form is the
 // map's alone. With ENVS false the kernel is the one of WFPT_FLAG_NEE.
 // MIS (WFPT_FLAG_MIS contexts with an emitter; never with ENVS): the sample is weighed by wl = pl / (pl + pb), and every diffuse hit stores
-// its point in a.origin for the next step's emission_mis_kernel (one 16-byte store next to the `emitted` update of the same pixel); the
+// its point in a.origin for the next step's weighed emission pass (one 16-byte store next to the `emitted` update of the same pixel); the
 // sampler form answers 12 floats a row. With MIS false the source is the one above.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
     extern __shared__ float4 lds[];
     WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
-    const bool sampler = a.sample_in != nullptr, records = a.rec_in != nullptr;
+    const bool sampler = a.sample_in != nullptr;
     const uint32_t per_smp = sampler ? (a.sample_n + kChunk - 1u) / kChunk : a.n_chunks_max;
-    const uint32_t n_items = sampler ? per_smp : per_smp * a.batch.n;
-    const uint32_t frame0 = sampler ? 0u : uniform(a.ctl->frame.frame); // the batch's first frame, as shade_kernel and aov_body take it
+    const uint32_t n_items = sampler ? per_smp : per_smp * a.w.batch.n;
+    const uint32_t frame0 = sampler ? 0u : uniform(a.w.ctl->frame.frame); // the batch's first frame, as shade_kernel and aov_body take it
     bool staged = false;
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const uint32_t smp = sampler ? 0u : item / per_smp, chunk = item - smp * per_smp;
         uint32_t count;
         if (sampler) {
             count = umin(static_cast<uint32_t>(kChunk), a.sample_n - chunk * kChunk);
-        } else { // the segment's hits among those the step shades, as emission_kernel finds them (all block-uniform)
-            const Control *ctl = a.ctl + smp;
-            const uint32_t n = records ? umin(ctl->shade_n, a.capacity) : umin(a.n_hits[static_cast<size_t>(smp) * a.batch.ctl_stride], a.limit);
-            if (chunk >= (umin(ctl->seg_n, a.capacity) + kChunk - 1) / kChunk) continue;
-            const size_t co = smp * static_cast<size_t>(a.batch.chunk_stride);
-            const uint32_t base = a.in_hit_base[co + chunk];
-            if (base >= n) continue;
-            count = umin(umin(a.in_hits[co + chunk], static_cast<uint32_t>(kChunk)), n - base);
+        } else { // the segment's hits among those the step shades
+            if (!segment_hits(a.w, sample_hits(a.w, smp), chunk, count)) continue;
+            count = umin(count, static_cast<uint32_t>(kChunk));
         }
         count = uniform(count);
         if (count == 0u) continue;
@@ -3478,36 +3410,37 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
                 u0 = row[6]; u1 = row[7]; u2 = row[8];
             }
         } else if (live) {
-            const size_t slot = smp * static_cast<size_t>(a.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk + threadIdx.x;
+            // the hit's point, pixel and primitive: load_hit's two forms in this kernel's own statement order, with which three instantiations
+            // at the SGPR ceiling keep their VGPR count
+            const size_t slot = smp * static_cast<size_t>(a.w.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk + threadIdx.x;
             uint32_t prim, pixel_idx;
-            if (records) {
-                const float4 ra = a.rec_in[2u * slot], rb = a.rec_in[2u * slot + 1u];
+            if (a.w.rec_in) {
+                const float4 ra = a.w.rec_in[2u * slot], rb = a.w.rec_in[2u * slot + 1u];
                 p = {ra.x, ra.y, ra.z};
                 pixel_idx = __float_as_uint(ra.w);
                 prim = __float_as_uint(rb.w);
             } else {
-                const RayQueue q = slice(a.q, smp * static_cast<size_t>(a.batch.ray_stride));
-                const float t = a.hq.t()[slot];
-                const uint32_t ridx = a.hq.ridx()[slot];
-                prim = a.hq.prim()[slot];
+                const RayQueue q = slice(a.w.q, smp * static_cast<size_t>(a.w.batch.ray_stride));
+                const float t = a.w.hq.t()[slot];
+                const uint32_t ridx = a.w.hq.ridx()[slot];
+                prim = a.w.hq.prim()[slot];
                 p = {q.ox()[ridx] + t * q.dx()[ridx], q.oy()[ridx] + t * q.dy()[ridx], q.oz()[ridx] + t * q.dz()[ridx]}; // sh:91
                 pixel_idx = q.pixel()[ridx];
             }
             const float4 rec0 = a.scene.shade_rec[3u * prim];
             rec1 = a.scene.shade_rec[3u * prim + 1u];
-            uint32_t m = __float_as_uint(a.scene.shade_rec[3u * prim + 2u].x); // `case 0u, default` folds > 2 into 0
-            if (m > 2u) m = 0u;
-            if (a.material != 0xffffffffu && m != a.material) {
+            const uint32_t m = material_class(a.scene.shade_rec, prim);
+            if (a.w.material != 0xffffffffu && m != a.w.material) {
                 live = false; // one per-material shade stage: its class only
             } else {
-                const uint32_t lp = local_pixel(pixel_idx, a.image_width, a.tile);
-                out = pixel_of(a.emitted + smp * static_cast<size_t>(a.batch.image_stride), lp);
+                const uint32_t lp = local_pixel(pixel_idx, a.w.image_width, a.w.tile);
+                out = pixel_of(a.emitted + smp * static_cast<size_t>(a.w.batch.image_stride), lp);
                 // (ENVS: no emission table while no material emits)
                 if (m != 0u || ((!ENVS || a.prim_em) && a.prim_em[prim] != kNoEmission)) { // metal, dielectric, emitter: the flag is cleared, nothing else
                     out->w = 0.0f;
                     live = false;
                 } else {
-                    px = pixel_of(a.image + smp * static_cast<size_t>(a.batch.image_stride), lp);
+                    px = pixel_of(a.w.image + smp * static_cast<size_t>(a.w.batch.image_stride), lp);
                     // the normal scatter() uses, never flipped
                     n = PRIM == 0 ? normalize3({p.x - rec0.x, p.y - rec0.y, p.z - rec0.z}) : float3_{rec0.x, rec0.y, rec0.z};
                     uint32_t rng = jenkins_hash(pixel_idx ^ jenkins_hash(frame0 + smp)); // init_rng((x, y), (W, H), frame): x + y W is the pixel
@@ -4312,18 +4245,16 @@ hipError_t launch_env_tables(const EnvDev &env, const float *f, float M, uint32_
 
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(texture_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    hipLaunchKernelGGL(texture_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_emission(const EmissionArgs &a, uint32_t grid, hipStream_t s, bool nee, const MisArgs *mis) {
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    if (nee && mis)
-        hipLaunchKernelGGL(emission_mis_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *mis);
-    else if (nee)
-        hipLaunchKernelGGL(emission_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
-    else
-        hipLaunchKernelGGL(emission_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
+    void (*const k)(EmissionArgs) = kind == kEmitWeighed ? emission_kernel<kEmitWeighed>
+                                    : kind == kEmitGated ? emission_kernel<kEmitGated>
+                                                         : emission_kernel<kEmitAll>;
+    hipLaunchKernelGGL(k, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
 }
 
