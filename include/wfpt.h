@@ -241,7 +241,13 @@ enum {
     WFPT_FLAG_MIS = 1u << 17         /* multiple importance sampling, see "Multiple importance sampling" below: the emitter hits of
                                         scattered rays and the shadow rays of the connect pass are both kept, weighed by the balance
                                         heuristic. Needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with WFPT_FLAG_ENV_NEE. With no emitter
-                                        set the context renders bit for bit as without the flag, and launches the same kernels. */
+                                        set the context renders bit for bit as without the flag, and launches the same kernels. */,
+    WFPT_FLAG_ENV_MIS = 1u << 18     /* multiple importance sampling between the environment map and the scatter, see "Environment multiple
+                                        importance sampling" below: the map's connect samples and the misses of scattered rays are both
+                                        kept, weighed by the balance heuristic, and so are the emitters' samples and hits. Needs
+                                        WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and WFPT_FLAG_ENV_NEE, refused with
+                                        WFPT_FLAG_MIS. With no map set (or a black one) the context renders bit for bit as without the
+                                        flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -810,7 +816,8 @@ int wfpt_sample_lights(wfpt_ctx *ctx, const float *in9, size_t n, float *out8);
  * With no map set, or a black one, a flagged context launches exactly the kernels a context with the three other flags launches and
  * renders the same bits, with and without emitters. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag; the
  * connect launches stay under wfpt_nee_timing_ms.
- * Not done: multiple importance sampling between the map and the scatter, a distribution that accounts for the receiver's normal or for
+ * (Multiple importance sampling between the map and the scatter: WFPT_FLAG_ENV_MIS, "Environment multiple importance sampling" below.)
+ * Not done: a distribution that accounts for the receiver's normal or for
  * visibility, a coarser importance grid or an alias table for very large maps, the class-binned loop and wfpt_render_chunked*, object
  * lights selected by power, retiring dead paths. */
 /* the environment share: finite, in (0, 1]. Acts like wfpt_set_emission: the accumulation restarts, the graphs and the history are dropped */
@@ -865,7 +872,8 @@ int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, fl
  * flagged context with an emitter never runs the class-binned loop (see "Emission"); wfpt_render_chunked* masks the flag off. The
  * launches are booked under wfpt_emission_timing_ms and wfpt_nee_timing_ms. The calls below are blocking and return
  * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while no primitive emits.
- * Not done: weighing the environment map against the scatter (WFPT_FLAG_ENV_NEE is refused), the power heuristic, cone sampling of
+ * (Weighing the environment map against the scatter: WFPT_FLAG_ENV_MIS, a flag of its own below; WFPT_FLAG_ENV_NEE stays refused here.)
+ * Not done: the power heuristic, cone sampling of
  * sphere lights, light selection by power, MIS for fuzzy metal, retiring dead paths, the class-binned loop and wfpt_render_chunked*. */
 /* Steps 3 to 5 with the weight for n caller-supplied receivers on the device. in9: as wfpt_sample_lights; out12: n rows of (q.xyz, the
  * light's primitive index as a float, ((e_q * G) * wl) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pl, pb, wl, 0) --
@@ -875,6 +883,62 @@ int wfpt_sample_lights_mis(wfpt_ctx *ctx, const float *in9, size_t n, float *out
  * of its integer value), with ph = o + t d per component; out4: n rows of (pl, pb, wb, cos_l). A primitive that does not emit or is out
  * of range (a NaN included) gives (0, pb, 1, 0). */
 int wfpt_mis_hit_weight(wfpt_ctx *ctx, const float *in8, size_t n, float *out4);
+
+/* ------------------------------------------------------------------ Environment multiple importance sampling (WFPT_FLAG_ENV_MIS)
+ * wfpt_create* accepts WFPT_FLAG_ENV_MIS only together with WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and
+ * WFPT_FLAG_ENV_NEE, and refuses it together with WFPT_FLAG_MIS (WFPT_ERR_INVALID_ARGUMENT either way; WFPT_FLAG_MIS stays refused with
+ * WFPT_FLAG_ENV_NEE, which is why this is a bit of its own). "Environment next-event estimation" takes all light of the map after a
+ * diffuse bounce from the one shadow ray and zeroes the scattered ray's miss, although that ray is traced anyway. This flag keeps both
+ * and weighs them by the balance heuristic, and does the same for the emitters (as "Multiple importance sampling" does without a map).
+ * No ray is added. The scatter's density comes from the identity of "Multiple importance sampling": the miss queue of a
+ * WFPT_FLAG_ENVIRONMENT context carries the un-normalised direction d, and (0.5 |d|) / pi is the density of the scatter that made it.
+ *
+ * The flag acts only while the map has a sampling distribution. With no map set, or a black one, a flagged context launches exactly the
+ * kernels the same context without the flag launches and renders the same bits, with and without emitters. While a distribution exists
+ * the step order stays texture, emission, connect, shade, then miss; the stream, the draws u0..u4, the branch choice, the selections,
+ * the direction, the occlusion tests and the connected flag of "Next-event estimation" and "Environment next-event estimation" are
+ * unchanged. All operations are IEEE f32 in the order written, no fma, pi = 3.1415927f, 2 pi^2 = 19.739209f; p is the effective share (1
+ * with an empty light list), q = 1 - p. Four things change:
+ *  1. Connect pass, environment branch. For a contributing, unoccluded sample
+ *       pe = pdf * p;  pb = cos_s / pi;  we = pe / (pe + pb)
+ *       emitted[pixel] += (((thr * albedo) * e) * Genv) * we
+ *  2. Connect pass, emitter branch (only when p < 1). With pl and pb as step 1 of "Multiple importance sampling" computes them
+ *       plq = pl * q;  wl = plq / (plq + pb)
+ *       emitted[pixel] += ((((thr * albedo) * e_q) * G) / q) * wl
+ *     At every diffuse hit, in either branch, contributing or not, the pass writes the hit point into the `origin` plane as described
+ *     there. On a flagged context the plane is allocated wherever `emitted` is: with the first emitter or the first map that has a
+ *     distribution, whichever comes first.
+ *  3. Emission pass. Where the pixel's connected flag is 0 nothing changes. Where it is 1, step 2 of "Multiple importance sampling" with
+ *     plq = pl * q in place of pl: wb = pb / (pb + plq), and wb = 1 on a failed condition. (With p = 1 and emitters, a share the caller
+ *     set, plq = 0 and the hit counts whole: the connect pass never samples an emitter then.)
+ *  4. Miss pass. Where the pixel's connected flag is 0: thr *= c, as before. Where it is 1, with d the miss queue's direction:
+ *       len = sqrt((d.x d.x + d.y d.y) + d.z d.z);  pb = (0.5 * len) / pi
+ *       n, phi, theta, u (after its wrap), v: exactly the values the map's lookup forms for d ("Environment map")
+ *       st = sqrt(n.x n.x + n.z n.z)   (the value the lookup hands to atan2)
+ *       xt = min(u32(floor(u * f32(w))), w - 1);  yt = min(u32(floor(v * f32(h))), h - 1)   (a NaN u or v selects 0)
+ *       k = row[yt][xt] - row[yt][xt - 1]   (row[yt][-1] = 0);  P = f32(k) / f32(total)
+ *       pdf = ((P * f32(w)) * f32(h)) / ((2 pi^2) * st);  pe = pdf * p
+ *       wb = 1 and pe = 0           if st > 0 or pdf > 0 fails (a NaN fails each test)
+ *       wb = pb / (pb + pe)         otherwise
+ *       thr <- (thr * c) * wb       per channel, c the lookup's value as before
+ *     The two sides take pb from different expressions (cos_s / pi in connect, the length in the miss) and the miss finds its texel from
+ *     a rounded direction, so we + wb is 1 to rounding, not exactly (DESIGN.md 9l measures it), and a direction within a few ulp of a
+ *     texel edge may find the neighbouring texel's k.
+ * Every batch size, loop, RNG mode and band sharding gives the same weights: they depend on the path alone. A change of the map, the
+ * share or the emitters drops the captured graphs as before. wfpt_render_chunked* masks the flag off. The launches are booked under
+ * wfpt_emission_timing_ms, wfpt_nee_timing_ms and the miss stage. The calls below are blocking, use the context's effective share p, and
+ * return WFPT_ERR_INVALID_ARGUMENT on a context without the flag, while no map with a distribution is set, and for a NULL pointer with
+ * n > 0.
+ * Not done: the power heuristic, a distribution aware of the receiver's normal, MIS for fuzzy metal, the class-binned loop,
+ * wfpt_render_chunked*, retiring dead paths, the samplers of WFPT_FLAG_MIS (wfpt_sample_lights_mis, wfpt_mis_hit_weight) on a context
+ * with this flag. */
+/* The environment branch with its weight for n caller-supplied receivers on the device. in10: as wfpt_sample_environment_light; out12: n
+ * rows of (wdir.xyz, f32(y * w + x), ((e * Genv) * we) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pe, pb, we, 0) --
+ * the three channels and pe, pb, we are 0 where the sample contributes nothing. */
+int wfpt_sample_environment_light_mis(wfpt_ctx *ctx, const float *in10, size_t n, float *out12);
+/* The miss pass's weight for n caller-supplied directions on the device. dirs3: n rows of an un-normalised direction; out4: n rows of
+ * (pe, pb, wb, f32(yt * w + xt)). */
+int wfpt_env_mis_miss_weight(wfpt_ctx *ctx, const float *dirs3, size_t n, float *out4);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

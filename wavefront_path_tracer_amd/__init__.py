@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -44,6 +44,9 @@ FLAG_NEE = 1 << 15  # shadow rays from diffuse hits to the emitters (include/wfp
 # FLAG_EMISSION and FLAG_NEE
 FLAG_ENV_NEE = 1 << 16
 FLAG_MIS = 1 << 17
+# the map and the emitters weighed against the scatter (include/wfpt.h "Environment multiple importance sampling"); needs the four flags
+# of FLAG_ENV_NEE, refused with FLAG_MIS
+FLAG_ENV_MIS = 1 << 18
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -357,6 +360,8 @@ def lib():
         "wfpt_sample_environment_light": (i32, [vp, vp, sz, vp]),
         "wfpt_sample_lights_mis": (i32, [vp, vp, sz, vp]),
         "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
+        "wfpt_sample_environment_light_mis": (i32, [vp, vp, sz, vp]),
+        "wfpt_env_mis_miss_weight": (i32, [vp, vp, sz, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -1454,6 +1459,28 @@ class PathTracer:
             raise ValueError(f"mis_hit_weight: expected rows of 8 floats, got shape {a.shape}")
         out = np.zeros((a.shape[0], 4), "<f4")
         self._check(lib().wfpt_mis_hit_weight(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
+
+    # ---- environment multiple importance sampling (FLAG_ENV_NEE's four flags | FLAG_ENV_MIS; include/wfpt.h "Environment multiple importance sampling")
+    def sample_environment_light_mis(self, rows):
+        """The connect pass's weighed sample of the map, with the context's effective share p, for caller-supplied receivers, computed on
+        the device. rows: (n, 10) float32 as for sample_environment_light; returns (n, 12) float32 of (wdir.xyz, the texel index
+        y * w + x, (e * Genv) * we per channel, occluded 0/1, pe, pb, we, 0)."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != 10:
+            raise ValueError(f"sample_environment_light_mis: expected rows of 10 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 12), "<f4")
+        self._check(lib().wfpt_sample_environment_light_mis(self.handle, _p(a), a.shape[0], _p(out)))
+        return out
+
+    def env_mis_miss_weight(self, dirs):
+        """The miss pass's weight for caller-supplied un-normalised directions, computed on the device. dirs: (n, 3) float32; returns
+        (n, 4) float32 of (pe, pb, wb, the texel index yt * w + xt)."""
+        a = np.ascontiguousarray(dirs, "<f4")
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"env_mis_miss_weight: expected rows of 3 floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], 4), "<f4")
+        self._check(lib().wfpt_env_mis_miss_weight(self.handle, _p(a), a.shape[0], _p(out)))
         return out
 
     # ---- read-back

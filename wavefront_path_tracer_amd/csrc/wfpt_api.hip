@@ -599,7 +599,7 @@ constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
 
 // a material emits: the emission passes run before the shade steps (after their texture passes) and accumulate takes the second plane
 bool emitting(const wfpt_ctx *c) { return c->em_prim.get() != nullptr; }
-// (the last four fields: the weighing kind's alone)
+// (the last four fields: the weighing kinds' alone)
 EmissionArgs emission_args(wfpt_ctx *c, const HitWalk &w) {
     return EmissionArgs{w, c->emitted.get(), c->em_prim.get(), c->em_mat.get(), c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind,
                         static_cast<float>(c->n_lights)};
@@ -616,7 +616,12 @@ bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || en
 bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c); }
 // a WFPT_FLAG_MIS context holds an emitter (never with a map's distribution: the flag excludes WFPT_FLAG_ENV_NEE): the connect and
 // emission passes are the MIS variants
-bool weighing(const wfpt_ctx *c) { return c->mis_origin.get() != nullptr && c->n_lights > 0; }
+bool weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_MIS) != 0 && c->mis_origin.get() != nullptr && c->n_lights > 0; }
+// a WFPT_FLAG_ENV_MIS context holds a map with a sampling distribution: the connect, emission and miss passes weigh the map and the
+// emitters against the scatter (without a distribution the flag does nothing)
+bool env_weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_ENV_MIS) != 0 && env_connecting(c) && c->mis_origin.get() != nullptr; }
+// the map with its distribution and the effective share: 1 while there is no light to pick instead
+EnvDist env_dist(const wfpt_ctx *c) { return EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f}; }
 // the connect pass before a shade step of wavefront `wavefront`
 ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w) {
     ConnectArgs a{};
@@ -631,8 +636,7 @@ ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w) {
     a.origin = c->mis_origin.get();
     a.ts = tex_scene(c);
     a.scene = c->scene;
-    if (env_connecting(c)) // the effective share: 1 while there is no light to pick instead
-        a.envd = EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f};
+    if (env_connecting(c)) a.envd = env_dist(c);
     return a;
 }
 // the sampler form of the connect pass (no hits: the caller's rows)
@@ -645,11 +649,12 @@ ConnectArgs sampler_args(wfpt_ctx *c, const float *in, float *out, size_t n) {
 }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
-    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c));
+    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c));
 }
 // the emission pass of the context's kind
 hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
-    return launch_emission(a, !connecting(c) ? kEmitAll : weighing(c) ? kEmitWeighed : kEmitGated, grid, c->stream.get());
+    return launch_emission(a, !connecting(c) ? kEmitAll : env_weighing(c) ? kEmitWeighedEnv : weighing(c) ? kEmitWeighed : kEmitGated, grid,
+                           c->stream.get(), 1.0f - env_dist(c).share);
 }
 // the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
 const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
@@ -683,6 +688,11 @@ PlanArgs plan_args(wfpt_ctx *c, uint32_t nb, bool last) {
 }
 // the map the kernels light misses with, null for the gradient sky: selects the environment variants (and the miss launches of the fused loops)
 const EnvDev *env_of(const wfpt_ctx *c) { return c->env_tex.get() ? &c->env : nullptr; }
+// the miss pass of the context's kind: the sky, the map, the map gated by the connected flags, or (env_weighing) weighed where they are set
+hipError_t launch_miss_pass(wfpt_ctx *c, const MissArgs &a, uint32_t grid) {
+    const EnvDist d = env_dist(c);
+    return launch_miss(a, grid, c->stream.get(), env_of(c) ? &d : nullptr, miss_gate(c), env_weighing(c));
+}
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
@@ -742,7 +752,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                      return launch_shade(sa, consumer_grid(c, nb), st);
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] {
-                     return launch_miss(miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb), st, env, miss_gate(c));
+                     return launch_miss_pass(c, miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb));
                  }));
     }
     return WFPT_OK;
@@ -761,7 +771,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const int par = static_cast<int>(b & 1u);
         const bool last = b + 1 >= c->p.max_wavefronts;
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
-        if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
+        if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
@@ -807,7 +817,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         const bool last = b + 1 >= c->p.max_wavefronts;
         if (!last || env) // (the last launch's miss items: a launch of their own only with the map)
-            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss(fused_miss_args(c, par, nb), consumer_grid(c, nb), st, env, miss_gate(c)); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
         if (!last) {
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
@@ -1402,6 +1412,18 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
             return nullptr;
         }
     }
+    if ((params->flags & WFPT_FLAG_ENV_MIS) != 0) {
+        constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE;
+        if ((params->flags & need) != need) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_MIS needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and "
+                                                     "WFPT_FLAG_ENV_NEE (it weighs the map's connect samples against the scattered rays' misses)");
+            return nullptr;
+        }
+        if ((params->flags & WFPT_FLAG_MIS) != 0) { // (already refused above with WFPT_FLAG_ENV_NEE; stated for the flag's own rule)
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_MIS does not go with WFPT_FLAG_MIS (it weighs the emitters itself)");
+            return nullptr;
+        }
+    }
     if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
         constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
         if ((params->flags & need) != need) {
@@ -1619,7 +1641,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1882,7 +1904,7 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         break;
     }
     case WFPT_STAGE_MISS:
-        WFPT_HIP(c, launch_miss(miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1), c->stream.get(), env_of(c), miss_gate(c)));
+        WFPT_HIP(c, launch_miss_pass(c, miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1)));
         break;
     case WFPT_STAGE_ACCUMULATE:
         if (second_plane(c))
@@ -2776,6 +2798,7 @@ struct EnvTables {
     DeviceBuffer<uint64_t> marg;
     uint64_t total = 0;
     DeviceBuffer<float> plane;
+    DeviceBuffer<float4> origin; // WFPT_FLAG_ENV_MIS: the hit-point plane comes and stays with the second plane
 };
 static int build_env_tables(wfpt_ctx *c, const EnvDev &env, EnvTables &out) {
     if (!(c->p.flags & WFPT_FLAG_ENV_NEE)) return WFPT_OK;
@@ -2800,6 +2823,7 @@ static int build_env_tables(wfpt_ctx *c, const EnvDev &env, EnvTables &out) {
     if (!c->emitted.get()) {
         WFPT_HIP(c, out.plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
         WFPT_HIP(c, hipMemset(out.plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
+        if (c->p.flags & WFPT_FLAG_ENV_MIS) WFPT_HIP(c, out.origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
     }
     return WFPT_OK;
 }
@@ -2812,6 +2836,7 @@ static int environment_changed(wfpt_ctx *c, DeviceBuffer<float4> tex, uint32_t w
     c->env_marg = std::move(t.marg);
     c->env_total = t.total;
     if (t.plane.get()) c->emitted = std::move(t.plane);
+    if (t.origin.get()) c->mis_origin = std::move(t.origin);
     return scene_changed(c);
 }
 
@@ -3105,11 +3130,11 @@ static int apply_emission(wfpt_ctx *c, std::vector<float> &&rgb) {
     EmissionTables tables;
     if (int r = build_emission_tables(c, rgb, c->h_prim_mat_idx, tables); r != WFPT_OK) return r;
     DeviceBuffer<float> plane;
-    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS: the hit-point plane comes and stays with the second plane
+    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS, WFPT_FLAG_ENV_MIS: the hit-point plane comes and stays with the second plane
     if (tables.prim.get() && !c->emitted.get()) {
         WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
         WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
-        if (c->p.flags & WFPT_FLAG_MIS) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
+        if (c->p.flags & (WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS)) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
     if (plane.get()) c->emitted = std::move(plane);
@@ -3298,6 +3323,53 @@ int wfpt_sample_environment_light(wfpt_ctx *c, const float *in10, size_t n, floa
     if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
     if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment_light");
+    return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- environment multiple importance sampling (include/wfpt.h)
+static int env_mis_check(wfpt_ctx *c, const char *who) {
+    if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & WFPT_FLAG_ENV_MIS)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_ENV_MIS");
+    if (!env_weighing(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no map with a distribution is set");
+    return WFPT_OK;
+}
+
+int wfpt_sample_environment_light_mis(wfpt_ctx *c, const float *in10, size_t n, float *out12) {
+    if (int r = env_mis_check(c, "wfpt_sample_environment_light_mis"); r != WFPT_OK) return r;
+    if ((!in10 || !out12) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light_mis: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light_mis: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(10 * n);
+    if (e == hipSuccess) e = d_out.alloc(12 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in10, sizeof(float) * 10 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) {
+        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n); // (envd.share: the effective share)
+        const uint64_t items = (n + kChunk - 1) / kChunk;
+        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
+                           textured(c), true, true);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out12, d_out.get(), sizeof(float) * 12 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment_light_mis");
+    return WFPT_OK;
+}
+
+int wfpt_env_mis_miss_weight(wfpt_ctx *c, const float *dirs3, size_t n, float *out4) {
+    if (int r = env_mis_check(c, "wfpt_env_mis_miss_weight"); r != WFPT_OK) return r;
+    if ((!dirs3 || !out4) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_env_mis_miss_weight: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_env_mis_miss_weight: too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(3 * n);
+    if (e == hipSuccess) e = d_out.alloc(4 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), dirs3, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) e = launch_env_mis_weight(env_dist(c), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out4, d_out.get(), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, "wfpt_env_mis_miss_weight");
     return WFPT_OK;
 }
 

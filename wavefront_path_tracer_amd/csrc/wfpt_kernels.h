@@ -437,8 +437,12 @@ struct TextureArgs {
 //   kEmitWeighed: the contexts that connect and weigh (WFPT_FLAG_MIS with an emitter): where the flag is 1 the hit is not dropped but adds
 //                 (thr * e) * wb (mis_hit_weight: the distance comes from `origin`, the scatter's density from the length of the ray's
 //                 direction). The extra loads happen per hit on an emitter after a diffuse bounce only. The last four fields are its alone.
+//   kEmitWeighedEnv: the contexts that weigh their map as well (WFPT_FLAG_ENV_MIS with a distribution and an emitter; include/wfpt.h
+//                 "Environment multiple importance sampling"): kEmitWeighed with the light list's density scaled by the share of the
+//                 connect samples that go to it, plq = pl * q. Its own kernel, emission_weighed_env_kernel, which takes q as a second
+//                 argument: EmissionArgs, and with it the three kernels above, stay as they are.
 constexpr uint32_t kNoEmission = 0xffffffffu;
-enum EmissionKind : int { kEmitAll, kEmitGated, kEmitWeighed };
+enum EmissionKind : int { kEmitAll, kEmitGated, kEmitWeighed, kEmitWeighedEnv };
 struct EmissionArgs {
     HitWalk w;
     float *emitted;           // the second per-sample plane: image's shape and strides
@@ -476,6 +480,11 @@ struct EnvDist {
 // cosine scatter and the connect pass's area sampling. They weigh their sample by wl and store the hit point of every diffuse hit in
 // `origin` (one float4 per pixel per sample in flight, never zeroed: read only where the connected flag is 1, which the same lane set
 // with it) for the next step's kEmitWeighed emission pass; their sampler form answers 12 floats a row (wfpt_sample_lights_mis).
+// The ENVS MIS variants (WFPT_FLAG_ENV_MIS contexts whose map has a distribution; include/wfpt.h "Environment multiple importance
+// sampling"): the ENVS variants with both branches weighed against the scatter -- the map's sample by we = pe / (pe + pb), pe = pdf * p,
+// an emitter's by wl = plq / (plq + pb), plq = pl * (1 - p) -- and `origin` stored as the MIS variants do, for the kEmitWeighedEnv emission
+// pass and for nothing else (miss_env_mis_kernel takes pb from the miss's own direction). Their sampler form
+// (wfpt_sample_environment_light_mis) answers 12 floats a row with the effective share p.
 struct ConnectArgs {
     HitWalk w;
     float *emitted;
@@ -632,14 +641,20 @@ hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
 // connected: the `emitted` plane of a context that connects to its map (WFPT_FLAG_ENV_NEE): miss_env_nee_kernel, which leaves thr = +0
 // where the pixel's connected flag (emitted.w) is 1
-hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const float *connected = nullptr);
+// weigh: miss_env_mis_kernel instead (WFPT_FLAG_ENV_MIS; needs `connected` and env's tables), which keeps thr * c there, times the balance
+// weight wb of the scatter against the map's own sampling (env_mis_weight)
+hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDist *env = nullptr, const float *connected = nullptr,
+                       bool weigh = false);
+// wfpt_env_mis_miss_weight: n rows of an un-normalised direction -> (pe, pb, wb, texel), one thread per row
+hipError_t launch_env_mis_weight(const EnvDist &env, const float *dirs3, float *out4, uint32_t n, hipStream_t s);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
-hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s);
+// q: kEmitWeighedEnv's alone, 1 - the effective environment share
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q = 1.0f);
 // wfpt_mis_hit_weight: n rows of (o.xyz, d.xyz, t, primitive) -> (pl, pb, wb, cos_l), one thread per row
 hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s);
 // grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture
 // envs: the ENVS variants (a.envd holds a distribution)
-// mis: the MIS variants (a.origin set; never with envs)
+// mis: the MIS variants (a.origin set, or the sampler form's rows out); with envs, the ENVS MIS variants
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false);
 // The sampling distribution of a map (include/wfpt.h "Environment next-event estimation"), built on the device in three launches on `s`:
 // f = Lm * s_y per texel into `f` (w * h floats) and its maximum's bits into *max_bits (zeroed by the caller); then, once the caller has

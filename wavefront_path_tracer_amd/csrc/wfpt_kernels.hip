@@ -1801,6 +1801,93 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs
     }
 }
 
+// The balance weight of a scattered ray that misses into the map (WFPT_FLAG_ENV_MIS; include/wfpt.h "Environment multiple importance
+// sampling", the miss pass, in its operation order: IEEE f32, no fma; tests/env_mis_ref.py restates it). d: the miss's direction as shade
+// scattered it, not normalised, so the scatter's density is (0.5 |d|) / pi (mis_hit_weight's identity). pe: the density with which the
+// connect pass samples d's texel -- env_lookup's own n, phi, theta, u and v restated, the texel the one that holds (u, v), sample_env's
+// pdf with the sine the lookup hands to atan2_ -- times the effective share. st > 0 or pdf > 0 failing (a NaN fails each) leaves the
+// scatter alone: pe = 0, wb = 1. The indices are clamped as floats first (a NaN u or v selects texel 0): no read outside the table.
+constexpr float kTwoPiSq = 19.739209f; // 2 pi^2
+struct EnvMisWeight {
+    float pe, pb, wb;
+    uint32_t texel;
+};
+__device__ __forceinline__ EnvMisWeight env_mis_weight(const EnvDist &e, float dx, float dy, float dz) {
+    const uint32_t w = e.env.w, h = e.env.h;
+    EnvMisWeight m;
+    const float len = sqrt_(dot3({dx, dy, dz}, {dx, dy, dz}));
+    m.pb = (0.5f * len) / kPi;
+    const float3_ n = normalize3({dx, dy, dz});
+    const float phi = atan2_(n.x, -n.z);
+    const float st = sqrt_(n.x * n.x + n.z * n.z);
+    const float theta = atan2_(st, n.y);
+    float u = phi * 0.15915494f + (0.5f + e.env.rotation);
+    u = u - __builtin_floorf(u);
+    const float v = theta * 0.31830988f;
+    const float fw = static_cast<float>(w), fh = static_cast<float>(h);
+    const uint32_t xt = static_cast<uint32_t>(__builtin_fminf(__builtin_fmaxf(__builtin_floorf(u * fw), 0.0f), fw - 1.0f));
+    const uint32_t yt = static_cast<uint32_t>(__builtin_fminf(__builtin_fmaxf(__builtin_floorf(v * fh), 0.0f), fh - 1.0f));
+    const uint32_t *row = e.row + static_cast<size_t>(yt) * w;
+    const uint32_t k = row[xt] - (xt ? row[xt - 1u] : 0u);
+    m.texel = yt * w + xt;
+    const float P = static_cast<float>(k) / static_cast<float>(e.total);
+    const float pdf = ((P * fw) * fh) / (kTwoPiSq * st);
+    if (st > 0.0f && pdf > 0.0f) {
+        m.pe = pdf * e.share;
+        m.wb = m.pb / (m.pb + m.pe);
+    } else {
+        m.pe = 0.0f;
+        m.wb = 1.0f;
+    }
+    return m;
+}
+
+// The miss pass of a context that weighs its map against the scatter (WFPT_FLAG_ENV_MIS with a distribution): miss_env_nee_kernel's shape,
+// gate first and unpipelined, with one difference: where the pixel's connected flag is 1 the throughput is not zeroed but becomes
+// (thr * c) * wb -- the connect pass counted the map with the other weight.
+__global__ __launch_bounds__(kConsumerThreads) void miss_env_mis_kernel(MissArgs a, EnvDist envd, const float *emitted) {
+    const uint32_t sample = blockIdx.y;
+    a.ctl += sample;
+    a.mq.base += sample * a.batch.queue_stride;
+    a.chunk_miss += sample * a.batch.chunk_stride;
+    a.chunk_miss_base += sample * a.batch.chunk_stride;
+    a.image += sample * a.batch.image_stride;
+    emitted += sample * a.batch.image_stride;
+    const EnvDev &env = envd.env;
+    const uint32_t n_miss = umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit);
+    const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t count = a.chunk_miss[chunk];
+        const uint32_t base = a.chunk_miss_base[chunk];
+        if (base >= n_miss) break;
+        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
+            if (base + r >= n_miss) break;
+            const size_t slot = chunk * kChunk + r;
+            const uint32_t lp = local_pixel(a.mq.pixel()[slot], a.image_width, a.tile);
+            float4 *px = pixel_of(a.image, lp);
+            const float4 thr = *px;
+            const float dx = a.mq.dx()[slot], dy = a.mq.dy()[slot], dz = a.mq.dz()[slot];
+            const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, dx, dy, dz);
+            if (reinterpret_cast<const float4 *>(emitted)[lp].w != 0.0f) {
+                const float wb = env_mis_weight(envd, dx, dy, dz).wb;
+                *px = make_float4((thr.x * c.x) * wb, (thr.y * c.y) * wb, (thr.z * c.z) * wb, thr.w);
+            } else {
+                *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+            }
+        }
+    }
+}
+
+// wfpt_env_mis_miss_weight: env_mis_weight for caller rows of an un-normalised direction, one thread per row
+__global__ __launch_bounds__(256) void env_mis_weight_kernel(EnvDist envd, const float *dirs3, float *out4, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *d = dirs3 + 3u * static_cast<size_t>(i);
+    const EnvMisWeight m = env_mis_weight(envd, d[0], d[1], d[2]);
+    float *out = out4 + 4u * static_cast<size_t>(i);
+    out[0] = m.pe; out[1] = m.pb; out[2] = m.wb; out[3] = static_cast<float>(m.texel);
+}
+
 // ================================================================================================
 // texture pass (WFPT_FLAG_TEXTURES; include/wfpt.h "Textures")
 // ================================================================================================
@@ -1949,8 +2036,11 @@ __device__ __forceinline__ void light_normal_area(const float4 *prim_geom, const
 struct MisWeight {
     float pl, pb, wb, cos_l;
 };
+// SCALED (the kEmitWeighedEnv emission pass; include/wfpt.h "Environment multiple importance sampling"): pl is plq = pl * q, the light list's
+// density times the share q of the connect samples that go to it.
+template <bool SCALED = false>
 __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, const float4 *shade_rec, uint32_t prim_kind, uint32_t prim, float nf,
-                                                    float3_ o, float3_ ph, float3_ d) {
+                                                    float3_ o, float3_ ph, float3_ d, float q = 1.0f) {
     const float3_ v = {ph.x - o.x, ph.y - o.y, ph.z - o.z};
     const float dist2 = dot3(v, v);
     const float dist = sqrt_(dist2);
@@ -1964,6 +2054,7 @@ __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, con
     m.pb = (0.5f * len) / kPi;
     if (area > 0.0f && dist2 > 0.0f && m.cos_l > 0.0f) {
         m.pl = dist2 / ((m.cos_l * area) * nf);
+        if (SCALED) m.pl = m.pl * q;
         m.wb = m.pb / (m.pb + m.pl);
     } else {
         m.pl = 0.0f;
@@ -1976,10 +2067,11 @@ __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, con
 // thr * e (gated, or weighed, by the pixel's connected flag) to the pixel's `emitted` and leaves the throughput +0: the path is dead,
 // shade scatters it all the same.
 template <int KIND>
-__global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
+__device__ __forceinline__ void emission_body(EmissionArgs a, float q) {
     const SampleHits s = sample_hits(a.w, blockIdx.y);
     float *emitted = a.emitted + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride);
-    const float4 *origin = KIND == kEmitWeighed ? a.origin + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride / 4u) : nullptr;
+    constexpr bool kWeighed = KIND == kEmitWeighed || KIND == kEmitWeighedEnv;
+    const float4 *origin = kWeighed ? a.origin + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride / 4u) : nullptr;
     for_each_shaded_hit<false>(a.w, s, [&](size_t slot, const Hit &hit) {
         const uint32_t m_idx = a.prim_em[hit.prim];
         if (m_idx == kNoEmission) return;
@@ -1989,14 +2081,23 @@ __global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs
         const float4 thr = *px, had = *out;
         if (KIND == kEmitAll || had.w == 0.0f) {
             *out = make_float4(had.x + thr.x * e.x, had.y + thr.y * e.y, had.z + thr.z * e.z, had.w);
-        } else if (KIND == kEmitWeighed) {
+        } else if (kWeighed) {
             const Hit h = load_hit<true>(a.w, s, slot); // the point and the direction: for the hits that are weighed only
             const float4 o = origin[lp];
-            const float wb = mis_hit_weight(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, a.nf, {o.x, o.y, o.z}, h.p, h.d).wb;
+            const float wb = mis_hit_weight<KIND == kEmitWeighedEnv>(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, a.nf, {o.x, o.y, o.z}, h.p, h.d,
+                                                                     q).wb;
             *out = make_float4(had.x + (thr.x * e.x) * wb, had.y + (thr.y * e.y) * wb, had.z + (thr.z * e.z) * wb, had.w);
         }
         *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
     });
+}
+template <int KIND>
+__global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs a) {
+    emission_body<KIND>(a, 1.0f);
+}
+// kEmitWeighedEnv: q = 1 - the effective environment share
+__global__ __launch_bounds__(kConsumerThreads) void emission_weighed_env_kernel(EmissionArgs a, float q) {
+    emission_body<kEmitWeighedEnv>(a, q);
 }
 
 // wfpt_mis_hit_weight: mis_hit_weight for caller rows (o.xyz, d.xyz, t, the primitive index as a float), one thread per row; a primitive
@@ -3311,7 +3412,7 @@ __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, fl
 // two tables, a direction inside it, its probability and the map's value there. Fills s.w (the shadow ray's direction), s.e (env_lookup),
 // s.G (Genv = (cos_s / pi) / (pdf * share)) and s.prim (y * w + x). False: no contribution (a NaN fails each comparison). The selections
 // clamp T and C into their tables (a NaN or negative draw of a caller's row selects 0), so every index read lies inside the tables.
-constexpr float kTwoPiSq = 19.739209f; // 2 pi^2
+template <bool MIS = false>
 __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1, float u2, float u3, float u4, float share, LightSample &s) {
     const uint32_t w = d.env.w, h = d.env.h;
     const double ft = static_cast<double>(d.total);
@@ -3349,6 +3450,10 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
     const float cos_s = dot3(n, s.w);
     s.e = env_lookup(d.env.texels, w, h, d.env.intensity, d.env.rotation, s.w.x, s.w.y, s.w.z);
     s.G = (cos_s / kPi) / (pdf * share);
+    if (MIS) { // pe and pb: the direction's densities under this sampling, share included, and under shade's scatter
+        s.pl = pdf * share;
+        s.pb = cos_s / kPi;
+    }
     return st > 0.0f && cos_s > 0.0f && pdf > 0.0f;
 }
 
@@ -3366,6 +3471,9 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // MIS (WFPT_FLAG_MIS contexts with an emitter; never with ENVS): the sample is weighed by wl = pl / (pl + pb), and every diffuse hit stores
 // its point in a.origin for the next step's weighed emission pass (one 16-byte store next to the `emitted` update of the same pixel); the
 // sampler form answers 12 floats a row. With MIS false the source is the one above.
+// ENVS and MIS (WFPT_FLAG_ENV_MIS contexts whose map has a distribution; include/wfpt.h "Environment multiple importance sampling"): the
+// map's sample is weighed by we = pe / (pe + pb), pe = pdf * share, an emitter's by wl = plq / (plq + pb), plq = pl * share, each with
+// the share of its own branch; the point is stored as above. The sampler form is the map's, with the effective share and 12 floats a row.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
     extern __shared__ float4 lds[];
@@ -3406,6 +3514,7 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
             if (ENVS) {
                 u1 = row[6]; u2 = row[7]; u3 = row[8]; u4 = row[9];
                 to_env = true;
+                if (MIS) share = a.envd.share;
             } else {
                 u0 = row[6]; u1 = row[7]; u2 = row[8];
             }
@@ -3465,7 +3574,7 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
         }
         LightSample s;
         bool lit = false, occluded = false;
-        if (ENVS && to_env) lit = sample_env(a.envd, n, u1, u2, u3, u4, share, s);
+        if (ENVS && to_env) lit = sample_env<MIS>(a.envd, n, u1, u2, u3, u4, share, s);
         else if (live) lit = sample_light<PRIM, TEX, MIS>(a, p, n, u0, u1, u2, s);
         if (lit) {
 #if WFPT_STAMPS
@@ -3489,9 +3598,11 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
                 occluded = verdict == kOccHit;
             }
         }
+        if (ENVS && MIS && !to_env && lit) s.pl = s.pl * share; // plq: the light list's density times the share of the samples that go to it
         if (MIS && live && sampler) { // (q, primitive, (e_q G) wl, occluded, pl, pb, wl, 0): zeros where the sample contributes nothing
             float *row = a.sample_out + 12u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
             const float wl = lit ? s.pl / (s.pl + s.pb) : 0.0f; // (sample_light sets pl and pb only where it answers true)
+            if (ENVS) s.q = s.w; // (wdir, texel, (e Genv) we, occluded, pe, pb, we, 0)
             row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
             row[3] = static_cast<float>(s.prim);
             row[4] = lit ? (s.e.x * s.G) * wl : 0.0f; row[5] = lit ? (s.e.y * s.G) * wl : 0.0f; row[6] = lit ? (s.e.z * s.G) * wl : 0.0f;
@@ -3501,7 +3612,11 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
             const float4 thr = *px, had = *out;
             const size_t lp4 = static_cast<size_t>(out - reinterpret_cast<float4 *>(a.emitted)); // the pixel's float4 in `emitted`: `origin` has its shape
             a.origin[lp4] = make_float4(p.x, p.y, p.z, 0.0f);
-            if (lit && !occluded) {
+            if (ENVS && lit && !occluded && !to_env) { // an emitter of an ENVS context: the division by its share before the weight
+                const float wl = s.pl / (s.pl + s.pb);
+                *out = make_float4(had.x + ((((thr.x * rec1.x) * s.e.x) * s.G) / share) * wl, had.y + ((((thr.y * rec1.y) * s.e.y) * s.G) / share) * wl,
+                                   had.z + ((((thr.z * rec1.z) * s.e.z) * s.G) / share) * wl, 1.0f);
+            } else if (lit && !occluded) {
                 const float wl = s.pl / (s.pl + s.pb);
                 *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) * wl, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) * wl,
                                    had.z + (((thr.z * rec1.z) * s.e.z) * s.G) * wl, 1.0f);
@@ -4219,12 +4334,15 @@ hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const float *connected) {
+hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const EnvDist *env, const float *connected, bool weigh) {
     if (grid == 0) return hipSuccess;
-    if (env && connected)
-        hipLaunchKernelGGL(miss_env_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *env, connected);
+    if (weigh && !(env && connected && env->row)) return hipErrorInvalidValue;
+    if (weigh)
+        hipLaunchKernelGGL(miss_env_mis_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *env, connected);
+    else if (env && connected)
+        hipLaunchKernelGGL(miss_env_nee_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, env->env, connected);
     else if (env)
-        hipLaunchKernelGGL(miss_env_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, *env);
+        hipLaunchKernelGGL(miss_env_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a, env->env);
     else
         hipLaunchKernelGGL(miss_kernel, dim3(grid, a.batch.n), dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
@@ -4249,8 +4367,12 @@ hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s) {
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q) {
     if (grid == 0) return hipSuccess;
+    if (kind == kEmitWeighedEnv) {
+        hipLaunchKernelGGL(emission_weighed_env_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a, q);
+        return hipGetLastError();
+    }
     void (*const k)(EmissionArgs) = kind == kEmitWeighed ? emission_kernel<kEmitWeighed>
                                     : kind == kEmitGated ? emission_kernel<kEmitGated>
                                                          : emission_kernel<kEmitAll>;
@@ -4261,6 +4383,12 @@ hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t gr
 hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_env_mis_weight(const EnvDist &env, const float *dirs3, float *out4, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(env_mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, env, dirs3, out4, n);
     return hipGetLastError();
 }
 
@@ -4349,9 +4477,12 @@ template <bool TEX, bool ENVS, bool MIS = false> struct ConnectK {
 };
 ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = false, bool mis = false) {
     const bool lds = sc.lds_scene != 0;
-    if (mis) return tex ? pick_variant<ConnectK<true, false, true>>(sc, exact, lds) : pick_variant<ConnectK<false, false, true>>(sc, exact, lds);
-    if (envs) return tex ? pick_variant<ConnectK<true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true>>(sc, exact, lds);
-    return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
+    // (the ENVS MIS variants are named last: the order of instantiation numbers the labels of the walks' inline assembly, and the earlier
+    // variants keep the parent's instructions to the label, tools/isa_compare.py)
+    if (mis && !envs) return tex ? pick_variant<ConnectK<true, false, true>>(sc, exact, lds) : pick_variant<ConnectK<false, false, true>>(sc, exact, lds);
+    if (envs && !mis) return tex ? pick_variant<ConnectK<true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true>>(sc, exact, lds);
+    if (!envs) return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
+    return tex ? pick_variant<ConnectK<true, true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true, true>>(sc, exact, lds);
 }
 } // namespace
 
@@ -4359,7 +4490,8 @@ hipError_t connect_prepare(const SceneDev &scene) {
     for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
         const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true),
                                                connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true),
-                                               connect_variant(scene, exact, false, false, true), connect_variant(scene, exact, true, false, true));
+                                               connect_variant(scene, exact, false, false, true), connect_variant(scene, exact, true, false, true),
+                                               connect_variant(scene, exact, false, true, true), connect_variant(scene, exact, true, true, true));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -4367,7 +4499,7 @@ hipError_t connect_prepare(const SceneDev &scene) {
 
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis) {
     if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
-    if (mis && (envs || !a.origin)) return hipErrorInvalidValue; // (a.origin: the plane, or the sampler form's rows out)
+    if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
     hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }

@@ -411,6 +411,20 @@ class PathTracer {
         check(wfpt_mis_hit_weight(ctx_, in8.data(), in8.size() / 8, out.data()));
         return out;
     }
+    // Environment multiple importance sampling (the four flags of environment next-event estimation | WFPT_FLAG_ENV_MIS, include/wfpt.h
+    // "Environment multiple importance sampling"): the map's connect samples and the scattered rays' misses, both weighed.
+    // rows of (p.xyz, n.xyz, u1, u2, u3, u4) -> rows of (wdir.xyz, texel index, (e Genv) we rgb, occluded, pe, pb, we, 0)
+    std::vector<float> sample_environment_light_mis(const std::vector<float> &in10) {
+        std::vector<float> out(in10.size() / 10 * 12);
+        check(wfpt_sample_environment_light_mis(ctx_, in10.data(), in10.size() / 10, out.data()));
+        return out;
+    }
+    // rows of an un-normalised direction -> rows of (pe, pb, wb, texel index)
+    std::vector<float> env_mis_miss_weight(const std::vector<float> &dirs3) {
+        std::vector<float> out(dirs3.size() / 3 * 4);
+        check(wfpt_env_mis_miss_weight(ctx_, dirs3.data(), dirs3.size() / 3, out.data()));
+        return out;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
