@@ -242,12 +242,14 @@ enum {
                                         scattered rays and the shadow rays of the connect pass are both kept, weighed by the balance
                                         heuristic. Needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with WFPT_FLAG_ENV_NEE. With no emitter
                                         set the context renders bit for bit as without the flag, and launches the same kernels. */,
-    WFPT_FLAG_ENV_MIS = 1u << 18     /* multiple importance sampling between the environment map and the scatter, see "Environment multiple
+    WFPT_FLAG_ENV_MIS = 1u << 18,    /* multiple importance sampling between the environment map and the scatter, see "Environment multiple
                                         importance sampling" below: the map's connect samples and the misses of scattered rays are both
                                         kept, weighed by the balance heuristic, and so are the emitters' samples and hits. Needs
                                         WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and WFPT_FLAG_ENV_NEE, refused with
                                         WFPT_FLAG_MIS. With no map set (or a black one) the context renders bit for bit as without the
                                         flag, and launches the same kernels. */
+    WFPT_FLAG_NO_TILE_LISTS = 1u << 19 /* the first fused launch walks the tree for every tile instead of testing its tile's candidate list,
+                                        see "Tile lists" below (A/B runs and tests; the results are the same bits either way) */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -1020,6 +1022,32 @@ int wfpt_debug_read_stamps_ex(wfpt_ctx *ctx, int which, uint64_t out[16], int re
  * `nodes` and verifies that every quantised child box encloses the binary node's box and that the two trees have the
  * same leaves. counts = {four-wide nodes, depth, leaf children, inner children}. */
 int wfpt_debug_bvh4(const wfpt_bvh_node *nodes, uint32_t n_nodes, uint32_t counts[4]);
+/* ------------------------------------------------------------------ Tile lists
+ * A wave of the first fused launch traces the 64 primary rays of one 8x8 pixel tile: one lens, one small patch of the focus plane, the
+ * same for every sample while the camera stands. WFPT_LOOP_FUSED contexts whose scene lies in LDS and is walked by the default
+ * (conservative) traversal therefore keep, per tile, the list of every leaf whose margin-grown box a ray of the tile can reach -- one
+ * 64-byte record: WFPT_TILE_LIST_CAP words `left_first | prim_count << 16` in ascending node order, the rest 0; word 0 =
+ * WFPT_TILE_NO_LIST where the tile has more candidates or the camera is one the bound does not cover -- and the first launch tests the
+ * listed leaves' primitives instead of walking the tree from the root (no list: it walks, as every other context does). The results are
+ * bit for bit those of the walk (a superset of what the reference tests, the verdict on the final hit's leaf, the
+ * hand-over to the reference's own walk). wfpt_create, wfpt_update_render_parameters and every change of the scene leave every tile
+ * without a list; the table is built on the device before the SECOND batch rendered since (a camera that moves before every frame never
+ * pays for a table it would use once). WFPT_FLAG_NO_TILE_LISTS turns it off.
+ *   wfpt_tile_lists_host: the same table computed on the host (no GPU needed), record for record. nodes_ch: 8 floats per node as
+ *     wfpt_debug_nodes_ch writes them; n_tiles = ceil(width / 8) * (the 8-row bands k with k % tile_world == tile_rank).
+ *   wfpt_debug_nodes_ch: the margin-grown (centre | left_first), (half-extent | prim_count) boxes a context of this tree and camera
+ *     walks; WFPT_ERR_UNSUPPORTED where a box is not finite (such a context walks the reference's boxes and keeps no lists).
+ *   wfpt_debug_read_tile_lists: the context's table (blocking; builds it at once if it is not built). *n_tiles: in, the records `records`
+ *     holds; out, the context's tiles -- 0 when the context keeps no lists, and nothing is written then (nor with records == NULL: the
+ *     count alone).
+ *   wfpt_tile_lists_timing_ms: the device time of the last build and the builds since wfpt_create (blocking). */
+#define WFPT_TILE_LIST_CAP 16u
+#define WFPT_TILE_NO_LIST 0xffffffffu
+int wfpt_tile_lists_host(const float *nodes_ch, uint32_t n_nodes, const wfpt_gpu_camera *camera, const float inv_proj[16], const float view[16],
+                         uint32_t width, uint32_t height, uint32_t tile_rank, uint32_t tile_world, uint32_t *records, uint32_t n_tiles);
+int wfpt_debug_nodes_ch(const wfpt_bvh_node *nodes, uint32_t n_nodes, const wfpt_gpu_camera *camera, float *nodes_ch);
+int wfpt_debug_read_tile_lists(wfpt_ctx *ctx, uint32_t *records, uint32_t *n_tiles);
+int wfpt_tile_lists_timing_ms(wfpt_ctx *ctx, float *ms_last, uint32_t *builds);
 /* Static facts about the built library, e.g. "gfx950;chunk=512;..." */
 const char *wfpt_build_info(void);
 

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -47,6 +47,8 @@ FLAG_MIS = 1 << 17
 # the map and the emitters weighed against the scatter (include/wfpt.h "Environment multiple importance sampling"); needs the four flags
 # of FLAG_ENV_NEE, refused with FLAG_MIS
 FLAG_ENV_MIS = 1 << 18
+FLAG_NO_TILE_LISTS = 1 << 19  # the first fused launch walks the tree for every tile (include/wfpt.h "Tile lists")
+TILE_LIST_CAP, TILE_NO_LIST = 16, 0xFFFFFFFF
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_luminance": 4.0, "sigma_normal": 128.0, "sigma_depth": 1.0, "sigma_albedo": 0.5}
@@ -362,6 +364,10 @@ def lib():
         "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
         "wfpt_sample_environment_light_mis": (i32, [vp, vp, sz, vp]),
         "wfpt_env_mis_miss_weight": (i32, [vp, vp, sz, vp]),
+        "wfpt_tile_lists_host": (i32, [vp, u32, vp, vp, vp, u32, u32, u32, u32, vp, u32]),
+        "wfpt_debug_nodes_ch": (i32, [vp, u32, vp, vp]),
+        "wfpt_debug_read_tile_lists": (i32, [vp, vp, C.POINTER(u32)]),
+        "wfpt_tile_lists_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what wfpt.h declares
@@ -385,6 +391,32 @@ def abi_symbols():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ---- tile lists (include/wfpt.h "Tile lists"): the host twin of the device builder, no GPU needed
+def nodes_ch(nodes, gpu_camera):
+    """The margin-grown (centre | left_first), (half-extent | prim_count) boxes a context of this tree and camera walks: float32
+    [n_nodes, 8] (the two index words as their bits)."""
+    out = np.zeros((len(nodes), 8), np.float32)
+    st = lib().wfpt_debug_nodes_ch(_p(nodes), len(nodes), _p(gpu_camera), _p(out))
+    if st != 0:
+        raise WfptError(st, lib().wfpt_last_error(None).decode())
+    return out
+
+
+def tile_lists_host(nodes, gpu_camera, inv_proj, view, width, height, tile_rank=0, tile_world=1):
+    """The per-tile candidate lists of the first fused launch, computed on the host: uint32 [tiles, TILE_LIST_CAP] records (leaf words
+    `left_first | prim_count << 16` in ascending node order, then 0; record[0] == TILE_NO_LIST: the tile keeps no list)."""
+    ch = nodes_ch(nodes, gpu_camera)
+    gx, bands = (width + 7) // 8, (height + 7) // 8
+    gy = (bands - tile_rank + tile_world - 1) // tile_world if bands > tile_rank else 0
+    out = np.zeros((gx * gy, TILE_LIST_CAP), np.uint32)
+    inv_proj, view = np.ascontiguousarray(inv_proj, np.float32), np.ascontiguousarray(view, np.float32)
+    st = lib().wfpt_tile_lists_host(_p(ch), len(nodes), _p(gpu_camera), _p(inv_proj), _p(view), width, height, tile_rank, tile_world,
+                                    _p(out), gx * gy)
+    if st != 0:
+        raise WfptError(st, "wfpt_tile_lists_host: invalid argument")
+    return out
 
 
 def device_count():
@@ -1227,6 +1259,24 @@ class PathTracer:
             raise ValueError(f"denoise_to_tensor: tensor must live on this context's device (cuda:{self._params.device})")
         self._check(lib().wfpt_denoise_to_device(self.handle, C.byref(p), C.c_void_p(tensor.data_ptr()), 4 * n))
         return tensor
+
+    # ---- tile lists (include/wfpt.h "Tile lists")
+    def read_tile_lists(self):
+        """The context's per-tile candidate lists as uint32 [tiles, TILE_LIST_CAP] (blocking; see tile_lists_host), or None where
+        the context keeps none (its first launch walks the tree for every tile)."""
+        n = C.c_uint32(0)
+        self._check(lib().wfpt_debug_read_tile_lists(self.handle, None, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros((n.value, TILE_LIST_CAP), np.uint32)
+        self._check(lib().wfpt_debug_read_tile_lists(self.handle, _p(out), C.byref(n)))
+        return out
+
+    def tile_lists_timing(self):
+        """(milliseconds of the last build of the tile lists on the device, builds since creation)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_tile_lists_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def denoise_timing(self):
         """(milliseconds of the last denoise call's launches, denoise calls since creation)."""

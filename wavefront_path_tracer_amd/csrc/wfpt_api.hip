@@ -279,6 +279,19 @@ struct wfpt_ctx {
     uint32_t accumulate_grid = 0;
     uint32_t progress_frame = 0, accumulated_samples = 0;
     bool dev_frame_valid = false;
+    // the first fused launch's per-tile candidate lists (include/wfpt.h "Tile lists"): [capacity / 64][kTileListCap] words, allocated once
+    // (the captured graphs hold its address), rebuilt before the next batch whenever the camera, the viewport or the scene has changed
+    // A camera that moves before every frame would pay a build per frame for lists it uses once (profiles/r06_tile_lists_ab.txt), so a
+    // change only marks every tile "no list" (one memset; the first launch then walks) and the table is built before the SECOND batch the
+    // camera and the scene have been kept for: tl_kept says that a batch has been rendered since the last change.
+    DeviceBuffer<uint32_t> tile_lists;
+    bool tile_lists_valid = false;
+    bool tl_cleared = true;     // every record reads "no list" (the state after wfpt_create and after a change)
+    bool tl_kept = false;
+    EventPair tl_ev;
+    bool tl_pending = false;    // tl_ev brackets a build whose time has not been read yet
+    float tl_ms = 0.0f;         // the last build (wfpt_tile_lists_timing_ms)
+    uint32_t tl_builds = 0;
 
     std::map<uint32_t, Graph> graphs; // captured chain, keyed by samples per launch
 
@@ -705,6 +718,12 @@ wfpt_loop_kind loop_of(const wfpt_ctx *c) {
     if (c->rec_dense.get() && !c->scene.exact) return WFPT_LOOP_REFILL;
     return use_binned(c) ? WFPT_LOOP_FUSED_BINNED : WFPT_LOOP_FUSED;
 }
+// The per-tile candidate lists of the first fused launch (include/wfpt.h "Tile lists"): kept by the contexts whose first launch is
+// bounce_kernel<first> over a scene in LDS with the default walk, null for every other one (their first launch walks the tree)
+const uint4 *tile_lists_of(const wfpt_ctx *c) {
+    const bool keeps = c->tile_lists.get() && loop_of(c) == WFPT_LOOP_FUSED && c->scene.lds_scene && !c->scene.exact && c->scene.nodes_ch;
+    return keeps ? reinterpret_cast<const uint4 *>(c->tile_lists.get()) : nullptr;
+}
 uint32_t bounce_grid(const wfpt_ctx *c, uint32_t n) {
     // hit items + miss items never exceed 1.25 work items per segment
     const uint64_t items = (static_cast<uint64_t>(c->n_chunks_max) * 5u / 4u + 1u) * n;
@@ -766,7 +785,11 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
     const hipStream_t st = c->stream.get();
     const uint32_t grid = bounce_grid(c, nb);
     const EnvDev *env = env_of(c);
-    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_bounce(bounce_args(c, 1, 0, nb), kBounceFirst, grid, st, env != nullptr); }));
+    WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] {
+                 BounceArgs a = bounce_args(c, 1, 0, nb);
+                 a.tile_lists = tile_lists_of(c);
+                 return launch_bounce(a, kBounceFirst, grid, st, env != nullptr);
+             }));
     for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
         const int par = static_cast<int>(b & 1u);
         const bool last = b + 1 >= c->p.max_wavefronts;
@@ -911,10 +934,23 @@ void drop_history(wfpt_ctx *c) {
     c->tp_read_ok = false;
 }
 
+// The camera, the viewport or the scene has changed: the lists no longer hold. Every record becomes "no list" (0xff bytes: word 0 =
+// kTileNoList), ordered on the stream behind the batches that still read the old table.
+int drop_tile_lists(wfpt_ctx *c) {
+    c->tile_lists_valid = false;
+    c->tl_kept = false;
+    if (!c->tile_lists.get() || c->tl_cleared) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipMemsetAsync(c->tile_lists.get(), 0xff, sizeof(uint32_t) * c->tile_lists.size(), c->stream.get()));
+    c->tl_cleared = true;
+    return WFPT_OK;
+}
+
 // The scene the kernels see has changed (its primitives or its environment map): the captured graphs hold the old one in their
 // arguments, the stage API's path records, the temporal history and the accumulation show it.
 int scene_changed(wfpt_ctx *c) {
     c->graphs.clear();
+    if (int r = drop_tile_lists(c); r != WFPT_OK) return r;
     c->hit_rec_valid = false;
     drop_history(c);
     return wfpt_reset_progress(c);
@@ -927,6 +963,7 @@ void batch_rendered(wfpt_ctx *c, uint32_t nb) {
     c->progress_frame += nb;      // the device advanced ctl->frame.frame itself
     c->accumulated_samples += nb; // pt:363
     c->last_slot = nb - 1;
+    c->tl_kept = true;
 }
 
 int ensure_device_frame(wfpt_ctx *c) {
@@ -937,10 +974,43 @@ int ensure_device_frame(wfpt_ctx *c) {
     return WFPT_OK;
 }
 
+// Builds the table where a change has dropped it: on the stream, outside the captured graphs (its address never changes), guarded by a
+// flag as the frame uniform is. Not a wfpt_stage, and not in a batch's event record either (timed() brackets what enqueue_batch
+// enqueues, which is what a graph captures; the build must stay outside): its time is kept beside the context, with an event pair of
+// its own (wfpt_tile_lists_timing_ms). `now`: build although no batch has been rendered since the last change (the read-back).
+#ifndef WFPT_TILE_LISTS_EAGER
+#define WFPT_TILE_LISTS_EAGER 0 // tuning builds: 1 = build before the first batch after every change (the A/B of the deferral)
+#endif
+int ensure_tile_lists(wfpt_ctx *c, bool now = false) {
+    if (c->tile_lists_valid || !tile_lists_of(c)) return WFPT_OK;
+    if (!now && !WFPT_TILE_LISTS_EAGER && !c->tl_kept) return WFPT_OK; // (every record reads "no list": this batch walks)
+    TileListArgs a{};
+    a.nodes_ch = c->scene.nodes_ch;
+    a.n_nodes = c->scene.n_nodes;
+    a.camera = c->camera.get();
+    a.gx = c->tiles_x;
+    a.gy = c->tiles_y_local;
+    a.width = c->width;
+    a.height = c->height;
+    a.tile = c->tile;
+    a.records = c->tile_lists.get();
+    if (static_cast<size_t>(a.gx) * a.gy * kTileListCap > c->tile_lists.size()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "tile lists: the viewport exceeds the table");
+    WFPT_HIP(c, c->tl_ev.create());
+    WFPT_HIP(c, hipEventRecord(c->tl_ev.start.get(), c->stream.get()));
+    WFPT_HIP(c, launch_tile_lists(a, c->stream.get()));
+    WFPT_HIP(c, hipEventRecord(c->tl_ev.stop.get(), c->stream.get()));
+    c->tl_pending = true;
+    c->tl_builds += 1;
+    c->tile_lists_valid = true;
+    c->tl_cleared = false;
+    return WFPT_OK;
+}
+
 // Renders `nb` samples (frames progress_frame+1 ...) with one pass of the chain; 1 <= nb <= batch_max.
 int render_batch(wfpt_ctx *c, uint32_t nb) {
     WFPT_HIP(c, hipSetDevice(c->device));
     if (int r = ensure_device_frame(c); r != WFPT_OK) return r;
+    if (int r = ensure_tile_lists(c); r != WFPT_OK) return r;
     if (c->p.flags & WFPT_FLAG_NO_GRAPH) {
         if (int r = enqueue_batch(c, nullptr, nb); r != WFPT_OK) return r;
     } else {
@@ -1557,6 +1627,13 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
             CREATE_HIP(c->f_chunk_miss[k].alloc_zeroed(counts, st));
         }
         CREATE_HIP(c->first_seg.alloc_zeroed(counts, st));
+        if (!(c->p.flags & WFPT_FLAG_NO_TILE_LISTS)) {
+            // One record per 64 ray slots of the CAPACITY, not of the viewport: a wave of the first launch reads the record of its slots'
+            // tile before it knows whether any of them is live, and the last work item reaches up to the next multiple of kChunk, which
+            // the capacity is. All "no list" (0xff bytes) until a build: a record is never read as garbage.
+            CREATE_HIP(c->tile_lists.alloc(static_cast<size_t>(c->capacity / 64u) * kTileListCap));
+            CREATE_HIP(hipMemsetAsync(c->tile_lists.get(), 0xff, sizeof(uint32_t) * c->tile_lists.size(), st));
+        }
         if (c->bin_capable) {
             for (int k = 0; k < 2; ++k) CREATE_HIP(c->f_cls[k].alloc_zeroed(counts * ClsPack<kBinClasses>::kWords, st));
             CREATE_HIP(c->cls_table.alloc_zeroed(counts * kBinClasses, st));
@@ -1642,6 +1719,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_world = chunks;
         p.max_pixels = 0;
         p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
         wfpt_ctx *c = create_impl(&p, spheres, triangles, n_prims, materials, n_materials, nodes, n_nodes, camera, inv_proj, view);
@@ -1719,6 +1797,7 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
     WFPT_HIP(c, hipMemcpy(c->camera.get(), &cam, sizeof cam, hipMemcpyHostToDevice));       // pt:259-272
     if (int r = wfpt_reset_progress(c); r != WFPT_OK) return r;
     c->graphs.clear(); // grid shapes (and the kernel variant) are baked into the captured graph
+    if (int r = drop_tile_lists(c); r != WFPT_OK) return r;
     c->h_camera = *camera;
     std::memcpy(c->h_inv_proj, inv_proj, sizeof c->h_inv_proj);
     std::memcpy(c->h_view, view, sizeof c->h_view);
@@ -1953,6 +2032,7 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
     while (n_samples > 0) {
         const uint32_t nb = std::min(n_samples, c->batch_max); // same batching as wfpt_render
         if (int r = ensure_device_frame(c); r != WFPT_OK) return r;
+        if (int r = ensure_tile_lists(c); r != WFPT_OK) return r;
         std::vector<EventRec> ev;
         if (int r = enqueue_batch(c, &ev, nb); r != WFPT_OK) return r;
         WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
@@ -2757,6 +2837,42 @@ int wfpt_debug_read_stamps_ex(wfpt_ctx *c, int which, uint64_t out[16], int rese
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
     WFPT_HIP(c, hipMemcpy(out, c->d_stamps.get() + 16 * which, sizeof(uint64_t) * 16, hipMemcpyDeviceToHost));
     if (reset) WFPT_HIP(c, hipMemset(c->d_stamps.get() + 16 * which, 0, sizeof(uint64_t) * 16));
+    return WFPT_OK;
+}
+
+int wfpt_debug_nodes_ch(const wfpt_bvh_node *nodes, uint32_t n_nodes, const wfpt_gpu_camera *camera, float *nodes_ch) {
+    if (!nodes || !camera || !nodes_ch || n_nodes == 0) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_debug_nodes_ch: null or empty argument");
+    float reach[3], extent[3];
+    camera_reach(*camera, reach);
+    std::vector<float4> ch;
+    if (!build_nodes_ch(nodes, n_nodes, reach, ch, extent)) return fail(nullptr, WFPT_ERR_UNSUPPORTED, "wfpt_debug_nodes_ch: a box is not finite");
+    std::memcpy(nodes_ch, ch.data(), sizeof(float4) * ch.size());
+    return WFPT_OK;
+}
+
+int wfpt_debug_read_tile_lists(wfpt_ctx *c, uint32_t *records, uint32_t *n_tiles) {
+    if (!c || !n_tiles) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_debug_read_tile_lists: null argument");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    const uint32_t have = *n_tiles, tiles = tile_lists_of(c) ? c->tiles_x * c->tiles_y_local : 0u;
+    *n_tiles = tiles;
+    if (tiles == 0 || !records) return WFPT_OK; // (records == NULL: the count alone)
+    if (have < tiles) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_debug_read_tile_lists: the buffer holds fewer records than the context has tiles");
+    if (int r = ensure_tile_lists(c, true); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipMemcpyAsync(records, c->tile_lists.get(), sizeof(uint32_t) * kTileListCap * tiles, hipMemcpyDeviceToHost, c->stream.get()));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    return WFPT_OK;
+}
+
+int wfpt_tile_lists_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *builds) {
+    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_tile_lists_timing_ms: null context");
+    if (c->tl_pending) {
+        WFPT_HIP(c, hipSetDevice(c->device));
+        WFPT_HIP(c, hipEventSynchronize(c->tl_ev.stop.get()));
+        WFPT_HIP(c, hipEventElapsedTime(&c->tl_ms, c->tl_ev.start.get(), c->tl_ev.stop.get()));
+        c->tl_pending = false;
+    }
+    if (ms_last) *ms_last = c->tl_ms;
+    if (builds) *builds = c->tl_builds;
     return WFPT_OK;
 }
 

@@ -7,6 +7,7 @@
 // Citations are relative to the reference root (wc = wavefront_common/src).
 #include "wfpt.h"
 #include "wfpt_bvh4.h"
+#include "wfpt_tile_lists.h"
 
 #include <algorithm>
 #include <cmath>
@@ -726,6 +727,41 @@ int wfpt_write_png_rgb8(const char *path, const uint8_t *rgb, uint32_t width, ui
     const bool ok = std::fwrite(sig, 1, 8, f) == 8 && png_chunk(f, "IHDR", ihdr) && png_chunk(f, "IDAT", z) && png_chunk(f, "IEND", {});
     std::fclose(f);
     return ok ? WFPT_OK : WFPT_ERR_INVALID_ARGUMENT;
+}
+
+// The per-tile candidate lists of the first fused launch (wfpt_tile_lists.h), in plain loops: the statement of what the device builder
+// (tile_lists_kernel) computes, record for record, and what the tests without a GPU call. nodes_ch: 8 floats per node, (centre |
+// left_first), (half-extent | prim_count), as wfpt_debug_nodes_ch returns them.
+int wfpt_tile_lists_host(const float *nodes_ch, uint32_t n_nodes, const wfpt_gpu_camera *camera, const float inv_proj[16], const float view[16],
+                         uint32_t width, uint32_t height, uint32_t tile_rank, uint32_t tile_world, uint32_t *records, uint32_t n_tiles) {
+    if (!nodes_ch || !camera || !inv_proj || !view || !records || n_nodes == 0 || width == 0 || height == 0 || tile_world == 0 || tile_rank >= tile_world)
+        return WFPT_ERR_INVALID_ARGUMENT;
+    const uint32_t gx = (width + 7u) / 8u, bands = (height + 7u) / 8u;
+    const uint32_t gy = bands > tile_rank ? (bands - tile_rank + tile_world - 1u) / tile_world : 0u;
+    if (static_cast<uint64_t>(gx) * gy != n_tiles) return WFPT_ERR_INVALID_ARGUMENT;
+    auto word = [&](uint32_t i, int k) { uint32_t u; std::memcpy(&u, nodes_ch + 8u * static_cast<size_t>(i) + k, 4); return u; };
+    const bool root_leaf = word(0, 7) != 0u; // the root's box is never tested (ex:84): the walk decides
+    for (uint32_t tile = 0; tile < n_tiles; ++tile) {
+        uint32_t *rec = records + static_cast<size_t>(tile) * wfpt::kTileListCap;
+        uint32_t x0, y0, count = 0;
+        wfpt::tile_origin(tile, gx, tile_rank, tile_world, x0, y0);
+        const wfpt::TileBundle b = wfpt::tile_bundle(*camera, inv_proj, view, x0, y0, width, height);
+        bool list = b.ok != 0u && !root_leaf;
+        for (uint32_t k = 0; k < wfpt::kTileListCap; ++k) rec[k] = 0u;
+        for (uint32_t i = 0; i < n_nodes && list; ++i) {
+            const uint32_t w = wfpt::tile_leaf_word(i, word(i, 3), word(i, 7));
+            if (w == 0u) continue;
+            const float *n = nodes_ch + 8u * static_cast<size_t>(i);
+            if (w != wfpt::kTileNoList && !wfpt::tile_bundle_reaches(b, n[0], n[1], n[2], n[4], n[5], n[6])) continue;
+            if (w == wfpt::kTileNoList || count == wfpt::kTileListCap) list = false;
+            else rec[count++] = w;
+        }
+        if (!list) {
+            for (uint32_t k = 0; k < wfpt::kTileListCap; ++k) rec[k] = 0u;
+            rec[0] = wfpt::kTileNoList;
+        }
+    }
+    return WFPT_OK;
 }
 
 } // extern "C"

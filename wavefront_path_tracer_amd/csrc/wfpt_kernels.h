@@ -8,6 +8,7 @@
 #include "wfpt.h"
 #include "wfpt_bvh4.h"
 #include "wfpt_device_math.h"
+#include "wfpt_tile_lists.h"
 
 namespace wfpt {
 
@@ -281,6 +282,20 @@ struct BounceArgs {
     const uint2 *cls_table;         // in:  [n][segments][K] {class-k hits before this segment, first slot of the segment's class-k run}
     const uint32_t *first_seg_cls;  // in:  [n][K][segments]: segment that holds class-k hit number kChunk * run
     uint32_t *out_cls;              // out: [n][segments][words] per-segment class totals, packed 10 bits each (ClsPack)
+    // ---- first launch of WFPT_LOOP_FUSED over a scene in LDS, default walk: the per-tile candidate lists (wfpt_tile_lists.h), one
+    // 64-byte record per local tile; null = every wave walks the tree
+    const uint4 *tile_lists;
+};
+
+// The builder of the per-tile candidate lists (tile_lists_kernel): one wave per local tile, lanes over the nodes
+struct TileListArgs {
+    const float4 *nodes_ch;
+    uint32_t n_nodes;
+    const CameraDev *camera;
+    uint32_t gx, gy;       // tiles of this context (gy counts this rank's bands)
+    uint32_t width, height;
+    Tiling tile;
+    uint32_t *records;     // [gx * gy][kTileListCap]
 };
 
 // Packed counters of the class-binned compaction: field f of a word array sits in word f / 3 at bit 10 * (f % 3); a field holds at most
@@ -629,6 +644,7 @@ hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per s
 // env_dirs: the variant of WFPT_FLAG_ENVIRONMENT contexts with a map: misses carry direction.x and .z, no miss items (launch_miss with the
 // map lights them)
 hipError_t launch_bounce(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s, bool env_dirs = false);
+hipError_t launch_tile_lists(const TileListArgs &a, hipStream_t s);
 hipError_t launch_bounce_binned(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s); // LDS-resident scenes only
 hipError_t launch_scan_binned(const ScanBinnedArgs &a, hipStream_t s);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t s);

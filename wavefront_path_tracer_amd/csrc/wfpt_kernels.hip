@@ -2207,6 +2207,73 @@ __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32
 //      kBounceMiddle: hit items = 512 consecutive hits h of the previous wavefront: shade -> trace; then miss items.
 //      kBounceLast  : after the last extend: shade only multiplies the throughput (sh:84-87); miss items.
 // ================================================================================================
+// ---- the first launch's per-tile candidate lists (wfpt_tile_lists.h)
+// The closest hit of a primary ray among the leaves its tile's record names, in place of trace_ray_conservative: the record holds every
+// leaf whose margin-grown box a ray of the tile can reach, which is a superset U of the leaves the free walk would reach and so of what
+// the reference tests (visit_leaf: nothing is pruned here, so "T is a subset of U" holds without the walk's qualification); min U, one
+// leaf_box_verdict on the final hit's leaf, and the hand-over on a failed verdict or a near-tie (hit_prim<TRACK>'s watch is two-sided:
+// whatever the order of the tests, the final minimum and any accepted candidate within the window meet at one of the two tests) are the
+// walk's own. The record is read through the scalar path, four words at a time: the loop is wave-uniform and ends at the first 0.
+typedef uint32_t v4u_ __attribute__((ext_vector_type(4)));
+#define WFPT_AS_CONSTANT __attribute__((address_space(4)))
+template <int PRIM>
+__device__ __forceinline__ bool trace_tile_list(const uint4 *record, uint32_t w0, const float4 *prim_geom, float ox, float oy, float oz, float dx,
+                                                float dy, float dz, float &t_out, uint32_t &prim_out) {
+    const float a = (dx * dx + dy * dy) + dz * dz; // dot(direction, direction), ex:190
+    float nearest = 1e30f;
+    uint32_t best = 0xffffffffu, best_leaf = 0;
+    const WFPT_AS_CONSTANT v4u_ *rec = (const WFPT_AS_CONSTANT v4u_ *)reinterpret_cast<uintptr_t>(record);
+    uint32_t w = w0;
+    for (uint32_t q = 0; q < kTileListCap / 4u && w != 0u; ++q) {
+        const v4u_ four = rec[q];
+        const uint32_t ws[4] = {four.x, four.y, four.z, four.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            w = ws[k];
+            if (w == 0u) break;
+            visit_leaf<PRIM>(prim_geom, w & 0xffffu, w >> 16, w, ox, oy, oz, dx, dy, dz, a, nearest, best, best_leaf);
+        }
+    }
+    leaf_box_verdict<PRIM>(prim_geom, best_leaf & 0xffffu, best_leaf >> 16, false, ox, oy, oz, dx, dy, dz, nearest, best);
+    t_out = nearest;
+    prim_out = best;
+    return nearest < 1e30f;
+}
+
+// The builder: one wave per local tile, lanes over the nodes in ascending order (so the record is the host twin's, wfpt_tile_lists_host).
+constexpr int kTileListThreads = 256;
+__global__ __launch_bounds__(kTileListThreads) void tile_lists_kernel(TileListArgs a) {
+    const uint32_t lane = lane_id();
+    const uint32_t tile = uniform(blockIdx.x * (kTileListThreads / 64u) + (threadIdx.x >> 6));
+    if (tile >= a.gx * a.gy) return;
+    uint32_t *rec = a.records + static_cast<size_t>(tile) * kTileListCap;
+    uint32_t x0, y0;
+    tile_origin(tile, a.gx, a.tile.rank, a.tile.world, x0, y0);
+    const CameraDev &cam = *a.camera;
+    const TileBundle b = tile_bundle(cam.cam, cam.inv_proj, cam.view, x0, y0, a.width, a.height);
+    bool list = b.ok != 0u && __float_as_uint(a.nodes_ch[1].w) == 0u; // (a root that is a leaf: its box is never tested, the walk decides)
+    uint32_t count = 0;
+    for (uint32_t base = 0; base < a.n_nodes && list; base += 64u) {
+        const uint32_t i = base + lane;
+        uint32_t w = 0u;
+        if (i < a.n_nodes) {
+            const float4 c = a.nodes_ch[2u * i], h = a.nodes_ch[2u * i + 1u];
+            w = tile_leaf_word(i, __float_as_uint(c.w), __float_as_uint(h.w));
+            if (w != 0u && w != kTileNoList && !tile_bundle_reaches(b, c.x, c.y, c.z, h.x, h.y, h.z)) w = 0u;
+        }
+        const unsigned long long mask = __ballot(w != 0u);
+        const uint32_t slot = count + mbcnt(mask);
+        if (__ballot(w == kTileNoList) != 0ull) list = false;
+        if (w != 0u && slot < kTileListCap) rec[slot] = w;
+        count += static_cast<uint32_t>(__popcll(mask));
+        if (count > kTileListCap) list = false;
+    }
+    if (lane < kTileListCap) {
+        if (!list) rec[lane] = lane == 0u ? kTileNoList : 0u;
+        else if (lane >= count) rec[lane] = 0u;
+    }
+}
+
 // Tickets -> work items of a fused bounce launch. Hit items (shade + walk: vector-ALU work) come first in the numbering, miss items (one
 // 16-byte read-modify-write per miss: memory latency, idle ALUs) after them; drawn in that order, every launch ended on a tail of nothing
 // but miss items -- a tenth of its time (round 5: +9 % on the frame). A ticket is therefore mapped so that one miss item follows every
@@ -2384,7 +2451,23 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         float t = 0.0f;
         uint32_t prim = 0;
         bool hit = false;
-        if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
+        if (MODE == kBounceFirst && LDS_SCENE && !EXACT) {
+            // this wave's tile and its candidate list (wfpt_tile_lists.h): word 0 through the scalar path; no table, or no list: the walk
+            const uint4 *record = nullptr;
+            uint32_t w0 = kTileNoList;
+            if (a.tile_lists) {
+                record = a.tile_lists + (kTileListCap / 4u) * uniform(h >> 6); // (64 bytes: four uint4; in bounds for every slot below the capacity)
+                w0 = uniform(*reinterpret_cast<const uint32_t *>(record));
+            }
+            if (w0 == kTileNoList) {
+                if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
+            } else if (live) {
+                prim = kHandOver; // (a far origin is handed over as WFPT_TRACE_ANY does)
+                if (!far_origin(a.scene, ox, oy, oz)) hit = trace_tile_list<PRIM>(record, w0, s_geom, ox, oy, oz, dx, dy, dz, t, prim);
+                if (prim == kHandOver)
+                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
+            }
+        } else if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
         WFPT_STAMP(t_traced);
         const bool miss = live && !hit;
         const unsigned long long hit_mask = __ballot(hit), miss_mask = __ballot(miss);
@@ -4267,6 +4350,13 @@ hipError_t launch_scan_binned(const ScanBinnedArgs &a, hipStream_t s) {
 
 hipError_t launch_plan(const PlanArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(plan_kernel<kBinClasses>, dim3(1), dim3(kPlanThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_lists(const TileListArgs &a, hipStream_t s) {
+    const uint32_t tiles = a.gx * a.gy, per_block = kTileListThreads / 64u;
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(tile_lists_kernel, dim3((tiles + per_block - 1u) / per_block), dim3(kTileListThreads), 0, s, a);
     return hipGetLastError();
 }
 
