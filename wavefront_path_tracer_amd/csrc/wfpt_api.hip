@@ -191,7 +191,7 @@ struct wfpt_ctx {
     DeviceBuffer<float> gather_stage; // root: [world - 1] slabs received from the peers
     DeviceBuffer<float> gather_frame; // root: assembled frame, whole bands (ceil(height / 8) * 8 rows)
     EventPair gather_ev;              // wfpt_gather_accumulated_timed
-    DeviceBuffer<unsigned long long> d_stamps; // diagnostic builds: 16 counters (wfpt_debug_read_stamps)
+    DeviceBuffer<unsigned long long> d_stamps; // diagnostic builds: 16 counters per launch kind (wfpt_debug_read_stamps_ex)
     DeviceBuffer<float4> rec_dense; // HBM-resident scenes: per-ray results of the refill traversal, [batch][capacity][2]
     uint32_t classic_batch = 1; // slices of the stage-by-stage queues: batch_max when the loop runs unfused, else 1 (stage API)
     uint32_t bounce_blocks_per_cu = 1;
@@ -1645,7 +1645,7 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
     if (c->p.flags & WFPT_FLAG_DENOISE) CREATE_HIP(c->moments.alloc_zeroed(kMomentPlanes * static_cast<size_t>(c->pixel_capacity), st));
     CREATE_HIP(c->ctl.alloc_zeroed(kMaxBatch, st));
     CREATE_HIP(c->camera.alloc(1));
-    CREATE_HIP(c->d_stamps.alloc_zeroed(48, st));
+    CREATE_HIP(c->d_stamps.alloc_zeroed(64, st));
 
     hipDeviceProp_t prop;
     CREATE_HIP(hipGetDeviceProperties(&prop, c->device));
@@ -2830,9 +2830,11 @@ int wfpt_debug_read_stamps_ex(wfpt_ctx *c, int which, uint64_t out[16], int rese
     // which = 1 / 2: the refill traversal's first / middle launches (scenes beyond LDS), per wave summed: [0] loop iterations, [1] lanes holding a
     // ray, [2] four-box visit steps, [3] lanes in them, [4] leaf rounds, [5] lanes in them, [6] refill passes, [7] lanes refilled, [8] lanes that sat
     // at a leaf through an iteration without a leaf round; shader cycles: [9] refill, [10] visit step, [11] leaf round + result, [12] whole loop;
-    // [13] waves. which = 0: wfpt_debug_read_stamps.
+    // [13] waves. which = 0: wfpt_debug_read_stamps. which = 3: the first fused launch (bounce_kernel<kBounceFirst>), shader cycles per wave
+    // summed: [0] item start -> ray generated, [1] the tile's list or the walk, [2] waiting at the barrier, [3] compaction, stores issued;
+    // [4] wave-items, [5] live rays; wave 0 alone: [6] cycles from issuing the ticket's atomic to holding its value, [7] tickets drawn.
     if (which == 0) return wfpt_debug_read_stamps(c, out, reset);
-    if (!c || !out || which < 0 || which > 2) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_debug_read_stamps_ex: bad argument");
+    if (!c || !out || which < 0 || which > 3) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_debug_read_stamps_ex: bad argument");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
     WFPT_HIP(c, hipMemcpy(out, c->d_stamps.get() + 16 * which, sizeof(uint64_t) * 16, hipMemcpyDeviceToHost));

@@ -8,6 +8,7 @@
 #include "wfpt.h"
 #include "wfpt_bvh4.h"
 #include "wfpt_device_math.h"
+#include "wfpt_first_schedule.h"
 #include "wfpt_tile_lists.h"
 
 namespace wfpt {
@@ -255,6 +256,16 @@ constexpr int kMissSegsPerItem = WFPT_MISS_SEGS; // miss work item = this many i
 #define WFPT_MISS_EVERY 0
 #endif
 constexpr uint32_t kMissEvery = WFPT_MISS_EVERY; // fused bounce launches: every kMissEvery-th ticket is a miss item while both kinds are left; 0 = hit items / miss items + 1, per launch
+#ifndef WFPT_FIRST_STATIC_SHARE_NUM
+#define WFPT_FIRST_STATIC_SHARE_NUM 1
+#endif
+#ifndef WFPT_FIRST_STATIC_SHARE_DEN
+#define WFPT_FIRST_STATIC_SHARE_DEN 2
+#endif
+// bounce_kernel<kBounceFirst>: the share of its items that the workgroups take without a ticket (wfpt_first_schedule.h); 0 = every item by ticket.
+// 1/2 is the best of the sweep 0 .. 1 (profiles/r07_first_schedule_ab.txt): a larger share leaves too short a tail to even out the workgroups
+constexpr uint32_t kFirstStaticNum = WFPT_FIRST_STATIC_SHARE_NUM, kFirstStaticDen = WFPT_FIRST_STATIC_SHARE_DEN;
+static_assert(kFirstStaticDen > 0 && kFirstStaticNum <= kFirstStaticDen, "the static share of the first launch's items lies in [0, 1]");
 
 struct BounceArgs {
     Batch batch;

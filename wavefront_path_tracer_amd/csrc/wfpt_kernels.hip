@@ -2376,6 +2376,11 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     if (MODE == kBounceFirst && blockIdx.x == 0 && threadIdx.x < a.batch.n)
         a.ctl[threadIdx.x].n_in = umin(n_slots, a.capacity); // pt:313-316: counter[2] = rays of the first wavefront (read by scan)
     const TicketMap tickets(n_hit_items, n_items, MODE != kBounceFirst);
+    // The first launch's items are known before it starts and cost nearly the same: a workgroup takes a share of them by its index alone
+    // and draws tickets for the tail only (wfpt_first_schedule.h). There an item is its ticket (nothing is mixed), so `ticket` carries the
+    // item through both ranges; every other launch has no static range.
+    constexpr bool STATIC = MODE == kBounceFirst && kFirstStaticNum > 0;
+    const uint32_t n_static = STATIC ? uniform(first_n_static(n_items, gridDim.x, kFirstStaticNum, kFirstStaticDen)) : 0u;
     uint32_t ticket = blockIdx.x;
     if (ticket >= n_items) return;
     uint32_t item = tickets.item_of(ticket);
@@ -2389,11 +2394,25 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     uint32_t iter = 0;
 #if WFPT_STAMPS
     unsigned long long acc_cyc[4] = {0, 0, 0, 0}, acc_search = 0, acc_record = 0; // (the last two: lane 0's view of shade's first two memory levels)
-    uint32_t acc_cnt[5] = {0, 0, 0, 0, 0};
+    unsigned long long acc_ticket = 0; // first launch, wave 0: from issuing the ticket's atomic to holding its value
+    uint32_t acc_cnt[5] = {0, 0, 0, 0, 0}, acc_drawn = 0;
 #endif
     while (ticket < n_items) {
         const uint32_t buf = iter & 1u;
-        if (threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
+        const bool next_static = STATIC && first_next_is_static(ticket, n_static); // (uniform) the next item follows from this one: no ticket
+#if WFPT_STAMPS
+        if (MODE == kBounceFirst && !next_static && wave == 0) { // (the wait is the one the store to L.next makes anyway, placed between two stamps)
+            WFPT_STAMP(t_draw);
+            uint32_t drawn = 0;
+            if (threadIdx.x == 0) drawn = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            WFPT_STAMP(t_drawn);
+            if (threadIdx.x == 0) L.next[buf] = drawn;
+            acc_ticket += t_drawn - t_draw;
+            acc_drawn += 1u;
+        } else if (MODE != kBounceFirst)
+#endif
+        if (!next_static && threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
         if (!ENV && item >= n_hit_items) {
             while (item >= first_m + uniform(L.items_m[smp_m])) first_m += uniform(L.items_m[smp_m++]);
             WFPT_MISS_ITEM(smp_m, (item - first_m) * kMissSegsPerItem, (uniform(umin(a.ctl[smp_m].seg_n, a.capacity)) + kChunk - 1) / kChunk);
@@ -2502,6 +2521,15 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             a.out_miss[co + seg_out] = miss_total;
         }
 #if WFPT_STAMPS
+        if (MODE == kBounceFirst) { // per wave, summed over its items: ray generated | list or walk | barrier | compaction, stores issued (not waited for)
+            WFPT_STAMP(t_done);
+            acc_cyc[0] += t_trace - t_item;
+            acc_cyc[1] += t_traced - t_trace;
+            acc_cyc[2] += t_synced - t_traced;
+            acc_cyc[3] += t_done - t_synced;
+            acc_cnt[0] += 1u;
+            acc_cnt[1] += static_cast<uint32_t>(__popcll(__ballot(live)));
+        }
         if (MODE == kBounceMiddle) { // per wave, summed over its items in registers (flushed once, at the end of the kernel)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             WFPT_STAMP(t_done);
@@ -2520,11 +2548,21 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             acc_cnt[2] += w_visits; acc_cnt[3] += w_leaves; acc_cnt[4] += l_visits;
         }
 #endif
-        ticket = uniform(L.next[buf]);
+        if (next_static) ticket += gridDim.x;
+        else ticket = first_dynamic_item(n_static, uniform(L.next[buf]));
         item = tickets.item_of(ticket);
         iter += 1;
     }
 #if WFPT_STAMPS
+    if (MODE == kBounceFirst && a.stamps && lane == 0) { // counters 48..63: wfpt_debug_read_stamps_ex(which = 3)
+        for (int k = 0; k < 4; ++k) atomicAdd(&a.stamps[48 + k], acc_cyc[k]);
+        atomicAdd(&a.stamps[48 + 4], static_cast<unsigned long long>(acc_cnt[0]));
+        atomicAdd(&a.stamps[48 + 5], static_cast<unsigned long long>(acc_cnt[1]));
+        if (wave == 0) {
+            atomicAdd(&a.stamps[48 + 6], acc_ticket);
+            atomicAdd(&a.stamps[48 + 7], static_cast<unsigned long long>(acc_drawn));
+        }
+    }
     if (MODE == kBounceMiddle && a.stamps && lane == 0) {
         for (int k = 0; k < 4; ++k) atomicAdd(&a.stamps[k], acc_cyc[k]);
         atomicAdd(&a.stamps[4], static_cast<unsigned long long>(acc_cnt[0]));
