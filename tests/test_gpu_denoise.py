@@ -82,6 +82,33 @@ def test_moments_and_denoise_are_the_same_for_every_loop_and_batch(gpu):
         pt.close()
 
 
+@pytest.mark.parametrize("flags, emitter", [("", False), ("DENOISE", False), ("EMISSION", True), ("EMISSION|DENOISE", True)])
+def test_one_accumulate_launch_with_every_trip_size_matches_single_samples(gpu, flags, emitter):
+    """23 samples in one accumulate launch against 23 launches of one: the four accumulate kernels take their samples 16 + 4 + 1 + 1 + 1
+    (plain), 4 x 5 + 3 (moments), 8 x 2 + 7 (second plane) and 4 x 5 + 3 (second plane with moments), and every sum has to come out as
+    the sample-by-sample one, bit for bit."""
+    W = gpu
+    fl = 0
+    for name in filter(None, flags.split("|")):
+        fl |= getattr(W, "FLAG_" + name)
+    spp, got = 23, {}
+    for batch in (1, spp):
+        pt = make_tracer(W, "shirley", 40, 24, max_wavefronts=3, rng_mode=W.RNG_PIXEL, miss_floor=0, flags=fl, batch=batch)  # partial tiles both ways
+        if emitter:
+            sp = pt.scene.spheres
+            pt.set_emission(int(sp["material_idx"][sp["radius"] == 1.0][0]), (4.0, 3.0, 2.0))
+        _, launches = pt.render_timed(spp)
+        assert launches[W.STAGES["accumulate"]] == spp // batch, (batch, launches)
+        got[batch] = (pt.accumulated(), pt.variance() if fl & W.FLAG_DENOISE else None)
+        pt.close()
+    # a sample's value is at most 1 per channel without an emitter (sky and albedos are) and (4, 3, 2) where a primary ray hits the
+    # emitter: the brightest sum tells whether the second plane was added
+    assert (got[spp][0].max() > 1.5 * spp) == emitter, got[spp][0].max()
+    assert_bits(got[spp][0], got[1][0], f"accumulated, flags {flags!r}")
+    if fl & W.FLAG_DENOISE:
+        assert_bits(got[spp][1], got[1][1], f"variance, flags {flags!r}")
+
+
 def test_denoise_to_tensor_gives_the_same_bits(gpu):
     torch = pytest.importorskip("torch")
     W = gpu

@@ -1366,12 +1366,18 @@ class PathTracer:
         self._check(lib().wfpt_clear_environment(self.handle))
         self._env_shape = None
 
+    def _probe(self, fn, name, rows, in_width, out_width, *leading):
+        """A device probe: fn(handle, *leading, rows, n, out) with `rows` as (n, in_width) float32; returns out, (n, out_width) float32."""
+        a = np.ascontiguousarray(rows, "<f4")
+        if a.ndim != 2 or a.shape[1] != in_width:
+            raise ValueError(f"{name}: expected rows of {in_width} floats, got shape {a.shape}")
+        out = np.zeros((a.shape[0], out_width), "<f4")
+        self._check(fn(self.handle, *leading, _p(a), a.shape[0], _p(out)))
+        return out
+
     def sample_environment(self, dirs):
         """(n, 3) float32: the map's value (with its intensity) in each of the (n, 3) directions, looked up on the device."""
-        d = np.ascontiguousarray(dirs, "<f4").reshape(-1, 3)
-        out = np.zeros_like(d)
-        self._check(lib().wfpt_sample_environment(self.handle, _p(d), d.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_environment, "sample_environment", np.asarray(dirs, "<f4").reshape(-1, 3), 3, 3)
 
     # ---- textures (contexts created with FLAG_TEXTURES; include/wfpt.h "Textures")
     def set_texture(self, slot, rgb, scale=(1.0, 1.0), offset=(0.0, 0.0), filter="bilinear"):
@@ -1403,10 +1409,7 @@ class PathTracer:
 
     def sample_texture(self, slot, uv):
         """(n, 3) float32: the texture of slot `slot` at each of the (n, 2) UVs, looked up on the device."""
-        a = np.ascontiguousarray(uv, "<f4").reshape(-1, 2)
-        out = np.zeros((a.shape[0], 3), "<f4")
-        self._check(lib().wfpt_sample_texture(self.handle, slot, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_texture, "sample_texture", np.asarray(uv, "<f4").reshape(-1, 2), 2, 3, slot)
 
     def texture_timing(self):
         """(milliseconds, launches) of the texture launches of every timed render since creation (apart from render_timed's stage times)."""
@@ -1455,12 +1458,7 @@ class PathTracer:
     def sample_lights(self, rows):
         """The connect pass's light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 of (p.xyz, n.xyz,
         u0, u1, u2); returns (n, 8) float32 of (q.xyz, the light's primitive index, the unoccluded factor e_q * G per channel, occluded 0/1)."""
-        a = np.ascontiguousarray(rows, "<f4")
-        if a.ndim != 2 or a.shape[1] != 9:
-            raise ValueError(f"sample_lights: expected rows of 9 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 8), "<f4")
-        self._check(lib().wfpt_sample_lights(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_lights, "sample_lights", rows, 9, 8)
 
     # ---- environment next-event estimation (contexts created with FLAG_ENVIRONMENT | FLAG_EMISSION | FLAG_NEE | FLAG_ENV_NEE)
     def set_environment_share(self, share):
@@ -1483,55 +1481,30 @@ class PathTracer:
         """The connect pass's sample of the map (its environment branch with p = 1) for caller-supplied receivers, computed on the device.
         rows: (n, 10) float32 of (p.xyz, n.xyz, u1, u2, u3, u4); returns (n, 8) float32 of (wdir.xyz, the texel index y * w + x, the
         unoccluded factor e * Genv per channel, occluded 0/1)."""
-        a = np.ascontiguousarray(rows, "<f4")
-        if a.ndim != 2 or a.shape[1] != 10:
-            raise ValueError(f"sample_environment_light: expected rows of 10 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 8), "<f4")
-        self._check(lib().wfpt_sample_environment_light(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_environment_light, "sample_environment_light", rows, 10, 8)
 
     # ---- multiple importance sampling (contexts created with FLAG_EMISSION | FLAG_NEE | FLAG_MIS; include/wfpt.h "Multiple importance sampling")
     def sample_lights_mis(self, rows):
         """The connect pass's weighed light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 as for
         sample_lights; returns (n, 12) float32 of (q.xyz, the light's primitive index, (e_q * G) * wl per channel, occluded 0/1, pl, pb, wl, 0)."""
-        a = np.ascontiguousarray(rows, "<f4")
-        if a.ndim != 2 or a.shape[1] != 9:
-            raise ValueError(f"sample_lights_mis: expected rows of 9 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 12), "<f4")
-        self._check(lib().wfpt_sample_lights_mis(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_lights_mis, "sample_lights_mis", rows, 9, 12)
 
     def mis_hit_weight(self, rows):
         """The emission pass's weight for caller-supplied hits, computed on the device. rows: (n, 8) float32 of (o.xyz, d.xyz, t, the
         primitive index); returns (n, 4) float32 of (pl, pb, wb, cos_l)."""
-        a = np.ascontiguousarray(rows, "<f4")
-        if a.ndim != 2 or a.shape[1] != 8:
-            raise ValueError(f"mis_hit_weight: expected rows of 8 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 4), "<f4")
-        self._check(lib().wfpt_mis_hit_weight(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_mis_hit_weight, "mis_hit_weight", rows, 8, 4)
 
     # ---- environment multiple importance sampling (FLAG_ENV_NEE's four flags | FLAG_ENV_MIS; include/wfpt.h "Environment multiple importance sampling")
     def sample_environment_light_mis(self, rows):
         """The connect pass's weighed sample of the map, with the context's effective share p, for caller-supplied receivers, computed on
         the device. rows: (n, 10) float32 as for sample_environment_light; returns (n, 12) float32 of (wdir.xyz, the texel index
         y * w + x, (e * Genv) * we per channel, occluded 0/1, pe, pb, we, 0)."""
-        a = np.ascontiguousarray(rows, "<f4")
-        if a.ndim != 2 or a.shape[1] != 10:
-            raise ValueError(f"sample_environment_light_mis: expected rows of 10 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 12), "<f4")
-        self._check(lib().wfpt_sample_environment_light_mis(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_sample_environment_light_mis, "sample_environment_light_mis", rows, 10, 12)
 
     def env_mis_miss_weight(self, dirs):
         """The miss pass's weight for caller-supplied un-normalised directions, computed on the device. dirs: (n, 3) float32; returns
         (n, 4) float32 of (pe, pb, wb, the texel index yt * w + xt)."""
-        a = np.ascontiguousarray(dirs, "<f4")
-        if a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError(f"env_mis_miss_weight: expected rows of 3 floats, got shape {a.shape}")
-        out = np.zeros((a.shape[0], 4), "<f4")
-        self._check(lib().wfpt_env_mis_miss_weight(self.handle, _p(a), a.shape[0], _p(out)))
-        return out
+        return self._probe(lib().wfpt_env_mis_miss_weight, "env_mis_miss_weight", dirs, 3, 4)
 
     # ---- read-back
     def accumulated(self):

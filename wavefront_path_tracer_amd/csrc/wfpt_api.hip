@@ -317,6 +317,13 @@ int hip_fail(wfpt_ctx *c, hipError_t e, const char *what) {
         hipError_t e_ = (call);                             \
         if (e_ != hipSuccess) return hip_fail(c, e_, #call); \
     } while (0)
+// an entry point of a feature on a context that may lack it: `name` is the flag's, for the message
+int flag_check(const wfpt_ctx *c, const char *who, uint32_t flag, const char *name) {
+    if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
+    if (!(c->p.flags & flag))
+        return fail(const_cast<wfpt_ctx *>(c), WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without " + name);
+    return WFPT_OK;
+}
 
 void set_queue(RayQueue &q, float *base, size_t cap) {
     q.base = base;
@@ -660,6 +667,30 @@ ConnectArgs sampler_args(wfpt_ctx *c, const float *in, float *out, size_t n) {
     a.sample_n = static_cast<uint32_t>(n);
     return a;
 }
+// ... launched for the probes: a workgroup per kChunk rows, at most the resident set
+hipError_t launch_sampler(wfpt_ctx *c, const ConnectArgs &a, bool envs, bool mis) {
+    const uint64_t items = (static_cast<uint64_t>(a.sample_n) + kChunk - 1) / kChunk;
+    return launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
+                          textured(c), envs, mis);
+}
+// The body of a host probe (wfpt_sample_*, wfpt_*_weight), blocking: n caller rows of in_width floats to the device, launch(d_in, d_out) on
+// the context's stream, n rows of out_width floats back. rows31: the launch counts its rows in 31 bits.
+template <typename Launch>
+int probe(wfpt_ctx *c, const char *who, const float *in, size_t in_width, float *out, size_t out_width, size_t n, bool rows31, Launch &&launch) {
+    if ((!in || !out) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (rows31 && n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": too many rows");
+    if (n == 0) return WFPT_OK;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> d_in, d_out;
+    hipError_t e = d_in.alloc(in_width * n);
+    if (e == hipSuccess) e = d_out.alloc(out_width * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in, sizeof(float) * in_width * n, hipMemcpyHostToDevice, c->stream.get());
+    if (e == hipSuccess) e = launch(d_in.get(), d_out.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.get(), sizeof(float) * out_width * n, hipMemcpyDeviceToHost, c->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
+    if (e != hipSuccess) return hip_fail(c, e, who);
+    return WFPT_OK;
+}
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
     return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c));
@@ -874,13 +905,12 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
     return static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu));
 }
 
-// The batch's accumulate launch: with the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way)
+// The batch's accumulate launch: with the second plane where the context holds an emitter (each sample's value is image + emitted) and
+// the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way). second_plane(c) implies the plane:
+// apply_emission and the environment's distribution allocate `emitted` before either of its conditions can hold.
 hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
-    const AccumulateArgs a = accumulate_args(c, c->n_pixels, true, nb);
-    if (second_plane(c)) // each sample's value is image + emitted (the same kernels with the second plane)
-        return launch_accumulate_emission(a, c->emitted.get(), c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
-    if (c->moments.get()) return launch_accumulate_moments(a, c->moments.get(), c->pixel_capacity, c->accumulate_grid, c->stream.get());
-    return launch_accumulate(a, c->accumulate_grid, c->stream.get());
+    return launch_accumulate(accumulate_args(c, c->n_pixels, true, nb), second_plane(c) ? c->emitted.get() : nullptr, c->moments.get(),
+                             c->pixel_capacity, c->accumulate_grid, c->stream.get());
 }
 
 int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
@@ -1986,10 +2016,8 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         WFPT_HIP(c, launch_miss_pass(c, miss_args(c, c->cur, &c->ctl.get()->counters[0], threads), consumer_grid(c, 1)));
         break;
     case WFPT_STAGE_ACCUMULATE:
-        if (second_plane(c))
-            WFPT_HIP(c, launch_accumulate_emission(accumulate_args(c, threads, false), c->emitted.get(), nullptr, 0, c->accumulate_grid, c->stream.get()));
-        else
-            WFPT_HIP(c, launch_accumulate(accumulate_args(c, threads, false), c->accumulate_grid, c->stream.get()));
+        WFPT_HIP(c, launch_accumulate(accumulate_args(c, threads, false), second_plane(c) ? c->emitted.get() : nullptr, nullptr, 0,
+                                      c->accumulate_grid, c->stream.get()));
         break;
     default: break;
     }
@@ -2900,9 +2928,7 @@ void wfpt_environment_params_default(wfpt_environment_params *p) {
 }
 
 static int environment_check(wfpt_ctx *c, const char *who) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_ENVIRONMENT))
-        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_ENVIRONMENT");
+    if (int r = flag_check(c, who, WFPT_FLAG_ENVIRONMENT, "WFPT_FLAG_ENVIRONMENT"); r != WFPT_OK) return r;
     if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
         return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no environment map");
     return WFPT_OK;
@@ -3004,19 +3030,11 @@ int wfpt_clear_environment(wfpt_ctx *c) {
 
 int wfpt_sample_environment(wfpt_ctx *c, const float *dirs, size_t n, float *rgb_out) {
     if (int r = environment_check(c, "wfpt_sample_environment"); r != WFPT_OK) return r;
-    if ((!dirs || !rgb_out) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment: null argument");
-    if (!c->env_tex.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment: no map is set");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_dirs, d_rgb;
-    hipError_t e = d_dirs.alloc(3 * n);
-    if (e == hipSuccess) e = d_rgb.alloc(3 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_dirs.get(), dirs, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) e = launch_env_sample(c->env, d_dirs.get(), d_rgb.get(), n, c->stream.get());
-    if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment");
-    return WFPT_OK;
+    // (a null argument has always been reported ahead of a missing map: probe() reports it, this only steps aside for it)
+    const bool null_argument = (!dirs || !rgb_out) && n;
+    if (!null_argument && !c->env_tex.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment: no map is set");
+    return probe(c, "wfpt_sample_environment", dirs, 3, rgb_out, 3, n, false,
+                 [&](const float *d_dirs, float *d_rgb) { return launch_env_sample(c->env, d_dirs, d_rgb, n, c->stream.get()); });
 }
 
 // ---------------------------------------------------------------- textures (include/wfpt.h "Textures")
@@ -3048,9 +3066,7 @@ static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t) {
 }
 
 static int texture_check(wfpt_ctx *c, const char *who) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_TEXTURES))
-        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_TEXTURES");
+    if (int r = flag_check(c, who, WFPT_FLAG_TEXTURES, "WFPT_FLAG_TEXTURES"); r != WFPT_OK) return r;
     if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
         return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no textures");
     return WFPT_OK;
@@ -3166,24 +3182,12 @@ int wfpt_sample_texture(wfpt_ctx *c, uint32_t slot, const float *uv, size_t n, f
     if (int r = texture_check(c, "wfpt_sample_texture"); r != WFPT_OK) return r;
     if (slot >= WFPT_MAX_TEXTURES || !c->tex_texels[slot].get())
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_texture: the slot holds no texture");
-    if ((!uv || !rgb_out) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_texture: null argument");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_uv, d_rgb;
-    hipError_t e = d_uv.alloc(2 * n);
-    if (e == hipSuccess) e = d_rgb.alloc(3 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_uv.get(), uv, sizeof(float) * 2 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) e = launch_tex_sample(c->tex_dev[slot], d_uv.get(), d_rgb.get(), n, c->stream.get());
-    if (e == hipSuccess) e = hipMemcpyAsync(rgb_out, d_rgb.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_texture");
-    return WFPT_OK;
+    return probe(c, "wfpt_sample_texture", uv, 2, rgb_out, 3, n, false,
+                 [&](const float *d_uv, float *d_rgb) { return launch_tex_sample(c->tex_dev[slot], d_uv, d_rgb, n, c->stream.get()); });
 }
 
 int wfpt_texture_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_texture_timing_ms: null context");
-    if (!(c->p.flags & WFPT_FLAG_TEXTURES))
-        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_texture_timing_ms: the context was created without WFPT_FLAG_TEXTURES");
+    if (int r = flag_check(c, "wfpt_texture_timing_ms", WFPT_FLAG_TEXTURES, "WFPT_FLAG_TEXTURES"); r != WFPT_OK) return r;
     if (ms_total) *ms_total = static_cast<float>(c->tex_ms);
     if (launches) *launches = c->tex_launches;
     return WFPT_OK;
@@ -3234,9 +3238,7 @@ static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t) {
 }
 
 static int emission_check(wfpt_ctx *c, const char *who, bool changes) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_EMISSION))
-        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_EMISSION");
+    if (int r = flag_check(c, who, WFPT_FLAG_EMISSION, "WFPT_FLAG_EMISSION"); r != WFPT_OK) return r;
     if (changes && wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
         return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no emitters");
     return WFPT_OK;
@@ -3298,11 +3300,7 @@ int wfpt_emission_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
 }
 
 // ---------------------------------------------------------------- next-event estimation (include/wfpt.h "Next-event estimation")
-static int nee_check(wfpt_ctx *c, const char *who) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_NEE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_NEE");
-    return WFPT_OK;
-}
+static int nee_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_NEE, "WFPT_FLAG_NEE"); }
 
 int wfpt_nee_light_count(wfpt_ctx *c) {
     if (int r = nee_check(c, "wfpt_nee_light_count"); r != WFPT_OK) return r;
@@ -3319,82 +3317,33 @@ int wfpt_nee_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
 int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (int r = nee_check(c, "wfpt_sample_lights"); r != WFPT_OK) return r;
     if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
-    if ((!in9 || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(9 * n);
-    if (e == hipSuccess) e = d_out.alloc(8 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) {
-        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
-        const uint64_t items = (n + kChunk - 1) / kChunk;
-        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                           textured(c));
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights");
-    return WFPT_OK;
+    return probe(c, "wfpt_sample_lights", in9, 9, out8, 8, n, true,
+                 [&](const float *d_in, float *d_out) { return launch_sampler(c, sampler_args(c, d_in, d_out, n), false, false); });
 }
 
 // ---------------------------------------------------------------- multiple importance sampling (include/wfpt.h "Multiple importance sampling")
 static int mis_check(wfpt_ctx *c, const char *who) {
-    if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_MIS)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_MIS");
+    if (int r = flag_check(c, who, WFPT_FLAG_MIS, "WFPT_FLAG_MIS"); r != WFPT_OK) return r;
     if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no primitive emits");
     return WFPT_OK;
 }
 
 int wfpt_sample_lights_mis(wfpt_ctx *c, const float *in9, size_t n, float *out12) {
     if (int r = mis_check(c, "wfpt_sample_lights_mis"); r != WFPT_OK) return r;
-    if ((!in9 || !out12) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights_mis: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights_mis: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(9 * n);
-    if (e == hipSuccess) e = d_out.alloc(12 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in9, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) {
-        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
-        const uint64_t items = (n + kChunk - 1) / kChunk;
-        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                           textured(c), false, true);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out12, d_out.get(), sizeof(float) * 12 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_lights_mis");
-    return WFPT_OK;
+    return probe(c, "wfpt_sample_lights_mis", in9, 9, out12, 12, n, true,
+                 [&](const float *d_in, float *d_out) { return launch_sampler(c, sampler_args(c, d_in, d_out, n), false, true); });
 }
 
 int wfpt_mis_hit_weight(wfpt_ctx *c, const float *in8, size_t n, float *out4) {
     if (int r = mis_check(c, "wfpt_mis_hit_weight"); r != WFPT_OK) return r;
-    if ((!in8 || !out4) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_mis_hit_weight: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_mis_hit_weight: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(8 * n);
-    if (e == hipSuccess) e = d_out.alloc(4 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in8, sizeof(float) * 8 * n, hipMemcpyHostToDevice, c->stream.get());
-    const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
-    if (e == hipSuccess)
-        e = launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
-    if (e == hipSuccess) e = hipMemcpyAsync(out4, d_out.get(), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_mis_hit_weight");
-    return WFPT_OK;
+    return probe(c, "wfpt_mis_hit_weight", in8, 8, out4, 4, n, true, [&](const float *d_in, float *d_out) {
+        const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
+        return launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
 }
 
 // ---------------------------------------------------------------- environment next-event estimation (include/wfpt.h)
-static int env_nee_check(const wfpt_ctx *c, const char *who) {
-    if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_ENV_NEE))
-        return fail(const_cast<wfpt_ctx *>(c), WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_ENV_NEE");
-    return WFPT_OK;
-}
+static int env_nee_check(const wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_ENV_NEE, "WFPT_FLAG_ENV_NEE"); }
 
 int wfpt_set_environment_share(wfpt_ctx *c, float share) {
     if (int r = env_nee_check(c, "wfpt_set_environment_share"); r != WFPT_OK) return r;
@@ -3423,72 +3372,31 @@ int wfpt_read_environment_distribution(wfpt_ctx *c, uint32_t *row_wh, uint64_t *
 int wfpt_sample_environment_light(wfpt_ctx *c, const float *in10, size_t n, float *out8) {
     if (int r = env_nee_check(c, "wfpt_sample_environment_light"); r != WFPT_OK) return r;
     if (!env_connecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: no map with a distribution is set");
-    if ((!in10 || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(10 * n);
-    if (e == hipSuccess) e = d_out.alloc(8 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in10, sizeof(float) * 10 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) {
-        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n);
+    return probe(c, "wfpt_sample_environment_light", in10, 10, out8, 8, n, true, [&](const float *d_in, float *d_out) {
+        ConnectArgs a = sampler_args(c, d_in, d_out, n);
         a.envd.share = 1.0f; // the environment branch alone
-        const uint64_t items = (n + kChunk - 1) / kChunk;
-        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                           textured(c), true);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out8, d_out.get(), sizeof(float) * 8 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment_light");
-    return WFPT_OK;
+        return launch_sampler(c, a, true, false);
+    });
 }
 
 // ---------------------------------------------------------------- environment multiple importance sampling (include/wfpt.h)
 static int env_mis_check(wfpt_ctx *c, const char *who) {
-    if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
-    if (!(c->p.flags & WFPT_FLAG_ENV_MIS)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_ENV_MIS");
+    if (int r = flag_check(c, who, WFPT_FLAG_ENV_MIS, "WFPT_FLAG_ENV_MIS"); r != WFPT_OK) return r;
     if (!env_weighing(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no map with a distribution is set");
     return WFPT_OK;
 }
 
 int wfpt_sample_environment_light_mis(wfpt_ctx *c, const float *in10, size_t n, float *out12) {
     if (int r = env_mis_check(c, "wfpt_sample_environment_light_mis"); r != WFPT_OK) return r;
-    if ((!in10 || !out12) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light_mis: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_environment_light_mis: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(10 * n);
-    if (e == hipSuccess) e = d_out.alloc(12 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), in10, sizeof(float) * 10 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) {
-        ConnectArgs a = sampler_args(c, d_in.get(), d_out.get(), n); // (envd.share: the effective share)
-        const uint64_t items = (n + kChunk - 1) / kChunk;
-        e = launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                           textured(c), true, true);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out12, d_out.get(), sizeof(float) * 12 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_sample_environment_light_mis");
-    return WFPT_OK;
+    return probe(c, "wfpt_sample_environment_light_mis", in10, 10, out12, 12, n, true, // (envd.share: the effective share)
+                 [&](const float *d_in, float *d_out) { return launch_sampler(c, sampler_args(c, d_in, d_out, n), true, true); });
 }
 
 int wfpt_env_mis_miss_weight(wfpt_ctx *c, const float *dirs3, size_t n, float *out4) {
     if (int r = env_mis_check(c, "wfpt_env_mis_miss_weight"); r != WFPT_OK) return r;
-    if ((!dirs3 || !out4) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_env_mis_miss_weight: null argument");
-    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_env_mis_miss_weight: too many rows");
-    if (n == 0) return WFPT_OK;
-    WFPT_HIP(c, hipSetDevice(c->device));
-    DeviceBuffer<float> d_in, d_out;
-    hipError_t e = d_in.alloc(3 * n);
-    if (e == hipSuccess) e = d_out.alloc(4 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.get(), dirs3, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream.get());
-    if (e == hipSuccess) e = launch_env_mis_weight(env_dist(c), d_in.get(), d_out.get(), static_cast<uint32_t>(n), c->stream.get());
-    if (e == hipSuccess) e = hipMemcpyAsync(out4, d_out.get(), sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream.get());
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream.get());
-    if (e != hipSuccess) return hip_fail(c, e, "wfpt_env_mis_miss_weight");
-    return WFPT_OK;
+    return probe(c, "wfpt_env_mis_miss_weight", dirs3, 3, out4, 4, n, true, [&](const float *d_in, float *d_out) {
+        return launch_env_mis_weight(env_dist(c), d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
 }
 
 int wfpt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n) {

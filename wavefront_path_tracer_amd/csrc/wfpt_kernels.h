@@ -689,9 +689,10 @@ hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bo
 hipError_t launch_env_weights(const EnvDev &env, float *f, uint32_t *max_bits, hipStream_t s);
 hipError_t launch_env_tables(const EnvDev &env, const float *f, float M, uint32_t *row, uint64_t *marg, hipStream_t s);
 hipError_t connect_prepare(const SceneDev &scene); // raises the connect kernels' dynamic-LDS limit where the scene needs more than 64 KiB
-hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s);
-// accumulate_kernel / accumulate_moments_kernel with the second plane: each sample's value is image_k + emitted_k (moments: null = none)
-hipError_t launch_accumulate_emission(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s);
+// The accumulate launch. emitted (null = none): the second per-sample plane, each sample's value is image_k + emitted_k. moments (null =
+// none; WFPT_FLAG_DENOISE contexts): plus the luminance moments, two planes `plane` floats apart. One kernel of four, the same
+// `accumulated` bits from each.
+hipError_t launch_accumulate(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s);
 hipError_t launch_fill(float *p, float v, size_t n, hipStream_t s);
 hipError_t launch_set_frame(Control *ctl, const wfpt_frame_buffer &f, hipStream_t s); // ctl->frame = f, ordered on the stream
 // frame band (j * world + rank) <- slab band j for the first n_valid floats of a slab: the root of the multi-GPU gather
@@ -704,8 +705,6 @@ hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t 
 hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const TexScene *tex = nullptr);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
-// accumulate_kernel's work plus the luminance moments (WFPT_FLAG_DENOISE contexts, in its place)
-hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, size_t plane, uint32_t grid, hipStream_t s);
 hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_denoise_atrous(const DenoiseArgs &a, hipStream_t s);
 hipError_t launch_temporal_prepare(const DenoiseArgs &a, const TemporalArgs &t, hipStream_t s);

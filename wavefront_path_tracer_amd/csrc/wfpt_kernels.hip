@@ -11,6 +11,8 @@
 #include "wfpt_kernels.h"
 #include "wfpt_device_math.h"
 
+#include <type_traits>
+
 namespace wfpt {
 
 namespace {
@@ -816,6 +818,24 @@ __device__ __forceinline__ void descend_asm(uint32_t nodes_lds, uint32_t parent_
 // (kWalkDone) instead of a flag, so both loop conditions are one vector compare each, the descent is computed for every lane and
 // overwritten by the (one-sided) pop, and nothing but the exec mask itself lives in scalar registers across an iteration.
 constexpr uint32_t kWalkDone = 0xffffffffu; // prim_count of a lane whose walk has ended (a scene in LDS holds fewer than 2^16 primitives)
+// LIFO pop (Traversal::pop) of the two walks below, on their locals node, left_first, prim_count and trail: the deepest pending sibling,
+// found by walking the parent table up from the current node; nothing pending ends the walk (ex:95-97, 125-127: break). A macro, and the
+// only piece the two walks share: as functions or members over a shared state (seven shapes) the pieces left no tracing kernel the
+// instructions it had.
+#define WFPT_POP()                                                                                                                     \
+    do {                                                                                                                               \
+        if (trail == 0) {                                                                                                              \
+            prim_count = kWalkDone;                                                                                                    \
+        } else {                                                                                                                       \
+            const uint32_t up = (sizeof(Trail) == 8) ? static_cast<uint32_t>(__ffsll(static_cast<long long>(trail)) - 1)              \
+                                                     : static_cast<uint32_t>(__ffs(static_cast<int>(trail)) - 1);                      \
+            trail = (trail >> up) & ~static_cast<Trail>(1);                                                                            \
+            for (uint32_t k = 0; k < up; ++k) node = pair_parent[node >> 1];                                                           \
+            node ^= 1u;                                                                                                                \
+            left_first = __float_as_uint(nodes_ch[2u * node].w);                                                                       \
+            prim_count = __float_as_uint(nodes_ch[2u * node + 1u].w);                                                                  \
+        }                                                                                                                              \
+    } while (0)
 template <typename Trail, int PRIM, typename ParentT>
 __device__ __forceinline__ bool trace_ray_conservative(const float4 *nodes_ch, const float4 *prim_geom, const ParentT *pair_parent, float ox,
                                                        float oy, float oz, float dx, float dy, float dz, uint32_t max_steps, float &t_out,
@@ -833,22 +853,6 @@ __device__ __forceinline__ bool trace_ray_conservative(const float4 *nodes_ch, c
     uint32_t best_leaf = 0; // the leaf of `best`: left_first | prim_count << 16
     uint32_t budget = max_steps; // see trace_ray
     const uint32_t nodes_lds = uniform(lds_offset(nodes_ch)), parent_lds = uniform(lds_offset(pair_parent));
-    // LIFO pop (Traversal::pop): the deepest pending sibling, found by walking the parent table up from the current node; nothing
-    // pending ends the walk (ex:95-97, 125-127: break)
-#define WFPT_POP()                                                                                                                     \
-    do {                                                                                                                               \
-        if (trail == 0) {                                                                                                              \
-            prim_count = kWalkDone;                                                                                                    \
-        } else {                                                                                                                       \
-            const uint32_t up = (sizeof(Trail) == 8) ? static_cast<uint32_t>(__ffsll(static_cast<long long>(trail)) - 1)              \
-                                                     : static_cast<uint32_t>(__ffs(static_cast<int>(trail)) - 1);                      \
-            trail = (trail >> up) & ~static_cast<Trail>(1);                                                                            \
-            for (uint32_t k = 0; k < up; ++k) node = pair_parent[node >> 1];                                                           \
-            node ^= 1u;                                                                                                                \
-            left_first = __float_as_uint(nodes_ch[2u * node].w);                                                                       \
-            prim_count = __float_as_uint(nodes_ch[2u * node + 1u].w);                                                                  \
-        }                                                                                                                              \
-    } while (0)
     while (prim_count != kWalkDone) {
         if (WFPT_WALK_ASM && sizeof(Trail) == 4 && sizeof(ParentT) == 2) { // inner nodes (ex:105-138), hand-written loop
             uint32_t trail32 = static_cast<uint32_t>(trail);
@@ -894,7 +898,6 @@ __device__ __forceinline__ bool trace_ray_conservative(const float4 *nodes_ch, c
             }
         }
     }
-#undef WFPT_POP
     leaf_box_verdict<PRIM>(prim_geom, best_leaf & 0xffffu, best_leaf >> 16, root_leaf, ox, oy, oz, dx, dy, dz, nearest, best);
     t_out = nearest;
     prim_out = best; // kHandOver: the caller re-traces with the reference's walk
@@ -927,20 +930,6 @@ __device__ __forceinline__ uint32_t occluded_conservative(const float4 *nodes_ch
     const bool root_leaf = prim_count != 0u;
     uint32_t budget = max_steps, verdict = kOccNone;
     const uint32_t nodes_lds = uniform(lds_offset(nodes_ch)), parent_lds = uniform(lds_offset(pair_parent));
-#define WFPT_OCC_POP()                                                                                                                 \
-    do {                                                                                                                               \
-        if (trail == 0) {                                                                                                              \
-            prim_count = kWalkDone;                                                                                                    \
-        } else {                                                                                                                       \
-            const uint32_t up = (sizeof(Trail) == 8) ? static_cast<uint32_t>(__ffsll(static_cast<long long>(trail)) - 1)              \
-                                                     : static_cast<uint32_t>(__ffs(static_cast<int>(trail)) - 1);                      \
-            trail = (trail >> up) & ~static_cast<Trail>(1);                                                                            \
-            for (uint32_t k = 0; k < up; ++k) node = pair_parent[node >> 1];                                                           \
-            node ^= 1u;                                                                                                                \
-            left_first = __float_as_uint(nodes_ch[2u * node].w);                                                                       \
-            prim_count = __float_as_uint(nodes_ch[2u * node + 1u].w);                                                                  \
-        }                                                                                                                              \
-    } while (0)
     while (prim_count != kWalkDone) {
         if (WFPT_WALK_ASM && sizeof(Trail) == 4 && sizeof(ParentT) == 2) {
             uint32_t trail32 = static_cast<uint32_t>(trail);
@@ -966,7 +955,7 @@ __device__ __forceinline__ uint32_t occluded_conservative(const float4 *nodes_ch
                 left_first = __float_as_uint(go_right ? rc.w : lc.w);
                 prim_count = __float_as_uint(go_right ? rh.w : lh.w);
             } else {
-                WFPT_OCC_POP();
+                WFPT_POP();
             }
         }
         if (prim_count != kWalkDone) { // leaf
@@ -982,14 +971,14 @@ __device__ __forceinline__ uint32_t occluded_conservative(const float4 *nodes_ch
                     verdict = b == kHandOver ? kOccUndecided : kOccHit;
                     prim_count = kWalkDone;
                 } else {
-                    WFPT_OCC_POP();
+                    WFPT_POP();
                 }
             }
         }
     }
-#undef WFPT_OCC_POP
     return verdict;
 }
+#undef WFPT_POP
 
 // ---- four-wide traversal for HBM-resident scenes (build extension) ----------------------------
 // The closest hit does not depend on the order in which nodes are visited (only on which primitives pass the exact
@@ -1724,16 +1713,20 @@ __device__ __forceinline__ float3_ miss_factor(const EnvDev &env, const MissQueu
     return sky(dy);
 }
 
-template <bool ENV>
-__device__ __forceinline__ void miss_body(MissArgs a, const EnvDev &env) {
-    const uint32_t sample = blockIdx.y;
+// Slices the argument block to one sample of the batch (block-uniform); returns the sample's miss count (mk:24)
+__device__ __forceinline__ uint32_t miss_sample(MissArgs &a, uint32_t sample) {
     a.ctl += sample;
     a.q = slice(a.q, sample * a.batch.ray_stride);
     a.mq.base += sample * a.batch.queue_stride;
     a.chunk_miss += sample * a.batch.chunk_stride;
     a.chunk_miss_base += sample * a.batch.chunk_stride;
     a.image += sample * a.batch.image_stride;
-    const uint32_t n_miss = umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit); // mk:24
+    return umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit);
+}
+
+template <bool ENV>
+__device__ __forceinline__ void miss_body(MissArgs a, const EnvDev &env) {
+    const uint32_t n_miss = miss_sample(a, blockIdx.y);
     const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const uint32_t count = a.chunk_miss[chunk];
@@ -1766,20 +1759,18 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_kernel(MissArgs a) {
 }
 __global__ __launch_bounds__(kConsumerThreads) void miss_env_kernel(MissArgs a, EnvDev env) { miss_body<true>(a, env); }
 
-// The miss pass of a context that connects to its map (WFPT_FLAG_ENV_NEE with a distribution; include/wfpt.h "Environment next-event
-// estimation"): miss_body<true> restated with one difference: where the pixel's connected flag (emitted.w, set by the connect pass of the
-// step that scattered this ray) is 1 the throughput becomes +0 -- the connect pass has already counted the map -- and the map is not read.
-// Its own kernel, not a miss_body<ENV, GATED>: the gate sits before the direction is read, so the walk is not pipelined, and folded into
-// miss_body it took more registers than this form.
-__global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs a, EnvDev env, const float *emitted) {
-    const uint32_t sample = blockIdx.y;
-    a.ctl += sample;
-    a.mq.base += sample * a.batch.queue_stride;
-    a.chunk_miss += sample * a.batch.chunk_stride;
-    a.chunk_miss_base += sample * a.batch.chunk_stride;
-    a.image += sample * a.batch.image_stride;
-    emitted += sample * a.batch.image_stride;
-    const uint32_t n_miss = umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit);
+// The walk of the miss passes that read the connect pass's flag (WFPT_FLAG_ENV_NEE / _ENV_MIS with a distribution), in the manner of
+// for_each_shaded_hit: per_miss(mq, slot, px, thr, flag) for every miss of sample blockIdx.y, with
+//   mq, slot  the sample's miss queue and the miss's slot in it;
+//   px, thr   the miss's pixel and its throughput as read;
+//   flag      the pixel of the `emitted` plane, by reference (per_miss decides when to read it): .w is the connected flag, 1 where
+//             the connect pass of the step that scattered this ray counted the map.
+// Not miss_body<ENV, GATED>: the gate sits before the direction is read, so the walk is not pipelined, and folded into miss_body it
+// took more registers than this form. (miss_sample also slices a.q, which this walk does not read.)
+template <typename F>
+__device__ __forceinline__ void for_each_miss(MissArgs a, const float *emitted, F &&per_miss) {
+    const float4 *flags = reinterpret_cast<const float4 *>(emitted + blockIdx.y * a.batch.image_stride);
+    const uint32_t n_miss = miss_sample(a, blockIdx.y);
     const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
     for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const uint32_t count = a.chunk_miss[chunk];
@@ -1791,14 +1782,23 @@ __global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs
             const uint32_t lp = local_pixel(a.mq.pixel()[slot], a.image_width, a.tile);
             float4 *px = pixel_of(a.image, lp);
             const float4 thr = *px;
-            if (reinterpret_cast<const float4 *>(emitted)[lp].w != 0.0f) {
-                *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
-            } else {
-                const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, a.mq.dx()[slot], a.mq.dy()[slot], a.mq.dz()[slot]);
-                *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
-            }
+            per_miss(a.mq, slot, px, thr, flags[lp]);
         }
     }
+}
+
+// The miss pass of a context that connects to its map (WFPT_FLAG_ENV_NEE with a distribution; include/wfpt.h "Environment next-event
+// estimation"): miss_env_kernel with one difference: where the connected flag is 1 the throughput becomes +0 -- the connect pass has
+// already counted the map -- and the map is not read.
+__global__ __launch_bounds__(kConsumerThreads) void miss_env_nee_kernel(MissArgs a, EnvDev env, const float *emitted) {
+    for_each_miss(a, emitted, [&](const MissQueue &mq, size_t slot, float4 *px, const float4 &thr, const float4 &flag) {
+        if (flag.w != 0.0f) {
+            *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
+        } else {
+            const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, mq.dx()[slot], mq.dy()[slot], mq.dz()[slot]);
+            *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
+        }
+    });
 }
 
 // The balance weight of a scattered ray that misses into the map (WFPT_FLAG_ENV_MIS; include/wfpt.h "Environment multiple importance
@@ -1842,40 +1842,21 @@ __device__ __forceinline__ EnvMisWeight env_mis_weight(const EnvDist &e, float d
     return m;
 }
 
-// The miss pass of a context that weighs its map against the scatter (WFPT_FLAG_ENV_MIS with a distribution): miss_env_nee_kernel's shape,
-// gate first and unpipelined, with one difference: where the pixel's connected flag is 1 the throughput is not zeroed but becomes
-// (thr * c) * wb -- the connect pass counted the map with the other weight.
+// The miss pass of a context that weighs its map against the scatter (WFPT_FLAG_ENV_MIS with a distribution): miss_env_nee_kernel's walk
+// with one difference: where the pixel's connected flag is 1 the throughput is not zeroed but becomes (thr * c) * wb -- the connect pass
+// counted the map with the other weight.
 __global__ __launch_bounds__(kConsumerThreads) void miss_env_mis_kernel(MissArgs a, EnvDist envd, const float *emitted) {
-    const uint32_t sample = blockIdx.y;
-    a.ctl += sample;
-    a.mq.base += sample * a.batch.queue_stride;
-    a.chunk_miss += sample * a.batch.chunk_stride;
-    a.chunk_miss_base += sample * a.batch.chunk_stride;
-    a.image += sample * a.batch.image_stride;
-    emitted += sample * a.batch.image_stride;
     const EnvDev &env = envd.env;
-    const uint32_t n_miss = umin(a.n_miss[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit);
-    const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = a.chunk_miss[chunk];
-        const uint32_t base = a.chunk_miss_base[chunk];
-        if (base >= n_miss) break;
-        for (uint32_t r = threadIdx.x; r < count; r += kConsumerThreads) {
-            if (base + r >= n_miss) break;
-            const size_t slot = chunk * kChunk + r;
-            const uint32_t lp = local_pixel(a.mq.pixel()[slot], a.image_width, a.tile);
-            float4 *px = pixel_of(a.image, lp);
-            const float4 thr = *px;
-            const float dx = a.mq.dx()[slot], dy = a.mq.dy()[slot], dz = a.mq.dz()[slot];
-            const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, dx, dy, dz);
-            if (reinterpret_cast<const float4 *>(emitted)[lp].w != 0.0f) {
-                const float wb = env_mis_weight(envd, dx, dy, dz).wb;
-                *px = make_float4((thr.x * c.x) * wb, (thr.y * c.y) * wb, (thr.z * c.z) * wb, thr.w);
-            } else {
-                *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
-            }
+    for_each_miss(a, emitted, [&](const MissQueue &mq, size_t slot, float4 *px, const float4 &thr, const float4 &flag) {
+        const float dx = mq.dx()[slot], dy = mq.dy()[slot], dz = mq.dz()[slot];
+        const float3_ c = env_lookup(env.texels, env.w, env.h, env.intensity, env.rotation, dx, dy, dz);
+        if (flag.w != 0.0f) {
+            const float wb = env_mis_weight(envd, dx, dy, dz).wb;
+            *px = make_float4((thr.x * c.x) * wb, (thr.y * c.y) * wb, (thr.z * c.z) * wb, thr.w);
+        } else {
+            *px = make_float4(thr.x * c.x, thr.y * c.y, thr.z * c.z, thr.w);
         }
-    }
+    });
 }
 
 // wfpt_env_mis_miss_weight: env_mis_weight for caller rows of an un-normalised direction, one thread per row
@@ -3247,77 +3228,100 @@ __global__ __launch_bounds__(kExtendThreads) void compact_kernel(CompactArgs a) 
 // ================================================================================================
 // accumulate (ac:4-17): pure streaming, 16 B per lane and sample
 // ================================================================================================
-__global__ __launch_bounds__(256) void accumulate_kernel(AccumulateArgs a) {
-    // accumulated += image_0; += image_1; ... in sample order, so a batch gives exactly the sums that sequential samples (one
-    // accumulate dispatch each, pt:362) would. One thread = one pixel: 16 B of each image slice (float4 per pixel) in, 12 B of
-    // `accumulated` (the reference's stride-12 layout) read and written. Sixteen samples' loads are in flight before the first add:
-    // a band-sharded slab gives a SIMD only a few waves, and with one sample per trip each had one load in flight (1.2 TB/s
-    // on 1/8 of the frame); the adds keep the sample order.
-    const size_t stride4 = a.batch.image_stride / 4u; // a slice is a whole number of float4 pixels
-    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n_pixels; i += gridDim.x * blockDim.x) {
-        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
-        const float4 *im0 = image4 + i;
-        uint32_t smp = 0;
-        for (; smp + 16u <= a.batch.n; smp += 16u) {
-            float4 p[16];
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; ++k) p[k] = im0[(smp + k) * stride4];
-#pragma unroll
-            for (uint32_t k = 0; k < 16u; ++k) { r += p[k].x; g += p[k].y; b += p[k].z; }
+// End of a fused batch (the last accumulate launch's block 0): the samples' per-wavefront rows -> the context's totals, frame += n.
+// One thread per sample and integer sums through LDS (one thread walking samples x rows of global memory took ~0.1 ms, a fixed cost
+// per frame that a band-sharded rank pays in full).
+__device__ __forceinline__ void accumulate_bookkeeping(const AccumulateArgs &a, uint32_t block) {
+    __shared__ unsigned long long s_rows[kMaxRows][2]; // hits, misses per wavefront over the batch
+    for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += block) (&s_rows[0][0])[k] = 0ull;
+    __syncthreads();
+    for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += block) {
+        const Control *c = a.ctl + smp;
+        const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
+        for (uint32_t b = 0; b < rows; ++b) {
+            if (c->rows[b][0] == 0) continue;
+            atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
+            atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
         }
-        for (; smp + 4u <= a.batch.n; smp += 4u) {
-            float4 p[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) p[k] = im0[(smp + k) * stride4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) { r += p[k].x; g += p[k].y; b += p[k].z; }
-        }
-        for (; smp < a.batch.n; ++smp) {
-            const float4 p = im0[smp * stride4];
-            r += p.x; g += p.y; b += p.z;
-        }
-        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
     }
-    if (blockIdx.x == 0 && a.bookkeeping) { // end of a fused batch: the samples' per-wavefront rows -> the context's totals
-        // one thread per sample and integer sums through LDS (one thread walking samples x rows of global memory took ~0.1 ms,
-        // a fixed cost per frame that a band-sharded rank pays in full)
-        __shared__ unsigned long long s_rows[kMaxRows][2]; // hits, misses per wavefront over the batch
-        for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += blockDim.x) (&s_rows[0][0])[k] = 0ull;
-        __syncthreads();
-        for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += blockDim.x) {
-            const Control *c = a.ctl + smp;
-            const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
-            for (uint32_t b = 0; b < rows; ++b) {
-                if (c->rows[b][0] == 0) continue;
-                atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
-                atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
-            }
+    __syncthreads();
+    Control *c0 = a.ctl;
+    if (threadIdx.x < kMaxRows) {
+        const uint32_t b = threadIdx.x;
+        const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
+        if (h + m) {
+            c0->wave_totals[b][0] += h + m;
+            c0->wave_totals[b][1] += h;
+            c0->wave_totals[b][2] += m;
         }
-        __syncthreads();
-        Control *c0 = a.ctl;
-        if (threadIdx.x < kMaxRows) {
-            const uint32_t b = threadIdx.x;
-            const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
-            if (h + m) {
-                c0->wave_totals[b][0] += h + m;
-                c0->wave_totals[b][1] += h;
-                c0->wave_totals[b][2] += m;
-            }
-        }
-        if (threadIdx.x == 0) {
-            unsigned long long h = 0, m = 0;
-            for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
-            c0->totals[0] += h + m;
-            c0->totals[1] += h;
-            c0->totals[2] += m;
-            c0->totals[3] += a.batch.n;
-            c0->samples += a.batch.n;
-            c0->ticket = 0; // the fused loop's last bounce launch drew tickets after the last scan
-            c0->frame.frame += a.batch.n; // RenderProgress::get_next_frame (parameters.rs:78-83) for the next samples
-        }
+    }
+    if (threadIdx.x == 0) {
+        unsigned long long h = 0, m = 0;
+        for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
+        c0->totals[0] += h + m;
+        c0->totals[1] += h;
+        c0->totals[2] += m;
+        c0->totals[3] += a.batch.n;
+        c0->samples += a.batch.n;
+        c0->ticket = 0; // the fused loop's last bounce launch drew tickets after the last scan
+        c0->frame.frame += a.batch.n; // RenderProgress::get_next_frame (parameters.rs:78-83) for the next samples
     }
 }
+
+// The pixel loop of the four accumulate kernels. accumulated += image_0; += image_1; ... in sample order, so a batch gives exactly the
+// sums that sequential samples (one accumulate dispatch each, pt:362) would. One thread = one pixel: 16 B of each image slice (float4
+// per pixel) in, 12 B of `accumulated` (the reference's stride-12 layout) read and written. TRIP samples' loads are in flight before
+// the first add, then TRIP2 (1: none), then single samples: a band-sharded slab gives a SIMD only a few waves, and with one sample per
+// trip each had one load in flight (1.2 TB/s on 1/8 of the frame); the adds keep the sample order.
+// EMIT (WFPT_FLAG_EMISSION contexts that hold an emitter; include/wfpt.h "Emission"): the sample's value is image_k + emitted_k, one add
+// for the value and one into the sum, two loads a sample. MOMENTS (WFPT_FLAG_DENOISE): plus the luminance moments of each sample's
+// value, the two extra planes read and written once per batch (8 B of 28 per pixel).
+// block: blockDim.x, read by the __global__ kernel and handed down, here and to accumulate_bookkeeping. Keep it so: read in a device
+// function the block size is not folded with the kernel's uniform-workgroup attribute (a 16-bit load chosen by the workgroup's index
+// instead), which cost accumulate_moments_kernel two VGPRs over its bound.
+template <bool EMIT, bool MOMENTS, uint32_t TRIP, uint32_t TRIP2>
+__device__ __forceinline__ void accumulate_body(const AccumulateArgs &a, const float *emitted, float *moments, Stride32 plane, uint32_t block) {
+    const size_t stride4 = a.batch.image_stride / 4u; // a slice is a whole number of float4 pixels
+    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
+    const float4 *emit4 = reinterpret_cast<const float4 *>(emitted);
+    float *s2p = MOMENTS ? moments + static_cast<size_t>(plane) : nullptr;
+    for (uint32_t i = blockIdx.x * block + threadIdx.x; i < a.n_pixels; i += gridDim.x * block) {
+        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
+        float s1 = 0.0f, s2 = 0.0f;
+        if (MOMENTS) { s1 = moments[i]; s2 = s2p[i]; }
+        auto add = [&](const float4 &p, const float4 &e) {
+            float vr = p.x, vg = p.y, vb = p.z;
+            if (EMIT) { vr += e.x; vg += e.y; vb += e.z; }
+            r += vr; g += vg; b += vb;
+            if (MOMENTS) {
+                const float l = denoise_luma(vr, vg, vb);
+                s1 += l; s2 += l * l;
+            }
+        };
+        const float4 *im0 = image4 + i, *em0 = EMIT ? emit4 + i : nullptr;
+        uint32_t smp = 0;
+        auto trips = [&](auto n) { // while N samples remain: N samples' loads, then their adds
+            constexpr uint32_t N = decltype(n)::value;
+            for (; smp + N <= a.batch.n; smp += N) {
+                float4 p[N], e[N];
+#pragma unroll
+                for (uint32_t k = 0; k < N; ++k) {
+                    p[k] = im0[(smp + k) * stride4];
+                    if (EMIT) e[k] = em0[(smp + k) * stride4]; // (add() reads e under EMIT only)
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < N; ++k) add(p[k], e[k]);
+            }
+        };
+        trips(std::integral_constant<uint32_t, TRIP>{});
+        if (TRIP2 > 1u) trips(std::integral_constant<uint32_t, TRIP2>{});
+        for (; smp < a.batch.n; ++smp) add(im0[smp * stride4], EMIT ? em0[smp * stride4] : float4{});
+        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
+        if (MOMENTS) { moments[i] = s1; s2p[i] = s2; }
+    }
+    if (blockIdx.x == 0 && a.bookkeeping) accumulate_bookkeeping(a, block);
+}
+__global__ __launch_bounds__(256) void accumulate_kernel(AccumulateArgs a) { accumulate_body<false, false, 16u, 4u>(a, nullptr, nullptr, Stride32{}, blockDim.x); }
 
 // ================================================================================================
 // helpers
@@ -3775,157 +3779,18 @@ __global__ __launch_bounds__(256) void aov_resolve_kernel(const float *sums, siz
 // ================================================================================================
 // denoiser (WFPT_FLAG_DENOISE; include/wfpt.h "Denoiser")
 // ================================================================================================
-// accumulate_kernel's adds in the same order -- `accumulated` gets the same bits -- plus the luminance moments of each sample's value.
-// Runs in place of accumulate_kernel on flagged contexts only (that kernel stays as it is: profiles and the resource tests key on it).
-// Four samples' loads in flight per trip: the moments' two extra planes read and written once per batch cost 8 B of 28 per pixel.
+// accumulate_kernel's adds in the same order -- `accumulated` gets the same bits -- plus the luminance moments of each sample's value
+// (accumulate_body's MOMENTS), in place of accumulate_kernel on flagged contexts only. Four samples' loads in flight per trip.
 __global__ __launch_bounds__(256) void accumulate_moments_kernel(AccumulateArgs a, float *moments, Stride32 plane) {
-    const size_t stride4 = a.batch.image_stride / 4u;
-    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
-    float *s2p = moments + static_cast<size_t>(plane);
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n_pixels; i += gridDim.x * blockDim.x) {
-        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
-        float s1 = moments[i], s2 = s2p[i];
-        const float4 *im0 = image4 + i;
-        uint32_t smp = 0;
-        for (; smp + 4u <= a.batch.n; smp += 4u) {
-            float4 p[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) p[k] = im0[(smp + k) * stride4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) {
-                r += p[k].x; g += p[k].y; b += p[k].z;
-                const float l = denoise_luma(p[k].x, p[k].y, p[k].z);
-                s1 += l; s2 += l * l;
-            }
-        }
-        for (; smp < a.batch.n; ++smp) {
-            const float4 p = im0[smp * stride4];
-            r += p.x; g += p.y; b += p.z;
-            const float l = denoise_luma(p.x, p.y, p.z);
-            s1 += l; s2 += l * l;
-        }
-        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
-        moments[i] = s1; s2p[i] = s2;
-    }
-    if (blockIdx.x == 0 && a.bookkeeping) { // the end of accumulate_kernel, restated: the batch's bounce rows -> totals, frame += n
-        __shared__ unsigned long long s_rows[kMaxRows][2];
-        for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += blockDim.x) (&s_rows[0][0])[k] = 0ull;
-        __syncthreads();
-        for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += blockDim.x) {
-            const Control *c = a.ctl + smp;
-            const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
-            for (uint32_t b = 0; b < rows; ++b) {
-                if (c->rows[b][0] == 0) continue;
-                atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
-                atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
-            }
-        }
-        __syncthreads();
-        Control *c0 = a.ctl;
-        if (threadIdx.x < kMaxRows) {
-            const uint32_t b = threadIdx.x;
-            const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
-            if (h + m) {
-                c0->wave_totals[b][0] += h + m;
-                c0->wave_totals[b][1] += h;
-                c0->wave_totals[b][2] += m;
-            }
-        }
-        if (threadIdx.x == 0) {
-            unsigned long long h = 0, m = 0;
-            for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
-            c0->totals[0] += h + m;
-            c0->totals[1] += h;
-            c0->totals[2] += m;
-            c0->totals[3] += a.batch.n;
-            c0->samples += a.batch.n;
-            c0->ticket = 0;
-            c0->frame.frame += a.batch.n;
-        }
-    }
+    accumulate_body<false, true, 4u, 1u>(a, nullptr, moments, plane, blockDim.x);
 }
-
-// ---- accumulate with the second per-sample plane (WFPT_FLAG_EMISSION contexts that hold an emitter; include/wfpt.h "Emission")
-// The end of accumulate_kernel and accumulate_moments_kernel, restated for the two kernels below (those two stay as they are): the
-// batch's bounce rows -> the context's totals, frame += n.
-__device__ __forceinline__ void accumulate_bookkeeping(const AccumulateArgs &a) {
-    __shared__ unsigned long long s_rows[kMaxRows][2]; // hits, misses per wavefront over the batch
-    for (uint32_t k = threadIdx.x; k < 2u * kMaxRows; k += blockDim.x) (&s_rows[0][0])[k] = 0ull;
-    __syncthreads();
-    for (uint32_t smp = threadIdx.x; smp < a.batch.n; smp += blockDim.x) {
-        const Control *c = a.ctl + smp;
-        const uint32_t rows = c->bounce < kMaxRows ? c->bounce : kMaxRows;
-        for (uint32_t b = 0; b < rows; ++b) {
-            if (c->rows[b][0] == 0) continue;
-            atomicAdd(&s_rows[b][0], static_cast<unsigned long long>(c->rows[b][1]));
-            atomicAdd(&s_rows[b][1], static_cast<unsigned long long>(c->rows[b][2]));
-        }
-    }
-    __syncthreads();
-    Control *c0 = a.ctl;
-    if (threadIdx.x < kMaxRows) {
-        const uint32_t b = threadIdx.x;
-        const unsigned long long h = s_rows[b][0], m = s_rows[b][1];
-        if (h + m) {
-            c0->wave_totals[b][0] += h + m;
-            c0->wave_totals[b][1] += h;
-            c0->wave_totals[b][2] += m;
-        }
-    }
-    if (threadIdx.x == 0) {
-        unsigned long long h = 0, m = 0;
-        for (uint32_t b = 0; b < kMaxRows; ++b) { h += s_rows[b][0]; m += s_rows[b][1]; }
-        c0->totals[0] += h + m;
-        c0->totals[1] += h;
-        c0->totals[2] += m;
-        c0->totals[3] += a.batch.n;
-        c0->samples += a.batch.n;
-        c0->ticket = 0;
-        c0->frame.frame += a.batch.n;
-    }
-}
-
-// accumulated += (image_k + emitted_k) in sample order: one add for the sample's value, one into the sum (MOMENTS: the luminance moments
-// take L of that same value). TRIP samples a trip, two loads each: 8 for the plain kernel -- accumulate_kernel's sixteen loads in flight
-// -- and 4 with the moments, accumulate_moments_kernel's trip.
-template <bool MOMENTS, uint32_t TRIP>
-__device__ __forceinline__ void accumulate_emission_body(const AccumulateArgs &a, const float *emitted, float *moments, Stride32 plane) {
-    const size_t stride4 = a.batch.image_stride / 4u;
-    const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
-    const float4 *emit4 = reinterpret_cast<const float4 *>(emitted);
-    float *s2p = MOMENTS ? moments + static_cast<size_t>(plane) : nullptr;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n_pixels; i += gridDim.x * blockDim.x) {
-        float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
-        float s1 = 0.0f, s2 = 0.0f;
-        if (MOMENTS) { s1 = moments[i]; s2 = s2p[i]; }
-        auto add = [&](const float4 &p, const float4 &e) {
-            const float vr = p.x + e.x, vg = p.y + e.y, vb = p.z + e.z;
-            r += vr; g += vg; b += vb;
-            if (MOMENTS) {
-                const float l = denoise_luma(vr, vg, vb);
-                s1 += l; s2 += l * l;
-            }
-        };
-        const float4 *im0 = image4 + i, *em0 = emit4 + i;
-        uint32_t smp = 0;
-        for (; smp + TRIP <= a.batch.n; smp += TRIP) {
-            float4 p[TRIP], e[TRIP];
-#pragma unroll
-            for (uint32_t k = 0; k < TRIP; ++k) { p[k] = im0[(smp + k) * stride4]; e[k] = em0[(smp + k) * stride4]; }
-#pragma unroll
-            for (uint32_t k = 0; k < TRIP; ++k) add(p[k], e[k]);
-        }
-        for (; smp < a.batch.n; ++smp) add(im0[smp * stride4], em0[smp * stride4]);
-        a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
-        if (MOMENTS) { moments[i] = s1; s2p[i] = s2; }
-    }
-    if (blockIdx.x == 0 && a.bookkeeping) accumulate_bookkeeping(a);
-}
+// ... with the second per-sample plane (accumulate_body's EMIT): 8 samples a trip for the plain kernel -- accumulate_kernel's sixteen loads
+// in flight -- and 4 with the moments, accumulate_moments_kernel's trip.
 __global__ __launch_bounds__(256) void accumulate_emission_kernel(AccumulateArgs a, const float *emitted) {
-    accumulate_emission_body<false, 8u>(a, emitted, nullptr, Stride32{});
+    accumulate_body<true, false, 8u, 1u>(a, emitted, nullptr, Stride32{}, blockDim.x);
 }
 __global__ __launch_bounds__(256) void accumulate_emission_moments_kernel(AccumulateArgs a, const float *emitted, float *moments, Stride32 plane) {
-    accumulate_emission_body<true, 4u>(a, emitted, moments, plane);
+    accumulate_body<true, true, 4u, 1u>(a, emitted, moments, plane, blockDim.x);
 }
 
 // The filter's pixel of this thread: a workgroup covers a kDenoiseTile^2 block, each wave an 8 x 8 block of it (2-D locality for the taps,
@@ -4520,8 +4385,18 @@ hipError_t launch_env_mis_weight(const EnvDist &env, const float *dirs3, float *
     return hipGetLastError();
 }
 
-hipError_t launch_accumulate(const AccumulateArgs &a, uint32_t grid, hipStream_t s) {
-    hipLaunchKernelGGL(accumulate_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a);
+hipError_t launch_accumulate(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s) {
+    const dim3 g(grid ? grid : 1u), b(256);
+    Stride32 pl{};
+    pl = plane;
+    if (emitted && moments)
+        hipLaunchKernelGGL(accumulate_emission_moments_kernel, g, b, 0, s, a, emitted, moments, pl);
+    else if (emitted)
+        hipLaunchKernelGGL(accumulate_emission_kernel, g, b, 0, s, a, emitted);
+    else if (moments)
+        hipLaunchKernelGGL(accumulate_moments_kernel, g, b, 0, s, a, moments, pl);
+    else
+        hipLaunchKernelGGL(accumulate_kernel, g, b, 0, s, a);
     return hipGetLastError();
 }
 
@@ -4637,23 +4512,6 @@ hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, u
     const size_t blocks = (n_words + 255) / 256;
     hipLaunchKernelGGL(aov_resolve_kernel, dim3(static_cast<uint32_t>(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, sums, plane, which,
                        n_samples, out, n_words);
-    return hipGetLastError();
-}
-
-hipError_t launch_accumulate_moments(const AccumulateArgs &a, float *moments, size_t plane, uint32_t grid, hipStream_t s) {
-    Stride32 pl{};
-    pl = plane;
-    hipLaunchKernelGGL(accumulate_moments_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, moments, pl);
-    return hipGetLastError();
-}
-
-hipError_t launch_accumulate_emission(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s) {
-    Stride32 pl{};
-    pl = plane;
-    if (moments)
-        hipLaunchKernelGGL(accumulate_emission_moments_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, emitted, moments, pl);
-    else
-        hipLaunchKernelGGL(accumulate_emission_kernel, dim3(grid ? grid : 1u), dim3(256), 0, s, a, emitted);
     return hipGetLastError();
 }
 
