@@ -10,6 +10,8 @@
 //     launch stays balanced by whoever is free.
 // A workgroup's items ascend: its static items, then n_static + b, then what it draws (all larger).
 // share = WFPT_FIRST_STATIC_SHARE_NUM / WFPT_FIRST_STATIC_SHARE_DEN; 0 is the launch as it was up to round 6.
+// Since round 9 a ticket of the dynamic range buys a chunk of items (wfpt_ticket_chunks.h: ticket -> position, item = n_static + position;
+// with a chunk length of 1 the position is the ticket, as described here), and share 0 ships.
 #pragma once
 #include <stdint.h>
 

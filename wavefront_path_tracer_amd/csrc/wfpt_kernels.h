@@ -9,6 +9,7 @@
 #include "wfpt_bvh4.h"
 #include "wfpt_device_math.h"
 #include "wfpt_first_schedule.h"
+#include "wfpt_ticket_chunks.h"
 #include "wfpt_tile_lists.h"
 
 namespace wfpt {
@@ -257,15 +258,35 @@ constexpr int kMissSegsPerItem = WFPT_MISS_SEGS; // miss work item = this many i
 #endif
 constexpr uint32_t kMissEvery = WFPT_MISS_EVERY; // fused bounce launches: every kMissEvery-th ticket is a miss item while both kinds are left; 0 = hit items / miss items + 1, per launch
 #ifndef WFPT_FIRST_STATIC_SHARE_NUM
-#define WFPT_FIRST_STATIC_SHARE_NUM 1
+#define WFPT_FIRST_STATIC_SHARE_NUM 0
 #endif
 #ifndef WFPT_FIRST_STATIC_SHARE_DEN
 #define WFPT_FIRST_STATIC_SHARE_DEN 2
 #endif
 // bounce_kernel<kBounceFirst>: the share of its items that the workgroups take without a ticket (wfpt_first_schedule.h); 0 = every item by ticket.
-// 1/2 is the best of the sweep 0 .. 1 (profiles/r07_first_schedule_ab.txt): a larger share leaves too short a tail to even out the workgroups
+// 1/2 was the best of the sweep 0 .. 1 while every other item cost a draw (profiles/r07_first_schedule_ab.txt); since a draw buys a chunk
+// (below) share 0 is the fastest at every chunk length (profiles/r09_chunk_schedule_ab.txt) and ships: the whole launch is handed out dynamically
 constexpr uint32_t kFirstStaticNum = WFPT_FIRST_STATIC_SHARE_NUM, kFirstStaticDen = WFPT_FIRST_STATIC_SHARE_DEN;
 static_assert(kFirstStaticDen > 0 && kFirstStaticNum <= kFirstStaticDen, "the static share of the first launch's items lies in [0, 1]");
+#ifndef WFPT_FIRST_CHUNK
+#define WFPT_FIRST_CHUNK 4
+#endif
+#ifndef WFPT_FIRST_TAIL_ROUNDS
+#define WFPT_FIRST_TAIL_ROUNDS 4
+#endif
+#ifndef WFPT_BOUNCE_CHUNK
+#define WFPT_BOUNCE_CHUNK 4
+#endif
+#ifndef WFPT_BOUNCE_TAIL_ROUNDS
+#define WFPT_BOUNCE_TAIL_ROUNDS 4
+#endif
+// What one draw from Control::ticket buys (wfpt_ticket_chunks.h): a chunk of this many consecutive positions, but for the last
+// `tail rounds` positions per workgroup, which go out singly. The first launch applies it to the items behind its static range, the
+// middle and last launches to their tickets (before TicketMap). 1 = one position per draw, the launches as they were up to round 8.
+// 4 and 4 tail rounds are the best of the sweeps for both (profiles/r09_chunk_schedule_ab.txt); the tail rounds hardly matter (2, 4, 8 alike).
+constexpr uint32_t kFirstChunk = WFPT_FIRST_CHUNK, kFirstTailRounds = WFPT_FIRST_TAIL_ROUNDS;
+constexpr uint32_t kBounceChunk = WFPT_BOUNCE_CHUNK, kBounceTailRounds = WFPT_BOUNCE_TAIL_ROUNDS;
+static_assert(kFirstChunk >= 1 && kBounceChunk >= 1, "a draw buys at least one position");
 
 struct BounceArgs {
     Batch batch;

@@ -2362,7 +2362,14 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     // item through both ranges; every other launch has no static range.
     constexpr bool STATIC = MODE == kBounceFirst && kFirstStaticNum > 0;
     const uint32_t n_static = STATIC ? uniform(first_n_static(n_items, gridDim.x, kFirstStaticNum, kFirstStaticDen)) : 0u;
+    // Behind the static range -- in every other launch: from ticket 0 -- a draw buys CHUNK consecutive positions and the last positions go
+    // out singly (wfpt_ticket_chunks.h): position p is item n_static + p here, ticket p there. CHUNK 1: a position is its draw.
+    constexpr uint32_t CHUNK = MODE == kBounceFirst ? kFirstChunk : kBounceChunk, TAIL_ROUNDS = MODE == kBounceFirst ? kFirstTailRounds : kBounceTailRounds;
+    constexpr bool CHUNKED = CHUNK > 1;
+    const uint32_t n_dynamic = n_items - n_static;
+    const uint32_t chunk_end = CHUNKED ? uniform(chunk_body(n_dynamic, gridDim.x, CHUNK, TAIL_ROUNDS)) : 0u; // positions [0, chunk_end) go out in chunks
     uint32_t ticket = blockIdx.x;
+    if (CHUNKED && n_static == 0u) ticket = chunk_draw_position(ticket, n_dynamic, chunk_end, CHUNK); // (no static round leads to the workgroup's own draw)
     if (ticket >= n_items) return;
     uint32_t item = tickets.item_of(ticket);
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
@@ -2378,9 +2385,20 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     unsigned long long acc_ticket = 0; // first launch, wave 0: from issuing the ticket's atomic to holding its value
     uint32_t acc_cnt[5] = {0, 0, 0, 0, 0}, acc_drawn = 0;
 #endif
+    // the item after this one, from the loop's in_static / in_chunk (DRAWN: what the draw at the top of this item left in L.next[buf], read only where it is needed)
+#define WFPT_NEXT_TICKET(DRAWN)                                                                                                        \
+    if (in_static) {                                                                                                                   \
+        ticket += gridDim.x;                                                                                                           \
+        if (CHUNKED && ticket >= n_static) ticket = n_static + chunk_draw_position(ticket - n_static, n_dynamic, chunk_end, CHUNK);    \
+    } else if (in_chunk) ticket += 1u;                                                                                                 \
+    else if (CHUNKED) ticket = n_static + chunk_draw_position(DRAWN, n_dynamic, chunk_end, CHUNK);                                     \
+    else ticket = first_dynamic_item(n_static, DRAWN);                                                                                 \
+    item = tickets.item_of(ticket);
     while (ticket < n_items) {
         const uint32_t buf = iter & 1u;
-        const bool next_static = STATIC && first_next_is_static(ticket, n_static); // (uniform) the next item follows from this one: no ticket
+        const bool in_static = STATIC && first_next_is_static(ticket, n_static);                         // (uniform) the next item is this one + the grid,
+        const bool in_chunk = CHUNKED && !in_static && chunk_follows(ticket - n_static, chunk_end, CHUNK); // (uniform) or this one + 1:
+        const bool next_static = in_static || in_chunk;                                                    // either way it follows from this one, no ticket
 #if WFPT_STAMPS
         if (MODE == kBounceFirst && !next_static && wave == 0) { // (the wait is the one the store to L.next makes anyway, placed between two stamps)
             WFPT_STAMP(t_draw);
@@ -2398,8 +2416,12 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             while (item >= first_m + uniform(L.items_m[smp_m])) first_m += uniform(L.items_m[smp_m++]);
             WFPT_MISS_ITEM(smp_m, (item - first_m) * kMissSegsPerItem, (uniform(umin(a.ctl[smp_m].seg_n, a.capacity)) + kChunk - 1) / kChunk);
             __syncthreads(); // L.next[buf] is visible
-            ticket = uniform(L.next[buf]);
-            item = tickets.item_of(ticket);
+            if (MODE == kBounceFirst) { // (the first launch has no miss items: its arm stays the parent's instructions)
+                ticket = uniform(L.next[buf]);
+                item = tickets.item_of(ticket);
+            } else {
+                WFPT_NEXT_TICKET(uniform(L.next[buf]));
+            }
             iter += 1;
             continue;
         }
@@ -2438,8 +2460,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         }
         if (!TRACE) {
             __syncthreads();
-            ticket = uniform(L.next[buf]);
-            item = tickets.item_of(ticket);
+            WFPT_NEXT_TICKET(uniform(L.next[buf]));
             iter += 1;
             continue;
         }
@@ -2529,11 +2550,10 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             acc_cnt[2] += w_visits; acc_cnt[3] += w_leaves; acc_cnt[4] += l_visits;
         }
 #endif
-        if (next_static) ticket += gridDim.x;
-        else ticket = first_dynamic_item(n_static, uniform(L.next[buf]));
-        item = tickets.item_of(ticket);
+        WFPT_NEXT_TICKET(uniform(L.next[buf]));
         iter += 1;
     }
+#undef WFPT_NEXT_TICKET
 #if WFPT_STAMPS
     if (MODE == kBounceFirst && a.stamps && lane == 0) { // counters 48..63: wfpt_debug_read_stamps_ex(which = 3)
         for (int k = 0; k < 4; ++k) atomicAdd(&a.stamps[48 + k], acc_cyc[k]);
