@@ -249,7 +249,10 @@ enum {
                                         WFPT_FLAG_MIS. With no map set (or a black one) the context renders bit for bit as without the
                                         flag, and launches the same kernels. */
     WFPT_FLAG_NO_TILE_LISTS = 1u << 19 /* the first fused launch walks the tree for every tile instead of testing its tile's candidate list,
-                                        see "Tile lists" below (A/B runs and tests; the results are the same bits either way) */
+                                        see "Tile lists" below (A/B runs and tests; the results are the same bits either way) */,
+    WFPT_FLAG_RETIRE = 1u << 20      /* path termination, see "Path termination" below: a path whose throughput is zero is retired at
+                                        once, and from wavefront roulette_start on Russian roulette retires or re-weights the others.
+                                        Refused with WFPT_FLAG_BINNING; combines freely with every other flag. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -762,8 +765,8 @@ int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
  * context with the flag and an emitter never runs the class-binned loop (set and clear on such a context are refused, see "Emission");
  * wfpt_render_chunked* masks the flag off. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag.
- * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, retiring dead or fully
- * shadowed paths, contact shadows thinner than the 0.001 / 0.1 % windows. (Importance sampling of the environment map: WFPT_FLAG_ENV_NEE.) */
+ * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, retiring fully
+ * shadowed paths (dead ones: WFPT_FLAG_RETIRE), contact shadows thinner than the 0.001 / 0.1 % windows. (Importance sampling of the environment map: WFPT_FLAG_ENV_NEE.) */
 /* the number of emitting primitives (the light list's length), 0 with none; negative: a wfpt_status */
 int wfpt_nee_light_count(wfpt_ctx *ctx);
 /* the connect launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
@@ -821,7 +824,7 @@ int wfpt_sample_lights(wfpt_ctx *ctx, const float *in9, size_t n, float *out8);
  * (Multiple importance sampling between the map and the scatter: WFPT_FLAG_ENV_MIS, "Environment multiple importance sampling" below.)
  * Not done: a distribution that accounts for the receiver's normal or for
  * visibility, a coarser importance grid or an alias table for very large maps, the class-binned loop and wfpt_render_chunked*, object
- * lights selected by power, retiring dead paths. */
+ * lights selected by power. */
 /* the environment share: finite, in (0, 1]. Acts like wfpt_set_emission: the accumulation restarts, the graphs and the history are dropped */
 int wfpt_set_environment_share(wfpt_ctx *ctx, float share);
 float wfpt_environment_share(const wfpt_ctx *ctx); /* 0 on a context without the flag */
@@ -876,7 +879,7 @@ int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, fl
  * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while no primitive emits.
  * (Weighing the environment map against the scatter: WFPT_FLAG_ENV_MIS, a flag of its own below; WFPT_FLAG_ENV_NEE stays refused here.)
  * Not done: the power heuristic, cone sampling of
- * sphere lights, light selection by power, MIS for fuzzy metal, retiring dead paths, the class-binned loop and wfpt_render_chunked*. */
+ * sphere lights, light selection by power, MIS for fuzzy metal, the class-binned loop and wfpt_render_chunked*. */
 /* Steps 3 to 5 with the weight for n caller-supplied receivers on the device. in9: as wfpt_sample_lights; out12: n rows of (q.xyz, the
  * light's primitive index as a float, ((e_q * G) * wl) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pl, pb, wl, 0) --
  * the three channels and pl, pb, wl are 0 where the sample contributes nothing. */
@@ -932,7 +935,7 @@ int wfpt_mis_hit_weight(wfpt_ctx *ctx, const float *in8, size_t n, float *out4);
  * return WFPT_ERR_INVALID_ARGUMENT on a context without the flag, while no map with a distribution is set, and for a NULL pointer with
  * n > 0.
  * Not done: the power heuristic, a distribution aware of the receiver's normal, MIS for fuzzy metal, the class-binned loop,
- * wfpt_render_chunked*, retiring dead paths, the samplers of WFPT_FLAG_MIS (wfpt_sample_lights_mis, wfpt_mis_hit_weight) on a context
+ * wfpt_render_chunked*, the samplers of WFPT_FLAG_MIS (wfpt_sample_lights_mis, wfpt_mis_hit_weight) on a context
  * with this flag. */
 /* The environment branch with its weight for n caller-supplied receivers on the device. in10: as wfpt_sample_environment_light; out12: n
  * rows of (wdir.xyz, f32(y * w + x), ((e * Genv) * we) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pe, pb, we, 0) --
@@ -941,6 +944,53 @@ int wfpt_sample_environment_light_mis(wfpt_ctx *ctx, const float *in10, size_t n
 /* The miss pass's weight for n caller-supplied directions on the device. dirs3: n rows of an un-normalised direction; out4: n rows of
  * (pe, pb, wb, f32(yt * w + xt)). */
 int wfpt_env_mis_miss_weight(wfpt_ctx *ctx, const float *dirs3, size_t n, float *out4);
+
+/* ------------------------------------------------------------------ Path termination (WFPT_FLAG_RETIRE)
+ * Without this flag no path ends before it misses or max_wavefronts ends it: a path that hit an emitter (thr = +0, "Emission") is
+ * scattered, traced, connected and shaded on, and a closed room rendered with miss_floor = 0 runs every path to max_wavefronts.
+ * wfpt_create* refuses the flag together with WFPT_FLAG_BINNING (WFPT_ERR_INVALID_ARGUMENT): such a context never runs the class-binned
+ * loop. wfpt_render_chunked* masks the flag off, as the other feature flags. It combines freely with every other flag.
+ *
+ * A flagged context holds a wfpt_termination_params (defaults: roulette_start = 3, q_min = 0.05; roulette_start = 0xffffffff means no
+ * roulette; q_min must be finite and in (0, 1]; _reserved must be 0). The termination step sits at the end of the shade step of
+ * wavefront b (b = 0 for the primary hits; the stage API counts the extend stages since the last generate_rays stage, as the connect pass
+ * does). The step order stays texture, emission, connect, shade. Shade forms t' = thr * albedo as before, the same bits, and then:
+ *  1. The step applies only if b + 1 < max_wavefronts: the last shade of a loop emits nothing that is ever traced and stays as it is.
+ *  2. Dead. If t'.x == 0 && t'.y == 0 && t'.z == 0 the hit is retired and thr <- t' as before (a -0 counts as zero; a NaN channel makes
+ *     the test false).
+ *  3. Roulette. Otherwise, if roulette_start != 0xffffffff and b >= roulette_start:
+ *       m = t'.x;  if (t'.y > m) m = t'.y;  if (t'.z > m) m = t'.z
+ *       q = m;  if (!(q >= q_min)) q = q_min          (a NaN m gives q_min)
+ *       if q >= 1: the hit survives untouched and nothing is drawn. Otherwise one u is drawn from a stream of the step's own, keyed
+ *       by the pixel in both RNG modes, with `frame` the sample's frame as the connect pass takes it:
+ *         s = jenkins_hash(pixel_idx ^ jenkins_hash(frame));  s <- jenkins_hash(s ^ (0x85EBCA6Bu * (b + 1)));  u = rng_next_float(s)
+ *       if u < q: the hit survives with thr <- t' / q (three IEEE f32 divisions); otherwise it is retired with thr <- (+0, +0, +0).
+ *       thr.w stays as it is.
+ *  4. A retired hit emits an INACTIVE extension ray: the next extend neither hits nor misses with it. It still occupies its slot:
+ *     rays_in of the bounce table, counters[2] and n_in count slots as before, and the retired paths show up as rays_in - hits -
+ *     misses. Shade's own RNG, the scatter, and the hit order and thread index of the surviving hits (shade's key under
+ *     WFPT_RNG_DISPATCH) are those of a queue with gaps, exactly as for the padding rays of an image whose size is no multiple of 8.
+ *     A survivor's scatter is unchanged; a retired hit's extension ray holds no direction anyone may rely on.
+ * What does not change: the loop exit `misses < miss_floor` is untouched -- it now sees fewer misses in later wavefronts, so a flagged
+ * context may leave the loop a wavefront earlier than an unflagged one; emission, connect, miss, the AOVs, accumulation, the moments and
+ * the denoisers. The connected flag and the `origin` plane of a retired path are never read again. With the flag clear every context
+ * launches the kernels it launched before.
+ * wfpt_set_termination drops the captured graphs and restarts the accumulation, like wfpt_set_emission. The calls below return
+ * WFPT_ERR_INVALID_ARGUMENT on a context without the flag or for a bad parameter; a refused call leaves the context as it was.
+ * Not done: retiring fully shadowed paths, the class-binned loop and wfpt_render_chunked*. */
+typedef struct wfpt_termination_params {
+    uint32_t roulette_start; /* first wavefront b whose shade step plays roulette; 0xffffffff = never */
+    float q_min;             /* the survival probability's floor, in (0, 1] */
+    uint32_t _reserved[6];   /* must be 0 */
+} wfpt_termination_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_termination_params) == 32, "wfpt_termination_params is 32 bytes");
+void wfpt_termination_params_default(wfpt_termination_params *p);
+int wfpt_set_termination(wfpt_ctx *ctx, const wfpt_termination_params *p);
+int wfpt_get_termination(wfpt_ctx *ctx, wfpt_termination_params *p);
+/* Steps 2 and 3 (without the test of step 1) for n caller-supplied hits on the device, blocking. thr3: n rows of t'; pixel_idx: n
+ * pixels; frame, b: the sample's frame and the wavefront. out8: n rows of (q, u, verdict, 0, thr'.rgb, 0) -- verdict 0 = retired dead,
+ * 1 = retired by roulette, 2 = survives; q and u are 0 where nothing is drawn. */
+int wfpt_sample_termination(wfpt_ctx *ctx, const float *thr3, const uint32_t *pixel_idx, uint32_t frame, uint32_t b, size_t n, float *out8);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

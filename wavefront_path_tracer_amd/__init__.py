@@ -48,6 +48,8 @@ FLAG_MIS = 1 << 17
 # of FLAG_ENV_NEE, refused with FLAG_MIS
 FLAG_ENV_MIS = 1 << 18
 FLAG_NO_TILE_LISTS = 1 << 19  # the first fused launch walks the tree for every tile (include/wfpt.h "Tile lists")
+FLAG_RETIRE = 1 << 20  # dead paths are retired and Russian roulette ends or re-weights the others (include/wfpt.h "Path termination")
+NO_ROULETTE = 0xFFFFFFFF  # set_termination(roulette_start=NO_ROULETTE): dead paths alone are retired
 TILE_LIST_CAP, TILE_NO_LIST = 16, 0xFFFFFFFF
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
@@ -108,6 +110,10 @@ class _DenoiseParams(C.Structure):
 
 class _EnvironmentParams(C.Structure):
     _fields_ = [("intensity", C.c_float), ("rotation", C.c_float), ("_reserved", C.c_uint32 * 6)]
+
+
+class _TerminationParams(C.Structure):
+    _fields_ = [("roulette_start", C.c_uint32), ("q_min", C.c_float), ("_reserved", C.c_uint32 * 6)]
 
 
 class _TextureParams(C.Structure):
@@ -364,6 +370,10 @@ def lib():
         "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
         "wfpt_sample_environment_light_mis": (i32, [vp, vp, sz, vp]),
         "wfpt_env_mis_miss_weight": (i32, [vp, vp, sz, vp]),
+        "wfpt_termination_params_default": (None, [C.POINTER(_TerminationParams)]),
+        "wfpt_set_termination": (i32, [vp, C.POINTER(_TerminationParams)]),
+        "wfpt_get_termination": (i32, [vp, C.POINTER(_TerminationParams)]),
+        "wfpt_sample_termination": (i32, [vp, vp, vp, u32, u32, sz, vp]),
         "wfpt_tile_lists_host": (i32, [vp, u32, vp, vp, vp, u32, u32, u32, u32, vp, u32]),
         "wfpt_debug_nodes_ch": (i32, [vp, u32, vp, vp]),
         "wfpt_debug_read_tile_lists": (i32, [vp, vp, C.POINTER(u32)]),
@@ -1505,6 +1515,32 @@ class PathTracer:
         """The miss pass's weight for caller-supplied un-normalised directions, computed on the device. dirs: (n, 3) float32; returns
         (n, 4) float32 of (pe, pb, wb, the texel index yt * w + xt)."""
         return self._probe(lib().wfpt_env_mis_miss_weight, "env_mis_miss_weight", dirs, 3, 4)
+
+    # ---- path termination (contexts created with FLAG_RETIRE; include/wfpt.h "Path termination")
+    def set_termination(self, roulette_start=3, q_min=0.05):
+        """Russian roulette from wavefront `roulette_start` on (NO_ROULETTE: never) with the survival probability's floor `q_min`, in
+        (0, 1]. Restarts the accumulation."""
+        p = _TerminationParams(int(roulette_start) & 0xFFFFFFFF, float(q_min))
+        self._check(lib().wfpt_set_termination(self.handle, C.byref(p)))
+        self.render_progress.reset()
+
+    def termination(self):
+        """(roulette_start, q_min) of the context."""
+        p = _TerminationParams()
+        self._check(lib().wfpt_get_termination(self.handle, C.byref(p)))
+        return int(p.roulette_start), float(p.q_min)
+
+    def sample_termination(self, thr, pixel_idx, frame, b):
+        """The termination step for caller-supplied hits of wavefront `b` of the sample with frame `frame`, computed on the device.
+        thr: (n, 3) float32 of t' = thr * albedo; pixel_idx: (n,) uint32; returns (n, 8) float32 of (q, u, verdict, 0, thr'.rgb, 0) with
+        verdict 0 = retired dead, 1 = retired by roulette, 2 = survives."""
+        thr = np.ascontiguousarray(thr, "<f4").reshape(-1, 3)
+        pix = np.ascontiguousarray(pixel_idx, "<u4").reshape(-1)
+        if len(pix) != len(thr):
+            raise ValueError("sample_termination: thr and pixel_idx differ in length")
+        out = np.zeros((len(thr), 8), "<f4")
+        self._check(lib().wfpt_sample_termination(self.handle, _p(thr), _p(pix), int(frame) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF, len(thr), _p(out)))
+        return out
 
     # ---- read-back
     def accumulated(self):

@@ -262,6 +262,7 @@ struct wfpt_ctx {
     DeviceBuffer<uint64_t> env_marg;
     uint64_t env_total = 0;
     float env_share = 0.5f;
+    wfpt_termination_params term{3u, 0.05f, {0, 0, 0, 0, 0, 0}}; // WFPT_FLAG_RETIRE: wfpt_set_termination
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -419,6 +420,11 @@ GenerateArgs generate_args(wfpt_ctx *c, uint32_t gx, uint32_t gy, bool fused, ui
     a.tile = c->tile;
     return a;
 }
+// a WFPT_FLAG_RETIRE context (include/wfpt.h "Path termination"): the shade step of wavefront b ends with the termination step while
+// b + 1 < max_wavefronts -- the last shade of a loop emits nothing that is ever traced and stays as it is
+bool retiring(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_RETIRE) != 0; }
+bool retires_at(const wfpt_ctx *c, uint32_t b) { return retiring(c) && b + 1u < c->p.max_wavefronts; }
+TermArgs term_args(const wfpt_ctx *c, uint32_t b) { return TermArgs{b, c->term.roulette_start, c->term.q_min}; }
 ExtendArgs extend_args(wfpt_ctx *c, int qi, const uint32_t *n_in, uint32_t limit, uint32_t nb = 1, bool partition = true) {
     ExtendArgs a{};
     a.batch = batch_of(c, nb);
@@ -436,7 +442,7 @@ ExtendArgs extend_args(wfpt_ctx *c, int qi, const uint32_t *n_in, uint32_t limit
     a.ctl = c->ctl.get();
     a.n_in = n_in;
     a.limit = std::min(limit, c->capacity);
-    a.has_inactive = c->has_inactive ? 1u : 0u;
+    a.has_inactive = (c->has_inactive || retiring(c)) ? 1u : 0u; // (a retired hit's extension ray is inactive)
     a.scene = c->scene;
     return a;
 }
@@ -799,7 +805,8 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
                      ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
                      sa.rec_in = c->hit_rec.get(); // this wavefront's extend has just written them
-                     return launch_shade(sa, consumer_grid(c, nb), st);
+                     const TermArgs term = term_args(c, b);
+                     return launch_shade(sa, consumer_grid(c, nb), st, retires_at(c, b) ? &term : nullptr);
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] {
                      return launch_miss_pass(c, miss_args(c, qi, &c->ctl.get()->miss_n, c->capacity, nb), consumer_grid(c, nb));
@@ -828,7 +835,9 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
-                     return launch_bounce(bounce_args(c, par, par ^ 1, nb), last ? kBounceLast : kBounceMiddle, grid, st, env != nullptr);
+                     BounceArgs a = bounce_args(c, par, par ^ 1, nb);
+                     a.term = term_args(c, b);
+                     return launch_bounce(a, last ? kBounceLast : retiring(c) ? kBounceMiddleRetire : kBounceMiddle, grid, st, env != nullptr);
                  }));
     }
     return WFPT_OK;
@@ -874,8 +883,13 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb)); r != WFPT_OK) return r;
         if (!last) {
-            WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] { return launch_shade_rays(refill_args(c, par, nb), c->n_chunks_max, st); }));
-            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE, [&] { return launch_refill(refill_args(c, par, nb), kBounceMiddle, grid, st); }));
+            WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] {
+                         RefillArgs a = refill_args(c, par, nb);
+                         a.term = term_args(c, b);
+                         return launch_shade_rays(a, c->n_chunks_max, st, retiring(c));
+                     }));
+            WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE,
+                              [&] { return launch_refill(refill_args(c, par, nb), retiring(c) ? kBounceMiddleRetire : kBounceMiddle, grid, st); }));
         } else {
             WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_LAST,
                               [&] { return launch_bounce(bounce_args(c, par, par ^ 1, nb), kBounceLast, bounce_grid(c, nb), st, env != nullptr); }));
@@ -1495,6 +1509,10 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
                                                  "shade.wgsl:72's RNG key, the dispatch's thread index, does not allow)");
         return nullptr;
     }
+    if ((params->flags & WFPT_FLAG_RETIRE) != 0 && (params->flags & WFPT_FLAG_BINNING) != 0) {
+        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_RETIRE does not go with WFPT_FLAG_BINNING (the class-binned loop has no termination step)");
+        return nullptr;
+    }
     if ((params->flags & WFPT_FLAG_NEE) != 0 && (params->flags & WFPT_FLAG_EMISSION) == 0) {
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
         return nullptr;
@@ -1748,7 +1766,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS); // AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -2009,7 +2027,9 @@ int wfpt_kernel_run(wfpt_ctx *c, int stage, uint32_t gx, uint32_t gy) {
         const uint32_t *n_hits = &c->ctl.get()->counters[1];
         if (int r = enqueue_pre_shade(c, untimed, stage_wavefront(c), 1, hit_walk(c, -1, 1, c->cur, n_hits, threads, material)); r != WFPT_OK)
             return r;
-        WFPT_HIP(c, launch_shade(shade_args(c, c->cur, n_hits, threads, gx, material, true), consumer_grid(c, 1), c->stream.get()));
+        ShadeArgs sa = shade_args(c, c->cur, n_hits, threads, gx, material, true);
+        const TermArgs term = term_args(c, stage_wavefront(c));
+        WFPT_HIP(c, launch_shade(sa, consumer_grid(c, 1), c->stream.get(), retires_at(c, stage_wavefront(c)) ? &term : nullptr));
         break;
     }
     case WFPT_STAGE_MISS:
@@ -3396,6 +3416,46 @@ int wfpt_env_mis_miss_weight(wfpt_ctx *c, const float *dirs3, size_t n, float *o
     if (int r = env_mis_check(c, "wfpt_env_mis_miss_weight"); r != WFPT_OK) return r;
     return probe(c, "wfpt_env_mis_miss_weight", dirs3, 3, out4, 4, n, true, [&](const float *d_in, float *d_out) {
         return launch_env_mis_weight(env_dist(c), d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
+}
+
+// ---------------------------------------------------------------- path termination (include/wfpt.h "Path termination")
+static int retire_check(const wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_RETIRE, "WFPT_FLAG_RETIRE"); }
+
+void wfpt_termination_params_default(wfpt_termination_params *p) {
+    if (p) *p = wfpt_termination_params{3u, 0.05f, {0, 0, 0, 0, 0, 0}};
+}
+
+int wfpt_set_termination(wfpt_ctx *c, const wfpt_termination_params *p) {
+    if (int r = retire_check(c, "wfpt_set_termination"); r != WFPT_OK) return r;
+    if (!p) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_termination: null parameters");
+    if (!(p->q_min > 0.0f && p->q_min <= 1.0f)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_termination: q_min must be in (0, 1]");
+    for (uint32_t r : p->_reserved)
+        if (r != 0u) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_termination: _reserved must be 0");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    c->term = *p;
+    return scene_changed(c); // the captured graphs hold the parameters in their kernel arguments
+}
+
+int wfpt_get_termination(wfpt_ctx *c, wfpt_termination_params *p) {
+    if (int r = retire_check(c, "wfpt_get_termination"); r != WFPT_OK) return r;
+    if (!p) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_termination: null parameters");
+    *p = c->term;
+    return WFPT_OK;
+}
+
+int wfpt_sample_termination(wfpt_ctx *c, const float *thr3, const uint32_t *pixel_idx, uint32_t frame, uint32_t b, size_t n, float *out8) {
+    if (int r = retire_check(c, "wfpt_sample_termination"); r != WFPT_OK) return r;
+    if ((!thr3 || !pixel_idx || !out8) && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_termination: null argument");
+    if (n > 0x7fffffffu) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_termination: too many rows");
+    std::vector<float> in4(4 * n); // (t'.rgb | the pixel index's bits) a row
+    for (size_t i = 0; i < n; ++i) {
+        std::memcpy(&in4[4 * i], thr3 + 3 * i, 3 * sizeof(float));
+        std::memcpy(&in4[4 * i + 3], pixel_idx + i, sizeof(uint32_t));
+    }
+    return probe(c, "wfpt_sample_termination", in4.data(), 4, out8, 8, n, true, [&](const float *d_in, float *d_out) {
+        return launch_termination_sampler(term_args(c, b), frame, d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
     });
 }
 

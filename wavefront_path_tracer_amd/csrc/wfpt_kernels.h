@@ -249,6 +249,13 @@ struct ScanArgs {
 constexpr int kBounceFirst = 0;  // generate_rays -> extend                 (wavefront 0)
 constexpr int kBounceMiddle = 1; // shade -> extend, miss_kernel            (wavefronts 1 .. max-1)
 constexpr int kBounceLast = 2;   // shade (throughput only), miss_kernel    (after the last extend)
+constexpr int kBounceMiddleRetire = 3; // kBounceMiddle of a WFPT_FLAG_RETIRE context: shade ends with the termination step, a retired hit is not traced
+// The termination step's inputs (include/wfpt.h "Path termination"): the wavefront b whose hits the shade step shades and the context's
+// wfpt_termination_params. Read by the WFPT_FLAG_RETIRE kernels alone.
+struct TermArgs {
+    uint32_t wavefront, roulette_start;
+    float q_min;
+};
 #ifndef WFPT_MISS_SEGS
 #define WFPT_MISS_SEGS 16
 #endif
@@ -317,6 +324,7 @@ struct BounceArgs {
     // ---- first launch of WFPT_LOOP_FUSED over a scene in LDS, default walk: the per-tile candidate lists (wfpt_tile_lists.h), one
     // 64-byte record per local tile; null = every wave walks the tree
     const uint4 *tile_lists;
+    TermArgs term; // kBounceMiddleRetire (appended: the offsets of everything above are those of the launches that do not read it)
 };
 
 // The builder of the per-tile candidate lists (tile_lists_kernel): one wave per local tile, lanes over the nodes
@@ -389,6 +397,7 @@ struct RefillArgs {
     uint32_t gx, gy, capacity, rng_mode, image_width;
     Tiling tile;
     SceneDev scene;
+    TermArgs term; // shade_rays_retire_kernel (appended, as in BounceArgs)
 };
 
 struct CompactArgs {
@@ -682,11 +691,14 @@ hipError_t launch_scan_binned(const ScanBinnedArgs &a, hipStream_t s);
 hipError_t launch_plan(const PlanArgs &a, hipStream_t s);
 hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s);
-hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s);
+hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s, bool retire = false);
 hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array
 hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
-hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s);
+// retire: the termination step's inputs (shade_retire_kernel), null = shade_kernel
+hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s, const TermArgs *retire = nullptr);
+// the termination step for n caller rows (wfpt_sample_termination): p.wavefront is the caller's b
+hipError_t launch_termination_sampler(const TermArgs &p, uint32_t frame, const float *in4, float *out8, uint32_t n, hipStream_t s);
 // connected: the `emitted` plane of a context that connects to its map (WFPT_FLAG_ENV_NEE): miss_env_nee_kernel, which leaves thr = +0
 // where the pixel's connected flag (emitted.w) is 1
 // weigh: miss_env_mis_kernel instead (WFPT_FLAG_ENV_MIS; needs `connected` and env's tables), which keeps thr * c there, times the balance

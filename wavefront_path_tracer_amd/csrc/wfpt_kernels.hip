@@ -1581,6 +1581,53 @@ __device__ __forceinline__ float3_ scatter(uint32_t rng, float3_ p, float3_ rdir
     return ext;
 }
 
+// The termination step of WFPT_FLAG_RETIRE contexts (include/wfpt.h "Path termination", steps 2 and 3) for one hit of wavefront `b`
+// whose shade formed t = thr * albedo: returns kTermDead / kTermRoulette (the hit is retired) or kTermSurvives, with t what the pixel's
+// throughput becomes. The draw's stream is the step's own, keyed by the pixel in both RNG modes (the connect pass's construction with
+// another multiplier). q, u: what the roulette compared (0 where nothing is drawn), for the sampler. Shared by every loop and the sampler.
+constexpr uint32_t kTermDead = 0u, kTermRoulette = 1u, kTermSurvives = 2u;
+__device__ __forceinline__ uint32_t terminate_path(const TermArgs &p, uint32_t b, uint32_t pixel_idx, uint32_t frame, float3_ &t, float &q_out,
+                                                   float &u_out) {
+    q_out = 0.0f;
+    u_out = 0.0f;
+    if (t.x == 0.0f && t.y == 0.0f && t.z == 0.0f) return kTermDead; // (-0 counts, a NaN channel does not)
+    if (p.roulette_start == 0xffffffffu || b < p.roulette_start) return kTermSurvives;
+    float m = t.x;
+    if (t.y > m) m = t.y;
+    if (t.z > m) m = t.z;
+    float q = m;
+    if (!(q >= p.q_min)) q = p.q_min; // (a NaN m too)
+    if (q >= 1.0f) return kTermSurvives; // nothing is drawn
+    uint32_t s = jenkins_hash(pixel_idx ^ jenkins_hash(frame));
+    s = jenkins_hash(s ^ (0x85EBCA6Bu * (b + 1u)));
+    const float u = rng_next_float(s);
+    q_out = q;
+    u_out = u;
+    if (u < q) {
+        t = {t.x / q, t.y / q, t.z / q};
+        return kTermSurvives;
+    }
+    t = {0.0f, 0.0f, 0.0f};
+    return kTermRoulette;
+}
+__device__ __forceinline__ bool retires(const TermArgs &p, uint32_t pixel_idx, uint32_t frame, float3_ &t) {
+    float q, u;
+    return terminate_path(p, p.wavefront, pixel_idx, frame, t, q, u) != kTermSurvives;
+}
+
+// The sampler form (wfpt_sample_termination): row i of in4 is (t'.rgb | the pixel index's bits), of out8 (q, u, verdict, 0, thr'.rgb, 0)
+__global__ __launch_bounds__(256) void termination_sampler_kernel(TermArgs p, uint32_t frame, const float *in4, float *out8, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *row = in4 + 4u * static_cast<size_t>(i);
+    float3_ t = {row[0], row[1], row[2]};
+    float q, u;
+    const uint32_t verdict = terminate_path(p, p.wavefront, __float_as_uint(row[3]), frame, t, q, u);
+    float *out = out8 + 8u * static_cast<size_t>(i);
+    out[0] = q; out[1] = u; out[2] = static_cast<float>(verdict); out[3] = 0.0f;
+    out[4] = t.x; out[5] = t.y; out[6] = t.z; out[7] = 0.0f;
+}
+
 // Walks the hit-queue segments: segment c holds chunk_hits[c] hits compacted at its front, and
 // chunk_hit_base[c] is the queue position of its first hit, so the logical hit index (the thread index
 // of the reference's shade dispatch) is base + rank. Whole waves beyond a segment's count skip, so lanes
@@ -1589,117 +1636,154 @@ __device__ __forceinline__ float3_ scatter(uint32_t rng, float3_ p, float3_ rdir
 // keeps the previous order (neighbouring pixels stay neighbours).
 // (capping the SGPR count with a min-waves launch bound, as extend does, was measured 2 % SLOWER here: the spills cost
 // more than the seventh and eighth wave per SIMD bring)
+// RETIRE (shade_retire_kernel, WFPT_FLAG_RETIRE contexts): the termination step decides before the scatter; a retired hit's extension ray
+// is inactive (pixel = WFPT_INACTIVE_PIXEL, its slot kept), which the HAS_INACTIVE extend variants neither hit nor miss with
+// A macro, for the reason given at WFPT_SCENE_LDS (as a forceinline function over the same text it changed shade_kernel's machine code): it
+// names the kernel's `a`; RETIRE is a literal and `term` is read only where it is true.
+#define WFPT_SHADE_BODY(RETIRE, term)                                                                                                                   \
+    const uint32_t sample = blockIdx.y;                                                                                                                 \
+    wfpt_frame_buffer fb = a.ctl->frame;                                                                                                                \
+    fb.frame += sample;                                                                                                                                 \
+    a.ctl += sample;                                                                                                                                    \
+    a.q = slice(a.q, sample * a.batch.ray_stride);                                                                                                      \
+    a.ext = slice(a.ext, sample * a.batch.ray_stride);                                                                                                  \
+    a.hq.base += sample * a.batch.queue_stride;                                                                                                         \
+    a.chunk_hits += sample * a.batch.chunk_stride;                                                                                                      \
+    a.chunk_hit_base += sample * a.batch.chunk_stride;                                                                                                  \
+    a.image += sample * a.batch.image_stride;                                                                                                           \
+    const uint32_t n_hits = umin(a.n_hits[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit); /* sh:66 */                                      \
+    const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;                                                                                     \
+    const uint32_t gx = a.gx ? a.gx : a.ctl->shade_gx;                                                                                                  \
+    /* split: this workgroup shades one material class, walking that class's per-segment lists (lanes stay */                                           \
+    /* packed and every lane takes the same branch of the material switch) */                                                                           \
+    const bool split = a.split != 0;                                                                                                                    \
+    const uint32_t mclass = a.material != 0xffffffffu ? a.material : blockIdx.z;                                                                        \
+    const uint16_t *mat_list = a.mat_list + mclass * a.mat_list_mstride + sample * a.batch.queue_stride;                                                \
+    const uint32_t *chunk_mat = a.chunk_mat + mclass * a.chunk_mat_mstride + sample * a.batch.chunk_stride;                                             \
+    if (a.count_out && !split && blockIdx.x == 0 && threadIdx.x == 0) a.ctl->counters[2] += n_hits; /* sh:155 */                                        \
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {                                                                           \
+        const uint32_t count = split ? chunk_mat[chunk] : a.chunk_hits[chunk];                                                                          \
+        const uint32_t base = a.chunk_hit_base[chunk];                                                                                                  \
+        if (base >= n_hits) break; /* bases ascend with the segment index */                                                                            \
+        if (a.rec_in) {                                                                                                                                 \
+            /* ---- streaming form: extend left (hit point | pixel), (direction | primitive) at the hit's slot; the next hit's record is */             \
+            /* loaded before this hit's dependent gathers (shade record, throughput) */                                                                 \
+            const float4 *rec = a.rec_in + 2u * (sample * static_cast<size_t>(a.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk);             \
+            uint32_t r0 = threadIdx.x, nr = 0;                                                                                                          \
+            float4 nra = make_float4(0, 0, 0, 0), nrb = nra;                                                                                            \
+            if (r0 < count) {                                                                                                                           \
+                nr = split ? mat_list[chunk * kChunk + r0] : r0;                                                                                        \
+                nra = rec[2u * nr]; nrb = rec[2u * nr + 1u];                                                                                            \
+            }                                                                                                                                           \
+            for (; r0 < count; r0 += kConsumerThreads) {                                                                                                \
+                const uint32_t r = nr;                                                                                                                  \
+                const float4 ra = nra, rb = nrb;                                                                                                        \
+                const uint32_t h = base + r; /* the reference's shade thread index */                                                                   \
+                if (h >= n_hits) break;                                                                                                                 \
+                if (r0 + kConsumerThreads < count) {                                                                                                    \
+                    nr = split ? mat_list[chunk * kChunk + r0 + kConsumerThreads] : r0 + kConsumerThreads;                                              \
+                    nra = rec[2u * nr]; nrb = rec[2u * nr + 1u];                                                                                        \
+                }                                                                                                                                       \
+                if (split && a.count_out) { /* per-material stage of the stage API: counters[2] += rays this stage emits */                             \
+                    const unsigned long long m = __ballot(true);                                                                                        \
+                    if (lane_id() == static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1))                                                     \
+                        atomicAdd(&a.ctl->counters[2], static_cast<uint32_t>(__popcll(m)));                                                             \
+                }                                                                                                                                       \
+                const uint32_t prim = __float_as_uint(rb.w), pixel_idx = __float_as_uint(ra.w);                                                         \
+                const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u], rec2 = a.scene.shade_rec[3u * prim + 2u];   \
+                float4 *px = pixel_of(a.image, local_pixel(pixel_idx, a.image_width, a.tile));                                                          \
+                const float4 thr = *px; /* sh:84-87: throughput *= albedo, for every material type (load now, store after the scatter math) */          \
+                if (RETIRE) {                                                                                                                           \
+                    float3_ tn = {thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z};                                                                      \
+                    const bool retired = retires(term, pixel_idx, fb.frame, tn);                                                                        \
+                    float3_ ext = {0.0f, 0.0f, 0.0f};                                                                                                   \
+                    if (!retired)                                                                                                                       \
+                        ext = scatter(shade_rng(a.rng_mode, h, gx, pixel_idx, fb), {ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, rec0, rec1,                  \
+                                      __float_as_uint(rec2.x), a.scene.prim_kind);                                                                      \
+                    a.ext.ox()[h] = ra.x; a.ext.oy()[h] = ra.y; a.ext.oz()[h] = ra.z;                                                                   \
+                    a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;                                                                \
+                    a.ext.pixel()[h] = retired ? WFPT_INACTIVE_PIXEL : pixel_idx;                                                                       \
+                    *px = make_float4(tn.x, tn.y, tn.z, thr.w);                                                                                         \
+                    continue;                                                                                                                           \
+                }                                                                                                                                       \
+                const uint32_t rng = shade_rng(a.rng_mode, h, gx, pixel_idx, fb);                                                                       \
+                const float3_ ext = scatter(rng, {ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, rec0, rec1, __float_as_uint(rec2.x), a.scene.prim_kind);       \
+                a.ext.ox()[h] = ra.x; a.ext.oy()[h] = ra.y; a.ext.oz()[h] = ra.z; /* sh:153-155 */                                                      \
+                a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;                                                                    \
+                a.ext.pixel()[h] = pixel_idx;                                                                                                           \
+                *px = make_float4(thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z, thr.w); /* albedo */                                                  \
+            }                                                                                                                                           \
+            continue;                                                                                                                                   \
+        }                                                                                                                                               \
+        /* Software-pipelined walk: the queue entry of the NEXT iteration is loaded before this iteration's */                                          \
+        /* dependent gathers, so each hit costs two dependent memory levels instead of three. */                                                        \
+        uint32_t r0 = threadIdx.x;                                                                                                                      \
+        uint32_t nr = 0, nprim = 0, nridx = 0;                                                                                                          \
+        float nt = 0.0f;                                                                                                                                \
+        if (r0 < count) {                                                                                                                               \
+            nr = split ? mat_list[chunk * kChunk + r0] : r0; /* rank within the segment's hit queue */                                                  \
+            nt = a.hq.t()[chunk * kChunk + nr];                                                                                                         \
+            nprim = a.hq.prim()[chunk * kChunk + nr];                                                                                                   \
+            nridx = a.hq.ridx()[chunk * kChunk + nr];                                                                                                   \
+        }                                                                                                                                               \
+        for (; r0 < count; r0 += kConsumerThreads) {                                                                                                    \
+            const uint32_t r = nr, prim = nprim, ridx = nridx;                                                                                          \
+            const float t = nt;                                                                                                                         \
+            const uint32_t h = base + r; /* the reference's shade thread index */                                                                       \
+            if (h >= n_hits) break;                                                                                                                     \
+            if (r0 + kConsumerThreads < count) {                                                                                                        \
+                nr = split ? mat_list[chunk * kChunk + r0 + kConsumerThreads] : r0 + kConsumerThreads;                                                  \
+                nt = a.hq.t()[chunk * kChunk + nr];                                                                                                     \
+                nprim = a.hq.prim()[chunk * kChunk + nr];                                                                                               \
+                nridx = a.hq.ridx()[chunk * kChunk + nr];                                                                                               \
+            }                                                                                                                                           \
+            if (split && a.count_out) { /* per-material stage of the stage API: counters[2] += rays this stage emits */                                 \
+                const unsigned long long m = __ballot(true);                                                                                            \
+                if (lane_id() == static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1))                                                         \
+                    atomicAdd(&a.ctl->counters[2], static_cast<uint32_t>(__popcll(m)));                                                                 \
+            }                                                                                                                                           \
+            /* one gather: primitive centre / normal, albedo, fuzz, refraction index, material type (== payload.mat_type, ex:199) */                    \
+            const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u],                                                 \
+                         rec2 = a.scene.shade_rec[3u * prim + 2u];                                                                                      \
+            const uint32_t mat_type = __float_as_uint(rec2.x);                                                                                          \
+            const float ox = a.q.ox()[ridx], oy = a.q.oy()[ridx], oz = a.q.oz()[ridx];                                                                  \
+            const float dx = a.q.dx()[ridx], dy = a.q.dy()[ridx], dz = a.q.dz()[ridx];                                                                  \
+            const uint32_t pixel_idx = a.q.pixel()[ridx];                                                                                               \
+            /* sh:84-87: throughput *= albedo, for every material type (load now, store after the scatter math) */                                      \
+            float4 *px = pixel_of(a.image, local_pixel(pixel_idx, a.image_width, a.tile));                                                              \
+            const float4 thr = *px;                                                                                                                     \
+            if (RETIRE) {                                                                                                                               \
+                float3_ tn = {thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z};                                                                          \
+                const bool retired = retires(term, pixel_idx, fb.frame, tn);                                                                            \
+                const float p_x = ox + t * dx, p_y = oy + t * dy, p_z = oz + t * dz;                                                                    \
+                float3_ ext = {0.0f, 0.0f, 0.0f};                                                                                                       \
+                if (!retired)                                                                                                                           \
+                    ext = scatter(shade_rng(a.rng_mode, h, gx, pixel_idx, fb), {p_x, p_y, p_z}, {dx, dy, dz}, rec0, rec1, mat_type, a.scene.prim_kind); \
+                a.ext.ox()[h] = p_x; a.ext.oy()[h] = p_y; a.ext.oz()[h] = p_z;                                                                          \
+                a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;                                                                    \
+                a.ext.pixel()[h] = retired ? WFPT_INACTIVE_PIXEL : pixel_idx;                                                                           \
+                *px = make_float4(tn.x, tn.y, tn.z, thr.w);                                                                                             \
+                continue;                                                                                                                               \
+            }                                                                                                                                           \
+                                                                                                                                                        \
+            const uint32_t rng = shade_rng(a.rng_mode, h, gx, pixel_idx, fb);                                                                           \
+            /* sh:91-93 */                                                                                                                              \
+            const float p_x = ox + t * dx, p_y = oy + t * dy, p_z = oz + t * dz;                                                                        \
+            const float3_ ext = scatter(rng, {p_x, p_y, p_z}, {dx, dy, dz}, rec0, rec1, mat_type, a.scene.prim_kind);                                   \
+            /* sh:153-155: direction is NOT normalised; invDirection is recomputed by extend */                                                         \
+            a.ext.ox()[h] = p_x; a.ext.oy()[h] = p_y; a.ext.oz()[h] = p_z;                                                                              \
+            a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;                                                                        \
+            a.ext.pixel()[h] = pixel_idx;                                                                                                               \
+            *px = make_float4(thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z, thr.w); /* albedo */                                                      \
+        }                                                                                                                                               \
+    }                                                                                                                                                   \
+    (void)0
 __global__ __launch_bounds__(kConsumerThreads) void shade_kernel(ShadeArgs a) {
-    const uint32_t sample = blockIdx.y;
-    wfpt_frame_buffer fb = a.ctl->frame;
-    fb.frame += sample;
-    a.ctl += sample;
-    a.q = slice(a.q, sample * a.batch.ray_stride);
-    a.ext = slice(a.ext, sample * a.batch.ray_stride);
-    a.hq.base += sample * a.batch.queue_stride;
-    a.chunk_hits += sample * a.batch.chunk_stride;
-    a.chunk_hit_base += sample * a.batch.chunk_stride;
-    a.image += sample * a.batch.image_stride;
-    const uint32_t n_hits = umin(a.n_hits[static_cast<size_t>(sample) * a.batch.ctl_stride], a.limit); // sh:66
-    const uint32_t n_chunks = (a.ctl->seg_n + kChunk - 1) / kChunk;
-    const uint32_t gx = a.gx ? a.gx : a.ctl->shade_gx;
-    // split: this workgroup shades one material class, walking that class's per-segment lists (lanes stay
-    // packed and every lane takes the same branch of the material switch)
-    const bool split = a.split != 0;
-    const uint32_t mclass = a.material != 0xffffffffu ? a.material : blockIdx.z;
-    const uint16_t *mat_list = a.mat_list + mclass * a.mat_list_mstride + sample * a.batch.queue_stride;
-    const uint32_t *chunk_mat = a.chunk_mat + mclass * a.chunk_mat_mstride + sample * a.batch.chunk_stride;
-    if (a.count_out && !split && blockIdx.x == 0 && threadIdx.x == 0) a.ctl->counters[2] += n_hits; // sh:155
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint32_t count = split ? chunk_mat[chunk] : a.chunk_hits[chunk];
-        const uint32_t base = a.chunk_hit_base[chunk];
-        if (base >= n_hits) break; // bases ascend with the segment index
-        if (a.rec_in) {
-            // ---- streaming form: extend left (hit point | pixel), (direction | primitive) at the hit's slot; the next hit's record is
-            // loaded before this hit's dependent gathers (shade record, throughput)
-            const float4 *rec = a.rec_in + 2u * (sample * static_cast<size_t>(a.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk);
-            uint32_t r0 = threadIdx.x, nr = 0;
-            float4 nra = make_float4(0, 0, 0, 0), nrb = nra;
-            if (r0 < count) {
-                nr = split ? mat_list[chunk * kChunk + r0] : r0;
-                nra = rec[2u * nr]; nrb = rec[2u * nr + 1u];
-            }
-            for (; r0 < count; r0 += kConsumerThreads) {
-                const uint32_t r = nr;
-                const float4 ra = nra, rb = nrb;
-                const uint32_t h = base + r; // the reference's shade thread index
-                if (h >= n_hits) break;
-                if (r0 + kConsumerThreads < count) {
-                    nr = split ? mat_list[chunk * kChunk + r0 + kConsumerThreads] : r0 + kConsumerThreads;
-                    nra = rec[2u * nr]; nrb = rec[2u * nr + 1u];
-                }
-                if (split && a.count_out) { // per-material stage of the stage API: counters[2] += rays this stage emits
-                    const unsigned long long m = __ballot(true);
-                    if (lane_id() == static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1))
-                        atomicAdd(&a.ctl->counters[2], static_cast<uint32_t>(__popcll(m)));
-                }
-                const uint32_t prim = __float_as_uint(rb.w), pixel_idx = __float_as_uint(ra.w);
-                const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u], rec2 = a.scene.shade_rec[3u * prim + 2u];
-                float4 *px = pixel_of(a.image, local_pixel(pixel_idx, a.image_width, a.tile));
-                const float4 thr = *px; // sh:84-87: throughput *= albedo, for every material type (load now, store after the scatter math)
-                const uint32_t rng = shade_rng(a.rng_mode, h, gx, pixel_idx, fb);
-                const float3_ ext = scatter(rng, {ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, rec0, rec1, __float_as_uint(rec2.x), a.scene.prim_kind);
-                a.ext.ox()[h] = ra.x; a.ext.oy()[h] = ra.y; a.ext.oz()[h] = ra.z; // sh:153-155
-                a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;
-                a.ext.pixel()[h] = pixel_idx;
-                *px = make_float4(thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z, thr.w); // albedo
-            }
-            continue;
-        }
-        // Software-pipelined walk: the queue entry of the NEXT iteration is loaded before this iteration's
-        // dependent gathers, so each hit costs two dependent memory levels instead of three.
-        uint32_t r0 = threadIdx.x;
-        uint32_t nr = 0, nprim = 0, nridx = 0;
-        float nt = 0.0f;
-        if (r0 < count) {
-            nr = split ? mat_list[chunk * kChunk + r0] : r0; // rank within the segment's hit queue
-            nt = a.hq.t()[chunk * kChunk + nr];
-            nprim = a.hq.prim()[chunk * kChunk + nr];
-            nridx = a.hq.ridx()[chunk * kChunk + nr];
-        }
-        for (; r0 < count; r0 += kConsumerThreads) {
-            const uint32_t r = nr, prim = nprim, ridx = nridx;
-            const float t = nt;
-            const uint32_t h = base + r; // the reference's shade thread index
-            if (h >= n_hits) break;
-            if (r0 + kConsumerThreads < count) {
-                nr = split ? mat_list[chunk * kChunk + r0 + kConsumerThreads] : r0 + kConsumerThreads;
-                nt = a.hq.t()[chunk * kChunk + nr];
-                nprim = a.hq.prim()[chunk * kChunk + nr];
-                nridx = a.hq.ridx()[chunk * kChunk + nr];
-            }
-            if (split && a.count_out) { // per-material stage of the stage API: counters[2] += rays this stage emits
-                const unsigned long long m = __ballot(true);
-                if (lane_id() == static_cast<uint32_t>(__ffsll(static_cast<long long>(m)) - 1))
-                    atomicAdd(&a.ctl->counters[2], static_cast<uint32_t>(__popcll(m)));
-            }
-            // one gather: primitive centre / normal, albedo, fuzz, refraction index, material type (== payload.mat_type, ex:199)
-            const float4 rec0 = a.scene.shade_rec[3u * prim], rec1 = a.scene.shade_rec[3u * prim + 1u],
-                         rec2 = a.scene.shade_rec[3u * prim + 2u];
-            const uint32_t mat_type = __float_as_uint(rec2.x);
-            const float ox = a.q.ox()[ridx], oy = a.q.oy()[ridx], oz = a.q.oz()[ridx];
-            const float dx = a.q.dx()[ridx], dy = a.q.dy()[ridx], dz = a.q.dz()[ridx];
-            const uint32_t pixel_idx = a.q.pixel()[ridx];
-            // sh:84-87: throughput *= albedo, for every material type (load now, store after the scatter math)
-            float4 *px = pixel_of(a.image, local_pixel(pixel_idx, a.image_width, a.tile));
-            const float4 thr = *px;
-
-            const uint32_t rng = shade_rng(a.rng_mode, h, gx, pixel_idx, fb);
-            // sh:91-93
-            const float p_x = ox + t * dx, p_y = oy + t * dy, p_z = oz + t * dz;
-            const float3_ ext = scatter(rng, {p_x, p_y, p_z}, {dx, dy, dz}, rec0, rec1, mat_type, a.scene.prim_kind);
-            // sh:153-155: direction is NOT normalised; invDirection is recomputed by extend
-            a.ext.ox()[h] = p_x; a.ext.oy()[h] = p_y; a.ext.oz()[h] = p_z;
-            a.ext.dx()[h] = ext.x; a.ext.dy()[h] = ext.y; a.ext.dz()[h] = ext.z;
-            a.ext.pixel()[h] = pixel_idx;
-            *px = make_float4(thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z, thr.w); // albedo
-        }
-    }
+    WFPT_SHADE_BODY(false, TermArgs{});
+}
+// (the step's inputs are an argument of their own: ShadeArgs, and with it shade_kernel's code, stays as it was)
+__global__ __launch_bounds__(kConsumerThreads) void shade_retire_kernel(ShadeArgs a, TermArgs term) {
+    WFPT_SHADE_BODY(true, term);
 }
 
 // ================================================================================================
@@ -2121,13 +2205,30 @@ struct HitSource {
 };
 // shade of one path record (ra = hit point | pixel, rb = incoming direction | -), primitive `prim`, as the reference's shade thread h.
 // WAVE_SMP: the wave's lanes belong to one sample (its counters are scalars); WAVE_H: they hold 64 consecutive, 64-aligned h (shade_rng).
-template <bool SCATTER, bool WAVE_SMP, bool WAVE_H>
+// RETIRE (WFPT_FLAG_RETIRE contexts, with SCATTER): the termination step `term` decides before the scatter and answers `retired`; a
+// retired hit has no extension ray.
+template <bool SCATTER, bool WAVE_SMP, bool WAVE_H, bool RETIRE = false>
 __device__ __forceinline__ void shade_record(const HitSource &s, float4 ra, float4 rb, uint32_t prim, uint32_t h, wfpt_frame_buffer fb, float &ox,
-                                             float &oy, float &oz, float &dx, float &dy, float &dz, uint32_t &pixel_idx) {
+                                             float &oy, float &oz, float &dx, float &dy, float &dz, uint32_t &pixel_idx,
+                                             const TermArgs *term = nullptr, bool *retired = nullptr) {
     pixel_idx = __float_as_uint(ra.w);
     const float4 rec1 = s.shade_rec[3u * prim + 1u];
     float4 *px = pixel_of(s.image, local_pixel(pixel_idx, s.image_width, s.tile));
     const float4 thr = *px;
+    if (RETIRE) {
+        float3_ tn = {thr.x * rec1.x, thr.y * rec1.y, thr.z * rec1.z};
+        *retired = retires(*term, pixel_idx, fb.frame, tn);
+        *px = make_float4(tn.x, tn.y, tn.z, thr.w);
+        if (!*retired) {
+            const float4 rec0 = s.shade_rec[3u * prim], rec2 = s.shade_rec[3u * prim + 2u];
+            const uint32_t gx = WAVE_SMP ? uniform(s.ctl->shade_gx) : s.ctl->shade_gx;
+            const uint32_t rng = shade_rng<WAVE_H>(s.rng_mode, h, gx, pixel_idx, fb);
+            const float3_ ext = scatter(rng, {ra.x, ra.y, ra.z}, {rb.x, rb.y, rb.z}, rec0, rec1, __float_as_uint(rec2.x), s.prim_kind);
+            ox = ra.x; oy = ra.y; oz = ra.z;
+            dx = ext.x; dy = ext.y; dz = ext.z;
+        }
+        return;
+    }
     if (SCATTER) {
         const float4 rec0 = s.shade_rec[3u * prim], rec2 = s.shade_rec[3u * prim + 2u];
         const uint32_t gx = WAVE_SMP ? uniform(s.ctl->shade_gx) : s.ctl->shade_gx;
@@ -2145,9 +2246,10 @@ __device__ __forceinline__ void shade_record(const HitSource &s, float4 ra, floa
 #else
 #define WFPT_SHADE_STAMPS_PARAM
 #endif
-template <bool SCATTER>
+template <bool SCATTER, bool RETIRE = false>
 __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32_t n_hits, wfpt_frame_buffer fb, float &ox, float &oy,
-                                          float &oz, float &dx, float &dy, float &dz, uint32_t &pixel_idx WFPT_SHADE_STAMPS_PARAM) {
+                                          float &oz, float &dx, float &dy, float &dz, uint32_t &pixel_idx WFPT_SHADE_STAMPS_PARAM,
+                                          const TermArgs *term = nullptr, bool *retired = nullptr) {
     const uint32_t run = uniform(h / kChunk), n_runs = (n_hits + kChunk - 1) / kChunk;
     uint32_t lo = s.in_first_seg[s.co + run];
     uint32_t hi = run + 1 < n_runs ? s.in_first_seg[s.co + run + 1] : (umin(s.ctl->seg_n, s.capacity) + kChunk - 1) / kChunk - 1u;
@@ -2164,7 +2266,7 @@ __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32
 #if WFPT_STAMPS
     if (shade_stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); shade_stamps[1] = stamp_now(); } // the record has arrived
 #endif
-    shade_record<SCATTER, true, true>(s, ra, rb, __float_as_uint(rb.w), h, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
+    shade_record<SCATTER, true, true, RETIRE>(s, ra, rb, __float_as_uint(rb.w), h, fb, ox, oy, oz, dx, dy, dz, pixel_idx, term, retired);
 }
 
 // ================================================================================================
@@ -2187,6 +2289,8 @@ __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32
 // MODE kBounceFirst : work item = 512 ray slots of generate_rays' numbering (8 tiles): generate -> trace.
 //      kBounceMiddle: hit items = 512 consecutive hits h of the previous wavefront: shade -> trace; then miss items.
 //      kBounceLast  : after the last extend: shade only multiplies the throughput (sh:84-87); miss items.
+//      kBounceMiddleRetire: kBounceMiddle of WFPT_FLAG_RETIRE contexts: shade ends with the termination step (terminate_path) and a
+//                     retired hit is not traced -- neither hit nor miss, as a lane outside the image in the first launch.
 // ================================================================================================
 // ---- the first launch's per-tile candidate lists (wfpt_tile_lists.h)
 // The closest hit of a primary ray among the leaves its tile's record names, in place of trace_ray_conservative: the record holds every
@@ -2322,6 +2426,7 @@ template <int MODE, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool E
 __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     extern __shared__ float4 lds[];
     constexpr bool TRACE = MODE != kBounceLast;
+    constexpr bool RETIRE = MODE == kBounceMiddleRetire;
     const bool stage_scene = TRACE && LDS_SCENE;
     WFPT_SCENE_LDS(stage_scene, s_misc);
     BounceLds L;
@@ -2452,9 +2557,19 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
                                 a.capacity, a.rng_mode, a.image_width, a.scene.prim_kind, a.tile};
 #if WFPT_STAMPS
             unsigned long long sst[2] = {t_item, t_item};
+            if (RETIRE) {
+                bool retired = false;
+                shade_hit<TRACE, RETIRE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, sst, &a.term, &retired);
+                live = !retired;
+            } else
             shade_hit<TRACE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, sst);
             if (MODE == kBounceMiddle) { acc_search += sst[0] - t_item; acc_record += sst[1] - sst[0]; }
 #else
+            if (RETIRE) { // (a retired hit is not traced: no hit, no miss)
+                bool retired = false;
+                shade_hit<TRACE, RETIRE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, &a.term, &retired);
+                live = !retired;
+            } else
             shade_hit<TRACE>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
 #endif
         }
@@ -3060,7 +3175,8 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
                 const float4 ra = a.dense_out[2u * slot], rb = a.dense_out[2u * slot + 1u];
                 pixel_idx = __float_as_uint(ra.w);
                 dx = rb.x; dy = rb.y; dz = rb.z;
-                if (MODE != kBounceFirst || __float_as_uint(rb.w) != kDenseInactive) { // (a lane outside the image: neither hit nor miss, the marker stays)
+                // (a lane outside the image, or kBounceMiddleRetire: a retired hit -- neither hit nor miss, the marker stays)
+                if (MODE == kBounceMiddle || __float_as_uint(rb.w) != kDenseInactive) {
                     r4 = make_ray4(ra.x, ra.y, ra.z, dx, dy, dz);
                     nearest = 1e30f; best = 0xffffffffu; cur = 0; st.reset(); budget = a.scene.n_nodes;
                     alive = true;
@@ -3157,7 +3273,10 @@ __global__ __launch_bounds__(kExtendThreads, WFPT_REFILL_MIN_WAVES) void refill_
 
 // shade (sh:56-156) of every hit of the previous wavefront at full waves, for the refill traversal: one workgroup = one run of
 // kChunk consecutive hits of one sample (blockIdx.y); the extension ray of hit h goes to slot h of the dense array.
-__global__ __launch_bounds__(kExtendThreads) void shade_rays_kernel(RefillArgs a) {
+// RETIRE (shade_rays_retire_kernel, WFPT_FLAG_RETIRE contexts): a retired hit leaves the inactive marker in its slot, which
+// refill_kernel<kBounceMiddleRetire> and compact_kernel honour.
+template <bool RETIRE>
+__device__ __forceinline__ void shade_rays_body(RefillArgs a) {
     const uint32_t smp = blockIdx.y;
     const uint32_t n = uniform(umin(a.ctl[smp].shade_n, a.capacity));
     if (blockIdx.x * kChunk >= n) return;
@@ -3170,10 +3289,28 @@ __global__ __launch_bounds__(kExtendThreads) void shade_rays_kernel(RefillArgs a
                         a.scene.prim_kind, a.tile};
     float ox, oy, oz, dx, dy, dz;
     uint32_t pixel_idx;
-    shade_hit<true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
     const size_t slot = smp * a.batch.queue_stride + h;
+    if (RETIRE) {
+        bool retired = false;
+        ox = oy = oz = dx = dy = dz = 0.0f;
+#if WFPT_STAMPS
+        shade_hit<true, true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, nullptr, &a.term, &retired);
+#else
+        shade_hit<true, true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx, &a.term, &retired);
+#endif
+        a.dense_out[2u * slot] = make_float4(ox, oy, oz, __uint_as_float(pixel_idx));
+        a.dense_out[2u * slot + 1u] = make_float4(dx, dy, dz, retired ? __uint_as_float(kDenseInactive) : 0.0f);
+        return;
+    }
+    shade_hit<true>(src, h, n, fb, ox, oy, oz, dx, dy, dz, pixel_idx);
     a.dense_out[2u * slot] = make_float4(ox, oy, oz, __uint_as_float(pixel_idx));
     a.dense_out[2u * slot + 1u] = make_float4(dx, dy, dz, 0.0f);
+}
+__global__ __launch_bounds__(kExtendThreads) void shade_rays_kernel(RefillArgs a) {
+    shade_rays_body<false>(a);
+}
+__global__ __launch_bounds__(kExtendThreads) void shade_rays_retire_kernel(RefillArgs a) {
+    shade_rays_body<true>(a);
 }
 
 // generate_rays (gr:42-91, true-size semantics) of the first wavefront at full waves, for the refill traversal: primary ray g of sample
@@ -4216,6 +4353,8 @@ BounceFn bounce_variant(const SceneDev &sc, bool exact, int mode, bool env = fal
     const bool lds = sc.lds_scene != 0;
     if (mode == kBounceLast) // no traversal: one variant
         return env ? bounce_kernel<kBounceLast, uint32_t, 0, false, false, true> : bounce_kernel<kBounceLast, uint32_t, 0, false, false>;
+    if (mode == kBounceMiddleRetire)
+        return env ? pick_variant<BounceK<kBounceMiddleRetire, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddleRetire, false>>(sc, exact, lds);
     if (env) return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, true>>(sc, exact, lds);
     return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, false>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, false>>(sc, exact, lds);
 }
@@ -4230,7 +4369,8 @@ hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks) {
     const uint32_t bytes = bounce_dynamic_lds(scene, kBounceMiddle);
     for (bool exact : {false, true}) { // both box tests, the first and the middle launches, both miss payloads
         const hipError_t e = allow_dynamic_lds(bytes, bounce_variant(scene, exact, kBounceFirst), bounce_variant(scene, exact, kBounceMiddle),
-                                               bounce_variant(scene, exact, kBounceFirst, true), bounce_variant(scene, exact, kBounceMiddle, true));
+                                               bounce_variant(scene, exact, kBounceFirst, true), bounce_variant(scene, exact, kBounceMiddle, true),
+                                               bounce_variant(scene, exact, kBounceMiddleRetire), bounce_variant(scene, exact, kBounceMiddleRetire, true));
         if (e != hipSuccess) return e;
     }
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
@@ -4298,14 +4438,15 @@ hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream
     using Fn = void (*)(RefillArgs);
     Fn fn;
     if (mode == kBounceFirst) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceFirst, 0> : refill_kernel<kBounceFirst, 1>;
+    else if (mode == kBounceMiddleRetire) fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceMiddleRetire, 0> : refill_kernel<kBounceMiddleRetire, 1>;
     else fn = a.scene.prim_kind == 0 ? refill_kernel<kBounceMiddle, 0> : refill_kernel<kBounceMiddle, 1>;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kExtendThreads), kRefillLdsFixed + 64u * a.scene.tile_n, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s) {
+hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s, bool retire) {
     if (n_chunks == 0) return hipSuccess;
-    hipLaunchKernelGGL(shade_rays_kernel, dim3(n_chunks, a.batch.n), dim3(kExtendThreads), 0, s, a);
+    hipLaunchKernelGGL(retire ? shade_rays_retire_kernel : shade_rays_kernel, dim3(n_chunks, a.batch.n), dim3(kExtendThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -4340,10 +4481,11 @@ hipError_t launch_scan(const ScanArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s) {
+hipError_t launch_shade(const ShadeArgs &a, uint32_t grid, hipStream_t s, const TermArgs *retire) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(shade_kernel, dim3(grid, a.batch.n, (a.split && a.material == 0xffffffffu) ? 3u : 1u), dim3(kConsumerThreads), 0,
-                       s, a);
+    const dim3 g(grid, a.batch.n, (a.split && a.material == 0xffffffffu) ? 3u : 1u);
+    if (retire) hipLaunchKernelGGL(shade_retire_kernel, g, dim3(kConsumerThreads), 0, s, a, *retire);
+    else hipLaunchKernelGGL(shade_kernel, g, dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -4396,6 +4538,12 @@ hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t gr
 hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_termination_sampler(const TermArgs &p, uint32_t frame, const float *in4, float *out8, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(termination_sampler_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, p, frame, in4, out8, n);
     return hipGetLastError();
 }
 

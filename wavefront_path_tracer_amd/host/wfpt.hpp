@@ -425,6 +425,27 @@ class PathTracer {
         check(wfpt_env_mis_miss_weight(ctx_, dirs3.data(), dirs3.size() / 3, out.data()));
         return out;
     }
+    // Path termination (WFPT_FLAG_RETIRE, include/wfpt.h "Path termination"): dead paths are retired, and from wavefront roulette_start on
+    // (0xffffffff: never) Russian roulette retires or re-weights the others with the survival probability's floor q_min, in (0, 1].
+    void set_termination(uint32_t roulette_start = 3, float q_min = 0.05f) {
+        wfpt_termination_params p;
+        wfpt_termination_params_default(&p);
+        p.roulette_start = roulette_start;
+        p.q_min = q_min;
+        check(wfpt_set_termination(ctx_, &p));
+    }
+    wfpt_termination_params termination() {
+        wfpt_termination_params p;
+        check(wfpt_get_termination(ctx_, &p));
+        return p;
+    }
+    // rows of t' = thr * albedo and their pixels -> rows of (q, u, verdict, 0, thr'.rgb, 0); verdict 0 = dead, 1 = retired by roulette, 2 = survives
+    std::vector<float> sample_termination(const std::vector<float> &thr3, const std::vector<uint32_t> &pixel_idx, uint32_t frame, uint32_t b) {
+        if (thr3.size() != 3 * pixel_idx.size()) throw Error(WFPT_ERR_INVALID_ARGUMENT, "sample_termination: thr3 must hold 3 floats per pixel index");
+        std::vector<float> out(pixel_idx.size() * 8);
+        check(wfpt_sample_termination(ctx_, thr3.data(), pixel_idx.data(), frame, b, pixel_idx.size(), out.data()));
+        return out;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
