@@ -3,7 +3,9 @@
  *
  *   gcc -std=c99 -O1 -Iinclude examples/wfpt_render.c -Lwavefront_path_tracer_amd -lwfpt \
  *       -Wl,-rpath,$PWD/wavefront_path_tracer_amd -lm -o wfpt_render
- *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]]
+ *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--adaptive]
+ * --adaptive: a WFPT_FLAG_ADAPTIVE context rendered with wfpt_render_adaptive (at most spp passes, an update every 8) at the default
+ * parameters; the image written is the mean (each pixel divided by its own sample count).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,8 +24,13 @@
 
 int main(int argc, char **argv) {
     wfpt_ctx *ctx = NULL;
+    int adaptive = 0;
+    if (argc > 2 && strcmp(argv[argc - 1], "--adaptive") == 0) {
+        adaptive = 1;
+        argc -= 1;
+    }
     if (argc < 2) {
-        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]]\n", argv[0]);
+        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--adaptive]\n", argv[0]);
         return 2;
     }
     const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[2]) : 400, height = argc > 3 ? (uint32_t)atoi(argv[3]) : 225;
@@ -54,13 +61,25 @@ int main(int argc, char **argv) {
     params.height = height;
     params.max_wavefronts = bounces; /* path_tracer.rs:323 uses 50 */
     params.miss_floor = 128;         /* path_tracer.rs:332 */
+    if (adaptive) params.flags |= WFPT_FLAG_ADAPTIVE;
     ctx = wfpt_create(&params, spheres, n, materials, n, nodes, n_nodes, &camera, inv_proj, view);
     if (!ctx) {
         fprintf(stderr, "wfpt_create: %s\n", wfpt_last_error(NULL));
         return 1;
     }
-    CHECK(wfpt_render(ctx, spp)); /* the loop of path_tracer.rs:291-368, resident on the device */
-    CHECK(wfpt_save_ppm(ctx, argv[1]));
+    uint32_t n_active = 0;
+    if (adaptive) CHECK(wfpt_render_adaptive(ctx, spp, 8, &n_active)); /* render 8 passes, make the next mask of the moments, and again */
+    else CHECK(wfpt_render(ctx, spp)); /* the loop of path_tracer.rs:291-368, resident on the device */
+    CHECK(wfpt_save_ppm(ctx, argv[1])); /* (a flagged context writes its mean) */
+    if (adaptive) {
+        uint32_t *counts = (uint32_t *)calloc((size_t)width * height, sizeof *counts);
+        unsigned long long samples = 0;
+        CHECK(wfpt_read_sample_counts(ctx, counts, (size_t)width * height));
+        for (size_t i = 0; i < (size_t)width * height; ++i) samples += counts[i];
+        printf("adaptive: %u passes, %.2f samples per pixel, %u pixels still active\n", wfpt_accumulated_samples(ctx),
+               (double)samples / ((double)width * height), n_active);
+        free(counts);
+    }
     uint64_t totals[4];
     CHECK(wfpt_read_totals(ctx, totals));
     printf("%ux%u, %u spp, %u bounces: %llu rays, %u BVH nodes%s -> %s\n", width, height, spp, bounces,

@@ -252,7 +252,11 @@ enum {
                                         see "Tile lists" below (A/B runs and tests; the results are the same bits either way) */,
     WFPT_FLAG_RETIRE = 1u << 20      /* path termination, see "Path termination" below: a path whose throughput is zero is retired at
                                         once, and from wavefront roulette_start on Russian roulette retires or re-weights the others.
-                                        Refused with WFPT_FLAG_BINNING; combines freely with every other flag. */
+                                        Refused with WFPT_FLAG_BINNING; combines freely with every other flag. */,
+    WFPT_FLAG_ADAPTIVE = 1u << 21    /* adaptive sampling, see "Adaptive sampling" below: a per-pixel active mask that generate_rays and
+                                        accumulate obey, per-pixel sample counts and luminance moments, and a device pass that turns the
+                                        moments into the next mask. Refused with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE and WFPT_FLAG_BINNING;
+                                        combines freely with every other flag. Without the flag nothing is allocated or launched. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -991,6 +995,84 @@ int wfpt_get_termination(wfpt_ctx *ctx, wfpt_termination_params *p);
  * pixels; frame, b: the sample's frame and the wavefront. out8: n rows of (q, u, verdict, 0, thr'.rgb, 0) -- verdict 0 = retired dead,
  * 1 = retired by roulette, 2 = survives; q and u are 0 where nothing is drawn. */
 int wfpt_sample_termination(wfpt_ctx *ctx, const float *thr3, const uint32_t *pixel_idx, uint32_t frame, uint32_t b, size_t n, float *out8);
+
+/* ------------------------------------------------------------------ Adaptive sampling (WFPT_FLAG_ADAPTIVE)
+ * Without this flag every sample goes to every pixel. A flagged context keeps, beside `accumulated`:
+ *   mask    one uint64_t per 8x8 tile of the context's slab, indexed by generate_rays' tile index (slot >> 6: tiles row-major, a sharded
+ *           context's own bands); bit ly * 8 + lx set = the pixel is active; bits of lanes outside the image are always clear. Allocated
+ *           once at wfpt_create: the captured graphs hold its address and stay valid while its contents change.
+ *   count   one uint32_t per pixel: the samples added to that pixel.
+ *   S1, S2  the luminance moments of "Denoiser" (the same planes, the same L_k), allocated here on their own.
+ * Whatever zeroes `accumulated` (wfpt_reset_accumulated, wfpt_reset_progress, a camera / size / scene change) zeroes count and the moments
+ * and sets the mask to every pixel inside the image. wfpt_accumulated_samples keeps its meaning: the sample passes rendered.
+ * wfpt_create* refuses the flag (WFPT_ERR_INVALID_ARGUMENT) together with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE -- the AOV sums, the denoiser's
+ * prepare and the temporal blend divide by one n for the whole image -- and WFPT_FLAG_BINNING; wfpt_render_chunked* refuses it. It
+ * combines freely with every other flag, both RNG modes, spheres and meshes, scenes in LDS and beyond, and tile_world > 1.
+ *
+ * Rendering (wfpt_render, wfpt_render_sample, both timed calls; every loop kind). In generate_rays a lane whose bit is clear does what a
+ * lane outside the image does: no primary ray is computed, its slot holds an inactive ray (the dense array's inactive marker in the
+ * refill loop), and the pixel's image slice is not reset. Slots are NOT compacted: the launch's slot count, n_in, the work items and the
+ * bounce table's rays_in are those of the unmasked frame, so the order of the hits -- shade's RNG key under WFPT_RNG_DISPATCH -- is that of
+ * the same queue with gaps, as for the padding rays of an odd-sized image. The masked pixels show up as rays_in - hits - misses in row 0.
+ * A wave (one tile) whose word is 0 computes no ray, reads no candidate list and walks nothing. Accumulate passes over a pixel whose bit
+ * is clear before it loads anything of it -- `accumulated` and the moments stay -- and an active pixel adds the batch's samples in
+ * ascending order as before, and count += the batch's samples. The mask is constant during a call: every batch size gives the same bits.
+ * The loop exit `misses < miss_floor` is untouched and counts the misses of the ACTIVE pixels: under a mask whose primary rays rarely miss
+ * (a region of ground, a few hard pixels left by the update) it ends a sample's loop earlier than it would for the whole frame -- before the
+ * first shade, where fewer than miss_floor primary rays miss. Create the context with miss_floor = 0 where that matters.
+ * The stage API (wfpt_kernel_run) ignores the mask and the counts, as it ignores the AOVs. wfpt_gather_accumulated* still gathers sums;
+ * a gather of counts is out of scope. wfpt_read_accumulated still returns sums; wfpt_read_variance works on a flagged context with the
+ * pixel's own n, and wfpt_save_ppm / _png / _pfm write the mean (wfpt_read_mean).
+ *
+ * wfpt_adaptive_update computes the next mask from the moments on the device, one wave per tile, one lane per pixel, on the context's
+ * stream outside the captured graphs; it blocks only when n_active is not NULL, which then receives the number of set bits. For pixel i
+ * with n = count[i], nf = (float)n, each line one IEEE f32 operation in this order:
+ *   mu  = S1 / nf
+ *   v   = max(0, S2 / nf - mu * mu) / nf           (wfpt_read_variance's formula with the pixel's own n; max(0, d) is d < 0 ? 0 : d)
+ *   tol = threshold * (mu + luminance_floor)
+ *   unconverged = !(n >= min_samples && v <= tol * tol)        (a NaN anywhere, and n == 0, leave the pixel unconverged)
+ * A lane outside the image is neither unconverged nor under the maximum. Then, on the tile's 64-bit words:
+ *   U = ballot(unconverged);  with dilate != 0, U is dilated by one pixel INSIDE THE TILE: H = U | ((U << 1) & ~col0) | ((U >> 1) & ~col7)
+ *   (col0 = 0x0101010101010101, col7 = 0x8080808080808080), D = H | (H << 8) | (H >> 8)
+ *   word = D & ballot(max_samples == 0 || n < max_samples) & ballot(inside the image)
+ * The dilation is clipped to the tile on purpose: the update of a band-sharded context then equals the unsharded one bit for bit (no
+ * rank needs another's moments), at the price of a converged pixel on a tile's edge not being kept alive by its neighbour across it.
+ * wfpt_set_adaptive refuses (WFPT_ERR_INVALID_ARGUMENT, the context as it was) a threshold or luminance_floor that is not finite and
+ * positive, min_samples < 2, a non-zero max_samples below min_samples and non-zero reserved words. A successful call neither resets the
+ * accumulation nor drops the graphs: the parameters are arguments of the update kernel only.
+ * Every call below returns WFPT_ERR_INVALID_ARGUMENT on a context without the flag. */
+typedef struct wfpt_adaptive_params {
+    uint32_t min_samples;    /* a pixel is never converged before it holds this many samples; >= 2 */
+    uint32_t max_samples;    /* a pixel that holds this many samples is switched off; 0 = no maximum */
+    float threshold;         /* relative tolerance of the mean's standard deviation; finite, > 0 */
+    float luminance_floor;   /* added to the mean before the tolerance is formed (dark pixels); finite, > 0 */
+    uint32_t dilate;         /* non-zero: the unconverged pixels keep their neighbours inside the tile alive */
+    uint32_t _reserved[3];   /* must be 0 */
+} wfpt_adaptive_params;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_adaptive_params) == 32 && offsetof(wfpt_adaptive_params, max_samples) == 4 &&
+                       offsetof(wfpt_adaptive_params, threshold) == 8 && offsetof(wfpt_adaptive_params, luminance_floor) == 12 &&
+                       offsetof(wfpt_adaptive_params, dilate) == 16 && offsetof(wfpt_adaptive_params, _reserved) == 20,
+                   "wfpt_adaptive_params: 32 bytes");
+/* min_samples 16, max_samples 0, threshold 0.05, luminance_floor 0.01, dilate 1; _reserved zeroed */
+void wfpt_adaptive_params_default(wfpt_adaptive_params *p);
+int wfpt_set_adaptive(wfpt_ctx *ctx, const wfpt_adaptive_params *p);
+int wfpt_get_adaptive(wfpt_ctx *ctx, wfpt_adaptive_params *p);
+/* A caller's mask (region rendering): one byte per pixel, row-major like wfpt_read_accumulated, non-zero = active; n_pixels must be
+ * wfpt_n_pixels. Bytes of a sharded slab's rows beyond the image are ignored. Blocking. wfpt_read_active_mask is the inverse (0 / 1). */
+int wfpt_set_active_mask(wfpt_ctx *ctx, const uint8_t *mask, size_t n_pixels);
+int wfpt_read_active_mask(wfpt_ctx *ctx, uint8_t *mask, size_t n_pixels);
+int wfpt_adaptive_update(wfpt_ctx *ctx, uint32_t *n_active);
+/* the per-pixel sample counts, n <= wfpt_n_pixels (blocking) */
+int wfpt_read_sample_counts(wfpt_ctx *ctx, uint32_t *out, size_t n);
+/* accumulated / (float)count, one IEEE f32 division per channel, 0 where the count is 0: 3 floats per pixel, stride 12 (blocking) */
+int wfpt_read_mean(wfpt_ctx *ctx, float *rgb, size_t n_floats);
+/* the same bits from a resolve kernel (mean_resolve_kernel) into a caller's device buffer of n_bytes (at most the whole image); ordered on
+ * the context's stream, returns when they are written */
+int wfpt_copy_mean_to_device(wfpt_ctx *ctx, void *device_ptr, size_t n_bytes);
+/* The convenience loop, a host loop over the two public calls and nothing more: wfpt_render(interval) then wfpt_adaptive_update, until
+ * no pixel is active or max_passes sample passes are done (the last wfpt_render takes what is left of them). interval >= 1. n_active
+ * (may be NULL) receives the set bits of the last update. */
+int wfpt_render_adaptive(wfpt_ctx *ctx, uint32_t max_passes, uint32_t interval, uint32_t *n_active);
 
 /* ------------------------------------------------------------------ read-back (blocking) */
 

@@ -50,6 +50,10 @@ FLAG_ENV_MIS = 1 << 18
 FLAG_NO_TILE_LISTS = 1 << 19  # the first fused launch walks the tree for every tile (include/wfpt.h "Tile lists")
 FLAG_RETIRE = 1 << 20  # dead paths are retired and Russian roulette ends or re-weights the others (include/wfpt.h "Path termination")
 NO_ROULETTE = 0xFFFFFFFF  # set_termination(roulette_start=NO_ROULETTE): dead paths alone are retired
+# a per-pixel active mask, sample counts and moments, and the device pass that makes the next mask (include/wfpt.h "Adaptive sampling");
+# refused with FLAG_AOV, FLAG_DENOISE and FLAG_BINNING
+FLAG_ADAPTIVE = 1 << 21
+ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
 TILE_LIST_CAP, TILE_NO_LIST = 16, 0xFFFFFFFF
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
 # wfpt_denoise_params_default: SVGF's iterations and sigmas, sigma_albedo chosen by tests/test_gpu_denoise.py's quality test
@@ -114,6 +118,11 @@ class _EnvironmentParams(C.Structure):
 
 class _TerminationParams(C.Structure):
     _fields_ = [("roulette_start", C.c_uint32), ("q_min", C.c_float), ("_reserved", C.c_uint32 * 6)]
+
+
+class _AdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("threshold", C.c_float), ("luminance_floor", C.c_float),
+                ("dilate", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
 
 
 class _TextureParams(C.Structure):
@@ -374,6 +383,16 @@ def lib():
         "wfpt_set_termination": (i32, [vp, C.POINTER(_TerminationParams)]),
         "wfpt_get_termination": (i32, [vp, C.POINTER(_TerminationParams)]),
         "wfpt_sample_termination": (i32, [vp, vp, vp, u32, u32, sz, vp]),
+        "wfpt_adaptive_params_default": (None, [C.POINTER(_AdaptiveParams)]),
+        "wfpt_set_adaptive": (i32, [vp, C.POINTER(_AdaptiveParams)]),
+        "wfpt_get_adaptive": (i32, [vp, C.POINTER(_AdaptiveParams)]),
+        "wfpt_set_active_mask": (i32, [vp, vp, sz]),
+        "wfpt_read_active_mask": (i32, [vp, vp, sz]),
+        "wfpt_adaptive_update": (i32, [vp, C.POINTER(u32)]),
+        "wfpt_read_sample_counts": (i32, [vp, vp, sz]),
+        "wfpt_read_mean": (i32, [vp, vp, sz]),
+        "wfpt_copy_mean_to_device": (i32, [vp, vp, sz]),
+        "wfpt_render_adaptive": (i32, [vp, u32, u32, C.POINTER(u32)]),
         "wfpt_tile_lists_host": (i32, [vp, u32, vp, vp, vp, u32, u32, u32, u32, vp, u32]),
         "wfpt_debug_nodes_ch": (i32, [vp, u32, vp, vp]),
         "wfpt_debug_read_tile_lists": (i32, [vp, vp, C.POINTER(u32)]),
@@ -1541,6 +1560,76 @@ class PathTracer:
         out = np.zeros((len(thr), 8), "<f4")
         self._check(lib().wfpt_sample_termination(self.handle, _p(thr), _p(pix), int(frame) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF, len(thr), _p(out)))
         return out
+
+    # ---- adaptive sampling (contexts created with FLAG_ADAPTIVE; include/wfpt.h "Adaptive sampling")
+    def set_adaptive(self, **params):
+        """The update's parameters, as ADAPTIVE_DEFAULTS (those not named keep their defaults). Neither resets the accumulation nor drops
+        the graphs."""
+        unknown = set(params) - set(ADAPTIVE_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown adaptive parameter(s) {sorted(unknown)}: one of {sorted(ADAPTIVE_DEFAULTS)}")
+        v = {**ADAPTIVE_DEFAULTS, **params}
+        p = _AdaptiveParams(int(v["min_samples"]), int(v["max_samples"]), float(v["threshold"]), float(v["luminance_floor"]), int(v["dilate"]))
+        self._check(lib().wfpt_set_adaptive(self.handle, C.byref(p)))
+
+    def adaptive(self):
+        """The context's update parameters as a dict like ADAPTIVE_DEFAULTS."""
+        p = _AdaptiveParams()
+        self._check(lib().wfpt_get_adaptive(self.handle, C.byref(p)))
+        return {"min_samples": int(p.min_samples), "max_samples": int(p.max_samples), "threshold": float(p.threshold),
+                "luminance_floor": float(p.luminance_floor), "dilate": int(p.dilate)}
+
+    def adaptive_update(self):
+        """Computes the next active mask from the moments on the device; returns the number of active pixels (blocking)."""
+        n = C.c_uint32(0)
+        self._check(lib().wfpt_adaptive_update(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def set_active_mask(self, mask):
+        """A caller's mask: one value per pixel of the context (any shape of n_pixels elements), non-zero = active."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8).reshape(-1)
+        self._check(lib().wfpt_set_active_mask(self.handle, _p(m), m.size))
+
+    def active_mask(self):
+        """(h, w) bool: the pixels the next render adds samples to. A sharded context holds its own bands."""
+        m = np.zeros(self.n_pixels, np.uint8)
+        self._check(lib().wfpt_read_active_mask(self.handle, _p(m), m.size))
+        return m.reshape(self.n_pixels // self.width, self.width).astype(bool)
+
+    def sample_counts(self):
+        """(h, w) uint32: the samples added to each pixel since the last reset."""
+        a = np.zeros((self.n_pixels // self.width, self.width), "<u4")
+        self._check(lib().wfpt_read_sample_counts(self.handle, _p(a), a.size))
+        return a
+
+    def mean(self):
+        """(n_pixels, 3) float32: accumulated / count per pixel, 0 where the count is 0."""
+        a = np.zeros((self.n_pixels, 3), "<f4")
+        self._check(lib().wfpt_read_mean(self.handle, _p(a), a.size))
+        return a
+
+    def mean_to_tensor(self, tensor):
+        """Writes mean() into a caller's contiguous float32 device tensor of n_pixels * 3 elements on the context's device, resolved by
+        the GPU (the same bits as mean()). Returns the tensor."""
+        n = self.n_pixels * 3
+        dt = str(getattr(tensor, "dtype", "")).replace("torch.", "")
+        if dt != "float32":
+            raise TypeError(f"mean_to_tensor: tensor dtype {dt or type(tensor).__name__} is not float32")
+        if tensor.numel() != n:
+            raise ValueError(f"mean_to_tensor: tensor has {tensor.numel()} elements, the image {n}")
+        if not tensor.is_contiguous():
+            raise ValueError("mean_to_tensor: tensor is not contiguous")
+        if getattr(tensor, "device", None) is None or tensor.device.type != "cuda" or tensor.device.index != self._params.device:
+            raise ValueError(f"mean_to_tensor: tensor must live on this context's device (cuda:{self._params.device})")
+        self._check(lib().wfpt_copy_mean_to_device(self.handle, C.c_void_p(tensor.data_ptr()), 4 * n))
+        return tensor
+
+    def render_adaptive(self, max_passes, interval):
+        """render(interval) and adaptive_update() in turn until no pixel is active or max_passes sample passes are done; returns the
+        number of pixels still active."""
+        n = C.c_uint32(0)
+        self._check(lib().wfpt_render_adaptive(self.handle, int(max_passes), int(interval), C.byref(n)))
+        return int(n.value)
 
     # ---- read-back
     def accumulated(self):

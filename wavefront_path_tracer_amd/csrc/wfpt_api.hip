@@ -263,6 +263,13 @@ struct wfpt_ctx {
     uint64_t env_total = 0;
     float env_share = 0.5f;
     wfpt_termination_params term{3u, 0.05f, {0, 0, 0, 0, 0, 0}}; // WFPT_FLAG_RETIRE: wfpt_set_termination
+    // WFPT_FLAG_ADAPTIVE (include/wfpt.h "Adaptive sampling"): the active mask, one word per 64 ray slots of the CAPACITY (as tile_lists:
+    // allocated once, the captured graphs hold its address while its contents change), the samples added per pixel, the update's total,
+    // and the update's parameters. `moments` above is allocated for the flag as well. All null without it.
+    DeviceBuffer<uint64_t> active_mask;
+    DeviceBuffer<uint32_t> sample_count;
+    DeviceBuffer<uint32_t> n_active;
+    wfpt_adaptive_params adaptive{16u, 0u, 0.05f, 0.01f, 1u, {0, 0, 0}};
     uint32_t frame_offset = 0;  // wfpt_set_frame_offset: added to the frame uniform the device-resident loop writes
     DeviceBuffer<Control> ctl;
     DeviceBuffer<CameraDev> camera;
@@ -425,6 +432,10 @@ GenerateArgs generate_args(wfpt_ctx *c, uint32_t gx, uint32_t gy, bool fused, ui
 bool retiring(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_RETIRE) != 0; }
 bool retires_at(const wfpt_ctx *c, uint32_t b) { return retiring(c) && b + 1u < c->p.max_wavefronts; }
 TermArgs term_args(const wfpt_ctx *c, uint32_t b) { return TermArgs{b, c->term.roulette_start, c->term.q_min}; }
+// a WFPT_FLAG_ADAPTIVE context (include/wfpt.h "Adaptive sampling"): the generate sites and accumulate obey the active mask
+bool adapting(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_ADAPTIVE) != 0; }
+const uint64_t *mask_of(const wfpt_ctx *c) { return adapting(c) ? c->active_mask.get() : nullptr; }
+MaskArgs mask_args(const wfpt_ctx *c) { return MaskArgs{c->active_mask.get(), c->sample_count.get(), c->width, c->tiles_x}; }
 ExtendArgs extend_args(wfpt_ctx *c, int qi, const uint32_t *n_in, uint32_t limit, uint32_t nb = 1, bool partition = true) {
     ExtendArgs a{};
     a.batch = batch_of(c, nb);
@@ -442,7 +453,7 @@ ExtendArgs extend_args(wfpt_ctx *c, int qi, const uint32_t *n_in, uint32_t limit
     a.ctl = c->ctl.get();
     a.n_in = n_in;
     a.limit = std::min(limit, c->capacity);
-    a.has_inactive = (c->has_inactive || retiring(c)) ? 1u : 0u; // (a retired hit's extension ray is inactive)
+    a.has_inactive = (c->has_inactive || retiring(c) || adapting(c)) ? 1u : 0u; // (a retired hit's extension ray is inactive, and so is a masked pixel's primary ray)
     a.scene = c->scene;
     return a;
 }
@@ -792,7 +803,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
     const hipStream_t st = c->stream.get();
     const bool split = (c->p.flags & WFPT_FLAG_SPLIT_SHADE) != 0;
     const EnvDev *env = env_of(c);
-    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate(generate_args(c, c->tiles_x, c->tiles_y_local, true, nb), st); }));
+    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate(generate_args(c, c->tiles_x, c->tiles_y_local, true, nb), st, mask_of(c)); }));
     for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
         const int qi = static_cast<int>(b & 1u);
         WFPT_HIP(c, timed(WFPT_STAGE_EXTEND, [&] {
@@ -826,7 +837,8 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
     WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] {
                  BounceArgs a = bounce_args(c, 1, 0, nb);
                  a.tile_lists = tile_lists_of(c);
-                 return launch_bounce(a, kBounceFirst, grid, st, env != nullptr);
+                 a.mask = mask_of(c);
+                 return launch_bounce(a, adapting(c) ? kBounceFirstMasked : kBounceFirst, grid, st, env != nullptr);
              }));
     for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
         const int par = static_cast<int>(b & 1u);
@@ -872,7 +884,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
     const hipStream_t st = c->stream.get();
     const uint32_t grid = c->cus * c->bounce_blocks_per_cu;
     const EnvDev *env = env_of(c);
-    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate_dense(refill_args(c, 1, nb), st); }));
+    WFPT_HIP(c, timed(WFPT_STAGE_GENERATE_RAYS, [&] { return launch_generate_dense(refill_args(c, 1, nb), st, mask_of(c)); }));
     WFPT_HIP(c, timed(WFPT_STAGE_BOUNCE_FIRST, [&] { return launch_refill(refill_args(c, 1, nb), kBounceFirst, grid, st); }));
     for (uint32_t b = 0; b < c->p.max_wavefronts; ++b) {
         const int par = static_cast<int>(b & 1u);
@@ -923,6 +935,9 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
 // the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way). second_plane(c) implies the plane:
 // apply_emission and the environment's distribution allocate `emitted` before either of its conditions can hold.
 hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
+    if (adapting(c)) // under the active mask, with the counts (the moments always)
+        return launch_accumulate_masked(accumulate_args(c, c->n_pixels, true, nb), second_plane(c) ? c->emitted.get() : nullptr, c->moments.get(),
+                                        c->pixel_capacity, mask_args(c), c->accumulate_grid, c->stream.get());
     return launch_accumulate(accumulate_args(c, c->n_pixels, true, nb), second_plane(c) ? c->emitted.get() : nullptr, c->moments.get(),
                              c->pixel_capacity, c->accumulate_grid, c->stream.get());
 }
@@ -962,13 +977,41 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     return WFPT_OK;
 }
 
+// The active mask of a WFPT_FLAG_ADAPTIVE context on the host: one word per tile of the viewport from one byte per pixel of the slab
+// (null: every pixel), bits of lanes outside the image clear; and back.
+std::vector<uint64_t> mask_words(const wfpt_ctx *c, const uint8_t *bytes) {
+    std::vector<uint64_t> words(static_cast<size_t>(c->tiles_x) * c->tiles_y_local, 0ull);
+    for (uint32_t i = 0; i < c->n_pixels; ++i) {
+        uint32_t bit;
+        const uint32_t tile = mask_tile_of(i, c->width, c->tiles_x, bit), r = i / c->width;
+        const uint32_t y = ((r >> 3) * c->tile.world + c->tile.rank) * 8u + (r & 7u); // the image row of slab row r
+        if (y < c->height && (!bytes || bytes[i])) words[tile] |= 1ull << bit;
+    }
+    return words;
+}
+std::vector<uint64_t> all_active_words(const wfpt_ctx *c) { return mask_words(c, nullptr); }
+// ... to the device, ordered on the stream behind the batches that still read the old one; the words behind the viewport's tiles (the
+// capacity's tail) are cleared. Blocks until the copy is done: `words` is the caller's.
+int upload_mask(wfpt_ctx *c, const std::vector<uint64_t> &words) {
+    if (words.size() > c->active_mask.size()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "active mask: the viewport exceeds the table");
+    WFPT_HIP(c, hipMemsetAsync(c->active_mask.get(), 0, sizeof(uint64_t) * c->active_mask.size(), c->stream.get()));
+    WFPT_HIP(c, hipMemcpyAsync(c->active_mask.get(), words.data(), sizeof(uint64_t) * words.size(), hipMemcpyHostToDevice, c->stream.get()));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    return WFPT_OK;
+}
+
 // Zeroes the sums the samples add to: `accumulated` (pt:248-250; its tail beyond 3 * n_pixels is padding nothing reads) and with it the AOV
-// sums and the luminance moments (include/wfpt.h "AOVs", "Denoiser"), and starts a new epoch of the temporal denoiser.
+// sums and the luminance moments (include/wfpt.h "AOVs", "Denoiser"), and starts a new epoch of the temporal denoiser. On a
+// WFPT_FLAG_ADAPTIVE context also the sample counts, and the active mask becomes every pixel inside the image.
 int clear_sums(wfpt_ctx *c) {
     WFPT_HIP(c, hipMemsetAsync(c->accumulated.get(), 0, sizeof(float) * c->acc_floats, c->stream.get()));
     c->epoch += 1;
     if (c->aov_sums.get()) WFPT_HIP(c, hipMemsetAsync(c->aov_sums.get(), 0, sizeof(float) * c->aov_sums.size(), c->stream.get()));
     if (c->moments.get()) WFPT_HIP(c, hipMemsetAsync(c->moments.get(), 0, sizeof(float) * c->moments.size(), c->stream.get()));
+    if (adapting(c)) { // the counts with the sums, and every pixel inside the image active again
+        WFPT_HIP(c, hipMemsetAsync(c->sample_count.get(), 0, sizeof(uint32_t) * c->sample_count.size(), c->stream.get()));
+        if (int r = upload_mask(c, all_active_words(c)); r != WFPT_OK) return r;
+    }
     return WFPT_OK;
 }
 
@@ -1513,6 +1556,11 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_RETIRE does not go with WFPT_FLAG_BINNING (the class-binned loop has no termination step)");
         return nullptr;
     }
+    if ((params->flags & WFPT_FLAG_ADAPTIVE) != 0 && (params->flags & (WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_BINNING)) != 0) {
+        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ADAPTIVE does not go with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE (their sums are "
+                                                 "resolved with one sample count for the whole image) or WFPT_FLAG_BINNING (the class-binned first launch has no masked form)");
+        return nullptr;
+    }
     if ((params->flags & WFPT_FLAG_NEE) != 0 && (params->flags & WFPT_FLAG_EMISSION) == 0) {
         fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
         return nullptr;
@@ -1690,7 +1738,19 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         }
     }
     if (c->p.flags & WFPT_FLAG_AOV) CREATE_HIP(c->aov_sums.alloc_zeroed(kAovPlanes * static_cast<size_t>(c->pixel_capacity), st));
-    if (c->p.flags & WFPT_FLAG_DENOISE) CREATE_HIP(c->moments.alloc_zeroed(kMomentPlanes * static_cast<size_t>(c->pixel_capacity), st));
+    if (c->p.flags & (WFPT_FLAG_DENOISE | WFPT_FLAG_ADAPTIVE)) CREATE_HIP(c->moments.alloc_zeroed(kMomentPlanes * static_cast<size_t>(c->pixel_capacity), st));
+    if (c->p.flags & WFPT_FLAG_ADAPTIVE) {
+        // One word per 64 ray slots of the CAPACITY, as the tile lists: a wave of the first launch reads the word of its slots' tile
+        // whether or not the viewport reaches it.
+        CREATE_HIP(c->active_mask.alloc_zeroed(c->capacity / 64u, st));
+        CREATE_HIP(c->sample_count.alloc_zeroed(c->pixel_capacity, st));
+        CREATE_HIP(c->n_active.alloc_zeroed(1, st));
+        if (upload_mask(c, all_active_words(c)) != WFPT_OK) {
+            g_last_error = c->err;
+            wfpt_destroy(c);
+            return nullptr;
+        }
+    }
     CREATE_HIP(c->ctl.alloc_zeroed(kMaxBatch, st));
     CREATE_HIP(c->camera.alloc(1));
     CREATE_HIP(c->d_stamps.alloc_zeroed(64, st));
@@ -1754,6 +1814,8 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
                                const wfpt_gpu_camera *camera, const float inv_proj[16], const float view[16], uint32_t n_samples,
                                uint32_t chunks, float *rgb) {
     if (!params || !rgb || chunks == 0) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_render_chunked: null or empty argument");
+    if (params->flags & WFPT_FLAG_ADAPTIVE)
+        return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_render_chunked: WFPT_FLAG_ADAPTIVE is refused (a chunk's context is destroyed with its mask and counts)");
     if (chunks > 1 && params->rng_mode != WFPT_RNG_PIXEL)
         return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT,
                     "wfpt_render_chunked: WFPT_RNG_DISPATCH keys shade's RNG on a ray's queue position, which depends on the cut; "
@@ -2233,7 +2295,7 @@ void wfpt_denoise_params_default(wfpt_denoise_params *p) {
 
 static int check_denoise(wfpt_ctx *c, const wfpt_denoise_params *p, const void *out, const char *who) {
     if (!c || !p || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
-    if (!c->moments.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_DENOISE");
+    if (!(c->p.flags & WFPT_FLAG_DENOISE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without WFPT_FLAG_DENOISE");
     if (c->tile.world > 1)
         return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": a band-sharded context holds only its own bands (the filter needs its neighbours')");
     auto sigma_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
@@ -2327,20 +2389,26 @@ int wfpt_denoise_to_device(wfpt_ctx *c, const wfpt_denoise_params *p, void *devi
 
 int wfpt_read_variance(wfpt_ctx *c, float *out, size_t n_elems) {
     if (!c || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: null argument");
-    if (!c->moments.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: the context was created without WFPT_FLAG_DENOISE");
+    if (!c->moments.get())
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: the context was created without WFPT_FLAG_DENOISE or WFPT_FLAG_ADAPTIVE");
     if (n_elems > c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_variance: n_elems exceeds the image");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
     const size_t plane = c->pixel_capacity;
     std::vector<float> m(kMomentPlanes * plane);
     WFPT_HIP(c, hipMemcpy(m.data(), c->moments.get(), sizeof(float) * m.size(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_elems; ++k) out[k] = variance_resolve(m[k], m[plane + k], c->accumulated_samples);
+    std::vector<uint32_t> count; // WFPT_FLAG_ADAPTIVE: the pixel's own n
+    if (adapting(c)) {
+        count.resize(n_elems);
+        WFPT_HIP(c, hipMemcpy(count.data(), c->sample_count.get(), sizeof(uint32_t) * n_elems, hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 0; k < n_elems; ++k) out[k] = variance_resolve(m[k], m[plane + k], adapting(c) ? count[k] : c->accumulated_samples);
     return WFPT_OK;
 }
 
 int wfpt_denoise_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *calls) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: null context");
-    if (!c->moments.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: the context was created without WFPT_FLAG_DENOISE");
+    if (!(c->p.flags & WFPT_FLAG_DENOISE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_denoise_timing_ms: the context was created without WFPT_FLAG_DENOISE");
     if (ms_last) *ms_last = c->dn_ms;
     if (calls) *calls = c->dn_calls;
     return WFPT_OK;
@@ -2476,7 +2544,7 @@ int wfpt_denoise_temporal_to_device(wfpt_ctx *c, const wfpt_temporal_params *p, 
 
 int wfpt_read_temporal(wfpt_ctx *c, int which, float *out, size_t n_elems) {
     if (!c || !out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: null argument");
-    if (!c->moments.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: the context was created without WFPT_FLAG_DENOISE");
+    if (!(c->p.flags & WFPT_FLAG_DENOISE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: the context was created without WFPT_FLAG_DENOISE");
     if (which < WFPT_TEMPORAL_COLOR || which > WFPT_TEMPORAL_MOTION) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: unknown output");
     if (!c->tp_read_ok) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_temporal: no temporal call since the history was dropped");
     const size_t ch = which == WFPT_TEMPORAL_COLOR || which == WFPT_TEMPORAL_MOTION ? 3u : which == WFPT_TEMPORAL_MOMENTS ? 2u : 1u;
@@ -2512,7 +2580,7 @@ int wfpt_reset_history(wfpt_ctx *c) {
 
 int wfpt_temporal_timing_ms(wfpt_ctx *c, float *ms_last, uint32_t *calls) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_temporal_timing_ms: null context");
-    if (!c->moments.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_temporal_timing_ms: the context was created without WFPT_FLAG_DENOISE");
+    if (!(c->p.flags & WFPT_FLAG_DENOISE)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_temporal_timing_ms: the context was created without WFPT_FLAG_DENOISE");
     if (ms_last) *ms_last = c->tp_ms;
     if (calls) *calls = c->tp_calls;
     return WFPT_OK;
@@ -2813,20 +2881,24 @@ int wfpt_read_gathered(wfpt_ctx *c, float *rgb, size_t n_floats) {
     return WFPT_OK;
 }
 
-static int read_frame(wfpt_ctx *c, std::vector<float> &acc, const char *who) {
+// The frame the savers write and the number of samples it sums: `accumulated` and the sample passes, or -- WFPT_FLAG_ADAPTIVE, where n
+// differs by pixel -- the mean (wfpt_read_mean) and 1.
+static int read_frame(wfpt_ctx *c, std::vector<float> &acc, uint32_t &n, const char *who) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
     if (c->tile.world > 1) return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": this context holds only its own pixel bands");
     if (c->accumulated_samples == 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": nothing accumulated yet");
     acc.resize(3 * static_cast<size_t>(c->n_pixels));
-    return wfpt_read_accumulated(c, acc.data(), acc.size());
+    n = (c->p.flags & WFPT_FLAG_ADAPTIVE) ? 1u : c->accumulated_samples;
+    return (c->p.flags & WFPT_FLAG_ADAPTIVE) ? wfpt_read_mean(c, acc.data(), acc.size()) : wfpt_read_accumulated(c, acc.data(), acc.size());
 }
 
 int wfpt_save_ppm(wfpt_ctx *c, const char *path) {
     std::vector<float> acc;
-    if (int r = read_frame(c, acc, "wfpt_save_ppm"); r != WFPT_OK) return r;
+    uint32_t n = 0;
+    if (int r = read_frame(c, acc, n, "wfpt_save_ppm"); r != WFPT_OK) return r;
     if (!path) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_save_ppm: null path");
     std::vector<uint8_t> rgb(acc.size());
-    wfpt_tonemap_rgb8(acc.data(), c->n_pixels, c->accumulated_samples, rgb.data());
+    wfpt_tonemap_rgb8(acc.data(), c->n_pixels, n, rgb.data());
     FILE *f = std::fopen(path, "wb");
     if (!f) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string("wfpt_save_ppm: cannot open ") + path);
     std::fprintf(f, "P6\n%u %u\n255\n", c->width, c->height);
@@ -2837,19 +2909,21 @@ int wfpt_save_ppm(wfpt_ctx *c, const char *path) {
 
 int wfpt_save_png(wfpt_ctx *c, const char *path) {
     std::vector<float> acc;
-    if (int r = read_frame(c, acc, "wfpt_save_png"); r != WFPT_OK) return r;
+    uint32_t n = 0;
+    if (int r = read_frame(c, acc, n, "wfpt_save_png"); r != WFPT_OK) return r;
     if (!path) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_save_png: null path");
     std::vector<uint8_t> rgb(acc.size());
-    wfpt_tonemap_rgb8(acc.data(), c->n_pixels, c->accumulated_samples, rgb.data());
+    wfpt_tonemap_rgb8(acc.data(), c->n_pixels, n, rgb.data());
     const int st = wfpt_write_png_rgb8(path, rgb.data(), c->width, c->height);
     return st == WFPT_OK ? WFPT_OK : fail(c, st, std::string("wfpt_save_png: cannot write ") + path);
 }
 
 int wfpt_save_pfm(wfpt_ctx *c, const char *path) {
     std::vector<float> acc;
-    if (int r = read_frame(c, acc, "wfpt_save_pfm"); r != WFPT_OK) return r;
+    uint32_t n = 0;
+    if (int r = read_frame(c, acc, n, "wfpt_save_pfm"); r != WFPT_OK) return r;
     if (!path) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_save_pfm: null path");
-    const float inv_n = 1.0f / static_cast<float>(c->accumulated_samples);
+    const float inv_n = 1.0f / static_cast<float>(n);
     for (float &v : acc) v = inv_n * v; // display_shader.wgsl:50: invN * color, before the sqrt
     FILE *f = std::fopen(path, "wb");
     if (!f) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string("wfpt_save_pfm: cannot open ") + path);
@@ -3457,6 +3531,147 @@ int wfpt_sample_termination(wfpt_ctx *c, const float *thr3, const uint32_t *pixe
     return probe(c, "wfpt_sample_termination", in4.data(), 4, out8, 8, n, true, [&](const float *d_in, float *d_out) {
         return launch_termination_sampler(term_args(c, b), frame, d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
     });
+}
+
+// ---------------------------------------------------------------- adaptive sampling (include/wfpt.h "Adaptive sampling")
+static int adaptive_check(const wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_ADAPTIVE, "WFPT_FLAG_ADAPTIVE"); }
+
+void wfpt_adaptive_params_default(wfpt_adaptive_params *p) {
+    if (p) *p = wfpt_adaptive_params{16u, 0u, 0.05f, 0.01f, 1u, {0, 0, 0}};
+}
+
+int wfpt_set_adaptive(wfpt_ctx *c, const wfpt_adaptive_params *p) {
+    if (int r = adaptive_check(c, "wfpt_set_adaptive"); r != WFPT_OK) return r;
+    if (!p) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_adaptive: null parameters");
+    auto positive = [](float v) { return std::isfinite(v) && v > 0.0f; };
+    if (!positive(p->threshold) || !positive(p->luminance_floor))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_adaptive: threshold and luminance_floor must be finite and positive");
+    if (p->min_samples < 2u) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_adaptive: min_samples must be at least 2 (a variance needs two samples)");
+    if (p->max_samples != 0u && p->max_samples < p->min_samples)
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_adaptive: max_samples must be 0 (no maximum) or at least min_samples");
+    for (uint32_t r : p->_reserved)
+        if (r != 0u) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_adaptive: _reserved must be 0");
+    c->adaptive = *p; // arguments of the update kernel alone: no graph holds them, the accumulation goes on
+    return WFPT_OK;
+}
+
+int wfpt_get_adaptive(wfpt_ctx *c, wfpt_adaptive_params *p) {
+    if (int r = adaptive_check(c, "wfpt_get_adaptive"); r != WFPT_OK) return r;
+    if (!p) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_adaptive: null parameters");
+    *p = c->adaptive;
+    return WFPT_OK;
+}
+
+int wfpt_set_active_mask(wfpt_ctx *c, const uint8_t *mask, size_t n_pixels) {
+    if (int r = adaptive_check(c, "wfpt_set_active_mask"); r != WFPT_OK) return r;
+    if (!mask) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_active_mask: null mask");
+    if (n_pixels != c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_active_mask: the mask must hold one byte per pixel of the context");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    return upload_mask(c, mask_words(c, mask));
+}
+
+// the mask's words of the viewport's tiles (blocking)
+static int read_mask_words(wfpt_ctx *c, std::vector<uint64_t> &words) {
+    words.resize(static_cast<size_t>(c->tiles_x) * c->tiles_y_local);
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    WFPT_HIP(c, hipMemcpy(words.data(), c->active_mask.get(), sizeof(uint64_t) * words.size(), hipMemcpyDeviceToHost));
+    return WFPT_OK;
+}
+
+int wfpt_read_active_mask(wfpt_ctx *c, uint8_t *mask, size_t n_pixels) {
+    if (int r = adaptive_check(c, "wfpt_read_active_mask"); r != WFPT_OK) return r;
+    if (!mask) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_active_mask: null mask");
+    if (n_pixels != c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_active_mask: the mask holds one byte per pixel of the context");
+    std::vector<uint64_t> words;
+    if (int r = read_mask_words(c, words); r != WFPT_OK) return r;
+    for (uint32_t i = 0; i < c->n_pixels; ++i) {
+        uint32_t bit;
+        const uint32_t tile = mask_tile_of(i, c->width, c->tiles_x, bit);
+        mask[i] = static_cast<uint8_t>((words[tile] >> bit) & 1ull);
+    }
+    return WFPT_OK;
+}
+
+int wfpt_adaptive_update(wfpt_ctx *c, uint32_t *n_active) {
+    if (int r = adaptive_check(c, "wfpt_adaptive_update"); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    AdaptiveArgs a{};
+    a.moments = c->moments.get();
+    a.plane = c->pixel_capacity;
+    a.count = c->sample_count.get();
+    a.mask = c->active_mask.get();
+    a.n_active = c->n_active.get();
+    a.gx = c->tiles_x;
+    a.gy = c->tiles_y_local;
+    a.width = c->width;
+    a.height = c->height;
+    a.tile = c->tile;
+    a.min_samples = c->adaptive.min_samples;
+    a.max_samples = c->adaptive.max_samples;
+    a.threshold = c->adaptive.threshold;
+    a.luminance_floor = c->adaptive.luminance_floor;
+    a.dilate = c->adaptive.dilate;
+    // on the stream, outside the captured graphs (which hold the mask's address): behind the batches that read the old mask
+    WFPT_HIP(c, hipMemsetAsync(c->n_active.get(), 0, sizeof(uint32_t), c->stream.get()));
+    WFPT_HIP(c, launch_adaptive_update(a, c->stream.get()));
+    if (n_active) {
+        WFPT_HIP(c, hipMemcpyAsync(n_active, c->n_active.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream.get()));
+        WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    }
+    return WFPT_OK;
+}
+
+int wfpt_read_sample_counts(wfpt_ctx *c, uint32_t *out, size_t n) {
+    if (int r = adaptive_check(c, "wfpt_read_sample_counts"); r != WFPT_OK) return r;
+    if (!out) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_sample_counts: null argument");
+    if (n > c->n_pixels) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_sample_counts: n exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    WFPT_HIP(c, hipMemcpy(out, c->sample_count.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return WFPT_OK;
+}
+
+int wfpt_read_mean(wfpt_ctx *c, float *rgb, size_t n_floats) {
+    if (int r = adaptive_check(c, "wfpt_read_mean"); r != WFPT_OK) return r;
+    if (!rgb) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_mean: null argument");
+    if (n_floats > 3 * static_cast<size_t>(c->n_pixels)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_mean: n_floats exceeds the image");
+    if (int r = wfpt_read_accumulated(c, rgb, n_floats); r != WFPT_OK) return r;
+    std::vector<uint32_t> count((n_floats + 2) / 3);
+    WFPT_HIP(c, hipMemcpy(count.data(), c->sample_count.get(), sizeof(uint32_t) * count.size(), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_floats; ++k) rgb[k] = mean_resolve(rgb[k], count[k / 3]);
+    return WFPT_OK;
+}
+
+int wfpt_copy_mean_to_device(wfpt_ctx *c, void *device_ptr, size_t n_bytes) {
+    if (int r = adaptive_check(c, "wfpt_copy_mean_to_device"); r != WFPT_OK) return r;
+    if (!device_ptr) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_copy_mean_to_device: null argument");
+    if (n_bytes > sizeof(float) * 3 * static_cast<size_t>(c->n_pixels))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_copy_mean_to_device: n_bytes exceeds the image");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, launch_mean_resolve(c->accumulated.get(), c->sample_count.get(), static_cast<float *>(device_ptr), n_bytes / sizeof(float), c->stream.get()));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    return WFPT_OK;
+}
+
+int wfpt_render_adaptive(wfpt_ctx *c, uint32_t max_passes, uint32_t interval, uint32_t *n_active) {
+    if (int r = adaptive_check(c, "wfpt_render_adaptive"); r != WFPT_OK) return r;
+    if (interval == 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_render_adaptive: interval must be at least 1");
+    uint32_t active = 0;
+    if (max_passes == 0) { // nothing to render: the mask as it is
+        std::vector<uint64_t> words;
+        if (int r = read_mask_words(c, words); r != WFPT_OK) return r;
+        for (uint64_t w : words) active += static_cast<uint32_t>(__builtin_popcountll(w));
+    }
+    for (uint32_t done = 0; done < max_passes;) {
+        const uint32_t n = std::min(interval, max_passes - done);
+        if (int r = wfpt_render(c, n); r != WFPT_OK) return r;
+        done += n;
+        if (int r = wfpt_adaptive_update(c, &active); r != WFPT_OK) return r;
+        if (active == 0) break;
+    }
+    if (n_active) *n_active = active;
+    return WFPT_OK;
 }
 
 int wfpt_selftest_math(int device, int op, const float *a, const float *b, float *out, size_t n) {

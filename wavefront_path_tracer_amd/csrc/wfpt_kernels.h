@@ -250,6 +250,7 @@ constexpr int kBounceFirst = 0;  // generate_rays -> extend                 (wav
 constexpr int kBounceMiddle = 1; // shade -> extend, miss_kernel            (wavefronts 1 .. max-1)
 constexpr int kBounceLast = 2;   // shade (throughput only), miss_kernel    (after the last extend)
 constexpr int kBounceMiddleRetire = 3; // kBounceMiddle of a WFPT_FLAG_RETIRE context: shade ends with the termination step, a retired hit is not traced
+constexpr int kBounceFirstMasked = 4;  // kBounceFirst of a WFPT_FLAG_ADAPTIVE context: a lane whose bit of its tile's mask word is clear generates no ray
 // The termination step's inputs (include/wfpt.h "Path termination"): the wavefront b whose hits the shade step shades and the context's
 // wfpt_termination_params. Read by the WFPT_FLAG_RETIRE kernels alone.
 struct TermArgs {
@@ -325,6 +326,7 @@ struct BounceArgs {
     // 64-byte record per local tile; null = every wave walks the tree
     const uint4 *tile_lists;
     TermArgs term; // kBounceMiddleRetire (appended: the offsets of everything above are those of the launches that do not read it)
+    const uint64_t *mask; // kBounceFirstMasked (appended likewise): one word per 8x8 tile of generate_rays' numbering, [capacity / 64]
 };
 
 // The builder of the per-tile candidate lists (tile_lists_kernel): one wave per local tile, lanes over the nodes
@@ -576,6 +578,50 @@ struct AccumulateArgs {
     uint32_t bookkeeping; // fused loop: fold the bounce table into totals, frame += 1
 };
 
+// ---- adaptive sampling (WFPT_FLAG_ADAPTIVE; include/wfpt.h "Adaptive sampling"). The active mask is one 64-bit word per 8x8 tile of the
+// context's slab, indexed by generate_rays' tile index (slot >> 6), bit ly * 8 + lx set = the pixel is rendered; `count` one u32 per pixel
+// of the slab, indexed like `accumulated`. What a kernel that walks PIXELS needs to find a pixel's bit:
+struct MaskArgs {
+    const uint64_t *mask;
+    uint32_t *count;
+    uint32_t width, tiles_x; // pixel i of the slab: x = i % width, row r = i / width; tile (r / 8) * tiles_x + x / 8, bit (r % 8) * 8 + x % 8
+};
+__host__ __device__ inline uint32_t mask_tile_of(uint32_t i, uint32_t width, uint32_t tiles_x, uint32_t &bit) {
+    const uint32_t r = i / width, x = i - r * width;
+    bit = (r & 7u) * 8u + (x & 7u);
+    return (r >> 3) * tiles_x + (x >> 3);
+}
+// wfpt_adaptive_update's criterion for one pixel (adaptive_update_kernel; compiled for the host as well, for the tests of the formula):
+// one IEEE f32 operation per step in the header's order. max(0, d) keeps a NaN d, so a NaN anywhere leaves the pixel unconverged.
+__host__ __device__ inline bool adaptive_unconverged(float s1, float s2, uint32_t n, uint32_t min_samples, float threshold, float luminance_floor) {
+    const float nf = static_cast<float>(n);
+    const float mu = s1 / nf;
+    const float d = s2 / nf - mu * mu;
+    const float v = (d < 0.0f ? 0.0f : d) / nf;
+    const float tol = threshold * (mu + luminance_floor);
+    return !(n >= min_samples && v <= tol * tol);
+}
+// one pixel of dilation inside the tile: horizontally, then vertically
+__host__ __device__ inline uint64_t dilate_tile(uint64_t u) {
+    const uint64_t h = u | ((u << 1) & ~0x0101010101010101ull) | ((u >> 1) & ~0x8080808080808080ull);
+    return h | (h << 8) | (h >> 8);
+}
+struct AdaptiveArgs {
+    const float *moments;     // kMomentPlanes planes of `plane`
+    Stride32 plane;
+    const uint32_t *count;
+    uint64_t *mask;           // written: one word per tile
+    uint32_t *n_active;       // += the set bits (zeroed by the caller)
+    uint32_t gx, gy;          // tiles of this context (gy counts this rank's bands)
+    uint32_t width, height;
+    Tiling tile;
+    uint32_t min_samples, max_samples;
+    float threshold, luminance_floor;
+    uint32_t dilate;
+};
+// The mean of a pixel's channel (wfpt_read_mean on the host, mean_resolve_kernel on the device): one IEEE f32 division, 0 where n == 0
+__host__ __device__ inline float mean_resolve(float sum, uint32_t n) { return n ? sum / static_cast<float>(n) : 0.0f; }
+
 // ---- first-hit AOVs (WFPT_FLAG_AOV; include/wfpt.h "AOVs"). The per-pixel sums are kAovPlanes planes of `plane` elements (the context's
 // pixel capacity) behind one base pointer, indexed by the pixel's slot in this context's slab. All zero = nothing accumulated (the reset state).
 // The id planes hold 0 until the first sample since the reset has run, then primitive / material_idx + 1 for a hit, kAovMissWord for a miss.
@@ -679,7 +725,9 @@ struct TemporalArgs {
     float4 *motion;          // (x', y', z', 0)
 };
 
-hipError_t launch_generate(const GenerateArgs &a, hipStream_t s);
+// mask (null = none; WFPT_FLAG_ADAPTIVE contexts, here and in launch_generate_dense): one word per tile, bit ly * 8 + lx clear = the
+// lane leaves an inactive ray, as a lane outside the image does, and does not reset its pixel's image slice
+hipError_t launch_generate(const GenerateArgs &a, hipStream_t s, const uint64_t *mask = nullptr);
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s, bool env_dirs = false); // env_dirs: also write the miss queue's dx, dz planes
 hipError_t launch_scan(const ScanArgs &a, hipStream_t s); // one workgroup per sample
 // env_dirs: the variant of WFPT_FLAG_ENVIRONMENT contexts with a map: misses carry direction.x and .z, no miss items (launch_miss with the
@@ -692,7 +740,7 @@ hipError_t launch_plan(const PlanArgs &a, hipStream_t s);
 hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks);
 hipError_t launch_refill(const RefillArgs &a, int mode, uint32_t grid, hipStream_t s);
 hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t s, bool retire = false);
-hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s); // the first wavefront's primary rays into the dense array
+hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s, const uint64_t *mask = nullptr); // the first wavefront's primary rays into the dense array
 hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s, bool env_dirs = false);
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks);
 // retire: the termination step's inputs (shade_retire_kernel), null = shade_kernel
@@ -726,6 +774,13 @@ hipError_t connect_prepare(const SceneDev &scene); // raises the connect kernels
 // none; WFPT_FLAG_DENOISE contexts): plus the luminance moments, two planes `plane` floats apart. One kernel of four, the same
 // `accumulated` bits from each.
 hipError_t launch_accumulate(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, uint32_t grid, hipStream_t s);
+// The accumulate launch of WFPT_FLAG_ADAPTIVE contexts (include/wfpt.h "Adaptive sampling"): the moments always, and only for the pixels
+// whose mask bit is set, whose count grows by the batch's samples. One kernel of two (emitted or not).
+hipError_t launch_accumulate_masked(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, const MaskArgs &m, uint32_t grid,
+                                    hipStream_t s);
+hipError_t launch_adaptive_update(const AdaptiveArgs &a, hipStream_t s);  // one wave per tile of the context
+// accumulated / count into out (stride 3), the first n_floats floats: wfpt_copy_mean_to_device
+hipError_t launch_mean_resolve(const float *accumulated, const uint32_t *count, float *out, size_t n_floats, hipStream_t s);
 hipError_t launch_fill(float *p, float v, size_t n, hipStream_t s);
 hipError_t launch_set_frame(Control *ctl, const wfpt_frame_buffer &f, hipStream_t s); // ctl->frame = f, ordered on the stream
 // frame band (j * world + rank) <- slab band j for the first n_valid floats of a slab: the root of the multi-GPU gather

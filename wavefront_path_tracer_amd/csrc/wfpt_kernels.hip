@@ -147,6 +147,13 @@ __device__ __forceinline__ TilePixel tile_pixel(uint32_t tile_index, uint32_t sl
     __VA_ARGS__;                                                                                                                       \
     *pixel_of(image, local_pixel(pixel_idx, (fb).width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f)
 
+// WFPT_FLAG_ADAPTIVE (include/wfpt.h "Adaptive sampling"): the mask word of a wave's tile, `tile_index` wave-uniform (one wave = one 8x8
+// tile in every generate_rays site): one load through the scalar path. The mask is constant while a batch runs.
+__device__ __forceinline__ uint64_t tile_mask_word(const uint64_t *mask, uint32_t tile_index) {
+    return reinterpret_cast<const __attribute__((address_space(4))) uint64_t *>(reinterpret_cast<uintptr_t>(mask))[tile_index];
+}
+__device__ __forceinline__ bool mask_bit(uint64_t word, uint32_t lane) { return ((word >> lane) & 1ull) != 0ull; }
+
 // The frame of a batch's first sample, the same for every lane: kept in scalar registers
 __device__ __forceinline__ wfpt_frame_buffer uniform_frame(const Control *ctl) {
     wfpt_frame_buffer fb = ctl->frame;
@@ -165,8 +172,11 @@ __device__ __forceinline__ float3_ sky(float dy) {
 // generate_rays (gr:42-91): one thread per queue slot, slot = tile*64 + local (8x8-tile order), so a
 // wave is one 8x8 pixel tile and the SoA stores are fully coalesced.
 // ================================================================================================
-__global__ __launch_bounds__(256) void generate_rays_kernel(GenerateArgs a) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+// MASKED (generate_rays_masked_kernel, WFPT_FLAG_ADAPTIVE contexts): a lane whose bit of its tile's word is clear does what a padding
+// lane does. block: blockDim.x, read by the __global__ kernel (as for accumulate_body).
+template <bool MASKED>
+__device__ __forceinline__ void generate_rays_body(GenerateArgs a, const uint64_t *mask, uint32_t block) {
+    const uint32_t idx = blockIdx.x * block + threadIdx.x;
     const uint32_t n_threads = a.gx * a.gy * 64u;
     if (idx >= n_threads || idx >= a.capacity) return;
     const uint32_t sample = blockIdx.y; // batch slice; renders frame (base frame + sample)
@@ -179,7 +189,9 @@ __global__ __launch_bounds__(256) void generate_rays_kernel(GenerateArgs a) {
     const uint32_t width = a.true_size ? fb.width : a.gx * 8u;   // gr:55-56
     const uint32_t height = a.true_size ? fb.height : a.gy * 8u;
 
-    if (a.true_size && (p.x >= width || p.y >= height)) { // padding lane of a partial tile
+    bool off = a.true_size && (p.x >= width || p.y >= height); // padding lane of a partial tile
+    if (MASKED) off = off || !mask_bit(tile_mask_word(mask, uniform(idx >> 6)), lane_id());
+    if (off) {
         a.q.ox()[idx] = 0.0f; a.q.oy()[idx] = 0.0f; a.q.oz()[idx] = 0.0f;
         a.q.dx()[idx] = 0.0f; a.q.dy()[idx] = 0.0f; a.q.dz()[idx] = 0.0f;
         a.q.pixel()[idx] = WFPT_INACTIVE_PIXEL;
@@ -195,6 +207,8 @@ __global__ __launch_bounds__(256) void generate_rays_kernel(GenerateArgs a) {
         *pixel_of(a.image, local_pixel(pixel_idx, width, a.tile)) = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     }
 }
+__global__ __launch_bounds__(256) void generate_rays_kernel(GenerateArgs a) { generate_rays_body<false>(a, nullptr, blockDim.x); }
+__global__ __launch_bounds__(256) void generate_rays_masked_kernel(GenerateArgs a, const uint64_t *mask) { generate_rays_body<true>(a, mask, blockDim.x); }
 
 // ================================================================================================
 // extend (ex:47-210)
@@ -2291,6 +2305,8 @@ __device__ __forceinline__ void shade_hit(const HitSource &s, uint32_t h, uint32
 //      kBounceLast  : after the last extend: shade only multiplies the throughput (sh:84-87); miss items.
 //      kBounceMiddleRetire: kBounceMiddle of WFPT_FLAG_RETIRE contexts: shade ends with the termination step (terminate_path) and a
 //                     retired hit is not traced -- neither hit nor miss, as a lane outside the image in the first launch.
+//      kBounceFirstMasked: kBounceFirst of WFPT_FLAG_ADAPTIVE contexts: a lane whose bit of its tile's mask word (BounceArgs::mask) is clear is
+//                     a lane outside the image -- no primary ray, no image reset, neither hit nor miss; its slot is kept.
 // ================================================================================================
 // ---- the first launch's per-tile candidate lists (wfpt_tile_lists.h)
 // The closest hit of a primary ray among the leaves its tile's record names, in place of trace_ray_conservative: the record holds every
@@ -2427,6 +2443,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     extern __shared__ float4 lds[];
     constexpr bool TRACE = MODE != kBounceLast;
     constexpr bool RETIRE = MODE == kBounceMiddleRetire;
+    constexpr bool MASKED = MODE == kBounceFirstMasked, FIRST = MODE == kBounceFirst || MASKED; // (the masked first launch is the first launch)
     const bool stage_scene = TRACE && LDS_SCENE;
     WFPT_SCENE_LDS(stage_scene, s_misc);
     BounceLds L;
@@ -2445,10 +2462,10 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     __syncthreads();
     if (threadIdx.x < a.batch.n) {
         const uint32_t smp = threadIdx.x;
-        const uint32_t n = MODE == kBounceFirst ? umin(n_slots, a.capacity) : umin(a.ctl[smp].shade_n, a.capacity);
+        const uint32_t n = FIRST ? umin(n_slots, a.capacity) : umin(a.ctl[smp].shade_n, a.capacity);
         const uint32_t items_h = (n + kChunk - 1) / kChunk;
         uint32_t segs = 0;
-        if (MODE != kBounceFirst && !ENV && a.ctl[smp].miss_n > 0) segs = (umin(a.ctl[smp].seg_n, a.capacity) + kChunk - 1) / kChunk;
+        if (!FIRST && !ENV && a.ctl[smp].miss_n > 0) segs = (umin(a.ctl[smp].seg_n, a.capacity) + kChunk - 1) / kChunk;
         const uint32_t items_m = (segs + kMissSegsPerItem - 1) / kMissSegsPerItem;
         L.items_h[smp] = static_cast<uint16_t>(items_h);
         L.items_m[smp] = static_cast<uint16_t>(items_m);
@@ -2459,17 +2476,17 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     const uint32_t n_hit_items = uniform(L.total[0]), n_items = uniform(L.total[1]);
     // a workgroup's tickets only grow, so the sample of an item is found by walking on from where the previous item was
     uint32_t smp_h = 0, first_h = 0, smp_m = 0, first_m = n_hit_items;
-    if (MODE == kBounceFirst && blockIdx.x == 0 && threadIdx.x < a.batch.n)
+    if (FIRST && blockIdx.x == 0 && threadIdx.x < a.batch.n)
         a.ctl[threadIdx.x].n_in = umin(n_slots, a.capacity); // pt:313-316: counter[2] = rays of the first wavefront (read by scan)
-    const TicketMap tickets(n_hit_items, n_items, MODE != kBounceFirst);
+    const TicketMap tickets(n_hit_items, n_items, !FIRST);
     // The first launch's items are known before it starts and cost nearly the same: a workgroup takes a share of them by its index alone
     // and draws tickets for the tail only (wfpt_first_schedule.h). There an item is its ticket (nothing is mixed), so `ticket` carries the
     // item through both ranges; every other launch has no static range.
-    constexpr bool STATIC = MODE == kBounceFirst && kFirstStaticNum > 0;
+    constexpr bool STATIC = FIRST && kFirstStaticNum > 0;
     const uint32_t n_static = STATIC ? uniform(first_n_static(n_items, gridDim.x, kFirstStaticNum, kFirstStaticDen)) : 0u;
     // Behind the static range -- in every other launch: from ticket 0 -- a draw buys CHUNK consecutive positions and the last positions go
     // out singly (wfpt_ticket_chunks.h): position p is item n_static + p here, ticket p there. CHUNK 1: a position is its draw.
-    constexpr uint32_t CHUNK = MODE == kBounceFirst ? kFirstChunk : kBounceChunk, TAIL_ROUNDS = MODE == kBounceFirst ? kFirstTailRounds : kBounceTailRounds;
+    constexpr uint32_t CHUNK = FIRST ? kFirstChunk : kBounceChunk, TAIL_ROUNDS = FIRST ? kFirstTailRounds : kBounceTailRounds;
     constexpr bool CHUNKED = CHUNK > 1;
     const uint32_t n_dynamic = n_items - n_static;
     const uint32_t chunk_end = CHUNKED ? uniform(chunk_body(n_dynamic, gridDim.x, CHUNK, TAIL_ROUNDS)) : 0u; // positions [0, chunk_end) go out in chunks
@@ -2505,7 +2522,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         const bool in_chunk = CHUNKED && !in_static && chunk_follows(ticket - n_static, chunk_end, CHUNK); // (uniform) or this one + 1:
         const bool next_static = in_static || in_chunk;                                                    // either way it follows from this one, no ticket
 #if WFPT_STAMPS
-        if (MODE == kBounceFirst && !next_static && wave == 0) { // (the wait is the one the store to L.next makes anyway, placed between two stamps)
+        if (FIRST && !next_static && wave == 0) { // (the wait is the one the store to L.next makes anyway, placed between two stamps)
             WFPT_STAMP(t_draw);
             uint32_t drawn = 0;
             if (threadIdx.x == 0) drawn = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
@@ -2514,14 +2531,14 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             if (threadIdx.x == 0) L.next[buf] = drawn;
             acc_ticket += t_drawn - t_draw;
             acc_drawn += 1u;
-        } else if (MODE != kBounceFirst)
+        } else if (!FIRST)
 #endif
         if (!next_static && threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
         if (!ENV && item >= n_hit_items) {
             while (item >= first_m + uniform(L.items_m[smp_m])) first_m += uniform(L.items_m[smp_m++]);
             WFPT_MISS_ITEM(smp_m, (item - first_m) * kMissSegsPerItem, (uniform(umin(a.ctl[smp_m].seg_n, a.capacity)) + kChunk - 1) / kChunk);
             __syncthreads(); // L.next[buf] is visible
-            if (MODE == kBounceFirst) { // (the first launch has no miss items: its arm stays the parent's instructions)
+            if (FIRST) { // (the first launch has no miss items: its arm stays the parent's instructions)
                 ticket = uniform(L.next[buf]);
                 item = tickets.item_of(ticket);
             } else {
@@ -2534,7 +2551,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         while (item >= first_h + uniform(L.items_h[smp_h])) first_h += uniform(L.items_h[smp_h++]); // block-uniform
         const uint32_t smp = smp_h;
         const uint32_t seg_out = item - first_h;
-        const uint32_t n = MODE == kBounceFirst ? umin(n_slots, a.capacity) : uniform(umin(a.ctl[smp].shade_n, a.capacity));
+        const uint32_t n = FIRST ? umin(n_slots, a.capacity) : uniform(umin(a.ctl[smp].shade_n, a.capacity));
         const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
         float *image = a.image + smp * a.batch.image_stride;
         wfpt_frame_buffer fb = fb0;
@@ -2544,10 +2561,13 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         bool live = h < n;
         float ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0;
         uint32_t pixel_idx = 0;
-        if (MODE == kBounceFirst) {
+        // the masked first launch: this wave's tile word, once per item (0: no ray is generated, no list read, nothing walked)
+        const uint64_t tile_word = MASKED ? tile_mask_word(a.mask, uniform(h >> 6)) : ~0ull;
+        if (FIRST) {
             // ---------------- generate_rays (gr:42-91), true-size semantics: lanes outside the image emit nothing
             const TilePixel p = tile_pixel(uniform(h >> 6), h, a.gx, a.tile); // one wave = one 8x8 tile of generate_rays
             live = live && p.x < fb.width && p.y < fb.height;
+            if (MASKED) live = live && mask_bit(tile_word, lane); // a clear bit: what a lane outside the image does
             if (live) {
                 WFPT_START_PATH(pr, p, fb, image, ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz);
             }
@@ -2587,11 +2607,11 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         float t = 0.0f;
         uint32_t prim = 0;
         bool hit = false;
-        if (MODE == kBounceFirst && LDS_SCENE && !EXACT) {
+        if (FIRST && LDS_SCENE && !EXACT) {
             // this wave's tile and its candidate list (wfpt_tile_lists.h): word 0 through the scalar path; no table, or no list: the walk
             const uint4 *record = nullptr;
             uint32_t w0 = kTileNoList;
-            if (a.tile_lists) {
+            if (a.tile_lists && (!MASKED || tile_word != 0ull)) {
                 record = a.tile_lists + (kTileListCap / 4u) * uniform(h >> 6); // (64 bytes: four uint4; in bounds for every slot below the capacity)
                 w0 = uniform(*reinterpret_cast<const uint32_t *>(record));
             }
@@ -2638,7 +2658,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             a.out_miss[co + seg_out] = miss_total;
         }
 #if WFPT_STAMPS
-        if (MODE == kBounceFirst) { // per wave, summed over its items: ray generated | list or walk | barrier | compaction, stores issued (not waited for)
+        if (FIRST) { // per wave, summed over its items: ray generated | list or walk | barrier | compaction, stores issued (not waited for)
             WFPT_STAMP(t_done);
             acc_cyc[0] += t_trace - t_item;
             acc_cyc[1] += t_traced - t_trace;
@@ -2670,7 +2690,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     }
 #undef WFPT_NEXT_TICKET
 #if WFPT_STAMPS
-    if (MODE == kBounceFirst && a.stamps && lane == 0) { // counters 48..63: wfpt_debug_read_stamps_ex(which = 3)
+    if (FIRST && a.stamps && lane == 0) { // counters 48..63: wfpt_debug_read_stamps_ex(which = 3)
         for (int k = 0; k < 4; ++k) atomicAdd(&a.stamps[48 + k], acc_cyc[k]);
         atomicAdd(&a.stamps[48 + 4], static_cast<unsigned long long>(acc_cnt[0]));
         atomicAdd(&a.stamps[48 + 5], static_cast<unsigned long long>(acc_cnt[1]));
@@ -3316,24 +3336,31 @@ __global__ __launch_bounds__(kExtendThreads) void shade_rays_retire_kernel(Refil
 // generate_rays (gr:42-91, true-size semantics) of the first wavefront at full waves, for the refill traversal: primary ray g of sample
 // blockIdx.y goes to slot g of the dense array, (o | pixel), (d | 0); a lane outside the image leaves the inactive marker. Generating at
 // refill time ran ~250 instructions for the 16-24 idle lanes of a wave and kept the first launch's kernel 12 vector registers over budget.
-__global__ __launch_bounds__(256) void generate_dense_kernel(RefillArgs a) {
-    const uint32_t smp = blockIdx.y;
-    const uint32_t n = umin(a.gx * a.gy * 64u, a.capacity);
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    wfpt_frame_buffer fb = uniform_frame(a.ctl);
-    fb.frame += smp;
-    const TilePixel p = tile_pixel(g >> 6, g, a.gx, a.tile); // one wave = one 8x8 tile of generate_rays
-    const size_t slot = smp * a.batch.queue_stride + g;
-    if (p.x < fb.width && p.y < fb.height) {
-        uint32_t pixel_idx;
-        WFPT_START_PATH(pr, p, fb, a.image + smp * a.batch.image_stride,
-                        a.dense_out[2u * slot] = make_float4(pr.ox, pr.oy, pr.oz, __uint_as_float(pixel_idx));
-                        a.dense_out[2u * slot + 1u] = make_float4(pr.dx, pr.dy, pr.dz, 0.0f));
-    } else {
-        a.dense_out[2u * slot + 1u] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kDenseInactive));
+// MASKED (generate_dense_masked_kernel, WFPT_FLAG_ADAPTIVE contexts): a lane whose bit of its tile's word MASK_WORDS[g >> 6] is clear leaves
+// the marker too. A macro, for the reason given at WFPT_SCENE_LDS: the unflagged kernel keeps its instructions in their order (as a
+// function that is handed blockDim.x, its load of the block size moved).
+#define WFPT_GENERATE_DENSE(MASKED, MASK_WORDS)                                                                                        \
+    const uint32_t smp = blockIdx.y;                                                                                                   \
+    const uint32_t n = umin(a.gx * a.gy * 64u, a.capacity);                                                                            \
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;                                                                          \
+    if (g >= n) return;                                                                                                                \
+    wfpt_frame_buffer fb = uniform_frame(a.ctl);                                                                                       \
+    fb.frame += smp;                                                                                                                   \
+    const TilePixel p = tile_pixel(g >> 6, g, a.gx, a.tile); /* one wave = one 8x8 tile of generate_rays */                            \
+    const size_t slot = smp * a.batch.queue_stride + g;                                                                                \
+    bool on = p.x < fb.width && p.y < fb.height;                                                                                       \
+    if (MASKED) on = on && mask_bit(tile_mask_word(MASK_WORDS, uniform(g >> 6)), lane_id());                                           \
+    if (on) {                                                                                                                          \
+        uint32_t pixel_idx;                                                                                                            \
+        WFPT_START_PATH(pr, p, fb, a.image + smp * a.batch.image_stride,                                                               \
+                        a.dense_out[2u * slot] = make_float4(pr.ox, pr.oy, pr.oz, __uint_as_float(pixel_idx));                         \
+                        a.dense_out[2u * slot + 1u] = make_float4(pr.dx, pr.dy, pr.dz, 0.0f));                                         \
+    } else {                                                                                                                           \
+        a.dense_out[2u * slot + 1u] = make_float4(0.f, 0.f, 0.f, __uint_as_float(kDenseInactive));                                     \
     }
-}
+__global__ __launch_bounds__(256) void generate_dense_kernel(RefillArgs a) { WFPT_GENERATE_DENSE(false, static_cast<const uint64_t *>(nullptr)) }
+__global__ __launch_bounds__(256) void generate_dense_masked_kernel(RefillArgs a, const uint64_t *mask) { WFPT_GENERATE_DENSE(true, mask) }
+#undef WFPT_GENERATE_DENSE
 
 // dense per-ray results -> the segment-compacted path-record and miss queues of the fused loop, in ray order
 // ENV: the miss queue also gets direction.x and .z
@@ -3436,13 +3463,21 @@ __device__ __forceinline__ void accumulate_bookkeeping(const AccumulateArgs &a, 
 // block: blockDim.x, read by the __global__ kernel and handed down, here and to accumulate_bookkeeping. Keep it so: read in a device
 // function the block size is not folded with the kernel's uniform-workgroup attribute (a 16-bit load chosen by the workgroup's index
 // instead), which cost accumulate_moments_kernel two VGPRs over its bound.
-template <bool EMIT, bool MOMENTS, uint32_t TRIP, uint32_t TRIP2>
-__device__ __forceinline__ void accumulate_body(const AccumulateArgs &a, const float *emitted, float *moments, Stride32 plane, uint32_t block) {
+// MASKED (WFPT_FLAG_ADAPTIVE contexts; include/wfpt.h "Adaptive sampling"): a pixel whose bit of the active mask is clear is passed over
+// before any load of its slices -- its sums stay as they are -- and an active pixel's count grows by the batch's samples.
+template <bool EMIT, bool MOMENTS, uint32_t TRIP, uint32_t TRIP2, bool MASKED = false>
+__device__ __forceinline__ void accumulate_body(const AccumulateArgs &a, const float *emitted, float *moments, Stride32 plane, uint32_t block,
+                                                const MaskArgs *m = nullptr) {
     const size_t stride4 = a.batch.image_stride / 4u; // a slice is a whole number of float4 pixels
     const float4 *image4 = reinterpret_cast<const float4 *>(a.image);
     const float4 *emit4 = reinterpret_cast<const float4 *>(emitted);
     float *s2p = MOMENTS ? moments + static_cast<size_t>(plane) : nullptr;
     for (uint32_t i = blockIdx.x * block + threadIdx.x; i < a.n_pixels; i += gridDim.x * block) {
+        if (MASKED) {
+            uint32_t bit;
+            const uint32_t tile = mask_tile_of(i, m->width, m->tiles_x, bit);
+            if (!mask_bit(m->mask[tile], bit)) continue;
+        }
         float r = a.accumulated[3u * i], g = a.accumulated[3u * i + 1u], b = a.accumulated[3u * i + 2u];
         float s1 = 0.0f, s2 = 0.0f;
         if (MOMENTS) { s1 = moments[i]; s2 = s2p[i]; }
@@ -3475,6 +3510,7 @@ __device__ __forceinline__ void accumulate_body(const AccumulateArgs &a, const f
         for (; smp < a.batch.n; ++smp) add(im0[smp * stride4], EMIT ? em0[smp * stride4] : float4{});
         a.accumulated[3u * i] = r; a.accumulated[3u * i + 1u] = g; a.accumulated[3u * i + 2u] = b;
         if (MOMENTS) { moments[i] = s1; s2p[i] = s2; }
+        if (MASKED) m->count[i] += a.batch.n;
     }
     if (blockIdx.x == 0 && a.bookkeeping) accumulate_bookkeeping(a, block);
 }
@@ -3949,6 +3985,45 @@ __global__ __launch_bounds__(256) void accumulate_emission_kernel(AccumulateArgs
 __global__ __launch_bounds__(256) void accumulate_emission_moments_kernel(AccumulateArgs a, const float *emitted, float *moments, Stride32 plane) {
     accumulate_body<true, true, 4u, 1u>(a, emitted, moments, plane, blockDim.x);
 }
+// ... and the two of WFPT_FLAG_ADAPTIVE contexts (accumulate_body's MASKED): the moments always, under the active mask, with the counts
+__global__ __launch_bounds__(256) void accumulate_masked_kernel(AccumulateArgs a, float *moments, Stride32 plane, MaskArgs m) {
+    accumulate_body<false, true, 4u, 1u, true>(a, nullptr, moments, plane, blockDim.x, &m);
+}
+__global__ __launch_bounds__(256) void accumulate_emission_masked_kernel(AccumulateArgs a, const float *emitted, float *moments, Stride32 plane, MaskArgs m) {
+    accumulate_body<true, true, 4u, 1u, true>(a, emitted, moments, plane, blockDim.x, &m);
+}
+
+// wfpt_adaptive_update (include/wfpt.h "Adaptive sampling"): one wave per tile of the context, one lane per pixel, lane = ly * 8 + lx as in
+// generate_rays. A lane outside the image is neither unconverged nor under the maximum. The tile's words are wave-uniform: the
+// dilation and the store run once per wave.
+constexpr int kAdaptiveThreads = 256;
+__global__ __launch_bounds__(kAdaptiveThreads) void adaptive_update_kernel(AdaptiveArgs a) {
+    const uint32_t lane = lane_id();
+    const uint32_t tile = uniform(blockIdx.x * (kAdaptiveThreads / 64u) + (threadIdx.x >> 6));
+    if (tile >= a.gx * a.gy) return;
+    const TilePixel p = tile_pixel(tile, lane, a.gx, a.tile);
+    const bool in_image = p.x < a.width && p.y < a.height;
+    bool unconverged = false, under_max = false;
+    if (in_image) {
+        const uint32_t i = local_pixel(p.x + p.y * a.width, a.width, a.tile);
+        const uint32_t n = a.count[i];
+        unconverged = adaptive_unconverged(a.moments[i], a.moments[static_cast<size_t>(a.plane) + i], n, a.min_samples, a.threshold, a.luminance_floor);
+        under_max = a.max_samples == 0u || n < a.max_samples;
+    }
+    uint64_t word = __ballot(unconverged);
+    if (a.dilate) word = dilate_tile(word);
+    word &= __ballot(under_max) & __ballot(in_image);
+    if (lane == 0) {
+        a.mask[tile] = word;
+        if (word) atomicAdd(a.n_active, static_cast<uint32_t>(__popcll(word)));
+    }
+}
+
+// wfpt_copy_mean_to_device: float k of the mean (stride 3) = accumulated[k] / count[k / 3]
+__global__ __launch_bounds__(256) void mean_resolve_kernel(const float *accumulated, const uint32_t *count, float *out, size_t n) {
+    for (size_t k = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x; k < n; k += static_cast<size_t>(gridDim.x) * blockDim.x)
+        out[k] = mean_resolve(accumulated[k], count[k / 3u]);
+}
 
 // The filter's pixel of this thread: a workgroup covers a kDenoiseTile^2 block, each wave an 8 x 8 block of it (2-D locality for the taps,
 // as generate_rays_kernel's tiles). False for the padding lanes of partial blocks.
@@ -4355,6 +4430,8 @@ BounceFn bounce_variant(const SceneDev &sc, bool exact, int mode, bool env = fal
         return env ? bounce_kernel<kBounceLast, uint32_t, 0, false, false, true> : bounce_kernel<kBounceLast, uint32_t, 0, false, false>;
     if (mode == kBounceMiddleRetire)
         return env ? pick_variant<BounceK<kBounceMiddleRetire, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddleRetire, false>>(sc, exact, lds);
+    if (mode == kBounceFirstMasked)
+        return env ? pick_variant<BounceK<kBounceFirstMasked, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceFirstMasked, false>>(sc, exact, lds);
     if (env) return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, true>>(sc, exact, lds);
     return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, false>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, false>>(sc, exact, lds);
 }
@@ -4370,7 +4447,8 @@ hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks) {
     for (bool exact : {false, true}) { // both box tests, the first and the middle launches, both miss payloads
         const hipError_t e = allow_dynamic_lds(bytes, bounce_variant(scene, exact, kBounceFirst), bounce_variant(scene, exact, kBounceMiddle),
                                                bounce_variant(scene, exact, kBounceFirst, true), bounce_variant(scene, exact, kBounceMiddle, true),
-                                               bounce_variant(scene, exact, kBounceMiddleRetire), bounce_variant(scene, exact, kBounceMiddleRetire, true));
+                                               bounce_variant(scene, exact, kBounceMiddleRetire), bounce_variant(scene, exact, kBounceMiddleRetire, true),
+                                               bounce_variant(scene, exact, kBounceFirstMasked), bounce_variant(scene, exact, kBounceFirstMasked, true));
         if (e != hipSuccess) return e;
     }
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
@@ -4450,10 +4528,11 @@ hipError_t launch_shade_rays(const RefillArgs &a, uint32_t n_chunks, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s) {
+hipError_t launch_generate_dense(const RefillArgs &a, hipStream_t s, const uint64_t *mask) {
     const uint32_t n = a.gx * a.gy * 64u < a.capacity ? a.gx * a.gy * 64u : a.capacity;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(generate_dense_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a);
+    if (mask) hipLaunchKernelGGL(generate_dense_masked_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a, mask);
+    else hipLaunchKernelGGL(generate_dense_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -4463,10 +4542,11 @@ hipError_t launch_compact(const CompactArgs &a, uint32_t n_chunks, hipStream_t s
     return hipGetLastError();
 }
 
-hipError_t launch_generate(const GenerateArgs &a, hipStream_t s) {
+hipError_t launch_generate(const GenerateArgs &a, hipStream_t s, const uint64_t *mask) {
     const uint32_t n = a.gx * a.gy * 64u;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(generate_rays_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a);
+    if (mask) hipLaunchKernelGGL(generate_rays_masked_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a, mask);
+    else hipLaunchKernelGGL(generate_rays_kernel, dim3((n + 255u) / 256u, a.batch.n), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -4565,6 +4645,31 @@ hipError_t launch_accumulate(const AccumulateArgs &a, const float *emitted, floa
         hipLaunchKernelGGL(accumulate_moments_kernel, g, b, 0, s, a, moments, pl);
     else
         hipLaunchKernelGGL(accumulate_kernel, g, b, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_masked(const AccumulateArgs &a, const float *emitted, float *moments, size_t plane, const MaskArgs &m, uint32_t grid,
+                                    hipStream_t s) {
+    const dim3 g(grid ? grid : 1u), b(256);
+    Stride32 pl{};
+    pl = plane;
+    if (!moments || !m.mask || !m.count || m.width == 0) return hipErrorInvalidValue;
+    if (emitted) hipLaunchKernelGGL(accumulate_emission_masked_kernel, g, b, 0, s, a, emitted, moments, pl, m);
+    else hipLaunchKernelGGL(accumulate_masked_kernel, g, b, 0, s, a, moments, pl, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_adaptive_update(const AdaptiveArgs &a, hipStream_t s) {
+    const uint32_t tiles = a.gx * a.gy, per_block = kAdaptiveThreads / 64u;
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_update_kernel, dim3((tiles + per_block - 1u) / per_block), dim3(kAdaptiveThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mean_resolve(const float *accumulated, const uint32_t *count, float *out, size_t n_floats, hipStream_t s) {
+    if (n_floats == 0) return hipSuccess;
+    const size_t blocks = (n_floats + 255) / 256;
+    hipLaunchKernelGGL(mean_resolve_kernel, dim3(static_cast<uint32_t>(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, accumulated, count, out, n_floats);
     return hipGetLastError();
 }
 

@@ -446,6 +446,50 @@ class PathTracer {
         check(wfpt_sample_termination(ctx_, thr3.data(), pixel_idx.data(), frame, b, pixel_idx.size(), out.data()));
         return out;
     }
+    // Adaptive sampling (WFPT_FLAG_ADAPTIVE, include/wfpt.h "Adaptive sampling"): a per-pixel active mask the renders obey, per-pixel sample
+    // counts, and the device pass that turns the luminance moments into the next mask.
+    void set_adaptive(const wfpt_adaptive_params &p) { check(wfpt_set_adaptive(ctx_, &p)); }
+    static wfpt_adaptive_params adaptive_defaults() {
+        wfpt_adaptive_params p;
+        wfpt_adaptive_params_default(&p);
+        return p;
+    }
+    wfpt_adaptive_params adaptive() {
+        wfpt_adaptive_params p;
+        check(wfpt_get_adaptive(ctx_, &p));
+        return p;
+    }
+    // the number of pixels the next render adds samples to (blocking)
+    uint32_t adaptive_update() {
+        uint32_t n = 0;
+        check(wfpt_adaptive_update(ctx_, &n));
+        return n;
+    }
+    // one byte per pixel of the context, non-zero = active
+    void set_active_mask(const std::vector<uint8_t> &mask) { check(wfpt_set_active_mask(ctx_, mask.data(), mask.size())); }
+    std::vector<uint8_t> active_mask() {
+        std::vector<uint8_t> m(wfpt_n_pixels(ctx_));
+        check(wfpt_read_active_mask(ctx_, m.data(), m.size()));
+        return m;
+    }
+    std::vector<uint32_t> sample_counts() {
+        std::vector<uint32_t> n(wfpt_n_pixels(ctx_));
+        check(wfpt_read_sample_counts(ctx_, n.data(), n.size()));
+        return n;
+    }
+    // accumulated / count per pixel (0 where the count is 0), 3 floats per pixel
+    std::vector<float> mean() {
+        std::vector<float> rgb(3 * static_cast<size_t>(wfpt_n_pixels(ctx_)));
+        check(wfpt_read_mean(ctx_, rgb.data(), rgb.size()));
+        return rgb;
+    }
+    void mean_to_device(void *device_ptr, size_t n_bytes) { check(wfpt_copy_mean_to_device(ctx_, device_ptr, n_bytes)); }
+    // render(interval) and adaptive_update() in turn until no pixel is active or max_passes passes are done; the pixels still active
+    uint32_t render_adaptive(uint32_t max_passes, uint32_t interval) {
+        uint32_t n = 0;
+        check(wfpt_render_adaptive(ctx_, max_passes, interval, &n));
+        return n;
+    }
     // Multi-GPU (build-side addition, include/wfpt.h): this context was created with Options::tile_rank / tile_world;
     // rank 0 makes the 128-byte id with wfpt::comm_unique_id() and hands it to every rank.
     void comm_init(const std::array<uint8_t, WFPT_COMM_UNIQUE_ID_BYTES> &id, int rank, int world) { check(wfpt_comm_init(ctx_, id.data(), rank, world)); }
