@@ -2433,6 +2433,36 @@ static_assert(kBounceMiscWords % 4u == 0, "the stack column area stays 16-byte a
         }                                                                                                                              \
     }
 
+// bounce_kernel's argument block, read again from the kernarg segment where a work item uses it. The
+// compiler loads every field of a by-value kernel argument before the work-item loop and keeps it live across shade, walk and compaction:
+// more scalars than the 80 registers of eight waves per SIMD hold, so it parked them in lanes of vector registers and paid a v_readlane
+// (half-rate vector issue, the launches' bound unit) per use. The segment is read-only and sits in the scalar cache; the empty asm keeps
+// the loads behind it, where they stand in the code; fields nobody reads behind a call cost nothing (the copy is taken apart).
+// The blocks of the loop that call this name the result `a`, like the parameter it hides, because the shared macros name the kernel's `a`.
+static_assert(sizeof(BounceArgs) % 4u == 0, "the argument block is copied by words");
+__device__ __forceinline__ BounceArgs bounce_args_here() {
+    const WFPT_AS_CONSTANT uint32_t *k = (const WFPT_AS_CONSTANT uint32_t *)reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr());
+    asm volatile("" : "+s"(k));
+    uint32_t w[sizeof(BounceArgs) / 4u];
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(BounceArgs) / 4u; ++i) w[i] = k[i];
+    BounceArgs b;
+    __builtin_memcpy(&b, w, sizeof b);
+    // a pointer of a kernel argument is known to be global memory; one loaded from memory is not, and every access through it would be a
+    // flat_ instruction (both the vector-memory and the LDS counter, a 64-bit address per lane): say so (through the integer: a cast of the
+    // pointer to the global address space and back is folded away)
+#define WFPT_GLOBAL_PTR(f) b.f = (decltype(b.f))(WFPT_AS_GLOBAL std::remove_pointer_t<decltype(b.f)> *)reinterpret_cast<uintptr_t>(b.f)
+    WFPT_GLOBAL_PTR(stamps); WFPT_GLOBAL_PTR(rec_in); WFPT_GLOBAL_PTR(rec_out); WFPT_GLOBAL_PTR(in_hits); WFPT_GLOBAL_PTR(in_hit_base);
+    WFPT_GLOBAL_PTR(in_miss); WFPT_GLOBAL_PTR(in_first_seg); WFPT_GLOBAL_PTR(out_hits); WFPT_GLOBAL_PTR(out_miss); WFPT_GLOBAL_PTR(mq_in.base);
+    WFPT_GLOBAL_PTR(mq_out.base); WFPT_GLOBAL_PTR(image); WFPT_GLOBAL_PTR(ctl); WFPT_GLOBAL_PTR(camera); WFPT_GLOBAL_PTR(scene.nodes);
+    WFPT_GLOBAL_PTR(scene.prim_geom); WFPT_GLOBAL_PTR(scene.pair_parent); WFPT_GLOBAL_PTR(scene.pair_parent32); WFPT_GLOBAL_PTR(scene.spheres);
+    WFPT_GLOBAL_PTR(scene.triangles); WFPT_GLOBAL_PTR(scene.materials); WFPT_GLOBAL_PTR(scene.shade_rec); WFPT_GLOBAL_PTR(scene.nodes4);
+    WFPT_GLOBAL_PTR(scene.stack_spill); WFPT_GLOBAL_PTR(scene.nodes_ch); WFPT_GLOBAL_PTR(plan); WFPT_GLOBAL_PTR(cls_table);
+    WFPT_GLOBAL_PTR(first_seg_cls); WFPT_GLOBAL_PTR(out_cls); WFPT_GLOBAL_PTR(tile_lists); WFPT_GLOBAL_PTR(mask);
+#undef WFPT_GLOBAL_PTR
+    return b;
+}
+
 #ifndef WFPT_BOUNCE_ATTR
 #define WFPT_BOUNCE_ATTR __launch_bounds__(kExtendThreads, WFPT_EXTEND_MIN_WAVES)
 #endif
@@ -2494,14 +2524,16 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
     if (CHUNKED && n_static == 0u) ticket = chunk_draw_position(ticket, n_dynamic, chunk_end, CHUNK); // (no static round leads to the workgroup's own draw)
     if (ticket >= n_items) return;
     uint32_t item = tickets.item_of(ticket);
-    const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
     if (stage_scene) {
-        WFPT_STAGE_SCENE(g_nodes);
+        WFPT_STAGE_SCENE(reinterpret_cast<const float4 *>(a.scene.nodes));
         __syncthreads();
     }
     const wfpt_frame_buffer fb0 = uniform_frame(a.ctl);
     const uint32_t lane = lane_id(), wave = uniform(threadIdx.x >> 6); // (a scalar: what is selected or summed per wave below runs on the scalar unit)
     uint32_t iter = 0;
+    // The loop below reads the argument block where it uses it (bounce_args_here): `a` in its blocks is the copy taken there, not the
+    // parameter. g_nodes, which only the rare hand-over to the reference's walk reads, is loaded inside that arm.
+#define WFPT_G_NODES reinterpret_cast<const float4 *>(bounce_args_here().scene.nodes)
 #if WFPT_STAMPS
     unsigned long long acc_cyc[4] = {0, 0, 0, 0}, acc_search = 0, acc_record = 0; // (the last two: lane 0's view of shade's first two memory levels)
     unsigned long long acc_ticket = 0; // first launch, wave 0: from issuing the ticket's atomic to holding its value
@@ -2533,9 +2565,10 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             acc_drawn += 1u;
         } else if (!FIRST)
 #endif
-        if (!next_static && threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&a.ctl->ticket, 1u);
+        if (!next_static && threadIdx.x == 0) L.next[buf] = gridDim.x + atomicAdd(&bounce_args_here().ctl->ticket, 1u);
         if (!ENV && item >= n_hit_items) {
             while (item >= first_m + uniform(L.items_m[smp_m])) first_m += uniform(L.items_m[smp_m++]);
+            const BounceArgs a = bounce_args_here();
             WFPT_MISS_ITEM(smp_m, (item - first_m) * kMissSegsPerItem, (uniform(umin(a.ctl[smp_m].seg_n, a.capacity)) + kChunk - 1) / kChunk);
             __syncthreads(); // L.next[buf] is visible
             if (FIRST) { // (the first launch has no miss items: its arm stays the parent's instructions)
@@ -2551,9 +2584,8 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         while (item >= first_h + uniform(L.items_h[smp_h])) first_h += uniform(L.items_h[smp_h++]); // block-uniform
         const uint32_t smp = smp_h;
         const uint32_t seg_out = item - first_h;
+        const BounceArgs a = bounce_args_here(); // what the item reads up to and in its walk
         const uint32_t n = FIRST ? umin(n_slots, a.capacity) : uniform(umin(a.ctl[smp].shade_n, a.capacity));
-        const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
-        float *image = a.image + smp * a.batch.image_stride;
         wfpt_frame_buffer fb = fb0;
         fb.frame += smp;
 
@@ -2569,10 +2601,13 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
             live = live && p.x < fb.width && p.y < fb.height;
             if (MASKED) live = live && mask_bit(tile_word, lane); // a clear bit: what a lane outside the image does
             if (live) {
+                float *image = a.image + smp * a.batch.image_stride;
                 WFPT_START_PATH(pr, p, fb, image, ox = pr.ox; oy = pr.oy; oz = pr.oz; dx = pr.dx; dy = pr.dy; dz = pr.dz);
             }
         } else if (live) {
             // ---------------- shade (sh:56-156) of hit h of the previous wavefront
+            const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
+            float *image = a.image + smp * a.batch.image_stride;
             const HitSource src{a.rec_in, a.in_hit_base, a.in_first_seg, a.ctl + smp, image, a.scene.shade_rec, qo, co,
                                 a.capacity, a.rng_mode, a.image_width, a.scene.prim_kind, a.tile};
 #if WFPT_STAMPS
@@ -2616,14 +2651,14 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
                 w0 = uniform(*reinterpret_cast<const uint32_t *>(record));
             }
             if (w0 == kTileNoList) {
-                if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
+                if (live) WFPT_TRACE_ANY(WFPT_G_NODES, L.stack, ox, oy, oz, dx, dy, dz);
             } else if (live) {
                 prim = kHandOver; // (a far origin is handed over as WFPT_TRACE_ANY does)
                 if (!far_origin(a.scene, ox, oy, oz)) hit = trace_tile_list<PRIM>(record, w0, s_geom, ox, oy, oz, dx, dy, dz, t, prim);
                 if (prim == kHandOver)
-                    hit = retrace_reference<Trail, PRIM, uint16_t>(g_nodes, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
+                    hit = retrace_reference<Trail, PRIM, uint16_t>(WFPT_G_NODES, s_geom, s_parent, ox, oy, oz, dx, dy, dz, a.scene.n_nodes, t, prim);
             }
-        } else if (live) WFPT_TRACE_ANY(g_nodes, L.stack, ox, oy, oz, dx, dy, dz);
+        } else if (live) WFPT_TRACE_ANY(WFPT_G_NODES, L.stack, ox, oy, oz, dx, dy, dz);
         WFPT_STAMP(t_traced);
         const bool miss = live && !hit;
         const unsigned long long hit_mask = __ballot(hit), miss_mask = __ballot(miss);
@@ -2635,27 +2670,31 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         WFPT_STAMP(t_synced);
         uint32_t hit_before, miss_before, hit_total, miss_total;
         wave_offsets(L.cnt + buf * 2u * kExtendWaves, wave, lane, hit_before, hit_total, miss_before, miss_total);
-        const size_t seg = qo + static_cast<size_t>(seg_out) * kChunk;
-        // (the wave's first slot is a scalar address; a lane adds its 32-bit rank: no 64-bit vector arithmetic per store)
-        if (hit) { // the path record shade will read: p = origin + t * direction (sh:91), incoming direction, primitive, pixel
-            float4 *rec = a.rec_out + 2u * (seg + hit_before);
-            const uint32_t rank = mbcnt(hit_mask);
-            rec[2u * rank] = make_float4(ox + t * dx, oy + t * dy, oz + t * dz, __uint_as_float(pixel_idx));
-            rec[2u * rank + 1u] = make_float4(dx, dy, dz, __uint_as_float(prim));
-        }
-        if (miss) { // what miss_kernel reads of the ray (mk:29-32)
-            const size_t first = seg + miss_before;
-            const uint32_t rank = mbcnt(miss_mask);
-            (a.mq_out.dy() + first)[rank] = dy;
-            (a.mq_out.pixel() + first)[rank] = pixel_idx;
-            if (ENV) {
-                (a.mq_out.dx() + first)[rank] = dx;
-                (a.mq_out.dz() + first)[rank] = dz;
+        {
+            const BounceArgs a = bounce_args_here(); // the queues the item writes: nothing of them is held across the walk
+            const size_t qo = smp * a.batch.queue_stride, co = smp * a.batch.chunk_stride;
+            const size_t seg = qo + static_cast<size_t>(seg_out) * kChunk;
+            // (the wave's first slot is a scalar address; a lane adds its 32-bit rank: no 64-bit vector arithmetic per store)
+            if (hit) { // the path record shade will read: p = origin + t * direction (sh:91), incoming direction, primitive, pixel
+                float4 *rec = a.rec_out + 2u * (seg + hit_before);
+                const uint32_t rank = mbcnt(hit_mask);
+                rec[2u * rank] = make_float4(ox + t * dx, oy + t * dy, oz + t * dz, __uint_as_float(pixel_idx));
+                rec[2u * rank + 1u] = make_float4(dx, dy, dz, __uint_as_float(prim));
             }
-        }
-        if (threadIdx.x == 0) {
-            a.out_hits[co + seg_out] = hit_total;
-            a.out_miss[co + seg_out] = miss_total;
+            if (miss) { // what miss_kernel reads of the ray (mk:29-32)
+                const size_t first = seg + miss_before;
+                const uint32_t rank = mbcnt(miss_mask);
+                (a.mq_out.dy() + first)[rank] = dy;
+                (a.mq_out.pixel() + first)[rank] = pixel_idx;
+                if (ENV) {
+                    (a.mq_out.dx() + first)[rank] = dx;
+                    (a.mq_out.dz() + first)[rank] = dz;
+                }
+            }
+            if (threadIdx.x == 0) {
+                a.out_hits[co + seg_out] = hit_total;
+                a.out_miss[co + seg_out] = miss_total;
+            }
         }
 #if WFPT_STAMPS
         if (FIRST) { // per wave, summed over its items: ray generated | list or walk | barrier | compaction, stores issued (not waited for)
@@ -2689,6 +2728,7 @@ __global__ WFPT_BOUNCE_ATTR void bounce_kernel(BounceArgs a) {
         iter += 1;
     }
 #undef WFPT_NEXT_TICKET
+#undef WFPT_G_NODES
 #if WFPT_STAMPS
     if (FIRST && a.stamps && lane == 0) { // counters 48..63: wfpt_debug_read_stamps_ex(which = 3)
         for (int k = 0; k < 4; ++k) atomicAdd(&a.stamps[48 + k], acc_cyc[k]);
