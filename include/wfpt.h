@@ -256,7 +256,11 @@ enum {
     WFPT_FLAG_ADAPTIVE = 1u << 21    /* adaptive sampling, see "Adaptive sampling" below: a per-pixel active mask that generate_rays and
                                         accumulate obey, per-pixel sample counts and luminance moments, and a device pass that turns the
                                         moments into the next mask. Refused with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE and WFPT_FLAG_BINNING;
-                                        combines freely with every other flag. Without the flag nothing is allocated or launched. */
+                                        combines freely with every other flag. Without the flag nothing is allocated or launched. */,
+    WFPT_FLAG_LIGHT_POWER = 1u << 22 /* the connect pass selects its light in proportion to the lights' power (luminance times area), see
+                                        "Light selection by power" below. Needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with
+                                        WFPT_FLAG_ENV_NEE (and so WFPT_FLAG_ENV_MIS). With no emitter set, and with one light, the context
+                                        renders bit for bit as without the flag. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -769,7 +773,8 @@ int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
  * context with the flag and an emitter never runs the class-binned loop (set and clear on such a context are refused, see "Emission");
  * wfpt_render_chunked* masks the flag off. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag.
- * Not done: multiple importance sampling, cone sampling of sphere lights, light selection by power or a light BVH, retiring fully
+ * (Light selection by power: WFPT_FLAG_LIGHT_POWER, "Light selection by power" below.)
+ * Not done: multiple importance sampling, cone sampling of sphere lights, a light BVH, retiring fully
  * shadowed paths (dead ones: WFPT_FLAG_RETIRE), contact shadows thinner than the 0.001 / 0.1 % windows. (Importance sampling of the environment map: WFPT_FLAG_ENV_NEE.) */
 /* the number of emitting primitives (the light list's length), 0 with none; negative: a wfpt_status */
 int wfpt_nee_light_count(wfpt_ctx *ctx);
@@ -827,8 +832,9 @@ int wfpt_sample_lights(wfpt_ctx *ctx, const float *in9, size_t n, float *out8);
  * connect launches stay under wfpt_nee_timing_ms.
  * (Multiple importance sampling between the map and the scatter: WFPT_FLAG_ENV_MIS, "Environment multiple importance sampling" below.)
  * Not done: a distribution that accounts for the receiver's normal or for
- * visibility, a coarser importance grid or an alias table for very large maps, the class-binned loop and wfpt_render_chunked*, object
- * lights selected by power. */
+ * visibility, a coarser importance grid or an alias table for very large maps, the class-binned loop and wfpt_render_chunked*. (Object
+ * lights selected by power: WFPT_FLAG_LIGHT_POWER, refused together with this flag: the emitter branch beside the map's share selects
+ * uniformly.) */
 /* the environment share: finite, in (0, 1]. Acts like wfpt_set_emission: the accumulation restarts, the graphs and the history are dropped */
 int wfpt_set_environment_share(wfpt_ctx *ctx, float share);
 float wfpt_environment_share(const wfpt_ctx *ctx); /* 0 on a context without the flag */
@@ -882,8 +888,9 @@ int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, fl
  * launches are booked under wfpt_emission_timing_ms and wfpt_nee_timing_ms. The calls below are blocking and return
  * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while no primitive emits.
  * (Weighing the environment map against the scatter: WFPT_FLAG_ENV_MIS, a flag of its own below; WFPT_FLAG_ENV_NEE stays refused here.)
+ * (Light selection by power: WFPT_FLAG_LIGHT_POWER, "Light selection by power" below, which restates pl with the selected light's weight.)
  * Not done: the power heuristic, cone sampling of
- * sphere lights, light selection by power, MIS for fuzzy metal, the class-binned loop and wfpt_render_chunked*. */
+ * sphere lights, MIS for fuzzy metal, the class-binned loop and wfpt_render_chunked*. */
 /* Steps 3 to 5 with the weight for n caller-supplied receivers on the device. in9: as wfpt_sample_lights; out12: n rows of (q.xyz, the
  * light's primitive index as a float, ((e_q * G) * wl) per channel, 1.0 if the sample is occluded and 0.0 otherwise, pl, pb, wl, 0) --
  * the three channels and pl, pb, wl are 0 where the sample contributes nothing. */
@@ -892,6 +899,50 @@ int wfpt_sample_lights_mis(wfpt_ctx *ctx, const float *in9, size_t n, float *out
  * of its integer value), with ph = o + t d per component; out4: n rows of (pl, pb, wb, cos_l). A primitive that does not emit or is out
  * of range (a NaN included) gives (0, pb, 1, 0). */
 int wfpt_mis_hit_weight(wfpt_ctx *ctx, const float *in8, size_t n, float *out4);
+
+/* ------------------------------------------------------------------ Light selection by power (WFPT_FLAG_LIGHT_POWER)
+ * wfpt_create* accepts WFPT_FLAG_LIGHT_POWER only together with WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, and refuses it together with
+ * WFPT_FLAG_ENV_NEE, and therefore WFPT_FLAG_ENV_MIS (WFPT_ERR_INVALID_ARGUMENT either way). It combines freely with WFPT_FLAG_MIS,
+ * WFPT_FLAG_TEXTURES, WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_RETIRE, WFPT_FLAG_ADAPTIVE, WFPT_FLAG_AOV, WFPT_FLAG_DENOISE, every loop the emitters
+ * run in, both RNG modes and band sharding. "Next-event estimation" picks light i = floor(u0 * n_l) uniformly and weighs the sample by
+ * nf = f32(n_l): a bright lamp among 63 dim ones is sampled 1/64 of the time with weight 64, and a light of no area draws its share of
+ * shadow rays for nothing. A flagged context picks light i with a probability proportional to its power, luminance times area.
+ *
+ * The distribution belongs to the light list and is rebuilt wherever the list is (wfpt_set_emission, wfpt_clear_emission,
+ * wfpt_update_scene*); viewport changes keep it; texture bindings do not enter it. It is made of integers, so every build order gives the
+ * same tables. For light i of the list (primitive lights[i], its material's colour e), all f32, no fma:
+ *       A_i = the area exactly as step 3 of "Next-event estimation" computes it
+ *             (sphere: (4 pi) * (ra ra);  triangle: 0.5 * sqrt((cr.x cr.x + cr.y cr.y) + cr.z cr.z))
+ *       L_i = (0.2126 e.r + 0.7152 e.g) + 0.0722 e.b   (the denoiser's luminance, in its order);  f_i = L_i * A_i
+ *       M = the maximum of the f_i that are > 0
+ *       k_i = u32(ceil((f_i / M) * 65535.0)) where f_i > 0, and 1 where that quotient underflows to 0;  k_i = 0 where f_i > 0 fails (a NaN
+ *             included): such a light is never selected
+ *       cdf[i] = k_0 + ... + k_i  (u64);  total = cdf[n_l - 1];  prim_k[primitive] = k_i for the lights, 0 for every other primitive
+ * If M is not a finite number above 0 (no f_i > 0, or one overflows) there is no distribution, and the context behaves, for this flag, as
+ * a context without it: the same kernels, the same bits. The tables cost 8 bytes per light and 4 per primitive.
+ *
+ * With a distribution, steps 1, 2 and 4 of "Next-event estimation" are unchanged: the stream, the three draws, the point on the light from
+ * u1 u2, the occlusion window and the connected flag. What changes:
+ *  - Step 3, the selection.  T = u64(floor(f64(u0) * f64(total))), at most total - 1; a NaN or negative product selects 0.  i = the first
+ *    index with cdf[i] > T (a binary search; lights with k = 0 are never chosen).  k = cdf[i] - cdf[i - 1]  (cdf[-1] = 0).
+ *    nfi = f32(total) / f32(k): the two conversions round to nearest even, then one division.
+ *  - Steps 3 and 5, the weight. nfi stands wherever nf stood:  G = (((cos_s * cos_l) * A) * nfi) / (pi * dist2).
+ *  - WFPT_FLAG_MIS, connect pass:  pl = dist2 / ((cos_l * A) * nfi);  pb and wl as before.
+ *  - WFPT_FLAG_MIS, emission pass, where the connected flag is 1:  k = prim_k[hit primitive];  wb = 1 and pl = 0 if k == 0 or one of the
+ *    existing conditions fails;  otherwise nfi = f32(total) / f32(k),  pl = dist2 / ((cos_l * A) * nfi),  wb = pb / (pb + pl).
+ * wfpt_sample_lights, wfpt_sample_lights_mis and wfpt_mis_hit_weight on such a context follow this section and keep their row layouts. The
+ * connect launches stay under wfpt_nee_timing_ms, the emission launches under wfpt_emission_timing_ms.
+ * Consequences:
+ *  - No emitter. With no emitter set a flagged context launches the kernels of the unflagged one and renders the same bits.
+ *  - One light. With exactly one light total = k = 65535, nfi = 1.0f = nf and the selection is trivial: the images and every sampler row are
+ *    bit-identical to the unflagged context's.
+ *  - Several equal lights. Nothing of the kind is promised: the f64 selection and the f32 one round differently at the boundaries.
+ * wfpt_render_chunked* masks the flag off, as it does its prerequisites.
+ * Not done: the emitter branch of WFPT_FLAG_ENV_NEE / WFPT_FLAG_ENV_MIS contexts (the flag is refused there), an alias table, power that
+ * accounts for a light's texture, a light BVH (selection that knows the receiver). */
+/* The light list and its distribution: light_prims and cdf get wfpt_nee_light_count entries each; either may be NULL. Blocking.
+ * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while the list has no distribution. */
+int wfpt_read_light_distribution(wfpt_ctx *ctx, uint32_t *light_prims, uint64_t *cdf);
 
 /* ------------------------------------------------------------------ Environment multiple importance sampling (WFPT_FLAG_ENV_MIS)
  * wfpt_create* accepts WFPT_FLAG_ENV_MIS only together with WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and

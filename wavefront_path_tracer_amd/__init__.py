@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -53,6 +53,9 @@ NO_ROULETTE = 0xFFFFFFFF  # set_termination(roulette_start=NO_ROULETTE): dead pa
 # a per-pixel active mask, sample counts and moments, and the device pass that makes the next mask (include/wfpt.h "Adaptive sampling");
 # refused with FLAG_AOV, FLAG_DENOISE and FLAG_BINNING
 FLAG_ADAPTIVE = 1 << 21
+# the connect pass selects its light in proportion to power, luminance times area (include/wfpt.h "Light selection by power"); needs
+# FLAG_EMISSION and FLAG_NEE, refused with FLAG_ENV_NEE
+FLAG_LIGHT_POWER = 1 << 22
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
 TILE_LIST_CAP, TILE_NO_LIST = 16, 0xFFFFFFFF
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
@@ -374,6 +377,7 @@ def lib():
         "wfpt_set_environment_share": (i32, [vp, f32]),
         "wfpt_environment_share": (f32, [vp]),
         "wfpt_read_environment_distribution": (i32, [vp, vp, vp]),
+        "wfpt_read_light_distribution": (i32, [vp, vp, vp]),
         "wfpt_sample_environment_light": (i32, [vp, vp, sz, vp]),
         "wfpt_sample_lights_mis": (i32, [vp, vp, sz, vp]),
         "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
@@ -1488,6 +1492,15 @@ class PathTracer:
         """The connect pass's light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 of (p.xyz, n.xyz,
         u0, u1, u2); returns (n, 8) float32 of (q.xyz, the light's primitive index, the unoccluded factor e_q * G per channel, occluded 0/1)."""
         return self._probe(lib().wfpt_sample_lights, "sample_lights", rows, 9, 8)
+
+    # ---- light selection by power (contexts created with FLAG_EMISSION | FLAG_NEE | FLAG_LIGHT_POWER; include/wfpt.h "Light selection by power")
+    def light_distribution(self):
+        """(light_prims, cdf) of the light list's sampling distribution: light_prims (n_l,) uint32, the emitting primitives in list order,
+        and cdf (n_l,) uint64, the inclusive prefix sums of their integer weights. Raises while the list has no distribution."""
+        n = self.nee_light_count()
+        prims, cdf = np.zeros(n, "<u4"), np.zeros(n, "<u8")
+        self._check(lib().wfpt_read_light_distribution(self.handle, _p(prims), _p(cdf)))
+        return prims, cdf
 
     # ---- environment next-event estimation (contexts created with FLAG_ENVIRONMENT | FLAG_EMISSION | FLAG_NEE | FLAG_ENV_NEE)
     def set_environment_share(self, share):

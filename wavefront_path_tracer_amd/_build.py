@@ -12,6 +12,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libwfpt.so")
 SOURCES = ["wfpt_kernels.hip", "wfpt_api.hip", "wfpt_bvh_build.hip", "wfpt_host.cpp"]
 HEADERS = [os.path.join(CSRC, "wfpt_kernels.h"), os.path.join(CSRC, "wfpt_bvh4.h"), os.path.join(CSRC, "wfpt_device_math.h"), os.path.join(CSRC, "wfpt_tile_lists.h"), os.path.join(CSRC, "wfpt_first_schedule.h"), os.path.join(CSRC, "wfpt_ticket_chunks.h"),
+           os.path.join(CSRC, "wfpt_connect_body.inc"),
            os.path.join(ROOT, "include", "wfpt.h")]
 # -ffp-contract=off: results must be bit-identical to the oracle, the only fused ops are explicit fmaf.
 # Correctly rounded fp32 divide/sqrt is hipcc's default and is requested explicitly anyway.

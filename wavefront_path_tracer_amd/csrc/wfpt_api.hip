@@ -122,6 +122,10 @@ struct EmissionTables {
     DeviceBuffer<float4> mat;
     DeviceBuffer<uint32_t> lights; // WFPT_FLAG_NEE contexts: the primitives whose material emits, in primitive order
     uint32_t n_lights = 0;
+    // WFPT_FLAG_LIGHT_POWER contexts: the list's sampling distribution (all null / 0 where it has none)
+    DeviceBuffer<uint64_t> cdf;
+    DeviceBuffer<uint32_t> prim_k;
+    uint64_t total = 0;
 };
 
 struct HistoryBuffers {
@@ -256,6 +260,11 @@ struct wfpt_ctx {
     // WFPT_FLAG_MIS (include/wfpt.h "Multiple importance sampling"): the hit points of the diffuse hits, `emitted`'s shape (one float4 per
     // pixel per sample in flight), allocated with the first emitter and kept; never zeroed (read only where the connected flag is 1)
     DeviceBuffer<float4> mis_origin;
+    // WFPT_FLAG_LIGHT_POWER (include/wfpt.h "Light selection by power"): the light list's sampling distribution, built and dropped with the
+    // list (null where the list has none: the context then runs as one without the flag)
+    DeviceBuffer<uint64_t> light_cdf;
+    DeviceBuffer<uint32_t> light_prim_k;
+    uint64_t light_total = 0;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
     // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
     DeviceBuffer<uint32_t> env_row;
@@ -659,6 +668,10 @@ bool weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_MIS) != 0 && c
 bool env_weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_ENV_MIS) != 0 && env_connecting(c) && c->mis_origin.get() != nullptr; }
 // the map with its distribution and the effective share: 1 while there is no light to pick instead
 EnvDist env_dist(const wfpt_ctx *c) { return EnvDist{c->env, c->env_row.get(), c->env_marg.get(), c->env_total, c->n_lights ? c->env_share : 1.0f}; }
+// a WFPT_FLAG_LIGHT_POWER context whose light list has a distribution: the connect pass, the weighed emission pass and the samplers are
+// the POWER variants
+bool power_selecting(const wfpt_ctx *c) { return c->light_cdf.get() != nullptr; }
+LightDist light_dist(const wfpt_ctx *c) { return LightDist{c->light_cdf.get(), c->light_prim_k.get(), c->light_total}; }
 // the connect pass before a shade step of wavefront `wavefront`
 ConnectArgs connect_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w) {
     ConnectArgs a{};
@@ -687,8 +700,9 @@ ConnectArgs sampler_args(wfpt_ctx *c, const float *in, float *out, size_t n) {
 // ... launched for the probes: a workgroup per kChunk rows, at most the resident set
 hipError_t launch_sampler(wfpt_ctx *c, const ConnectArgs &a, bool envs, bool mis) {
     const uint64_t items = (static_cast<uint64_t>(a.sample_n) + kChunk - 1) / kChunk;
+    const LightDist ld = light_dist(c);
     return launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                          textured(c), envs, mis);
+                          textured(c), envs, mis, !envs && power_selecting(c) ? &ld : nullptr);
 }
 // The body of a host probe (wfpt_sample_*, wfpt_*_weight), blocking: n caller rows of in_width floats to the device, launch(d_in, d_out) on
 // the context's stream, n rows of out_width floats back. rows31: the launch counts its rows in 31 bits.
@@ -710,12 +724,20 @@ int probe(wfpt_ctx *c, const char *who, const float *in, size_t in_width, float 
 }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
-    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c));
+    const LightDist ld = light_dist(c);
+    return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c),
+                          power_selecting(c) ? &ld : nullptr);
 }
 // the emission pass of the context's kind
 hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
-    return launch_emission(a, !connecting(c) ? kEmitAll : env_weighing(c) ? kEmitWeighedEnv : weighing(c) ? kEmitWeighed : kEmitGated, grid,
-                           c->stream.get(), 1.0f - env_dist(c).share);
+    const LightDist ld = light_dist(c);
+    return launch_emission(a,
+                           !connecting(c)                          ? kEmitAll
+                           : env_weighing(c)                       ? kEmitWeighedEnv
+                           : weighing(c) && power_selecting(c)     ? kEmitWeighedPower
+                           : weighing(c)                           ? kEmitWeighed
+                                                                   : kEmitGated,
+                           grid, c->stream.get(), 1.0f - env_dist(c).share, &ld);
 }
 // the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
 const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
@@ -1578,6 +1600,19 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
             return nullptr;
         }
     }
+    if ((params->flags & WFPT_FLAG_LIGHT_POWER) != 0) {
+        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
+        if ((params->flags & need) != need) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_LIGHT_POWER needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+                                                     "(it selects the light the connect pass samples)");
+            return nullptr;
+        }
+        if ((params->flags & (WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS)) != 0) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_LIGHT_POWER does not go with WFPT_FLAG_ENV_NEE or WFPT_FLAG_ENV_MIS "
+                                                     "(the emitter branch beside the map's share selects uniformly)");
+            return nullptr;
+        }
+    }
     if ((params->flags & WFPT_FLAG_ENV_MIS) != 0) {
         constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE;
         if ((params->flags & need) != need) {
@@ -1828,7 +1863,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -1924,7 +1959,8 @@ int wfpt_update_render_parameters(wfpt_ctx *c, uint32_t width, uint32_t height, 
 static int build_texture_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mat_idx,
                                 const std::vector<uint32_t> &row, TextureTables &out);
 static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t);
-static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out);
+static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out,
+                                 const float4 *geom = nullptr, uint32_t prim_kind = 0);
 static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
@@ -1964,7 +2000,18 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         em_rgb.resize(3 * static_cast<size_t>(n_materials), 0.0f);
         std::vector<uint32_t> mat_idx(n_prims);
         for (uint32_t i = 0; i < n_prims; ++i) mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
-        if (int r = build_emission_tables(c, em_rgb, mat_idx, em_tables); r != WFPT_OK) return r;
+        // (WFPT_FLAG_LIGHT_POWER: the light list's distribution needs the areas of the NEW primitives, which the device does not hold yet)
+        DeviceBuffer<float4> geom;
+        if (c->p.flags & WFPT_FLAG_LIGHT_POWER) {
+            std::vector<float4> g(spheres ? n_prims : 3 * static_cast<size_t>(n_prims));
+            if (spheres)
+                for (uint32_t i = 0; i < n_prims; ++i) g[i] = make_float4(spheres[i].center[0], spheres[i].center[1], spheres[i].center[2], spheres[i].radius);
+            else
+                std::memcpy(g.data(), triangles, sizeof(wfpt_triangle) * n_prims);
+            WFPT_HIP(c, geom.alloc(g.size()));
+            WFPT_HIP(c, hipMemcpy(geom.get(), g.data(), sizeof(float4) * g.size(), hipMemcpyHostToDevice));
+        }
+        if (int r = build_emission_tables(c, em_rgb, mat_idx, em_tables, geom.get(), spheres ? 0u : 1u); r != WFPT_OK) return r;
     }
     if (int r = upload_scene(c, spheres, triangles, n_prims, materials, n_materials, nodes.data(), n_nodes, pair_parent,
                              static_cast<uint32_t>(depth), &c->h_camera);
@@ -3291,7 +3338,9 @@ int wfpt_texture_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
 // The kernels' view of the colours and the scene: per primitive its material_idx when that material emits, kNoEmission otherwise, and the
 // colours as float4 (both null while no material emits). Built whole for a CANDIDATE state -- colours `rgb` (3 per material) and per
 // primitive its material_idx -- without touching the context, like build_texture_tables.
-static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out) {
+// geom / prim_kind (WFPT_FLAG_LIGHT_POWER): the candidate's primitives in SceneDev::prim_geom's layout, null = the context's own scene.
+static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, const std::vector<uint32_t> &mat_idx, EmissionTables &out,
+                                 const float4 *geom, uint32_t prim_kind) {
     const size_t n_mat = rgb.size() / 3;
     std::vector<float4> mat(n_mat);
     bool any = false;
@@ -3321,6 +3370,37 @@ static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, con
             out.n_lights = static_cast<uint32_t>(lights.size());
         }
     }
+    // The list's sampling distribution (include/wfpt.h "Light selection by power"), on the device as the map's is (build_env_tables). A list
+    // whose largest f is not a finite number above 0 has none: its buffers stay null.
+    if ((c->p.flags & WFPT_FLAG_LIGHT_POWER) && out.n_lights) {
+        const uint32_t n_l = out.n_lights, tiles = (n_l + kLightTile - 1u) / kLightTile;
+        const hipStream_t st = c->stream.get();
+        DeviceBuffer<float> f;
+        DeviceBuffer<uint32_t> max_bits, k, tile_sum;
+        WFPT_HIP(c, f.alloc(n_l));
+        WFPT_HIP(c, max_bits.alloc(1));
+        WFPT_HIP(c, hipMemsetAsync(max_bits.get(), 0, sizeof(uint32_t), st));
+        WFPT_HIP(c, launch_light_weights(out.lights.get(), n_l, geom ? geom : c->scene.prim_geom, geom ? prim_kind : c->scene.prim_kind,
+                                         out.prim.get(), out.mat.get(), f.get(), max_bits.get(), st));
+        float M = 0.0f;
+        WFPT_HIP(c, hipMemcpyAsync(&M, max_bits.get(), sizeof(float), hipMemcpyDeviceToHost, st));
+        WFPT_HIP(c, hipStreamSynchronize(st));
+        if (M > 0.0f && M <= FLT_MAX) {
+            DeviceBuffer<uint64_t> cdf;
+            DeviceBuffer<uint32_t> prim_k;
+            WFPT_HIP(c, k.alloc(n_l));
+            WFPT_HIP(c, tile_sum.alloc(tiles));
+            WFPT_HIP(c, cdf.alloc(n_l));
+            WFPT_HIP(c, prim_k.alloc(n));
+            WFPT_HIP(c, hipMemsetAsync(prim_k.get(), 0, sizeof(uint32_t) * n, st));
+            WFPT_HIP(c, launch_light_tables(out.lights.get(), n_l, f.get(), M, k.get(), tile_sum.get(), cdf.get(), prim_k.get(), st));
+            WFPT_HIP(c, hipMemcpyAsync(&out.total, cdf.get() + (n_l - 1u), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            WFPT_HIP(c, hipStreamSynchronize(st));
+            if (out.total == 0) return fail(c, WFPT_ERR_HIP, "the sampling distribution of a lit light list is empty");
+            out.cdf = std::move(cdf);
+            out.prim_k = std::move(prim_k);
+        }
+    }
     return WFPT_OK;
 }
 // the new tables replace the old ones (the stream is idle: the caller synchronised it)
@@ -3329,6 +3409,9 @@ static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t) {
     c->em_mat = std::move(t.mat);
     c->nee_lights = std::move(t.lights);
     c->n_lights = t.n_lights;
+    c->light_cdf = std::move(t.cdf);
+    c->light_prim_k = std::move(t.prim_k);
+    c->light_total = t.total;
 }
 
 static int emission_check(wfpt_ctx *c, const char *who, bool changes) {
@@ -3432,8 +3515,21 @@ int wfpt_mis_hit_weight(wfpt_ctx *c, const float *in8, size_t n, float *out4) {
     if (int r = mis_check(c, "wfpt_mis_hit_weight"); r != WFPT_OK) return r;
     return probe(c, "wfpt_mis_hit_weight", in8, 8, out4, 4, n, true, [&](const float *d_in, float *d_out) {
         const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
-        return launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+        const LightDist ld = light_dist(c);
+        return launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in, d_out, static_cast<uint32_t>(n), c->stream.get(),
+                                 power_selecting(c) ? &ld : nullptr);
     });
+}
+
+// ---------------------------------------------------------------- light selection by power (include/wfpt.h "Light selection by power")
+int wfpt_read_light_distribution(wfpt_ctx *c, uint32_t *light_prims, uint64_t *cdf) {
+    if (int r = flag_check(c, "wfpt_read_light_distribution", WFPT_FLAG_LIGHT_POWER, "WFPT_FLAG_LIGHT_POWER"); r != WFPT_OK) return r;
+    if (!power_selecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_read_light_distribution: the light list has no distribution");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
+    if (light_prims) WFPT_HIP(c, hipMemcpy(light_prims, c->nee_lights.get(), sizeof(uint32_t) * c->n_lights, hipMemcpyDeviceToHost));
+    if (cdf) WFPT_HIP(c, hipMemcpy(cdf, c->light_cdf.get(), sizeof(uint64_t) * c->n_lights, hipMemcpyDeviceToHost));
+    return WFPT_OK;
 }
 
 // ---------------------------------------------------------------- environment next-event estimation (include/wfpt.h)

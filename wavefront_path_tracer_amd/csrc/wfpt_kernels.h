@@ -500,7 +500,10 @@ struct TextureArgs {
 //                 connect samples that go to it, plq = pl * q. Its own kernel, emission_weighed_env_kernel, which takes q as a second
 //                 argument: EmissionArgs, and with it the three kernels above, stay as they are.
 constexpr uint32_t kNoEmission = 0xffffffffu;
-enum EmissionKind : int { kEmitAll, kEmitGated, kEmitWeighed, kEmitWeighedEnv };
+//   kEmitWeighedPower: the weighing contexts whose light list has a distribution (WFPT_FLAG_LIGHT_POWER with WFPT_FLAG_MIS; include/wfpt.h
+//                 "Light selection by power"): kEmitWeighed with nfi = f32(total) / f32(prim_k[hit primitive]) in nf's place, and wb = 1
+//                 where that k is 0. Its own kernel, emission_weighed_power_kernel, which takes the distribution as a second argument.
+enum EmissionKind : int { kEmitAll, kEmitGated, kEmitWeighed, kEmitWeighedEnv, kEmitWeighedPower };
 struct EmissionArgs {
     HitWalk w;
     float *emitted;           // the second per-sample plane: image's shape and strides
@@ -523,6 +526,15 @@ struct EnvDist {
     float share;
 };
 
+// The light list's sampling distribution (WFPT_FLAG_LIGHT_POWER, include/wfpt.h "Light selection by power"): cdf[i] the inclusive prefix
+// sum of the lights' integer weights k in list order, total = cdf[n_lights - 1] > 0, prim_k[primitive] = k of a light and 0 of every other
+// primitive. All null / 0 while the list has no distribution.
+struct LightDist {
+    const uint64_t *cdf;
+    const uint32_t *prim_k;
+    uint64_t total;
+};
+
 // The connect pass (connect_kernel; WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): before a shade step, after that step's texture
 // and emission passes, every hit the step will shade either sends one shadow ray to a sampled point of a light and adds the unoccluded
 // sample to the pixel's `emitted` (a diffuse hit: the pixel's connected flag, emitted.w, becomes 1) or only clears the flag (every other
@@ -543,6 +555,10 @@ struct EnvDist {
 // an emitter's by wl = plq / (plq + pb), plq = pl * (1 - p) -- and `origin` stored as the MIS variants do, for the kEmitWeighedEnv emission
 // pass and for nothing else (miss_env_mis_kernel takes pb from the miss's own direction). Their sampler form
 // (wfpt_sample_environment_light_mis) answers 12 floats a row with the effective share p.
+// The POWER variants (WFPT_FLAG_LIGHT_POWER contexts whose list has a distribution; never with ENVS): the light is selected by a binary
+// search of the distribution's cdf and weighed by nfi = f32(total) / f32(k) wherever nf stands; with and without MIS, render and sampler
+// forms alike. Their kernels (connect_power_kernel) take the LightDist as a second argument: ConnectArgs, and with it the kernels above, stay
+// as they are.
 struct ConnectArgs {
     HitWalk w;
     float *emitted;
@@ -757,13 +773,28 @@ hipError_t launch_miss(const MissArgs &a, uint32_t grid, hipStream_t s, const En
 hipError_t launch_env_mis_weight(const EnvDist &env, const float *dirs3, float *out4, uint32_t n, hipStream_t s);
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s);
 // q: kEmitWeighedEnv's alone, 1 - the effective environment share
-hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q = 1.0f);
+// ld: kEmitWeighedPower's alone
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q = 1.0f, const LightDist *ld = nullptr);
 // wfpt_mis_hit_weight: n rows of (o.xyz, d.xyz, t, primitive) -> (pl, pb, wb, cos_l), one thread per row
-hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s);
+// ld (null = none): the light list's distribution, nfi in nf's place (mis_weight_power_kernel)
+hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s,
+                             const LightDist *ld = nullptr);
 // grid: at most extend's (the four-wide walk's spill area is sized for that); textured: a light's material is bound to a texture
 // envs: the ENVS variants (a.envd holds a distribution)
 // mis: the MIS variants (a.origin set, or the sampler form's rows out); with envs, the ENVS MIS variants
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false);
+// power (null = none): the POWER variants with this distribution (never with envs)
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false,
+                          const LightDist *power = nullptr);
+// The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
+// primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
+// emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the
+// caller has read M back, k into `k` with the sum of every kLightTile lights into tile_sum; then cdf, and k scattered into prim_k
+// (zeroed by the caller) at the lights' primitives.
+constexpr uint32_t kLightTile = 256;
+hipError_t launch_light_weights(const uint32_t *lights, uint32_t n_l, const float4 *geom, uint32_t prim_kind, const uint32_t *prim_em, const float4 *em,
+                                float *f, uint32_t *max_bits, hipStream_t s);
+hipError_t launch_light_tables(const uint32_t *lights, uint32_t n_l, const float *f, float M, uint32_t *k, uint32_t *tile_sum, uint64_t *cdf,
+                               uint32_t *prim_k, hipStream_t s);
 // The sampling distribution of a map (include/wfpt.h "Environment next-event estimation"), built on the device in three launches on `s`:
 // f = Lm * s_y per texel into `f` (w * h floats) and its maximum's bits into *max_bits (zeroed by the caller); then, once the caller has
 // read M back, row (w * h) and the row-total prefix marg (h).

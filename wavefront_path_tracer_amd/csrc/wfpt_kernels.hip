@@ -2146,10 +2146,10 @@ __device__ __forceinline__ MisWeight mis_hit_weight(const float4 *prim_geom, con
 // thr * e (gated, or weighed, by the pixel's connected flag) to the pixel's `emitted` and leaves the throughput +0: the path is dead,
 // shade scatters it all the same.
 template <int KIND>
-__device__ __forceinline__ void emission_body(EmissionArgs a, float q) {
+__device__ __forceinline__ void emission_body(EmissionArgs a, float q, LightDist ld = LightDist{}) {
     const SampleHits s = sample_hits(a.w, blockIdx.y);
     float *emitted = a.emitted + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride);
-    constexpr bool kWeighed = KIND == kEmitWeighed || KIND == kEmitWeighedEnv;
+    constexpr bool kWeighed = KIND == kEmitWeighed || KIND == kEmitWeighedEnv || KIND == kEmitWeighedPower;
     const float4 *origin = kWeighed ? a.origin + blockIdx.y * static_cast<size_t>(a.w.batch.image_stride / 4u) : nullptr;
     for_each_shaded_hit<false>(a.w, s, [&](size_t slot, const Hit &hit) {
         const uint32_t m_idx = a.prim_em[hit.prim];
@@ -2163,8 +2163,15 @@ __device__ __forceinline__ void emission_body(EmissionArgs a, float q) {
         } else if (kWeighed) {
             const Hit h = load_hit<true>(a.w, s, slot); // the point and the direction: for the hits that are weighed only
             const float4 o = origin[lp];
-            const float wb = mis_hit_weight<KIND == kEmitWeighedEnv>(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, a.nf, {o.x, o.y, o.z}, h.p, h.d,
-                                                                     q).wb;
+            float wb;
+            if (KIND == kEmitWeighedPower) { // nfi of the light hit; a light the connect pass never selects (k = 0) keeps its whole weight
+                const uint32_t k = ld.prim_k[hit.prim];
+                wb = k ? mis_hit_weight(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, static_cast<float>(ld.total) / static_cast<float>(k),
+                                        {o.x, o.y, o.z}, h.p, h.d).wb
+                       : 1.0f;
+            } else {
+                wb = mis_hit_weight<KIND == kEmitWeighedEnv>(a.prim_geom, a.w.shade_rec, a.prim_kind, hit.prim, a.nf, {o.x, o.y, o.z}, h.p, h.d, q).wb;
+            }
             *out = make_float4(had.x + (thr.x * e.x) * wb, had.y + (thr.y * e.y) * wb, had.z + (thr.z * e.z) * wb, had.w);
         }
         *px = make_float4(0.0f, 0.0f, 0.0f, thr.w);
@@ -2178,11 +2185,18 @@ __global__ __launch_bounds__(kConsumerThreads) void emission_kernel(EmissionArgs
 __global__ __launch_bounds__(kConsumerThreads) void emission_weighed_env_kernel(EmissionArgs a, float q) {
     emission_body<kEmitWeighedEnv>(a, q);
 }
+// kEmitWeighedPower: the light list's distribution (include/wfpt.h "Light selection by power")
+__global__ __launch_bounds__(kConsumerThreads) void emission_weighed_power_kernel(EmissionArgs a, LightDist ld) {
+    emission_body<kEmitWeighedPower>(a, 1.0f, ld);
+}
 
 // wfpt_mis_hit_weight: mis_hit_weight for caller rows (o.xyz, d.xyz, t, the primitive index as a float), one thread per row; a primitive
 // that does not emit or lies outside the scene (a NaN index included) answers (0, pb, 1, 0)
-__global__ __launch_bounds__(256) void mis_weight_kernel(MisArgs mis, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4,
-                                                         uint32_t n) {
+// POWER (mis_weight_power_kernel; include/wfpt.h "Light selection by power"): nfi = f32(total) / f32(k) of the primitive in nf's place, and
+// (0, pb, 1, cos_l) for an emitter the connect pass never selects (k = 0)
+template <bool POWER>
+__device__ __forceinline__ void mis_weight_body(const MisArgs &mis, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4,
+                                                uint32_t n, const LightDist &ld) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float *row = in8 + 8u * static_cast<size_t>(i);
@@ -2191,7 +2205,17 @@ __global__ __launch_bounds__(256) void mis_weight_kernel(MisArgs mis, const floa
     const float3_ ph = {o.x + t * d.x, o.y + t * d.y, o.z + t * d.z}; // sh:91
     MisWeight m;
     if (pf >= 0.0f && pf < static_cast<float>(mis.n_prims) && prim_em[static_cast<uint32_t>(pf)] != kNoEmission) {
-        m = mis_hit_weight(mis.prim_geom, shade_rec, mis.prim_kind, static_cast<uint32_t>(pf), mis.nf, o, ph, d);
+        if (POWER) {
+            const uint32_t k = ld.prim_k[static_cast<uint32_t>(pf)];
+            m = mis_hit_weight(mis.prim_geom, shade_rec, mis.prim_kind, static_cast<uint32_t>(pf),
+                               k ? static_cast<float>(ld.total) / static_cast<float>(k) : 1.0f, o, ph, d);
+            if (k == 0u) {
+                m.pl = 0.0f;
+                m.wb = 1.0f;
+            }
+        } else {
+            m = mis_hit_weight(mis.prim_geom, shade_rec, mis.prim_kind, static_cast<uint32_t>(pf), mis.nf, o, ph, d);
+        }
     } else {
         m.pl = 0.0f;
         m.pb = (0.5f * sqrt_(dot3(d, d))) / kPi;
@@ -2200,6 +2224,14 @@ __global__ __launch_bounds__(256) void mis_weight_kernel(MisArgs mis, const floa
     }
     float *out = out4 + 4u * static_cast<size_t>(i);
     out[0] = m.pl; out[1] = m.pb; out[2] = m.wb; out[3] = m.cos_l;
+}
+__global__ __launch_bounds__(256) void mis_weight_kernel(MisArgs mis, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4,
+                                                         uint32_t n) {
+    mis_weight_body<false>(mis, shade_rec, prim_em, in8, out4, n, LightDist{});
+}
+__global__ __launch_bounds__(256) void mis_weight_power_kernel(MisArgs mis, const float4 *shade_rec, const uint32_t *prim_em, const float *in8,
+                                                               float *out4, uint32_t n, LightDist ld) {
+    mis_weight_body<true>(mis, shade_rec, prim_em, in8, out4, n, ld);
 }
 
 // shade (sh:56-156) of hit h of the previous wavefront, as the fused loop runs it: find the hit's path record (its
@@ -3724,11 +3756,31 @@ struct LightSample {
     uint32_t prim;
     float pl, pb; // MIS only: the solid-angle densities of this sample under the light list's area sampling and under shade's scatter
 };
-template <int PRIM, bool TEX, bool MIS = false>
-__device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, float3_ n, float u0, float u1, float u2, LightSample &s) {
-    const float nl_f = static_cast<float>(a.n_lights);
-    // (max_ first: a NaN or negative u0 of a caller's row picks light 0, and no float outside the u32 range is converted)
-    const uint32_t i = umin(static_cast<uint32_t>(min_(max_(__builtin_floorf(u0 * nl_f), 0.0f), nl_f)), a.n_lights - 1u);
+// POWER (include/wfpt.h "Light selection by power"; tests/light_power_ref.py restates it): the light is the first one whose cdf entry
+// exceeds T = floor(f64(u0) * f64(total)) -- T clamped into [0, total - 1], so a NaN or negative u0 of a caller's row selects 0 and every
+// index read lies inside the table -- and nfi = f32(total) / f32(k) stands wherever nf does. The search's upper levels are the same
+// addresses for every lane of a wave (one cache line each); the lanes part only in the last levels.
+template <int PRIM, bool TEX, bool MIS = false, bool POWER = false>
+__device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, float3_ n, float u0, float u1, float u2, LightSample &s,
+                                             const LightDist &ld = LightDist{}) {
+    float nl_f = static_cast<float>(a.n_lights);
+    uint32_t i;
+    if (POWER) {
+        const double ft = static_cast<double>(ld.total);
+        const double tr = __builtin_floor(static_cast<double>(u0) * ft);
+        const uint64_t T = tr >= 0.0 ? (tr < ft ? static_cast<uint64_t>(tr) : ld.total - 1u) : 0u;
+        uint32_t lo = 0u, hi = a.n_lights - 1u; // the first light with cdf[i] > T: cdf[n_lights - 1] = total > T
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (ld.cdf[mid] > T) hi = mid; else lo = mid + 1u;
+        }
+        i = lo;
+        const uint64_t k = ld.cdf[i] - (i ? ld.cdf[i - 1u] : 0u); // > 0: cdf[i] > T >= cdf[i - 1]
+        nl_f = static_cast<float>(ld.total) / static_cast<float>(k);
+    } else {
+        // (max_ first: a NaN or negative u0 of a caller's row picks light 0, and no float outside the u32 range is converted)
+        i = umin(static_cast<uint32_t>(min_(max_(__builtin_floorf(u0 * nl_f), 0.0f), nl_f)), a.n_lights - 1u);
+    }
     const uint32_t prim = a.lights[i];
     s.prim = prim;
     float3_ nl;
@@ -3834,172 +3886,16 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // the share of its own branch; the point is stored as above. The sampler form is the map's, with the effective share and 12 floats a row.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
-    extern __shared__ float4 lds[];
-    WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
-    const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
-    const bool sampler = a.sample_in != nullptr;
-    const uint32_t per_smp = sampler ? (a.sample_n + kChunk - 1u) / kChunk : a.n_chunks_max;
-    const uint32_t n_items = sampler ? per_smp : per_smp * a.w.batch.n;
-    const uint32_t frame0 = sampler ? 0u : uniform(a.w.ctl->frame.frame); // the batch's first frame, as shade_kernel and aov_body take it
-    bool staged = false;
-    for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const uint32_t smp = sampler ? 0u : item / per_smp, chunk = item - smp * per_smp;
-        uint32_t count;
-        if (sampler) {
-            count = umin(static_cast<uint32_t>(kChunk), a.sample_n - chunk * kChunk);
-        } else { // the segment's hits among those the step shades
-            if (!segment_hits(a.w, sample_hits(a.w, smp), chunk, count)) continue;
-            count = umin(count, static_cast<uint32_t>(kChunk));
-        }
-        count = uniform(count);
-        if (count == 0u) continue;
-        if (LDS_SCENE && !staged) {
-            WFPT_STAGE_SCENE(g_nodes);
-            __syncthreads();
-            staged = true;
-        }
-        bool live = threadIdx.x < count;
-        float3_ p = {0.0f, 0.0f, 0.0f}, n = p;
-        float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f;
-        float u3 = 0.0f, u4 = 0.0f, share = 1.0f; // ENVS: the environment branch's two draws and the probability of the branch taken
-        bool to_env = false;
-        float4 *px = nullptr, *out = nullptr;
-        float4 rec1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (live && sampler) {
-            const float *row = a.sample_in + (ENVS ? 10u : 9u) * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
-            p = {row[0], row[1], row[2]};
-            n = {row[3], row[4], row[5]};
-            if (ENVS) {
-                u1 = row[6]; u2 = row[7]; u3 = row[8]; u4 = row[9];
-                to_env = true;
-                if (MIS) share = a.envd.share;
-            } else {
-                u0 = row[6]; u1 = row[7]; u2 = row[8];
-            }
-        } else if (live) {
-            // the hit's point, pixel and primitive: load_hit's two forms in this kernel's own statement order, with which three instantiations
-            // at the SGPR ceiling keep their VGPR count
-            const size_t slot = smp * static_cast<size_t>(a.w.batch.queue_stride) + static_cast<size_t>(chunk) * kChunk + threadIdx.x;
-            uint32_t prim, pixel_idx;
-            if (a.w.rec_in) {
-                const float4 ra = a.w.rec_in[2u * slot], rb = a.w.rec_in[2u * slot + 1u];
-                p = {ra.x, ra.y, ra.z};
-                pixel_idx = __float_as_uint(ra.w);
-                prim = __float_as_uint(rb.w);
-            } else {
-                const RayQueue q = slice(a.w.q, smp * static_cast<size_t>(a.w.batch.ray_stride));
-                const float t = a.w.hq.t()[slot];
-                const uint32_t ridx = a.w.hq.ridx()[slot];
-                prim = a.w.hq.prim()[slot];
-                p = {q.ox()[ridx] + t * q.dx()[ridx], q.oy()[ridx] + t * q.dy()[ridx], q.oz()[ridx] + t * q.dz()[ridx]}; // sh:91
-                pixel_idx = q.pixel()[ridx];
-            }
-            const float4 rec0 = a.scene.shade_rec[3u * prim];
-            rec1 = a.scene.shade_rec[3u * prim + 1u];
-            const uint32_t m = material_class(a.scene.shade_rec, prim);
-            if (a.w.material != 0xffffffffu && m != a.w.material) {
-                live = false; // one per-material shade stage: its class only
-            } else {
-                const uint32_t lp = local_pixel(pixel_idx, a.w.image_width, a.w.tile);
-                out = pixel_of(a.emitted + smp * static_cast<size_t>(a.w.batch.image_stride), lp);
-                // (ENVS: no emission table while no material emits)
-                if (m != 0u || ((!ENVS || a.prim_em) && a.prim_em[prim] != kNoEmission)) { // metal, dielectric, emitter: the flag is cleared, nothing else
-                    out->w = 0.0f;
-                    live = false;
-                } else {
-                    px = pixel_of(a.w.image + smp * static_cast<size_t>(a.w.batch.image_stride), lp);
-                    // the normal scatter() uses, never flipped
-                    n = PRIM == 0 ? normalize3({p.x - rec0.x, p.y - rec0.y, p.z - rec0.z}) : float3_{rec0.x, rec0.y, rec0.z};
-                    uint32_t rng = jenkins_hash(pixel_idx ^ jenkins_hash(frame0 + smp)); // init_rng((x, y), (W, H), frame): x + y W is the pixel
-                    rng = jenkins_hash(rng ^ (0x9E3779B9u * (a.wavefront + 1u)));
-                    u0 = rng_next_float(rng);
-                    u1 = rng_next_float(rng);
-                    u2 = rng_next_float(rng);
-                    if (ENVS) { // the map with probability envd.share (the effective one: 1 with no light). At 1 there is no comparison:
-                        // u0 = 1.0f must never reach an empty light list, nor a division by 1 - 1
-                        to_env = !(a.envd.share < 1.0f) || u0 < a.envd.share;
-                        if (to_env) {
-                            share = a.envd.share;
-                            u3 = rng_next_float(rng);
-                            u4 = rng_next_float(rng);
-                        } else {
-                            share = 1.0f - a.envd.share;
-                            u0 = (u0 - a.envd.share) / share;
-                        }
-                    }
-                }
-            }
-        }
-        LightSample s;
-        bool lit = false, occluded = false;
-        if (ENVS && to_env) lit = sample_env<MIS>(a.envd, n, u1, u2, u3, u4, share, s);
-        else if (live) lit = sample_light<PRIM, TEX, MIS>(a, p, n, u0, u1, u2, s);
-        if (lit) {
-#if WFPT_STAMPS
-            uint32_t dbg[3] = {0, 0, 0};
-#endif
-            // (the map: any hit occludes. Started with the closest-hit walk's own far end the early-out walk answers "is there a hit": kOccNone
-            // means the reference tests no primitive below 1e30, kOccHit that it accepts one)
-            const float window = (ENVS && to_env) ? 1e30f : s.dist * 0.999f;
-            uint32_t verdict = kOccUndecided;
-            // scenes in LDS, conservative boxes: the early-out walk answers most rays (3.4 % of a Shirley frame, same booleans)
-            if (WFPT_NEE_EARLY_OUT && LDS_SCENE && !EXACT && !far_origin(a.scene, p.x, p.y, p.z))
-                verdict = occluded_conservative<Trail, PRIM, uint16_t>(s_nodes, s_geom, s_parent, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z,
-                                                                      a.scene.n_nodes, window WFPT_DBG_ARG);
-            if (verdict == kOccUndecided) { // every other scene kind, and the rays that walk hands back: the closest hit decides
-                float t = 0.0f;
-                uint32_t prim = 0;
-                bool hit = false;
-                WFPT_TRACE_ANY(g_nodes, s_stack, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z);
-                occluded = hit && ((ENVS && to_env) || t < window);
-            } else {
-                occluded = verdict == kOccHit;
-            }
-        }
-        if (ENVS && MIS && !to_env && lit) s.pl = s.pl * share; // plq: the light list's density times the share of the samples that go to it
-        if (MIS && live && sampler) { // (q, primitive, (e_q G) wl, occluded, pl, pb, wl, 0): zeros where the sample contributes nothing
-            float *row = a.sample_out + 12u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
-            const float wl = lit ? s.pl / (s.pl + s.pb) : 0.0f; // (sample_light sets pl and pb only where it answers true)
-            if (ENVS) s.q = s.w; // (wdir, texel, (e Genv) we, occluded, pe, pb, we, 0)
-            row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
-            row[3] = static_cast<float>(s.prim);
-            row[4] = lit ? (s.e.x * s.G) * wl : 0.0f; row[5] = lit ? (s.e.y * s.G) * wl : 0.0f; row[6] = lit ? (s.e.z * s.G) * wl : 0.0f;
-            row[7] = occluded ? 1.0f : 0.0f;
-            row[8] = lit ? s.pl : 0.0f; row[9] = lit ? s.pb : 0.0f; row[10] = wl; row[11] = 0.0f;
-        } else if (MIS && live) {
-            const float4 thr = *px, had = *out;
-            const size_t lp4 = static_cast<size_t>(out - reinterpret_cast<float4 *>(a.emitted)); // the pixel's float4 in `emitted`: `origin` has its shape
-            a.origin[lp4] = make_float4(p.x, p.y, p.z, 0.0f);
-            if (ENVS && lit && !occluded && !to_env) { // an emitter of an ENVS context: the division by its share before the weight
-                const float wl = s.pl / (s.pl + s.pb);
-                *out = make_float4(had.x + ((((thr.x * rec1.x) * s.e.x) * s.G) / share) * wl, had.y + ((((thr.y * rec1.y) * s.e.y) * s.G) / share) * wl,
-                                   had.z + ((((thr.z * rec1.z) * s.e.z) * s.G) / share) * wl, 1.0f);
-            } else if (lit && !occluded) {
-                const float wl = s.pl / (s.pl + s.pb);
-                *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) * wl, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) * wl,
-                                   had.z + (((thr.z * rec1.z) * s.e.z) * s.G) * wl, 1.0f);
-            } else {
-                out->w = 1.0f;
-            }
-        } else if (live && sampler) {
-            float *row = a.sample_out + 8u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
-            if (ENVS) s.q = s.w;
-            row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
-            row[3] = static_cast<float>(s.prim);
-            row[4] = lit ? s.e.x * s.G : 0.0f; row[5] = lit ? s.e.y * s.G : 0.0f; row[6] = lit ? s.e.z * s.G : 0.0f;
-            row[7] = occluded ? 1.0f : 0.0f;
-        } else if (live) {
-            const float4 thr = *px, had = *out;
-            if (ENVS && lit && !occluded && !to_env) // an emitter, picked with probability `share` = 1 - envd.share: the last operation
-                *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) / share, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) / share,
-                                   had.z + (((thr.z * rec1.z) * s.e.z) * s.G) / share, 1.0f);
-            else if (lit && !occluded)
-                *out = make_float4(had.x + ((thr.x * rec1.x) * s.e.x) * s.G, had.y + ((thr.y * rec1.y) * s.e.y) * s.G,
-                                   had.z + ((thr.z * rec1.z) * s.e.z) * s.G, 1.0f);
-            else
-                out->w = 1.0f;
-        }
-    }
+    constexpr bool POWER = false;
+    const LightDist ld{};
+#include "wfpt_connect_body.inc"
+}
+// POWER (WFPT_FLAG_LIGHT_POWER contexts whose light list has a distribution; never with ENVS): sample_light selects by ld and weighs by
+// nfi; nothing else differs. The distribution is a second argument: connect_kernel keeps its name, its arguments and its instructions.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
+__global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectArgs a, LightDist ld) {
+    constexpr bool ENVS = false, POWER = true;
+#include "wfpt_connect_body.inc"
 }
 
 // sums -> resolved AOV words (aov_resolve_word, shared with the host read-back)
@@ -4372,6 +4268,91 @@ __global__ void env_marg_kernel(const uint32_t *row, uint32_t w, uint32_t h, uin
     }
 }
 
+// ---- the sampling distribution of a light list (include/wfpt.h "Light selection by power"; three launches wherever the list is rebuilt,
+// wfpt_update_scene_mesh's every frame included). All-f32 in the header's order; the tables are integers, so no order of the sums matters.
+// f = L * A per light (A: light_normal_area's own expressions), and the bits of the largest f > 0 into *max_bits (a NaN is not above 0)
+__global__ __launch_bounds__(256) void light_weight_kernel(const uint32_t *lights, uint32_t n_l, const float4 *geom, uint32_t prim_kind,
+                                                           const uint32_t *prim_em, const float4 *em, float *f, uint32_t *max_bits) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    float v = 0.0f;
+    if (i < n_l) {
+        const uint32_t prim = lights[i];
+        float area;
+        if (prim_kind == 0) {
+            const float ra = __builtin_fabsf(geom[prim].w);
+            area = (4.0f * kPi) * (ra * ra);
+        } else {
+            const float4 g1 = geom[3u * prim + 1u], g2 = geom[3u * prim + 2u];
+            const float3_ cr = {g1.y * g2.z - g1.z * g2.y, g1.z * g2.x - g1.x * g2.z, g1.x * g2.y - g1.y * g2.x};
+            area = 0.5f * sqrt_(dot3(cr, cr));
+        }
+        const float4 e = em[prim_em[prim]];
+        const float fv = denoise_luma(e.x, e.y, e.z) * area;
+        f[i] = fv;
+        if (fv > 0.0f) v = fv;
+    }
+    for (int off = 32; off > 0; off >>= 1) v = max_(v, __shfl_xor(v, off));
+    if ((threadIdx.x & 63u) == 0u && v > 0.0f) atomicMax(max_bits, __float_as_uint(v));
+}
+// k = u32(ceil((f / M) * 65535)) where f > 0 -- at least 1: a quotient that underflows -- and 0 elsewhere, a NaN included; the sum of the
+// workgroup's kLightTile values into tile_sum (at most 256 * 65535: it fits a u32)
+__global__ __launch_bounds__(kLightTile) void light_quantise_kernel(const float *f, float M, uint32_t n_l, uint32_t *k_out, uint32_t *tile_sum) {
+    __shared__ uint32_t s_wave[kLightTile / 64u];
+    const uint32_t i = blockIdx.x * kLightTile + threadIdx.x;
+    uint32_t k = 0u;
+    if (i < n_l) {
+        const float fv = f[i];
+        if (fv > 0.0f) {
+            k = static_cast<uint32_t>(__builtin_ceilf((fv / M) * 65535.0f));
+            if (k == 0u) k = 1u;
+        }
+        k_out[i] = k;
+    }
+    uint32_t sum = k;
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    if ((threadIdx.x & 63u) == 0u) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t = 0u;
+        for (uint32_t w = 0; w < kLightTile / 64u; ++w) t += s_wave[w];
+        tile_sum[blockIdx.x] = t;
+    }
+}
+// cdf = the inclusive prefix sum of k, one tile of kLightTile lights per workgroup: the workgroup's base is the sum of the tiles before it
+// (every workgroup adds them up for itself: n_l / 256 words at most, and no workgroup waits for another), the rest a scan inside the tile.
+// k is scattered into prim_k (zeroed by the caller) at the lights' primitives.
+__global__ __launch_bounds__(kLightTile) void light_scan_kernel(const uint32_t *lights, const uint32_t *k_in, const uint32_t *tile_sum, uint32_t n_l,
+                                                                uint64_t *cdf, uint32_t *prim_k) {
+    __shared__ uint64_t s_base[kLightTile / 64u];
+    __shared__ uint32_t s_wave[kLightTile / 64u];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t part = 0u;
+    for (uint32_t t = threadIdx.x; t < blockIdx.x; t += kLightTile) part += tile_sum[t];
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(part), off), hi = __shfl_xor(static_cast<uint32_t>(part >> 32), off);
+        part += (static_cast<uint64_t>(hi) << 32) | lo;
+    }
+    const uint32_t i = blockIdx.x * kLightTile + threadIdx.x;
+    const uint32_t k = i < n_l ? k_in[i] : 0u;
+    uint32_t incl = k;
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t t = __shfl_up(incl, off);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63u) s_wave[wave] = incl;
+    if (lane == 0u) s_base[wave] = part;
+    __syncthreads();
+    uint64_t base = 0u;
+    for (uint32_t w = 0; w < kLightTile / 64u; ++w) {
+        base += s_base[w];
+        if (w < wave) base += s_wave[w];
+    }
+    if (i < n_l) {
+        cdf[i] = base + incl;
+        prim_k[lights[i]] = k;
+    }
+}
+
 __global__ __launch_bounds__(256) void tex_sample_kernel(TexDev tex, const float *uv, float *rgb, size_t n) {
     const size_t i = blockIdx.x * static_cast<size_t>(blockDim.x) + threadIdx.x;
     if (i >= n) return;
@@ -4636,14 +4617,36 @@ hipError_t launch_env_tables(const EnvDev &env, const float *f, float M, uint32_
     return hipGetLastError();
 }
 
+hipError_t launch_light_weights(const uint32_t *lights, uint32_t n_l, const float4 *geom, uint32_t prim_kind, const uint32_t *prim_em, const float4 *em,
+                                float *f, uint32_t *max_bits, hipStream_t s) {
+    if (n_l == 0) return hipSuccess;
+    hipLaunchKernelGGL(light_weight_kernel, dim3((n_l + 255u) / 256u), dim3(256), 0, s, lights, n_l, geom, prim_kind, prim_em, em, f, max_bits);
+    return hipGetLastError();
+}
+
+hipError_t launch_light_tables(const uint32_t *lights, uint32_t n_l, const float *f, float M, uint32_t *k, uint32_t *tile_sum, uint64_t *cdf,
+                               uint32_t *prim_k, hipStream_t s) {
+    if (n_l == 0) return hipSuccess;
+    const dim3 grid((n_l + kLightTile - 1u) / kLightTile), block(kLightTile);
+    hipLaunchKernelGGL(light_quantise_kernel, grid, block, 0, s, f, M, n_l, k, tile_sum);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(light_scan_kernel, grid, block, 0, s, lights, k, tile_sum, n_l, cdf, prim_k);
+    return hipGetLastError();
+}
+
 hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
     hipLaunchKernelGGL(texture_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q) {
+hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q, const LightDist *ld) {
     if (grid == 0) return hipSuccess;
+    if (kind == kEmitWeighedPower) {
+        if (!ld || !ld->prim_k) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(emission_weighed_power_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a, *ld);
+        return hipGetLastError();
+    }
     if (kind == kEmitWeighedEnv) {
         hipLaunchKernelGGL(emission_weighed_env_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a, q);
         return hipGetLastError();
@@ -4655,9 +4658,11 @@ hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t gr
     return hipGetLastError();
 }
 
-hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s) {
+hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const uint32_t *prim_em, const float *in8, float *out4, uint32_t n, hipStream_t s,
+                             const LightDist *ld) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n);
+    if (ld) hipLaunchKernelGGL(mis_weight_power_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n, *ld);
+    else hipLaunchKernelGGL(mis_weight_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, m, shade_rec, prim_em, in8, out4, n);
     return hipGetLastError();
 }
 
@@ -4800,6 +4805,16 @@ ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = 
     if (!envs) return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
     return tex ? pick_variant<ConnectK<true, true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true, true>>(sc, exact, lds);
 }
+// (the POWER variants after all of those, for the same reason)
+using ConnectPowerFn = void (*)(ConnectArgs, LightDist);
+template <bool TEX, bool MIS> struct ConnectPowerK {
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectPowerFn get() { return connect_power_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, MIS>; }
+};
+ConnectPowerFn connect_power_variant(const SceneDev &sc, bool exact, bool tex, bool mis) {
+    const bool lds = sc.lds_scene != 0;
+    if (mis) return tex ? pick_variant<ConnectPowerK<true, true>>(sc, exact, lds) : pick_variant<ConnectPowerK<false, true>>(sc, exact, lds);
+    return tex ? pick_variant<ConnectPowerK<true, false>>(sc, exact, lds) : pick_variant<ConnectPowerK<false, false>>(sc, exact, lds);
+}
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
@@ -4807,15 +4822,23 @@ hipError_t connect_prepare(const SceneDev &scene) {
         const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true),
                                                connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true),
                                                connect_variant(scene, exact, false, false, true), connect_variant(scene, exact, true, false, true),
-                                               connect_variant(scene, exact, false, true, true), connect_variant(scene, exact, true, true, true));
+                                               connect_variant(scene, exact, false, true, true), connect_variant(scene, exact, true, true, true),
+                                               connect_power_variant(scene, exact, false, false), connect_power_variant(scene, exact, true, false),
+                                               connect_power_variant(scene, exact, false, true), connect_power_variant(scene, exact, true, true));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis) {
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power) {
     if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
     if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
+    if (power) {
+        if (envs || !power->cdf || power->total == 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(connect_power_variant(a.scene, a.scene.exact != 0, textured, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene),
+                           s, a, *power);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }

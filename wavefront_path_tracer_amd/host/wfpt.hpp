@@ -381,6 +381,14 @@ class PathTracer {
         check(wfpt_sample_lights(ctx_, in9.data(), in9.size() / 9, out.data()));
         return out;
     }
+    // Light selection by power (WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_LIGHT_POWER, include/wfpt.h "Light selection by power"):
+    // (the emitting primitives in list order, the inclusive prefix sums of their integer weights)
+    std::pair<std::vector<uint32_t>, std::vector<uint64_t>> light_distribution() {
+        const size_t n = nee_light_count();
+        std::pair<std::vector<uint32_t>, std::vector<uint64_t>> t{std::vector<uint32_t>(n), std::vector<uint64_t>(n)};
+        check(wfpt_read_light_distribution(ctx_, t.first.data(), t.second.data()));
+        return t;
+    }
     // Environment next-event estimation (the three flags above | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment
     // next-event estimation"): the map as one more light of the connect pass, sampled in proportion to its radiance.
     void set_environment_share(float share) { check(wfpt_set_environment_share(ctx_, share)); }
