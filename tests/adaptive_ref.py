@@ -6,10 +6,10 @@ per-sample values to the active pixels alone, and `criterion` / `dilate_tile` / 
 IEEE f32 operation in the header's order, the dilation on the 64-bit word of one 8x8 tile."""
 import numpy as np
 
-f32 = np.float32
+from transport_ref import INACTIVE_PIXEL, BounceTables, f32
+
 u32 = np.uint32
 u64 = np.uint64
-INACTIVE_PIXEL = 0xFFFFFFFF
 DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}
 COL0, COL7 = 0x0101010101010101, 0x8080808080808080
 ALL = 0xFFFFFFFFFFFFFFFF
@@ -158,19 +158,15 @@ class Local:
         return r
 
 
-class Masked:
+class Masked(BounceTables):
     """An Oracle (or a wrapper around one) whose generate_rays obeys a mask: one bool per slab pixel, False = no ray. zero_only and drop
     are the two mutations of tests/test_adaptive_host.py: the masked rays zeroed but left with their pixel, and the masked slots dropped
     from the queue instead of kept. `bounce_table()` gives the last sample's rows (rays_in, hits, misses, shaded)."""
 
     def __init__(self, o, mask, zero_only=False, drop=False):
-        self.o = o
+        super().__init__(o)
         self.mask = np.asarray(mask, bool).reshape(-1)
         self.zero_only, self.drop = zero_only, drop
-        self.tables = []
-
-    def __getattr__(self, name):
-        return getattr(self.o, name)
 
     def local_pixel(self, pixel_idx):
         P = self.o.params
@@ -178,8 +174,7 @@ class Masked:
 
     def generate_rays(self, gx, gy, true_size=False):
         o = self.o
-        o.generate_rays(gx, gy, true_size)
-        self.tables.append([])
+        super().generate_rays(gx, gy, true_size)
         n = gx * gy * 64
         rays = o.rays(n)
         live = rays["pixel_idx"] != INACTIVE_PIXEL
@@ -198,19 +193,6 @@ class Masked:
         rays["pixel_idx"] = pix if self.zero_only else np.where(off, u32(INACTIVE_PIXEL), pix)
         o.write_rays(rays)
 
-    def extend(self, gx, gy):
-        rays_in = int(self.o.counters()[2])
-        self.o.extend(gx, gy)
-        c = self.o.counters()
-        self.tables[-1].append([rays_in, int(c[1]), int(c[0]), 0])
-
-    def shade(self, gx, gy):
-        self.tables[-1][-1][3] = 1
-        self.o.shade(gx, gy)
-
-    def bounce_table(self):
-        return np.array(self.tables[-1], "<u4").reshape(-1, 4)
-
 
 class Sums:
     """`accumulated`, the luminance moments and the sample counts of a flagged context"""
@@ -223,9 +205,7 @@ class Sums:
     def add(self, parts, active):
         """the samples of a restatement's render (its parts=True dict) under the mask they were rendered with, in sample order"""
         a = np.asarray(active, bool).reshape(-1)
-        emitted = parts.get("emitted")
-        for k in range(len(parts["image"])):
-            value = parts["image"][k] if emitted is None else parts["image"][k] + emitted[k]
+        for value in parts["value"]:
             L = luma(value)
             self.acc[a] = self.acc[a] + value[a]
             self.s1[a] = self.s1[a] + L[a]

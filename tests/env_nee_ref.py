@@ -1,15 +1,15 @@
 """numpy restatement of environment next-event estimation (WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment next-event estimation"):
-the map's sampling distribution (integer tables), the environment branch of the connect pass, and nee_ref.render_with_nee's loop with
-the branch choice, the two extra draws and the gated miss. float32 in the header's operation order, float64 only in the two selections;
-sin / cos are the oracle's own statement of the library's, the lookup is environment_ref's. Shadow rays are traced by a second oracle,
-as nee_ref.occluded does, with "any hit" in place of the window."""
+the map's sampling distribution (integer tables), the environment branch of the connect pass, and transport_ref.render with the branch
+choice, the two extra draws and the gated miss. float32 in the header's operation order, float64 only in the two selections; sin / cos
+are the oracle's own statement of the library's, the lookup is environment_ref's. Shadow rays are traced by a second oracle, as
+nee_ref.occluded does, with "any hit" in place of the window."""
 import numpy as np
 
-from denoise_ref import luma
-from environment_ref import env_lookup, normalize3
-from nee_ref import Lights, connect_draws, dot3, jenkins_hash, occluded, rng_next_float, sincos
+from environment_ref import env_lookup
+from nee_ref import Lights, jenkins_hash, occluded, rng_next_float, sincos
+from transport_ref import dot3, f32, render
 
-f32, f64, u32, u64 = np.float32, np.float64, np.uint32, np.uint64
+f64, u32, u64 = np.float64, np.uint32, np.uint64
 PI = f32(3.1415927)
 TWO_PI_SQ = f32(19.739209)
 
@@ -112,119 +112,13 @@ def connect_draws5(pixel_idx, frame, b):
     return out
 
 
-def render_with_env_nee(o, shadow, em, light, share=0.5, spp=1, first_frame=1, tx=None, parts=False, never_gate_miss=False):
-    """nee_ref.render_with_nee with the map as one more light. light: an EnvLight (its map also lights the ungated misses). With a black
-    map it is render_with_nee itself. never_gate_miss: the mutation that counts the map twice after a diffuse bounce."""
-    from nee_ref import render_with_nee
-    from oracle import oracle as O
-    if not light.dist.ok:
-        return render_with_nee(o, shadow, em, spp=spp, first_frame=first_frame, tx=tx, env=light.env,
-                               env_params={"intensity": light.intensity, "rotation": light.rotation}, parts=parts)
-    P = o.params
-    assert P.tile_world == 1, "the restatement keys the connect stream by the oracle's pixel index: whole frames only"
-    lights = Lights(em, tx)
-    p_eff = f32(share) if lights.n else f32(1)
-    gx = (o.width + 7) // 8
-    gy = (o.height + 7) // 8
-    prims = em.prims()
-    albedo = np.asarray(em.materials["albedo"][:, :3], f32)
-    acc = np.zeros((o.n_pixels, 3), f32)
-    s1, s2 = np.zeros(o.n_pixels, f32), np.zeros(o.n_pixels, f32)
-    images, emitteds, values = [], [], []
-    for k in range(spp):
-        frame = first_frame + k
-        o.set_frame(frame, 0)
-        o.reset_image()
-        o.set_counters([0, 0, gx * gy * 64])
-        o.generate_rays(gx, gy, True)
-        thr = o.image().copy()
-        emitted = np.zeros_like(thr)
-        flag = np.zeros(o.n_pixels, bool)
-        ex, ey = O.workgroup_size_64(gx * gy * 64)
-        for b in range(P.max_wavefronts):
-            n_rays = int(o.counters()[2])
-            o.extend(ex, ey)
-            c = o.counters()
-            n_miss, n_hit = int(c[0]), int(c[1])
-            rays = o.rays(max(n_rays, 1))
-            hits = o.hits(n_hit)
-            ridx = hits["ray_idx"].astype(np.int64)
-            hp = rays["pixel_idx"][ridx].astype(np.int64)
-            prim = hits["sphere_idx"].astype(np.int64)
-            if n_miss < P.miss_floor:
-                break
-            t = thr[hp]
-            e, emits = em.colour(prim)
-            org, d = rays["origin"][ridx, :3].astype(f32), rays["direction"][ridx, :3].astype(f32)
-            pt = org + hits["t"].astype(f32)[:, None] * d
-            if tx is not None:
-                tex, bound = tx.factor(prim, pt)
-                t = np.where(bound[:, None], t * tex, t)
-            add = emits & ~flag[hp]  # the emission pass, gated by the flag the step before left
-            emitted[hp[add]] = emitted[hp[add]] + t[add] * e[add]
-            t = np.where(emits[:, None], f32(0), t)
-            alb = albedo[prims["material_idx"][prim].astype(np.int64)]
-            # the connect pass
-            mclass = prims["material_type"][prim].astype(np.int64)
-            diffuse = ((mclass == 0) | (mclass > 2)) & ~emits
-            flag[hp[~diffuse]] = False
-            flag[hp[diffuse]] = True
-            dp, dpix = pt[diffuse], hp[diffuse]
-            if em.triangles is None:
-                nrm = np.stack(normalize3(*[dp[:, a] - em.spheres["center"][prim[diffuse], a] for a in range(3)]), 1).astype(f32)
-            else:
-                tr = em.triangles[prim[diffuse]]
-                a_, b_ = tr["e1"], tr["e2"]
-                nrm = np.stack(normalize3(a_[:, 1] * b_[:, 2] - a_[:, 2] * b_[:, 1], a_[:, 2] * b_[:, 0] - a_[:, 0] * b_[:, 2],
-                                          a_[:, 0] * b_[:, 1] - a_[:, 1] * b_[:, 0]), 1).astype(f32)
-            u0, u1, u2, u3, u4 = connect_draws5(dpix, frame, b)
-            to_env = np.ones(len(dp), bool) if not p_eff < 1 else u0 < p_eff
-            with np.errstate(all="ignore"):
-                base = t[diffuse] * alb[diffuse]
-                # the environment branch
-                ie = np.flatnonzero(to_env)
-                s = light.sample(nrm[ie], u1[ie], u2[ie], u3[ie], u4[ie], p_eff)
-                occ = np.zeros(len(ie), bool)
-                occ[s["lit"]] = any_hit(shadow, dp[ie][s["lit"]], s["w"][s["lit"]])
-                ok = s["lit"] & ~occ
-                contrib = (base[ie] * s["e"]) * s["G"][:, None]
-                emitted[dpix[ie][ok]] = emitted[dpix[ie][ok]] + contrib[ok]
-                # the emitter branch
-                il = np.flatnonzero(~to_env)
-                if len(il):
-                    q = f32(1) - p_eff
-                    sl = lights.sample(dp[il], nrm[il], (u0[il] - p_eff) / q, u1[il], u2[il])
-                    occ = np.zeros(len(il), bool)
-                    occ[sl["lit"]] = occluded(shadow, dp[il][sl["lit"]], sl["w"][sl["lit"]], sl["dist"][sl["lit"]])
-                    ok = sl["lit"] & ~occ
-                    contrib = ((base[il] * sl["e_q"]) * sl["G"][:, None]) / q
-                    emitted[dpix[il][ok]] = emitted[dpix[il][ok]] + contrib[ok]
-            thr[hp] = t * alb
-            midx = o.misses(n_miss).astype(np.int64)
-            mp = rays["pixel_idx"][midx].astype(np.int64)
-            md = rays["direction"][midx, :3].astype(f32)
-            factor = env_lookup(light.env, md, light.intensity, light.rotation)
-            if not never_gate_miss:  # the map is already counted where the pixel's connected flag is set
-                factor = np.where(flag[mp][:, None], f32(0), factor)
-            thr[mp] = thr[mp] * factor
-            o.set_counters([c[0], c[1], 0] + list(c[3:]))
-            sx, sy = O.workgroup_size_64(n_hit)
-            o.shade(sx, sy)
-            n_ext = int(o.counters()[2])
-            o.swap_ray_queues()
-            ex, ey = O.workgroup_size_64(n_ext)
-            o.set_counters([0, 0, n_ext])
-        value = thr + emitted
-        acc = acc + value
-        L = luma(value)
-        s1, s2 = s1 + L, s2 + L * L
-        if parts:
-            images.append(thr)
-            emitteds.append(emitted)
-            values.append(value)
-    if not parts:
-        return acc
-    return {"acc": acc, "image": np.stack(images), "emitted": np.stack(emitteds), "value": np.stack(values), "s1": s1, "s2": s2}
+def render_with_env_nee(o, shadow, em, light, share=0.5, spp=1, first_frame=1, tx=None, parts=False, never_gate_miss=False, termination=None):
+    """nee_ref.render_with_nee with the map as one more light (the loop's `env_connecting`: five draws, the map or an emitter by `share`,
+    the gated miss). light: an EnvLight (its map also lights the ungated misses). With a black map the loop connects to the emitters
+    alone and the map lights every miss: render_with_nee with that map. never_gate_miss: the mutation that counts the map twice after a
+    diffuse bounce."""
+    return render(o, shadow=shadow, em=em, tx=tx, lights=Lights(em, tx), env_light=light, share=share, termination=termination, spp=spp,
+                  first_frame=first_frame, parts=parts, never_gate_miss=never_gate_miss)
 
 
 # ---------------------------------------------------------------- scenes and maps

@@ -4,7 +4,7 @@ colour a miss. Every step is one IEEE f32 operation (numpy float32 rounds each o
 are the device's bits."""
 import numpy as np
 
-f32 = np.float32
+from transport_ref import f32, normalize3, render
 INV_2PI = f32(0.15915494)
 INV_PI = f32(0.31830988)
 TAN_PI_8 = f32(0.41421356)
@@ -12,13 +12,6 @@ ATAN_HALF = (f32(4.636476040e-01), f32(5.012158688e-09))  # atan(1/2), pi/2, pi 
 PI_2 = (f32(1.570796371e+00), f32(-4.371138829e-08))
 PI = (f32(3.141592741e+00), f32(-8.742277657e-08))
 C3, C2, C1, C0 = f32(8.05374449538e-2), f32(1.38776856032e-1), f32(1.99777106478e-1), f32(3.33329491539e-1)
-
-
-def normalize3(x, y, z):
-    x, y, z = (np.asarray(v, f32) for v in (x, y, z))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        inv = f32(1.0) / np.sqrt((x * x + y * y) + z * z)
-    return x * inv, y * inv, z * inv
 
 
 def atan2_(y, x):
@@ -81,48 +74,8 @@ def sky(dirs):
 
 
 def render_with_environment(o, env, params=None, spp=1, first_frame=1):
-    """The oracle's per-sample loop (orc_render_sample) driven from Python, with the map in place of its miss stage: generate_rays, then per
-    wavefront extend, the miss_floor exit, shade, and -- instead of miss -- the pixel and direction of every miss are recorded; swap. Nothing
-    touches a pixel's throughput after its miss within a sample, so the recorded pixels of image() are multiplied by the lookup at the end
-    of the sample, and the sample is added to a float32 accumulator. Returns the accumulated image (n_pixels x 3). env=None: the gradient sky
-    (the oracle's own result)."""
-    from oracle import oracle as O
-    params = dict(params or {})
-    intensity, rotation = params.get("intensity", 1.0), params.get("rotation", 0.0)
-    p = o.params
-    gx = (o.width + 7) // 8
-    gy = ((o.height + 7) // 8 - p.tile_rank + p.tile_world - 1) // p.tile_world
-    acc = np.zeros((o.n_pixels, 3), f32)
-    for k in range(spp):
-        o.set_frame(first_frame + k, 0)
-        o.reset_image()
-        o.set_counters([0, 0, gx * gy * 64])
-        o.generate_rays(gx, gy, True)
-        ex, ey = O.workgroup_size_64(gx * gy * 64)
-        pix, dirs = [], []
-        for _ in range(p.max_wavefronts):
-            n_rays = int(o.counters()[2])
-            o.extend(ex, ey)
-            c = o.counters()
-            n_miss, n_hit = int(c[0]), int(c[1])
-            if n_miss < p.miss_floor:
-                break
-            if n_miss:
-                rays = o.rays(max(n_rays, 1))
-                idx = o.misses(n_miss)
-                pix.append(rays["pixel_idx"][idx].astype(np.int64))
-                dirs.append(rays["direction"][idx, :3].astype(f32))
-            o.set_counters([c[0], c[1], 0] + list(c[3:]))
-            sx, sy = O.workgroup_size_64(n_hit)
-            o.shade(sx, sy)
-            n_ext = int(o.counters()[2])
-            o.swap_ray_queues()
-            ex, ey = O.workgroup_size_64(n_ext)
-            o.set_counters([0, 0, n_ext])
-        img = o.image().copy()
-        if pix:
-            px, d = np.concatenate(pix), np.concatenate(dirs)
-            f = sky(d) if env is None else env_lookup(env, d, intensity, rotation)
-            img[px] = img[px] * f
-        acc = acc + img
-    return acc
+    """transport_ref.render with the map in place of the oracle's miss stage: at every miss the pixel's throughput is multiplied by the
+    lookup (nothing touches it afterwards within the sample), and the samples are added to a float32 accumulator. The wrapper names no
+    scene, so shade's albedo is the oracle's own. Returns the accumulated image (n_pixels x 3). env=None: the gradient sky (the oracle's
+    own result)."""
+    return render(o, env=env, env_params=params, spp=spp, first_frame=first_frame)

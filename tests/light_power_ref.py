@@ -1,16 +1,14 @@
 """numpy restatement of light selection by power (WFPT_FLAG_LIGHT_POWER, include/wfpt.h "Light selection by power") on nee_ref's and
-mis_ref's pieces, none of which is edited: PowerLights is nee_ref.Lights with the light list's integer distribution (tables) and the
-selection by it (sample: steps 3 and 4 with nfi = f32(total) / f32(k) in nf's place); the weights of mis_ref take nfi through a view of
-the lights whose `n` is the per-sample nfi; and the two render loops run as they stand with these pieces put in their modules' names for
-the length of the call. Every step is one IEEE operation in the header's order (f64 in the selection alone)."""
-import contextlib
-
+mis_ref's pieces: PowerLights is nee_ref.Lights with the light list's integer distribution (tables), the selection by it (sample: steps 3
+and 4 with nfi = f32(total) / f32(k) in nf's place), and the densities and the hit weight with nfi in nf's place; transport_ref.render and
+mis_ref's row samplers take it as their light list. Every step is one IEEE operation in the header's order (f64 in the selection alone)."""
 import numpy as np
 
 import mis_ref as M
 import nee_ref as N
 from denoise_ref import luma
-from nee_ref import PI, dot3, f32
+from nee_ref import PI
+from transport_ref import dot3, f32, render, triangle_normal_area
 
 u64 = np.uint64
 
@@ -21,7 +19,7 @@ def light_areas(em, prim):
         if em.triangles is None:
             ra = np.abs(em.spheres[prim]["radius"].astype(f32))
             return ((f32(4) * PI) * (ra * ra)).astype(f32)
-        return M.triangle_normal_area(em.triangles[prim])[1].astype(f32)
+        return triangle_normal_area(em.triangles[prim])[1].astype(f32)
 
 
 class PowerLights(N.Lights):
@@ -90,8 +88,7 @@ class PowerLights(N.Lights):
         w = nf if self.uniform_weight else nfi
         with np.errstate(all="ignore"):
             # G = (((cos_s * cos_l) * A) * nfi) / (pi * dist2), from the same cos_s, cos_l, A, dist2 (recomputed as mis_ref does)
-            area = light_areas(self.em, s["prim"])
-            nl = self._normals(s)
+            nl, area = self.normal_area(s["prim"], s["q"])
             v = s["q"] - np.asarray(p, f32)
             dist2 = dot3(v, v)
             cos_s, cos_l = dot3(np.asarray(n, f32), s["w"]), np.abs(dot3(nl, s["w"]))
@@ -99,12 +96,22 @@ class PowerLights(N.Lights):
         s["nfi"] = nfi
         return s
 
-    def _normals(self, s):
-        em = self.em
-        if em.triangles is None:
-            sp = em.spheres[s["prim"]]
-            return (s["q"] - sp["center"][:, :3].astype(f32)) / np.abs(sp["radius"].astype(f32))[:, None]
-        return M.triangle_normal_area(em.triangles[s["prim"]])[0]
+    def densities(self, p, s, nf=None):
+        """nee_ref.Lights.densities with pl = dist2 / ((cos_l * A) * nfi), the sample's own nfi"""
+        return super().densities(p, s, s["nfi"] if self.has_distribution else nf)
+
+    def hit_weight(self, o, ph, d, prim, pb_of_len=None, with_nf=True, nf=None):
+        """nee_ref.Lights.hit_weight with nfi = f32(total) / f32(prim_k[prim]) in nf's place; wb = 1 and pl = 0 where that k is 0."""
+        if not self.has_distribution:
+            return super().hit_weight(o, ph, d, prim, pb_of_len, with_nf, nf)
+        prim = np.asarray(prim, np.int64)
+        k = self.prim_k[prim]
+        with np.errstate(all="ignore"):
+            nfi = (np.full(len(prim), self.total, u64).astype(f32) / k.astype(f32)).astype(f32)
+        r = super().hit_weight(o, ph, d, prim, pb_of_len, with_nf, nfi)
+        r["pl"] = np.where(k == 0, f32(0), r["pl"]).astype(f32)
+        r["wb"] = np.where(k == 0, f32(1), r["wb"]).astype(f32)
+        return r
 
     def sample_rows(self, shadow, rows):
         """wfpt_sample_lights for rows (k, 9): (k, 8) of (q, primitive, e_q G, occluded)."""
@@ -122,64 +129,20 @@ class PowerLights(N.Lights):
         return out, s
 
 
-class _WithNf:
-    """A view of lights whose `n` -- what mis_ref's weights turn into nf by f32(lights.n) -- is the per-row nfi."""
-
-    def __init__(self, lights, nfi):
-        self.em, self.list, self.tx, self.n = lights.em, lights.list, lights.tx, np.asarray(nfi, f32)
-
-
-_light_densities, _hit_weight = M.light_densities, M.hit_weight
-
-
-def light_densities(lights, p, s):
-    """mis_ref.light_densities with pl = dist2 / ((cos_l * A) * nfi)."""
-    if not getattr(lights, "has_distribution", False):
-        return _light_densities(lights, p, s)
-    return _light_densities(_WithNf(lights, s["nfi"]), p, s)
-
-
-def hit_weight(lights, o, ph, d, prim, pb_of_len=None, with_nf=True):
-    """mis_ref.hit_weight with nfi = f32(total) / f32(prim_k[prim]) in nf's place; wb = 1 and pl = 0 where that k is 0."""
-    if not getattr(lights, "has_distribution", False):
-        return _hit_weight(lights, o, ph, d, prim, pb_of_len=pb_of_len, with_nf=with_nf)
-    prim = np.asarray(prim, np.int64)
-    k = lights.prim_k[prim]
-    with np.errstate(all="ignore"):
-        nfi = (np.full(len(prim), lights.total, u64).astype(f32) / k.astype(f32)).astype(f32)
-    r = _hit_weight(_WithNf(lights, nfi), o, ph, d, prim, pb_of_len=pb_of_len, with_nf=with_nf)
-    r["pl"] = np.where(k == 0, f32(0), r["pl"]).astype(f32)
-    r["wb"] = np.where(k == 0, f32(1), r["wb"]).astype(f32)
-    return r
-
-
-@contextlib.contextmanager
-def _power_pieces():
-    """nee_ref's and mis_ref's loops look their pieces up by name at each call: for the length of one call the names mean these."""
-    saved = (N.Lights, M.light_densities, M.hit_weight)
-    N.Lights, M.light_densities, M.hit_weight = PowerLights, light_densities, hit_weight
-    try:
-        yield
-    finally:
-        N.Lights, M.light_densities, M.hit_weight = saved
-
-
-def render_with_power(o, shadow, em, mis=False, **kw):
-    """nee_ref.render_with_nee (mis: mis_ref.render_with_mis) of a WFPT_FLAG_LIGHT_POWER context; the keywords are theirs."""
-    with _power_pieces():
-        return (M.render_with_mis if mis else N.render_with_nee)(o, shadow, em, **kw)
+def render_with_power(o, shadow, em, mis=False, tx=None, **kw):
+    """nee_ref.render_with_nee (mis: mis_ref.render_with_mis) of a WFPT_FLAG_LIGHT_POWER context: transport_ref.render with PowerLights
+    as its light list; the other keywords are theirs."""
+    return render(o, shadow=shadow, em=em, tx=tx, lights=PowerLights(em, tx), weigh=mis, **kw)
 
 
 def sample_rows_mis(lights, shadow, rows):
-    """wfpt_sample_lights_mis on a flagged context: mis_ref.sample_rows with these pieces."""
-    with _power_pieces():
-        return M.sample_rows(lights, shadow, rows)
+    """wfpt_sample_lights_mis on a flagged context: mis_ref.sample_rows, with lights' own densities."""
+    return M.sample_rows(lights, shadow, rows)
 
 
 def hit_weight_rows(lights, rows):
-    """wfpt_mis_hit_weight on a flagged context: mis_ref.hit_weight_rows with these pieces."""
-    with _power_pieces():
-        return M.hit_weight_rows(lights, rows)
+    """wfpt_mis_hit_weight on a flagged context: mis_ref.hit_weight_rows, with lights' own weight."""
+    return M.hit_weight_rows(lights, rows)
 
 
 # ---------------------------------------------------------------- the payoff scene

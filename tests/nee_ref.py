@@ -1,16 +1,15 @@
-"""numpy float32 restatement of next-event estimation (WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): emission_ref.render_with_emission
-with the per-pixel connected flag, the gated emission add, and the connect pass between the emission pass and shade's albedo. Every step
-is one IEEE f32 operation in the header's order (sin / cos are the oracle's own statement of the library's), so the results are the
-device's bits. Occlusion comes from the oracle itself: a second Oracle over the same scene traces the shadow rays (write_rays, extend) and
-its closest t is compared with dist * 0.999 -- no traversal is rewritten here."""
+"""numpy float32 restatement of next-event estimation (WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): the connect pass's random
+stream, the light list with its sampler, densities and weights, and the occlusion test; transport_ref.render runs them with the per-pixel
+connected flag, the gated emission add, and the connect pass between the emission pass and shade's albedo. Every step is one IEEE f32
+operation in the header's order (sin / cos are the oracle's own statement of the library's), so the results are the device's bits.
+Occlusion comes from the oracle itself: a second Oracle over the same scene traces the shadow rays (write_rays, extend) and its closest t
+is compared with dist * 0.999 -- no traversal is rewritten here."""
 import ctypes as C
 
 import numpy as np
 
-from denoise_ref import luma
-from environment_ref import env_lookup, normalize3, sky
+from transport_ref import dot3, f32, render, triangle_normal_area
 
-f32 = np.float32
 u32 = np.uint32
 PI = f32(3.1415927)
 
@@ -54,10 +53,6 @@ def sincos(x):
     return s, c
 
 
-def dot3(a, b):
-    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-
-
 class Lights:
     """The light list of an emission_ref.Emission: the primitives whose material emits, in primitive order; tx (texture_ref.Textures or None)
     modulates a textured light's colour at the sampled point."""
@@ -87,17 +82,13 @@ class Lights:
                 r = np.sqrt(np.fmax(f32(0), f32(1) - z * z))
                 sn, cs = sincos((f32(2) * PI) * u2)
                 q = np.stack([c[:, 0] + ra * (r * cs), c[:, 1] + ra * (r * sn), c[:, 2] + ra * z], 1)
-                nl = (q - c) / ra[:, None]
-                area = (f32(4) * PI) * (ra * ra)
             else:
                 t = em.triangles[prim]
                 v0, e1, e2 = t["v0"].astype(f32), t["e1"].astype(f32), t["e2"].astype(f32)
                 su = np.sqrt(u1)
                 b1, b2 = f32(1) - su, u2 * su
                 q = (v0 + b1[:, None] * e1) + b2[:, None] * e2
-                cr = [e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]]
-                nl = np.stack(normalize3(*cr), 1).astype(f32)
-                area = f32(0.5) * np.sqrt((cr[0] * cr[0] + cr[1] * cr[1]) + cr[2] * cr[2])
+            nl, area = self.normal_area(prim, q)
             v = q - p
             dist2 = dot3(v, v)
             dist = np.sqrt(dist2)
@@ -111,6 +102,51 @@ class Lights:
             lit = (area > 0) & (dist2 > 0) & (cos_s > 0) & (cos_l > 0)
         return {"q": q.astype(f32), "prim": prim, "w": w.astype(f32), "dist": dist.astype(f32), "e_q": e_q.astype(f32), "G": G.astype(f32),
                 "lit": lit}
+
+    def normal_area(self, prim, q):
+        """(nl (k, 3), A (k,)) of the lights prim (k,) at their points q (k, 3), by the operations sample() uses: the same bits."""
+        em = self.em
+        with np.errstate(all="ignore"):
+            if em.triangles is not None:
+                return triangle_normal_area(em.triangles[prim])
+            sp = em.spheres[prim]
+            ra = np.abs(sp["radius"].astype(f32))
+            return (q - sp["center"][:, :3].astype(f32)) / ra[:, None], (f32(4) * PI) * (ra * ra)
+
+    def densities(self, p, s, nf=None):
+        """(pl, pb, wl) of connect samples s = self.sample(p, n, ...) with s["n"] = n -- step 5 of "Multiple importance sampling". cos_s,
+        cos_l, A and dist2 are recomputed (sample() does not return them). nf: the light count per sample, where it is not self.n."""
+        nf = f32(self.n) if nf is None else nf
+        with np.errstate(all="ignore"):
+            nl, area = self.normal_area(s["prim"], s["q"])
+            v = s["q"] - np.asarray(p, f32)
+            dist2 = dot3(v, v)
+            cos_s, cos_l = dot3(np.asarray(s["n"], f32), s["w"]), np.abs(dot3(nl, s["w"]))
+            pb = cos_s / PI
+            pl = dist2 / ((cos_l * area) * nf)
+            wl = pl / (pl + pb)
+        return pl.astype(f32), pb.astype(f32), wl.astype(f32)
+
+    def hit_weight(self, o, ph, d, prim, pb_of_len=None, with_nf=True, nf=None):
+        """The emission pass's weight for hits at ph on emitter `prim` (k,) of rays that left o with direction d (not normalised): a dict of
+        pl, pb, wb, cos_l (k,), the header's operation order. pb_of_len / with_nf: the mutations of tests/test_mis_host.py. nf: the light
+        count per hit, where it is not self.n."""
+        o, ph, d = np.asarray(o, f32), np.asarray(ph, f32), np.asarray(d, f32)
+        prim = np.asarray(prim, np.int64)
+        nf = f32(1) if not with_nf else f32(self.n) if nf is None else nf
+        with np.errstate(all="ignore"):
+            v = ph - o
+            dist2 = dot3(v, v)
+            dist = np.sqrt(dist2)
+            w = v / dist[:, None]
+            nl, area = self.normal_area(prim, ph)
+            cos_l = np.abs(dot3(nl, w))
+            ln = np.sqrt(dot3(d, d))
+            pb = ((f32(0.5) * ln) / PI) if pb_of_len is None else pb_of_len(ln)
+            ok = (area > 0) & (dist2 > 0) & (cos_l > 0)
+            pl = np.where(ok, dist2 / ((cos_l * area) * nf), f32(0)).astype(f32)
+            wb = np.where(ok, pb / (pb + pl), f32(1)).astype(f32)
+        return {"pl": pl, "pb": pb.astype(f32), "wb": wb, "cos_l": cos_l.astype(f32)}
 
 
 def occluded(shadow, p, w, dist):
@@ -139,103 +175,14 @@ def occluded(shadow, p, w, dist):
 
 
 def render_with_nee(o, shadow, em, spp=1, first_frame=1, tx=None, env=None, env_params=None, parts=False, never_set_flag=False,
-                    never_clear_flag=False):
-    """emission_ref.render_with_emission with the connect pass. o: the Oracle that renders; shadow: a second Oracle over the same scene
-    (any viewport with at least as many ray slots) that traces the shadow rays. With no light it is render_with_emission itself.
+                    never_clear_flag=False, termination=None):
+    """transport_ref.render with the connect pass to the emitters (three draws) and the gated emission pass. o: the Oracle that renders;
+    shadow: a second Oracle over the same scene (any viewport with at least as many ray slots) that traces the shadow rays. With no light
+    the loop selects no connect pass and the emission pass `all`: emission_ref.render_with_emission.
     never_set_flag / never_clear_flag: the two mutations of tests/test_nee_host.py (a diffuse hit leaves the flag 0: lights found after a
     diffuse bounce are counted twice; a non-diffuse hit leaves the flag as it was: a lamp seen in a mirror after a diffuse hit goes black)."""
-    from oracle import oracle as O
-    P = o.params
-    assert P.tile_world == 1, "the restatement keys the connect stream by the oracle's pixel index: whole frames only"
-    lights = Lights(em, tx)
-    gx = (o.width + 7) // 8
-    gy = (o.height + 7) // 8
-    prims = em.prims()
-    albedo = np.asarray(em.materials["albedo"][:, :3], f32)
-    ep = dict(env_params or {})
-    acc = np.zeros((o.n_pixels, 3), f32)
-    s1, s2 = np.zeros(o.n_pixels, f32), np.zeros(o.n_pixels, f32)
-    images, emitteds = [], []
-    for k in range(spp):
-        frame = first_frame + k
-        o.set_frame(frame, 0)
-        o.reset_image()
-        o.set_counters([0, 0, gx * gy * 64])
-        o.generate_rays(gx, gy, True)
-        thr = o.image().copy()
-        emitted = np.zeros_like(thr)
-        flag = np.zeros(o.n_pixels, bool)
-        ex, ey = O.workgroup_size_64(gx * gy * 64)
-        for b in range(P.max_wavefronts):
-            n_rays = int(o.counters()[2])
-            o.extend(ex, ey)
-            c = o.counters()
-            n_miss, n_hit = int(c[0]), int(c[1])
-            rays = o.rays(max(n_rays, 1))
-            hits = o.hits(n_hit)
-            ridx = hits["ray_idx"].astype(np.int64)
-            hp = rays["pixel_idx"][ridx].astype(np.int64)
-            prim = hits["sphere_idx"].astype(np.int64)
-            if n_miss < P.miss_floor:
-                break
-            t = thr[hp]
-            e, emits = em.colour(prim)
-            org, d = rays["origin"][ridx, :3].astype(f32), rays["direction"][ridx, :3].astype(f32)
-            pt = org + hits["t"].astype(f32)[:, None] * d  # sh:91, per component o + t d
-            if tx is not None:  # the texture pass
-                tex, bound = tx.factor(prim, pt)
-                t = np.where(bound[:, None], t * tex, t)
-            # the emission pass: thr * e only where the pixel's connected flag is 0 (always, with no light list)
-            add = emits & ~flag[hp] if lights.n else emits
-            emitted[hp[add]] = emitted[hp[add]] + t[add] * e[add]
-            t = np.where(emits[:, None], f32(0), t)
-            alb = albedo[prims["material_idx"][prim].astype(np.int64)]
-            if lights.n:  # the connect pass
-                mclass = prims["material_type"][prim].astype(np.int64)
-                diffuse = ((mclass == 0) | (mclass > 2)) & ~emits
-                if not never_clear_flag:
-                    flag[hp[~diffuse]] = False
-                if not never_set_flag:
-                    flag[hp[diffuse]] = True
-                dp, dpix = pt[diffuse], hp[diffuse]
-                if em.triangles is None:
-                    nrm = np.stack(normalize3(*[dp[:, a] - em.spheres["center"][prim[diffuse], a] for a in range(3)]), 1).astype(f32)
-                else:
-                    tr = em.triangles[prim[diffuse]]
-                    a_, b_ = tr["e1"], tr["e2"]
-                    nrm = np.stack(normalize3(a_[:, 1] * b_[:, 2] - a_[:, 2] * b_[:, 1], a_[:, 2] * b_[:, 0] - a_[:, 0] * b_[:, 2],
-                                              a_[:, 0] * b_[:, 1] - a_[:, 1] * b_[:, 0]), 1).astype(f32)
-                u0, u1, u2 = connect_draws(dpix, frame, b)
-                s = lights.sample(dp, nrm, u0, u1, u2)
-                lit = s["lit"]
-                occ = np.zeros(len(dp), bool)
-                occ[lit] = occluded(shadow, dp[lit], s["w"][lit], s["dist"][lit])
-                ok = lit & ~occ
-                with np.errstate(all="ignore"):
-                    contrib = ((t[diffuse] * alb[diffuse]) * s["e_q"]) * s["G"][:, None]
-                emitted[dpix[ok]] = emitted[dpix[ok]] + contrib[ok]
-            thr[hp] = t * alb
-            midx = o.misses(n_miss).astype(np.int64)
-            mp = rays["pixel_idx"][midx].astype(np.int64)
-            md = rays["direction"][midx, :3].astype(f32)
-            thr[mp] = thr[mp] * (sky(md) if env is None else env_lookup(env, md, ep.get("intensity", 1.0), ep.get("rotation", 0.0)))
-            o.set_counters([c[0], c[1], 0] + list(c[3:]))
-            sx, sy = O.workgroup_size_64(n_hit)
-            o.shade(sx, sy)
-            n_ext = int(o.counters()[2])
-            o.swap_ray_queues()
-            ex, ey = O.workgroup_size_64(n_ext)
-            o.set_counters([0, 0, n_ext])
-        value = thr + emitted
-        acc = acc + value
-        L = luma(value)
-        s1, s2 = s1 + L, s2 + L * L
-        if parts:
-            images.append(thr)
-            emitteds.append(emitted)
-    if not parts:
-        return acc
-    return {"acc": acc, "image": np.stack(images), "emitted": np.stack(emitteds), "s1": s1, "s2": s2}
+    return render(o, shadow=shadow, em=em, tx=tx, env=env, env_params=env_params, lights=Lights(em, tx), termination=termination, spp=spp,
+                  first_frame=first_frame, parts=parts, never_set_flag=never_set_flag, never_clear_flag=never_clear_flag)
 
 
 # ---------------------------------------------------------------- the lamp scene

@@ -1,17 +1,15 @@
 """numpy float32 restatement of path termination (WFPT_FLAG_RETIRE, include/wfpt.h "Path termination"), on top of the existing
-restatements so that textures, emission, NEE and MIS compose: `Retiring` wraps the Oracle a restatement drives (render_with_emission,
-render_with_nee, render_with_mis, render_with_env_nee, render_with_env_mis, render_with_textures) and adds the termination step to
-its shade step. Every restatement keeps the per-pixel throughput in the array it copies from o.image() after generate_rays and updates it
-in place, forms t' = thr * albedo before it calls o.shade, and swaps the queues right after: the wrapper hands out that array, applies
-steps 1-3 to it when shade is called and, after the queue swap, reads the rays, sets pixel_idx = INACTIVE_PIXEL on the retired ones and
-writes them back with write_rays -- the oracle's extend skips such rays. Every step is one IEEE f32 operation in the header's order."""
+restatements so that textures, emission, NEE and MIS compose: transport_ref.render takes a `Retiring` as its termination= (every
+render_with_* passes the keyword on). Before the shade of every wavefront b with b + 1 < max_wavefronts (step 1), with t' = thr * albedo
+formed, the loop hands it thr and the hits' pixels; `retire` applies steps 2 and 3 in place, and after the queue swap the loop sets
+pixel_idx = INACTIVE_PIXEL on the retired hits' extension rays and writes them back with write_rays -- the oracle's extend skips such
+rays. Every step is one IEEE f32 operation in the header's order."""
 import numpy as np
 
 from nee_ref import jenkins_hash, rng_next_float
+from transport_ref import BounceTables, f32
 
-f32 = np.float32
 u32 = np.uint32
-INACTIVE_PIXEL = 0xFFFFFFFF
 NO_ROULETTE = 0xFFFFFFFF
 DEAD, ROULETTE, SURVIVES = 0, 1, 2
 DEFAULTS = {"roulette_start": 3, "q_min": 0.05}
@@ -93,84 +91,28 @@ def lamp_room_inputs(orc, w, h):
     return sp, mt, nodes, cam, ip, vw
 
 
-class _Handed(np.ndarray):
-    """o.image() of a wrapped oracle: the copy a restatement takes of it is the throughput array it goes on to update in place"""
-    owner = None
-
-    def copy(self, *a, **k):
-        c = np.array(self, f32)
-        if self.owner is not None:
-            self.owner.thr = c
-        return c
-
-
-class Retiring:
-    """An Oracle with the termination step in its shade step. o: the Oracle; roulette_start, q_min: the context's parameters; no_divide,
-    keep_retired: decide()'s mutations. After a render, `tables` holds one bounce table per sample, rows (rays_in, hits, misses, shaded)
-    as wfpt_read_bounce_table gives them, and `retired` the number of hits retired per sample and wavefront."""
+class Retiring(BounceTables):
+    """The termination step of a context, as transport_ref.render takes it (termination=), around the Oracle it renders with (o, whose
+    bounce tables it keeps). roulette_start, q_min: the context's parameters; no_divide, keep_retired: decide()'s mutations. After a
+    render, `tables` holds one bounce table per sample, rows (rays_in, hits, misses, shaded) as wfpt_read_bounce_table gives them, and
+    `retired` the number of hits retired per sample and wavefront."""
 
     def __init__(self, o, roulette_start=DEFAULTS["roulette_start"], q_min=DEFAULTS["q_min"], no_divide=False, keep_retired=False):
-        self.o = o
+        super().__init__(o)
         self.roulette_start, self.q_min = roulette_start, q_min
         self.no_divide, self.keep_retired = no_divide, keep_retired
-        self.thr = None
-        self.frame, self.b = 0, 0
-        self.gone = None
-        self.tables, self.retired = [], []
-
-    def __getattr__(self, name):
-        return getattr(self.o, name)
-
-    def set_frame(self, frame, sample_number=0):
-        self.frame = int(frame)
-        self.o.set_frame(frame, sample_number)
+        self.retired = []
 
     def generate_rays(self, gx, gy, true_size=False):
-        self.o.generate_rays(gx, gy, true_size)
-        self.b, self.thr, self.gone = -1, None, None
-        self.tables.append([])
+        super().generate_rays(gx, gy, true_size)
         self.retired.append([])
 
-    def image(self):
-        a = self.o.image().view(_Handed)
-        a.owner = self
-        return a
-
-    def extend(self, gx, gy):
-        rays_in = int(self.o.counters()[2])
-        self.o.extend(gx, gy)
-        self.b += 1
-        c = self.o.counters()
-        self.tables[-1].append([rays_in, int(c[1]), int(c[0]), 0])
-
-    def shade(self, gx, gy):
-        o, P = self.o, self.o.params
-        self.tables[-1][-1][3] = 1
-        self.gone = None
-        if self.b + 1 < P.max_wavefronts:  # step 1
-            assert self.thr is not None, "the restatement did not copy o.image() after generate_rays"
-            n_hit = int(o.counters()[1])
-            hits = o.hits(n_hit)
-            rays = o.rays(max(self.tables[-1][-1][0], 1))
-            hp = rays["pixel_idx"][hits["ray_idx"].astype(np.int64)].astype(np.int64)
-            out, verdict, _, _ = decide(self.thr[hp], hp, self.frame, self.b, self.roulette_start, self.q_min, no_divide=self.no_divide,
-                                        keep_retired=self.keep_retired)
-            self.thr[hp] = out
-            self.gone = verdict != SURVIVES  # by hit index = the extension ray's slot
-            self.retired[-1].append(int(self.gone.sum()))
-        o.shade(gx, gy)
-
-    def swap_ray_queues(self):
-        o = self.o
-        o.swap_ray_queues()
-        if self.gone is not None and self.gone.any():
-            n_ext = int(o.counters()[2])
-            rays = o.rays(n_ext)
-            assert n_ext == len(self.gone)
-            rays["pixel_idx"][self.gone] = INACTIVE_PIXEL
-            o.write_rays(rays)
-        self.gone = None
-
-    def bounce_table(self):
-        """of the last sample"""
-        return np.array(self.tables[-1], "<u4").reshape(-1, 4)
+    def retire(self, thr, hp, frame, b):
+        """Steps 2 and 3 on thr (n_pixels, 3), in place, for the hits of wavefront b at pixels hp -- the loop calls it where step 1 allows,
+        after thr <- thr * albedo. Returns the mask of the retired hits."""
+        out, verdict, _, _ = decide(thr[hp], hp, frame, b, self.roulette_start, self.q_min, no_divide=self.no_divide,
+                                    keep_retired=self.keep_retired)
+        thr[hp] = out
+        gone = verdict != SURVIVES
+        self.retired[-1].append(int(gone.sum()))
+        return gone

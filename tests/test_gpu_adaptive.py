@@ -119,8 +119,9 @@ class Ref:
             sp, mt, colours = shirley_scene(O)
             inner = O.shirley_oracle(W_, H_, **self.kw())
             if case == "retire":
-                o = A.Masked(RR.Retiring(inner, roulette_start=RETIRE[0], q_min=RETIRE[1]), mask)
-                r = M.render_with_mis(o, O.shirley_oracle(W_, H_), E.Emission(colours, spheres=sp, materials=mt), **common)
+                retiring = RR.Retiring(inner, roulette_start=RETIRE[0], q_min=RETIRE[1])
+                o = A.Masked(retiring, mask)
+                r = M.render_with_mis(o, O.shirley_oracle(W_, H_), E.Emission(colours, spheres=sp, materials=mt), termination=retiring, **common)
             elif case == "tex":
                 slots, bind = shirley_textures(O, sp, mt)
                 o = A.Masked(inner, mask)

@@ -207,7 +207,7 @@ def test_textured_light_and_retire(W, O, mis):
     light(pt, colours)
     pt.render(spp)
     o = RR.Retiring(O.shirley_oracle(W_, H_, max_wavefronts=MAXW), roulette_start=1, q_min=0.25)
-    r = P.render_with_power(o, O.shirley_oracle(W_, H_), em, mis=mis, spp=spp, parts=True)
+    r = P.render_with_power(o, O.shirley_oracle(W_, H_), em, mis=mis, spp=spp, parts=True, termination=o)
     assert_bits(pt.accumulated(), r["acc"], f"retire, mis {mis}")
     assert sum(map(sum, o.retired)) > 0
     pt.close()

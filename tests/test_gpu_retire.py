@@ -71,15 +71,15 @@ def reference(O, case, rng, params):
             inputs = V.ground_inputs(O, W_, H_, occluder=True, mirror=True, lamp=True)
             em = E.Emission({1: LAMP_E}, spheres=inputs[0], materials=inputs[1])
             o = wrapped(make_oracle(O, inputs, W_, H_, max_wavefronts=WAVEFRONTS, miss_floor=0, rng_mode=rng), params)
-            r = X.render_with_env_mis(o, make_oracle(O, inputs, W_, H_), em, env_light(V.sun_map()), spp=SPP, parts=True)
+            r = X.render_with_env_mis(o, make_oracle(O, inputs, W_, H_), em, env_light(V.sun_map()), spp=SPP, parts=True, termination=o)
         else:
             sp, mt, colours = shirley_scene(O)
             em = E.Emission(colours if case != "alone" else {}, spheres=sp, materials=mt)
             o = wrapped(O.shirley_oracle(W_, H_, max_wavefronts=WAVEFRONTS, rng_mode=rng), params)
             if case == "mis":
-                r = M.render_with_mis(o, O.shirley_oracle(W_, H_), em, spp=SPP, parts=True)
+                r = M.render_with_mis(o, O.shirley_oracle(W_, H_), em, spp=SPP, parts=True, termination=o)
             else:
-                r = E.render_with_emission(o, em, spp=SPP, parts=True)
+                r = E.render_with_emission(o, em, spp=SPP, parts=True, termination=o)
         _refs[key] = (r, o.bounce_table(), o.retired)
     return _refs[key]
 
@@ -140,7 +140,7 @@ def mesh_reference(O, rng):
         tris, mt, nodes, cam, ip, vw = mesh_inputs(O, w, h)
         o = wrapped(O.Oracle(w, h, np.zeros(1, O.SPHERE), mt, nodes, cam, ip, vw, triangles=tris, max_wavefronts=WAVEFRONTS, rng_mode=rng,
                              miss_floor=16), (1, 0.25))
-        r = E.render_with_emission(o, E.Emission({1: (2.0, 1.0, 0.5)}, triangles=tris, materials=mt), spp=SPP, parts=True)
+        r = E.render_with_emission(o, E.Emission({1: (2.0, 1.0, 0.5)}, triangles=tris, materials=mt), spp=SPP, parts=True, termination=o)
         _mesh[rng] = (r, o.bounce_table(), o.retired)
     return _mesh[rng]
 
@@ -198,7 +198,8 @@ def test_open_furnace_leaves_the_loop_at_row_one(W, O, loop):
     e = np.asarray(COLOUR, F)
     if not _open_furnace:
         o = wrapped(O.shirley_oracle(w, h, max_wavefronts=WAVEFRONTS, miss_floor=128), (NO, 0.05))
-        r = E.render_with_emission(o, E.Emission({m: COLOUR for m in range(len(mt))}, spheres=sp, materials=mt), spp=SPP, parts=True)
+        r = E.render_with_emission(o, E.Emission({m: COLOUR for m in range(len(mt))}, spheres=sp, materials=mt), spp=SPP, parts=True,
+                                   termination=o)
         _open_furnace.update(r=r, table=o.bounce_table())
     r, table = _open_furnace["r"], _open_furnace["table"]
     for k in range(SPP):

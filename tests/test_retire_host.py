@@ -120,7 +120,7 @@ def test_draw_is_equal_across_rng_modes(orc):
     seen = []
     for rng in (0, 1):
         o = RR.Retiring(make_oracle(orc, inputs, w, h, max_wavefronts=3, miss_floor=0, rng_mode=rng), roulette_start=0, q_min=0.9)
-        r = E.render_with_emission(o, em, spp=2, parts=True)
+        r = E.render_with_emission(o, em, spp=2, parts=True, termination=o)
         seen.append((o.tables[0][1], o.tables[1][1], r["image"]))
     assert seen[0][0] == seen[1][0] and seen[0][1] == seen[1][1], "rays_in, hits of wavefront 1: the same paths were retired at b = 0"
     assert seen[0][0][0] > seen[0][0][1] + seen[0][0][2], "nothing was retired"
@@ -142,7 +142,7 @@ def test_retiring_dead_paths_changes_no_bit(orc, scene):
 
     plain = E.render_with_emission(oracle(), em, spp=spp, parts=True)
     o = RR.Retiring(oracle(), roulette_start=RR.NO_ROULETTE)
-    got = E.render_with_emission(o, em, spp=spp, parts=True)
+    got = E.render_with_emission(o, em, spp=spp, parts=True, termination=o)
     for k in ("acc", "image", "emitted", "s1", "s2"):
         assert np.array_equal(bits(got[k]), bits(plain[k])), k
     t = o.bounce_table().astype(np.int64)
@@ -151,7 +151,8 @@ def test_retiring_dead_paths_changes_no_bit(orc, scene):
     # with NEE on top: the same
     shadow = make_oracle(orc, inputs, w, h)
     plain = N.render_with_nee(oracle(), shadow, em, spp=spp, parts=True)
-    got = N.render_with_nee(RR.Retiring(oracle(), roulette_start=RR.NO_ROULETTE), shadow, em, spp=spp, parts=True)
+    o = RR.Retiring(oracle(), roulette_start=RR.NO_ROULETTE)
+    got = N.render_with_nee(o, shadow, em, spp=spp, parts=True, termination=o)
     for k in ("acc", "image", "emitted"):
         assert np.array_equal(bits(got[k]), bits(plain[k])), k
 
@@ -163,7 +164,7 @@ def test_last_shade_of_the_loop_stays_as_it_is(orc):
     em = E.Emission({1: RR.ROOM["e"]}, spheres=inputs[0], materials=inputs[1])
     plain = E.render_with_emission(make_oracle(orc, inputs, w, h, max_wavefronts=1, miss_floor=0), em, spp=2)
     o = RR.Retiring(make_oracle(orc, inputs, w, h, max_wavefronts=1, miss_floor=0), roulette_start=0, q_min=0.5)
-    assert np.array_equal(bits(E.render_with_emission(o, em, spp=2)), bits(plain)) and o.retired == [[], []]
+    assert np.array_equal(bits(E.render_with_emission(o, em, spp=2, termination=o)), bits(plain)) and o.retired == [[], []]
 
 
 UNBIASED = {"w": 48, "h": 32, "spp": 16, "max_wavefronts": 12, "roulette_start": 1, "q_min": 0.25}
@@ -175,9 +176,10 @@ def room_sample_means(orc, **kw):
     inputs = RR.lamp_room_inputs(orc, w, h)
     em = E.Emission({1: RR.ROOM["e"]}, spheres=inputs[0], materials=inputs[1])
     o = make_oracle(orc, inputs, w, h, max_wavefronts=UNBIASED["max_wavefronts"], miss_floor=0, rng_mode=1)
-    if kw.pop("retire", True):
+    retiring = kw.pop("retire", True)
+    if retiring:
         o = RR.Retiring(o, roulette_start=UNBIASED["roulette_start"], q_min=UNBIASED["q_min"], **kw)
-    r = E.render_with_emission(o, em, spp=UNBIASED["spp"], parts=True)
+    r = E.render_with_emission(o, em, spp=UNBIASED["spp"], parts=True, termination=o if retiring else None)
     v = (r["image"] + r["emitted"]).astype(np.float64)
     return (0.2126 * v[..., 0] + 0.7152 * v[..., 1] + 0.0722 * v[..., 2]).mean(axis=1)
 

@@ -3,14 +3,11 @@ of wfpt_device_math.h, and a whole textured render driven through the oracle's s
 rounds each one as the device does with -ffp-contract=off), so the results are the device's bits."""
 import numpy as np
 
-from environment_ref import INV_2PI, INV_PI, atan2_, env_lookup, normalize3, sky
+from environment_ref import INV_2PI, INV_PI, atan2_
+from transport_ref import dot3_components as dot3
+from transport_ref import f32, normalize3, render
 
-f32 = np.float32
 FILTERS = {"bilinear": 0, "nearest": 1}
-
-
-def dot3(ax, ay, az, bx, by, bz):
-    return (ax * bx + ay * by) + az * bz
 
 
 def sphere_uv(p, centre):
@@ -105,59 +102,8 @@ class Textures:
         return tex, slot >= 0
 
 
-def render_with_textures(o, tx, spp=1, first_frame=1, env=None, env_params=None, aov=False):
-    """The oracle's per-sample loop (orc_render_sample) driven from Python with its own per-pixel throughput: generate_rays, then per
-    wavefront extend, the miss_floor exit, and at every hit thr <- (thr * tex) * albedo (thr * albedo where unbound), at every miss
-    thr <- thr * sky (or the environment map); the oracle's shade supplies the extension rays and RNG. Returns the accumulated image
-    (n_pixels x 3), and with aov=True also the sum of the primary hits' tex * albedo (the sky / map value of a primary miss)."""
-    from oracle import oracle as O
-    p = o.params
-    gx = (o.width + 7) // 8
-    gy = ((o.height + 7) // 8 - p.tile_rank + p.tile_world - 1) // p.tile_world
-    prims = tx.spheres if tx.triangles is None else tx.triangles
-    albedo = np.asarray(tx.materials["albedo"][:, :3], f32)
-    ep = dict(env_params or {})
-    acc = np.zeros((o.n_pixels, 3), f32)
-    alb_sum = np.zeros((o.n_pixels, 3), f32)
-    for k in range(spp):
-        o.set_frame(first_frame + k, 0)
-        o.reset_image()
-        o.set_counters([0, 0, gx * gy * 64])
-        o.generate_rays(gx, gy, True)
-        thr = o.image().copy()
-        ex, ey = O.workgroup_size_64(gx * gy * 64)
-        for b in range(p.max_wavefronts):
-            n_rays = int(o.counters()[2])
-            o.extend(ex, ey)
-            c = o.counters()
-            n_miss, n_hit = int(c[0]), int(c[1])
-            rays = o.rays(max(n_rays, 1))
-            hits = o.hits(n_hit)
-            ridx = hits["ray_idx"].astype(np.int64)
-            hp = rays["pixel_idx"][ridx].astype(np.int64)
-            org, d = rays["origin"][ridx, :3].astype(f32), rays["direction"][ridx, :3].astype(f32)
-            pt = org + hits["t"].astype(f32)[:, None] * d  # sh:91, per component o + t d
-            prim = hits["sphere_idx"].astype(np.int64)
-            tex, bound = tx.factor(prim, pt)
-            alb = albedo[prims["material_idx"][prim].astype(np.int64)]
-            midx = o.misses(n_miss).astype(np.int64)
-            mp = rays["pixel_idx"][midx].astype(np.int64)
-            md = rays["direction"][midx, :3].astype(f32)
-            mf = sky(md) if env is None else env_lookup(env, md, ep.get("intensity", 1.0), ep.get("rotation", 0.0))
-            if b == 0 and aov:
-                alb_sum[hp] = alb_sum[hp] + np.where(bound[:, None], tex * alb, alb)
-                alb_sum[mp] = alb_sum[mp] + mf
-            if n_miss < p.miss_floor:
-                break
-            t = thr[hp]
-            thr[hp] = np.where(bound[:, None], (t * tex) * alb, t * alb)
-            thr[mp] = thr[mp] * mf
-            o.set_counters([c[0], c[1], 0] + list(c[3:]))
-            sx, sy = O.workgroup_size_64(n_hit)
-            o.shade(sx, sy)
-            n_ext = int(o.counters()[2])
-            o.swap_ray_queues()
-            ex, ey = O.workgroup_size_64(n_ext)
-            o.set_counters([0, 0, n_ext])
-        acc = acc + thr
-    return (acc, alb_sum) if aov else acc
+def render_with_textures(o, tx, spp=1, first_frame=1, env=None, env_params=None, aov=False, termination=None):
+    """transport_ref.render with the texture pass alone: at every hit thr <- (thr * tex) * albedo (thr * albedo where unbound), at every
+    miss thr <- thr * sky (or the environment map). Returns the accumulated image (n_pixels x 3), and with aov=True also the sum of the
+    primary hits' tex * albedo (the sky / map value of a primary miss)."""
+    return render(o, tx=tx, env=env, env_params=env_params, termination=termination, spp=spp, first_frame=first_frame, aov=aov)
