@@ -121,6 +121,23 @@ def capacity_rule(width, height, max_pixels=0, tile_rank=0, tile_world=1, batch=
     return c
 
 
+K_EXTEND_LDS_OWN = 860          # extend_lds_bytes: extend_kernel's own area behind the staged scene
+K_LDS_DEFAULT_MAX = 64 * 1024   # the dynamic LDS a launch may ask for unless hipFuncSetAttribute raised the kernel's limit
+K_LDS_SCENE_MAX = 80 * 1024     # upload_scene: a scene is staged in LDS while extend's need stays within this
+
+
+def scene_lds_bytes(n_nodes, n_prims, triangles=False):
+    """scene_lds_bytes (csrc/wfpt_kernels.hip): the staged scene's nodes, primitive geometry and u16 parent table."""
+    return 32 * n_nodes + 16 * (3 if triangles else 1) * n_prims + 16 * -(-(n_nodes // 2 + 1) // 8)
+
+
+def in_lds_window(n_nodes, n_prims, triangles=False):
+    """The scene is staged in LDS (upload_scene's rule on extend_lds_bytes) and every kernel that stages it asks for more than the
+    default limit: each of their variants must have had its limit raised before its first launch."""
+    b = scene_lds_bytes(n_nodes, n_prims, triangles)
+    return K_LDS_DEFAULT_MAX < b and b + K_EXTEND_LDS_OWN <= K_LDS_SCENE_MAX and n_nodes <= 65536
+
+
 def needed_bytes(cap, refill=False):
     """What a case needs free on the card: the allocations above, the refill walk's dense records, and 2 GiB for the rest."""
     extra = 2 * cap.batch_max * cap.capacity * 16 if refill else 0

@@ -91,3 +91,13 @@ def test_viewports_of_a_resized_context():
     for w, h in [(0xFFFFFFF9, 613566756), (0xFFFFFFFF, 1), (65536, 65536), (2 ** 31, 2)]:
         assert not c.accepts_viewport(w, h)
     assert (0xFFFFFFF9 * 613566756) % 2 ** 32 == 4 and ((0xFFFFFFF9 + 7) % 2 ** 32) // 8 == 0
+
+
+def test_staged_scene_bytes_and_the_window_above_the_default_lds_limit():
+    # 900 spheres, 1800 nodes: 57600 of nodes, 14400 of spheres, 113 uint4 of parents (901 u16); + 860 of extend's own = 74668
+    assert R.scene_lds_bytes(1800, 900) == 57600 + 14400 + 1808 == 73808
+    # 650 triangles, 1300 nodes: 41600 of nodes, 31200 of triangles, 82 uint4 of parents (651 u16)
+    assert R.scene_lds_bytes(1300, 650, triangles=True) == 41600 + 31200 + 1312 == 74112
+    assert R.in_lds_window(1800, 900) and R.in_lds_window(1300, 650, triangles=True)
+    assert R.scene_lds_bytes(1580, 790) == 64784 and not R.in_lds_window(1580, 790)   # within the default limit
+    assert R.scene_lds_bytes(1980, 990) == 81184 and not R.in_lds_window(1980, 990)   # with extend's 860: beyond 80 KiB, stays in HBM

@@ -4404,25 +4404,56 @@ template <typename F> auto pick_variant(const SceneDev &sc, bool exact, bool lds
     if (sc.prim_kind == 0) return exact ? pick_walk<F, 0, true>(lds_scene, deep) : pick_walk<F, 0, false>(lds_scene, deep);
     return exact ? pick_walk<F, 1, true>(lds_scene, deep) : pick_walk<F, 1, false>(lds_scene, deep);
 }
-// A kernel may use more than 64 KiB of dynamic LDS only once that is allowed for it: for every variant the context may switch to
-template <typename... Fn> hipError_t allow_dynamic_lds(uint32_t bytes, Fn... fns) {
-    if (bytes <= 64u * 1024u) return hipSuccess;
-    for (const void *fn : {reinterpret_cast<const void *>(fns)...}) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
-        if (e != hipSuccess) return e;
+// A family of tracing kernels, described once: K::get<selectors..., Trail, PRIM, LDS_SCENE, EXACT>() names the kernel (the order of the
+// kernel's own template arguments is K's business), and one Range per selector lists the values it takes. Both the variant a launch picks
+// and the variants a context prepares come from this description, so the two cannot name different sets.
+template <auto... V> struct Range {};
+using Bool = Range<false, true>;
+template <typename K, auto... Bound> struct Bind { // K with its selectors bound: what pick_variant takes
+    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static auto get() { return K::template get<Bound..., Trail, PRIM, LDS_SCENE, EXACT>(); }
+};
+template <typename K, typename... Ranges> struct Family;
+template <typename K> struct Family<K> { // every selector is bound
+    template <auto... Bound> static auto pick(const SceneDev &sc, bool exact, bool lds_scene) { return pick_variant<Bind<K, Bound...>>(sc, exact, lds_scene); }
+    template <auto... Bound, typename F> static hipError_t each(const SceneDev &sc, bool lds_scene, F f) {
+        for (bool exact : {false, true}) // both box tests: the context may switch between them later (decide_exact)
+            if (const hipError_t e = f(pick<Bound...>(sc, exact, lds_scene)); e != hipSuccess) return e;
+        return hipSuccess;
     }
-    return hipSuccess;
+};
+template <typename K, auto V0, auto... Vn, typename... Ranges> struct Family<K, Range<V0, Vn...>, Ranges...> {
+    using Next = Family<K, Ranges...>;
+    using Rest = Family<K, Range<Vn...>, Ranges...>; // the same selector's other values
+    // pick(sc, exact, lds_scene, v...): the variant for this scene with each selector bound to the value of its range that equals its v
+    // (to the range's last value if none does)
+    template <auto... Bound, typename V, typename... Vs> static auto pick(const SceneDev &sc, bool exact, bool lds_scene, V v, Vs... vs) {
+        if constexpr (sizeof...(Vn) == 0) return Next::template pick<Bound..., V0>(sc, exact, lds_scene, vs...);
+        else return v == V0 ? Next::template pick<Bound..., V0>(sc, exact, lds_scene, vs...) : Rest::template pick<Bound...>(sc, exact, lds_scene, v, vs...);
+    }
+    // each(sc, lds_scene, f): f(variant) for every variant a context of this scene may launch, until one fails
+    template <auto... Bound, typename F> static hipError_t each(const SceneDev &sc, bool lds_scene, F f) {
+        hipError_t e = Next::template each<Bound..., V0>(sc, lds_scene, f);
+        if constexpr (sizeof...(Vn) != 0)
+            if (e == hipSuccess) e = Rest::template each<Bound...>(sc, lds_scene, f);
+        return e;
+    }
+};
+// A kernel may use more than 64 KiB of dynamic LDS only once that is allowed for it: for every variant of the families
+template <typename... Families> hipError_t allow_dynamic_lds(const SceneDev &sc, bool lds_scene, uint32_t bytes) {
+    if (bytes <= 64u * 1024u) return hipSuccess;
+    const auto allow = [bytes](auto fn) {
+        return hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes));
+    };
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? Families::each(sc, lds_scene, allow) : e), ...);
+    return e;
 }
 
 using ExtendFn = void (*)(ExtendArgs);
-template <bool INACT, bool ENV> struct ExtendK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ExtendFn get() { return extend_kernel<INACT, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+struct ExtendK {
+    template <bool INACT, bool ENV, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ExtendFn get() { return extend_kernel<INACT, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
 };
-ExtendFn extend_variant(const SceneDev &sc, bool exact, bool has_inactive, bool env = false) {
-    const bool lds = sc.lds_scene != 0;
-    if (env) return has_inactive ? pick_variant<ExtendK<true, true>>(sc, exact, lds) : pick_variant<ExtendK<false, true>>(sc, exact, lds);
-    return has_inactive ? pick_variant<ExtendK<true, false>>(sc, exact, lds) : pick_variant<ExtendK<false, false>>(sc, exact, lds);
-}
+using Extend = Family<ExtendK, Bool, Bool>; // a partial tile in the image, both miss payloads
 } // namespace
 
 uint32_t extend_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind, bool lds_scene) {
@@ -4431,31 +4462,18 @@ uint32_t extend_lds_bytes(uint32_t n_nodes, uint32_t n_prims, uint32_t prim_kind
 }
 
 hipError_t extend_blocks_per_cu(const SceneDev &scene, int *blocks) {
-    for (bool exact : {false, true}) { // both box tests (the context may switch between them later: decide_exact), both miss payloads
-        const hipError_t e = allow_dynamic_lds(scene.lds_bytes, extend_variant(scene, exact, false), extend_variant(scene, exact, true),
-                                               extend_variant(scene, exact, false, true), extend_variant(scene, exact, true, true));
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, extend_variant(scene, scene.exact != 0, false), kExtendThreads, scene.lds_bytes);
+    const bool lds = scene.lds_scene != 0;
+    if (const hipError_t e = allow_dynamic_lds<Extend>(scene, lds, scene.lds_bytes); e != hipSuccess) return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, Extend::pick(scene, scene.exact != 0, lds, false, false), kExtendThreads, scene.lds_bytes);
 }
 
 namespace {
 using BounceFn = void (*)(BounceArgs);
-template <int MODE, bool ENV> struct BounceK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_kernel<MODE, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+struct BounceK {
+    template <int MODE, bool ENV, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_kernel<MODE, Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
 };
-// env: the variant of WFPT_FLAG_ENVIRONMENT contexts with a map (bounce_kernel's ENV)
-BounceFn bounce_variant(const SceneDev &sc, bool exact, int mode, bool env = false) {
-    const bool lds = sc.lds_scene != 0;
-    if (mode == kBounceLast) // no traversal: one variant
-        return env ? bounce_kernel<kBounceLast, uint32_t, 0, false, false, true> : bounce_kernel<kBounceLast, uint32_t, 0, false, false>;
-    if (mode == kBounceMiddleRetire)
-        return env ? pick_variant<BounceK<kBounceMiddleRetire, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddleRetire, false>>(sc, exact, lds);
-    if (mode == kBounceFirstMasked)
-        return env ? pick_variant<BounceK<kBounceFirstMasked, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceFirstMasked, false>>(sc, exact, lds);
-    if (env) return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, true>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, true>>(sc, exact, lds);
-    return mode == kBounceFirst ? pick_variant<BounceK<kBounceFirst, false>>(sc, exact, lds) : pick_variant<BounceK<kBounceMiddle, false>>(sc, exact, lds);
-}
+// the launches that trace (any other mode counts as kBounceMiddle); ENV: WFPT_FLAG_ENVIRONMENT contexts with a map
+using Bounce = Family<BounceK, Range<kBounceFirst, kBounceFirstMasked, kBounceMiddleRetire, kBounceMiddle>, Bool>;
 uint32_t bounce_dynamic_lds(const SceneDev &sc, int mode) {
     const uint32_t misc = 4u * kBounceMiscWords;
     if (mode == kBounceLast) return misc;
@@ -4465,14 +4483,9 @@ uint32_t bounce_dynamic_lds(const SceneDev &sc, int mode) {
 
 hipError_t bounce_blocks_per_cu(const SceneDev &scene, int *blocks) {
     const uint32_t bytes = bounce_dynamic_lds(scene, kBounceMiddle);
-    for (bool exact : {false, true}) { // both box tests, the first and the middle launches, both miss payloads
-        const hipError_t e = allow_dynamic_lds(bytes, bounce_variant(scene, exact, kBounceFirst), bounce_variant(scene, exact, kBounceMiddle),
-                                               bounce_variant(scene, exact, kBounceFirst, true), bounce_variant(scene, exact, kBounceMiddle, true),
-                                               bounce_variant(scene, exact, kBounceMiddleRetire), bounce_variant(scene, exact, kBounceMiddleRetire, true),
-                                               bounce_variant(scene, exact, kBounceFirstMasked), bounce_variant(scene, exact, kBounceFirstMasked, true));
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
+    const bool lds = scene.lds_scene != 0;
+    if (const hipError_t e = allow_dynamic_lds<Bounce>(scene, lds, bytes); e != hipSuccess) return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, Bounce::pick(scene, scene.exact != 0, lds, kBounceMiddle, false), kExtendThreads, bytes);
 }
 
 // ---- class-binned loop
@@ -4481,27 +4494,23 @@ uint32_t bounce_binned_lds(const SceneDev &sc, int mode) {
     const uint32_t misc = 4u * (2u * kExtendWaves * ClsPack<kBinClasses>::kWords + 2u + 2u) + ((sc.n_spheres + 15u) & ~15u);
     return mode == kBounceLast ? misc : misc + scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind);
 }
-template <int MODE> struct BinnedK { // LDS-resident scenes only: no LDS_SCENE parameter
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_binned_kernel<MODE, Trail, PRIM, EXACT, kBinClasses>; }
+struct BinnedK { // LDS-resident scenes only: no LDS_SCENE parameter
+    template <int MODE, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static BounceFn get() { return bounce_binned_kernel<MODE, Trail, PRIM, EXACT, kBinClasses>; }
 };
-BounceFn bounce_binned_variant(const SceneDev &sc, bool exact, int mode) {
-    if (mode == kBounceLast) return bounce_binned_kernel<kBounceLast, uint32_t, 0, false, kBinClasses>; // no traversal: one variant
-    return mode == kBounceFirst ? pick_variant<BinnedK<kBounceFirst>>(sc, exact, true) : pick_variant<BinnedK<kBounceMiddle>>(sc, exact, true);
-}
+using Binned = Family<BinnedK, Range<kBounceFirst, kBounceMiddle>>; // the launches that trace
 } // namespace
 
 hipError_t bounce_binned_blocks_per_cu(const SceneDev &scene, int *blocks) {
     const uint32_t bytes = bounce_binned_lds(scene, kBounceMiddle);
-    for (bool exact : {false, true}) {
-        const hipError_t e = allow_dynamic_lds(bytes, bounce_binned_variant(scene, exact, kBounceFirst), bounce_binned_variant(scene, exact, kBounceMiddle));
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, bounce_binned_variant(scene, scene.exact != 0, kBounceMiddle), kExtendThreads, bytes);
+    if (const hipError_t e = allow_dynamic_lds<Binned>(scene, true, bytes); e != hipSuccess) return e;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, Binned::pick(scene, scene.exact != 0, true, kBounceMiddle), kExtendThreads, bytes);
 }
 
 hipError_t launch_bounce_binned(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(bounce_binned_variant(a.scene, a.scene.exact != 0, mode), dim3(grid), dim3(kExtendThreads), bounce_binned_lds(a.scene, mode), s, a);
+    const BounceFn fn = mode == kBounceLast ? bounce_binned_kernel<kBounceLast, uint32_t, 0, false, kBinClasses> // no traversal: one variant
+                                            : Binned::pick(a.scene, a.scene.exact != 0, true, mode);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kExtendThreads), bounce_binned_lds(a.scene, mode), s, a);
     return hipGetLastError();
 }
 
@@ -4524,7 +4533,10 @@ hipError_t launch_tile_lists(const TileListArgs &a, hipStream_t s) {
 
 hipError_t launch_bounce(const BounceArgs &a, int mode, uint32_t grid, hipStream_t s, bool env_dirs) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(bounce_variant(a.scene, a.scene.exact != 0, mode, env_dirs), dim3(grid), dim3(kExtendThreads), bounce_dynamic_lds(a.scene, mode), s, a);
+    const BounceFn last = env_dirs ? bounce_kernel<kBounceLast, uint32_t, 0, false, false, true> : bounce_kernel<kBounceLast, uint32_t, 0, false, false>;
+    const BounceFn fn = mode == kBounceLast ? last // no traversal: one variant per miss payload
+                                            : Bounce::pick(a.scene, a.scene.exact != 0, a.scene.lds_scene != 0, mode, env_dirs);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kExtendThreads), bounce_dynamic_lds(a.scene, mode), s, a);
     return hipGetLastError();
 }
 
@@ -4573,7 +4585,8 @@ hipError_t launch_generate(const GenerateArgs &a, hipStream_t s, const uint64_t 
 
 hipError_t launch_extend(const ExtendArgs &a, uint32_t grid, hipStream_t s, bool env_dirs) {
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(extend_variant(a.scene, a.scene.exact != 0, a.has_inactive != 0, env_dirs), dim3(grid), dim3(kExtendThreads), a.scene.lds_bytes, s, a);
+    const ExtendFn fn = Extend::pick(a.scene, a.scene.exact != 0, a.scene.lds_scene != 0, a.has_inactive != 0, env_dirs);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(kExtendThreads), a.scene.lds_bytes, s, a);
     return hipGetLastError();
 }
 
@@ -4753,93 +4766,65 @@ hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t 
 namespace {
 using AovFn = void (*)(AovArgs);
 using AovEnvFn = void (*)(AovArgs, EnvDev);
-template <bool ENV> struct AovK {
+struct AovK {
     template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovFn get() { return aov_kernel<Trail, PRIM, LDS_SCENE, EXACT>; }
 };
-template <> struct AovK<true> {
+struct AovEnvK {
     template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovEnvFn get() { return aov_env_kernel<Trail, PRIM, LDS_SCENE, EXACT>; }
 };
-template <bool ENV = false> auto aov_variant(const SceneDev &sc, bool exact) { return pick_variant<AovK<ENV>>(sc, exact, sc.lds_scene != 0); }
 using AovTexFn = void (*)(AovArgs, EnvDev, TexScene);
-template <bool ENV> struct AovTexK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovTexFn get() { return aov_tex_kernel<Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
+struct AovTexK {
+    template <bool ENV, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovTexFn get() { return aov_tex_kernel<Trail, PRIM, LDS_SCENE, EXACT, ENV>; }
 };
-AovTexFn aov_tex_variant(const SceneDev &sc, bool exact, bool env) {
-    return env ? pick_variant<AovTexK<true>>(sc, exact, sc.lds_scene != 0) : pick_variant<AovTexK<false>>(sc, exact, sc.lds_scene != 0);
-}
+using Aov = Family<AovK>;
+using AovEnv = Family<AovEnvK>;
+using AovTex = Family<AovTexK, Bool>;
 uint32_t aov_lds_bytes(const SceneDev &sc) { return sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes; }
 } // namespace
 
 hipError_t aov_prepare(const SceneDev &scene) {
-    for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
-        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), aov_variant(scene, exact), aov_variant<true>(scene, exact),
-                                               aov_tex_variant(scene, exact, false), aov_tex_variant(scene, exact, true));
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return allow_dynamic_lds<Aov, AovEnv, AovTex>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
 }
 
 hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex) {
     if (grid == 0 || a.n == 0 || a.gx * a.gy == 0) return hipSuccess;
-    if (tex)
-        hipLaunchKernelGGL(aov_tex_variant(a.scene, a.scene.exact != 0, env != nullptr), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s,
-                           a, env ? *env : EnvDev{}, *tex);
-    else if (env)
-        hipLaunchKernelGGL(aov_variant<true>(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a, *env);
-    else
-        hipLaunchKernelGGL(aov_variant(a.scene, a.scene.exact != 0), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+    const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
+    const dim3 g(grid), b(kExtendThreads);
+    if (tex) hipLaunchKernelGGL(AovTex::pick(a.scene, exact, lds, env != nullptr), g, b, aov_lds_bytes(a.scene), s, a, env ? *env : EnvDev{}, *tex);
+    else if (env) hipLaunchKernelGGL(AovEnv::pick(a.scene, exact, lds), g, b, aov_lds_bytes(a.scene), s, a, *env);
+    else hipLaunchKernelGGL(Aov::pick(a.scene, exact, lds), g, b, aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }
 
 namespace {
 using ConnectFn = void (*)(ConnectArgs);
-template <bool TEX, bool ENVS, bool MIS = false> struct ConnectK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() { return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS, MIS>; }
+struct ConnectK {
+    template <bool TEX, bool ENVS, bool MIS, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectFn get() {
+        return connect_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS, MIS>;
+    }
 };
-ConnectFn connect_variant(const SceneDev &sc, bool exact, bool tex, bool envs = false, bool mis = false) {
-    const bool lds = sc.lds_scene != 0;
-    // (the ENVS MIS variants are named last: the order of instantiation numbers the labels of the walks' inline assembly, and the earlier
-    // variants keep the parent's instructions to the label, tools/isa_compare.py)
-    if (mis && !envs) return tex ? pick_variant<ConnectK<true, false, true>>(sc, exact, lds) : pick_variant<ConnectK<false, false, true>>(sc, exact, lds);
-    if (envs && !mis) return tex ? pick_variant<ConnectK<true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true>>(sc, exact, lds);
-    if (!envs) return tex ? pick_variant<ConnectK<true, false>>(sc, exact, lds) : pick_variant<ConnectK<false, false>>(sc, exact, lds);
-    return tex ? pick_variant<ConnectK<true, true, true>>(sc, exact, lds) : pick_variant<ConnectK<false, true, true>>(sc, exact, lds);
-}
-// (the POWER variants after all of those, for the same reason)
+using Connect = Family<ConnectK, Bool, Bool, Bool>;
 using ConnectPowerFn = void (*)(ConnectArgs, LightDist);
-template <bool TEX, bool MIS> struct ConnectPowerK {
-    template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectPowerFn get() { return connect_power_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, MIS>; }
+struct ConnectPowerK {
+    template <bool TEX, bool MIS, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectPowerFn get() {
+        return connect_power_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, MIS>;
+    }
 };
-ConnectPowerFn connect_power_variant(const SceneDev &sc, bool exact, bool tex, bool mis) {
-    const bool lds = sc.lds_scene != 0;
-    if (mis) return tex ? pick_variant<ConnectPowerK<true, true>>(sc, exact, lds) : pick_variant<ConnectPowerK<false, true>>(sc, exact, lds);
-    return tex ? pick_variant<ConnectPowerK<true, false>>(sc, exact, lds) : pick_variant<ConnectPowerK<false, false>>(sc, exact, lds);
-}
+using ConnectPower = Family<ConnectPowerK, Bool, Bool>;
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
-    for (bool exact : {false, true}) { // both box tests: the context may switch between them later (decide_exact)
-        const hipError_t e = allow_dynamic_lds(aov_lds_bytes(scene), connect_variant(scene, exact, false), connect_variant(scene, exact, true),
-                                               connect_variant(scene, exact, false, true), connect_variant(scene, exact, true, true),
-                                               connect_variant(scene, exact, false, false, true), connect_variant(scene, exact, true, false, true),
-                                               connect_variant(scene, exact, false, true, true), connect_variant(scene, exact, true, true, true),
-                                               connect_power_variant(scene, exact, false, false), connect_power_variant(scene, exact, true, false),
-                                               connect_power_variant(scene, exact, false, true), connect_power_variant(scene, exact, true, true));
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return allow_dynamic_lds<Connect, ConnectPower>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
 }
 
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power) {
     if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
     if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
-    if (power) {
-        if (envs || !power->cdf || power->total == 0) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(connect_power_variant(a.scene, a.scene.exact != 0, textured, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene),
-                           s, a, *power);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(connect_variant(a.scene, a.scene.exact != 0, textured, envs, mis), dim3(grid), dim3(kExtendThreads), aov_lds_bytes(a.scene), s, a);
+    if (power && (envs || !power->cdf || power->total == 0)) return hipErrorInvalidValue;
+    const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
+    const dim3 g(grid), b(kExtendThreads);
+    if (power) hipLaunchKernelGGL(ConnectPower::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *power);
+    else hipLaunchKernelGGL(Connect::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }
 
