@@ -260,7 +260,11 @@ enum {
     WFPT_FLAG_LIGHT_POWER = 1u << 22 /* the connect pass selects its light in proportion to the lights' power (luminance times area), see
                                         "Light selection by power" below. Needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with
                                         WFPT_FLAG_ENV_NEE (and so WFPT_FLAG_ENV_MIS). With no emitter set, and with one light, the context
-                                        renders bit for bit as without the flag. */
+                                        renders bit for bit as without the flag. */,
+    WFPT_FLAG_ANALYTIC_LIGHTS = 1u << 23 /* point, spot and directional lights for the connect pass, see "Analytic lights" below. Needs
+                                        WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, refused with WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENV_MIS and
+                                        WFPT_FLAG_LIGHT_POWER. With no analytic light set the context renders bit for bit as without the
+                                        flag, and launches the same kernels. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -773,7 +777,8 @@ int wfpt_emission_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * With no emitter set a flagged context launches exactly the kernels a context without the flag launches and renders the same bits. A
  * context with the flag and an emitter never runs the class-binned loop (set and clear on such a context are refused, see "Emission");
  * wfpt_render_chunked* masks the flag off. The calls below return WFPT_ERR_INVALID_ARGUMENT on a context without the flag.
- * (Light selection by power: WFPT_FLAG_LIGHT_POWER, "Light selection by power" below.)
+ * (Light selection by power: WFPT_FLAG_LIGHT_POWER, "Light selection by power" below. Lights without a surface -- point, spot, directional:
+ * WFPT_FLAG_ANALYTIC_LIGHTS, "Analytic lights" below.)
  * Not done: multiple importance sampling, cone sampling of sphere lights, a light BVH, retiring fully
  * shadowed paths (dead ones: WFPT_FLAG_RETIRE), contact shadows thinner than the 0.001 / 0.1 % windows. (Importance sampling of the environment map: WFPT_FLAG_ENV_NEE.) */
 /* the number of emitting primitives (the light list's length), 0 with none; negative: a wfpt_status */
@@ -889,6 +894,7 @@ int wfpt_sample_environment_light(wfpt_ctx *ctx, const float *in10, size_t n, fl
  * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while no primitive emits.
  * (Weighing the environment map against the scatter: WFPT_FLAG_ENV_MIS, a flag of its own below; WFPT_FLAG_ENV_NEE stays refused here.)
  * (Light selection by power: WFPT_FLAG_LIGHT_POWER, "Light selection by power" below, which restates pl with the selected light's weight.)
+ * (Analytic lights: WFPT_FLAG_ANALYTIC_LIGHTS, "Analytic lights" below: their samples are not weighed, and nf counts them.)
  * Not done: the power heuristic, cone sampling of
  * sphere lights, MIS for fuzzy metal, the class-binned loop and wfpt_render_chunked*. */
 /* Steps 3 to 5 with the weight for n caller-supplied receivers on the device. in9: as wfpt_sample_lights; out12: n rows of (q.xyz, the
@@ -943,6 +949,81 @@ int wfpt_mis_hit_weight(wfpt_ctx *ctx, const float *in8, size_t n, float *out4);
 /* The light list and its distribution: light_prims and cdf get wfpt_nee_light_count entries each; either may be NULL. Blocking.
  * WFPT_ERR_INVALID_ARGUMENT on a context without the flag and while the list has no distribution. */
 int wfpt_read_light_distribution(wfpt_ctx *ctx, uint32_t *light_prims, uint64_t *cdf);
+
+/* ------------------------------------------------------------------ Analytic lights (WFPT_FLAG_ANALYTIC_LIGHTS)
+ * Lights without a surface: point lights, spot lights and directional lights (a sun). No ray can hit them, so they are reached by the
+ * connect pass alone. wfpt_create* accepts WFPT_FLAG_ANALYTIC_LIGHTS only together with WFPT_FLAG_EMISSION and WFPT_FLAG_NEE, and refuses
+ * it together with WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENV_MIS and WFPT_FLAG_LIGHT_POWER (WFPT_ERR_INVALID_ARGUMENT either way). It combines
+ * freely with WFPT_FLAG_MIS, WFPT_FLAG_TEXTURES, WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_RETIRE, WFPT_FLAG_ADAPTIVE, WFPT_FLAG_AOV,
+ * WFPT_FLAG_DENOISE, every loop the emitters run in, both RNG modes and band sharding.
+ *
+ * wfpt_set_lights replaces the context's analytic lights (NULL / 0: none) and acts like wfpt_set_emission: the accumulation and the frame
+ * counter restart, the temporal history and the captured graphs are dropped; wfpt_update_scene* and viewport changes keep the lights; a
+ * refused call leaves the context as it was; WFPT_ERR_UNSUPPORTED on a context that runs WFPT_LOOP_FUSED_BINNED (a context that holds an
+ * analytic light never runs that loop); wfpt_render_chunked* masks the flag off. WFPT_ERR_INVALID_ARGUMENT: a context without the flag,
+ * n > WFPT_MAX_LIGHTS, n > 0 with a NULL array, an unknown type, a position that is not finite (point, spot), a colour that is not
+ * finite or is negative, a direction (spot, directional) that is not finite or has length 0 -- or whose squared length overflows or
+ * underflows to 0 in f32 --, a spot that does not satisfy -1 <= cos_outer < cos_inner <= 1 (a NaN fails it). The fields a type does not
+ * read (a directional light's position, a point light's direction, the cosines of both) are stored as given and never looked at.
+ * The direction of a spot or directional light is normalised once, at the call, on the host, in IEEE f32:
+ *       len = sqrt((x x + y y) + z z);  direction <- (x / len, y / len, z / len)
+ * and the normalised direction is what is stored, what wfpt_get_lights returns and what every formula below reads. A colour of -0 is
+ * stored as +0. On the device the lights are three 16-byte rows each, wfpt_light's own layout.
+ *
+ * Semantics. n_l: the length of the emitter list of "Next-event estimation"; n_a: the number of analytic lights; N = n_l + n_a;
+ * Nf = f32(N). Wherever the sections above say "a context with an emitter" a flagged context reads "with N > 0": the connect pass runs,
+ * and the `emitted` plane, the connected flag and (WFPT_FLAG_MIS) the `origin` plane exist, from the first call that makes N > 0 -- a
+ * scene lit by a sun alone, with no emissive material, is the main case. The emission pass runs while a material emits, as before.
+ * With n_a = 0 a flagged context launches exactly the kernels of the unflagged context and renders the same bits; with N = 0 those of a
+ * context without any of the flags.
+ * Steps 1, 2 and 4 of "Next-event estimation" are unchanged: the stream, the three draws (u1 and u2 are drawn and not used by an analytic
+ * light), the connected flag. All operations are IEEE f32 in the order written, no fma, pi = 3.1415927f. What changes:
+ *  - Selection.  i = min(u32(min(max(floor(u0 * Nf), 0), Nf)), N - 1)  (a NaN or negative u0 of a caller's row selects 0).  i < n_l picks
+ *    emitter lights[i]: everything as today with Nf wherever nf stood -- in G, and under WFPT_FLAG_MIS in pl of the connect pass and of
+ *    the emission pass. Otherwise the pass picks analytic light j = i - n_l, in the order of the array wfpt_set_lights took.
+ *  - Point and spot light (position c, stored axis a, colour e):
+ *       v = c - p;  dist2 = (v.x v.x + v.y v.y) + v.z v.z;  dist = sqrt(dist2);  w = v / dist   (three divisions)
+ *       cos_s = (n.x w.x + n.y w.y) + n.z w.z
+ *       point:  fall = 1
+ *       spot:   cd = -((a.x w.x + a.y w.y) + a.z w.z);  s = (cd - cos_outer) / (cos_inner - cos_outer);
+ *               s <- s where s > 0, else 0 (a NaN gives 0);  s <- s where s < 1, else 1;  fall = (s s) * (3 - 2 s)
+ *       G = ((cos_s * fall) * Nf) / (pi * dist2)
+ *    The sample contributes only if dist2 > 0, cos_s > 0 and fall > 0 (a NaN fails each test). The ray (p, w) is traced as in step 4; the
+ *    sample is occluded iff the closest hit has t < dist * 0.999, the emitters' window.
+ *  - Directional light (stored axis a, the way the light travels; colour e, the irradiance on a surface that faces it):
+ *       w = -a;  cos_s as above;  G = (cos_s * Nf) / pi
+ *    The sample contributes only if cos_s > 0. The ray (p, w) is traced as the environment branch of "Environment next-event estimation"
+ *    traces its ray (t_min = 0.001, no far end); the sample is occluded iff the walk reports any hit.
+ *  - Contribution.  emitted[pixel] += ((thr * albedo) * e) * G per channel, as step 5. No texture applies to an analytic light.
+ *  - WFPT_FLAG_MIS. The scatter can never produce an analytic light's sample, so it has wl = 1 and its contribution is not weighed (the
+ *    value above is added as it stands). The `origin` plane and the connected flag are written as for any diffuse hit. The emission pass
+ *    never sees an analytic light: it only reads Nf in nf's place. (After a diffuse bounce an emitter hit is therefore weighed against a
+ *    connect pass that picks that emitter with probability 1 / N.)
+ *  - Samplers. wfpt_sample_lights and wfpt_sample_lights_mis keep their row layouts and work while N > 0, n_l = 0 included. For analytic
+ *    light j the primitive column holds -(1 + j) as a float; q is the light's position for point and spot lights and w for a directional
+ *    one; the MIS row reports pl = 0, pb = cos_s / pi and wl = 1 where the sample contributes, zeros elsewhere. wfpt_mis_hit_weight uses
+ *    Nf (and still needs an emitter).
+ * Shade, the tracing kernels, miss, the loop exit, the AOVs, accumulation and the moments are untouched. The connect launches stay under
+ * wfpt_nee_timing_ms.
+ * Not done: the flag together with WFPT_FLAG_ENV_NEE, with WFPT_FLAG_ENV_MIS, and with WFPT_FLAG_LIGHT_POWER (refused: the map's share and
+ * the power distribution both select among emitters only); area-less lights with a radius (soft shadows), IES profiles, selection that
+ * knows the receiver, the class-binned loop and wfpt_render_chunked*. */
+typedef enum wfpt_light_type { WFPT_LIGHT_POINT = 0, WFPT_LIGHT_SPOT = 1, WFPT_LIGHT_DIRECTIONAL = 2 } wfpt_light_type;
+typedef struct wfpt_light {      /* 48 bytes, three 16-byte rows */
+    float position[3];  uint32_t type;        /* a wfpt_light_type */
+    float direction[3]; float cos_inner;      /* direction: the way the light travels (spot axis, sun direction) */
+    float colour[3];    float cos_outer;      /* point / spot: radiant intensity; directional: irradiance on a facing surface */
+} wfpt_light;
+WFPT_LAYOUT_ASSERT(sizeof(wfpt_light) == 48 && offsetof(wfpt_light, direction) == 16 &&
+                       offsetof(wfpt_light, cos_inner) == 28 && offsetof(wfpt_light, colour) == 32 && offsetof(wfpt_light, cos_outer) == 44,
+                   "wfpt_light layout");
+#define WFPT_MAX_LIGHTS 1024u
+/* lights: n entries, copied; NULL / 0 clears */
+int wfpt_set_lights(wfpt_ctx *ctx, const wfpt_light *lights, uint32_t n);
+/* the lights as stored (directions normalised): up to `capacity` entries into out (may be NULL with capacity 0), the count into *n (may be NULL) */
+int wfpt_get_lights(wfpt_ctx *ctx, wfpt_light *out, uint32_t capacity, uint32_t *n);
+/* the number of analytic lights, 0 with none; negative: a wfpt_status */
+int wfpt_analytic_light_count(wfpt_ctx *ctx);
 
 /* ------------------------------------------------------------------ Environment multiple importance sampling (WFPT_FLAG_ENV_MIS)
  * wfpt_create* accepts WFPT_FLAG_ENV_MIS only together with WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and

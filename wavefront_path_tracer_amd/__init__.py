@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -56,6 +56,11 @@ FLAG_ADAPTIVE = 1 << 21
 # the connect pass selects its light in proportion to power, luminance times area (include/wfpt.h "Light selection by power"); needs
 # FLAG_EMISSION and FLAG_NEE, refused with FLAG_ENV_NEE
 FLAG_LIGHT_POWER = 1 << 22
+# point, spot and directional lights for the connect pass (include/wfpt.h "Analytic lights"); needs FLAG_EMISSION and FLAG_NEE, refused with
+# FLAG_ENV_NEE, FLAG_ENV_MIS and FLAG_LIGHT_POWER
+FLAG_ANALYTIC_LIGHTS = 1 << 23
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2  # wfpt_light_type
+MAX_LIGHTS = 1024  # WFPT_MAX_LIGHTS
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
 TILE_LIST_CAP, TILE_NO_LIST = 16, 0xFFFFFFFF
 FLAG_DENOISE = 1 << 11  # luminance moments and the a-trous denoiser (include/wfpt.h "Denoiser"); implies FLAG_AOV
@@ -82,6 +87,10 @@ SPHERE = np.dtype([("center", "<f4", 4), ("radius", "<f4"), ("material_idx", "<u
                    ("material_type", "<u4"), ("_buffer", "<u4")])
 MATERIAL = np.dtype([("albedo", "<f4", 4), ("fuzz", "<f4"), ("refract_index", "<f4"),
                      ("material_type", "<u4"), ("_buffer", "<u4")])
+# wfpt_light: direction is the way the light travels (spot axis, sun direction); colour is the radiant intensity of a point or spot light and
+# the irradiance on a facing surface of a directional one
+LIGHT = np.dtype([("position", "<f4", 3), ("type", "<u4"), ("direction", "<f4", 3), ("cos_inner", "<f4"),
+                  ("colour", "<f4", 3), ("cos_outer", "<f4")])
 BVH_NODE = np.dtype([("aabb_min", "<f4", 3), ("left_first", "<u4"), ("aabb_max", "<f4", 3),
                      ("prim_count", "<u4")])
 GPU_CAMERA = np.dtype([("position", "<f4", 4), ("pitch", "<f4"), ("yaw", "<f4"),
@@ -378,6 +387,9 @@ def lib():
         "wfpt_environment_share": (f32, [vp]),
         "wfpt_read_environment_distribution": (i32, [vp, vp, vp]),
         "wfpt_read_light_distribution": (i32, [vp, vp, vp]),
+        "wfpt_set_lights": (i32, [vp, vp, u32]),
+        "wfpt_get_lights": (i32, [vp, vp, u32, C.POINTER(u32)]),
+        "wfpt_analytic_light_count": (i32, [vp]),
         "wfpt_sample_environment_light": (i32, [vp, vp, sz, vp]),
         "wfpt_sample_lights_mis": (i32, [vp, vp, sz, vp]),
         "wfpt_mis_hit_weight": (i32, [vp, vp, sz, vp]),
@@ -1501,6 +1513,30 @@ class PathTracer:
         prims, cdf = np.zeros(n, "<u4"), np.zeros(n, "<u8")
         self._check(lib().wfpt_read_light_distribution(self.handle, _p(prims), _p(cdf)))
         return prims, cdf
+
+    # ---- analytic lights (contexts created with FLAG_EMISSION | FLAG_NEE | FLAG_ANALYTIC_LIGHTS; include/wfpt.h "Analytic lights")
+    def set_lights(self, lights):
+        """The context's point, spot and directional lights: a LIGHT array (or None / empty: none). Directions are normalised at the call.
+        Restarts the accumulation like a scene update."""
+        a = np.zeros(0, LIGHT) if lights is None else np.ascontiguousarray(lights, LIGHT).reshape(-1)
+        self._check(lib().wfpt_set_lights(self.handle, _p(a) if len(a) else None, len(a)))
+        self.render_progress.reset()
+
+    def lights(self):
+        """The analytic lights as stored (directions normalised): a LIGHT array."""
+        out = np.zeros(self.analytic_light_count(), LIGHT)
+        n = C.c_uint32(0)
+        self._check(lib().wfpt_get_lights(self.handle, _p(out) if len(out) else None, len(out), C.byref(n)))
+        return out[:int(n.value)]
+
+    get_lights = lights
+
+    def analytic_light_count(self):
+        """The number of analytic lights, 0 with none."""
+        n = lib().wfpt_analytic_light_count(self.handle)
+        if n < 0:
+            self._check(n)
+        return int(n)
 
     # ---- environment next-event estimation (contexts created with FLAG_ENVIRONMENT | FLAG_EMISSION | FLAG_NEE | FLAG_ENV_NEE)
     def set_environment_share(self, share):

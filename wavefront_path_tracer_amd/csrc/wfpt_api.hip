@@ -265,6 +265,10 @@ struct wfpt_ctx {
     DeviceBuffer<uint64_t> light_cdf;
     DeviceBuffer<uint32_t> light_prim_k;
     uint64_t light_total = 0;
+    // WFPT_FLAG_ANALYTIC_LIGHTS (include/wfpt.h "Analytic lights"): the lights as stored (directions normalised) and their device table,
+    // three float4 rows each (null while there is none: the context then runs as one without the flag)
+    std::vector<wfpt_light> h_lights;
+    DeviceBuffer<float4> light_rows;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
     // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
     DeviceBuffer<uint32_t> env_row;
@@ -646,23 +650,29 @@ constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
 // a material emits: the emission passes run before the shade steps (after their texture passes) and accumulate takes the second plane
 bool emitting(const wfpt_ctx *c) { return c->em_prim.get() != nullptr; }
 // (the last four fields: the weighing kinds' alone)
+// a WFPT_FLAG_ANALYTIC_LIGHTS context holds an analytic light: the connect pass and the samplers are the ANALYTIC variants, and the light
+// count wherever nf stands is N = n_l + n_a
+bool analytic_selecting(const wfpt_ctx *c) { return c->light_rows.get() != nullptr; }
+LightTable light_table(const wfpt_ctx *c) { return LightTable{c->light_rows.get(), static_cast<uint32_t>(c->h_lights.size())}; }
+uint32_t light_count(const wfpt_ctx *c) { return c->n_lights + static_cast<uint32_t>(c->h_lights.size()); }
 EmissionArgs emission_args(wfpt_ctx *c, const HitWalk &w) {
     return EmissionArgs{w, c->emitted.get(), c->em_prim.get(), c->em_mat.get(), c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind,
-                        static_cast<float>(c->n_lights)};
+                        static_cast<float>(light_count(c))};
 }
 // The emission launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::em_ms
 constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
 
 // a WFPT_FLAG_NEE context holds an emitter: the connect passes run before the shade steps (after their emission passes, which then add a
 // hit light only where the pixel's connected flag is 0)
-// (or, WFPT_FLAG_ENV_NEE, a map with a sampling distribution: env_connecting)
+// (or, WFPT_FLAG_ENV_NEE, a map with a sampling distribution: env_connecting; or, WFPT_FLAG_ANALYTIC_LIGHTS, an analytic light)
 bool env_connecting(const wfpt_ctx *c) { return c->env_row.get() != nullptr; }
-bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || env_connecting(c); }
+bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || env_connecting(c) || analytic_selecting(c); }
 // the second plane is in use: accumulate adds it, the head of every batch zeroes it
-bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c); }
+bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c) || analytic_selecting(c); }
 // a WFPT_FLAG_MIS context holds an emitter (never with a map's distribution: the flag excludes WFPT_FLAG_ENV_NEE): the connect and
 // emission passes are the MIS variants
-bool weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_MIS) != 0 && c->mis_origin.get() != nullptr && c->n_lights > 0; }
+// (an emitter or an analytic light: N > 0)
+bool weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_MIS) != 0 && c->mis_origin.get() != nullptr && light_count(c) > 0; }
 // a WFPT_FLAG_ENV_MIS context holds a map with a sampling distribution: the connect, emission and miss passes weigh the map and the
 // emitters against the scatter (without a distribution the flag does nothing)
 bool env_weighing(const wfpt_ctx *c) { return (c->p.flags & WFPT_FLAG_ENV_MIS) != 0 && env_connecting(c) && c->mis_origin.get() != nullptr; }
@@ -701,8 +711,9 @@ ConnectArgs sampler_args(wfpt_ctx *c, const float *in, float *out, size_t n) {
 hipError_t launch_sampler(wfpt_ctx *c, const ConnectArgs &a, bool envs, bool mis) {
     const uint64_t items = (static_cast<uint64_t>(a.sample_n) + kChunk - 1) / kChunk;
     const LightDist ld = light_dist(c);
+    const LightTable lt = light_table(c);
     return launch_connect(a, static_cast<uint32_t>(std::min<uint64_t>(items, static_cast<uint64_t>(c->cus) * c->blocks_per_cu)), c->stream.get(),
-                          textured(c), envs, mis, !envs && power_selecting(c) ? &ld : nullptr);
+                          textured(c), envs, mis, !envs && power_selecting(c) ? &ld : nullptr, !envs && analytic_selecting(c) ? &lt : nullptr);
 }
 // The body of a host probe (wfpt_sample_*, wfpt_*_weight), blocking: n caller rows of in_width floats to the device, launch(d_in, d_out) on
 // the context's stream, n rows of out_width floats back. rows31: the launch counts its rows in 31 bits.
@@ -725,8 +736,9 @@ int probe(wfpt_ctx *c, const char *who, const float *in, size_t in_width, float 
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb) {
     const LightDist ld = light_dist(c);
+    const LightTable lt = light_table(c);
     return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c),
-                          power_selecting(c) ? &ld : nullptr);
+                          power_selecting(c) ? &ld : nullptr, analytic_selecting(c) ? &lt : nullptr);
 }
 // the emission pass of the context's kind
 hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
@@ -779,7 +791,7 @@ hipError_t launch_miss_pass(wfpt_ctx *c, const MissArgs &a, uint32_t grid) {
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
-    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
+    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && !analytic_selecting(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
 }
 // The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
@@ -1613,6 +1625,19 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
             return nullptr;
         }
     }
+    if ((params->flags & WFPT_FLAG_ANALYTIC_LIGHTS) != 0) {
+        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
+        if ((params->flags & need) != need) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+                                                     "(its lights are reached by the connect pass, their samples land in the emission plane)");
+            return nullptr;
+        }
+        if ((params->flags & (WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS | WFPT_FLAG_LIGHT_POWER)) != 0) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS does not go with WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENV_MIS or "
+                                                     "WFPT_FLAG_LIGHT_POWER (the map's share and the power distribution select among emitters only)");
+            return nullptr;
+        }
+    }
     if ((params->flags & WFPT_FLAG_ENV_MIS) != 0) {
         constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE;
         if ((params->flags & need) != need) {
@@ -1863,7 +1888,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -3493,20 +3518,21 @@ int wfpt_nee_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
 
 int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
     if (int r = nee_check(c, "wfpt_sample_lights"); r != WFPT_OK) return r;
-    if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
+    if (!c->nee_lights.get() && !analytic_selecting(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_lights: no primitive emits");
     return probe(c, "wfpt_sample_lights", in9, 9, out8, 8, n, true,
                  [&](const float *d_in, float *d_out) { return launch_sampler(c, sampler_args(c, d_in, d_out, n), false, false); });
 }
 
 // ---------------------------------------------------------------- multiple importance sampling (include/wfpt.h "Multiple importance sampling")
-static int mis_check(wfpt_ctx *c, const char *who) {
+// analytic: an analytic light serves as well (wfpt_sample_lights_mis; wfpt_mis_hit_weight reads the emitters' tables)
+static int mis_check(wfpt_ctx *c, const char *who, bool analytic = false) {
     if (int r = flag_check(c, who, WFPT_FLAG_MIS, "WFPT_FLAG_MIS"); r != WFPT_OK) return r;
-    if (!c->nee_lights.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no primitive emits");
+    if (!c->nee_lights.get() && !(analytic && analytic_selecting(c))) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": no primitive emits");
     return WFPT_OK;
 }
 
 int wfpt_sample_lights_mis(wfpt_ctx *c, const float *in9, size_t n, float *out12) {
-    if (int r = mis_check(c, "wfpt_sample_lights_mis"); r != WFPT_OK) return r;
+    if (int r = mis_check(c, "wfpt_sample_lights_mis", true); r != WFPT_OK) return r;
     return probe(c, "wfpt_sample_lights_mis", in9, 9, out12, 12, n, true,
                  [&](const float *d_in, float *d_out) { return launch_sampler(c, sampler_args(c, d_in, d_out, n), false, true); });
 }
@@ -3514,7 +3540,7 @@ int wfpt_sample_lights_mis(wfpt_ctx *c, const float *in9, size_t n, float *out12
 int wfpt_mis_hit_weight(wfpt_ctx *c, const float *in8, size_t n, float *out4) {
     if (int r = mis_check(c, "wfpt_mis_hit_weight"); r != WFPT_OK) return r;
     return probe(c, "wfpt_mis_hit_weight", in8, 8, out4, 4, n, true, [&](const float *d_in, float *d_out) {
-        const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(c->n_lights)};
+        const MisArgs mis{c->scene.prim_geom, c->scene.prim_kind, c->scene.n_spheres, static_cast<float>(light_count(c))};
         const LightDist ld = light_dist(c);
         return launch_mis_weight(mis, c->scene.shade_rec, c->em_prim.get(), d_in, d_out, static_cast<uint32_t>(n), c->stream.get(),
                                  power_selecting(c) ? &ld : nullptr);
@@ -3530,6 +3556,77 @@ int wfpt_read_light_distribution(wfpt_ctx *c, uint32_t *light_prims, uint64_t *c
     if (light_prims) WFPT_HIP(c, hipMemcpy(light_prims, c->nee_lights.get(), sizeof(uint32_t) * c->n_lights, hipMemcpyDeviceToHost));
     if (cdf) WFPT_HIP(c, hipMemcpy(cdf, c->light_cdf.get(), sizeof(uint64_t) * c->n_lights, hipMemcpyDeviceToHost));
     return WFPT_OK;
+}
+
+// ---------------------------------------------------------------- analytic lights (include/wfpt.h "Analytic lights")
+static int lights_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_ANALYTIC_LIGHTS, "WFPT_FLAG_ANALYTIC_LIGHTS"); }
+
+static bool finite3(const float v[3]) { return std::fabs(v[0]) <= FLT_MAX && std::fabs(v[1]) <= FLT_MAX && std::fabs(v[2]) <= FLT_MAX; }
+
+int wfpt_set_lights(wfpt_ctx *c, const wfpt_light *lights, uint32_t n) {
+    const char *who = "wfpt_set_lights";
+    if (int r = lights_check(c, who); r != WFPT_OK) return r;
+    if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
+        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no lights");
+    if (n > WFPT_MAX_LIGHTS) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": more than WFPT_MAX_LIGHTS lights");
+    if (!lights && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null lights");
+    std::vector<wfpt_light> cand(lights, lights + (lights ? n : 0u));
+    for (wfpt_light &l : cand) {
+        const bool point = l.type == WFPT_LIGHT_POINT, spot = l.type == WFPT_LIGHT_SPOT, sun = l.type == WFPT_LIGHT_DIRECTIONAL;
+        if (!point && !spot && !sun) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown light type");
+        if (!sun && !finite3(l.position)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the position must be finite");
+        for (int k = 0; k < 3; ++k) {
+            if (!(l.colour[k] >= 0.0f && l.colour[k] <= FLT_MAX))
+                return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the colour must be finite and >= 0");
+            l.colour[k] = l.colour[k] + 0.0f; // (-0 -> +0)
+        }
+        if (!point) { // normalised once, here: one f32 operation each, in the header's order (this file is compiled without contraction)
+            if (!finite3(l.direction)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the direction must be finite");
+            const float x = l.direction[0], y = l.direction[1], z = l.direction[2];
+            const float xx = x * x, yy = y * y, zz = z * z;
+            const float s2 = xx + yy;
+            const float len2 = s2 + zz;
+            const float len = std::sqrt(len2);
+            if (!(len > 0.0f && len <= FLT_MAX)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the direction has no length");
+            l.direction[0] = x / len; l.direction[1] = y / len; l.direction[2] = z / len;
+        }
+        if (spot && !(-1.0f <= l.cos_outer && l.cos_outer < l.cos_inner && l.cos_inner <= 1.0f))
+            return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": a spot needs -1 <= cos_outer < cos_inner <= 1");
+    }
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float4> rows;
+    DeviceBuffer<float> plane;
+    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS: the hit-point plane comes and stays with the second plane
+    if (!cand.empty()) {
+        static_assert(sizeof(wfpt_light) == 3 * sizeof(float4), "a light is three rows");
+        WFPT_HIP(c, rows.alloc(3 * cand.size()));
+        WFPT_HIP(c, hipMemcpy(rows.get(), cand.data(), sizeof(wfpt_light) * cand.size(), hipMemcpyHostToDevice));
+        if (!c->emitted.get()) {
+            WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
+            WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
+            if (c->p.flags & WFPT_FLAG_MIS) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
+        }
+    }
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
+    if (plane.get()) c->emitted = std::move(plane);
+    if (origin.get()) c->mis_origin = std::move(origin);
+    c->light_rows = std::move(rows);
+    c->h_lights = std::move(cand);
+    return scene_changed(c);
+}
+
+int wfpt_get_lights(wfpt_ctx *c, wfpt_light *out, uint32_t capacity, uint32_t *n) {
+    if (int r = lights_check(c, "wfpt_get_lights"); r != WFPT_OK) return r;
+    if (!out && capacity) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_lights: null lights");
+    const size_t k = std::min<size_t>(capacity, c->h_lights.size());
+    if (k) std::memcpy(out, c->h_lights.data(), sizeof(wfpt_light) * k);
+    if (n) *n = static_cast<uint32_t>(c->h_lights.size());
+    return WFPT_OK;
+}
+
+int wfpt_analytic_light_count(wfpt_ctx *c) {
+    if (int r = lights_check(c, "wfpt_analytic_light_count"); r != WFPT_OK) return r;
+    return static_cast<int>(c->h_lights.size());
 }
 
 // ---------------------------------------------------------------- environment next-event estimation (include/wfpt.h)

@@ -1,7 +1,8 @@
-// The body of the connect kernels, included into connect_kernel and connect_power_kernel (wfpt_kernels.hip): one text, so that each kernel
+// The body of the connect kernels, included into connect_kernel, connect_power_kernel and connect_analytic_kernel (wfpt_kernels.hip): one text, so that each kernel
 // is compiled from its own statements and connect_kernel keeps its instructions whatever the other one gains (a shared function is optimised
 // on its own first, and then schedules differently). In scope: the kernel's template parameters Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS and
-// MIS, the constant POWER, the argument `a` (ConnectArgs) and `ld` (LightDist; read where POWER is set only).
+// MIS, the constants POWER and ANALYTIC, the argument `a` (ConnectArgs), `ld` (LightDist; read where POWER is set only) and `lt` (LightTable;
+// read where ANALYTIC is set only).
     extern __shared__ float4 lds[];
     WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
@@ -9,6 +10,7 @@
     const uint32_t per_smp = sampler ? (a.sample_n + kChunk - 1u) / kChunk : a.n_chunks_max;
     const uint32_t n_items = sampler ? per_smp : per_smp * a.w.batch.n;
     const uint32_t frame0 = sampler ? 0u : uniform(a.w.ctl->frame.frame); // the batch's first frame, as shade_kernel and aov_body take it
+    constexpr bool NO_EMITTERS = ENVS || ANALYTIC; // the kernels that run while no material emits (prim_em is null then)
     bool staged = false;
     for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
         const uint32_t smp = sampler ? 0u : item / per_smp, chunk = item - smp * per_smp;
@@ -70,8 +72,8 @@
             } else {
                 const uint32_t lp = local_pixel(pixel_idx, a.w.image_width, a.w.tile);
                 out = pixel_of(a.emitted + smp * static_cast<size_t>(a.w.batch.image_stride), lp);
-                // (ENVS: no emission table while no material emits)
-                if (m != 0u || ((!ENVS || a.prim_em) && a.prim_em[prim] != kNoEmission)) { // metal, dielectric, emitter: the flag is cleared, nothing else
+                // (ENVS, ANALYTIC: no emission table while no material emits)
+                if (m != 0u || ((!NO_EMITTERS || a.prim_em) && a.prim_em[prim] != kNoEmission)) { // metal, dielectric, emitter: the flag is cleared, nothing else
                     out->w = 0.0f;
                     live = false;
                 } else {
@@ -101,14 +103,15 @@
         LightSample s;
         bool lit = false, occluded = false;
         if (ENVS && to_env) lit = sample_env<MIS>(a.envd, n, u1, u2, u3, u4, share, s);
-        else if (live) lit = sample_light<PRIM, TEX, MIS, POWER>(a, p, n, u0, u1, u2, s, ld);
+        else if (live) lit = sample_light<PRIM, TEX, MIS, POWER, ANALYTIC>(a, p, n, u0, u1, u2, s, ld, lt);
         if (lit) {
 #if WFPT_STAMPS
             uint32_t dbg[3] = {0, 0, 0};
 #endif
             // (the map: any hit occludes. Started with the closest-hit walk's own far end the early-out walk answers "is there a hit": kOccNone
             // means the reference tests no primitive below 1e30, kOccHit that it accepts one)
-            const float window = (ENVS && to_env) ? 1e30f : s.dist * 0.999f;
+            float window = (ENVS && to_env) ? 1e30f : s.dist * 0.999f;
+            if (ANALYTIC && is_sun(s)) window = 1e30f; // (a directional light's sample takes the map's window and rule)
             uint32_t verdict = kOccUndecided;
             // scenes in LDS, conservative boxes: the early-out walk answers most rays (DESIGN.md 9h: 3.4 % of a Shirley frame, same booleans)
             if (WFPT_NEE_EARLY_OUT && LDS_SCENE && !EXACT && !far_origin(a.scene, p.x, p.y, p.z))
@@ -120,6 +123,7 @@
                 bool hit = false;
                 WFPT_TRACE_ANY(g_nodes, s_stack, p.x, p.y, p.z, s.w.x, s.w.y, s.w.z);
                 occluded = hit && ((ENVS && to_env) || t < window);
+                if (ANALYTIC && is_sun(s)) occluded = hit;
             } else {
                 occluded = verdict == kOccHit;
             }
@@ -127,10 +131,12 @@
         if (ENVS && MIS && !to_env && lit) s.pl = s.pl * share; // plq: the light list's density times the share of the samples that go to it
         if (MIS && live && sampler) { // (q, primitive, (e_q G) wl, occluded, pl, pb, wl, 0): zeros where the sample contributes nothing
             float *row = a.sample_out + 12u * (static_cast<size_t>(chunk) * kChunk + threadIdx.x);
-            const float wl = lit ? s.pl / (s.pl + s.pb) : 0.0f; // (sample_light sets pl and pb only where it answers true)
+            float wl = lit ? s.pl / (s.pl + s.pb) : 0.0f; // (sample_light sets pl and pb only where it answers true)
+            if (ANALYTIC && lit && is_analytic(s)) wl = 1.0f; // (the scatter never produces an analytic light's sample)
             if (ENVS) s.q = s.w; // (wdir, texel, (e Genv) we, occluded, pe, pb, we, 0)
             row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
             row[3] = static_cast<float>(s.prim);
+            if (ANALYTIC) row[3] = static_cast<float>(static_cast<int32_t>(s.prim)); // (analytic light j: -(1 + j))
             row[4] = lit ? (s.e.x * s.G) * wl : 0.0f; row[5] = lit ? (s.e.y * s.G) * wl : 0.0f; row[6] = lit ? (s.e.z * s.G) * wl : 0.0f;
             row[7] = occluded ? 1.0f : 0.0f;
             row[8] = lit ? s.pl : 0.0f; row[9] = lit ? s.pb : 0.0f; row[10] = wl; row[11] = 0.0f;
@@ -143,7 +149,8 @@
                 *out = make_float4(had.x + ((((thr.x * rec1.x) * s.e.x) * s.G) / share) * wl, had.y + ((((thr.y * rec1.y) * s.e.y) * s.G) / share) * wl,
                                    had.z + ((((thr.z * rec1.z) * s.e.z) * s.G) / share) * wl, 1.0f);
             } else if (lit && !occluded) {
-                const float wl = s.pl / (s.pl + s.pb);
+                float wl = s.pl / (s.pl + s.pb);
+                if (ANALYTIC && is_analytic(s)) wl = 1.0f; // (an analytic light's sample is not weighed: x * 1 is x)
                 *out = make_float4(had.x + (((thr.x * rec1.x) * s.e.x) * s.G) * wl, had.y + (((thr.y * rec1.y) * s.e.y) * s.G) * wl,
                                    had.z + (((thr.z * rec1.z) * s.e.z) * s.G) * wl, 1.0f);
             } else {
@@ -154,6 +161,7 @@
             if (ENVS) s.q = s.w;
             row[0] = s.q.x; row[1] = s.q.y; row[2] = s.q.z;
             row[3] = static_cast<float>(s.prim);
+            if (ANALYTIC) row[3] = static_cast<float>(static_cast<int32_t>(s.prim)); // (analytic light j: -(1 + j))
             row[4] = lit ? s.e.x * s.G : 0.0f; row[5] = lit ? s.e.y * s.G : 0.0f; row[6] = lit ? s.e.z * s.G : 0.0f;
             row[7] = occluded ? 1.0f : 0.0f;
         } else if (live) {

@@ -535,6 +535,13 @@ struct LightDist {
     uint64_t total;
 };
 
+// The analytic lights (WFPT_FLAG_ANALYTIC_LIGHTS, include/wfpt.h "Analytic lights"): three float4 rows per light, wfpt_light's own layout --
+// (position, type's bits), (direction as stored: normalised, cos_inner), (colour, cos_outer). Null / 0 while the context holds none.
+struct LightTable {
+    const float4 *rows;
+    uint32_t n;
+};
+
 // The connect pass (connect_kernel; WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): before a shade step, after that step's texture
 // and emission passes, every hit the step will shade either sends one shadow ray to a sampled point of a light and adds the unoccluded
 // sample to the pixel's `emitted` (a diffuse hit: the pixel's connected flag, emitted.w, becomes 1) or only clears the flag (every other
@@ -559,6 +566,11 @@ struct LightDist {
 // search of the distribution's cdf and weighed by nfi = f32(total) / f32(k) wherever nf stands; with and without MIS, render and sampler
 // forms alike. Their kernels (connect_power_kernel) take the LightDist as a second argument: ConnectArgs, and with it the kernels above, stay
 // as they are.
+// The ANALYTIC variants (WFPT_FLAG_ANALYTIC_LIGHTS contexts that hold an analytic light; never with ENVS or POWER; include/wfpt.h
+// "Analytic lights"): the selection runs over the emitters followed by the analytic lights, N = n_lights + n, and Nf = f32(N) stands
+// wherever nf does; an index past the emitters evaluates a point, spot or directional light with no area, no cos_l and no texture, and
+// under MIS with wl = 1. Their kernels (connect_analytic_kernel) take the LightTable as a second argument: ConnectArgs, and with it the
+// kernels above, stay as they are. n_lights may be 0 there (lights, prim_em and em null).
 struct ConnectArgs {
     HitWalk w;
     float *emitted;
@@ -783,8 +795,9 @@ hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const ui
 // envs: the ENVS variants (a.envd holds a distribution)
 // mis: the MIS variants (a.origin set, or the sampler form's rows out); with envs, the ENVS MIS variants
 // power (null = none): the POWER variants with this distribution (never with envs)
+// analytic (null = none): the ANALYTIC variants with this table (never with envs or power)
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false,
-                          const LightDist *power = nullptr);
+                          const LightDist *power = nullptr, const LightTable *analytic = nullptr);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the

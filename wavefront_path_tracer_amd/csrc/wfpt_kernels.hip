@@ -3756,16 +3756,58 @@ struct LightSample {
     uint32_t prim;
     float pl, pb; // MIS only: the solid-angle densities of this sample under the light list's area sampling and under shade's scatter
 };
+// ANALYTIC, an index past the emitters (include/wfpt.h "Analytic lights"; tests/analytic_lights_ref.py restates it): light j of the table,
+// one straight-line path for the three types -- three 16-byte loads, then point, spot and directional evaluated side by side and chosen
+// by selects on the type, so that the lanes of a wave, which part in j, share every instruction. A directional light reads no position
+// (whatever v holds is selected away). nf: Nf. LightSample keeps its layout (with it connect_kernel keeps its registers): analytic light j
+// is told by prim = -(1 + j) in two's complement -- is_analytic; a primitive index never has that bit, the hit queue keeps it for its own
+// use -- and a directional one by dist = +inf -- is_sun.
+__device__ __forceinline__ bool is_analytic(const LightSample &s) { return static_cast<int32_t>(s.prim) < 0; }
+__device__ __forceinline__ bool is_sun(const LightSample &s) { return is_analytic(s) && s.dist > 3.0e38f; }
+template <bool MIS>
+__device__ __forceinline__ bool sample_analytic(const LightTable &lt, uint32_t j, float nf, float3_ p, float3_ n, LightSample &s) {
+    const float4 r0 = lt.rows[3u * j], r1 = lt.rows[3u * j + 1u], r2 = lt.rows[3u * j + 2u];
+    const uint32_t type = __float_as_uint(r0.w);
+    const bool sun = type == static_cast<uint32_t>(WFPT_LIGHT_DIRECTIONAL), spot = type == static_cast<uint32_t>(WFPT_LIGHT_SPOT);
+    const float3_ v = {r0.x - p.x, r0.y - p.y, r0.z - p.z};
+    const float dist2 = dot3(v, v);
+    const float dist = sqrt_(dist2);
+    const float3_ wp = {v.x / dist, v.y / dist, v.z / dist};
+    s.w = {sun ? -r1.x : wp.x, sun ? -r1.y : wp.y, sun ? -r1.z : wp.z};
+    const float cos_s = dot3(n, s.w);
+    const float cd = -dot3({r1.x, r1.y, r1.z}, wp);
+    float t = (cd - r2.w) / (r1.w - r2.w);
+    t = t > 0.0f ? t : 0.0f; // (a NaN gives 0)
+    t = t < 1.0f ? t : 1.0f;
+    const float fall = spot ? (t * t) * (3.0f - 2.0f * t) : 1.0f;
+    s.G = sun ? (cos_s * nf) / kPi : ((cos_s * fall) * nf) / (kPi * dist2);
+    s.q = {sun ? s.w.x : r0.x, sun ? s.w.y : r0.y, sun ? s.w.z : r0.z};
+    s.e = {r2.x, r2.y, r2.z};
+    s.dist = sun ? __builtin_inff() : dist;
+    s.prim = ~j;
+    if (MIS) { // the scatter never produces this sample: wl = 1 (the body), pl is reported as 0
+        s.pb = cos_s / kPi;
+        s.pl = 0.0f;
+    }
+    return cos_s > 0.0f && (sun || (dist2 > 0.0f && fall > 0.0f));
+}
 // POWER (include/wfpt.h "Light selection by power"; tests/light_power_ref.py restates it): the light is the first one whose cdf entry
 // exceeds T = floor(f64(u0) * f64(total)) -- T clamped into [0, total - 1], so a NaN or negative u0 of a caller's row selects 0 and every
 // index read lies inside the table -- and nfi = f32(total) / f32(k) stands wherever nf does. The search's upper levels are the same
 // addresses for every lane of a wave (one cache line each); the lanes part only in the last levels.
-template <int PRIM, bool TEX, bool MIS = false, bool POWER = false>
+// ANALYTIC (include/wfpt.h "Analytic lights"): the index runs over N = n_lights + lt.n, Nf = f32(N) stands wherever nf does, and an index
+// past the emitters is sample_analytic's. The one divergence this adds is emitter against analytic light.
+template <int PRIM, bool TEX, bool MIS = false, bool POWER = false, bool ANALYTIC = false>
 __device__ __forceinline__ bool sample_light(const ConnectArgs &a, float3_ p, float3_ n, float u0, float u1, float u2, LightSample &s,
-                                             const LightDist &ld = LightDist{}) {
+                                             const LightDist &ld = LightDist{}, const LightTable &lt = LightTable{}) {
     float nl_f = static_cast<float>(a.n_lights);
     uint32_t i;
-    if (POWER) {
+    if (ANALYTIC) {
+        const uint32_t n_all = a.n_lights + lt.n; // > 0: the host launches nothing otherwise
+        nl_f = static_cast<float>(n_all);
+        i = umin(static_cast<uint32_t>(min_(max_(__builtin_floorf(u0 * nl_f), 0.0f), nl_f)), n_all - 1u);
+        if (i >= a.n_lights) return sample_analytic<MIS>(lt, i - a.n_lights, nl_f, p, n, s);
+    } else if (POWER) {
         const double ft = static_cast<double>(ld.total);
         const double tr = __builtin_floor(static_cast<double>(u0) * ft);
         const uint64_t T = tr >= 0.0 ? (tr < ft ? static_cast<uint64_t>(tr) : ld.total - 1u) : 0u;
@@ -3886,15 +3928,26 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // the share of its own branch; the point is stored as above. The sampler form is the map's, with the effective share and 12 floats a row.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
-    constexpr bool POWER = false;
+    constexpr bool POWER = false, ANALYTIC = false;
     const LightDist ld{};
+    const LightTable lt{};
 #include "wfpt_connect_body.inc"
 }
 // POWER (WFPT_FLAG_LIGHT_POWER contexts whose light list has a distribution; never with ENVS): sample_light selects by ld and weighs by
 // nfi; nothing else differs. The distribution is a second argument: connect_kernel keeps its name, its arguments and its instructions.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectArgs a, LightDist ld) {
-    constexpr bool ENVS = false, POWER = true;
+    constexpr bool ENVS = false, POWER = true, ANALYTIC = false;
+    const LightTable lt{};
+#include "wfpt_connect_body.inc"
+}
+// ANALYTIC (WFPT_FLAG_ANALYTIC_LIGHTS contexts that hold an analytic light; never with ENVS or POWER): sample_light selects among the
+// emitters and the table's lights and evaluates the latter; a directional sample takes the map branch's walk (no far end, any hit
+// occludes); under MIS an analytic sample is not weighed. The table is a second argument, as the distribution above.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
+__global__ __launch_bounds__(kExtendThreads) void connect_analytic_kernel(ConnectArgs a, LightTable lt) {
+    constexpr bool ENVS = false, POWER = false, ANALYTIC = true;
+    const LightDist ld{};
 #include "wfpt_connect_body.inc"
 }
 
@@ -4811,19 +4864,29 @@ struct ConnectPowerK {
     }
 };
 using ConnectPower = Family<ConnectPowerK, Bool, Bool>;
+using ConnectAnalyticFn = void (*)(ConnectArgs, LightTable);
+struct ConnectAnalyticK {
+    template <bool TEX, bool MIS, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectAnalyticFn get() {
+        return connect_analytic_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, MIS>;
+    }
+};
+using ConnectAnalytic = Family<ConnectAnalyticK, Bool, Bool>;
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
-    return allow_dynamic_lds<Connect, ConnectPower>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
+    return allow_dynamic_lds<Connect, ConnectPower, ConnectAnalytic>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
 }
 
-hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power) {
-    if (grid == 0 || (a.n_lights == 0 && !envs)) return hipSuccess;
+hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power,
+                          const LightTable *analytic) {
+    if (grid == 0 || (a.n_lights == 0 && !envs && !analytic)) return hipSuccess;
+    if (analytic && (envs || power || !analytic->rows || analytic->n == 0)) return hipErrorInvalidValue;
     if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
     if (power && (envs || !power->cdf || power->total == 0)) return hipErrorInvalidValue;
     const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
     const dim3 g(grid), b(kExtendThreads);
-    if (power) hipLaunchKernelGGL(ConnectPower::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *power);
+    if (analytic) hipLaunchKernelGGL(ConnectAnalytic::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *analytic);
+    else if (power) hipLaunchKernelGGL(ConnectPower::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *power);
     else hipLaunchKernelGGL(Connect::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
 }

@@ -389,6 +389,23 @@ class PathTracer {
         check(wfpt_read_light_distribution(ctx_, t.first.data(), t.second.data()));
         return t;
     }
+    // Analytic lights (WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ANALYTIC_LIGHTS, include/wfpt.h "Analytic lights"): point, spot and
+    // directional lights for the connect pass; an empty vector clears them. lights() returns them as stored (directions normalised).
+    void set_lights(const std::vector<wfpt_light> &lights) {
+        check(wfpt_set_lights(ctx_, lights.empty() ? nullptr : lights.data(), static_cast<uint32_t>(lights.size())));
+    }
+    std::vector<wfpt_light> lights() {
+        std::vector<wfpt_light> out(analytic_light_count());
+        uint32_t n = 0;
+        check(wfpt_get_lights(ctx_, out.empty() ? nullptr : out.data(), static_cast<uint32_t>(out.size()), &n));
+        out.resize(std::min<size_t>(out.size(), n));
+        return out;
+    }
+    uint32_t analytic_light_count() {
+        const int n = wfpt_analytic_light_count(ctx_);
+        if (n < 0) check(n);
+        return static_cast<uint32_t>(n);
+    }
     // Environment next-event estimation (the three flags above | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_ENV_NEE, include/wfpt.h "Environment
     // next-event estimation"): the map as one more light of the connect pass, sampled in proportion to its radiance.
     void set_environment_share(float share) { check(wfpt_set_environment_share(ctx_, share)); }
