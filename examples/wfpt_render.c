@@ -3,9 +3,11 @@
  *
  *   gcc -std=c99 -O1 -Iinclude examples/wfpt_render.c -Lwavefront_path_tracer_amd -lwfpt \
  *       -Wl,-rpath,$PWD/wavefront_path_tracer_amd -lm -o wfpt_render
- *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--adaptive]
+ *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj] [--adaptive]
  * --adaptive: a WFPT_FLAG_ADAPTIVE context rendered with wfpt_render_adaptive (at most spp passes, an update every 8) at the default
  * parameters; the image written is the mean (each pixel divided by its own sample count).
+ * --obj-normals mesh.obj: instead of the book's scene, the triangles of a Wavefront OBJ file (grey Lambertian, about the origin, seen from
+ * (0, 1, 4.5)) shaded with the file's `vn` vertex normals: a WFPT_FLAG_SHADING_NORMALS context and wfpt_set_triangle_normals.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,17 +27,69 @@
 int main(int argc, char **argv) {
     wfpt_ctx *ctx = NULL;
     int adaptive = 0;
+    const char *obj = NULL;
     if (argc > 2 && strcmp(argv[argc - 1], "--adaptive") == 0) {
         adaptive = 1;
         argc -= 1;
     }
+    if (argc > 3 && strcmp(argv[argc - 2], "--obj-normals") == 0) {
+        obj = argv[argc - 1];
+        argc -= 2;
+    }
     if (argc < 2) {
-        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--adaptive]\n", argv[0]);
+        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj] [--adaptive]\n", argv[0]);
         return 2;
     }
     const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[2]) : 400, height = argc > 3 ? (uint32_t)atoi(argv[3]) : 225;
     const uint32_t spp = argc > 4 ? (uint32_t)atoi(argv[4]) : 8, bounces = argc > 5 ? (uint32_t)atoi(argv[5]) : 8;
     const int device_bvh = argc > 6 ? atoi(argv[6]) : 0;
+    if (obj) { /* a mesh with per-vertex normals (build extension; include/wfpt.h "Shading normals") */
+        uint32_t n_tris = 0, n_mesh_nodes = 0;
+        CHECK(wfpt_load_obj_normals(obj, NULL, NULL, NULL, 0, &n_tris, 0, 0));
+        if (n_tris == 0) {
+            fprintf(stderr, "%s holds no triangle\n", obj);
+            return 1;
+        }
+        wfpt_triangle *tris = (wfpt_triangle *)calloc(n_tris, sizeof *tris);
+        float *n9 = (float *)calloc(9u * (size_t)n_tris, sizeof *n9);
+        wfpt_bvh_node *mesh_nodes = (wfpt_bvh_node *)calloc(2u * (size_t)n_tris, sizeof *mesh_nodes);
+        wfpt_material grey;
+        memset(&grey, 0, sizeof grey);
+        grey.albedo[0] = grey.albedo[1] = grey.albedo[2] = 0.7f;
+        grey.albedo[3] = 1.0f;
+        CHECK(wfpt_load_obj_normals(obj, tris, NULL, n9, n_tris, &n_tris, 0, 0)); /* triangle i: _pad = i, row i of n9 */
+        CHECK(wfpt_build_bvh_triangles(tris, n_tris, mesh_nodes, 2u * n_tris, &n_mesh_nodes, 32)); /* reorders: the rows follow by _pad */
+        const float from[3] = {0.0f, 1.0f, 4.5f}, at[3] = {0.0f, 0.0f, 0.0f};
+        float pitch, yaw, view[16], inv_proj[16];
+        wfpt_gpu_camera camera;
+        wfpt_camera_new(from, at, &pitch, &yaw);
+        wfpt_view_transform(from, pitch, yaw, view);
+        wfpt_p_inv(wfpt_to_radians(40.0f), (float)width / (float)height, 0.1f, 100.0f, inv_proj);
+        wfpt_gpu_camera_new(from, pitch, yaw, 0.0f, 10.0f, &camera);
+        wfpt_params params;
+        memset(&params, 0, sizeof params);
+        params.width = width;
+        params.height = height;
+        params.max_wavefronts = bounces;
+        params.miss_floor = 128;
+        params.flags = WFPT_FLAG_SHADING_NORMALS | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u);
+        ctx = wfpt_create_mesh(&params, tris, n_tris, &grey, 1, mesh_nodes, n_mesh_nodes, &camera, inv_proj, view);
+        if (!ctx) {
+            fprintf(stderr, "wfpt_create_mesh: %s\n", wfpt_last_error(NULL));
+            return 1;
+        }
+        CHECK(wfpt_set_triangle_normals(ctx, n9, n_tris));
+        uint32_t still = 0;
+        if (adaptive) CHECK(wfpt_render_adaptive(ctx, spp, 8, &still));
+        else CHECK(wfpt_render(ctx, spp));
+        CHECK(wfpt_save_ppm(ctx, argv[1]));
+        printf("%ux%u, %u spp, %u bounces: %u triangles of %s with their vertex normals -> %s\n", width, height, spp, bounces, n_tris, obj, argv[1]);
+        wfpt_destroy(ctx);
+        free(mesh_nodes);
+        free(n9);
+        free(tris);
+        return 0;
+    }
 
     /* main.rs:20: the book's final scene (seeded here), path_tracer.rs:117-118: its BVH */
     wfpt_sphere spheres[512];

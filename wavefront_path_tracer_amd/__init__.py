@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -59,6 +59,8 @@ FLAG_LIGHT_POWER = 1 << 22
 # point, spot and directional lights for the connect pass (include/wfpt.h "Analytic lights"); needs FLAG_EMISSION and FLAG_NEE, refused with
 # FLAG_ENV_NEE, FLAG_ENV_MIS and FLAG_LIGHT_POWER
 FLAG_ANALYTIC_LIGHTS = 1 << 23
+# per-vertex shading normals on triangle meshes (include/wfpt.h "Shading normals"); refused with FLAG_LIGHT_POWER and FLAG_ANALYTIC_LIGHTS
+FLAG_SHADING_NORMALS = 1 << 24
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2  # wfpt_light_type
 MAX_LIGHTS = 1024  # WFPT_MAX_LIGHTS
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
@@ -376,6 +378,12 @@ def lib():
         "wfpt_sample_texture": (i32, [vp, u32, vp, sz, vp]),
         "wfpt_texture_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
         "wfpt_load_obj_uv": (i32, [C.c_char_p, vp, vp, u32, C.POINTER(u32), u32, u32]),
+        "wfpt_load_obj_normals": (i32, [C.c_char_p, vp, vp, vp, u32, C.POINTER(u32), u32, u32]),
+        "wfpt_normalize_triangle_normals": (i32, [vp, u32, vp]),
+        "wfpt_set_triangle_normals": (i32, [vp, vp, u32]),
+        "wfpt_get_triangle_normals": (i32, [vp, vp, u32, C.POINTER(u32)]),
+        "wfpt_sample_shading_normal": (i32, [vp, vp, sz, vp]),
+        "wfpt_shading_normal_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
         "wfpt_set_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_clear_emission": (i32, [vp]),
@@ -729,9 +737,27 @@ class Scene:
         return cls(np.zeros(0, SPHERE), materials, triangles=tris)
 
     @classmethod
-    def load_obj(cls, path, materials=None, material_idx=0, uvs=False):
+    def load_obj(cls, path, materials=None, material_idx=0, uvs=False, normals=False):
         """from_obj; with uvs=True returns (scene, uv) -- the (n, 6) float32 UV rows u0 v0 u1 v1 u2 v2 of the triangles in file order (each
-        triangle's _pad names its row), for PathTracer.set_triangle_uvs."""
+        triangle's _pad names its row), for PathTracer.set_triangle_uvs. With normals=True returns (scene, normals), or (scene, uv, normals)
+        with uvs=True too -- the (n, 9) float32 rows of corner normals as the file gives them (a corner without one: the face's own), for
+        PathTracer.set_triangle_normals; a face wound against its normals has its winding swapped (wfpt_load_obj_normals)."""
+        if normals:
+            if materials is None:
+                materials = np.zeros(1, MATERIAL)
+                materials["albedo"][0] = (0.7, 0.7, 0.7, 1.0)
+            materials = np.ascontiguousarray(materials, MATERIAL)
+            n = C.c_uint32()
+            st = lib().wfpt_load_obj_normals(os.fsencode(path), None, None, None, 0, C.byref(n), 0, 0)
+            if st != 0 or n.value == 0:
+                raise WfptError(st or ERR_INVALID_ARGUMENT, f"cannot read triangles from {path}")
+            tris, uv, n9 = np.zeros(n.value, TRIANGLE), np.zeros((n.value, 6), "<f4"), np.zeros((n.value, 9), "<f4")
+            mtype = int(materials["material_type"][material_idx])
+            st = lib().wfpt_load_obj_normals(os.fsencode(path), _p(tris), _p(uv), _p(n9), len(tris), C.byref(n), material_idx, mtype)
+            if st != 0:
+                raise WfptError(st, f"cannot read triangles from {path}")
+            scene = cls(np.zeros(0, SPHERE), materials, triangles=tris)
+            return (scene, uv, n9) if uvs else (scene, n9)
         if not uvs:
             return cls.from_obj(path, materials, material_idx)
         if materials is None:
@@ -1460,6 +1486,37 @@ class PathTracer:
         """(milliseconds, launches) of the texture launches of every timed render since creation (apart from render_timed's stage times)."""
         ms, n = C.c_float(0.0), C.c_uint32(0)
         self._check(lib().wfpt_texture_timing_ms(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    # ---- shading normals (triangle contexts created with FLAG_SHADING_NORMALS; include/wfpt.h "Shading normals")
+    def set_triangle_normals(self, n):
+        """The table of corner normals: (n, 9) rows of the normals of corners 0, 1, 2 (finite; normalised as stored); a triangle uses the
+        row its _pad names. None clears it. Restarts the accumulation like a scene update."""
+        if n is None:
+            self._check(lib().wfpt_set_triangle_normals(self.handle, None, 0))
+        else:
+            a = np.ascontiguousarray(n, "<f4").reshape(-1, 9)
+            self._check(lib().wfpt_set_triangle_normals(self.handle, _p(a), a.shape[0]))
+        self.render_progress.reset()
+
+    def triangle_normals(self):
+        """The table as stored, (n, 9) float32 (n = 0: none is set)."""
+        n = C.c_uint32(0)
+        self._check(lib().wfpt_get_triangle_normals(self.handle, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 9), "<f4")
+        if len(out):
+            self._check(lib().wfpt_get_triangle_normals(self.handle, _p(out), len(out), C.byref(n)))
+        return out
+
+    def sample_shading_normal(self, rows):
+        """The shading normal for caller-supplied hits, computed on the device. rows: (n, 4) float32 of (p.xyz, the triangle's index in the
+        device's order as the BITS of the fourth float); returns (n, 4) float32 of (ns.xyz, 1.0 where it fell back to the stored normal)."""
+        return self._probe(lib().wfpt_sample_shading_normal, "sample_shading_normal", rows, 4, 4)
+
+    def shading_normal_timing(self):
+        """(milliseconds, launches) of the shading-normal launches of every timed render since creation (apart from render_timed's stage times)."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(lib().wfpt_shading_normal_timing_ms(self.handle, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     # ---- emission (contexts created with FLAG_EMISSION; include/wfpt.h "Emission")

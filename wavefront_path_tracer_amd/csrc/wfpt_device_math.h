@@ -216,20 +216,42 @@ __host__ __device__ __forceinline__ void sphere_uv(float3_ n, float &u, float &v
     v = atan2_(sqrt_(n.x * n.x + n.z * n.z), -n.y) * 0.31830988f;
 }
 
+// The barycentrics b0, b1, b2 of point p on the triangle (v0, e1, e2), from the normal equations; b1 = b2 = 0 unless den > 0. One text
+// for triangle_uv and shading_normal (a macro: each user is compiled from these statements, in this order)
+#define WFPT_TRIANGLE_BARYCENTRICS(p, v0, e1, e2)                                                                          \
+    const float3_ w = {p.x - v0.x, p.y - v0.y, p.z - v0.z};                                                                \
+    const float d00 = dot3(e1, e1), d01 = dot3(e1, e2), d11 = dot3(e2, e2), d20 = dot3(w, e1), d21 = dot3(w, e2);          \
+    const float den = d00 * d11 - d01 * d01;                                                                               \
+    float b1 = 0.0f, b2 = 0.0f;                                                                                            \
+    if (den > 0.0f) {                                                                                                      \
+        const float inv = 1.0f / den;                                                                                      \
+        b1 = (d11 * d20 - d01 * d21) * inv;                                                                                \
+        b2 = (d00 * d21 - d01 * d20) * inv;                                                                                \
+    }                                                                                                                      \
+    const float b0 = (1.0f - b1) - b2
+
 // (u, v) of point p on the triangle (v0, e1, e2) with corner UVs uv[0..5] = u0 v0 u1 v1 u2 v2: barycentrics from the normal equations
 __host__ __device__ __forceinline__ void triangle_uv(float3_ p, float3_ v0, float3_ e1, float3_ e2, const float *uv, float &u, float &v) {
-    const float3_ w = {p.x - v0.x, p.y - v0.y, p.z - v0.z};
-    const float d00 = dot3(e1, e1), d01 = dot3(e1, e2), d11 = dot3(e2, e2), d20 = dot3(w, e1), d21 = dot3(w, e2);
-    const float den = d00 * d11 - d01 * d01;
-    float b1 = 0.0f, b2 = 0.0f;
-    if (den > 0.0f) {
-        const float inv = 1.0f / den;
-        b1 = (d11 * d20 - d01 * d21) * inv;
-        b2 = (d00 * d21 - d01 * d20) * inv;
-    }
-    const float b0 = (1.0f - b1) - b2;
+    WFPT_TRIANGLE_BARYCENTRICS(p, v0, e1, e2);
     u = (uv[0] * b0 + uv[2] * b1) + uv[4] * b2;
     v = (uv[1] * b0 + uv[3] * b1) + uv[5] * b2;
+}
+
+// ---------------- shading normals (WFPT_FLAG_SHADING_NORMALS; include/wfpt.h "Shading normals") ----------------
+// The same rules as the textures: IEEE f32 add / sub / mul / div / sqrt and comparisons, no fma; restated bit for bit by
+// tests/shading_normals_ref.py. The normal shade scatters about at point p of the triangle (v0, e1, e2) with stored normal ng and corner
+// normals n0, n1, n2: the corner normals weighed by triangle_uv's barycentrics and normalised, or ng where that has no length (zero, NaN
+// or infinite) or leaves ng's hemisphere. Returns true where it fell back to ng.
+__host__ __device__ __forceinline__ bool shading_normal(float3_ p, float3_ v0, float3_ e1, float3_ e2, float3_ ng, float3_ n0, float3_ n1,
+                                                        float3_ n2, float3_ &ns) {
+    WFPT_TRIANGLE_BARYCENTRICS(p, v0, e1, e2);
+    const float3_ m = {(n0.x * b0 + n1.x * b1) + n2.x * b2, (n0.y * b0 + n1.y * b1) + n2.y * b2, (n0.z * b0 + n1.z * b1) + n2.z * b2};
+    const float l2 = dot3(m, m);
+    const float il = 1.0f / sqrt_(l2); // normalize3's own expressions
+    ns = {m.x * il, m.y * il, m.z * il};
+    const bool keep = l2 > 0.0f && l2 < __builtin_inff() && dot3(ns, ng) > 0.0f; // (a NaN fails each)
+    if (!keep) ns = ng;
+    return !keep;
 }
 
 // index of a texel coordinate c0 (floor of a float, expected in -1 .. n-1) and of c0 + 1, both wrapped into 0 .. n-1; NaN reads index n-1

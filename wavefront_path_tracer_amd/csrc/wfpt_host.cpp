@@ -10,6 +10,7 @@
 #include "wfpt_tile_lists.h"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -473,16 +474,30 @@ int wfpt_build_bvh_triangles(wfpt_triangle *tris, uint32_t n, wfpt_bvh_node *nod
     return WFPT_OK;
 }
 
-// The OBJ reader behind wfpt_load_obj and wfpt_load_obj_uv. uvs: also read `vt` records and the faces' texture indices into uv6 (when
-// triangles are written), and number each triangle's row in _pad.
+// normalize3's expressions on the host (this file is compiled without contraction); a vector whose squared length is not a finite number
+// above 0 becomes +0
+static Vec3 unit_or_zero(Vec3 v) {
+    const float l2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
+    if (!(l2 > 0.0f && l2 <= FLT_MAX)) return Vec3{0.0f, 0.0f, 0.0f};
+    const float inv = 1.0f / std::sqrt(l2);
+    return Vec3{v.x * inv, v.y * inv, v.z * inv};
+}
+static Vec3 cross3(const float a[3], const float b[3]) {
+    return Vec3{a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+}
+
+// The OBJ reader behind wfpt_load_obj, wfpt_load_obj_uv and wfpt_load_obj_normals. uvs: also read `vt` records and the faces' texture
+// indices into uv6 (when triangles are written and uv6 is given), and number each triangle's row in _pad. normals (with uvs): also read
+// `vn` records and the faces' normal indices into n9, and swap the winding of a face wound against its normals.
 static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool uvs, uint32_t capacity, uint32_t *n_tris,
-                         uint32_t material_idx, uint32_t material_type) {
+                         uint32_t material_idx, uint32_t material_type, float *n9 = nullptr, bool normals = false) {
     if (!path || !n_tris) return WFPT_ERR_INVALID_ARGUMENT;
     std::FILE *f = std::fopen(path, "r");
     if (!f) return WFPT_ERR_INVALID_ARGUMENT;
     std::vector<Vec3> verts;
     std::vector<std::pair<float, float>> tex;
-    std::vector<long long> face, face_t; // face_t: -1 = no texture index
+    std::vector<Vec3> nrm;
+    std::vector<long long> face, face_t, face_n; // face_t, face_n: -1 = no texture / normal index
     uint32_t count = 0;
     int status = WFPT_OK;
     char line[4096];
@@ -497,9 +512,14 @@ static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool
             float u = 0.0f, v = 0.0f;
             if (std::sscanf(p + 2, "%f %f", &u, &v) != 2) status = WFPT_ERR_INVALID_ARGUMENT;
             tex.emplace_back(u, v);
+        } else if (normals && p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) { // vn x y z
+            Vec3 v{0.0f, 0.0f, 0.0f};
+            if (std::sscanf(p + 2, "%f %f %f", &v.x, &v.y, &v.z) != 3) status = WFPT_ERR_INVALID_ARGUMENT;
+            nrm.push_back(v);
         } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
             face.clear();
             face_t.clear();
+            face_n.clear();
             char *q = const_cast<char *>(p + 1);
             for (;;) {
                 while (*q == ' ' || *q == '\t') ++q;
@@ -518,6 +538,17 @@ static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool
                     tidx = t;
                     end = tend;
                 }
+                long long nidx = -1;
+                if (normals && *end == '/' && (end[1] == '/' || tidx >= 0)) { // i//n or the n of i/t/n
+                    char *ns = end + (end[1] == '/' ? 2 : 1), *nend = nullptr;
+                    long long k = std::strtoll(ns, &nend, 10);
+                    if (nend == ns) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
+                    if (k < 0) k += static_cast<long long>(nrm.size());
+                    else k -= 1;
+                    if (k < 0 || k >= static_cast<long long>(nrm.size())) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
+                    nidx = k;
+                    end = nend;
+                }
                 while (*end && *end != ' ' && *end != '\t' && *end != '\n' && *end != '\r') ++end;
                 q = end;
                 if (idx < 0) idx += static_cast<long long>(verts.size()); // relative to the vertices read so far
@@ -525,6 +556,7 @@ static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool
                 if (idx < 0 || idx >= static_cast<long long>(verts.size())) { status = WFPT_ERR_INVALID_ARGUMENT; break; }
                 face.push_back(idx);
                 face_t.push_back(tidx);
+                face_n.push_back(nidx);
             }
             for (size_t k = 2; status == WFPT_OK && k < face.size(); ++k) { // fan around the first vertex
                 if (tris) {
@@ -543,6 +575,26 @@ static int load_obj_impl(const char *path, wfpt_triangle *tris, float *uv6, bool
                             uv6[6 * static_cast<size_t>(count) + 2 * j] = corner[j] >= 0 ? tex[corner[j]].first : 0.0f;
                             uv6[6 * static_cast<size_t>(count) + 2 * j + 1] = corner[j] >= 0 ? tex[corner[j]].second : 0.0f;
                         }
+                    }
+                    if (normals && n9) {
+                        const long long corner[3] = {face_n[0], face_n[k - 1], face_n[k]};
+                        const Vec3 own = unit_or_zero(cross3(t.e1, t.e2)); // the face's own normal, for the corners without one
+                        Vec3 cn[3];
+                        for (int j = 0; j < 3; ++j) cn[j] = corner[j] >= 0 ? nrm[corner[j]] : own;
+                        const Vec3 cr = cross3(t.e1, t.e2);
+                        const Vec3 sum{(cn[0].x + cn[1].x) + cn[2].x, (cn[0].y + cn[1].y) + cn[2].y, (cn[0].z + cn[1].z) + cn[2].z};
+                        if ((cr.x * sum.x + cr.y * sum.y) + cr.z * sum.z < 0.0f) { // wound against its normals: swap corners 1 and 2
+                            for (int ax = 0; ax < 3; ++ax) std::swap(t.e1[ax], t.e2[ax]);
+                            std::swap(cn[1], cn[2]);
+                            const Vec3 flipped{own.x * -1.0f, own.y * -1.0f, own.z * -1.0f};
+                            if (corner[0] < 0) cn[0] = flipped;
+                            if (corner[2] < 0) cn[1] = flipped; // (corner k of the file is corner 1 now)
+                            if (corner[1] < 0) cn[2] = flipped;
+                            if (uv6)
+                                for (int j = 0; j < 2; ++j) std::swap(uv6[6 * static_cast<size_t>(count) + 2 + j], uv6[6 * static_cast<size_t>(count) + 4 + j]);
+                        }
+                        float *row = n9 + 9 * static_cast<size_t>(count);
+                        for (int j = 0; j < 3; ++j) { row[3 * j] = cn[j].x; row[3 * j + 1] = cn[j].y; row[3 * j + 2] = cn[j].z; }
                     }
                 }
                 count += 1;
@@ -563,6 +615,24 @@ int wfpt_load_obj_uv(const char *path, wfpt_triangle *tris, float *uv6, uint32_t
                      uint32_t material_type) {
     if (tris && !uv6) return WFPT_ERR_INVALID_ARGUMENT;
     return load_obj_impl(path, tris, uv6, true, capacity, n_tris, material_idx, material_type);
+}
+
+int wfpt_load_obj_normals(const char *path, wfpt_triangle *tris, float *uv6, float *n9, uint32_t capacity, uint32_t *n_tris,
+                          uint32_t material_idx, uint32_t material_type) {
+    if (tris && !n9) return WFPT_ERR_INVALID_ARGUMENT;
+    return load_obj_impl(path, tris, uv6, true, capacity, n_tris, material_idx, material_type, n9, true);
+}
+
+int wfpt_normalize_triangle_normals(const float *n9, uint32_t n_rows, float *out9) {
+    if ((!n9 || !out9) && n_rows) return WFPT_ERR_INVALID_ARGUMENT;
+    const size_t n = 3 * static_cast<size_t>(n_rows);
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!(std::fabs(n9[i]) <= FLT_MAX)) return WFPT_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n; ++i) {
+        const Vec3 u = unit_or_zero(Vec3{n9[3 * i], n9[3 * i + 1], n9[3 * i + 2]});
+        out9[3 * i] = u.x; out9[3 * i + 1] = u.y; out9[3 * i + 2] = u.z;
+    }
+    return WFPT_OK;
 }
 
 uint32_t wfpt_scene_random_mesh(uint64_t seed, uint32_t n, wfpt_triangle *tris, wfpt_material *mt) {

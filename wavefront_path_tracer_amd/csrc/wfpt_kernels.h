@@ -597,6 +597,23 @@ struct MisArgs {
     float nf;                 // f32(n_lights)
 };
 
+// The shading-normal pass (shading_normal_kernel; WFPT_FLAG_SHADING_NORMALS contexts that hold a table, include/wfpt.h "Shading normals"):
+// the last pass before a shade step that scatters. For every hit the step will shade it forms the shading normal ns (shading_normal) and
+// writes the hit's own shade record -- (ns | fuzz), rec1, rec2: the primitive's ShadeRec with ns in the stored normal's place -- at the
+// hit's slot of `table` (3 x float4 per queue slot per sample in flight), then overwrites the primitive word of the record the shade step
+// streams (rec_out[2 slot + 1].w) with the slot. The shade launch that follows is handed `table` as its scene.shade_rec, so it gathers
+// `3 * slot` where it gathered `3 * prim`: shade_kernel, bounce_kernel and shade_rays_kernel run as they are. Nothing reads a record's
+// primitive after its shade step (DESIGN.md 9r lists the read sites).
+// normals: per PRIMITIVE, in the order the device holds them, three rows (corner normal | 0) -- the caller's table resolved through each
+// triangle's _pad on the host (build_normal_rows), so the pass gathers geometry, normals and shade record side by side, none behind another.
+struct ShadingArgs {
+    HitWalk w;
+    const float4 *prim_geom;
+    const float4 *normals;
+    float4 *table;
+    float4 *rec_out;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -796,8 +813,15 @@ hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const ui
 // mis: the MIS variants (a.origin set, or the sampler form's rows out); with envs, the ENVS MIS variants
 // power (null = none): the POWER variants with this distribution (never with envs)
 // analytic (null = none): the ANALYTIC variants with this table (never with envs or power)
+// shading (null = none): the SHADING variants with these per-primitive normal rows (triangles; never with power or analytic): the
+// receiver's normal is the shading normal
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false,
-                          const LightDist *power = nullptr, const LightTable *analytic = nullptr);
+                          const LightDist *power = nullptr, const LightTable *analytic = nullptr, const float4 *shading = nullptr);
+hipError_t launch_shading_normal(const ShadingArgs &a, uint32_t grid, hipStream_t s);
+// wfpt_sample_shading_normal: n rows of (p.xyz | the primitive's bits) -> (ns.xyz | 1 where it fell back to the stored normal, else 0), one
+// thread per row; a primitive outside the scene answers (0, 0, 0, 1)
+hipError_t launch_shading_sample(const float4 *prim_geom, const float4 *shade_rec, const float4 *normals, uint32_t n_prims, const float *in4,
+                                 float *out4, uint32_t n, hipStream_t s);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the
@@ -834,7 +858,9 @@ hipError_t launch_rays_to_aos(const RayQueue &q, wfpt_ray *out, uint32_t n, hipS
 hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t n, hipStream_t s);
 // AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
 // sized for it)
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const TexScene *tex = nullptr);
+// shading (null = none): aov_shading_kernel with these per-primitive normal rows (triangles): the normal sum takes the shading normal
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const TexScene *tex = nullptr,
+                      const float4 *shading = nullptr);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
 hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);

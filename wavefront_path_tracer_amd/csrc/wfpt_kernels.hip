@@ -2087,6 +2087,51 @@ __global__ __launch_bounds__(kConsumerThreads) void texture_kernel(TextureArgs a
 }
 
 // ================================================================================================
+// shading-normal pass (WFPT_FLAG_SHADING_NORMALS; include/wfpt.h "Shading normals")
+// ================================================================================================
+// The shading normal at point p of triangle `prim` with stored normal ng: shading_normal with the triangle's geometry and its three rows
+// of `normals` (per primitive: corner normal | 0). Two independent gathers of 48 bytes, 16-byte loads. True where it fell back to ng.
+__device__ __forceinline__ bool shading_normal_at(const float4 *prim_geom, const float4 *normals, uint32_t prim, float3_ p, float3_ ng, float3_ &ns) {
+    const float4 g0 = prim_geom[3u * prim], g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+    const float4 r0 = normals[3u * prim], r1 = normals[3u * prim + 1u], r2 = normals[3u * prim + 2u];
+    return shading_normal(p, {g0.x, g0.y, g0.z}, {g1.x, g1.y, g1.z}, {g2.x, g2.y, g2.z}, ng, {r0.x, r0.y, r0.z}, {r1.x, r1.y, r1.z},
+                          {r2.x, r2.y, r2.z}, ns);
+}
+
+// One launch before a shade step that scatters, after that step's other passes (ShadingArgs): the hit's own shade record with the shading
+// normal goes to the hit's slot of the table, and the slot's index takes the primitive's place in the record the step streams.
+__global__ __launch_bounds__(kConsumerThreads) void shading_normal_kernel(ShadingArgs a) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    for_each_shaded_hit<true>(a.w, s, [&](size_t slot, const Hit &h) {
+        const float4 rec0 = a.w.shade_rec[3u * h.prim], rec1 = a.w.shade_rec[3u * h.prim + 1u], rec2 = a.w.shade_rec[3u * h.prim + 2u];
+        float3_ ns;
+        shading_normal_at(a.prim_geom, a.normals, h.prim, h.p, {rec0.x, rec0.y, rec0.z}, ns);
+        float4 *out = a.table + 3u * slot;
+        out[0] = make_float4(ns.x, ns.y, ns.z, rec0.w);
+        out[1] = rec1;
+        out[2] = rec2;
+        a.rec_out[2u * slot + 1u].w = __uint_as_float(static_cast<uint32_t>(slot)); // (3 * slot stays below 2^32: wfpt_create's size check)
+    });
+}
+
+// wfpt_sample_shading_normal: shading_normal_at for caller rows of (p | the primitive's bits), one thread per row
+__global__ __launch_bounds__(256) void shading_sample_kernel(const float4 *prim_geom, const float4 *shade_rec, const float4 *normals,
+                                                             uint32_t n_prims, const float *in4, float *out4, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *row = in4 + 4u * static_cast<size_t>(i);
+    const uint32_t prim = __float_as_uint(row[3]);
+    float3_ ns = {0.0f, 0.0f, 0.0f};
+    bool fell = true;
+    if (prim < n_prims) {
+        const float4 rec0 = shade_rec[3u * prim];
+        fell = shading_normal_at(prim_geom, normals, prim, {row[0], row[1], row[2]}, {rec0.x, rec0.y, rec0.z}, ns);
+    }
+    float *out = out4 + 4u * static_cast<size_t>(i);
+    out[0] = ns.x; out[1] = ns.y; out[2] = ns.z; out[3] = fell ? 1.0f : 0.0f;
+}
+
+// ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
 // The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
@@ -3649,8 +3694,10 @@ __global__ void rays_from_aos_kernel(RayQueue q, const wfpt_ray *in, uint32_t n)
 // Sample order per pixel, no atomics: the sums do not depend on the batch size or on anything else that runs beside this kernel.
 // (No min-waves launch bound: capped at 64 vector registers like extend_kernel, every variant spills 96-164 bytes to scratch; unbounded
 // it takes 86-110 and runs 4 waves per SIMD.)
-template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX = false>
-__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, const TexScene &ts = TexScene{}) {
+// SHADING (aov_shading_kernel; WFPT_FLAG_SHADING_NORMALS contexts that hold a table, triangles): the normal sum takes the shading normal
+// of the primary hit (`sn`: the per-primitive normal rows) in the stored normal's place.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX = false, bool SHADING = false>
+__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, const TexScene &ts = TexScene{}, const float4 *sn = nullptr) {
     extern __shared__ float4 lds[];
     const uint32_t n_slots = a.gx * a.gy * 64u;
     const uint32_t n_items = (n_slots + kExtendThreads - 1u) / kExtendThreads;
@@ -3690,6 +3737,7 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, co
                 // the normal scatter() uses: spheres normalize3(p - centre) with p = o + t d (extend's path record, sh:91), triangles the stored one
                 float3_ n = {rec0.x, rec0.y, rec0.z};
                 if (PRIM == 0) n = normalize3({(r.ox + t * r.dx) - rec0.x, (r.oy + t * r.dy) - rec0.y, (r.oz + t * r.dz) - rec0.z});
+                if (SHADING) shading_normal_at(a.scene.prim_geom, sn, prim, {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, {rec0.x, rec0.y, rec0.z}, n);
                 float3_ tc;
                 if (TEX && texture_factor(ts, a.scene.prim_geom, a.scene.shade_rec, PRIM, prim,
                                           {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, tc)) { // the textured albedo tex * albedo
@@ -3742,6 +3790,12 @@ __global__ __launch_bounds__(kExtendThreads) void aov_env_kernel(AovArgs a, EnvD
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV>
 __global__ __launch_bounds__(kExtendThreads) void aov_tex_kernel(AovArgs a, EnvDev env, TexScene ts) {
     aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, true>(a, env, ts);
+}
+
+// WFPT_FLAG_SHADING_NORMALS with a table (triangle contexts): the normal sum takes the shading normal (every ENV and TEX case)
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX>
+__global__ __launch_bounds__(kExtendThreads) void aov_shading_kernel(AovArgs a, EnvDev env, TexScene ts, const float4 *sn) {
+    aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, TEX, true>(a, env, ts, sn);
 }
 
 // ================================================================================================
@@ -3928,17 +3982,19 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // the share of its own branch; the point is stored as above. The sampler form is the map's, with the effective share and 12 floats a row.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
-    constexpr bool POWER = false, ANALYTIC = false;
+    constexpr bool POWER = false, ANALYTIC = false, SHADING = false;
     const LightDist ld{};
     const LightTable lt{};
+    const float4 *const sn = nullptr;
 #include "wfpt_connect_body.inc"
 }
 // POWER (WFPT_FLAG_LIGHT_POWER contexts whose light list has a distribution; never with ENVS): sample_light selects by ld and weighs by
 // nfi; nothing else differs. The distribution is a second argument: connect_kernel keeps its name, its arguments and its instructions.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectArgs a, LightDist ld) {
-    constexpr bool ENVS = false, POWER = true, ANALYTIC = false;
+    constexpr bool ENVS = false, POWER = true, ANALYTIC = false, SHADING = false;
     const LightTable lt{};
+    const float4 *const sn = nullptr;
 #include "wfpt_connect_body.inc"
 }
 // ANALYTIC (WFPT_FLAG_ANALYTIC_LIGHTS contexts that hold an analytic light; never with ENVS or POWER): sample_light selects among the
@@ -3946,8 +4002,20 @@ __global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectAr
 // occludes); under MIS an analytic sample is not weighed. The table is a second argument, as the distribution above.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_analytic_kernel(ConnectArgs a, LightTable lt) {
-    constexpr bool ENVS = false, POWER = false, ANALYTIC = true;
+    constexpr bool ENVS = false, POWER = false, ANALYTIC = true, SHADING = false;
     const LightDist ld{};
+    const float4 *const sn = nullptr;
+#include "wfpt_connect_body.inc"
+}
+// SHADING (WFPT_FLAG_SHADING_NORMALS contexts that hold a table; triangles; never with POWER or ANALYTIC): the receiver's normal n is the
+// shading normal of the hit (shading_normal_at with `sn`, the per-primitive normal rows) -- what shade will scatter about -- in both the
+// emitter and the map branch; nothing else differs. The rows are a second argument, as the distribution and the table above. The sampler
+// form takes its normal from the caller's rows and is connect_kernel's.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
+__global__ __launch_bounds__(kExtendThreads) void connect_shading_kernel(ConnectArgs a, const float4 *sn) {
+    constexpr bool POWER = false, ANALYTIC = false, SHADING = true;
+    const LightDist ld{};
+    const LightTable lt{};
 #include "wfpt_connect_body.inc"
 }
 
@@ -4706,6 +4774,20 @@ hipError_t launch_texture(const TextureArgs &a, uint32_t grid, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_shading_normal(const ShadingArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    if (!a.normals || !a.table || !a.rec_out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shading_normal_kernel, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shading_sample(const float4 *prim_geom, const float4 *shade_rec, const float4 *normals, uint32_t n_prims, const float *in4,
+                                 float *out4, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(shading_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, prim_geom, shade_rec, normals, n_prims, in4, out4, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q, const LightDist *ld) {
     if (grid == 0) return hipSuccess;
     if (kind == kEmitWeighedPower) {
@@ -4832,18 +4914,32 @@ struct AovTexK {
 using Aov = Family<AovK>;
 using AovEnv = Family<AovEnvK>;
 using AovTex = Family<AovTexK, Bool>;
+// (triangles only: a sphere scene has no variant, and its contexts never ask for one)
+using AovShadingFn = void (*)(AovArgs, EnvDev, TexScene, const float4 *);
+struct AovShadingK {
+    template <bool ENV, bool TEX, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovShadingFn get() {
+        if constexpr (PRIM == 1) return aov_shading_kernel<Trail, PRIM, LDS_SCENE, EXACT, ENV, TEX>;
+        else return nullptr;
+    }
+};
+using AovShading = Family<AovShadingK, Bool, Bool>;
 uint32_t aov_lds_bytes(const SceneDev &sc) { return sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes; }
 } // namespace
 
 hipError_t aov_prepare(const SceneDev &scene) {
-    return allow_dynamic_lds<Aov, AovEnv, AovTex>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
+    if (const hipError_t e = allow_dynamic_lds<Aov, AovEnv, AovTex>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)); e != hipSuccess) return e;
+    return scene.prim_kind == 1 ? allow_dynamic_lds<AovShading>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
 }
 
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex) {
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex, const float4 *shading) {
     if (grid == 0 || a.n == 0 || a.gx * a.gy == 0) return hipSuccess;
+    if (shading && a.scene.prim_kind != 1) return hipErrorInvalidValue;
     const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
     const dim3 g(grid), b(kExtendThreads);
-    if (tex) hipLaunchKernelGGL(AovTex::pick(a.scene, exact, lds, env != nullptr), g, b, aov_lds_bytes(a.scene), s, a, env ? *env : EnvDev{}, *tex);
+    if (shading)
+        hipLaunchKernelGGL(AovShading::pick(a.scene, exact, lds, env != nullptr, tex != nullptr), g, b, aov_lds_bytes(a.scene), s, a,
+                           env ? *env : EnvDev{}, tex ? *tex : TexScene{}, shading);
+    else if (tex) hipLaunchKernelGGL(AovTex::pick(a.scene, exact, lds, env != nullptr), g, b, aov_lds_bytes(a.scene), s, a, env ? *env : EnvDev{}, *tex);
     else if (env) hipLaunchKernelGGL(AovEnv::pick(a.scene, exact, lds), g, b, aov_lds_bytes(a.scene), s, a, *env);
     else hipLaunchKernelGGL(Aov::pick(a.scene, exact, lds), g, b, aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();
@@ -4871,21 +4967,34 @@ struct ConnectAnalyticK {
     }
 };
 using ConnectAnalytic = Family<ConnectAnalyticK, Bool, Bool>;
+// (triangles only, as AovShading)
+using ConnectShadingFn = void (*)(ConnectArgs, const float4 *);
+struct ConnectShadingK {
+    template <bool TEX, bool ENVS, bool MIS, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectShadingFn get() {
+        if constexpr (PRIM == 1) return connect_shading_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS, MIS>;
+        else return nullptr;
+    }
+};
+using ConnectShading = Family<ConnectShadingK, Bool, Bool, Bool>;
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
-    return allow_dynamic_lds<Connect, ConnectPower, ConnectAnalytic>(scene, scene.lds_scene != 0, aov_lds_bytes(scene));
+    if (const hipError_t e = allow_dynamic_lds<Connect, ConnectPower, ConnectAnalytic>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)); e != hipSuccess)
+        return e;
+    return scene.prim_kind == 1 ? allow_dynamic_lds<ConnectShading>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
 }
 
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power,
-                          const LightTable *analytic) {
+                          const LightTable *analytic, const float4 *shading) {
     if (grid == 0 || (a.n_lights == 0 && !envs && !analytic)) return hipSuccess;
     if (analytic && (envs || power || !analytic->rows || analytic->n == 0)) return hipErrorInvalidValue;
     if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
     if (power && (envs || !power->cdf || power->total == 0)) return hipErrorInvalidValue;
+    if (shading && (power || analytic || a.scene.prim_kind != 1 || a.sample_in)) return hipErrorInvalidValue;
     const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
     const dim3 g(grid), b(kExtendThreads);
-    if (analytic) hipLaunchKernelGGL(ConnectAnalytic::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *analytic);
+    if (shading) hipLaunchKernelGGL(ConnectShading::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a, shading);
+    else if (analytic) hipLaunchKernelGGL(ConnectAnalytic::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *analytic);
     else if (power) hipLaunchKernelGGL(ConnectPower::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *power);
     else hipLaunchKernelGGL(Connect::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a);
     return hipGetLastError();

@@ -349,6 +349,29 @@ class PathTracer {
         check(wfpt_texture_timing_ms(ctx_, &ms, &n));
         return {ms, n};
     }
+    // Shading normals (WFPT_FLAG_SHADING_NORMALS, include/wfpt.h "Shading normals"): rows of the normals of corners 0, 1, 2, nine floats
+    // each, row r for the triangles whose _pad is r; empty clears.
+    void set_triangle_normals(const std::vector<float> &n9) {
+        check(wfpt_set_triangle_normals(ctx_, n9.empty() ? nullptr : n9.data(), static_cast<uint32_t>(n9.size() / 9)));
+    }
+    std::vector<float> triangle_normals() { // the table as stored (normalised)
+        uint32_t n = 0;
+        check(wfpt_get_triangle_normals(ctx_, nullptr, 0, &n));
+        std::vector<float> n9(9 * static_cast<size_t>(n));
+        if (n) check(wfpt_get_triangle_normals(ctx_, n9.data(), n, &n));
+        return n9;
+    }
+    std::vector<float> sample_shading_normal(const std::vector<float> &in4) { // (p.xyz | the triangle's bits) -> (ns.xyz | fell back)
+        std::vector<float> out(in4.size() / 4 * 4);
+        check(wfpt_sample_shading_normal(ctx_, in4.data(), in4.size() / 4, out.data()));
+        return out;
+    }
+    std::pair<float, uint32_t> shading_normal_timing() {
+        float ms = 0.0f;
+        uint32_t n = 0;
+        check(wfpt_shading_normal_timing_ms(ctx_, &ms, &n));
+        return {ms, n};
+    }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
