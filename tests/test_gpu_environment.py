@@ -61,7 +61,8 @@ def test_device_atan2_equals_restatement(W):
     assert_bits(W.selftest_math(8, y, xx), R.atan2_(y, xx), "atan2_")
 
 
-@pytest.mark.parametrize("w,h,intensity,rotation", [(1, 1, 2.5, 0.0), (3, 2, 1.0, 0.25), (64, 32, 0.5, 0.7), (2048, 1024, 1.0, 0.1)])
+@pytest.mark.parametrize("w,h,intensity,rotation", [(1, 1, 2.5, 0.0), (3, 2, 1.0, 0.25), (64, 32, 0.5, 0.7), (2048, 1024, 1.0, 0.1),
+                                                       (1025, 1024, 1.0, 0.0)])  # (a whole piece of the upload and a partial one)
 def test_sample_environment_equals_restatement(W, w, h, intensity, rotation):
     pt = W.shirley_path_tracer(16, 16, flags=W.FLAG_ENVIRONMENT)
     m = make_map(w, h)

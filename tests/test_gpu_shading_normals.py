@@ -209,6 +209,48 @@ def test_timed_render_books_the_pass_apart(W, O):
     pt.close()
 
 
+def test_timed_render_books_every_pass_in_its_own_counter(W, O):
+    """A context with all five passes that are no stage of render_timed's arrays -- AOV, texture, emission, connect, shading normals -- on
+    a 64-triangle mesh, 16 x 16, one sample in flight, N = 3 wavefronts. Per timed sample: one AOV launch; a texture, an emission and a
+    connect launch before each of the N shade steps, the second plane's memset at the head of the batch booked with the emission
+    launches; a shading-normal launch before the N - 1 shade steps that scatter."""
+    n_waves = 3
+    sc = W.Scene.random_mesh(64, 1)
+    cc = W.CameraController(W.Camera((0.0, 0.0, 30.0), (0.0, 0.0, 0.0)), 40.0, 0.0, 10.0, 0.1, 100.0)
+    pt = W.PathTracer(sc, W.RenderParameters(cc, (16, 16)), max_wavefronts=n_waves, batch=1,
+                      flags=flags_of(W, "AOV|TEXTURES|EMISSION|NEE|SHADING_NORMALS"))
+    tri = pt.scene.triangles
+    rows = int(tri["_pad"].max()) + 1
+    rng = np.random.default_rng(21)
+    pt.set_texture(0, rng.random((4, 8, 3)).astype(F))
+    pt.bind_texture(int(tri["material_idx"][1]), 0)
+    pt.set_triangle_uvs(rng.random((rows, 6)).astype(F))
+    pt.set_emission(int(tri["material_idx"][0]), LAMP_E)
+    pt.set_triangle_normals(rng.standard_normal((rows, 9)).astype(F))
+    assert pt.loop_kind == "fused" and pt.nee_light_count() > 0
+    timings = (pt.aov_timing, pt.texture_timing, pt.emission_timing, pt.nee_timing, pt.shading_normal_timing)
+    per_sample = np.array([1, n_waves, n_waves + 1, n_waves, n_waves - 1])
+    assert [t() for t in timings] == [(0.0, 0)] * 5
+    stage_ms, stage_launches = pt.render_timed(1)
+    # the stages' own array holds the fused loop's chain and nothing of the passes: bounce<first>, then N - 1 times (scan, bounce<middle>),
+    # scan, bounce<last>, accumulate (the library of the commit before the pass array returns this array for this context:
+    # [0, 0, 0, 0, 1, 0, 0, 0, 3, 1, 2, 1, 0])
+    want = np.zeros(W.STAGE_COUNT, np.uint32)
+    for name, n in (("bounce_first", 1), ("scan", n_waves), ("bounce", n_waves - 1), ("bounce_last", 1), ("accumulate", 1)):
+        want[W.STAGES[name]] = n
+    assert want.tolist() == [0, 0, 0, 0, 1, 0, 0, 0, 3, 1, 2, 1, 0]
+    assert stage_launches.tolist() == want.tolist()
+    assert np.array_equal(stage_ms > 0, want > 0), "a stage's time without its launches, or the reverse"
+    assert [t()[1] for t in timings] == per_sample.tolist()
+    assert all(t()[0] > 0.0 for t in timings)
+    _, again = pt.render_timed(1)
+    assert [t()[1] for t in timings] == (2 * per_sample).tolist()
+    assert np.array_equal(again, stage_launches), "the stages' own counts are per call"
+    pt.render(1)
+    assert [t()[1] for t in timings] == (2 * per_sample).tolist(), "an untimed render books nothing"
+    pt.close()
+
+
 def test_band_sharding_equals_restatement(W, O):
     w, h = SIZES["61x37"]
     for rank in range(2):

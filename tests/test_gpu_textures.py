@@ -91,7 +91,8 @@ def test_sample_texture_equals_restatement(W):
     pt = W.shirley_path_tracer(16, 16, flags=W.FLAG_TEXTURES)
     uv = probe_uvs()
     for s, (img, params) in enumerate([(random_tex(1, 1, 3), {}), (random_tex(3, 2, 4), {"scale": (1.5, -2.0), "offset": (0.1, 7.0)}),
-                                       (random_tex(64, 48, 5), {}), (random_tex(2048, 1024, 6), {"offset": (-0.3, 0.2)})]):
+                                       (random_tex(64, 48, 5), {}), (random_tex(2048, 1024, 6), {"offset": (-0.3, 0.2)}),
+                                       (random_tex(1025, 1024, 7), {})]):  # (a whole piece of the upload and a partial one)
         for flt in ("bilinear", "nearest"):
             pt.set_texture(s, img, filter=flt, **params)
             assert_bits(pt.sample_texture(s, uv), T.tex_lookup(img, uv[:, 0], uv[:, 1], filter=flt, **params), f"{img.shape} {flt}")

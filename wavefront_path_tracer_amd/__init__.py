@@ -1286,11 +1286,15 @@ class PathTracer:
         self._check(lib().wfpt_copy_aov_to_device(self.handle, which, C.c_void_p(tensor.data_ptr()), 4 * n))
         return tensor
 
+    def _timing(self, entry):
+        """(milliseconds, count) as one of the wfpt_*_timing_ms entry points reports them."""
+        ms, n = C.c_float(0.0), C.c_uint32(0)
+        self._check(entry(self.handle, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
     def aov_timing(self):
         """(milliseconds, launches) of the AOV launches of every timed render since creation (apart from render_timed's stage times)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_aov_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_aov_timing_ms)
 
     # ---- denoiser (contexts created with FLAG_DENOISE)
     def variance(self):
@@ -1345,15 +1349,11 @@ class PathTracer:
 
     def tile_lists_timing(self):
         """(milliseconds of the last build of the tile lists on the device, builds since creation)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_tile_lists_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_tile_lists_timing_ms)
 
     def denoise_timing(self):
         """(milliseconds of the last denoise call's launches, denoise calls since creation)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_denoise_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_denoise_timing_ms)
 
     # ---- temporal denoiser (contexts created with FLAG_DENOISE; include/wfpt.h "Temporal denoiser")
     def set_frame_offset(self, offset):
@@ -1417,9 +1417,7 @@ class PathTracer:
 
     def temporal_timing(self):
         """(milliseconds of the last temporal call's launches, temporal calls since creation)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_temporal_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_temporal_timing_ms)
 
     # ---- environment map (contexts created with FLAG_ENVIRONMENT; include/wfpt.h "Environment map")
     def set_environment(self, rgb, intensity=1.0, rotation=0.0):
@@ -1484,9 +1482,7 @@ class PathTracer:
 
     def texture_timing(self):
         """(milliseconds, launches) of the texture launches of every timed render since creation (apart from render_timed's stage times)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_texture_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_texture_timing_ms)
 
     # ---- shading normals (triangle contexts created with FLAG_SHADING_NORMALS; include/wfpt.h "Shading normals")
     def set_triangle_normals(self, n):
@@ -1515,9 +1511,7 @@ class PathTracer:
 
     def shading_normal_timing(self):
         """(milliseconds, launches) of the shading-normal launches of every timed render since creation (apart from render_timed's stage times)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_shading_normal_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_shading_normal_timing_ms)
 
     # ---- emission (contexts created with FLAG_EMISSION; include/wfpt.h "Emission")
     def set_emission(self, material_idx, rgb):
@@ -1539,9 +1533,7 @@ class PathTracer:
 
     def emission_timing(self):
         """(milliseconds, launches) of the emission launches of every timed render since creation (apart from render_timed's stage times)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_emission_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_emission_timing_ms)
 
     # ---- next-event estimation (contexts created with FLAG_EMISSION | FLAG_NEE; include/wfpt.h "Next-event estimation")
     def nee_light_count(self):
@@ -1553,9 +1545,7 @@ class PathTracer:
 
     def nee_timing(self):
         """(milliseconds, launches) of the connect launches of every timed render since creation (apart from render_timed's stage times)."""
-        ms, n = C.c_float(0.0), C.c_uint32(0)
-        self._check(lib().wfpt_nee_timing_ms(self.handle, C.byref(ms), C.byref(n)))
-        return float(ms.value), int(n.value)
+        return self._timing(lib().wfpt_nee_timing_ms)
 
     def sample_lights(self, rows):
         """The connect pass's light sample for caller-supplied receivers, computed on the device. rows: (n, 9) float32 of (p.xyz, n.xyz,

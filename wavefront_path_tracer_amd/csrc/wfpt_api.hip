@@ -148,6 +148,10 @@ static uint32_t bands_of(uint32_t height, uint32_t rank, uint32_t world) {
     return n_bands > rank ? (n_bands - rank + world - 1u) / world : 0u;
 }
 
+// The passes of the timed renders that are no wfpt_stage; a pass's entry in an event record is pass_stage(pass)
+enum Pass { kPassAov, kPassTexture, kPassEmission, kPassConnect, kPassShading, kPassCount };
+constexpr int pass_stage(Pass pass) { return WFPT_STAGE_COUNT + pass; }
+
 struct wfpt_ctx {
     // declared first, so destroyed last: after every buffer, event and graph below
     Stream stream;
@@ -202,8 +206,11 @@ struct wfpt_ctx {
     bool fused = true;
     DeviceBuffer<float> image, accumulated;
     DeviceBuffer<float> aov_sums; // WFPT_FLAG_AOV: [kAovPlanes][pixel_capacity] first-hit sums (wfpt_kernels.h), null without the flag
-    double aov_ms = 0.0;        // AOV launches of the timed renders since wfpt_create (wfpt_aov_timing_ms)
-    uint32_t aov_launches = 0;
+    // the launches of each pass in the timed renders since wfpt_create (wfpt_aov_timing_ms and its four siblings)
+    struct PassTimer {
+        double ms = 0.0;
+        uint32_t launches = 0;
+    } pass[kPassCount];
     DeviceBuffer<float> moments; // WFPT_FLAG_DENOISE: [kMomentPlanes][pixel_capacity] luminance moments, null without the flag
     DenoiseBuffers dn;
     EventPair dn_ev;
@@ -238,27 +245,22 @@ struct wfpt_ctx {
     DeviceBuffer<TexDev> tex_desc;
     DeviceBuffer<uint2> tex_prim;
     std::vector<uint32_t> h_prim_mat_idx, h_prim_row; // material_idx and _pad per primitive (textured, emitting and shading-normal contexts)
-    double tex_ms = 0.0;        // texture launches of the timed renders since wfpt_create (wfpt_texture_timing_ms)
-    uint32_t tex_launches = 0;
     // WFPT_FLAG_EMISSION (include/wfpt.h "Emission"): the colour per material (3 floats each, all zero = no emitter), what
     // build_emission_tables makes of them for the kernels -- per primitive its material_idx or kNoEmission, and the colours as float4 (both
-    // null while no material emits: nothing new is launched then) -- and the second per-sample plane, image's shape, allocated with the
-    // first emitter and kept
+    // null while no material emits: nothing new is launched then) -- and the second per-sample plane, image's shape, which comes with
+    // the first emitter, map with a distribution or analytic light and is kept (reserve_second_plane)
     std::vector<float> em_rgb;
     DeviceBuffer<uint32_t> em_prim;
     DeviceBuffer<float4> em_mat;
     DeviceBuffer<float> emitted;
-    double em_ms = 0.0;         // emission launches of the timed renders since wfpt_create (wfpt_emission_timing_ms)
-    uint32_t em_launches = 0;
     // WFPT_FLAG_NEE (include/wfpt.h "Next-event estimation"): the light list build_emission_tables resolves with the tables above (null
     // while no material emits: nothing new is launched then), and the stage API's wavefront counter (extends since the last generate_rays)
     DeviceBuffer<uint32_t> nee_lights;
     uint32_t n_lights = 0;
     uint32_t stage_extends = 0;
-    double nee_ms = 0.0;        // connect launches of the timed renders since wfpt_create (wfpt_nee_timing_ms)
-    uint32_t nee_launches = 0;
     // WFPT_FLAG_MIS (include/wfpt.h "Multiple importance sampling"): the hit points of the diffuse hits, `emitted`'s shape (one float4 per
-    // pixel per sample in flight), allocated with the first emitter and kept; never zeroed (read only where the connected flag is 1)
+    // pixel per sample in flight), which comes and stays with `emitted` (WFPT_FLAG_ENV_MIS contexts have it too); never zeroed (read only
+    // where the connected flag is 1)
     DeviceBuffer<float4> mis_origin;
     // WFPT_FLAG_LIGHT_POWER (include/wfpt.h "Light selection by power"): the light list's sampling distribution, built and dropped with the
     // list (null where the list has none: the context then runs as one without the flag)
@@ -276,8 +278,6 @@ struct wfpt_ctx {
     std::vector<float> h_normals;
     DeviceBuffer<float4> sn_rows;
     DeviceBuffer<float4> sn_table;
-    double sn_ms = 0.0;         // shading-normal launches of the timed renders since wfpt_create (wfpt_shading_normal_timing_ms)
-    uint32_t sn_launches = 0;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
     // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
     DeviceBuffer<uint32_t> env_row;
@@ -352,6 +352,20 @@ int flag_check(const wfpt_ctx *c, const char *who, uint32_t flag, const char *na
     if (!c) return fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null context");
     if (!(c->p.flags & flag))
         return fail(const_cast<wfpt_ctx *>(c), WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the context was created without " + name);
+    return WFPT_OK;
+}
+// ... and, where `binned_noun` names what the feature would bring, one the class-binned loop has no form of
+int feature_check(const wfpt_ctx *c, const char *who, uint32_t flag, const char *name, const char *binned_noun = nullptr) {
+    if (int r = flag_check(c, who, flag, name); r != WFPT_OK) return r;
+    if (binned_noun && wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
+        return fail(const_cast<wfpt_ctx *>(c), WFPT_ERR_UNSUPPORTED,
+                    std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no " + binned_noun);
+    return WFPT_OK;
+}
+// the body of wfpt_aov_timing_ms and its siblings, after their own check of the context
+int pass_timing(const wfpt_ctx *c, Pass pass, float *ms_total, uint32_t *launches) {
+    if (ms_total) *ms_total = static_cast<float>(c->pass[pass].ms);
+    if (launches) *launches = c->pass[pass].launches;
     return WFPT_OK;
 }
 
@@ -653,8 +667,6 @@ HitWalk hit_walk(wfpt_ctx *c, int parity, uint32_t nb, int qi = 0, const uint32_
     return w;
 }
 TextureArgs texture_args(wfpt_ctx *c, const HitWalk &w) { return TextureArgs{w, c->scene.prim_geom, c->scene.prim_kind, tex_scene(c)}; }
-// The texture launches' entry in an event record (not a wfpt_stage, like the AOV launch's): booked into wfpt_ctx::tex_ms
-constexpr int kStageTexture = WFPT_STAGE_COUNT + 1;
 
 // a material emits: the emission passes run before the shade steps (after their texture passes) and accumulate takes the second plane
 bool emitting(const wfpt_ctx *c) { return c->em_prim.get() != nullptr; }
@@ -668,8 +680,6 @@ EmissionArgs emission_args(wfpt_ctx *c, const HitWalk &w) {
     return EmissionArgs{w, c->emitted.get(), c->em_prim.get(), c->em_mat.get(), c->scene.prim_geom, c->mis_origin.get(), c->scene.prim_kind,
                         static_cast<float>(light_count(c))};
 }
-// The emission launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::em_ms
-constexpr int kStageEmission = WFPT_STAGE_COUNT + 2;
 
 // a WFPT_FLAG_NEE context holds an emitter: the connect passes run before the shade steps (after their emission passes, which then add a
 // hit light only where the pixel's connected flag is 0)
@@ -678,6 +688,29 @@ bool env_connecting(const wfpt_ctx *c) { return c->env_row.get() != nullptr; }
 bool connecting(const wfpt_ctx *c) { return c->nee_lights.get() != nullptr || env_connecting(c) || analytic_selecting(c); }
 // the second plane is in use: accumulate adds it, the head of every batch zeroes it
 bool second_plane(const wfpt_ctx *c) { return emitting(c) || env_connecting(c) || analytic_selecting(c); }
+// The second per-sample plane (wfpt_ctx::emitted, image's shape) and the hit-point plane that comes and stays with it
+// (wfpt_ctx::mis_origin), as candidates: whoever is about to make second_plane(c) hold -- the first emitter, the first map with a
+// distribution, the first analytic light -- reserves them with its own tables and commits them with those. Nothing else allocates either.
+struct SecondPlane {
+    DeviceBuffer<float> plane;
+    DeviceBuffer<float4> origin;
+};
+// Nothing to do once the context has the plane (it is kept). The origins go to every weighing context: each of the three callers once
+// asked for its own flag alone, and under wfpt_create's rules the union is the same set, since WFPT_FLAG_MIS excludes WFPT_FLAG_ENV_NEE
+// (no map's distribution on a MIS context) and WFPT_FLAG_ANALYTIC_LIGHTS excludes WFPT_FLAG_ENV_MIS.
+int reserve_second_plane(wfpt_ctx *c, SecondPlane &out) {
+    if (c->emitted.get()) return WFPT_OK;
+    const size_t n = static_cast<size_t>(c->batch_max) * c->image_floats;
+    WFPT_HIP(c, out.plane.alloc(n));
+    WFPT_HIP(c, hipMemset(out.plane.get(), 0, sizeof(float) * n));
+    if (c->p.flags & (WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS)) WFPT_HIP(c, out.origin.alloc(n / 4));
+    return WFPT_OK;
+}
+// (the stream is idle: the caller synchronised it)
+void commit_second_plane(wfpt_ctx *c, SecondPlane &&s) {
+    if (s.plane.get()) c->emitted = std::move(s.plane);
+    if (s.origin.get()) c->mis_origin = std::move(s.origin);
+}
 // a WFPT_FLAG_MIS context holds an emitter (never with a map's distribution: the flag excludes WFPT_FLAG_ENV_NEE): the connect and
 // emission passes are the MIS variants
 // (an emitter or an analytic light: N > 0)
@@ -763,8 +796,6 @@ hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t gri
 }
 // the plane whose connected flags gate the miss launches of a context that connects to its map (null otherwise: miss_env_kernel)
 const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitted.get() : nullptr; }
-// The connect launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::nee_ms
-constexpr int kStageConnect = WFPT_STAGE_COUNT + 3;
 
 // a WFPT_FLAG_SHADING_NORMALS context holds a table: the shading-normal pass runs before the shade steps that scatter, and the connect pass
 // and the AOV kernel are the SHADING variants
@@ -773,8 +804,6 @@ bool shading(const wfpt_ctx *c) { return c->sn_rows.get() != nullptr; }
 ShadingArgs shading_args(wfpt_ctx *c, const HitWalk &w, float4 *rec_out) {
     return ShadingArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->sn_table.get(), rec_out};
 }
-// The shading-normal launches' entry in an event record (not a wfpt_stage): booked into wfpt_ctx::sn_ms
-constexpr int kStageShading = WFPT_STAGE_COUNT + 4;
 
 ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
     ScanBinnedArgs a{};
@@ -849,11 +878,11 @@ struct EventRec { int stage; hipEvent_t start, stop; };
 template <typename Timed>
 int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const HitWalk &w, bool shaded = false, float4 *shade_rec_out = nullptr) {
     const uint32_t grid = consumer_grid(c, nb);
-    if (textured(c)) WFPT_HIP(c, timed(kStageTexture, [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
-    if (emitting(c)) WFPT_HIP(c, timed(kStageEmission, [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
-    if (connecting(c)) WFPT_HIP(c, timed(kStageConnect, [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
+    if (textured(c)) WFPT_HIP(c, timed(pass_stage(kPassTexture), [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
+    if (emitting(c)) WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
+    if (connecting(c)) WFPT_HIP(c, timed(pass_stage(kPassConnect), [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
     if (shaded && shade_rec_out)
-        WFPT_HIP(c, timed(kStageShading, [&] { return launch_shading_normal(shading_args(c, w, shade_rec_out), grid, c->stream.get()); }));
+        WFPT_HIP(c, timed(pass_stage(kPassShading), [&] { return launch_shading_normal(shading_args(c, w, shade_rec_out), grid, c->stream.get()); }));
     return WFPT_OK;
 }
 // the scene of a shade step that follows the shading-normal pass: the per-hit records in the primitives' place
@@ -984,9 +1013,6 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
     return WFPT_OK;
 }
 
-// The AOV launch's entry in an event record: not a wfpt_stage (WFPT_STAGE_COUNT and the stage_ms arrays callers size by it stay as they
-// are); wfpt_render_timed books it into wfpt_ctx::aov_ms.
-constexpr int kStageAov = WFPT_STAGE_COUNT;
 AovArgs aov_args(wfpt_ctx *c, uint32_t nb) {
     AovArgs a{};
     a.n = nb;
@@ -1007,7 +1033,7 @@ uint32_t aov_grid(const wfpt_ctx *c) { // persistent workgroups, at most extend'
 
 // The batch's accumulate launch: with the second plane where the context holds an emitter (each sample's value is image + emitted) and
 // the luminance moments on WFPT_FLAG_DENOISE contexts (the same `accumulated` bits either way). second_plane(c) implies the plane:
-// apply_emission and the environment's distribution allocate `emitted` before either of its conditions can hold.
+// reserve_second_plane allocates `emitted` before any of its conditions can hold.
 hipError_t launch_batch_accumulate(wfpt_ctx *c, uint32_t nb) {
     if (adapting(c)) // under the active mask, with the counts (the moments always)
         return launch_accumulate_masked(accumulate_args(c, c->n_pixels, true, nb), second_plane(c) ? c->emitted.get() : nullptr, c->moments.get(),
@@ -1031,13 +1057,13 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     };
     c->cur = 0;
     if (c->aov_sums.get()) // first in the batch, serially on the stream: it sees the batch's first frame, before accumulate advances it
-        WFPT_HIP(c, timed(kStageAov, [&] {
+        WFPT_HIP(c, timed(pass_stage(kPassAov), [&] {
                      const TexScene ts = tex_scene(c);
                      return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c), textured(c) ? &ts : nullptr,
                                        shading(c) ? c->sn_rows.get() : nullptr);
                  }));
     if (second_plane(c)) // the loops' first kernel sets every slice of `image` to 1: `emitted` starts at 0 with it
-        WFPT_HIP(c, timed(kStageEmission, [&] {
+        WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] {
                      return hipMemsetAsync(c->emitted.get(), 0, sizeof(float) * nb * c->image_floats, c->stream.get());
                  }));
     int r = WFPT_OK;
@@ -1369,6 +1395,17 @@ uint32_t decide_exact(uint32_t flags, const SceneDev &sc, bool ch_ok, const floa
     return exact ? 1u : 0u; // (scenes beyond LDS: the four-wide nodes exist only when the tree passed tree_is_recomputable)
 }
 
+// What build_texture_tables, build_emission_tables and build_normal_rows need of the primitives, in the order given (the order the
+// device holds them in): material_idx and _pad (0 for a sphere) of each
+void prim_mat_rows(const wfpt_sphere *spheres, const wfpt_triangle *triangles, uint32_t n, std::vector<uint32_t> &mat_idx, std::vector<uint32_t> &row) {
+    mat_idx.resize(n);
+    row.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
+        row[i] = spheres ? 0u : triangles[i]._pad;
+    }
+}
+
 // Uploads the scene in the reference's layouts (pt:120-128) plus the traversal's derivatives of it: primitive geometry,
 // the sibling-pair parent table, per-primitive shade records, conservative boxes (LDS-resident scenes) or four-wide nodes
 // (scenes beyond LDS), and sizes the launches for it. `pair_parent` / `bvh_depth` come from validate_bvh. The new scene is built
@@ -1535,14 +1572,8 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
     c->far_rays = false;
     c->depth4 = depth4;
     c->h_prim_mat_type = std::move(mat_type);
-    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS)) { // what build_texture_tables, build_emission_tables and build_normal_rows need of the primitives (in the order the device holds them)
-        c->h_prim_mat_idx.resize(n_spheres);
-        c->h_prim_row.resize(n_spheres);
-        for (uint32_t i = 0; i < n_spheres; ++i) {
-            c->h_prim_mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
-            c->h_prim_row[i] = spheres ? 0u : triangles[i]._pad;
-        }
-    }
+    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS))
+        prim_mat_rows(spheres, triangles, n_spheres, c->h_prim_mat_idx, c->h_prim_row);
     c->blocks_per_cu = static_cast<uint32_t>(blocks);
     c->bounce_blocks_per_cu = static_cast<uint32_t>(bounce_blocks);
     c->bounce_binned_blocks_per_cu = static_cast<uint32_t>(std::max(binned_blocks, 1));
@@ -1613,6 +1644,50 @@ int wfpt_device_count(void) {
 
 const char *wfpt_last_error(const wfpt_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
+// What wfpt_create asks of the optional features' flags: `flag` needs every flag of `needs` and goes with none of `refuses`. The rows are
+// walked in order and the first one violated is reported, what it needs ahead of what it refuses. A new flag adds its row here.
+struct FlagRule {
+    uint32_t flag, needs, refuses;
+    const char *needs_msg, *refuses_msg;
+};
+constexpr uint32_t kFlagsOfConnect = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
+const FlagRule kFlagRules[] = {
+    {WFPT_FLAG_RETIRE, 0, WFPT_FLAG_BINNING, nullptr,
+     "wfpt_create: WFPT_FLAG_RETIRE does not go with WFPT_FLAG_BINNING (the class-binned loop has no termination step)"},
+    {WFPT_FLAG_ADAPTIVE, 0, WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_BINNING, nullptr,
+     "wfpt_create: WFPT_FLAG_ADAPTIVE does not go with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE (their sums are "
+     "resolved with one sample count for the whole image) or WFPT_FLAG_BINNING (the class-binned first launch has no masked form)"},
+    {WFPT_FLAG_NEE, WFPT_FLAG_EMISSION, 0, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)", nullptr},
+    {WFPT_FLAG_MIS, kFlagsOfConnect, WFPT_FLAG_ENV_NEE,
+     "wfpt_create: WFPT_FLAG_MIS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+     "(it weighs the emission pass's hits against the connect pass's samples)",
+     "wfpt_create: WFPT_FLAG_MIS does not go with WFPT_FLAG_ENV_NEE "
+     "(the map's samples are not weighed against the scatter yet)"},
+    {WFPT_FLAG_LIGHT_POWER, kFlagsOfConnect, WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS,
+     "wfpt_create: WFPT_FLAG_LIGHT_POWER needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+     "(it selects the light the connect pass samples)",
+     "wfpt_create: WFPT_FLAG_LIGHT_POWER does not go with WFPT_FLAG_ENV_NEE or WFPT_FLAG_ENV_MIS "
+     "(the emitter branch beside the map's share selects uniformly)"},
+    {WFPT_FLAG_ANALYTIC_LIGHTS, kFlagsOfConnect, WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS | WFPT_FLAG_LIGHT_POWER,
+     "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+     "(its lights are reached by the connect pass, their samples land in the emission plane)",
+     "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS does not go with WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENV_MIS or "
+     "WFPT_FLAG_LIGHT_POWER (the map's share and the power distribution select among emitters only)"},
+    {WFPT_FLAG_SHADING_NORMALS, 0, WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS, nullptr,
+     "wfpt_create: WFPT_FLAG_SHADING_NORMALS does not go with WFPT_FLAG_LIGHT_POWER or "
+     "WFPT_FLAG_ANALYTIC_LIGHTS (their connect kernels are twins of their own)"},
+    // (WFPT_FLAG_ENV_MIS goes with no WFPT_FLAG_MIS either, since it weighs the emitters itself: the WFPT_FLAG_ENV_NEE it needs has
+    // refused that at WFPT_FLAG_MIS's row)
+    {WFPT_FLAG_ENV_MIS, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect | WFPT_FLAG_ENV_NEE, 0,
+     "wfpt_create: WFPT_FLAG_ENV_MIS needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and "
+     "WFPT_FLAG_ENV_NEE (it weighs the map's connect samples against the scattered rays' misses)",
+     nullptr},
+    {WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect, 0,
+     "wfpt_create: WFPT_FLAG_ENV_NEE needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
+     "(the map is one more light of the connect pass, its sample lands in the emission plane)",
+     nullptr},
+};
+
 static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spheres, const wfpt_triangle *triangles,
                              uint32_t n_spheres, const wfpt_material *materials, uint32_t n_materials,
                              const wfpt_bvh_node *nodes, uint32_t n_nodes, const wfpt_gpu_camera *camera,
@@ -1627,80 +1702,11 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
                                                  "shade.wgsl:72's RNG key, the dispatch's thread index, does not allow)");
         return nullptr;
     }
-    if ((params->flags & WFPT_FLAG_RETIRE) != 0 && (params->flags & WFPT_FLAG_BINNING) != 0) {
-        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_RETIRE does not go with WFPT_FLAG_BINNING (the class-binned loop has no termination step)");
-        return nullptr;
-    }
-    if ((params->flags & WFPT_FLAG_ADAPTIVE) != 0 && (params->flags & (WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_BINNING)) != 0) {
-        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ADAPTIVE does not go with WFPT_FLAG_AOV, WFPT_FLAG_DENOISE (their sums are "
-                                                 "resolved with one sample count for the whole image) or WFPT_FLAG_BINNING (the class-binned first launch has no masked form)");
-        return nullptr;
-    }
-    if ((params->flags & WFPT_FLAG_NEE) != 0 && (params->flags & WFPT_FLAG_EMISSION) == 0) {
-        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_NEE needs WFPT_FLAG_EMISSION (the lights it connects to are the emitters)");
-        return nullptr;
-    }
-    if ((params->flags & WFPT_FLAG_MIS) != 0) {
-        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
-        if ((params->flags & need) != need) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_MIS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
-                                                     "(it weighs the emission pass's hits against the connect pass's samples)");
-            return nullptr;
-        }
-        if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_MIS does not go with WFPT_FLAG_ENV_NEE "
-                                                     "(the map's samples are not weighed against the scatter yet)");
-            return nullptr;
-        }
-    }
-    if ((params->flags & WFPT_FLAG_LIGHT_POWER) != 0) {
-        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
-        if ((params->flags & need) != need) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_LIGHT_POWER needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
-                                                     "(it selects the light the connect pass samples)");
-            return nullptr;
-        }
-        if ((params->flags & (WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS)) != 0) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_LIGHT_POWER does not go with WFPT_FLAG_ENV_NEE or WFPT_FLAG_ENV_MIS "
-                                                     "(the emitter branch beside the map's share selects uniformly)");
-            return nullptr;
-        }
-    }
-    if ((params->flags & WFPT_FLAG_ANALYTIC_LIGHTS) != 0) {
-        constexpr uint32_t need = WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
-        if ((params->flags & need) != need) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS needs WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
-                                                     "(its lights are reached by the connect pass, their samples land in the emission plane)");
-            return nullptr;
-        }
-        if ((params->flags & (WFPT_FLAG_ENV_NEE | WFPT_FLAG_ENV_MIS | WFPT_FLAG_LIGHT_POWER)) != 0) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ANALYTIC_LIGHTS does not go with WFPT_FLAG_ENV_NEE, WFPT_FLAG_ENV_MIS or "
-                                                     "WFPT_FLAG_LIGHT_POWER (the map's share and the power distribution select among emitters only)");
-            return nullptr;
-        }
-    }
-    if ((params->flags & WFPT_FLAG_SHADING_NORMALS) != 0 && (params->flags & (WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS)) != 0) {
-        fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_SHADING_NORMALS does not go with WFPT_FLAG_LIGHT_POWER or "
-                                                 "WFPT_FLAG_ANALYTIC_LIGHTS (their connect kernels are twins of their own)");
-        return nullptr;
-    }
-    if ((params->flags & WFPT_FLAG_ENV_MIS) != 0) {
-        constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE;
-        if ((params->flags & need) != need) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_MIS needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION, WFPT_FLAG_NEE and "
-                                                     "WFPT_FLAG_ENV_NEE (it weighs the map's connect samples against the scattered rays' misses)");
-            return nullptr;
-        }
-        if ((params->flags & WFPT_FLAG_MIS) != 0) { // (already refused above with WFPT_FLAG_ENV_NEE; stated for the flag's own rule)
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_MIS does not go with WFPT_FLAG_MIS (it weighs the emitters itself)");
-            return nullptr;
-        }
-    }
-    if ((params->flags & WFPT_FLAG_ENV_NEE) != 0) {
-        constexpr uint32_t need = WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE;
-        if ((params->flags & need) != need) {
-            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, "wfpt_create: WFPT_FLAG_ENV_NEE needs WFPT_FLAG_ENVIRONMENT, WFPT_FLAG_EMISSION and WFPT_FLAG_NEE "
-                                                     "(the map is one more light of the connect pass, its sample lands in the emission plane)");
+    for (const FlagRule &rule : kFlagRules) {
+        if ((params->flags & rule.flag) == 0) continue;
+        const char *msg = (params->flags & rule.needs) != rule.needs ? rule.needs_msg : (params->flags & rule.refuses) != 0 ? rule.refuses_msg : nullptr;
+        if (msg) {
+            fail(nullptr, WFPT_ERR_INVALID_ARGUMENT, msg);
             return nullptr;
         }
     }
@@ -2068,28 +2074,20 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     std::vector<uint32_t> pair_parent;
     const int depth = validate_bvh(c, nodes.data(), n_nodes, n_prims, pair_parent);
     if (depth < 0) return depth;
+    // of the new primitive order (the builders above have reordered the caller's arrays), for the contexts that have a table to build
+    std::vector<uint32_t> mat_idx, row;
+    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS)) prim_mat_rows(spheres, triangles, n_prims, mat_idx, row);
     TextureTables tables; // the texture tables of the new primitive order, built before anything is replaced
-    if (c->p.flags & WFPT_FLAG_TEXTURES) {
-        std::vector<uint32_t> mat_idx(n_prims), row(n_prims);
-        for (uint32_t i = 0; i < n_prims; ++i) {
-            mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
-            row[i] = spheres ? 0u : triangles[i]._pad;
-        }
+    if (c->p.flags & WFPT_FLAG_TEXTURES)
         if (int r = build_texture_tables(c, c->tex_dev, c->tex_bind, mat_idx, row, tables); r != WFPT_OK) return r;
-    }
     DeviceBuffer<float4> sn_rows; // likewise the normal rows of the new primitive order
-    if (!c->h_normals.empty()) {
-        std::vector<uint32_t> row(n_prims);
-        for (uint32_t i = 0; i < n_prims; ++i) row[i] = triangles[i]._pad;
+    if (!c->h_normals.empty())
         if (int r = build_normal_rows(c, c->h_normals, row, sn_rows); r != WFPT_OK) return r;
-    }
     EmissionTables em_tables; // likewise; the colours of materials the new scene no longer has are dropped
     std::vector<float> em_rgb;
     if (c->p.flags & WFPT_FLAG_EMISSION) {
         em_rgb = c->em_rgb;
         em_rgb.resize(3 * static_cast<size_t>(n_materials), 0.0f);
-        std::vector<uint32_t> mat_idx(n_prims);
-        for (uint32_t i = 0; i < n_prims; ++i) mat_idx[i] = spheres ? spheres[i].material_idx : triangles[i].material_idx;
         // (WFPT_FLAG_LIGHT_POWER: the light list's distribution needs the areas of the NEW primitives, which the device does not hold yet)
         DeviceBuffer<float4> geom;
         if (c->p.flags & WFPT_FLAG_LIGHT_POWER) {
@@ -2287,29 +2285,10 @@ int wfpt_render_timed(wfpt_ctx *c, uint32_t n_samples, float *stage_ms, uint32_t
         for (const EventRec &e : ev) {
             float ms = 0.0f;
             WFPT_HIP(c, hipEventElapsedTime(&ms, e.start, e.stop));
-            if (e.stage == kStageAov) {
-                c->aov_ms += ms;
-                c->aov_launches += 1;
-                continue;
-            }
-            if (e.stage == kStageTexture) {
-                c->tex_ms += ms;
-                c->tex_launches += 1;
-                continue;
-            }
-            if (e.stage == kStageEmission) {
-                c->em_ms += ms;
-                c->em_launches += 1;
-                continue;
-            }
-            if (e.stage == kStageConnect) {
-                c->nee_ms += ms;
-                c->nee_launches += 1;
-                continue;
-            }
-            if (e.stage == kStageShading) {
-                c->sn_ms += ms;
-                c->sn_launches += 1;
+            if (e.stage >= WFPT_STAGE_COUNT) { // a pass (pass_stage), not a wfpt_stage: the caller's arrays have no entry for it
+                wfpt_ctx::PassTimer &t = c->pass[e.stage - WFPT_STAGE_COUNT];
+                t.ms += ms;
+                t.launches += 1;
                 continue;
             }
             stage_ms[e.stage] += ms;
@@ -2421,9 +2400,7 @@ int wfpt_copy_aov_to_device(wfpt_ctx *c, int which, void *device_ptr, size_t n_b
 int wfpt_aov_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (!c) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_aov_timing_ms: null context");
     if (!c->aov_sums.get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_aov_timing_ms: the context was created without WFPT_FLAG_AOV");
-    if (ms_total) *ms_total = static_cast<float>(c->aov_ms);
-    if (launches) *launches = c->aov_launches;
-    return WFPT_OK;
+    return pass_timing(c, kPassAov, ms_total, launches);
 }
 
 void wfpt_denoise_params_default(wfpt_denoise_params *p) {
@@ -3164,22 +3141,39 @@ void wfpt_environment_params_default(wfpt_environment_params *p) {
     p->rotation = 0.0f;
 }
 
-static int environment_check(wfpt_ctx *c, const char *who) {
-    if (int r = flag_check(c, who, WFPT_FLAG_ENVIRONMENT, "WFPT_FLAG_ENVIRONMENT"); r != WFPT_OK) return r;
-    if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
-        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no environment map");
+// The texels of a map or a texture, w x h x rgb on the host, checked and brought to the device for `who` (whose own arguments are in
+// order): float4 per texel (one 16-byte load in the kernels), converted in pieces so that the host never holds a second copy of a large one
+static int upload_texels(wfpt_ctx *c, const char *who, const float *rgb, uint32_t w, uint32_t h, DeviceBuffer<float4> &tex) {
+    const size_t n = static_cast<size_t>(w) * h;
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!(rgb[i] >= 0.0f && rgb[i] <= FLT_MAX)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": texels must be finite and >= 0");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    WFPT_HIP(c, tex.alloc(n));
+    constexpr size_t kPiece = 1u << 20;
+    std::vector<float4> piece(std::min(n, kPiece));
+    for (size_t i0 = 0; i0 < n; i0 += kPiece) {
+        const size_t m = std::min(kPiece, n - i0);
+        for (size_t i = 0; i < m; ++i) {
+            const float *t = rgb + 3 * (i0 + i);
+            piece[i] = make_float4(t[0], t[1], t[2], 0.0f);
+        }
+        if (const hipError_t e = hipMemcpy(tex.get() + i0, piece.data(), sizeof(float4) * m, hipMemcpyHostToDevice); e != hipSuccess)
+            return hip_fail(c, e, (std::string(who) + ": upload").c_str());
+    }
     return WFPT_OK;
 }
 
+static int environment_check(wfpt_ctx *c, const char *who) {
+    return feature_check(c, who, WFPT_FLAG_ENVIRONMENT, "WFPT_FLAG_ENVIRONMENT", "environment map");
+}
+
 // The sampling distribution of a candidate map (WFPT_FLAG_ENV_NEE contexts; include/wfpt.h "Environment next-event estimation"), built on
-// the device without touching the context. A black map has none (its buffers stay null). `plane`: the second plane, allocated here if the
-// context has none yet and the map gets a distribution.
+// the device without touching the context. A black map has none (its buffers stay null). `second`: reserved where the map gets one.
 struct EnvTables {
     DeviceBuffer<uint32_t> row;
     DeviceBuffer<uint64_t> marg;
     uint64_t total = 0;
-    DeviceBuffer<float> plane;
-    DeviceBuffer<float4> origin; // WFPT_FLAG_ENV_MIS: the hit-point plane comes and stays with the second plane
+    SecondPlane second;
 };
 static int build_env_tables(wfpt_ctx *c, const EnvDev &env, EnvTables &out) {
     if (!(c->p.flags & WFPT_FLAG_ENV_NEE)) return WFPT_OK;
@@ -3201,12 +3195,7 @@ static int build_env_tables(wfpt_ctx *c, const EnvDev &env, EnvTables &out) {
     WFPT_HIP(c, hipMemcpyAsync(&out.total, out.marg.get() + (env.h - 1u), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     WFPT_HIP(c, hipStreamSynchronize(st));
     if (out.total == 0) return fail(c, WFPT_ERR_HIP, "wfpt_set_environment: the sampling distribution of a lit map is empty");
-    if (!c->emitted.get()) {
-        WFPT_HIP(c, out.plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
-        WFPT_HIP(c, hipMemset(out.plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
-        if (c->p.flags & WFPT_FLAG_ENV_MIS) WFPT_HIP(c, out.origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
-    }
-    return WFPT_OK;
+    return reserve_second_plane(c, out.second);
 }
 
 // a new map (or none) is a new scene for the accumulation, the temporal history and the captured graphs (whose kernel arguments hold the map)
@@ -3216,8 +3205,7 @@ static int environment_changed(wfpt_ctx *c, DeviceBuffer<float4> tex, uint32_t w
     c->env_row = std::move(t.row); // and the old map's distribution
     c->env_marg = std::move(t.marg);
     c->env_total = t.total;
-    if (t.plane.get()) c->emitted = std::move(t.plane);
-    if (t.origin.get()) c->mis_origin = std::move(t.origin);
+    commit_second_plane(c, std::move(t.second));
     return scene_changed(c);
 }
 
@@ -3233,25 +3221,8 @@ int wfpt_set_environment(wfpt_ctx *c, const float *rgb, uint32_t w, uint32_t h, 
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_environment: intensity must be finite and >= 0, rotation in [0, 1)");
     for (uint32_t r : p->_reserved)
         if (r != 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_environment: _reserved must be 0");
-    const size_t n = static_cast<size_t>(w) * h;
-    for (size_t i = 0; i < 3 * n; ++i)
-        if (!(rgb[i] >= 0.0f && rgb[i] <= FLT_MAX))
-            return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_environment: texels must be finite and >= 0");
-    WFPT_HIP(c, hipSetDevice(c->device));
     DeviceBuffer<float4> tex;
-    WFPT_HIP(c, tex.alloc(n));
-    // float4 per texel (one 16-byte load in the kernels), converted in pieces so that the host never holds a second copy of a large map
-    constexpr size_t kPiece = 1u << 20;
-    std::vector<float4> piece(std::min(n, kPiece));
-    for (size_t i0 = 0; i0 < n; i0 += kPiece) {
-        const size_t m = std::min(kPiece, n - i0);
-        for (size_t i = 0; i < m; ++i) {
-            const float *t = rgb + 3 * (i0 + i);
-            piece[i] = make_float4(t[0], t[1], t[2], 0.0f);
-        }
-        if (const hipError_t e = hipMemcpy(tex.get() + i0, piece.data(), sizeof(float4) * m, hipMemcpyHostToDevice); e != hipSuccess)
-            return hip_fail(c, e, "wfpt_set_environment: upload");
-    }
+    if (int r = upload_texels(c, "wfpt_set_environment", rgb, w, h, tex); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old map
     EnvTables tables;
     if (int r = build_env_tables(c, EnvDev{tex.get(), w, h, p->intensity, p->rotation}, tables); r != WFPT_OK) return r;
@@ -3302,12 +3273,7 @@ static void commit_texture_tables(wfpt_ctx *c, TextureTables &&t) {
     c->tex_prim = std::move(t.prim);
 }
 
-static int texture_check(wfpt_ctx *c, const char *who) {
-    if (int r = flag_check(c, who, WFPT_FLAG_TEXTURES, "WFPT_FLAG_TEXTURES"); r != WFPT_OK) return r;
-    if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
-        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no textures");
-    return WFPT_OK;
-}
+static int texture_check(wfpt_ctx *c, const char *who) { return feature_check(c, who, WFPT_FLAG_TEXTURES, "WFPT_FLAG_TEXTURES", "textures"); }
 
 void wfpt_texture_params_default(wfpt_texture_params *p) {
     if (!p) return;
@@ -3329,23 +3295,8 @@ int wfpt_set_texture(wfpt_ctx *c, uint32_t slot, const float *rgb, uint32_t w, u
     if (p->filter > static_cast<uint32_t>(WFPT_TEXTURE_NEAREST)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: unknown filter");
     for (uint32_t r : p->_reserved)
         if (r != 0) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: _reserved must be 0");
-    const size_t n = static_cast<size_t>(w) * h;
-    for (size_t i = 0; i < 3 * n; ++i)
-        if (!(rgb[i] >= 0.0f && rgb[i] <= FLT_MAX)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_set_texture: texels must be finite and >= 0");
-    WFPT_HIP(c, hipSetDevice(c->device));
     DeviceBuffer<float4> tex;
-    WFPT_HIP(c, tex.alloc(n));
-    constexpr size_t kPiece = 1u << 20; // float4 per texel, converted in pieces (as wfpt_set_environment)
-    std::vector<float4> piece(std::min(n, kPiece));
-    for (size_t i0 = 0; i0 < n; i0 += kPiece) {
-        const size_t m = std::min(kPiece, n - i0);
-        for (size_t i = 0; i < m; ++i) {
-            const float *t = rgb + 3 * (i0 + i);
-            piece[i] = make_float4(t[0], t[1], t[2], 0.0f);
-        }
-        if (const hipError_t e = hipMemcpy(tex.get() + i0, piece.data(), sizeof(float4) * m, hipMemcpyHostToDevice); e != hipSuccess)
-            return hip_fail(c, e, "wfpt_set_texture: upload");
-    }
+    if (int r = upload_texels(c, "wfpt_set_texture", rgb, w, h, tex); r != WFPT_OK) return r;
     TexDev dev[WFPT_MAX_TEXTURES];
     std::copy(c->tex_dev, c->tex_dev + WFPT_MAX_TEXTURES, dev);
     dev[slot] = TexDev{tex.get(), w, h, p->scale[0], p->scale[1], p->offset[0], p->offset[1], p->filter, 0u};
@@ -3425,9 +3376,7 @@ int wfpt_sample_texture(wfpt_ctx *c, uint32_t slot, const float *uv, size_t n, f
 
 int wfpt_texture_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = flag_check(c, "wfpt_texture_timing_ms", WFPT_FLAG_TEXTURES, "WFPT_FLAG_TEXTURES"); r != WFPT_OK) return r;
-    if (ms_total) *ms_total = static_cast<float>(c->tex_ms);
-    if (launches) *launches = c->tex_launches;
-    return WFPT_OK;
+    return pass_timing(c, kPassTexture, ms_total, launches);
 }
 
 // ---------------------------------------------------------------- shading normals (include/wfpt.h "Shading normals")
@@ -3446,7 +3395,7 @@ static int build_normal_rows(wfpt_ctx *c, const std::vector<float> &n9, const st
 }
 
 static int shading_check(wfpt_ctx *c, const char *who) {
-    return flag_check(c, who, WFPT_FLAG_SHADING_NORMALS, "WFPT_FLAG_SHADING_NORMALS");
+    return feature_check(c, who, WFPT_FLAG_SHADING_NORMALS, "WFPT_FLAG_SHADING_NORMALS");
 }
 
 int wfpt_set_triangle_normals(wfpt_ctx *c, const float *n9, uint32_t n_rows) {
@@ -3454,8 +3403,10 @@ int wfpt_set_triangle_normals(wfpt_ctx *c, const float *n9, uint32_t n_rows) {
     if (int r = shading_check(c, who); r != WFPT_OK) return r;
     if (c->scene.prim_kind != 1) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sphere context takes no triangle normals");
     if (!n9) n_rows = 0;
-    if (n_rows && wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
-        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no shading normals");
+    // the class-binned refusal, of a call that brings rows only (clearing is always allowed); it has always come after the sphere
+    // context's, so the flag is looked at a second time here rather than the refusal moved up
+    if (int r = feature_check(c, who, WFPT_FLAG_SHADING_NORMALS, "WFPT_FLAG_SHADING_NORMALS", n_rows ? "shading normals" : nullptr); r != WFPT_OK)
+        return r;
     std::vector<float> stored(9 * static_cast<size_t>(n_rows));
     if (wfpt_normalize_triangle_normals(n9, n_rows, stored.data()) != WFPT_OK)
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": normals must be finite");
@@ -3497,9 +3448,7 @@ int wfpt_sample_shading_normal(wfpt_ctx *c, const float *in4, size_t n, float *o
 
 int wfpt_shading_normal_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = shading_check(c, "wfpt_shading_normal_timing_ms"); r != WFPT_OK) return r;
-    if (ms_total) *ms_total = static_cast<float>(c->sn_ms);
-    if (launches) *launches = c->sn_launches;
-    return WFPT_OK;
+    return pass_timing(c, kPassShading, ms_total, launches);
 }
 
 // ---------------------------------------------------------------- emission (include/wfpt.h "Emission")
@@ -3583,10 +3532,7 @@ static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t) {
 }
 
 static int emission_check(wfpt_ctx *c, const char *who, bool changes) {
-    if (int r = flag_check(c, who, WFPT_FLAG_EMISSION, "WFPT_FLAG_EMISSION"); r != WFPT_OK) return r;
-    if (changes && wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
-        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no emitters");
-    return WFPT_OK;
+    return feature_check(c, who, WFPT_FLAG_EMISSION, "WFPT_FLAG_EMISSION", changes ? "emitters" : nullptr);
 }
 
 // The candidate colours replace the context's: tables first, then the second plane if this is the first emitter, and only then the commit
@@ -3594,16 +3540,11 @@ static int apply_emission(wfpt_ctx *c, std::vector<float> &&rgb) {
     WFPT_HIP(c, hipSetDevice(c->device));
     EmissionTables tables;
     if (int r = build_emission_tables(c, rgb, c->h_prim_mat_idx, tables); r != WFPT_OK) return r;
-    DeviceBuffer<float> plane;
-    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS, WFPT_FLAG_ENV_MIS: the hit-point plane comes and stays with the second plane
-    if (tables.prim.get() && !c->emitted.get()) {
-        WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
-        WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
-        if (c->p.flags & (WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS)) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
-    }
+    SecondPlane second;
+    if (tables.prim.get())
+        if (int r = reserve_second_plane(c, second); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
-    if (plane.get()) c->emitted = std::move(plane);
-    if (origin.get()) c->mis_origin = std::move(origin);
+    commit_second_plane(c, std::move(second));
     c->em_rgb = std::move(rgb);
     commit_emission_tables(c, std::move(tables));
     return scene_changed(c);
@@ -3639,9 +3580,7 @@ int wfpt_clear_emission(wfpt_ctx *c) {
 
 int wfpt_emission_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = emission_check(c, "wfpt_emission_timing_ms", false); r != WFPT_OK) return r;
-    if (ms_total) *ms_total = static_cast<float>(c->em_ms);
-    if (launches) *launches = c->em_launches;
-    return WFPT_OK;
+    return pass_timing(c, kPassEmission, ms_total, launches);
 }
 
 // ---------------------------------------------------------------- next-event estimation (include/wfpt.h "Next-event estimation")
@@ -3654,9 +3593,7 @@ int wfpt_nee_light_count(wfpt_ctx *c) {
 
 int wfpt_nee_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = nee_check(c, "wfpt_nee_timing_ms"); r != WFPT_OK) return r;
-    if (ms_total) *ms_total = static_cast<float>(c->nee_ms);
-    if (launches) *launches = c->nee_launches;
-    return WFPT_OK;
+    return pass_timing(c, kPassConnect, ms_total, launches);
 }
 
 int wfpt_sample_lights(wfpt_ctx *c, const float *in9, size_t n, float *out8) {
@@ -3702,15 +3639,16 @@ int wfpt_read_light_distribution(wfpt_ctx *c, uint32_t *light_prims, uint64_t *c
 }
 
 // ---------------------------------------------------------------- analytic lights (include/wfpt.h "Analytic lights")
-static int lights_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_ANALYTIC_LIGHTS, "WFPT_FLAG_ANALYTIC_LIGHTS"); }
+// sets: the call brings lights (wfpt_set_lights)
+static int lights_check(wfpt_ctx *c, const char *who, bool sets = false) {
+    return feature_check(c, who, WFPT_FLAG_ANALYTIC_LIGHTS, "WFPT_FLAG_ANALYTIC_LIGHTS", sets ? "lights" : nullptr);
+}
 
 static bool finite3(const float v[3]) { return std::fabs(v[0]) <= FLT_MAX && std::fabs(v[1]) <= FLT_MAX && std::fabs(v[2]) <= FLT_MAX; }
 
 int wfpt_set_lights(wfpt_ctx *c, const wfpt_light *lights, uint32_t n) {
     const char *who = "wfpt_set_lights";
-    if (int r = lights_check(c, who); r != WFPT_OK) return r;
-    if (wfpt_loop_kind_of(c) == WFPT_LOOP_FUSED_BINNED)
-        return fail(c, WFPT_ERR_UNSUPPORTED, std::string(who) + ": the class-binned loop (WFPT_FLAG_BINNING) takes no lights");
+    if (int r = lights_check(c, who, true); r != WFPT_OK) return r;
     if (n > WFPT_MAX_LIGHTS) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": more than WFPT_MAX_LIGHTS lights");
     if (!lights && n) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": null lights");
     std::vector<wfpt_light> cand(lights, lights + (lights ? n : 0u));
@@ -3738,21 +3676,15 @@ int wfpt_set_lights(wfpt_ctx *c, const wfpt_light *lights, uint32_t n) {
     }
     WFPT_HIP(c, hipSetDevice(c->device));
     DeviceBuffer<float4> rows;
-    DeviceBuffer<float> plane;
-    DeviceBuffer<float4> origin; // WFPT_FLAG_MIS: the hit-point plane comes and stays with the second plane
+    SecondPlane second;
     if (!cand.empty()) {
         static_assert(sizeof(wfpt_light) == 3 * sizeof(float4), "a light is three rows");
         WFPT_HIP(c, rows.alloc(3 * cand.size()));
         WFPT_HIP(c, hipMemcpy(rows.get(), cand.data(), sizeof(wfpt_light) * cand.size(), hipMemcpyHostToDevice));
-        if (!c->emitted.get()) {
-            WFPT_HIP(c, plane.alloc(static_cast<size_t>(c->batch_max) * c->image_floats));
-            WFPT_HIP(c, hipMemset(plane.get(), 0, sizeof(float) * c->batch_max * c->image_floats));
-            if (c->p.flags & WFPT_FLAG_MIS) WFPT_HIP(c, origin.alloc(static_cast<size_t>(c->batch_max) * (c->image_floats / 4)));
-        }
+        if (int r = reserve_second_plane(c, second); r != WFPT_OK) return r;
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
-    if (plane.get()) c->emitted = std::move(plane);
-    if (origin.get()) c->mis_origin = std::move(origin);
+    commit_second_plane(c, std::move(second));
     c->light_rows = std::move(rows);
     c->h_lights = std::move(cand);
     return scene_changed(c);

@@ -343,12 +343,7 @@ class PathTracer {
         check(wfpt_sample_texture(ctx_, slot, uv.data(), uv.size() / 2, rgb.data()));
         return rgb;
     }
-    std::pair<float, uint32_t> texture_timing() {
-        float ms = 0.0f;
-        uint32_t n = 0;
-        check(wfpt_texture_timing_ms(ctx_, &ms, &n));
-        return {ms, n};
-    }
+    std::pair<float, uint32_t> texture_timing() { return timing(wfpt_texture_timing_ms); }
     // Shading normals (WFPT_FLAG_SHADING_NORMALS, include/wfpt.h "Shading normals"): rows of the normals of corners 0, 1, 2, nine floats
     // each, row r for the triangles whose _pad is r; empty clears.
     void set_triangle_normals(const std::vector<float> &n9) {
@@ -366,12 +361,7 @@ class PathTracer {
         check(wfpt_sample_shading_normal(ctx_, in4.data(), in4.size() / 4, out.data()));
         return out;
     }
-    std::pair<float, uint32_t> shading_normal_timing() {
-        float ms = 0.0f;
-        uint32_t n = 0;
-        check(wfpt_shading_normal_timing_ms(ctx_, &ms, &n));
-        return {ms, n};
-    }
+    std::pair<float, uint32_t> shading_normal_timing() { return timing(wfpt_shading_normal_timing_ms); }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
@@ -380,24 +370,14 @@ class PathTracer {
         return rgb;
     }
     void clear_emission() { check(wfpt_clear_emission(ctx_)); }
-    std::pair<float, uint32_t> emission_timing() {
-        float ms = 0.0f;
-        uint32_t n = 0;
-        check(wfpt_emission_timing_ms(ctx_, &ms, &n));
-        return {ms, n};
-    }
+    std::pair<float, uint32_t> emission_timing() { return timing(wfpt_emission_timing_ms); }
     // Next-event estimation (WFPT_FLAG_EMISSION | WFPT_FLAG_NEE, include/wfpt.h "Next-event estimation"): shadow rays from diffuse hits to the emitters.
     uint32_t nee_light_count() {
         const int n = wfpt_nee_light_count(ctx_);
         if (n < 0) check(n);
         return static_cast<uint32_t>(n);
     }
-    std::pair<float, uint32_t> nee_timing() {
-        float ms = 0.0f;
-        uint32_t n = 0;
-        check(wfpt_nee_timing_ms(ctx_, &ms, &n));
-        return {ms, n};
-    }
+    std::pair<float, uint32_t> nee_timing() { return timing(wfpt_nee_timing_ms); }
     // rows of (p.xyz, n.xyz, u0, u1, u2) -> rows of (q.xyz, light primitive, e_q G rgb, occluded)
     std::vector<float> sample_lights(const std::vector<float> &in9) {
         std::vector<float> out(in9.size() / 9 * 8);
@@ -558,6 +538,13 @@ class PathTracer {
   private:
     void check(int st) const {
         if (st != WFPT_OK) throw Error(st, wfpt_last_error(ctx_));
+    }
+    // (milliseconds, launches) as one of the wfpt_*_timing_ms entry points reports them
+    std::pair<float, uint32_t> timing(int (*entry)(wfpt_ctx *, float *, uint32_t *)) {
+        float ms = 0.0f;
+        uint32_t n = 0;
+        check(entry(ctx_, &ms, &n));
+        return {ms, n};
     }
     wfpt_ctx *ctx_ = nullptr;
     RenderParameters render_parameters_;
