@@ -149,7 +149,7 @@ static uint32_t bands_of(uint32_t height, uint32_t rank, uint32_t world) {
 }
 
 // The passes of the timed renders that are no wfpt_stage; a pass's entry in an event record is pass_stage(pass)
-enum Pass { kPassAov, kPassTexture, kPassEmission, kPassConnect, kPassShading, kPassCount };
+enum Pass { kPassAov, kPassTexture, kPassEmission, kPassConnect, kPassShading, kPassMicrofacet, kPassCount };
 constexpr int pass_stage(Pass pass) { return WFPT_STAGE_COUNT + pass; }
 
 struct wfpt_ctx {
@@ -206,7 +206,7 @@ struct wfpt_ctx {
     bool fused = true;
     DeviceBuffer<float> image, accumulated;
     DeviceBuffer<float> aov_sums; // WFPT_FLAG_AOV: [kAovPlanes][pixel_capacity] first-hit sums (wfpt_kernels.h), null without the flag
-    // the launches of each pass in the timed renders since wfpt_create (wfpt_aov_timing_ms and its four siblings)
+    // the launches of each pass in the timed renders since wfpt_create (wfpt_aov_timing_ms and its five siblings)
     struct PassTimer {
         double ms = 0.0;
         uint32_t launches = 0;
@@ -244,7 +244,7 @@ struct wfpt_ctx {
     uint32_t tex_uv_rows = 0;
     DeviceBuffer<TexDev> tex_desc;
     DeviceBuffer<uint2> tex_prim;
-    std::vector<uint32_t> h_prim_mat_idx, h_prim_row; // material_idx and _pad per primitive (textured, emitting and shading-normal contexts)
+    std::vector<uint32_t> h_prim_mat_idx, h_prim_row; // material_idx and _pad per primitive (textured, emitting, shading-normal and microfacet contexts)
     // WFPT_FLAG_EMISSION (include/wfpt.h "Emission"): the colour per material (3 floats each, all zero = no emitter), what
     // build_emission_tables makes of them for the kernels -- per primitive its material_idx or kNoEmission, and the colours as float4 (both
     // null while no material emits: nothing new is launched then) -- and the second per-sample plane, image's shape, which comes with
@@ -273,11 +273,18 @@ struct wfpt_ctx {
     DeviceBuffer<float4> light_rows;
     // WFPT_FLAG_SHADING_NORMALS (include/wfpt.h "Shading normals"): the table of corner normals as stored (9 floats a row), what
     // build_normal_rows makes of it for the kernels -- per primitive its row as three float4 (null while no table is set: nothing new is
-    // launched then) -- and the per-hit shade records of the shading-normal pass, 3 x float4 per ray-queue slot per sample in flight,
-    // allocated with the first table and released with the last
+    // launched then)
     std::vector<float> h_normals;
     DeviceBuffer<float4> sn_rows;
-    DeviceBuffer<float4> sn_table;
+    // WFPT_FLAG_MICROFACET (include/wfpt.h "Microfacet metals"): the roughness per material (empty or all zero = no rough material) and what
+    // build_roughness_table makes of it for the kernel -- per primitive its material's alpha where the primitive is metal, +0 otherwise
+    // (null while no alpha is above 0: nothing new is launched then)
+    std::vector<float> mf_alpha;
+    DeviceBuffer<float> mf_prim;
+    // The per-hit shade records of the shading-normal and microfacet passes, 3 x float4 per ray-queue slot per sample in flight: one table
+    // for both features, allocated with the first of {table of normals, roughness above 0} and released with the last
+    // (reserve_hit_table, commit_hit_table)
+    DeviceBuffer<float4> hit_table;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
     // dropped with it (null with no map, and for a black map: the context then runs as one without the flag), and the environment share
     DeviceBuffer<uint32_t> env_row;
@@ -802,7 +809,26 @@ const float *miss_gate(const wfpt_ctx *c) { return env_connecting(c) ? c->emitte
 bool shading(const wfpt_ctx *c) { return c->sn_rows.get() != nullptr; }
 // the pass over the hits `w` names; rec_out: the records the shade step that follows streams its hits from
 ShadingArgs shading_args(wfpt_ctx *c, const HitWalk &w, float4 *rec_out) {
-    return ShadingArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->sn_table.get(), rec_out};
+    return ShadingArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->hit_table.get(), rec_out};
+}
+// a WFPT_FLAG_MICROFACET context holds a roughness above 0: the microfacet pass runs before the shade steps that scatter, in the
+// shading-normal pass's place where the context holds a table of normals as well
+bool rough(const wfpt_ctx *c) { return c->mf_prim.get() != nullptr; }
+MicrofacetArgs microfacet_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w, float4 *rec_out) {
+    return MicrofacetArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->mf_prim.get(), c->hit_table.get(), rec_out, wavefront};
+}
+// the shade steps that scatter read their shade records per hit (shaded_scene), from the table one of the two passes has just written
+bool per_hit(const wfpt_ctx *c) { return shading(c) || rough(c); }
+// The per-hit table for a CANDIDATE state that needs one, into `out` unless the context already holds it; commit_hit_table(c, out, needed)
+// then installs it, or releases the context's once neither feature needs it (the stream is idle: the caller synchronised it)
+int reserve_hit_table(wfpt_ctx *c, DeviceBuffer<float4> &out) {
+    if (c->hit_table.get()) return WFPT_OK;
+    WFPT_HIP(c, out.alloc(3 * static_cast<size_t>(c->batch_max) * c->capacity));
+    return WFPT_OK;
+}
+void commit_hit_table(wfpt_ctx *c, DeviceBuffer<float4> &&t, bool needed) {
+    if (t.get()) c->hit_table = std::move(t);
+    if (!needed) c->hit_table.release();
 }
 
 ScanBinnedArgs scan_binned_args(wfpt_ctx *c, uint32_t bounce, uint32_t nb, int parity) {
@@ -840,7 +866,7 @@ hipError_t launch_miss_pass(wfpt_ctx *c, const MissArgs &a, uint32_t grid) {
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
-    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && !analytic_selecting(c) && !shading(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
+    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && !analytic_selecting(c) && !shading(c) && !rough(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
 }
 // The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
@@ -872,23 +898,28 @@ struct EventRec { int stage; hipEvent_t start, stop; };
 // see (it reads the flag the previous step's connect pass left). In the loops they follow the scan that decides whether the loop goes on
 // (shade_n = 0 once it has exited), as the shade they precede.
 // shaded: the loops of a context that holds a table of corner normals (include/wfpt.h "Shading normals"; the stage API passes false and
-// ignores the table): the connect pass takes the shading normal, and where the step scatters -- shade_rec_out names the records it
-// streams its hits from, null before the last wavefront's shade, whose extension rays nobody traces -- the shading-normal pass runs last:
-// it rewrites the records' primitive words, which the passes before it read. The caller then hands the step shaded_scene(c).
+// ignores the table): the connect pass takes the shading normal.
+// shade_rec_out: the loops of a context whose step reads its shade records per hit (per_hit(c): a table of normals, a roughness above 0 --
+// include/wfpt.h "Microfacet metals" -- or both; the stage API passes null and ignores both), where the step scatters: the records it
+// streams its hits from, null before the last wavefront's shade, whose extension rays nobody traces. The pass that writes the per-hit
+// table -- the microfacet pass where the context is rough, else the shading-normal pass -- then runs last: it rewrites the records'
+// primitive words, which the passes before it read. The caller then hands the step shaded_scene(c).
 template <typename Timed>
 int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const HitWalk &w, bool shaded = false, float4 *shade_rec_out = nullptr) {
     const uint32_t grid = consumer_grid(c, nb);
     if (textured(c)) WFPT_HIP(c, timed(pass_stage(kPassTexture), [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
     if (emitting(c)) WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
     if (connecting(c)) WFPT_HIP(c, timed(pass_stage(kPassConnect), [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
-    if (shaded && shade_rec_out)
+    if (shade_rec_out && rough(c))
+        WFPT_HIP(c, timed(pass_stage(kPassMicrofacet), [&] { return launch_microfacet(microfacet_args(c, b, w, shade_rec_out), grid, c->stream.get()); }));
+    else if (shade_rec_out)
         WFPT_HIP(c, timed(pass_stage(kPassShading), [&] { return launch_shading_normal(shading_args(c, w, shade_rec_out), grid, c->stream.get()); }));
     return WFPT_OK;
 }
-// the scene of a shade step that follows the shading-normal pass: the per-hit records in the primitives' place
+// the scene of a shade step that follows the shading-normal or the microfacet pass: the per-hit records in the primitives' place
 SceneDev shaded_scene(const wfpt_ctx *c) {
     SceneDev sc = c->scene;
-    sc.shade_rec = c->sn_table.get();
+    sc.shade_rec = c->hit_table.get();
     return sc;
 }
 
@@ -906,7 +937,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
                  }));
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), st); }));
         const HitWalk w = hit_walk(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity);
-        const bool scatters = shading(c) && b + 1 < c->p.max_wavefronts; // (the last wavefront's extension rays are never traced)
+        const bool scatters = per_hit(c) && b + 1 < c->p.max_wavefronts; // (the last wavefront's extension rays are never traced)
         if (int r = enqueue_pre_shade(c, timed, b, nb, w, shading(c), scatters ? c->hit_rec.get() : nullptr); r != WFPT_OK) return r;
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
@@ -942,7 +973,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const bool last = b + 1 >= c->p.max_wavefronts;
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
-        const bool scatters = shading(c) && !last;
+        const bool scatters = per_hit(c) && !last;
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
             return r;
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
@@ -993,7 +1024,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         const bool last = b + 1 >= c->p.max_wavefronts;
         if (!last || env) // (the last launch's miss items: a launch of their own only with the map)
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
-        const bool scatters = shading(c) && !last;
+        const bool scatters = per_hit(c) && !last;
         if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
             return r;
         if (!last) {
@@ -1572,7 +1603,7 @@ int upload_scene(wfpt_ctx *c, const wfpt_sphere *spheres, const wfpt_triangle *t
     c->far_rays = false;
     c->depth4 = depth4;
     c->h_prim_mat_type = std::move(mat_type);
-    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS))
+    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET))
         prim_mat_rows(spheres, triangles, n_spheres, c->h_prim_mat_idx, c->h_prim_row);
     c->blocks_per_cu = static_cast<uint32_t>(blocks);
     c->bounce_blocks_per_cu = static_cast<uint32_t>(bounce_blocks);
@@ -1676,6 +1707,9 @@ const FlagRule kFlagRules[] = {
     {WFPT_FLAG_SHADING_NORMALS, 0, WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS, nullptr,
      "wfpt_create: WFPT_FLAG_SHADING_NORMALS does not go with WFPT_FLAG_LIGHT_POWER or "
      "WFPT_FLAG_ANALYTIC_LIGHTS (their connect kernels are twins of their own)"},
+    // WFPT_FLAG_MICROFACET needs nothing and goes with every flag: metal hits never connect, so the connect kernels need no twin for it,
+    // and its pass writes the per-hit records whichever connect kernel ran before it
+    {WFPT_FLAG_MICROFACET, 0, 0, nullptr, nullptr},
     // (WFPT_FLAG_ENV_MIS goes with no WFPT_FLAG_MIS either, since it weighs the emitters itself: the WFPT_FLAG_ENV_NEE it needs has
     // refused that at WFPT_FLAG_MIS's row)
     {WFPT_FLAG_ENV_MIS, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect | WFPT_FLAG_ENV_NEE, 0,
@@ -1805,9 +1839,12 @@ static wfpt_ctx *create_impl(const wfpt_params *params, const wfpt_sphere *spher
         wfpt_destroy(c);
         return nullptr;
     }
-    // WFPT_FLAG_SHADING_NORMALS: shade gathers the per-hit record of queue slot k at 3 * k, in 32 bits as it gathers a primitive's
-    if ((params->flags & WFPT_FLAG_SHADING_NORMALS) != 0 && 3ull * nb_all * c->capacity > 0xffffffffull) {
-        fail(nullptr, WFPT_ERR_UNSUPPORTED, "wfpt_create: WFPT_FLAG_SHADING_NORMALS: samples in flight x ray capacity beyond 2^32 / 3 per-hit shade records");
+    // WFPT_FLAG_SHADING_NORMALS, WFPT_FLAG_MICROFACET: shade gathers the per-hit record of queue slot k at 3 * k, in 32 bits as it gathers a
+    // primitive's
+    if ((params->flags & (WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET)) != 0 && 3ull * nb_all * c->capacity > 0xffffffffull) {
+        fail(nullptr, WFPT_ERR_UNSUPPORTED,
+             std::string("wfpt_create: ") + ((params->flags & WFPT_FLAG_SHADING_NORMALS) ? "WFPT_FLAG_SHADING_NORMALS" : "WFPT_FLAG_MICROFACET") +
+                 ": samples in flight x ray capacity beyond 2^32 / 3 per-hit shade records");
         wfpt_destroy(c);
         return nullptr;
     }
@@ -1946,7 +1983,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -2046,6 +2083,8 @@ static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, con
                                  const float4 *geom = nullptr, uint32_t prim_kind = 0);
 static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t);
 static int build_normal_rows(wfpt_ctx *c, const std::vector<float> &n9, const std::vector<uint32_t> &row, DeviceBuffer<float4> &out);
+static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
+                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
     if (!c || !(spheres || triangles) || !materials || n_prims == 0 || n_materials == 0)
@@ -2063,6 +2102,8 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
             if (triangles[i]._pad >= c->h_normals.size() / 9)
                 return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene_mesh: a triangle's row (_pad) is beyond the table of normals");
     }
+    if (spheres && rough(c)) // WFPT_FLAG_MICROFACET with a roughness above 0: spheres take none
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a roughness above 0 (clear it first)");
     WFPT_HIP(c, hipSetDevice(c->device));
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old scene
     std::vector<wfpt_bvh_node> nodes(2 * static_cast<size_t>(n_prims));
@@ -2076,13 +2117,22 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     if (depth < 0) return depth;
     // of the new primitive order (the builders above have reordered the caller's arrays), for the contexts that have a table to build
     std::vector<uint32_t> mat_idx, row;
-    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS)) prim_mat_rows(spheres, triangles, n_prims, mat_idx, row);
+    if (c->p.flags & (WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET)) prim_mat_rows(spheres, triangles, n_prims, mat_idx, row);
     TextureTables tables; // the texture tables of the new primitive order, built before anything is replaced
     if (c->p.flags & WFPT_FLAG_TEXTURES)
         if (int r = build_texture_tables(c, c->tex_dev, c->tex_bind, mat_idx, row, tables); r != WFPT_OK) return r;
     DeviceBuffer<float4> sn_rows; // likewise the normal rows of the new primitive order
     if (!c->h_normals.empty())
         if (int r = build_normal_rows(c, c->h_normals, row, sn_rows); r != WFPT_OK) return r;
+    DeviceBuffer<float> mf_prim; // likewise the roughness table; the alphas of materials the new scene no longer has are dropped
+    std::vector<float> mf_alpha;
+    if (rough(c)) {
+        mf_alpha = c->mf_alpha;
+        mf_alpha.resize(n_materials, 0.0f);
+        std::vector<uint32_t> mat_type(n_prims);
+        for (uint32_t i = 0; i < n_prims; ++i) mat_type[i] = triangles[i].material_type;
+        if (int r = build_roughness_table(c, mf_alpha, mat_idx, mat_type, mf_prim); r != WFPT_OK) return r;
+    }
     EmissionTables em_tables; // likewise; the colours of materials the new scene no longer has are dropped
     std::vector<float> em_rgb;
     if (c->p.flags & WFPT_FLAG_EMISSION) {
@@ -2107,6 +2157,11 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         return r; // the context keeps its old scene, graphs, texture tables and accumulation
     if (c->p.flags & WFPT_FLAG_TEXTURES) commit_texture_tables(c, std::move(tables));
     if (sn_rows.get()) c->sn_rows = std::move(sn_rows);
+    if (rough(c)) { // (the dropped alphas may have been the last above 0: the per-hit records then go with them)
+        c->mf_alpha = std::move(mf_alpha);
+        c->mf_prim = std::move(mf_prim);
+        commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
+    }
     if (c->p.flags & WFPT_FLAG_EMISSION) {
         c->em_rgb = std::move(em_rgb);
         commit_emission_tables(c, std::move(em_tables));
@@ -3417,11 +3472,10 @@ int wfpt_set_triangle_normals(wfpt_ctx *c, const float *n9, uint32_t n_rows) {
     DeviceBuffer<float4> rows, table;
     if (n_rows) {
         if (int r = build_normal_rows(c, stored, c->h_prim_row, rows); r != WFPT_OK) return r;
-        if (!c->sn_table.get()) WFPT_HIP(c, table.alloc(3 * static_cast<size_t>(c->batch_max) * c->capacity));
+        if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old rows
-    if (table.get()) c->sn_table = std::move(table);
-    if (!n_rows) c->sn_table.release();
+    commit_hit_table(c, std::move(table), n_rows != 0 || rough(c));
     c->sn_rows = std::move(rows); // (the kernels take them from the context at each launch; the graphs that hold the old ones are dropped)
     c->h_normals = std::move(stored);
     return scene_changed(c);
@@ -3449,6 +3503,82 @@ int wfpt_sample_shading_normal(wfpt_ctx *c, const float *in4, size_t n, float *o
 int wfpt_shading_normal_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = shading_check(c, "wfpt_shading_normal_timing_ms"); r != WFPT_OK) return r;
     return pass_timing(c, kPassShading, ms_total, launches);
+}
+
+// ---------------------------------------------------------------- microfacet metals (include/wfpt.h "Microfacet metals")
+// The kernel's view of the roughnesses and the scene: per primitive its material's alpha where the primitive's material_type is 1 (Metal),
+// +0 otherwise, in the order the device holds the primitives; null while no alpha is above 0. Built for a CANDIDATE state -- alphas (one
+// per material, missing ones 0), and per primitive its material_idx and material_type -- without touching the context, like
+// build_emission_tables.
+static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
+                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out) {
+    bool any = false;
+    for (float a : alpha) any = any || a > 0.0f;
+    if (!any) return WFPT_OK;
+    const size_t n = mat_idx.size();
+    std::vector<float> t(n);
+    for (size_t i = 0; i < n; ++i) t[i] = mat_type[i] == 1u && mat_idx[i] < alpha.size() ? alpha[mat_idx[i]] : 0.0f;
+    WFPT_HIP(c, out.alloc(n));
+    WFPT_HIP(c, hipMemcpy(out.get(), t.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    return WFPT_OK;
+}
+
+static int microfacet_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_MICROFACET, "WFPT_FLAG_MICROFACET"); }
+
+// The candidate alphas replace the context's: the table first, then the per-hit records if this is the first feature that needs them, and
+// only then the commit
+static int apply_roughness(wfpt_ctx *c, const char *who, std::vector<float> &&alpha) {
+    if (c->scene.prim_kind != 1) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sphere context takes no roughness");
+    bool any = false;
+    for (float a : alpha) any = any || a > 0.0f;
+    if (int r = feature_check(c, who, WFPT_FLAG_MICROFACET, "WFPT_FLAG_MICROFACET", any ? "roughness" : nullptr); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipSetDevice(c->device));
+    DeviceBuffer<float> prim;
+    DeviceBuffer<float4> table;
+    if (int r = build_roughness_table(c, alpha, c->h_prim_mat_idx, c->h_prim_mat_type, prim); r != WFPT_OK) return r;
+    if (prim.get())
+        if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
+    commit_hit_table(c, std::move(table), prim.get() != nullptr || shading(c));
+    c->mf_prim = std::move(prim); // (the kernel takes it from the context at each launch; the graphs that hold the old one are dropped)
+    c->mf_alpha = std::move(alpha);
+    return scene_changed(c);
+}
+
+int wfpt_set_roughness(wfpt_ctx *c, uint32_t material_idx, float alpha) {
+    const char *who = "wfpt_set_roughness";
+    if (int r = microfacet_check(c, who); r != WFPT_OK) return r;
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": material_idx out of range");
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": alpha must lie in [0, 1]");
+    std::vector<float> cand = c->mf_alpha;
+    cand.resize(c->scene.n_materials, 0.0f);
+    cand[material_idx] = alpha + 0.0f; // (-0 -> +0)
+    return apply_roughness(c, who, std::move(cand));
+}
+
+int wfpt_get_roughness(wfpt_ctx *c, uint32_t material_idx, float *alpha) {
+    if (int r = microfacet_check(c, "wfpt_get_roughness"); r != WFPT_OK) return r;
+    if (!alpha) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_roughness: null alpha");
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_roughness: material_idx out of range");
+    *alpha = material_idx < c->mf_alpha.size() ? c->mf_alpha[material_idx] : 0.0f;
+    return WFPT_OK;
+}
+
+int wfpt_clear_roughness(wfpt_ctx *c) {
+    if (int r = microfacet_check(c, "wfpt_clear_roughness"); r != WFPT_OK) return r;
+    return apply_roughness(c, "wfpt_clear_roughness", std::vector<float>(c->scene.n_materials, 0.0f));
+}
+
+int wfpt_sample_microfacet(wfpt_ctx *c, const float *in12, size_t n, float *out8) {
+    if (int r = microfacet_check(c, "wfpt_sample_microfacet"); r != WFPT_OK) return r;
+    return probe(c, "wfpt_sample_microfacet", in12, 12, out8, 8, n, true, [&](const float *d_in, float *d_out) {
+        return launch_microfacet_sample(d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
+}
+
+int wfpt_microfacet_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
+    if (int r = microfacet_check(c, "wfpt_microfacet_timing_ms"); r != WFPT_OK) return r;
+    return pass_timing(c, kPassMicrofacet, ms_total, launches);
 }
 
 // ---------------------------------------------------------------- emission (include/wfpt.h "Emission")

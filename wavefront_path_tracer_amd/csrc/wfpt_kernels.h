@@ -614,6 +614,25 @@ struct ShadingArgs {
     float4 *rec_out;
 };
 
+// The microfacet pass (microfacet_kernel; WFPT_FLAG_MICROFACET contexts that hold a roughness above 0, include/wfpt.h "Microfacet metals"):
+// it takes the shading-normal pass's place as the last pass before a shade step that scatters, and writes the same per-hit table -- every
+// hit's own shade record at its slot, the slot in the primitive word of the record the step streams. At a rough hit the record is
+// (m | +0), (F * G1(wo) | rec1.w), rec2: a microfacet normal for the metal branch of scatter() to reflect about and the estimator's weight
+// for shade to multiply the throughput by; the shade launch is handed `table` exactly as after the shading-normal pass.
+// mf_prim: per PRIMITIVE, in the order the device holds them, its material's roughness alpha where the primitive's material_type is 1
+// (Metal) and +0 otherwise: the one 4-byte gather that decides whether a hit samples or only copies.
+// normals: the shading-normal pass's per-primitive rows where the context holds a table of corner normals (microfacet_kernel<true>: every
+// record carries the shading normal), null otherwise.
+struct MicrofacetArgs {
+    HitWalk w;
+    const float4 *prim_geom;
+    const float4 *normals;
+    const float *mf_prim;
+    float4 *table;
+    float4 *rec_out;
+    uint32_t wavefront;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -822,6 +841,10 @@ hipError_t launch_shading_normal(const ShadingArgs &a, uint32_t grid, hipStream_
 // thread per row; a primitive outside the scene answers (0, 0, 0, 1)
 hipError_t launch_shading_sample(const float4 *prim_geom, const float4 *shade_rec, const float4 *normals, uint32_t n_prims, const float *in4,
                                  float *out4, uint32_t n, hipStream_t s);
+hipError_t launch_microfacet(const MicrofacetArgs &a, uint32_t grid, hipStream_t s);
+// wfpt_sample_microfacet: n rows of (d.xyz, n.xyz, u1, u2, alpha, F0.rgb) -> (m.xyz | 2 where step 1 fell back, 1 where step 10 left the
+// weight at zero, else 0 | weight.rgb | cm), one thread per row; both buffers 16-byte aligned
+hipError_t launch_microfacet_sample(const float *in12, float *out8, uint32_t n, hipStream_t s);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the

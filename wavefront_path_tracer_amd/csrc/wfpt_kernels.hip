@@ -2132,6 +2132,127 @@ __global__ __launch_bounds__(256) void shading_sample_kernel(const float4 *prim_
 }
 
 // ================================================================================================
+// microfacet pass (WFPT_FLAG_MICROFACET; include/wfpt.h "Microfacet metals")
+// ================================================================================================
+// Steps 1-11 of the header in its operation order (IEEE f32 add / sub / mul / div / sqrt, sincos_, max_, no fma; tests/microfacet_ref.py
+// restates it): a GGX microfacet normal m drawn from the distribution of normals visible from wi = -normalize3(d) about the normal n, and
+// the estimator's weight F * G1(wo) of the reflection about it. fell: step 1 fell back (the hit is shaded as without roughness; m, weight
+// and cm are +0 then); dead: step 10 left the weight at +0.
+struct MicrofacetSample {
+    float3_ m, weight;
+    float cm;
+    bool fell, dead;
+};
+__device__ __forceinline__ MicrofacetSample microfacet_sample(float3_ d, float3_ n, float u1, float u2, float alpha, float3_ f0) {
+    MicrofacetSample o;
+    o.m = o.weight = {0.0f, 0.0f, 0.0f};
+    o.cm = 0.0f;
+    o.dead = false;
+    const float3_ dn = normalize3(d);
+    const float3_ wi = {-dn.x, -dn.y, -dn.z};
+    float cn = dot3(n, wi);
+    float3_ nf = n;
+    if (cn < 0.0f) { // conductors are two-sided
+        nf = {-n.x, -n.y, -n.z};
+        cn = -cn;
+    }
+    o.fell = !(cn > 0.0f); // (zero or NaN)
+    if (o.fell) return o;
+    // 2. the basis about nf (Duff et al. 2017)
+    const float sg = nf.z >= 0.0f ? 1.0f : -1.0f;
+    const float a = -1.0f / (sg + nf.z);
+    const float bb = (nf.x * nf.y) * a;
+    const float3_ t = {1.0f + ((sg * nf.x) * nf.x) * a, sg * bb, -(sg * nf.x)};
+    const float3_ bt = {bb, sg + (nf.y * nf.y) * a, -nf.y};
+    // 3-5. wi in the basis, stretched, and the basis about it
+    const float3_ l = {dot3(t, wi), dot3(bt, wi), cn};
+    const float3_ vh = normalize3({alpha * l.x, alpha * l.y, l.z});
+    const float l2 = vh.x * vh.x + vh.y * vh.y;
+    float3_ T1 = {1.0f, 0.0f, 0.0f};
+    if (l2 > 0.0f) {
+        const float il = 1.0f / sqrt_(l2);
+        T1 = {-vh.y * il, vh.x * il, 0.0f};
+    }
+    const float3_ T2 = {vh.y * T1.z - vh.z * T1.y, vh.z * T1.x - vh.x * T1.z, vh.x * T1.y - vh.y * T1.x};
+    // 6-8. a point of the projected disk, warped, lifted onto the hemisphere and unstretched (Heitz 2018)
+    const float r = sqrt_(u1);
+    float sn, cs;
+    sincos_((2.0f * kPi) * u2, sn, cs);
+    const float t1 = r * cs;
+    float t2 = r * sn;
+    const float s = 0.5f * (1.0f + vh.z);
+    t2 = (1.0f - s) * sqrt_(max_(0.0f, 1.0f - t1 * t1)) + s * t2;
+    const float h = sqrt_(max_(0.0f, (1.0f - t1 * t1) - t2 * t2));
+    const float3_ nh = {(t1 * T1.x + t2 * T2.x) + h * vh.x, (t1 * T1.y + t2 * T2.y) + h * vh.y, (t1 * T1.z + t2 * T2.z) + h * vh.z};
+    const float3_ ml = normalize3({alpha * nh.x, alpha * nh.y, max_(0.0f, nh.z)});
+    // 9. back to the world, not renormalised
+    o.m = {(ml.x * t.x + ml.y * bt.x) + ml.z * nf.x, (ml.x * t.y + ml.y * bt.y) + ml.z * nf.y, (ml.x * t.z + ml.y * bt.z) + ml.z * nf.z};
+    // 10. the reflection; below the horizon on either side the path is dead
+    const float cm = dot3(wi, o.m);
+    o.cm = cm;
+    const float k = 2.0f * cm;
+    const float3_ wo = {k * o.m.x - wi.x, k * o.m.y - wi.y, k * o.m.z - wi.z};
+    const float co = dot3(nf, wo);
+    o.dead = !(cm > 0.0f) || !(co > 0.0f);
+    if (o.dead) return o;
+    // 11. F * G1(wo): the separable Smith term and Schlick's Fresnel term on the microfacet's cosine
+    const float a2 = alpha * alpha;
+    const float G = (2.0f * co) / (co + sqrt_(a2 + (1.0f - a2) * (co * co)));
+    const float f = 1.0f - cm;
+    const float f5 = ((f * f) * (f * f)) * f;
+    o.weight = {(f0.x + (1.0f - f0.x) * f5) * G, (f0.y + (1.0f - f0.y) * f5) * G, (f0.z + (1.0f - f0.z) * f5) * G};
+    return o;
+}
+
+// One launch before a shade step that scatters, after that step's other passes, in shading_normal_kernel's place on a context that holds
+// a roughness above 0 (MicrofacetArgs). Every hit's own shade record goes to the hit's slot of the table and the slot's index takes the
+// primitive's place in the record the step streams, as there; a rough hit's record is (m | +0), (weight | rec1.w), rec2 -- the metal branch
+// of scatter() then reflects about m and shade multiplies the throughput by the weight -- and every other hit's is the primitive's own.
+// NORMALS: the context holds a table of corner normals as well: the normal of every record is the shading normal, bit for bit what
+// shading_normal_kernel writes, and a rough hit samples about it.
+// One 4-byte gather (mf_prim) decides; the sampler stays inside the branch, so a wave without a rough lane only copies.
+template <bool NORMALS>
+__global__ __launch_bounds__(kConsumerThreads) void microfacet_kernel(MicrofacetArgs a) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    const uint32_t frame = uniform(a.w.ctl->frame.frame) + blockIdx.y; // the sample's frame: the batch's first one, as the connect pass takes it, plus the sample
+    for_each_shaded_hit<true>(a.w, s, [&](size_t slot, const Hit &h) {
+        const float alpha = a.mf_prim[h.prim];
+        const float4 rec0 = a.w.shade_rec[3u * h.prim], rec1 = a.w.shade_rec[3u * h.prim + 1u], rec2 = a.w.shade_rec[3u * h.prim + 2u];
+        float3_ n = {rec0.x, rec0.y, rec0.z};
+        if (NORMALS) shading_normal_at(a.prim_geom, a.normals, h.prim, h.p, {rec0.x, rec0.y, rec0.z}, n);
+        float4 o0 = make_float4(n.x, n.y, n.z, rec0.w), o1 = rec1;
+        if (alpha > 0.0f) {
+            uint32_t rng = jenkins_hash(h.pixel_idx ^ jenkins_hash(frame)); // init_rng((x, y), (W, H), frame): x + y W is the pixel
+            rng = jenkins_hash(rng ^ (0xC2B2AE35u * (a.wavefront + 1u)));
+            const float u1 = rng_next_float(rng);
+            const float u2 = rng_next_float(rng);
+            const MicrofacetSample ms = microfacet_sample(h.d, n, u1, u2, alpha, {rec1.x, rec1.y, rec1.z});
+            if (!ms.fell) {
+                o0 = make_float4(ms.m.x, ms.m.y, ms.m.z, 0.0f);
+                o1 = make_float4(ms.weight.x, ms.weight.y, ms.weight.z, rec1.w);
+            }
+        }
+        float4 *out = a.table + 3u * slot;
+        out[0] = o0;
+        out[1] = o1;
+        out[2] = rec2;
+        a.rec_out[2u * slot + 1u].w = __uint_as_float(static_cast<uint32_t>(slot)); // (3 * slot stays below 2^32: wfpt_create's size check)
+    });
+}
+
+// wfpt_sample_microfacet: microfacet_sample for caller rows of (d.xyz, n.xyz, u1, u2, alpha, F0.rgb), one thread per row
+__global__ __launch_bounds__(256) void microfacet_sample_kernel(const float *in12, float *out8, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 *row = reinterpret_cast<const float4 *>(in12 + 12u * static_cast<size_t>(i)); // (48-byte rows of a 256-byte-aligned buffer)
+    const float4 r0 = row[0], r1 = row[1], r2 = row[2];
+    const MicrofacetSample ms = microfacet_sample({r0.x, r0.y, r0.z}, {r0.w, r1.x, r1.y}, r1.z, r1.w, r2.x, {r2.y, r2.z, r2.w});
+    float4 *out = reinterpret_cast<float4 *>(out8 + 8u * static_cast<size_t>(i));
+    out[0] = make_float4(ms.m.x, ms.m.y, ms.m.z, ms.fell ? 2.0f : ms.dead ? 1.0f : 0.0f);
+    out[1] = make_float4(ms.weight.x, ms.weight.y, ms.weight.z, ms.cm);
+}
+
+// ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
 // The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
@@ -4785,6 +4906,20 @@ hipError_t launch_shading_sample(const float4 *prim_geom, const float4 *shade_re
                                  float *out4, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(shading_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, prim_geom, shade_rec, normals, n_prims, in4, out4, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_microfacet(const MicrofacetArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    if (!a.mf_prim || !a.table || !a.rec_out) return hipErrorInvalidValue;
+    if (a.normals) hipLaunchKernelGGL(microfacet_kernel<true>, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
+    else hipLaunchKernelGGL(microfacet_kernel<false>, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_microfacet_sample(const float *in12, float *out8, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(microfacet_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, in12, out8, n);
     return hipGetLastError();
 }
 

@@ -362,6 +362,21 @@ class PathTracer {
         return out;
     }
     std::pair<float, uint32_t> shading_normal_timing() { return timing(wfpt_shading_normal_timing_ms); }
+    // Microfacet metals (WFPT_FLAG_MICROFACET, include/wfpt.h "Microfacet metals"): a material's GGX roughness alpha in [0, 1]; its metal
+    // primitives are shaded as rough conductors while it is above 0.
+    void set_roughness(uint32_t material_idx, float alpha) { check(wfpt_set_roughness(ctx_, material_idx, alpha)); }
+    float roughness(uint32_t material_idx) {
+        float alpha = 0.0f;
+        check(wfpt_get_roughness(ctx_, material_idx, &alpha));
+        return alpha;
+    }
+    void clear_roughness() { check(wfpt_clear_roughness(ctx_)); }
+    std::vector<float> sample_microfacet(const std::vector<float> &in12) { // (d.xyz, n.xyz, u1, u2, alpha, F0.rgb) -> (m.xyz | state | weight.rgb | cm)
+        std::vector<float> out(in12.size() / 12 * 8);
+        check(wfpt_sample_microfacet(ctx_, in12.data(), in12.size() / 12, out.data()));
+        return out;
+    }
+    std::pair<float, uint32_t> microfacet_timing() { return timing(wfpt_microfacet_timing_ms); }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
