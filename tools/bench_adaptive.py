@@ -19,19 +19,14 @@ since the criterion is a relative one, the RMS of the luminance error relative t
 uniform render that takes the adaptive one's time (equal time: its RMSE), and the uniform samples that would reach the adaptive RMSE
 under the 1/n law (equal error: its time, extrapolated).
 
-Method: every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that drift hits them alike. A
-child warms up (graph capture, first touch), then times --frames frames one by one, each ending in a device synchronise. A leg's
-figure is the median of all its frames; its spread is the range of its per-round medians. The quality leg runs once. Prints one JSON line
-per leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. The quality leg runs once, in a child of its own, after the frame legs."""
 import json
-import os
-import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+
+EXTRA_KEYS, DIGITS = ("rays_per_frame", "active_share"), None  # (as they came)
 
 
 def make(W, a, scene, flags):
@@ -57,17 +52,10 @@ def frame_leg(W, np, a, scene, setting):
         m = tile_mask(np, a, setting)
         pt.set_active_mask(m)
         active = float(m.mean())
-    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
-    pt.render(a.spp)
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
+    ms = ab.timed_frames(pt, a.spp, a.frames)
     totals = [int(x) for x in pt.totals()]
-    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms, "rays_per_frame": totals[0] / (a.frames + 2), "active_share": active}
+    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms, "rays_per_frame": totals[0] / (a.frames + 2),  # (timed_frames warms up with two)
+           "active_share": active}
     pt.close()
     return out
 
@@ -143,75 +131,44 @@ def leg(a):
     print(json.dumps(out), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
-    ap.add_argument("--frames", type=int, default=12)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--triangles", type=int, default=1000000)
+def options():
+    ap = ab.parser(frames=12)
     ap.add_argument("--max-passes", type=int, default=256)
     ap.add_argument("--interval", type=int, default=16)
     ap.add_argument("--reference-spp", type=int, default=1024)
     ap.add_argument("--scenes", nargs="+", default=["shirley", "mesh"])
     ap.add_argument("--no-quality", action="store_true", help="skip the scene:adaptive legs")
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    return ap
+
+
+def legs(a):
+    out = []
+    for scene in a.scenes:
+        out.append(ab.entry(f"{scene}:off"))
+        if a.parent_tree:
+            out.append(ab.entry(f"{scene}:off@parent", tree=a.parent_tree))
+        out += [ab.entry(f"{scene}:{setting}") for setting in ("on", "random", "contig")]
+    return out
+
+
+def main():
+    a = options().parse_args()
     if a.leg:
         return leg(a)
-
-    def run(name, tree):
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
-               str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--frames", str(a.frames), "--triangles", str(a.triangles),
-               "--max-passes", str(a.max_passes), "--interval", str(a.interval), "--reference-spp", str(a.reference_spp)]
-        env = dict(os.environ)
-        env.pop("WFPT_LIB", None)  # each tree loads its own library
-        res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
-        if res.returncode != 0:
-            sys.exit(f"bench_adaptive: leg {name} failed with status {res.returncode}")
-        return json.loads(res.stdout.strip().splitlines()[-1])
-
-    legs = []
-    for scene in a.scenes:
-        legs.append((f"{scene}:off", ROOT))
-        if a.parent_tree:
-            legs.append((f"{scene}:off@parent", os.path.abspath(a.parent_tree)))
-        legs += [(f"{scene}:{setting}", ROOT) for setting in ("on", "random", "contig")]
-    results = {name: {"rounds": [], "last": None} for name, _ in legs}
-    for _ in range(a.rounds):
-        for name, tree in legs:
-            r = run(name, tree)
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name, _ in legs:
-        rounds = results[name]["rounds"]
-        per_round = [statistics.median(r) for r in rounds]
-        last = results[name]["last"]
-        line = {"leg": name, "loop": last["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces, "frames": a.frames,
-                "rounds": a.rounds, "frame_ms_median": round(statistics.median(x for r in rounds for x in r), 3),
-                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3),
-                "rays_per_frame": last["rays_per_frame"], "active_share": last["active_share"]}
-        summary[name] = line
-        print(json.dumps(line), flush=True)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS)
     rel = {}
     for name in summary:
         scene, setting = name.split("@")[0].split(":")
-        ms = summary[name]["frame_ms_median"]
         if "@" in name:
-            rel[f"{scene}:off over {name}"] = round(summary[f"{scene}:off"]["frame_ms_median"] / ms - 1.0, 4)
+            rel.update(ab.ratios(summary, [(f"{scene}:off", name)]))
         elif setting == "on":
-            rel[f"{name} over {scene}:off"] = round(ms / summary[f"{scene}:off"]["frame_ms_median"] - 1.0, 4)
-        elif setting != "off":
-            rel[f"{name} over {scene}:on"] = round(ms / summary[f"{scene}:on"]["frame_ms_median"], 4)
+            rel.update(ab.ratios(summary, [(name, f"{scene}:off")]))
+        elif setting != "off":  # a share of the all-active frame, not an excess over it
+            rel[f"{name} over {scene}:on"] = round(summary[name]["frame_ms_median"] / summary[f"{scene}:on"]["frame_ms_median"], 4)
     if not a.no_quality:
         for scene in a.scenes:
-            q = run(f"{scene}:adaptive", ROOT)
+            q = ab.run_child(__file__, ab.entry(f"{scene}:adaptive"), a)
             print(json.dumps(q), flush=True)
             rel[f"{scene}: equal time, RMSE uniform over adaptive"] = q["equal_time"]["rmse_uniform_over_adaptive"]
             rel[f"{scene}: equal time, relative RMS uniform over adaptive"] = q["equal_time"]["relative_rms_uniform_over_adaptive"]

@@ -11,25 +11,22 @@ Legs on the Shirley scene, --spp samples per frame, all with WFPT_FLAG_EMISSION 
 `sun` and `far` carry WFPT_FLAG_DENOISE as well: after the timed frames each renders --variance-spp samples into a fresh accumulation
 and reports the sum of wfpt_read_variance over the image, the variance of the frame at equal samples.
 
-Method, as tools/bench_nee.py: every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that drift
-hits them alike. A child warms up (graph capture, first touch), then times --frames frames one by one, each ending in a device
-synchronise. A leg's figure is the median of all its frames; its spread is the range of its per-round medians. The connect launches' own
-time comes from wfpt_nee_timing_ms over one timed frame (hipEvent pairs around every launch, so it is slower than the frame it describes);
-connect_ms_per_launch is that total over its launch count. Prints one JSON line per leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. The connect launches' own time comes from wfpt_nee_timing_ms over one timed frame
+(hipEvent pairs around every launch, so it is slower than the frame it describes); connect_ms_per_launch is that total over its launch
+count."""
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+
+EXTRA_KEYS = ("emitters", "analytic_lights", "connect_ms_timed", "connect_launches_timed", "connect_ms_per_launch", "stages_ms_timed", "variance_sum",
+              "mean_luminance")
+DIGITS = 6
 SUN_DIRECTION, SUN_IRRADIANCE = (-0.4, -1.0, -0.3), (3.0, 2.7, 2.1)
 
 
 def leg(a):
-    sys.path.insert(0, ROOT)
+    sys.path.insert(0, a.tree)
     import numpy as np
     import wavefront_path_tracer_amd as W
     flags = W.FLAG_EMISSION | W.FLAG_NEE
@@ -67,15 +64,7 @@ def leg(a):
     elif a.leg == "far":
         omega = np.pi * (a.far_radius / a.far_distance) ** 2
         pt.set_emission(far_material, tuple(float(e) / omega for e in SUN_IRRADIANCE))
-    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
-    pt.render(a.spp)
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
+    ms = ab.timed_frames(pt, a.spp, a.frames)
     stage_ms, _ = pt.render_timed(a.spp)
     nee_ms, launches = pt.nee_timing()
     out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms, "emitters": pt.nee_light_count(),
@@ -90,53 +79,29 @@ def leg(a):
     pt.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
+def options():
+    ap = ab.parser(triangles=None)
     ap.add_argument("--variance-spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
-    ap.add_argument("--frames", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--far-radius", type=float, default=50.0)
     ap.add_argument("--far-distance", type=float, default=1000.0)
     ap.add_argument("--legs", nargs="+", default=["nee", "analytic", "sun", "far"])
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    return ap
+
+
+def legs(a):
+    return [ab.entry(name) for name in a.legs]
+
+
+def main():
+    a = options().parse_args()
     if a.leg:
         return leg(a)
-    results = {name: {"rounds": [], "last": None} for name in a.legs}
-    for _ in range(a.rounds):
-        for name in a.legs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--width", str(a.width), "--height", str(a.height), "--spp", str(a.spp),
-                   "--variance-spp", str(a.variance_spp), "--bounces", str(a.bounces), "--frames", str(a.frames), "--far-radius", str(a.far_radius),
-                   "--far-distance", str(a.far_distance)]
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=600)  # a failed or hung leg ends the run
-            if res.returncode != 0:
-                sys.exit(f"bench_analytic_lights: leg {name} failed with status {res.returncode}")
-            r = json.loads(res.stdout.strip().splitlines()[-1])
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name in a.legs:
-        rounds, last = results[name]["rounds"], results[name]["last"]
-        per_round = [statistics.median(r) for r in rounds]
-        line = {"leg": name, "loop": last["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces, "frames": a.frames,
-                "rounds": a.rounds, "frame_ms_median": round(statistics.median(x for r in rounds for x in r), 3),
-                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3)}
-        for k, v in last.items():
-            if k not in ("leg", "loop", "frame_ms"):
-                line[k] = round(v, 6) if isinstance(v, float) else v
-        summary[name] = line
-        print(json.dumps(line), flush=True)
-    rel = {}
-    if "analytic" in summary and "nee" in summary:
-        rel["analytic over nee, frame"] = round(summary["analytic"]["frame_ms_median"] / summary["nee"]["frame_ms_median"] - 1.0, 4)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS)
+    rel = ab.ratios(summary, [("analytic", "nee")], ", frame")
+    if rel:
         rel["analytic over nee, connect launch"] = round(summary["analytic"]["connect_ms_per_launch"] / summary["nee"]["connect_ms_per_launch"] - 1.0, 4)
     if "sun" in summary and "far" in summary:
-        rel["sun over far, frame"] = round(summary["sun"]["frame_ms_median"] / summary["far"]["frame_ms_median"] - 1.0, 4)
+        rel.update(ab.ratios(summary, [("sun", "far")], ", frame"))
         rel["variance sum, sun over far"] = round(summary["sun"]["variance_sum"] / summary["far"]["variance_sum"], 6)
     print(json.dumps({"summary": rel}), flush=True)
 

@@ -12,22 +12,16 @@ and, with --parent-tree DIR (a checkout of the parent commit with its library bu
 named `<leg>@parent` and run right after their twins: the kernels a context without the flag launches are the parent's, so each pair is
 expected to agree within the larger spread of the two.
 
-Method (tools/bench_nee.py's): every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that
-drift hits them alike. A child warms up, then times --frames frames one by one, each ending in a device synchronise. A leg's figure is
-the median of all its frames; its spread is the range of its per-round medians. Each leg then renders one frame on a second context with
-WFPT_FLAG_DENOISE and reports the sum of wfpt_read_variance over the frame. The summary gives, per map, the frame-time ratios, the
-variance ratios at equal spp and the variance ratios at equal time = (variance ratio) * (frame-time ratio) of env_mis against env_nee and
-against env. Prints one JSON line per leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. Each leg then renders one frame on a second context with WFPT_FLAG_DENOISE and
+reports the sum of wfpt_read_variance over the frame. The summary gives, per map, the frame-time ratios, the variance ratios at equal spp
+and the variance ratios at equal time = (variance ratio) * (frame-time ratio) of env_mis against env_nee and against env."""
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+from bench_env_nee import sun_map
+
+EXTRA_KEYS, DIGITS = ("connect_ms_timed", "connect_launches_timed", "miss_ms_timed", "stages_ms_timed", "variance_sum"), 6
 
 
 def soft_map(np, w=2048, h=1024):
@@ -43,7 +37,6 @@ def leg(a):
     sys.path.insert(0, a.tree)
     import numpy as np
     import wavefront_path_tracer_amd as W
-    from bench_env_nee import sun_map
     which, kind = a.leg.split(":")
     flags = W.FLAG_ENVIRONMENT
     if kind != "env":
@@ -58,16 +51,7 @@ def leg(a):
         return pt
 
     pt = tracer()
-    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
-    pt.render(a.spp)
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms}
+    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ab.timed_frames(pt, a.spp, a.frames)}
     stage_ms, _ = pt.render_timed(a.spp)
     out.update(stages_ms_timed=float(np.sum(stage_ms)), miss_ms_timed=float(stage_ms[W.STAGES["miss_kernel"]]))
     if kind != "env":
@@ -81,54 +65,24 @@ def leg(a):
     print(json.dumps(out), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
-    ap.add_argument("--frames", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=3)
+def options():
+    ap = ab.parser(triangles=None)
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    return ap
+
+
+def legs(a):  # the parent has no env_mis leg
+    return ab.with_twins([ab.entry(f"{m}:{k}") for m in ("sun", "soft") for k in ("env", "env_nee", "env_mis")], a.parent_tree,
+                         lambda name: not name.endswith("env_mis"))
+
+
+def main():
+    a = options().parse_args()
     if a.leg:
         return leg(a)
-    legs = [(f"{m}:{k}", ROOT) for m in ("sun", "soft") for k in ("env", "env_nee", "env_mis")]
-    if a.parent_tree:  # the parent has no env_mis leg
-        legs = [x for name, tree in legs
-                for x in ([(name, tree)] + ([(name + "@parent", os.path.abspath(a.parent_tree))] if not name.endswith("env_mis") else []))]
-    results = {name: {"rounds": [], "last": None} for name, _ in legs}
-    for _ in range(a.rounds):
-        for name, tree in legs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
-                   str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--frames", str(a.frames)]
-            env = dict(os.environ)
-            env.pop("WFPT_LIB", None)  # each tree loads its own library
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
-            if res.returncode != 0:
-                sys.exit(f"bench_env_mis: leg {name} failed with status {res.returncode}")
-            r = json.loads(res.stdout.strip().splitlines()[-1])
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name, _ in legs:
-        rounds = results[name]["rounds"]
-        med = statistics.median(x for r in rounds for x in r)
-        per_round = [statistics.median(r) for r in rounds]
-        line = {"leg": name, "loop": results[name]["last"]["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces,
-                "frames": a.frames, "rounds": a.rounds, "frame_ms_median": round(med, 3),
-                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3)}
-        for k in ("connect_ms_timed", "connect_launches_timed", "miss_ms_timed", "stages_ms_timed", "variance_sum"):
-            if k in results[name]["last"]:
-                line[k] = round(results[name]["last"][k], 6) if isinstance(results[name]["last"][k], float) else results[name]["last"][k]
-        summary[name] = line
-        print(json.dumps(line), flush=True)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS)
     rel = {}
-    for name, _ in legs:
-        base = name + "@parent"
+    for name, base in ab.twin_pairs(summary):
         if base in summary:  # the flag-off pairs: the difference against the larger spread of the two
             rel[f"{name} minus {base} ms"] = round(summary[name]["frame_ms_median"] - summary[base]["frame_ms_median"], 3)
             rel[f"{name} bound ms"] = max(summary[name]["spread_ms"], summary[base]["spread_ms"])

@@ -9,21 +9,16 @@ and, with --parent-tree DIR (a checkout of the parent commit with its library bu
 `<leg>@parent` and run right after its twin: the kernels a context without the flag launches are the parent's, so the plain pair is
 expected to be equal within the spread reported here, and the other pairs say what a change to the feature's own kernels costs.
 
-Method: tools/bench_nee.py's. Every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that drift
-hits them alike. A child warms up (graph capture, first touch), then times --frames frames one by one, each ending in a device
-synchronise. A leg's figure is the median of all its frames; its spread is the range of its per-round medians. The connect and emission
-launches' own times come from wfpt_nee_timing_ms and wfpt_emission_timing_ms over one timed frame (hipEvent pairs around every launch, so
-it is slower than the frame it describes). The lamp legs also report the sum of wfpt_read_variance over the frame (WFPT_FLAG_DENOISE is
-set on them), for the equal-time product variance x frame time. Prints one JSON line per leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. The connect and emission launches' own times come from wfpt_nee_timing_ms and
+wfpt_emission_timing_ms over one timed frame (hipEvent pairs around every launch, so it is slower than the frame it describes). The lamp
+legs also report the sum of wfpt_read_variance over the frame (WFPT_FLAG_DENOISE is set on them), for the equal-time product variance x
+frame time."""
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+
+EXTRA_KEYS, DIGITS = ("lights", "variance_sum", "connect_ms_timed", "connect_launches_timed", "emission_ms_timed", "stages_ms_timed"), 3
 
 
 def leg(a):
@@ -55,16 +50,7 @@ def leg(a):
                 pt.set_emission(int(m), c)
     else:
         sys.exit(f"bench_mis: unknown scene {scene}")
-    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
-    pt.render(a.spp)
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms}
+    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ab.timed_frames(pt, a.spp, a.frames)}
     if scene in ("lamp", "near"):  # the variance of the last frame's mean, summed over the frame (every leg restarts from the same state)
         pt.reset_progress()
         pt.render(a.spp)
@@ -78,65 +64,35 @@ def leg(a):
     pt.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
-    ap.add_argument("--frames", type=int, default=20)
-    ap.add_argument("--rounds", type=int, default=3)
+def options():
+    ap = ab.parser(triangles=None)
     ap.add_argument("--scenes", nargs="+", default=["shirley", "lamp", "near"])
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
-    a = ap.parse_args()
-    if a.leg:
-        return leg(a)
-    legs = []
+    return ap
+
+
+def legs(a):
+    out = []
     if "shirley" in a.scenes:
-        legs += [("shirley:plain", ROOT), ("shirley:lit", ROOT), ("shirley:nee", ROOT), ("shirley:mis", ROOT)]
+        out += [ab.entry(f"shirley:{kind}") for kind in ("plain", "lit", "nee", "mis")]
     for scene in ("lamp", "near"):
         if scene in a.scenes:
-            legs += [(f"{scene}:lit", ROOT), (f"{scene}:nee", ROOT), (f"{scene}:mis", ROOT)]
-    if a.parent_tree:
-        legs = [x for name, tree in legs for x in ((name, tree), (name + "@parent", os.path.abspath(a.parent_tree)))]
-    results = {name: {"rounds": [], "last": None} for name, _ in legs}
-    for _ in range(a.rounds):
-        for name, tree in legs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
-                   str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--frames", str(a.frames)]
-            env = dict(os.environ)
-            env.pop("WFPT_LIB", None)  # each tree loads its own library
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
-            if res.returncode != 0:
-                sys.exit(f"bench_mis: leg {name} failed with status {res.returncode}")
-            r = json.loads(res.stdout.strip().splitlines()[-1])
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name, _ in legs:
-        rounds = results[name]["rounds"]
-        med = statistics.median(x for r in rounds for x in r)
-        per_round = [statistics.median(r) for r in rounds]
-        line = {"leg": name, "loop": results[name]["last"]["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces,
-                "frames": a.frames, "rounds": a.rounds, "frame_ms_median": round(med, 3),
-                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3)}
-        for k in ("lights", "variance_sum", "connect_ms_timed", "connect_launches_timed", "emission_ms_timed", "stages_ms_timed"):
-            if k in results[name]["last"]:
-                line[k] = round(results[name]["last"][k], 3) if isinstance(results[name]["last"][k], float) else results[name]["last"][k]
-        summary[name] = line
-        print(json.dumps(line), flush=True)
+            out += [ab.entry(f"{scene}:{kind}") for kind in ("lit", "nee", "mis")]
+    return ab.with_twins(out, a.parent_tree)
+
+
+def main():
+    a = options().parse_args()
+    if a.leg:
+        return leg(a)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS)
     rel = {}
-    twins = [(name, name + "@parent") for name, _ in legs if not name.endswith("@parent")]
     for name, base in [("shirley:lit", "shirley:plain"), ("shirley:nee", "shirley:lit"), ("shirley:mis", "shirley:nee"), ("lamp:mis", "lamp:nee"),
-                       ("near:mis", "near:nee"), ("near:mis", "near:lit")] + twins:
-        if name in summary and base in summary:
-            rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
-            if "variance_sum" in summary[name] and "variance_sum" in summary[base]:  # equal time: variance x frame time, MIS over the base
-                rel[f"{name} over {base}, variance x time"] = round(
-                    summary[name]["variance_sum"] * summary[name]["frame_ms_median"] / (summary[base]["variance_sum"] * summary[base]["frame_ms_median"]), 4)
+                       ("near:mis", "near:nee"), ("near:mis", "near:lit")] + ab.twin_pairs(summary):
+        rel.update(ab.ratios(summary, [(name, base)]))
+        if "variance_sum" in summary.get(name, {}) and "variance_sum" in summary.get(base, {}):  # equal time: variance x frame time
+            rel[f"{name} over {base}, variance x time"] = round(
+                summary[name]["variance_sum"] * summary[name]["frame_ms_median"] / (summary[base]["variance_sum"] * summary[base]["frame_ms_median"]), 4)
     print(json.dumps({"summary": rel}), flush=True)
 
 

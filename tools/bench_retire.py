@@ -11,21 +11,16 @@ with the default parameters (roulette from wavefront 3 on, q_min 0.05).
 and, with --parent-tree DIR (a checkout of the parent commit with its library built), the plain Shirley frame of that tree: the kernels a
 context without the flag launches are the parent's, so the two are expected to be equal within the spread reported here.
 
-Method: every leg runs in a fresh child process (nothing is shared between legs but the machine), --rounds times, the legs alternating
-within a round so that drift hits them alike. A child warms up (graph capture, first touch), then times --frames frames one by one, each
-ending in a device synchronise. A leg's figure is the median of all its frames; its spread is the range of its per-round medians. With
---equal-time MS the lit and nee legs of shirley and room then render on a second context with WFPT_FLAG_DENOISE (the luminance moments)
-for MS milliseconds and report the samples that fitted and the image mean of wfpt_read_variance, the variance of the pixels' mean
-luminance: the variance at equal time. Prints one JSON line per leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. With --equal-time MS the lit and nee legs of shirley and room then render on a second
+context with WFPT_FLAG_DENOISE (the luminance moments) for MS milliseconds and report the samples that fitted and the image mean of
+wfpt_read_variance, the variance of the pixels' mean luminance: the variance at equal time."""
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+
+EXTRA_KEYS = ("rays_per_frame", "hits_per_frame", "wavefronts_last_sample", "equal_time_ms", "equal_time_samples", "equal_time_variance")
+DIGITS = None  # (as they came)
 
 
 def make(W, np, a, scene, kind, setting, extra_flags=0):
@@ -69,17 +64,9 @@ def leg(a):
     import wavefront_path_tracer_amd as W
     scene, kind, setting = a.leg.split(":")
     pt = make(W, np, a, scene, kind, setting)
-    pt.render(a.spp)  # warm-up: graph capture, first touch of every buffer
-    pt.render(a.spp)
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
+    ms = ab.timed_frames(pt, a.spp, a.frames)
     totals = [int(x) for x in pt.totals()]
-    frames = a.frames + 2
+    frames = a.frames + 2  # (timed_frames warms up with two)
     out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms, "rays_per_frame": totals[0] / frames, "hits_per_frame": totals[1] / frames,
            "wavefronts_last_sample": int(len(pt.bounce_table()))}
     pt.close()
@@ -88,84 +75,50 @@ def leg(a):
         pt.render(a.spp)
         pt.synchronize()
         pt.reset_progress()
-        n, t0 = 0, time.perf_counter()
-        while (time.perf_counter() - t0) * 1e3 < a.equal_time:
-            pt.render(a.spp)
-            pt.synchronize()
-            n += a.spp
+        n = a.spp * ab.frames_within(pt, a.spp, a.equal_time)
         out.update(equal_time_ms=a.equal_time, equal_time_samples=n, equal_time_variance=float(np.mean(pt.variance(), dtype=np.float64)))
         pt.close()
     print(json.dumps(out), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
+def options():
+    ap = ab.parser(frames=12)
     ap.add_argument("--room-bounces", type=int, default=50)
-    ap.add_argument("--frames", type=int, default=12)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--triangles", type=int, default=1000000)
     ap.add_argument("--equal-time", type=float, default=0.0, help="milliseconds of rendering for the variance at equal time (0: skip)")
     ap.add_argument("--scenes", nargs="+", default=["shirley", "room", "mesh"])
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    return ap
+
+
+def legs(a):
+    out = []
+    if "shirley" in a.scenes:
+        out += [ab.entry("shirley:plain:off")]
+        if a.parent_tree:  # (no variance at equal time in the parent's tree)
+            out.append(ab.entry("shirley:plain:off@parent", tree=a.parent_tree, equal_time=0.0))
+        out += [ab.entry(f"shirley:{kind}:{setting}") for kind in ("lit", "nee") for setting in ("off", "dead", "rr")]
+    for scene in ("room", "mesh"):
+        if scene in a.scenes:
+            out += [ab.entry(f"{scene}:lit:{setting}") for setting in ("off", "dead", "rr")]
+    return out
+
+
+def main():
+    a = options().parse_args()
     if a.leg:
         return leg(a)
-    legs = []
-    if "shirley" in a.scenes:
-        legs += [("shirley:plain:off", ROOT)]
-        if a.parent_tree:
-            legs.append(("shirley:plain:off@parent", os.path.abspath(a.parent_tree)))
-        legs += [(f"shirley:{kind}:{setting}", ROOT) for kind in ("lit", "nee") for setting in ("off", "dead", "rr")]
-    if "room" in a.scenes:
-        legs += [(f"room:lit:{setting}", ROOT) for setting in ("off", "dead", "rr")]
-    if "mesh" in a.scenes:
-        legs += [(f"mesh:lit:{setting}", ROOT) for setting in ("off", "dead", "rr")]
-    results = {name: {"rounds": [], "last": None} for name, _ in legs}
-    for _ in range(a.rounds):
-        for name, tree in legs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
-                   str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--room-bounces", str(a.room_bounces), "--frames",
-                   str(a.frames), "--triangles", str(a.triangles), "--equal-time", str(0.0 if "@" in name else a.equal_time)]
-            env = dict(os.environ)
-            env.pop("WFPT_LIB", None)  # each tree loads its own library
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
-            if res.returncode != 0:
-                sys.exit(f"bench_retire: leg {name} failed with status {res.returncode}")
-            r = json.loads(res.stdout.strip().splitlines()[-1])
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name, _ in legs:
-        rounds = results[name]["rounds"]
-        med = statistics.median(x for r in rounds for x in r)
-        per_round = [statistics.median(r) for r in rounds]
-        last = results[name]["last"]
-        line = {"leg": name, "loop": last["loop"], "size": [a.width, a.height], "spp": a.spp,
-                "bounces": a.room_bounces if name.startswith("room") else a.bounces, "frames": a.frames, "rounds": a.rounds,
-                "frame_ms_median": round(med, 3), "round_medians_ms": [round(x, 3) for x in per_round],
-                "spread_ms": round(max(per_round) - min(per_round), 3)}
-        for k in ("rays_per_frame", "hits_per_frame", "wavefronts_last_sample", "equal_time_ms", "equal_time_samples", "equal_time_variance"):
-            if k in last:
-                line[k] = last[k]
-        summary[name] = line
-        print(json.dumps(line), flush=True)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS,
+                           bounces_of=lambda name: a.room_bounces if name.startswith("room") else a.bounces)
     rel = {}
     for name in summary:
         scene, kind, setting = name.split("@")[0].split(":")
         base = f"{scene}:{kind}:off"
         if "@" in name:
-            rel[f"{base} over {name}"] = round(summary[base]["frame_ms_median"] / summary[name]["frame_ms_median"] - 1.0, 4)
+            rel.update(ab.ratios(summary, [(base, name)]))
         elif setting != "off":
-            rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
+            rel.update(ab.ratios(summary, [(name, base)]))
             if "equal_time_variance" in summary[name] and summary[base].get("equal_time_variance"):
-                rel[f"{name} over {base}, variance at equal time"] = round(summary[name]["equal_time_variance"] / summary[base]["equal_time_variance"] - 1.0, 4)
+                rel.update(ab.ratios(summary, [(name, base)], ", variance at equal time", "equal_time_variance"))
     print(json.dumps({"summary": rel}), flush=True)
 
 

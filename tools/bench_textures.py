@@ -7,20 +7,14 @@ Legs, --spp samples per frame: `<scene>:plain` no flag, `<scene>:textured` the f
 and, with --parent-tree DIR (a checkout of the parent commit with its library built), every leg once more in that tree, named
 `<leg>@parent` and run right after its twin.
 
-Method (tools/bench_nee.py's): every leg runs in a fresh child process, --rounds times, the legs alternating within a round so that
-drift hits them alike. A child warms up (graph capture, first touch of the textures), then times --frames frames one by one, each ending
-in a device synchronise. A leg's figure is the median of all its frames; its spread is the range of its per-round medians. The texture
-launches' own time and their share of a timed frame come from wfpt_texture_timing_ms against the stage times. Prints one JSON line per
-leg and one summary line."""
-import argparse
+Method: tools/ab_bench.py's. The texture launches' own time and their share of a timed frame come from
+wfpt_texture_timing_ms against the stage times."""
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import ab_bench as ab
+
+EXTRA_KEYS, DIGITS = ("texture_ms_timed", "texture_launches_timed", "texture_launch_share_timed"), 4
 
 
 def leg(a):
@@ -53,15 +47,7 @@ def leg(a):
         pt.set_triangle_uvs(uv)
         pt.set_texture(0, rng.random((2048, 2048, 3), dtype=np.float32))
         pt.bind_texture(0, 0)
-    pt.render(a.spp)  # warm-up: graph capture, first touch of the textures
-    pt.synchronize()
-    ms = []
-    for _ in range(a.frames):
-        t0 = time.perf_counter()
-        pt.render(a.spp)
-        pt.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ms}
+    out = {"leg": a.leg, "loop": pt.loop_kind, "frame_ms": ab.timed_frames(pt, a.spp, a.frames)}
     if kind == "textured":
         stage_ms, _ = pt.render_timed(a.spp)
         tex_ms, launches = pt.texture_timing()
@@ -71,56 +57,23 @@ def leg(a):
     pt.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--width", type=int, default=1920)
-    ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--spp", type=int, default=64)
-    ap.add_argument("--bounces", type=int, default=8)
-    ap.add_argument("--frames", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--triangles", type=int, default=1000000)
+def options():
+    ap = ab.parser(frames=5)
     ap.add_argument("--scenes", nargs="+", default=["shirley", "mesh"])
     ap.add_argument("--parent-tree", default=None, help="a checkout of the parent commit with its libwfpt.so built")
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
-    a = ap.parse_args()
+    return ap
+
+
+def legs(a):
+    return ab.with_twins([ab.entry(f"{scene}:{kind}") for scene in a.scenes for kind in ("plain", "textured")], a.parent_tree)
+
+
+def main():
+    a = options().parse_args()
     if a.leg:
         return leg(a)
-    legs = [(f"{scene}:{kind}", ROOT) for scene in a.scenes for kind in ("plain", "textured")]
-    if a.parent_tree:
-        legs = [x for name, tree in legs for x in ((name, tree), (name + "@parent", os.path.abspath(a.parent_tree)))]
-    results = {name: {"rounds": [], "last": None} for name, _ in legs}
-    for _ in range(a.rounds):
-        for name, tree in legs:
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", name.split("@")[0], "--tree", tree, "--width", str(a.width), "--height",
-                   str(a.height), "--spp", str(a.spp), "--bounces", str(a.bounces), "--frames", str(a.frames), "--triangles", str(a.triangles)]
-            env = dict(os.environ)
-            env.pop("WFPT_LIB", None)  # each tree loads its own library
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env, timeout=600)  # a failed or hung leg ends the run
-            if res.returncode != 0:
-                sys.exit(f"bench_textures: leg {name} failed with status {res.returncode}")
-            r = json.loads(res.stdout.strip().splitlines()[-1])
-            results[name]["rounds"].append(r["frame_ms"])
-            results[name]["last"] = r
-            print(f"{name}: {statistics.median(r['frame_ms']):.3f} ms", file=sys.stderr, flush=True)  # progress; the figures follow
-    summary = {}
-    for name, _ in legs:
-        rounds = results[name]["rounds"]
-        per_round = [statistics.median(r) for r in rounds]
-        line = {"leg": name, "loop": results[name]["last"]["loop"], "size": [a.width, a.height], "spp": a.spp, "bounces": a.bounces,
-                "frames": a.frames, "rounds": a.rounds, "frame_ms_median": round(statistics.median(x for r in rounds for x in r), 3),
-                "round_medians_ms": [round(x, 3) for x in per_round], "spread_ms": round(max(per_round) - min(per_round), 3)}
-        for k in ("texture_ms_timed", "texture_launches_timed", "texture_launch_share_timed"):
-            if k in results[name]["last"]:
-                line[k] = round(results[name]["last"][k], 4) if isinstance(results[name]["last"][k], float) else results[name]["last"][k]
-        summary[name] = line
-        print(json.dumps(line), flush=True)
-    rel = {}
-    twins = [(name, name + "@parent") for name, _ in legs if not name.endswith("@parent")]
-    for name, base in [(f"{scene}:textured", f"{scene}:plain") for scene in a.scenes] + twins:
-        if name in summary and base in summary:
-            rel[f"{name} over {base}"] = round(summary[name]["frame_ms_median"] / summary[base]["frame_ms_median"] - 1.0, 4)
+    summary = ab.summarise(ab.run_legs(__file__, legs(a), a), a, EXTRA_KEYS, DIGITS)
+    rel = ab.ratios(summary, [(f"{scene}:textured", f"{scene}:plain") for scene in a.scenes] + ab.twin_pairs(summary))
     print(json.dumps({"summary": rel}), flush=True)
 
 
