@@ -3,13 +3,15 @@
  *
  *   gcc -std=c99 -O1 -Iinclude examples/wfpt_render.c -Lwavefront_path_tracer_amd -lwfpt \
  *       -Wl,-rpath,$PWD/wavefront_path_tracer_amd -lm -o wfpt_render
- *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha]] [--adaptive]
+ *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]] [--adaptive]
  * --adaptive: a WFPT_FLAG_ADAPTIVE context rendered with wfpt_render_adaptive (at most spp passes, an update every 8) at the default
  * parameters; the image written is the mean (each pixel divided by its own sample count).
  * --obj-normals mesh.obj: instead of the book's scene, the triangles of a Wavefront OBJ file (grey Lambertian, about the origin, seen from
  * (0, 1, 4.5)) shaded with the file's `vn` vertex normals: a WFPT_FLAG_SHADING_NORMALS context and wfpt_set_triangle_normals.
  * --roughness alpha (after --obj-normals mesh.obj): the mesh is a metal of that albedo with the GGX roughness alpha in (0, 1] instead:
  * WFPT_FLAG_MICROFACET as well, and wfpt_set_roughness.
+ * --rough-glass alpha (after --obj-normals mesh.obj): the mesh is a white dielectric of refraction index 1.5 with the GGX roughness alpha
+ * in (0, 1] -- frosted glass: WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC, and wfpt_set_roughness on the dielectric material.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,7 +37,9 @@ int main(int argc, char **argv) {
         argc -= 1;
     }
     float roughness = 0.0f;
-    if (argc > 5 && strcmp(argv[argc - 2], "--roughness") == 0) {
+    int glass = 0;
+    if (argc > 5 && (strcmp(argv[argc - 2], "--roughness") == 0 || strcmp(argv[argc - 2], "--rough-glass") == 0)) {
+        glass = strcmp(argv[argc - 2], "--rough-glass") == 0;
         roughness = (float)atof(argv[argc - 1]);
         argc -= 2;
     }
@@ -43,8 +47,8 @@ int main(int argc, char **argv) {
         obj = argv[argc - 1];
         argc -= 2;
     }
-    if (argc < 2 || (roughness != 0.0f && !obj)) {
-        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha]] [--adaptive]\n", argv[0]);
+    if (argc < 2 || (roughness != 0.0f && !obj) || (glass && !(roughness > 0.0f))) {
+        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]] [--adaptive]\n", argv[0]);
         return 2;
     }
     const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[2]) : 400, height = argc > 3 ? (uint32_t)atoi(argv[3]) : 225;
@@ -64,7 +68,12 @@ int main(int argc, char **argv) {
         memset(&grey, 0, sizeof grey);
         grey.albedo[0] = grey.albedo[1] = grey.albedo[2] = 0.7f;
         grey.albedo[3] = 1.0f;
-        CHECK(wfpt_load_obj_normals(obj, tris, NULL, n9, n_tris, &n_tris, 0, roughness > 0.0f ? 1u : 0u)); /* triangle i: _pad = i, row i of n9; --roughness: Metal */
+        if (glass) { /* include/wfpt.h "Rough dielectrics" */
+            grey.albedo[0] = grey.albedo[1] = grey.albedo[2] = 1.0f;
+            grey.refract_index = 1.5f;
+            grey.material_type = 2u;
+        }
+        CHECK(wfpt_load_obj_normals(obj, tris, NULL, n9, n_tris, &n_tris, 0, glass ? 2u : roughness > 0.0f ? 1u : 0u)); /* triangle i: _pad = i, row i of n9; --roughness: Metal, --rough-glass: Dielectric */
         CHECK(wfpt_build_bvh_triangles(tris, n_tris, mesh_nodes, 2u * n_tris, &n_mesh_nodes, 32)); /* reorders: the rows follow by _pad */
         const float from[3] = {0.0f, 1.0f, 4.5f}, at[3] = {0.0f, 0.0f, 0.0f};
         float pitch, yaw, view[16], inv_proj[16];
@@ -79,14 +88,14 @@ int main(int argc, char **argv) {
         params.height = height;
         params.max_wavefronts = bounces;
         params.miss_floor = 128;
-        params.flags = WFPT_FLAG_SHADING_NORMALS | (roughness > 0.0f ? WFPT_FLAG_MICROFACET : 0u) | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u);
+        params.flags = WFPT_FLAG_SHADING_NORMALS | (roughness > 0.0f ? WFPT_FLAG_MICROFACET : 0u) | (glass ? WFPT_FLAG_ROUGH_DIELECTRIC : 0u) | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u);
         ctx = wfpt_create_mesh(&params, tris, n_tris, &grey, 1, mesh_nodes, n_mesh_nodes, &camera, inv_proj, view);
         if (!ctx) {
             fprintf(stderr, "wfpt_create_mesh: %s\n", wfpt_last_error(NULL));
             return 1;
         }
         CHECK(wfpt_set_triangle_normals(ctx, n9, n_tris));
-        if (roughness > 0.0f) CHECK(wfpt_set_roughness(ctx, 0, roughness)); /* include/wfpt.h "Microfacet metals" */
+        if (roughness > 0.0f) CHECK(wfpt_set_roughness(ctx, 0, roughness)); /* include/wfpt.h "Microfacet metals", "Rough dielectrics" */
         uint32_t still = 0;
         if (adaptive) CHECK(wfpt_render_adaptive(ctx, spp, 8, &still));
         else CHECK(wfpt_render(ctx, spp));

@@ -274,7 +274,11 @@ enum {
     WFPT_FLAG_MICROFACET = 1u << 25  /* GGX microfacet metals on triangle meshes, see "Microfacet metals" below: every material can carry a
                                         roughness alpha, and a metal hit of a material whose alpha is above 0 reflects about a sampled
                                         microfacet normal with the weight F * G1. Goes with every flag. With no roughness above 0 the
-                                        context renders bit for bit as without the flag, and launches the same kernels. */
+                                        context renders bit for bit as without the flag, and launches the same kernels. */,
+    WFPT_FLAG_ROUGH_DIELECTRIC = 1u << 26 /* GGX rough dielectrics on triangle meshes, see "Rough dielectrics" below: a dielectric hit of a
+                                        material whose roughness alpha is above 0 reflects or refracts about a sampled microfacet normal.
+                                        Needs WFPT_FLAG_MICROFACET and goes with everything that flag goes with. With no roughness above 0
+                                        on a dielectric the context launches the kernels it launches without the flag, same bits. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -822,8 +826,9 @@ int wfpt_shading_normal_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *laun
  * not a number in [0, 1]; WFPT_ERR_UNSUPPORTED for a call that would put a roughness above 0 on a WFPT_LOOP_FUSED_BINNED context (a
  * context with one never runs the class-binned loop). The flag composes with every other one, WFPT_FLAG_SHADING_NORMALS,
  * WFPT_FLAG_LIGHT_POWER and WFPT_FLAG_ANALYTIC_LIGHTS included.
+ * Rough dielectrics are a flag of their own, WFPT_FLAG_ROUGH_DIELECTRIC: see "Rough dielectrics" below.
  * Out of scope: sphere contexts (the shade step and the traversal share one prim_kind, and a sphere's record holds a centre, not a
- * normal); rough dielectrics; roughness, normal and bump maps; anisotropy; multiple-scattering energy compensation (single-scatter GGX
+ * normal); roughness, normal and bump maps; anisotropy; multiple-scattering energy compensation (single-scatter GGX
  * loses energy at high alpha by construction); next-event estimation or MIS at rough hits (unbiased without, and noisier); scatter
  * directions below a shading normal's geometric surface; the stage API (wfpt_kernel_run ignores roughness); wfpt_render_chunked* (the
  * flag is masked off). */
@@ -838,6 +843,58 @@ int wfpt_clear_roughness(wfpt_ctx *ctx);
 int wfpt_sample_microfacet(wfpt_ctx *ctx, const float *in12, size_t n, float *out8);
 /* the microfacet launches of every timed render since wfpt_create (not a wfpt_stage: WFPT_STAGE_COUNT stays as it is) */
 int wfpt_microfacet_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
+
+/* ------------------------------------------------------------------ Rough dielectrics (WFPT_FLAG_ROUGH_DIELECTRIC): GGX rough glass on meshes
+ * On a triangle context created with WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC a hit is ROUGH GLASS when its primitive's
+ * material_type is 2 (Dielectric) and its material's alpha (wfpt_set_roughness above: the same table, the same setters) is above 0. It is
+ * then shaded as the single-scatter GGX dielectric of Walter et al. 2007 with Schlick's Fresnel term, in place of Shirley's smooth glass.
+ * Metal hits behave exactly as under "Microfacet metals". Without this flag an alpha on a dielectric stays stored and inert.
+ * The pass, per rough glass hit of wavefront b, in the arithmetic of "Microfacet metals" (IEEE f32 add, sub, mul, div, sqrt in the order
+ * written, no fma, max and min as maxNum and minNum, dot and normalize3 as there); tests/rough_dielectric_ref.py restates it. Inputs: d,
+ * the ray's direction as stored (not normalised); n, the shading normal where a table of corner normals is set, else the stored normal;
+ * ior and albedo, the material's refraction index and albedo rgb:
+ *   0. the draws: the metals' construction with the multiplier 0x27D4EB2F (odd; the metals' is 0xC2B2AE35, the termination step's
+ *      0x85EBCA6B, the connect pass's 0x9E3779B9): s = jenkins_hash((x + y W) ^ jenkins_hash(frame)),
+ *      s <- jenkins_hash(s ^ (0x27D4EB2Fu * (b + 1))), u1 = rng_next_float(s), u2 = rng_next_float(s), u3 = rng_next_float(s)
+ *   1. uv = normalize3(d); wi = -uv (each component negated); cn = dot(n, wi); nf = n; eta = 1 / ior (outside). If cn < 0 (inside):
+ *      nf = -n, cn = -cn, eta = ior -- dielectrics are not two-sided: the stored orientation decides, as in scatter(). If !(cn > 0) (zero
+ *      or NaN) the hit FALLS BACK: it is shaded as without roughness
+ *   2-9. the microfacet normal m: steps 2-9 of "Microfacet metals" about nf with wi, cn, alpha, u1, u2 (one device function for both)
+ *  10. cm = dot(wi, m). If !(cm > 0) the path is DEAD: weight (+0, +0, +0), h = m. Otherwise F = schlick(min(cm, 1), eta), scatter()'s
+ *      own: r0 = (1 - eta) / (1 + eta); r0 <- r0 r0; F = r0 + (1 - r0) pow(1 - min(cm, 1), 5), pow the library's; ct = -cm;
+ *      k = 1 - (eta eta) (1 - ct ct)
+ *  11. if !(k >= 0) (total internal reflection about m) or F > u3, REFLECT: w = (2 cm) m - wi per component; co = dot(nf, w); h = m.
+ *      Otherwise REFRACT: mm = (1 - eta eta) / (sqrt(k) + eta cm) -- refract()'s eta ct + sqrt(k), multiplied out so that nothing
+ *      cancels --; w = eta uv - mm m per component; co = -dot(nf, w); hv = (eta - 1) uv - mm m per component (w - uv, again without
+ *      the cancellation: with w - uv as written a refraction index of 1 leaves rounding noise for h, and one near 1 little more);
+ *      l2 = dot(hv, hv); if !(l2 > 0) (ior 1: mm and hv are exactly 0, the ray goes straight on) the hit falls back as in step 1; else
+ *      h = hv (1 / sqrt(l2)).
+ *      In both arms, if !(co > 0) -- the direction left on the wrong side of the macro surface -- the path is dead: weight +0, h as
+ *      computed. A dead path keeps travelling, as the dead paths of "Emission" do; WFPT_FLAG_RETIRE retires it
+ *  12. otherwise a2 = alpha alpha; G = (2 co) / (co + sqrt(a2 + (1 - a2) (co co))); weight = albedo G per channel
+ *  13. the hit's shade record becomes (h | fuzz +0), (weight | ior), (material type 1 | the rest of the third row unchanged): for unit uv
+ *      and w != uv, reflect(uv, normalize(w - uv)) = w, so the unchanged metal branch of scatter() emits reflect(d, h) + 0 rb = |d| w --
+ *      the reflection or the refraction -- and shade multiplies the throughput by the weight.
+ * The weight is the BSDF times the cosine over the density of (visible normal x Fresnel choice): D, G1(wi), F or 1 - F and the
+ * half-vector Jacobians cancel in both arms, and G1(w) is left. As with the smooth glass there is no eta^2 radiance scaling. With
+ * alpha -> 0 the pass tends to scatter()'s smooth dielectric.
+ * Device side: on a context that holds a roughness above 0 on a dielectric primitive's material, rough_glass_kernel takes
+ * microfacet_kernel's place (same slot before every shade step that scatters, same table, same accounting: wfpt_microfacet_timing_ms
+ * covers both); it samples metal hits bit for bit as microfacet_kernel does. With the flag but no such alpha the context launches
+ * exactly the kernels it launches without the flag and renders the same bits. Everything that classifies a hit before the pass reads the
+ * primitive's own type 2: the connect pass ("specular"), the emission pass, the AOV albedo and ids, split-shade's material lists and
+ * the cost class; only the shade step's scatter() reads the rewritten type word.
+ * Carried over from "Microfacet metals": triangle contexts only; no pass before the last wavefront's step; never on a
+ * WFPT_LOOP_FUSED_BINNED context (WFPT_ERR_UNSUPPORTED for the call that would put an alpha above 0 there); masked off in
+ * wfpt_render_chunked*; ignored by the stage API; the setters restart the accumulation and drop history and graphs;
+ * wfpt_update_scene_mesh keeps the alphas; wfpt_update_scene to spheres is refused while an alpha is above 0.
+ * Out of scope: sphere contexts; roughness, normal and bump maps; anisotropy; multiple-scattering energy compensation; next-event
+ * estimation or MIS at rough hits; radiance scaling by eta^2; absorption inside the medium; thin-walled glass; directions below a
+ * shading normal's geometric surface. */
+/* steps 1-12 on the device for n caller rows in16 of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0): rows out8 of
+ * (h.xyz | 2.0 where the hit fell back, 1.0 where the path is dead, else 0.0), (weight.rgb | 1.0 refracted, 0.0 reflected); a row that
+ * fell back answers (+0, +0, +0, 2, +0, +0, +0, +0). Needs the flag and nothing else of the context. Blocking. */
+int wfpt_sample_rough_dielectric(wfpt_ctx *ctx, const float *in16, size_t n, float *out8);
 
 /* ------------------------------------------------------------------ Emission (WFPT_FLAG_EMISSION): materials that light the scene
  * A context created with WFPT_FLAG_EMISSION holds one emission colour per material, all zero at creation. A material with a non-zero colour

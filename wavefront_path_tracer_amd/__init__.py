@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "FLAG_ROUGH_DIELECTRIC", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -63,6 +63,8 @@ FLAG_ANALYTIC_LIGHTS = 1 << 23
 FLAG_SHADING_NORMALS = 1 << 24
 # GGX microfacet metals on triangle meshes: a roughness per material (include/wfpt.h "Microfacet metals"); goes with every flag
 FLAG_MICROFACET = 1 << 25
+# GGX rough dielectrics on triangle meshes: the same roughness on a dielectric (include/wfpt.h "Rough dielectrics"); needs FLAG_MICROFACET
+FLAG_ROUGH_DIELECTRIC = 1 << 26
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2  # wfpt_light_type
 MAX_LIGHTS = 1024  # WFPT_MAX_LIGHTS
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
@@ -391,6 +393,7 @@ def lib():
         "wfpt_clear_roughness": (i32, [vp]),
         "wfpt_sample_microfacet": (i32, [vp, vp, sz, vp]),
         "wfpt_microfacet_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
+        "wfpt_sample_rough_dielectric": (i32, [vp, vp, sz, vp]),
         "wfpt_set_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_clear_emission": (i32, [vp]),
@@ -1543,6 +1546,12 @@ class PathTracer:
         alpha, F0.rgb); returns (n, 8) float32 of (m.xyz, 2.0 where the hit fell back to its plain shading / 1.0 where the weight is zero /
         else 0.0, weight.rgb, cm)."""
         return self._probe(lib().wfpt_sample_microfacet, "sample_microfacet", rows, 12, 8)
+
+    def sample_rough_dielectric(self, rows):
+        """The rough-dielectric sampler of a FLAG_ROUGH_DIELECTRIC context for caller-supplied hits, computed on the device. rows: (n, 16)
+        float32 of (d.xyz, n.xyz, u1, u2, u3, alpha, ior, albedo.rgb, 0, 0); returns (n, 8) float32 of (h.xyz, 2.0 where the hit fell back
+        to its plain shading / 1.0 where the weight is zero / else 0.0, weight.rgb, 1.0 refracted / 0.0 reflected)."""
+        return self._probe(lib().wfpt_sample_rough_dielectric, "sample_rough_dielectric", rows, 16, 8)
 
     def microfacet_timing_ms(self):
         """(milliseconds, launches) of the microfacet launches of every timed render since creation (apart from render_timed's stage times)."""

@@ -279,8 +279,11 @@ struct wfpt_ctx {
     // WFPT_FLAG_MICROFACET (include/wfpt.h "Microfacet metals"): the roughness per material (empty or all zero = no rough material) and what
     // build_roughness_table makes of it for the kernel -- per primitive its material's alpha where the primitive is metal, +0 otherwise
     // (null while no alpha is above 0: nothing new is launched then)
+    // WFPT_FLAG_ROUGH_DIELECTRIC (include/wfpt.h "Rough dielectrics"): the table holds the alpha of dielectric primitives as well, and
+    // mf_glass says that one of them is above 0 -- the pass is then rough_glass_kernel, else microfacet_kernel as without the flag
     std::vector<float> mf_alpha;
     DeviceBuffer<float> mf_prim;
+    bool mf_glass = false;
     // The per-hit shade records of the shading-normal and microfacet passes, 3 x float4 per ray-queue slot per sample in flight: one table
     // for both features, allocated with the first of {table of normals, roughness above 0} and released with the last
     // (reserve_hit_table, commit_hit_table)
@@ -911,7 +914,10 @@ int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const 
     if (emitting(c)) WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
     if (connecting(c)) WFPT_HIP(c, timed(pass_stage(kPassConnect), [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
     if (shade_rec_out && rough(c))
-        WFPT_HIP(c, timed(pass_stage(kPassMicrofacet), [&] { return launch_microfacet(microfacet_args(c, b, w, shade_rec_out), grid, c->stream.get()); }));
+        WFPT_HIP(c, timed(pass_stage(kPassMicrofacet), [&] {
+            const MicrofacetArgs a = microfacet_args(c, b, w, shade_rec_out);
+            return c->mf_glass ? launch_rough_glass(a, grid, c->stream.get()) : launch_microfacet(a, grid, c->stream.get());
+        }));
     else if (shade_rec_out)
         WFPT_HIP(c, timed(pass_stage(kPassShading), [&] { return launch_shading_normal(shading_args(c, w, shade_rec_out), grid, c->stream.get()); }));
     return WFPT_OK;
@@ -1710,6 +1716,9 @@ const FlagRule kFlagRules[] = {
     // WFPT_FLAG_MICROFACET needs nothing and goes with every flag: metal hits never connect, so the connect kernels need no twin for it,
     // and its pass writes the per-hit records whichever connect kernel ran before it
     {WFPT_FLAG_MICROFACET, 0, 0, nullptr, nullptr},
+    // WFPT_FLAG_ROUGH_DIELECTRIC shares its tables, setters and pass slot; dielectric hits never connect either
+    {WFPT_FLAG_ROUGH_DIELECTRIC, WFPT_FLAG_MICROFACET, 0,
+     "wfpt_create: WFPT_FLAG_ROUGH_DIELECTRIC needs WFPT_FLAG_MICROFACET (the roughness per material and the pass it extends are that flag's)", nullptr},
     // (WFPT_FLAG_ENV_MIS goes with no WFPT_FLAG_MIS either, since it weighs the emitters itself: the WFPT_FLAG_ENV_NEE it needs has
     // refused that at WFPT_FLAG_MIS's row)
     {WFPT_FLAG_ENV_MIS, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect | WFPT_FLAG_ENV_NEE, 0,
@@ -1983,7 +1992,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -2084,7 +2093,7 @@ static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, con
 static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t);
 static int build_normal_rows(wfpt_ctx *c, const std::vector<float> &n9, const std::vector<uint32_t> &row, DeviceBuffer<float4> &out);
 static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
-                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out);
+                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out, bool &glass);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
     if (!c || !(spheres || triangles) || !materials || n_prims == 0 || n_materials == 0)
@@ -2126,12 +2135,13 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         if (int r = build_normal_rows(c, c->h_normals, row, sn_rows); r != WFPT_OK) return r;
     DeviceBuffer<float> mf_prim; // likewise the roughness table; the alphas of materials the new scene no longer has are dropped
     std::vector<float> mf_alpha;
+    bool mf_glass = false;
     if (rough(c)) {
         mf_alpha = c->mf_alpha;
         mf_alpha.resize(n_materials, 0.0f);
         std::vector<uint32_t> mat_type(n_prims);
         for (uint32_t i = 0; i < n_prims; ++i) mat_type[i] = triangles[i].material_type;
-        if (int r = build_roughness_table(c, mf_alpha, mat_idx, mat_type, mf_prim); r != WFPT_OK) return r;
+        if (int r = build_roughness_table(c, mf_alpha, mat_idx, mat_type, mf_prim, mf_glass); r != WFPT_OK) return r;
     }
     EmissionTables em_tables; // likewise; the colours of materials the new scene no longer has are dropped
     std::vector<float> em_rgb;
@@ -2160,6 +2170,7 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     if (rough(c)) { // (the dropped alphas may have been the last above 0: the per-hit records then go with them)
         c->mf_alpha = std::move(mf_alpha);
         c->mf_prim = std::move(mf_prim);
+        c->mf_glass = mf_glass;
         commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
     }
     if (c->p.flags & WFPT_FLAG_EMISSION) {
@@ -3506,18 +3517,25 @@ int wfpt_shading_normal_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launch
 }
 
 // ---------------------------------------------------------------- microfacet metals (include/wfpt.h "Microfacet metals")
-// The kernel's view of the roughnesses and the scene: per primitive its material's alpha where the primitive's material_type is 1 (Metal),
-// +0 otherwise, in the order the device holds the primitives; null while no alpha is above 0. Built for a CANDIDATE state -- alphas (one
+// The kernel's view of the roughnesses and the scene: per primitive its material's alpha where the primitive's material_type is 1 (Metal)
+// or, on a WFPT_FLAG_ROUGH_DIELECTRIC context, 2 (Dielectric), +0 otherwise, in the order the device holds the primitives; null while no
+// alpha is above 0. glass: a dielectric primitive's entry is above 0 (the pass is then rough_glass_kernel). Built for a CANDIDATE state -- alphas (one
 // per material, missing ones 0), and per primitive its material_idx and material_type -- without touching the context, like
 // build_emission_tables.
 static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
-                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out) {
+                                 const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out, bool &glass) {
+    glass = false;
     bool any = false;
     for (float a : alpha) any = any || a > 0.0f;
     if (!any) return WFPT_OK;
+    const bool dielectrics = (c->p.flags & WFPT_FLAG_ROUGH_DIELECTRIC) != 0;
     const size_t n = mat_idx.size();
     std::vector<float> t(n);
-    for (size_t i = 0; i < n; ++i) t[i] = mat_type[i] == 1u && mat_idx[i] < alpha.size() ? alpha[mat_idx[i]] : 0.0f;
+    for (size_t i = 0; i < n; ++i) {
+        const bool counts = mat_type[i] == 1u || (dielectrics && mat_type[i] == 2u);
+        t[i] = counts && mat_idx[i] < alpha.size() ? alpha[mat_idx[i]] : 0.0f;
+        glass = glass || (mat_type[i] == 2u && t[i] > 0.0f);
+    }
     WFPT_HIP(c, out.alloc(n));
     WFPT_HIP(c, hipMemcpy(out.get(), t.data(), sizeof(float) * n, hipMemcpyHostToDevice));
     return WFPT_OK;
@@ -3535,12 +3553,14 @@ static int apply_roughness(wfpt_ctx *c, const char *who, std::vector<float> &&al
     WFPT_HIP(c, hipSetDevice(c->device));
     DeviceBuffer<float> prim;
     DeviceBuffer<float4> table;
-    if (int r = build_roughness_table(c, alpha, c->h_prim_mat_idx, c->h_prim_mat_type, prim); r != WFPT_OK) return r;
+    bool glass = false;
+    if (int r = build_roughness_table(c, alpha, c->h_prim_mat_idx, c->h_prim_mat_type, prim, glass); r != WFPT_OK) return r;
     if (prim.get())
         if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
     commit_hit_table(c, std::move(table), prim.get() != nullptr || shading(c));
     c->mf_prim = std::move(prim); // (the kernel takes it from the context at each launch; the graphs that hold the old one are dropped)
+    c->mf_glass = glass;
     c->mf_alpha = std::move(alpha);
     return scene_changed(c);
 }
@@ -3573,6 +3593,14 @@ int wfpt_sample_microfacet(wfpt_ctx *c, const float *in12, size_t n, float *out8
     if (int r = microfacet_check(c, "wfpt_sample_microfacet"); r != WFPT_OK) return r;
     return probe(c, "wfpt_sample_microfacet", in12, 12, out8, 8, n, true, [&](const float *d_in, float *d_out) {
         return launch_microfacet_sample(d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
+}
+
+int wfpt_sample_rough_dielectric(wfpt_ctx *c, const float *in16, size_t n, float *out8) {
+    const char *who = "wfpt_sample_rough_dielectric";
+    if (int r = flag_check(c, who, WFPT_FLAG_ROUGH_DIELECTRIC, "WFPT_FLAG_ROUGH_DIELECTRIC"); r != WFPT_OK) return r;
+    return probe(c, who, in16, 16, out8, 8, n, true, [&](const float *d_in, float *d_out) {
+        return launch_rough_glass_sample(d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
     });
 }
 

@@ -845,6 +845,13 @@ hipError_t launch_microfacet(const MicrofacetArgs &a, uint32_t grid, hipStream_t
 // wfpt_sample_microfacet: n rows of (d.xyz, n.xyz, u1, u2, alpha, F0.rgb) -> (m.xyz | 2 where step 1 fell back, 1 where step 10 left the
 // weight at zero, else 0 | weight.rgb | cm), one thread per row; both buffers 16-byte aligned
 hipError_t launch_microfacet_sample(const float *in12, float *out8, uint32_t n, hipStream_t s);
+// The microfacet pass of a WFPT_FLAG_ROUGH_DIELECTRIC context that holds a roughness above 0 on a dielectric (rough_glass_kernel; include/wfpt.h
+// "Rough dielectrics"), in launch_microfacet's place: a.mf_prim then holds the alpha of metal and dielectric primitives. A metal hit's record
+// is launch_microfacet's; a rough glass hit's is (h | +0), (albedo * G1 | rec1.w), (material type 1 | rec2.yzw).
+hipError_t launch_rough_glass(const MicrofacetArgs &a, uint32_t grid, hipStream_t s);
+// wfpt_sample_rough_dielectric: n rows of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0) -> (h.xyz | 2 fell back, 1 dead, else
+// 0 | weight.rgb | 1 refracted, 0 reflected), one thread per row; both buffers 16-byte aligned
+hipError_t launch_rough_glass_sample(const float *in16, float *out8, uint32_t n, hipStream_t s);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the

@@ -2253,6 +2253,172 @@ __global__ __launch_bounds__(256) void microfacet_sample_kernel(const float *in1
 }
 
 // ================================================================================================
+// rough-dielectric pass (WFPT_FLAG_ROUGH_DIELECTRIC; include/wfpt.h "Rough dielectrics")
+// ================================================================================================
+// Steps 1-12 of the header in its operation order (tests/rough_dielectric_ref.py restates it): the microfacet normal m of the metals'
+// steps 2-9 about the facing normal, Schlick's choice between the reflection and the refraction about m, the outgoing unit direction w
+// and the pseudo-normal h with reflect(uv, h) = w that lets the metal branch of scatter() emit it; weight = albedo * G1(w).
+// fell: steps 1 or 11 fell back (the hit is shaded as without roughness; h and weight are +0 then); dead: the weight is +0.
+// Steps 2-9 of "Microfacet metals": the microfacet normal about the facing normal nf for the unit direction wi back along the ray,
+// cn = dot(nf, wi) > 0. The same operations as microfacet_sample's steps 2-9, stated a second time: calling this from microfacet_sample
+// changes the instructions of microfacet_kernel and microfacet_sample_kernel, which a context without the new flag launches.
+__device__ __forceinline__ float3_ ggx_visible_normal(float3_ nf, float3_ wi, float cn, float alpha, float u1, float u2) {
+    // 2. the basis about nf (Duff et al. 2017)
+    const float sg = nf.z >= 0.0f ? 1.0f : -1.0f;
+    const float a = -1.0f / (sg + nf.z);
+    const float bb = (nf.x * nf.y) * a;
+    const float3_ t = {1.0f + ((sg * nf.x) * nf.x) * a, sg * bb, -(sg * nf.x)};
+    const float3_ bt = {bb, sg + (nf.y * nf.y) * a, -nf.y};
+    // 3-5. wi in the basis, stretched, and the basis about it
+    const float3_ l = {dot3(t, wi), dot3(bt, wi), cn};
+    const float3_ vh = normalize3({alpha * l.x, alpha * l.y, l.z});
+    const float l2 = vh.x * vh.x + vh.y * vh.y;
+    float3_ T1 = {1.0f, 0.0f, 0.0f};
+    if (l2 > 0.0f) {
+        const float il = 1.0f / sqrt_(l2);
+        T1 = {-vh.y * il, vh.x * il, 0.0f};
+    }
+    const float3_ T2 = {vh.y * T1.z - vh.z * T1.y, vh.z * T1.x - vh.x * T1.z, vh.x * T1.y - vh.y * T1.x};
+    // 6-8. a point of the projected disk, warped, lifted onto the hemisphere and unstretched (Heitz 2018)
+    const float r = sqrt_(u1);
+    float sn, cs;
+    sincos_((2.0f * kPi) * u2, sn, cs);
+    const float t1 = r * cs;
+    float t2 = r * sn;
+    const float s = 0.5f * (1.0f + vh.z);
+    t2 = (1.0f - s) * sqrt_(max_(0.0f, 1.0f - t1 * t1)) + s * t2;
+    const float h = sqrt_(max_(0.0f, (1.0f - t1 * t1) - t2 * t2));
+    const float3_ nh = {(t1 * T1.x + t2 * T2.x) + h * vh.x, (t1 * T1.y + t2 * T2.y) + h * vh.y, (t1 * T1.z + t2 * T2.z) + h * vh.z};
+    const float3_ ml = normalize3({alpha * nh.x, alpha * nh.y, max_(0.0f, nh.z)});
+    // 9. back to the world, not renormalised
+    return {(ml.x * t.x + ml.y * bt.x) + ml.z * nf.x, (ml.x * t.y + ml.y * bt.y) + ml.z * nf.y, (ml.x * t.z + ml.y * bt.z) + ml.z * nf.z};
+}
+struct RoughGlassSample {
+    float3_ h, weight;
+    bool fell, dead, refracted;
+};
+__device__ __forceinline__ RoughGlassSample rough_glass_sample(float3_ d, float3_ n, float u1, float u2, float u3, float alpha, float ior,
+                                                               float3_ albedo) {
+    RoughGlassSample o;
+    o.h = o.weight = {0.0f, 0.0f, 0.0f};
+    o.dead = o.refracted = false;
+    const float3_ uv = normalize3(d);
+    const float3_ wi = {-uv.x, -uv.y, -uv.z};
+    float cn = dot3(n, wi);
+    float3_ nf = n;
+    float eta = 1.0f / ior;
+    if (cn < 0.0f) { // inside: the stored orientation decides, as in scatter()
+        nf = {-n.x, -n.y, -n.z};
+        cn = -cn;
+        eta = ior;
+    }
+    o.fell = !(cn > 0.0f); // (zero or NaN)
+    if (o.fell) return o;
+    const float3_ m = ggx_visible_normal(nf, wi, cn, alpha, u1, u2); // 2-9.
+    // 10. Fresnel's term and refract()'s discriminant on the microfacet's cosine
+    const float cm = dot3(wi, m);
+    o.h = m;
+    o.dead = !(cm > 0.0f);
+    if (o.dead) return o;
+    const float F = schlick(min_(cm, 1.0f), eta);
+    const float ct = -cm;
+    const float k = 1.0f - eta * eta * (1.0f - ct * ct);
+    // 11. the choice; total internal reflection about m reflects
+    float co;
+    if (!(k >= 0.0f) || F > u3) {
+        const float k2 = 2.0f * cm;
+        const float3_ w = {k2 * m.x - wi.x, k2 * m.y - wi.y, k2 * m.z - wi.z};
+        co = dot3(nf, w);
+    } else {
+        // (refract()'s eta ct + sqrt(k) without its cancellation, and w - uv without its own: at a refraction index of 1 both are exactly 0)
+        const float mm = (1.0f - eta * eta) / (sqrt_(k) + eta * cm);
+        const float3_ w = {eta * uv.x - mm * m.x, eta * uv.y - mm * m.y, eta * uv.z - mm * m.z};
+        co = -dot3(nf, w);
+        const float e1 = eta - 1.0f;
+        const float3_ hv = {e1 * uv.x - mm * m.x, e1 * uv.y - mm * m.y, e1 * uv.z - mm * m.z};
+        const float l2 = dot3(hv, hv);
+        o.fell = !(l2 > 0.0f); // (refraction index 1: the ray goes straight on, and no normal reflects it there)
+        if (o.fell) {
+            o.h = {0.0f, 0.0f, 0.0f};
+            return o;
+        }
+        const float il = 1.0f / sqrt_(l2);
+        o.h = {hv.x * il, hv.y * il, hv.z * il};
+        o.refracted = true;
+    }
+    o.dead = !(co > 0.0f); // the direction left on the wrong side of the macro surface
+    if (o.dead) return o;
+    // 12. albedo * G1(w): everything else of the estimator cancels against the density of (visible normal x Fresnel choice)
+    const float a2 = alpha * alpha;
+    const float G = (2.0f * co) / (co + sqrt_(a2 + (1.0f - a2) * (co * co)));
+    o.weight = {albedo.x * G, albedo.y * G, albedo.z * G};
+    return o;
+}
+
+// microfacet_kernel's twin for a context that holds a roughness above 0 on a dielectric as well (launch_rough_glass): the same walk, table
+// and slot rewrite; mf_prim holds the alpha of metal AND dielectric primitives there, and the record's own type word tells them apart. A
+// metal hit is sampled as microfacet_kernel samples it. A rough glass hit's record is (h | +0), (weight | rec1.w), (type 1 | rec2.yzw): the
+// metal branch of scatter() then emits reflect(d, h) = |d| w, the reflected or the refracted direction.
+constexpr uint32_t kRoughGlassStream = 0x27D4EB2Fu; // (odd; the metals', the termination step's and the connect pass's are others)
+template <bool NORMALS>
+__global__ __launch_bounds__(kConsumerThreads) void rough_glass_kernel(MicrofacetArgs a) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    const uint32_t frame = uniform(a.w.ctl->frame.frame) + blockIdx.y; // (as microfacet_kernel takes it)
+    for_each_shaded_hit<true>(a.w, s, [&](size_t slot, const Hit &h) {
+        const float alpha = a.mf_prim[h.prim];
+        const float4 rec0 = a.w.shade_rec[3u * h.prim], rec1 = a.w.shade_rec[3u * h.prim + 1u], rec2 = a.w.shade_rec[3u * h.prim + 2u];
+        float3_ n = {rec0.x, rec0.y, rec0.z};
+        if (NORMALS) shading_normal_at(a.prim_geom, a.normals, h.prim, h.p, {rec0.x, rec0.y, rec0.z}, n);
+        float4 o0 = make_float4(n.x, n.y, n.z, rec0.w), o1 = rec1, o2 = rec2;
+        if (alpha > 0.0f) {
+            const bool glass = __float_as_uint(rec2.x) == 2u;
+            uint32_t rng = jenkins_hash(h.pixel_idx ^ jenkins_hash(frame));
+            rng = jenkins_hash(rng ^ ((glass ? kRoughGlassStream : 0xC2B2AE35u) * (a.wavefront + 1u)));
+            const float u1 = rng_next_float(rng);
+            const float u2 = rng_next_float(rng);
+            if (glass) {
+                const float u3 = rng_next_float(rng);
+                const RoughGlassSample gs = rough_glass_sample(h.d, n, u1, u2, u3, alpha, rec1.w, {rec1.x, rec1.y, rec1.z});
+                if (!gs.fell) {
+                    o0 = make_float4(gs.h.x, gs.h.y, gs.h.z, 0.0f);
+                    o1 = make_float4(gs.weight.x, gs.weight.y, gs.weight.z, rec1.w);
+                    o2.x = __uint_as_float(1u);
+                }
+            } else {
+                const MicrofacetSample ms = microfacet_sample(h.d, n, u1, u2, alpha, {rec1.x, rec1.y, rec1.z});
+                if (!ms.fell) {
+                    o0 = make_float4(ms.m.x, ms.m.y, ms.m.z, 0.0f);
+                    o1 = make_float4(ms.weight.x, ms.weight.y, ms.weight.z, rec1.w);
+                }
+            }
+        }
+        float4 *out = a.table + 3u * slot;
+        out[0] = o0;
+        out[1] = o1;
+        out[2] = o2;
+        a.rec_out[2u * slot + 1u].w = __uint_as_float(static_cast<uint32_t>(slot)); // (3 * slot stays below 2^32: wfpt_create's size check)
+    });
+}
+
+// wfpt_sample_rough_dielectric: rough_glass_sample for caller rows of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0), one
+// thread per row
+__global__ __launch_bounds__(256) void rough_glass_sample_kernel(const float *in16, float *out8, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 *row = reinterpret_cast<const float4 *>(in16 + 16u * static_cast<size_t>(i)); // (64-byte rows of a 256-byte-aligned buffer)
+    const float4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3];
+    const RoughGlassSample gs = rough_glass_sample({r0.x, r0.y, r0.z}, {r0.w, r1.x, r1.y}, r1.z, r1.w, r2.x, r2.y, r2.z, {r2.w, r3.x, r3.y});
+    float4 *out = reinterpret_cast<float4 *>(out8 + 8u * static_cast<size_t>(i));
+    if (gs.fell) {
+        out[0] = make_float4(0.0f, 0.0f, 0.0f, 2.0f);
+        out[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    out[0] = make_float4(gs.h.x, gs.h.y, gs.h.z, gs.dead ? 1.0f : 0.0f);
+    out[1] = make_float4(gs.weight.x, gs.weight.y, gs.weight.z, gs.refracted ? 1.0f : 0.0f);
+}
+
+// ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
 // The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
@@ -4920,6 +5086,20 @@ hipError_t launch_microfacet(const MicrofacetArgs &a, uint32_t grid, hipStream_t
 hipError_t launch_microfacet_sample(const float *in12, float *out8, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(microfacet_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, in12, out8, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rough_glass(const MicrofacetArgs &a, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    if (!a.mf_prim || !a.table || !a.rec_out) return hipErrorInvalidValue;
+    if (a.normals) hipLaunchKernelGGL(rough_glass_kernel<true>, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
+    else hipLaunchKernelGGL(rough_glass_kernel<false>, dim3(grid, a.w.batch.n), dim3(kConsumerThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rough_glass_sample(const float *in16, float *out8, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rough_glass_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, in16, out8, n);
     return hipGetLastError();
 }
 

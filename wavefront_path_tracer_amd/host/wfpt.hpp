@@ -377,6 +377,12 @@ class PathTracer {
         return out;
     }
     std::pair<float, uint32_t> microfacet_timing() { return timing(wfpt_microfacet_timing_ms); }
+    // Rough dielectrics (WFPT_FLAG_ROUGH_DIELECTRIC, include/wfpt.h "Rough dielectrics"): set_roughness on a dielectric's material counts too.
+    std::vector<float> sample_rough_dielectric(const std::vector<float> &in16) { // (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0) -> (h.xyz | state | weight.rgb | refracted)
+        std::vector<float> out(in16.size() / 16 * 8);
+        check(wfpt_sample_rough_dielectric(ctx_, in16.data(), in16.size() / 16, out.data()));
+        return out;
+    }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
