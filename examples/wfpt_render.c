@@ -3,7 +3,8 @@
  *
  *   gcc -std=c99 -O1 -Iinclude examples/wfpt_render.c -Lwavefront_path_tracer_amd -lwfpt \
  *       -Wl,-rpath,$PWD/wavefront_path_tracer_amd -lm -o wfpt_render
- *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]] [--adaptive]
+ *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]
+ *                 [--normal-map strength]] [--adaptive]
  * --adaptive: a WFPT_FLAG_ADAPTIVE context rendered with wfpt_render_adaptive (at most spp passes, an update every 8) at the default
  * parameters; the image written is the mean (each pixel divided by its own sample count).
  * --obj-normals mesh.obj: instead of the book's scene, the triangles of a Wavefront OBJ file (grey Lambertian, about the origin, seen from
@@ -12,7 +13,11 @@
  * WFPT_FLAG_MICROFACET as well, and wfpt_set_roughness.
  * --rough-glass alpha (after --obj-normals mesh.obj): the mesh is a white dielectric of refraction index 1.5 with the GGX roughness alpha
  * in (0, 1] -- frosted glass: WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC, and wfpt_set_roughness on the dielectric material.
+ * --normal-map strength (after --obj-normals mesh.obj and its roughness option): the mesh's material takes a procedural 64 x 64 map of
+ * ripples as its tangent-space normal map at that strength (> 0), through the file's `vt` UVs: WFPT_FLAG_TEXTURES |
+ * WFPT_FLAG_NORMAL_MAPS as well, wfpt_set_triangle_uvs, wfpt_set_texture and wfpt_bind_normal_map.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,8 +41,12 @@ int main(int argc, char **argv) {
         adaptive = 1;
         argc -= 1;
     }
-    float roughness = 0.0f;
+    float roughness = 0.0f, map_strength = 0.0f;
     int glass = 0;
+    if (argc > 5 && strcmp(argv[argc - 2], "--normal-map") == 0) {
+        map_strength = (float)atof(argv[argc - 1]);
+        argc -= 2;
+    }
     if (argc > 5 && (strcmp(argv[argc - 2], "--roughness") == 0 || strcmp(argv[argc - 2], "--rough-glass") == 0)) {
         glass = strcmp(argv[argc - 2], "--rough-glass") == 0;
         roughness = (float)atof(argv[argc - 1]);
@@ -47,8 +56,8 @@ int main(int argc, char **argv) {
         obj = argv[argc - 1];
         argc -= 2;
     }
-    if (argc < 2 || (roughness != 0.0f && !obj) || (glass && !(roughness > 0.0f))) {
-        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]] [--adaptive]\n", argv[0]);
+    if (argc < 2 || ((roughness != 0.0f || map_strength != 0.0f) && !obj) || (glass && !(roughness > 0.0f)) || map_strength < 0.0f) {
+        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha] [--normal-map strength]] [--adaptive]\n", argv[0]);
         return 2;
     }
     const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[2]) : 400, height = argc > 3 ? (uint32_t)atoi(argv[3]) : 225;
@@ -63,6 +72,7 @@ int main(int argc, char **argv) {
         }
         wfpt_triangle *tris = (wfpt_triangle *)calloc(n_tris, sizeof *tris);
         float *n9 = (float *)calloc(9u * (size_t)n_tris, sizeof *n9);
+        float *uv6 = (float *)calloc(6u * (size_t)n_tris, sizeof *uv6);
         wfpt_bvh_node *mesh_nodes = (wfpt_bvh_node *)calloc(2u * (size_t)n_tris, sizeof *mesh_nodes);
         wfpt_material grey;
         memset(&grey, 0, sizeof grey);
@@ -73,7 +83,7 @@ int main(int argc, char **argv) {
             grey.refract_index = 1.5f;
             grey.material_type = 2u;
         }
-        CHECK(wfpt_load_obj_normals(obj, tris, NULL, n9, n_tris, &n_tris, 0, glass ? 2u : roughness > 0.0f ? 1u : 0u)); /* triangle i: _pad = i, row i of n9; --roughness: Metal, --rough-glass: Dielectric */
+        CHECK(wfpt_load_obj_normals(obj, tris, uv6, n9, n_tris, &n_tris, 0, glass ? 2u : roughness > 0.0f ? 1u : 0u)); /* triangle i: _pad = i, row i of n9; --roughness: Metal, --rough-glass: Dielectric */
         CHECK(wfpt_build_bvh_triangles(tris, n_tris, mesh_nodes, 2u * n_tris, &n_mesh_nodes, 32)); /* reorders: the rows follow by _pad */
         const float from[3] = {0.0f, 1.0f, 4.5f}, at[3] = {0.0f, 0.0f, 0.0f};
         float pitch, yaw, view[16], inv_proj[16];
@@ -88,7 +98,8 @@ int main(int argc, char **argv) {
         params.height = height;
         params.max_wavefronts = bounces;
         params.miss_floor = 128;
-        params.flags = WFPT_FLAG_SHADING_NORMALS | (roughness > 0.0f ? WFPT_FLAG_MICROFACET : 0u) | (glass ? WFPT_FLAG_ROUGH_DIELECTRIC : 0u) | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u);
+        params.flags = WFPT_FLAG_SHADING_NORMALS | (roughness > 0.0f ? WFPT_FLAG_MICROFACET : 0u) | (glass ? WFPT_FLAG_ROUGH_DIELECTRIC : 0u) | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u) |
+                       (map_strength > 0.0f ? WFPT_FLAG_TEXTURES | WFPT_FLAG_NORMAL_MAPS : 0u);
         ctx = wfpt_create_mesh(&params, tris, n_tris, &grey, 1, mesh_nodes, n_mesh_nodes, &camera, inv_proj, view);
         if (!ctx) {
             fprintf(stderr, "wfpt_create_mesh: %s\n", wfpt_last_error(NULL));
@@ -96,6 +107,25 @@ int main(int argc, char **argv) {
         }
         CHECK(wfpt_set_triangle_normals(ctx, n9, n_tris));
         if (roughness > 0.0f) CHECK(wfpt_set_roughness(ctx, 0, roughness)); /* include/wfpt.h "Microfacet metals", "Rough dielectrics" */
+        if (map_strength > 0.0f) { /* include/wfpt.h "Normal maps": rgb = 0.5 + 0.5 n of the height field 0.02 sin(8 2pi u) sin(8 2pi v), green = +v, row 0 = the top */
+            enum { MAP = 64 };
+            float *rgb = (float *)calloc(3u * MAP * MAP, sizeof *rgb);
+            const float k = 8.0f * 6.2831853f, amp = 0.02f;
+            for (int row = 0; row < MAP; ++row)
+                for (int col = 0; col < MAP; ++col) {
+                    const float u = ((float)col + 0.5f) / MAP, v = 1.0f - ((float)row + 0.5f) / MAP;
+                    const float dhu = amp * k * cosf(k * u) * sinf(k * v), dhv = amp * k * sinf(k * u) * cosf(k * v);
+                    const float il = 1.0f / sqrtf(dhu * dhu + dhv * dhv + 1.0f);
+                    float *c = rgb + 3 * (row * MAP + col);
+                    c[0] = 0.5f - 0.5f * dhu * il;
+                    c[1] = 0.5f - 0.5f * dhv * il;
+                    c[2] = 0.5f + 0.5f * il;
+                }
+            CHECK(wfpt_set_triangle_uvs(ctx, uv6, n_tris));
+            CHECK(wfpt_set_texture(ctx, 0, rgb, MAP, MAP, NULL));
+            CHECK(wfpt_bind_normal_map(ctx, 0, 0, map_strength));
+            free(rgb);
+        }
         uint32_t still = 0;
         if (adaptive) CHECK(wfpt_render_adaptive(ctx, spp, 8, &still));
         else CHECK(wfpt_render(ctx, spp));
@@ -104,6 +134,7 @@ int main(int argc, char **argv) {
         wfpt_destroy(ctx);
         free(mesh_nodes);
         free(n9);
+        free(uv6);
         free(tris);
         return 0;
     }

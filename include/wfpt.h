@@ -278,7 +278,12 @@ enum {
     WFPT_FLAG_ROUGH_DIELECTRIC = 1u << 26 /* GGX rough dielectrics on triangle meshes, see "Rough dielectrics" below: a dielectric hit of a
                                         material whose roughness alpha is above 0 reflects or refracts about a sampled microfacet normal.
                                         Needs WFPT_FLAG_MICROFACET and goes with everything that flag goes with. With no roughness above 0
-                                        on a dielectric the context launches the kernels it launches without the flag, same bits. */
+                                        on a dielectric the context launches the kernels it launches without the flag, same bits. */,
+    WFPT_FLAG_NORMAL_MAPS = 1u << 27 /* tangent-space normal maps on triangle meshes, see "Normal maps" below: a material bound to a
+                                        texture slot as its normal map scatters, connects and reports its AOV normal about the texel's
+                                        normal carried into the triangle's tangent frame. Needs WFPT_FLAG_TEXTURES and
+                                        WFPT_FLAG_SHADING_NORMALS and inherits the latter's refusals. With nothing bound the context
+                                        launches the kernels it launches without the flag, same bits. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -700,7 +705,8 @@ int wfpt_sample_environment(wfpt_ctx *ctx, const float *dirs, size_t n, float *r
  * range, a binding to an empty slot, a bad size, texel or parameter, a UV that is not finite, and a triangle whose row is >= the rows of a set
  * UV table (checked by wfpt_set_triangle_uvs and wfpt_update_scene_mesh); WFPT_ERR_UNSUPPORTED for a call that would texture a
  * WFPT_LOOP_FUSED_BINNED context (a context with a binding never runs the class-binned loop). wfpt_render_chunked* masks the flag off.
- * Out of scope: mip-mapping, normal / bump / roughness maps, .mtl files (per-vertex normals: "Shading normals" below). */
+ * Out of scope: mip-mapping, bump / roughness maps, .mtl files (per-vertex normals: "Shading normals" below; normal maps: "Normal maps"
+ * below). */
 #define WFPT_MAX_TEXTURES 64u
 typedef enum wfpt_texture_filter { WFPT_TEXTURE_BILINEAR = 0, WFPT_TEXTURE_NEAREST = 1 } wfpt_texture_filter;
 typedef struct wfpt_texture_params {
@@ -761,7 +767,8 @@ int wfpt_texture_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches);
  * table is set); WFPT_ERR_UNSUPPORTED for a call that would put a table on a WFPT_LOOP_FUSED_BINNED context (a context with a table never
  * runs the class-binned loop). wfpt_create refuses the flag together with WFPT_FLAG_LIGHT_POWER and WFPT_FLAG_ANALYTIC_LIGHTS: their
  * connect kernels are twins of their own, and a twin of each twin is not built. The flag composes with every other one.
- * Out of scope: normal and bump maps; correction of below-surface scatter directions; the flag together with WFPT_FLAG_LIGHT_POWER /
+ * Normal maps are a flag of their own, WFPT_FLAG_NORMAL_MAPS: see "Normal maps" below.
+ * Out of scope: bump maps; correction of below-surface scatter directions; the flag together with WFPT_FLAG_LIGHT_POWER /
  * WFPT_FLAG_ANALYTIC_LIGHTS; the stage API (wfpt_kernel_run ignores the table); wfpt_render_chunked* (the flag is masked off); .mtl files. */
 /* the table: n_rows rows of nine finite floats, the normals of corners 0, 1, 2 (v0, v0 + e1, v0 + e2), row r for the triangles whose _pad is
  * r -- the UV table's row number; normalised as stored (above). NULL / 0 clears it. Blocking. */
@@ -828,7 +835,7 @@ int wfpt_shading_normal_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *laun
  * WFPT_FLAG_LIGHT_POWER and WFPT_FLAG_ANALYTIC_LIGHTS included.
  * Rough dielectrics are a flag of their own, WFPT_FLAG_ROUGH_DIELECTRIC: see "Rough dielectrics" below.
  * Out of scope: sphere contexts (the shade step and the traversal share one prim_kind, and a sphere's record holds a centre, not a
- * normal); roughness, normal and bump maps; anisotropy; multiple-scattering energy compensation (single-scatter GGX
+ * normal); roughness and bump maps (normal maps: "Normal maps" below); anisotropy; multiple-scattering energy compensation (single-scatter GGX
  * loses energy at high alpha by construction); next-event estimation or MIS at rough hits (unbiased without, and noisier); scatter
  * directions below a shading normal's geometric surface; the stage API (wfpt_kernel_run ignores roughness); wfpt_render_chunked* (the
  * flag is masked off). */
@@ -888,13 +895,69 @@ int wfpt_microfacet_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches
  * WFPT_LOOP_FUSED_BINNED context (WFPT_ERR_UNSUPPORTED for the call that would put an alpha above 0 there); masked off in
  * wfpt_render_chunked*; ignored by the stage API; the setters restart the accumulation and drop history and graphs;
  * wfpt_update_scene_mesh keeps the alphas; wfpt_update_scene to spheres is refused while an alpha is above 0.
- * Out of scope: sphere contexts; roughness, normal and bump maps; anisotropy; multiple-scattering energy compensation; next-event
+ * Out of scope: sphere contexts; roughness and bump maps (normal maps: "Normal maps" below); anisotropy; multiple-scattering energy compensation; next-event
  * estimation or MIS at rough hits; radiance scaling by eta^2; absorption inside the medium; thin-walled glass; directions below a
  * shading normal's geometric surface. */
 /* steps 1-12 on the device for n caller rows in16 of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0): rows out8 of
  * (h.xyz | 2.0 where the hit fell back, 1.0 where the path is dead, else 0.0), (weight.rgb | 1.0 refracted, 0.0 reflected); a row that
  * fell back answers (+0, +0, +0, 2, +0, +0, +0, +0). Needs the flag and nothing else of the context. Blocking. */
 int wfpt_sample_rough_dielectric(wfpt_ctx *ctx, const float *in16, size_t n, float *out8);
+
+/* ------------------------------------------------------------------ Normal maps (WFPT_FLAG_NORMAL_MAPS): tangent-space normal maps on meshes
+ * On a triangle context created with WFPT_FLAG_TEXTURES | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_NORMAL_MAPS a material can be bound to a
+ * texture slot (wfpt_set_texture above) as its NORMAL MAP: linear texels whose rgb is 0.5 + 0.5 * the tangent-space normal. Green is +v and
+ * v = 1 is the image's top row -- the OpenGL convention. A material may hold a colour binding (wfpt_bind_texture) and a normal-map binding
+ * at once, and one slot may serve both kinds. A context is MAPPED while at least one material holds a normal-map binding (strength 0
+ * counts). With the flag and nothing bound the context launches exactly the kernels it launches without it and renders the same bits.
+ * The mapped normal of a hit at p on a triangle whose material is bound, in the arithmetic of "Microfacet metals" (IEEE f32 add, sub,
+ * mul, div, sqrt in the order written, no fma; dot, cross and normalize3 as there); tests/normal_map_ref.py restates it. Inputs: ng, the
+ * stored normal; ns, the result of "Shading normals" steps 1-5, or ng where no table of corner normals is set; e1, e2; the UV row
+ * u0 v0 u1 v1 u2 v2 the triangle's _pad names (all zero where no UV table is set); the bound slot's texture; the binding's strength s:
+ *   A. (u, v) = triangle_uv(p, ...) as under "Textures"; c = tex_lookup(texture, u, v): the slot's own scale, offset and filter apply
+ *   B. x = (2 c.x - 1) s; y = (2 c.y - 1) s; z = 2 c.z - 1. If x == 0 and y == 0 the answer is ns, bit for bit (code 1): strength 0 and
+ *      a flat texel are the identity, not a renormalised ns
+ *   C. du1 = u1 - u0; dv1 = v1 - v0; du2 = u2 - u0; dv2 = v2 - v0; det = du1 dv2 - du2 dv1. If neither det > 0 nor det < 0 (zero or NaN)
+ *      the answer is ns (code 2). sg = det > 0 ? 1 : -1; T = (e1 dv2 - e2 dv1) sg and Bt = (e2 du1 - e1 du2) sg per component: the
+ *      directions of dP/du and dP/dv (the division by |det| is left out: both are only ever normalised or tested for sign)
+ *   D. k = dot(ns, T); tt = T - ns k per component; l2 = dot(tt, tt). If !(l2 > 0) or !(l2 < inf) the answer is ns (code 2).
+ *      t = tt (1 / sqrt(l2))
+ *   E. bt = cross(ns, t); if dot(bt, Bt) < 0 each component of bt is negated: mirrored UVs keep their handedness
+ *   F. m = (t x + bt y) + ns z per component; l2m = dot(m, m); nm = m (1 / sqrt(l2m)). The answer is nm (code 0) if l2m > 0, l2m < inf
+ *      and dot(nm, ng) > 0; otherwise it is ns (code 3). "Never flipped" stays the rule: the stored orientation still decides inside and
+ *      outside for glass.
+ * Tangents are per triangle, not per vertex; the Gram-Schmidt step against the interpolated ns is what smooths them.
+ * The mapped normal goes exactly where the shading normal goes, and nowhere else: scatter()'s normal for all three materials through the
+ * per-hit record; the n the microfacet and rough-glass sampling start from; the connect pass's receiver normal, in the emitter and the
+ * map branch alike; the AOV normal of a primary hit. It does not go to a light's own normal, texture UVs, the traversal, the emission
+ * pass, any RNG draw, the hit order or any exit decision. As under "Shading normals" no record pass runs before the last wavefront's
+ * shade step; the connect pass before that step still uses the mapped normal.
+ * Device side: on a mapped context shading_nmap_kernel, microfacet_nmap_kernel or rough_glass_nmap_kernel takes the place of
+ * shading_normal_kernel, microfacet_kernel or rough_glass_kernel -- same slot, same walk, same table; a hit whose material has no map gets
+ * bit for bit the record of the kernel replaced -- and connect_nmap_kernel and aov_nmap_kernel take the connect and AOV twins' role. The
+ * launches are booked where the passes they replace are booked (wfpt_shading_normal_timing_ms, wfpt_microfacet_timing_ms).
+ * A bind or unbind restarts the accumulation and the frame counter and drops the temporal history and the captured graphs; a refused call
+ * leaves the context as it was. wfpt_clear_texture on a slot also drops the normal-map bindings to it; wfpt_set_texture on a bound slot
+ * keeps them. wfpt_update_scene_mesh keeps the bindings of material indices below the new count; wfpt_update_scene to spheres is refused
+ * while a map is bound. wfpt_render_chunked* masks the flag off; the stage API ignores it.
+ * Errors: WFPT_ERR_INVALID_ARGUMENT at wfpt_create without WFPT_FLAG_TEXTURES or WFPT_FLAG_SHADING_NORMALS, or with
+ * WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS; from the calls below for a context without the flag, a sphere context, a material
+ * out of range, an empty slot or one out of range, a strength that is NaN, infinite or negative; WFPT_ERR_UNSUPPORTED for a binding on a
+ * WFPT_LOOP_FUSED_BINNED context (a mapped context never runs the class-binned loop).
+ * Out of scope: sphere contexts; per-vertex or MikkTSpace tangents; bump (height) maps; roughness maps; mip-mapping; correction of
+ * scatter directions that dip below the geometric surface; the flag with WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS; .mtl files;
+ * the stage API and wfpt_render_chunked*. */
+/* material `material_idx` takes the texture of `slot` as its normal map at `strength` (finite, >= 0); slot = -1 unbinds. Blocking. */
+int wfpt_bind_normal_map(wfpt_ctx *ctx, uint32_t material_idx, int32_t slot, float strength);
+/* the binding of a material: its slot (-1 = none) and strength (0 where none) */
+int wfpt_get_normal_map(wfpt_ctx *ctx, uint32_t material_idx, int32_t *slot, float *strength);
+/* the mapped normal on the device for n caller rows in4 of (p.xyz | the triangle's index in the device's order as the BITS of the fourth
+ * float), as wfpt_sample_shading_normal takes them: rows out4 of (n.xyz | code) with code 0 mapped, 1 identity by step B, 2 no tangent
+ * frame, 3 rejected by step F, 4 the triangle's material has no map (n = ns), 5 with (0, 0, 0) an index outside the scene. Needs a
+ * binding. Blocking. */
+int wfpt_sample_normal_map(wfpt_ctx *ctx, const float *in4, size_t n, float *out4);
+/* steps B-F on the host, no GPU and no context, compiled from the function the kernels call: n rows in22 of
+ * (ng.xyz, ns.xyz, e1.xyz, e2.xyz, u0 v0 u1 v1 u2 v2, c.rgb, strength) -> rows out4 of (n.xyz | code 0..3) */
+int wfpt_mapped_normal_host(const float *in22, size_t n, float *out4);
 
 /* ------------------------------------------------------------------ Emission (WFPT_FLAG_EMISSION): materials that light the scene
  * A context created with WFPT_FLAG_EMISSION holds one emission colour per material, all zero at creation. A material with a non-zero colour

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "FLAG_ROUGH_DIELECTRIC", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "FLAG_ROUGH_DIELECTRIC", "FLAG_NORMAL_MAPS", "mapped_normal_host", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -65,6 +65,8 @@ FLAG_SHADING_NORMALS = 1 << 24
 FLAG_MICROFACET = 1 << 25
 # GGX rough dielectrics on triangle meshes: the same roughness on a dielectric (include/wfpt.h "Rough dielectrics"); needs FLAG_MICROFACET
 FLAG_ROUGH_DIELECTRIC = 1 << 26
+# tangent-space normal maps on triangle meshes (include/wfpt.h "Normal maps"); needs FLAG_TEXTURES and FLAG_SHADING_NORMALS
+FLAG_NORMAL_MAPS = 1 << 27
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2  # wfpt_light_type
 MAX_LIGHTS = 1024  # WFPT_MAX_LIGHTS
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
@@ -394,6 +396,10 @@ def lib():
         "wfpt_sample_microfacet": (i32, [vp, vp, sz, vp]),
         "wfpt_microfacet_timing_ms": (i32, [vp, C.POINTER(f32), C.POINTER(u32)]),
         "wfpt_sample_rough_dielectric": (i32, [vp, vp, sz, vp]),
+        "wfpt_bind_normal_map": (i32, [vp, u32, C.c_int32, f32]),
+        "wfpt_get_normal_map": (i32, [vp, u32, C.POINTER(C.c_int32), C.POINTER(f32)]),
+        "wfpt_sample_normal_map": (i32, [vp, vp, sz, vp]),
+        "wfpt_mapped_normal_host": (i32, [vp, sz, vp]),
         "wfpt_set_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_clear_emission": (i32, [vp]),
@@ -479,6 +485,19 @@ def tile_lists_host(nodes, gpu_camera, inv_proj, view, width, height, tile_rank=
                                     _p(out), gx * gy)
     if st != 0:
         raise WfptError(st, "wfpt_tile_lists_host: invalid argument")
+    return out
+
+
+def mapped_normal_host(rows):
+    """Steps B-F of include/wfpt.h "Normal maps" on the host (no GPU), from the function the kernels call. rows: (n, 22) float32 of
+    (ng.xyz, ns.xyz, e1.xyz, e2.xyz, u0 v0 u1 v1 u2 v2, c.rgb, strength); returns (n, 4) float32 of (n.xyz, code 0..3)."""
+    a = np.ascontiguousarray(rows, "<f4")
+    if a.ndim != 2 or a.shape[1] != 22:
+        raise ValueError(f"mapped_normal_host: expected rows of 22 floats, got shape {a.shape}")
+    out = np.zeros((a.shape[0], 4), "<f4")
+    st = lib().wfpt_mapped_normal_host(_p(a), a.shape[0], _p(out))
+    if st != 0:
+        raise WfptError(st, "wfpt_mapped_normal_host: invalid argument")
     return out
 
 
@@ -1556,6 +1575,25 @@ class PathTracer:
     def microfacet_timing_ms(self):
         """(milliseconds, launches) of the microfacet launches of every timed render since creation (apart from render_timed's stage times)."""
         return self._timing(lib().wfpt_microfacet_timing_ms)
+
+    # ---- normal maps (triangle contexts created with FLAG_NORMAL_MAPS; include/wfpt.h "Normal maps")
+    def bind_normal_map(self, material_idx, slot, strength=1.0):
+        """Material `material_idx` takes the texture of slot `slot` (linear texels, rgb = 0.5 + 0.5 * the tangent-space normal, green = +v)
+        as its normal map at `strength` (finite, >= 0); None or -1 unbinds it. Restarts the accumulation like a scene update."""
+        self._check(lib().wfpt_bind_normal_map(self.handle, _material_index(material_idx), -1 if slot is None else slot, float(strength)))
+        self.render_progress.reset()
+
+    def normal_map(self, material_idx):
+        """(slot, strength) of the material's normal-map binding; (None, 0.0) where it has none."""
+        slot, strength = C.c_int32(-1), C.c_float(0.0)
+        self._check(lib().wfpt_get_normal_map(self.handle, _material_index(material_idx), C.byref(slot), C.byref(strength)))
+        return (None if slot.value < 0 else int(slot.value)), float(strength.value)
+
+    def sample_normal_map(self, rows):
+        """The mapped normal for caller-supplied hits, computed on the device. rows: (n, 4) float32 of (p.xyz, the triangle's index in the
+        device's order as the BITS of the fourth float); returns (n, 4) float32 of (n.xyz, code): 0 mapped, 1 identity, 2 no tangent
+        frame, 3 rejected, 4 the material has no map, 5 an index outside the scene."""
+        return self._probe(lib().wfpt_sample_normal_map, "sample_normal_map", rows, 4, 4)
 
     # ---- emission (contexts created with FLAG_EMISSION; include/wfpt.h "Emission")
     def set_emission(self, material_idx, rgb):

@@ -116,6 +116,12 @@ struct TextureTables {
     DeviceBuffer<uint2> prim;
 };
 
+// The normal-map tables the kernels read (wfpt_ctx::nm_desc, nm_prim), built for a candidate state and then committed whole
+struct NmapTables {
+    DeviceBuffer<TexDev> desc;
+    DeviceBuffer<uint4> prim;
+};
+
 // The emission tables the kernels read (wfpt_ctx::em_prim, em_mat), built for a candidate state and then committed whole
 struct EmissionTables {
     DeviceBuffer<uint32_t> prim;
@@ -284,8 +290,15 @@ struct wfpt_ctx {
     std::vector<float> mf_alpha;
     DeviceBuffer<float> mf_prim;
     bool mf_glass = false;
+    // WFPT_FLAG_NORMAL_MAPS (include/wfpt.h "Normal maps"): the binding per material (slot, -1 = none; strength) and what build_nmap_tables
+    // makes of them for the kernels -- a copy of the slots' descriptors and the per-primitive {slot or kNoTexture, UV row, strength} table
+    // (both null while no material is bound: the context then runs as one without the flag)
+    std::vector<int32_t> nm_bind;
+    std::vector<float> nm_strength;
+    DeviceBuffer<TexDev> nm_desc;
+    DeviceBuffer<uint4> nm_prim;
     // The per-hit shade records of the shading-normal and microfacet passes, 3 x float4 per ray-queue slot per sample in flight: one table
-    // for both features, allocated with the first of {table of normals, roughness above 0} and released with the last
+    // for the three features, allocated with the first of {table of normals, roughness above 0, normal map bound} and released with the last
     // (reserve_hit_table, commit_hit_table)
     DeviceBuffer<float4> hit_table;
     // WFPT_FLAG_ENV_NEE (include/wfpt.h "Environment next-event estimation"): the sampling distribution of the map above, built and
@@ -785,13 +798,21 @@ int probe(wfpt_ctx *c, const char *who, const float *in, size_t in_width, float 
     if (e != hipSuccess) return hip_fail(c, e, who);
     return WFPT_OK;
 }
+// a WFPT_FLAG_NORMAL_MAPS context is "mapped" while a material holds a normal-map binding: the record pass that runs before the shade steps
+// that scatter is the NMAP one of its kind (and runs without a table of normals or a roughness too), and the connect pass and the AOV
+// kernel are the NMAP variants
+bool mapped(const wfpt_ctx *c) { return c->nm_prim.get() != nullptr; }
+NmapScene nmap_scene(const wfpt_ctx *c) { return NmapScene{c->nm_prim.get(), c->nm_desc.get(), c->tex_uv.get(), c->sn_rows.get()}; }
 // persistent workgroups over the (sample, segment) items, at most extend's grid (the four-wide walk's spill area is sized for that)
-// shaded: the receivers' normals are shading normals (the loops of a context that holds a table; the stage API ignores the table)
+// shaded: the receivers' normals are shading (or mapped) normals (the loops of a context that holds a table or a normal-map binding; the
+// stage API ignores both)
 hipError_t launch_connect_pass(wfpt_ctx *c, const ConnectArgs &a, uint32_t nb, bool shaded) {
     const LightDist ld = light_dist(c);
     const LightTable lt = light_table(c);
+    const NmapScene nm = nmap_scene(c);
     return launch_connect(a, extend_grid(c, nb), c->stream.get(), textured(c), env_connecting(c), weighing(c) || env_weighing(c),
-                          power_selecting(c) ? &ld : nullptr, analytic_selecting(c) ? &lt : nullptr, shaded ? c->sn_rows.get() : nullptr);
+                          power_selecting(c) ? &ld : nullptr, analytic_selecting(c) ? &lt : nullptr,
+                          shaded && !mapped(c) ? c->sn_rows.get() : nullptr, shaded && mapped(c) ? &nm : nullptr);
 }
 // the emission pass of the context's kind
 hipError_t launch_emission_pass(wfpt_ctx *c, const EmissionArgs &a, uint32_t grid) {
@@ -821,7 +842,7 @@ MicrofacetArgs microfacet_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w
     return MicrofacetArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->mf_prim.get(), c->hit_table.get(), rec_out, wavefront};
 }
 // the shade steps that scatter read their shade records per hit (shaded_scene), from the table one of the two passes has just written
-bool per_hit(const wfpt_ctx *c) { return shading(c) || rough(c); }
+bool per_hit(const wfpt_ctx *c) { return shading(c) || rough(c) || mapped(c); }
 // The per-hit table for a CANDIDATE state that needs one, into `out` unless the context already holds it; commit_hit_table(c, out, needed)
 // then installs it, or releases the context's once neither feature needs it (the stream is idle: the caller synchronised it)
 int reserve_hit_table(wfpt_ctx *c, DeviceBuffer<float4> &out) {
@@ -869,7 +890,7 @@ hipError_t launch_miss_pass(wfpt_ctx *c, const MissArgs &a, uint32_t grid) {
 // the class-binned loop runs when its buffers exist and the scene at hand is one it is built for: in LDS, primitive indices within
 // the record's 16 bits
 bool use_binned(const wfpt_ctx *c) {
-    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && !analytic_selecting(c) && !shading(c) && !rough(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
+    return c->bin_capable && !c->env_tex.get() && !textured(c) && !emitting(c) && !analytic_selecting(c) && !shading(c) && !rough(c) && !mapped(c) && c->fused && c->scene.lds_scene && !c->rec_dense.get() && c->scene.n_spheres <= (1u << 16) &&
            c->batch_max * static_cast<uint32_t>(kBinClasses) <= 1024u && c->p.rng_mode == WFPT_RNG_PIXEL;
 }
 // The loop this context runs (include/wfpt.h, wfpt_loop_kind): the one place that decides it
@@ -900,6 +921,7 @@ struct EventRec { int stage; hipEvent_t start, stop; };
 // emission pass after it (a textured emitter's light is (thr * tex) * e); the connect pass after that, which the emission pass must not
 // see (it reads the flag the previous step's connect pass left). In the loops they follow the scan that decides whether the loop goes on
 // (shade_n = 0 once it has exited), as the shade they precede.
+// On a mapped context (include/wfpt.h "Normal maps") the connect pass takes the mapped normal and the record pass is launch_nmap_record.
 // shaded: the loops of a context that holds a table of corner normals (include/wfpt.h "Shading normals"; the stage API passes false and
 // ignores the table): the connect pass takes the shading normal.
 // shade_rec_out: the loops of a context whose step reads its shade records per hit (per_hit(c): a table of normals, a roughness above 0 --
@@ -913,7 +935,11 @@ int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const 
     if (textured(c)) WFPT_HIP(c, timed(pass_stage(kPassTexture), [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
     if (emitting(c)) WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
     if (connecting(c)) WFPT_HIP(c, timed(pass_stage(kPassConnect), [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
-    if (shade_rec_out && rough(c))
+    if (shade_rec_out && mapped(c)) // (booked where the pass it replaces is booked)
+        WFPT_HIP(c, timed(pass_stage(rough(c) ? kPassMicrofacet : kPassShading), [&] {
+            return launch_nmap_record(microfacet_args(c, b, w, shade_rec_out), nmap_scene(c), c->mf_glass, grid, c->stream.get());
+        }));
+    else if (shade_rec_out && rough(c))
         WFPT_HIP(c, timed(pass_stage(kPassMicrofacet), [&] {
             const MicrofacetArgs a = microfacet_args(c, b, w, shade_rec_out);
             return c->mf_glass ? launch_rough_glass(a, grid, c->stream.get()) : launch_microfacet(a, grid, c->stream.get());
@@ -944,7 +970,7 @@ int enqueue_stages(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb), st); }));
         const HitWalk w = hit_walk(c, -1, nb, qi, &c->ctl.get()->shade_n, c->capacity);
         const bool scatters = per_hit(c) && b + 1 < c->p.max_wavefronts; // (the last wavefront's extension rays are never traced)
-        if (int r = enqueue_pre_shade(c, timed, b, nb, w, shading(c), scatters ? c->hit_rec.get() : nullptr); r != WFPT_OK) return r;
+        if (int r = enqueue_pre_shade(c, timed, b, nb, w, shading(c) || mapped(c), scatters ? c->hit_rec.get() : nullptr); r != WFPT_OK) return r;
         // split: one launch, blockIdx.z = material class (README.md:19's by-material shade kernels)
         WFPT_HIP(c, timed(split ? WFPT_STAGE_SHADE_LAMBERTIAN : WFPT_STAGE_SHADE, [&] {
                      ShadeArgs sa = shade_args(c, qi, &c->ctl.get()->shade_n, c->capacity, 0, 0xffffffffu, false, nb);
@@ -980,7 +1006,7 @@ int enqueue_fused(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         WFPT_HIP(c, timed(WFPT_STAGE_SCAN, [&] { return launch_scan(scan_args(c, &c->ctl.get()->n_in, c->capacity, true, b, nb, par), st); }));
         if (env) WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         const bool scatters = per_hit(c) && !last;
-        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
+        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c) || mapped(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
             return r;
         WFPT_HIP(c, timed(last ? WFPT_STAGE_BOUNCE_LAST : WFPT_STAGE_BOUNCE, [&] {
                      BounceArgs a = bounce_args(c, par, par ^ 1, nb);
@@ -1031,7 +1057,7 @@ int enqueue_refill(wfpt_ctx *c, Timed &timed, uint32_t nb) {
         if (!last || env) // (the last launch's miss items: a launch of their own only with the map)
             WFPT_HIP(c, timed(WFPT_STAGE_MISS, [&] { return launch_miss_pass(c, fused_miss_args(c, par, nb), consumer_grid(c, nb)); }));
         const bool scatters = per_hit(c) && !last;
-        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
+        if (int r = enqueue_pre_shade(c, timed, b, nb, hit_walk(c, par, nb), shading(c) || mapped(c), scatters ? c->rec_mem[par].get() : nullptr); r != WFPT_OK)
             return r;
         if (!last) {
             WFPT_HIP(c, timed(WFPT_STAGE_SHADE, [&] {
@@ -1096,8 +1122,9 @@ int enqueue_batch(wfpt_ctx *c, std::vector<EventRec> *ev, uint32_t nb) {
     if (c->aov_sums.get()) // first in the batch, serially on the stream: it sees the batch's first frame, before accumulate advances it
         WFPT_HIP(c, timed(pass_stage(kPassAov), [&] {
                      const TexScene ts = tex_scene(c);
+                     const NmapScene nm = nmap_scene(c);
                      return launch_aov(aov_args(c, nb), aov_grid(c), c->stream.get(), env_of(c), textured(c) ? &ts : nullptr,
-                                       shading(c) ? c->sn_rows.get() : nullptr);
+                                       shading(c) && !mapped(c) ? c->sn_rows.get() : nullptr, mapped(c) ? &nm : nullptr);
                  }));
     if (second_plane(c)) // the loops' first kernel sets every slice of `image` to 1: `emitted` starts at 0 with it
         WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] {
@@ -1719,6 +1746,13 @@ const FlagRule kFlagRules[] = {
     // WFPT_FLAG_ROUGH_DIELECTRIC shares its tables, setters and pass slot; dielectric hits never connect either
     {WFPT_FLAG_ROUGH_DIELECTRIC, WFPT_FLAG_MICROFACET, 0,
      "wfpt_create: WFPT_FLAG_ROUGH_DIELECTRIC needs WFPT_FLAG_MICROFACET (the roughness per material and the pass it extends are that flag's)", nullptr},
+    // WFPT_FLAG_NORMAL_MAPS reads WFPT_FLAG_TEXTURES' slots and UV table and takes WFPT_FLAG_SHADING_NORMALS' pass slot and twins' role:
+    // it inherits that flag's refusals (reported at that flag's row above)
+    {WFPT_FLAG_NORMAL_MAPS, WFPT_FLAG_TEXTURES | WFPT_FLAG_SHADING_NORMALS, WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS,
+     "wfpt_create: WFPT_FLAG_NORMAL_MAPS needs WFPT_FLAG_TEXTURES (the slots and the UV table) and WFPT_FLAG_SHADING_NORMALS "
+     "(the pass slot, and the connect and AOV twins it stands in for)",
+     "wfpt_create: WFPT_FLAG_NORMAL_MAPS does not go with WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS "
+     "(their connect kernels are twins of their own)"},
     // (WFPT_FLAG_ENV_MIS goes with no WFPT_FLAG_MIS either, since it weighs the emitters itself: the WFPT_FLAG_ENV_NEE it needs has
     // refused that at WFPT_FLAG_MIS's row)
     {WFPT_FLAG_ENV_MIS, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect | WFPT_FLAG_ENV_NEE, 0,
@@ -1992,7 +2026,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC | WFPT_FLAG_NORMAL_MAPS); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -2092,6 +2126,9 @@ static int build_emission_tables(wfpt_ctx *c, const std::vector<float> &rgb, con
                                  const float4 *geom = nullptr, uint32_t prim_kind = 0);
 static void commit_emission_tables(wfpt_ctx *c, EmissionTables &&t);
 static int build_normal_rows(wfpt_ctx *c, const std::vector<float> &n9, const std::vector<uint32_t> &row, DeviceBuffer<float4> &out);
+static int build_nmap_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<float> &strength,
+                             const std::vector<uint32_t> &mat_idx, const std::vector<uint32_t> &row, NmapTables &out);
+static void commit_nmap_tables(wfpt_ctx *c, NmapTables &&t);
 static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
                                  const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out, bool &glass);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
@@ -2111,6 +2148,8 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
             if (triangles[i]._pad >= c->h_normals.size() / 9)
                 return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene_mesh: a triangle's row (_pad) is beyond the table of normals");
     }
+    if (spheres && mapped(c)) // WFPT_FLAG_NORMAL_MAPS with a binding: spheres take none
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a normal-map binding (unbind it first)");
     if (spheres && rough(c)) // WFPT_FLAG_MICROFACET with a roughness above 0: spheres take none
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a roughness above 0 (clear it first)");
     WFPT_HIP(c, hipSetDevice(c->device));
@@ -2133,6 +2172,18 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     DeviceBuffer<float4> sn_rows; // likewise the normal rows of the new primitive order
     if (!c->h_normals.empty())
         if (int r = build_normal_rows(c, c->h_normals, row, sn_rows); r != WFPT_OK) return r;
+    NmapTables nm_tables; // likewise the normal-map tables; the bindings of materials the new scene no longer has are dropped
+    std::vector<int32_t> nm_bind;
+    std::vector<float> nm_strength;
+    if (mapped(c)) {
+        nm_bind = c->nm_bind;
+        nm_strength = c->nm_strength;
+        if (nm_bind.size() > n_materials) {
+            nm_bind.resize(n_materials);
+            nm_strength.resize(n_materials);
+        }
+        if (int r = build_nmap_tables(c, c->tex_dev, nm_bind, nm_strength, mat_idx, row, nm_tables); r != WFPT_OK) return r;
+    }
     DeviceBuffer<float> mf_prim; // likewise the roughness table; the alphas of materials the new scene no longer has are dropped
     std::vector<float> mf_alpha;
     bool mf_glass = false;
@@ -2167,6 +2218,12 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         return r; // the context keeps its old scene, graphs, texture tables and accumulation
     if (c->p.flags & WFPT_FLAG_TEXTURES) commit_texture_tables(c, std::move(tables));
     if (sn_rows.get()) c->sn_rows = std::move(sn_rows);
+    if (mapped(c)) { // (the dropped bindings may have been the last: the per-hit records go with them below, or here)
+        c->nm_bind = std::move(nm_bind);
+        c->nm_strength = std::move(nm_strength);
+        commit_nmap_tables(c, std::move(nm_tables));
+        if (!rough(c)) commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
+    }
     if (rough(c)) { // (the dropped alphas may have been the last above 0: the per-hit records then go with them)
         c->mf_alpha = std::move(mf_alpha);
         c->mf_prim = std::move(mf_prim);
@@ -3368,10 +3425,13 @@ int wfpt_set_texture(wfpt_ctx *c, uint32_t slot, const float *rgb, uint32_t w, u
     dev[slot] = TexDev{tex.get(), w, h, p->scale[0], p->scale[1], p->offset[0], p->offset[1], p->filter, 0u};
     TextureTables tables;
     if (int r = build_texture_tables(c, dev, c->tex_bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    NmapTables nm_tables; // (the normal-map bindings to the slot stay: their descriptors are the new texture's)
+    if (int r = build_nmap_tables(c, dev, c->nm_bind, c->nm_strength, c->h_prim_mat_idx, c->h_prim_row, nm_tables); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old texels
     c->tex_texels[slot] = std::move(tex);               // (frees the old texels: the old tables that named them go with them)
     std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
     commit_texture_tables(c, std::move(tables));
+    commit_nmap_tables(c, std::move(nm_tables));
     return scene_changed(c);
 }
 
@@ -3387,11 +3447,19 @@ int wfpt_clear_texture(wfpt_ctx *c, uint32_t slot) {
         if (b == static_cast<int32_t>(slot)) b = -1;
     TextureTables tables;
     if (int r = build_texture_tables(c, dev, bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    std::vector<int32_t> nm_bind = c->nm_bind; // the normal-map bindings to the slot go with it
+    for (int32_t &b : nm_bind)
+        if (b == static_cast<int32_t>(slot)) b = -1;
+    NmapTables nm_tables;
+    if (int r = build_nmap_tables(c, dev, nm_bind, c->nm_strength, c->h_prim_mat_idx, c->h_prim_row, nm_tables); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
     c->tex_texels[slot].release();
     std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
     c->tex_bind = std::move(bind);
     commit_texture_tables(c, std::move(tables));
+    c->nm_bind = std::move(nm_bind);
+    commit_nmap_tables(c, std::move(nm_tables));
+    commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
     return scene_changed(c);
 }
 
@@ -3486,7 +3554,7 @@ int wfpt_set_triangle_normals(wfpt_ctx *c, const float *n9, uint32_t n_rows) {
         if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
     }
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old rows
-    commit_hit_table(c, std::move(table), n_rows != 0 || rough(c));
+    commit_hit_table(c, std::move(table), n_rows != 0 || rough(c) || mapped(c));
     c->sn_rows = std::move(rows); // (the kernels take them from the context at each launch; the graphs that hold the old ones are dropped)
     c->h_normals = std::move(stored);
     return scene_changed(c);
@@ -3514,6 +3582,104 @@ int wfpt_sample_shading_normal(wfpt_ctx *c, const float *in4, size_t n, float *o
 int wfpt_shading_normal_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = shading_check(c, "wfpt_shading_normal_timing_ms"); r != WFPT_OK) return r;
     return pass_timing(c, kPassShading, ms_total, launches);
+}
+
+// ---------------------------------------------------------------- normal maps (include/wfpt.h "Normal maps")
+// The kernels' view of the bindings, the slots and the scene: a copy of the descriptor array and per primitive {slot or kNoTexture, UV row,
+// the strength's bits, 0}, in the order the device holds the primitives (both null while no material is bound). Built whole for a
+// CANDIDATE state without touching the context, like build_texture_tables.
+static int build_nmap_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<float> &strength,
+                             const std::vector<uint32_t> &mat_idx, const std::vector<uint32_t> &row, NmapTables &out) {
+    bool any = false;
+    for (int32_t b : bind) any = any || b >= 0;
+    if (!any) return WFPT_OK;
+    const size_t n = mat_idx.size();
+    std::vector<uint4> t(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t slot = mat_idx[i] < bind.size() ? bind[mat_idx[i]] : -1;
+        uint32_t bits = 0;
+        if (slot >= 0) std::memcpy(&bits, &strength[mat_idx[i]], sizeof(bits));
+        t[i] = make_uint4(slot >= 0 ? static_cast<uint32_t>(slot) : kNoTexture, row[i], bits, 0u);
+    }
+    WFPT_HIP(c, out.desc.alloc(WFPT_MAX_TEXTURES));
+    WFPT_HIP(c, out.prim.alloc(n));
+    WFPT_HIP(c, hipMemcpy(out.desc.get(), dev, sizeof(TexDev) * WFPT_MAX_TEXTURES, hipMemcpyHostToDevice));
+    WFPT_HIP(c, hipMemcpy(out.prim.get(), t.data(), sizeof(uint4) * n, hipMemcpyHostToDevice));
+    return WFPT_OK;
+}
+// the new tables replace the old ones (the stream is idle: the caller synchronised it)
+static void commit_nmap_tables(wfpt_ctx *c, NmapTables &&t) {
+    c->nm_desc = std::move(t.desc);
+    c->nm_prim = std::move(t.prim);
+}
+
+static int nmap_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_NORMAL_MAPS, "WFPT_FLAG_NORMAL_MAPS"); }
+
+int wfpt_bind_normal_map(wfpt_ctx *c, uint32_t material_idx, int32_t slot, float strength) {
+    const char *who = "wfpt_bind_normal_map";
+    if (int r = nmap_check(c, who); r != WFPT_OK) return r;
+    if (c->scene.prim_kind != 1) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sphere context takes no normal maps");
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": material_idx out of range");
+    if (slot < -1 || slot >= static_cast<int32_t>(WFPT_MAX_TEXTURES)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": slot out of range");
+    // the class-binned refusal, of a call that binds only (unbinding is always allowed); ahead of the empty slot's, since such a context
+    // takes no texture either
+    if (int r = feature_check(c, who, WFPT_FLAG_NORMAL_MAPS, "WFPT_FLAG_NORMAL_MAPS", slot >= 0 ? "normal maps" : nullptr); r != WFPT_OK) return r;
+    if (slot >= 0 && !c->tex_texels[slot].get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the slot holds no texture");
+    if (slot >= 0 && !(strength >= 0.0f && strength <= FLT_MAX))
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": strength must be finite and >= 0");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> bind = c->nm_bind;
+    std::vector<float> str = c->nm_strength;
+    if (bind.size() <= material_idx) {
+        bind.resize(material_idx + 1u, -1);
+        str.resize(material_idx + 1u, 0.0f);
+    }
+    bind[material_idx] = slot;
+    str[material_idx] = slot >= 0 ? strength : 0.0f;
+    NmapTables tables;
+    DeviceBuffer<float4> table;
+    if (int r = build_nmap_tables(c, c->tex_dev, bind, str, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
+    if (tables.prim.get())
+        if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
+    commit_hit_table(c, std::move(table), tables.prim.get() != nullptr || shading(c) || rough(c));
+    c->nm_bind = std::move(bind);
+    c->nm_strength = std::move(str);
+    commit_nmap_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_get_normal_map(wfpt_ctx *c, uint32_t material_idx, int32_t *slot, float *strength) {
+    if (int r = nmap_check(c, "wfpt_get_normal_map"); r != WFPT_OK) return r;
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_normal_map: material_idx out of range");
+    const bool bound = material_idx < c->nm_bind.size() && c->nm_bind[material_idx] >= 0;
+    if (slot) *slot = bound ? c->nm_bind[material_idx] : -1;
+    if (strength) *strength = bound ? c->nm_strength[material_idx] : 0.0f;
+    return WFPT_OK;
+}
+
+int wfpt_sample_normal_map(wfpt_ctx *c, const float *in4, size_t n, float *out4) {
+    if (int r = nmap_check(c, "wfpt_sample_normal_map"); r != WFPT_OK) return r;
+    const bool null_argument = (!in4 || !out4) && n; // (reported by probe, ahead of a missing binding)
+    if (!null_argument && !mapped(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_normal_map: no normal map is bound");
+    return probe(c, "wfpt_sample_normal_map", in4, 4, out4, 4, n, true, [&](const float *d_in, float *d_out) {
+        return launch_nmap_sample(c->scene.prim_geom, c->scene.shade_rec, nmap_scene(c), c->scene.n_spheres, d_in, d_out,
+                                  static_cast<uint32_t>(n), c->stream.get());
+    });
+}
+
+// Steps B-F on the host, from the function the kernels call (this file's host side is compiled without contraction, as the device side)
+int wfpt_mapped_normal_host(const float *in22, size_t n, float *out4) {
+    if ((!in22 || !out4) && n) return WFPT_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = in22 + 22u * i;
+        float3_ nn;
+        const uint32_t code = mapped_normal({r[0], r[1], r[2]}, {r[3], r[4], r[5]}, {r[6], r[7], r[8]}, {r[9], r[10], r[11]}, r + 12,
+                                            {r[18], r[19], r[20]}, r[21], nn);
+        float *o = out4 + 4u * i;
+        o[0] = nn.x; o[1] = nn.y; o[2] = nn.z; o[3] = static_cast<float>(code);
+    }
+    return WFPT_OK;
 }
 
 // ---------------------------------------------------------------- microfacet metals (include/wfpt.h "Microfacet metals")
@@ -3558,7 +3724,7 @@ static int apply_roughness(wfpt_ctx *c, const char *who, std::vector<float> &&al
     if (prim.get())
         if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
-    commit_hit_table(c, std::move(table), prim.get() != nullptr || shading(c));
+    commit_hit_table(c, std::move(table), prim.get() != nullptr || shading(c) || mapped(c));
     c->mf_prim = std::move(prim); // (the kernel takes it from the context at each launch; the graphs that hold the old one are dropped)
     c->mf_glass = glass;
     c->mf_alpha = std::move(alpha);

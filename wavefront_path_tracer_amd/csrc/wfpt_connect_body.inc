@@ -1,8 +1,9 @@
-// The body of the connect kernels, included into connect_kernel, connect_power_kernel, connect_analytic_kernel and connect_shading_kernel (wfpt_kernels.hip): one text, so that each kernel
+// The body of the connect kernels, included into connect_kernel, connect_power_kernel, connect_analytic_kernel, connect_shading_kernel and connect_nmap_kernel (wfpt_kernels.hip): one text, so that each kernel
 // is compiled from its own statements and connect_kernel keeps its instructions whatever the other one gains (a shared function is optimised
 // on its own first, and then schedules differently). In scope: the kernel's template parameters Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS and
-// MIS, the constants POWER, ANALYTIC and SHADING, the argument `a` (ConnectArgs), `ld` (LightDist; read where POWER is set only), `lt`
-// (LightTable; read where ANALYTIC is set only) and `sn` (the per-primitive normal rows; read where SHADING is set only).
+// MIS, the constants POWER, ANALYTIC, SHADING and NMAP, the argument `a` (ConnectArgs), `ld` (LightDist; read where POWER is set only), `lt`
+// (LightTable; read where ANALYTIC is set only), `sn` (the per-primitive normal rows; read where SHADING is set only) and `nm` (NmapScene;
+// read where NMAP is set only).
     extern __shared__ float4 lds[];
     WFPT_SCENE_LDS(LDS_SCENE, s_stack); // (HBM-resident scenes: s_stack holds the walk's stack columns)
     const float4 *g_nodes = reinterpret_cast<const float4 *>(a.scene.nodes);
@@ -81,6 +82,7 @@
                     // the normal scatter() uses, never flipped
                     n = PRIM == 0 ? normalize3({p.x - rec0.x, p.y - rec0.y, p.z - rec0.z}) : float3_{rec0.x, rec0.y, rec0.z};
                     if (SHADING) shading_normal_at(a.scene.prim_geom, sn, prim, p, {rec0.x, rec0.y, rec0.z}, n); // (triangles: n is the stored normal here)
+                    if (NMAP) mapped_normal_at(nm, a.scene.prim_geom, prim, p, {rec0.x, rec0.y, rec0.z}, n);
                     uint32_t rng = jenkins_hash(pixel_idx ^ jenkins_hash(frame0 + smp)); // init_rng((x, y), (W, H), frame): x + y W is the pixel
                     rng = jenkins_hash(rng ^ (0x9E3779B9u * (a.wavefront + 1u)));
                     u0 = rng_next_float(rng);

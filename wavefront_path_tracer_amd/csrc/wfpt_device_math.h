@@ -254,6 +254,45 @@ __host__ __device__ __forceinline__ bool shading_normal(float3_ p, float3_ v0, f
     return !keep;
 }
 
+// ---------------- normal maps (WFPT_FLAG_NORMAL_MAPS; include/wfpt.h "Normal maps") ----------------
+// Steps B-F of the header in its operation order, the same rules again (no fma); restated bit for bit by tests/normal_map_ref.py. The
+// normal a mapped hit scatters about: the texel c (rgb = 0.5 + 0.5 * the tangent-space normal) at strength s, carried into the world by
+// the frame (t, bt, ns) -- t the direction of dP/du of the triangle (e1, e2) with corner UVs uv[0..5], made orthogonal to the shading
+// normal ns, bt = +-cross(ns, t) on dP/dv's side. Never flipped against the stored normal ng. Returns the header's probe code: 0 mapped,
+// 1 identity (ns bit for bit), 2 no tangent frame (ns), 3 rejected (ns).
+__host__ __device__ __forceinline__ uint32_t mapped_normal(float3_ ng, float3_ ns, float3_ e1, float3_ e2, const float *uv, float3_ c, float s,
+                                                           float3_ &n) {
+    n = ns;
+    // B. the tangent-space normal
+    const float x = (2.0f * c.x - 1.0f) * s, y = (2.0f * c.y - 1.0f) * s, z = 2.0f * c.z - 1.0f;
+    if (x == 0.0f && y == 0.0f) return 1u;
+    // C. dP/du and dP/dv up to |det|
+    const float du1 = uv[2] - uv[0], dv1 = uv[3] - uv[1], du2 = uv[4] - uv[0], dv2 = uv[5] - uv[1];
+    const float det = du1 * dv2 - du2 * dv1;
+    if (!(det > 0.0f) && !(det < 0.0f)) return 2u; // (zero or NaN)
+    const float sg = det > 0.0f ? 1.0f : -1.0f;
+    const float3_ T = {(e1.x * dv2 - e2.x * dv1) * sg, (e1.y * dv2 - e2.y * dv1) * sg, (e1.z * dv2 - e2.z * dv1) * sg};
+    const float3_ Bt = {(e2.x * du1 - e1.x * du2) * sg, (e2.y * du1 - e1.y * du2) * sg, (e2.z * du1 - e1.z * du2) * sg};
+    // D. Gram-Schmidt against ns
+    const float k = dot3(ns, T);
+    const float3_ tt = {T.x - ns.x * k, T.y - ns.y * k, T.z - ns.z * k};
+    const float l2 = dot3(tt, tt);
+    if (!(l2 > 0.0f) || !(l2 < __builtin_inff())) return 2u;
+    const float il = 1.0f / sqrt_(l2);
+    const float3_ t = {tt.x * il, tt.y * il, tt.z * il};
+    // E. the bitangent, on Bt's side (mirrored UVs keep their handedness)
+    float3_ bt = {ns.y * t.z - ns.z * t.y, ns.z * t.x - ns.x * t.z, ns.x * t.y - ns.y * t.x};
+    if (dot3(bt, Bt) < 0.0f) bt = {-bt.x, -bt.y, -bt.z};
+    // F. into the world
+    const float3_ m = {(t.x * x + bt.x * y) + ns.x * z, (t.y * x + bt.y * y) + ns.y * z, (t.z * x + bt.z * y) + ns.z * z};
+    const float l2m = dot3(m, m);
+    const float ilm = 1.0f / sqrt_(l2m);
+    const float3_ nm = {m.x * ilm, m.y * ilm, m.z * ilm};
+    if (!(l2m > 0.0f && l2m < __builtin_inff() && dot3(nm, ng) > 0.0f)) return 3u;
+    n = nm;
+    return 0u;
+}
+
 // index of a texel coordinate c0 (floor of a float, expected in -1 .. n-1) and of c0 + 1, both wrapped into 0 .. n-1; NaN reads index n-1
 __host__ __device__ __forceinline__ void wrap_pair(float c0, float fn, uint32_t n, uint32_t &i0, uint32_t &i1) {
     const int k = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c0, -1.0f), fn - 1.0f)); // -1 .. n-1

@@ -633,6 +633,18 @@ struct MicrofacetArgs {
     uint32_t wavefront;
 };
 
+// Normal maps (WFPT_FLAG_NORMAL_MAPS contexts that hold a binding, include/wfpt.h "Normal maps"), as the kernels of a mapped context read
+// them: per PRIMITIVE, in the order the device holds them, {texture slot or kNoTexture, UV row, the strength's bits, 0} -- the bindings
+// resolved through each primitive's material_idx and _pad on the host (build_nmap_tables), as TexScene::prim_tex is -- the
+// WFPT_MAX_TEXTURES descriptors, the UV rows (null = (0, 0) at every corner) and the shading-normal pass's per-primitive rows of corner
+// normals (null = no table is set: ns is the stored normal). Passed by value, as TexScene.
+struct NmapScene {
+    const uint4 *prim_map;
+    const TexDev *tex;
+    const float *uv6;
+    const float4 *normals;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -834,8 +846,11 @@ hipError_t launch_mis_weight(const MisArgs &m, const float4 *shade_rec, const ui
 // analytic (null = none): the ANALYTIC variants with this table (never with envs or power)
 // shading (null = none): the SHADING variants with these per-primitive normal rows (triangles; never with power or analytic): the
 // receiver's normal is the shading normal
+// nmap (null = none): the NMAP variants (connect_nmap_kernel; triangles; never with power or analytic; `shading` is ignored, nmap->normals
+// names the rows): the receiver's normal is the mapped normal
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs = false, bool mis = false,
-                          const LightDist *power = nullptr, const LightTable *analytic = nullptr, const float4 *shading = nullptr);
+                          const LightDist *power = nullptr, const LightTable *analytic = nullptr, const float4 *shading = nullptr,
+                          const NmapScene *nmap = nullptr);
 hipError_t launch_shading_normal(const ShadingArgs &a, uint32_t grid, hipStream_t s);
 // wfpt_sample_shading_normal: n rows of (p.xyz | the primitive's bits) -> (ns.xyz | 1 where it fell back to the stored normal, else 0), one
 // thread per row; a primitive outside the scene answers (0, 0, 0, 1)
@@ -852,6 +867,15 @@ hipError_t launch_rough_glass(const MicrofacetArgs &a, uint32_t grid, hipStream_
 // wfpt_sample_rough_dielectric: n rows of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0) -> (h.xyz | 2 fell back, 1 dead, else
 // 0 | weight.rgb | 1 refracted, 0 reflected), one thread per row; both buffers 16-byte aligned
 hipError_t launch_rough_glass_sample(const float *in16, float *out8, uint32_t n, hipStream_t s);
+// The record pass of a mapped context (include/wfpt.h "Normal maps"), in the place of launch_shading_normal (a.mf_prim null:
+// shading_nmap_kernel), launch_microfacet (microfacet_nmap_kernel) or, with glass, launch_rough_glass (rough_glass_nmap_kernel): the same
+// walk, table and slot rewrite; the normal of every record, and the normal a rough hit samples about, is the mapped normal. A hit whose
+// material has no map gets bit for bit the record of the kernel replaced. a.normals is ignored: nm.normals names the rows (or null).
+hipError_t launch_nmap_record(const MicrofacetArgs &a, const NmapScene &nm, bool glass, uint32_t grid, hipStream_t s);
+// wfpt_sample_normal_map: n rows of (p.xyz | the primitive's bits) -> (n.xyz | the header's probe code), one thread per row; a primitive
+// outside the scene answers (0, 0, 0, 5)
+hipError_t launch_nmap_sample(const float4 *prim_geom, const float4 *shade_rec, const NmapScene &nm, uint32_t n_prims, const float *in4,
+                              float *out4, uint32_t n, hipStream_t s);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the
@@ -889,8 +913,9 @@ hipError_t launch_rays_from_aos(const RayQueue &q, const wfpt_ray *in, uint32_t 
 // AOV pass of one batch: `grid` persistent workgroups of kExtendThreads (at most the extend grid: the four-wide walk's stack spill area is
 // sized for it)
 // shading (null = none): aov_shading_kernel with these per-primitive normal rows (triangles): the normal sum takes the shading normal
+// nmap (null = none): aov_nmap_kernel (triangles; `shading` is ignored, nmap->normals names the rows): the normal sum takes the mapped normal
 hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env = nullptr, const TexScene *tex = nullptr,
-                      const float4 *shading = nullptr);
+                      const float4 *shading = nullptr, const NmapScene *nmap = nullptr);
 hipError_t aov_prepare(const SceneDev &scene); // raises the AOV kernels' dynamic-LDS limit where the scene needs more than 64 KiB
 hipError_t launch_aov_resolve(const float *sums, size_t plane, uint32_t which, uint32_t n_samples, uint32_t *out, size_t n_words, hipStream_t s);
 hipError_t launch_denoise_prepare(const DenoiseArgs &a, hipStream_t s);

@@ -2419,6 +2419,101 @@ __global__ __launch_bounds__(256) void rough_glass_sample_kernel(const float *in
 }
 
 // ================================================================================================
+// normal maps (WFPT_FLAG_NORMAL_MAPS; include/wfpt.h "Normal maps")
+// ================================================================================================
+// The normal shade scatters about at point p of triangle `prim` with stored normal ng on a mapped context: ns -- shading_normal with the
+// primitive's rows where the context holds a table of corner normals (block-uniform), ng otherwise -- and, where the primitive's material
+// is bound to a map, steps A-F about it: texture_factor's UV gather and lookup, then mapped_normal. Returns the header's probe code
+// (4: the material has no map, n = ns).
+__device__ __forceinline__ uint32_t mapped_normal_at(const NmapScene &nm, const float4 *prim_geom, uint32_t prim, float3_ p, float3_ ng, float3_ &n) {
+    const float4 g0 = prim_geom[3u * prim], g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+    const float3_ v0 = {g0.x, g0.y, g0.z}, e1 = {g1.x, g1.y, g1.z}, e2 = {g2.x, g2.y, g2.z};
+    const uint4 e = nm.prim_map[prim];
+    float3_ ns = ng;
+    if (nm.normals) {
+        const float4 r0 = nm.normals[3u * prim], r1 = nm.normals[3u * prim + 1u], r2 = nm.normals[3u * prim + 2u];
+        shading_normal(p, v0, e1, e2, ng, {r0.x, r0.y, r0.z}, {r1.x, r1.y, r1.z}, {r2.x, r2.y, r2.z}, ns);
+    }
+    n = ns;
+    if (e.x == kNoTexture) return 4u;
+    float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (nm.uv6) {
+        const float2 *row = reinterpret_cast<const float2 *>(nm.uv6 + 6u * static_cast<size_t>(e.y));
+        const float2 q0 = row[0], q1 = row[1], q2 = row[2];
+        uv[0] = q0.x; uv[1] = q0.y; uv[2] = q1.x; uv[3] = q1.y; uv[4] = q2.x; uv[5] = q2.y;
+    }
+    float u, v;
+    triangle_uv(p, v0, e1, e2, uv, u, v);                    // A.
+    const float3_ c = tex_lookup(nm.tex[e.x], u, v);
+    return mapped_normal(ng, ns, e1, e2, uv, c, __uint_as_float(e.z), n); // B-F.
+}
+
+// The record pass of a mapped context, one text for the three kernels below. KIND 0: shading_normal_kernel's records; 1: microfacet_kernel's;
+// 2: rough_glass_kernel's -- each with the mapped normal where those kernels have the shading (or stored) normal, the same draws from the
+// same streams, and the same slot rewrite.
+template <int KIND>
+__device__ __forceinline__ void nmap_record_body(const MicrofacetArgs &a, const NmapScene &nm) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    const uint32_t frame = uniform(a.w.ctl->frame.frame) + blockIdx.y; // (as microfacet_kernel takes it)
+    for_each_shaded_hit<true>(a.w, s, [&](size_t slot, const Hit &h) {
+        const float4 rec0 = a.w.shade_rec[3u * h.prim], rec1 = a.w.shade_rec[3u * h.prim + 1u], rec2 = a.w.shade_rec[3u * h.prim + 2u];
+        float3_ n;
+        mapped_normal_at(nm, a.prim_geom, h.prim, h.p, {rec0.x, rec0.y, rec0.z}, n);
+        float4 o0 = make_float4(n.x, n.y, n.z, rec0.w), o1 = rec1, o2 = rec2;
+        if (KIND != 0) {
+            const float alpha = a.mf_prim[h.prim];
+            if (alpha > 0.0f) {
+                const bool glass = KIND == 2 && __float_as_uint(rec2.x) == 2u;
+                uint32_t rng = jenkins_hash(h.pixel_idx ^ jenkins_hash(frame));
+                rng = jenkins_hash(rng ^ ((glass ? kRoughGlassStream : 0xC2B2AE35u) * (a.wavefront + 1u)));
+                const float u1 = rng_next_float(rng);
+                const float u2 = rng_next_float(rng);
+                if (glass) {
+                    const float u3 = rng_next_float(rng);
+                    const RoughGlassSample gs = rough_glass_sample(h.d, n, u1, u2, u3, alpha, rec1.w, {rec1.x, rec1.y, rec1.z});
+                    if (!gs.fell) {
+                        o0 = make_float4(gs.h.x, gs.h.y, gs.h.z, 0.0f);
+                        o1 = make_float4(gs.weight.x, gs.weight.y, gs.weight.z, rec1.w);
+                        o2.x = __uint_as_float(1u);
+                    }
+                } else {
+                    const MicrofacetSample ms = microfacet_sample(h.d, n, u1, u2, alpha, {rec1.x, rec1.y, rec1.z});
+                    if (!ms.fell) {
+                        o0 = make_float4(ms.m.x, ms.m.y, ms.m.z, 0.0f);
+                        o1 = make_float4(ms.weight.x, ms.weight.y, ms.weight.z, rec1.w);
+                    }
+                }
+            }
+        }
+        float4 *out = a.table + 3u * slot;
+        out[0] = o0;
+        out[1] = o1;
+        out[2] = o2;
+        a.rec_out[2u * slot + 1u].w = __uint_as_float(static_cast<uint32_t>(slot)); // (3 * slot stays below 2^32: wfpt_create's size check)
+    });
+}
+__global__ __launch_bounds__(kConsumerThreads) void shading_nmap_kernel(MicrofacetArgs a, NmapScene nm) { nmap_record_body<0>(a, nm); }
+__global__ __launch_bounds__(kConsumerThreads) void microfacet_nmap_kernel(MicrofacetArgs a, NmapScene nm) { nmap_record_body<1>(a, nm); }
+__global__ __launch_bounds__(kConsumerThreads) void rough_glass_nmap_kernel(MicrofacetArgs a, NmapScene nm) { nmap_record_body<2>(a, nm); }
+
+// wfpt_sample_normal_map: mapped_normal_at for caller rows of (p | the primitive's bits), one thread per row
+__global__ __launch_bounds__(256) void nmap_sample_kernel(const float4 *prim_geom, const float4 *shade_rec, NmapScene nm, uint32_t n_prims,
+                                                          const float *in4, float *out4, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *row = in4 + 4u * static_cast<size_t>(i);
+    const uint32_t prim = __float_as_uint(row[3]);
+    float3_ nn = {0.0f, 0.0f, 0.0f};
+    uint32_t code = 5u;
+    if (prim < n_prims) {
+        const float4 rec0 = shade_rec[3u * prim];
+        code = mapped_normal_at(nm, prim_geom, prim, {row[0], row[1], row[2]}, {rec0.x, rec0.y, rec0.z}, nn);
+    }
+    float *out = out4 + 4u * static_cast<size_t>(i);
+    out[0] = nn.x; out[1] = nn.y; out[2] = nn.z; out[3] = static_cast<float>(code);
+}
+
+// ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
 // The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
@@ -3983,8 +4078,10 @@ __global__ void rays_from_aos_kernel(RayQueue q, const wfpt_ray *in, uint32_t n)
 // it takes 86-110 and runs 4 waves per SIMD.)
 // SHADING (aov_shading_kernel; WFPT_FLAG_SHADING_NORMALS contexts that hold a table, triangles): the normal sum takes the shading normal
 // of the primary hit (`sn`: the per-primitive normal rows) in the stored normal's place.
-template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX = false, bool SHADING = false>
-__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, const TexScene &ts = TexScene{}, const float4 *sn = nullptr) {
+// NMAP (aov_nmap_kernel; WFPT_FLAG_NORMAL_MAPS contexts that hold a binding, triangles): the normal sum takes the mapped normal (`nm`).
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX = false, bool SHADING = false, bool NMAP = false>
+__device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, const TexScene &ts = TexScene{}, const float4 *sn = nullptr,
+                                         const NmapScene &nm = NmapScene{}) {
     extern __shared__ float4 lds[];
     const uint32_t n_slots = a.gx * a.gy * 64u;
     const uint32_t n_items = (n_slots + kExtendThreads - 1u) / kExtendThreads;
@@ -4025,6 +4122,7 @@ __device__ __forceinline__ void aov_body(const AovArgs &a, const EnvDev &env, co
                 float3_ n = {rec0.x, rec0.y, rec0.z};
                 if (PRIM == 0) n = normalize3({(r.ox + t * r.dx) - rec0.x, (r.oy + t * r.dy) - rec0.y, (r.oz + t * r.dz) - rec0.z});
                 if (SHADING) shading_normal_at(a.scene.prim_geom, sn, prim, {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, {rec0.x, rec0.y, rec0.z}, n);
+                if (NMAP) mapped_normal_at(nm, a.scene.prim_geom, prim, {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, {rec0.x, rec0.y, rec0.z}, n);
                 float3_ tc;
                 if (TEX && texture_factor(ts, a.scene.prim_geom, a.scene.shade_rec, PRIM, prim,
                                           {r.ox + t * r.dx, r.oy + t * r.dy, r.oz + t * r.dz}, tc)) { // the textured albedo tex * albedo
@@ -4083,6 +4181,12 @@ __global__ __launch_bounds__(kExtendThreads) void aov_tex_kernel(AovArgs a, EnvD
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX>
 __global__ __launch_bounds__(kExtendThreads) void aov_shading_kernel(AovArgs a, EnvDev env, TexScene ts, const float4 *sn) {
     aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, TEX, true>(a, env, ts, sn);
+}
+
+// WFPT_FLAG_NORMAL_MAPS with a binding (triangle contexts): the normal sum takes the mapped normal (every ENV and TEX case)
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool ENV, bool TEX>
+__global__ __launch_bounds__(kExtendThreads) void aov_nmap_kernel(AovArgs a, EnvDev env, TexScene ts, NmapScene nm) {
+    aov_body<Trail, PRIM, LDS_SCENE, EXACT, ENV, TEX, false, true>(a, env, ts, nullptr, nm);
 }
 
 // ================================================================================================
@@ -4269,7 +4373,8 @@ __device__ __forceinline__ bool sample_env(const EnvDist &d, float3_ n, float u1
 // the share of its own branch; the point is stored as above. The sampler form is the map's, with the effective share and 12 floats a row.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) {
-    constexpr bool POWER = false, ANALYTIC = false, SHADING = false;
+    constexpr bool POWER = false, ANALYTIC = false, SHADING = false, NMAP = false;
+    const NmapScene nm{};
     const LightDist ld{};
     const LightTable lt{};
     const float4 *const sn = nullptr;
@@ -4279,7 +4384,8 @@ __global__ __launch_bounds__(kExtendThreads) void connect_kernel(ConnectArgs a) 
 // nfi; nothing else differs. The distribution is a second argument: connect_kernel keeps its name, its arguments and its instructions.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectArgs a, LightDist ld) {
-    constexpr bool ENVS = false, POWER = true, ANALYTIC = false, SHADING = false;
+    constexpr bool ENVS = false, POWER = true, ANALYTIC = false, SHADING = false, NMAP = false;
+    const NmapScene nm{};
     const LightTable lt{};
     const float4 *const sn = nullptr;
 #include "wfpt_connect_body.inc"
@@ -4289,7 +4395,8 @@ __global__ __launch_bounds__(kExtendThreads) void connect_power_kernel(ConnectAr
 // occludes); under MIS an analytic sample is not weighed. The table is a second argument, as the distribution above.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_analytic_kernel(ConnectArgs a, LightTable lt) {
-    constexpr bool ENVS = false, POWER = false, ANALYTIC = true, SHADING = false;
+    constexpr bool ENVS = false, POWER = false, ANALYTIC = true, SHADING = false, NMAP = false;
+    const NmapScene nm{};
     const LightDist ld{};
     const float4 *const sn = nullptr;
 #include "wfpt_connect_body.inc"
@@ -4300,9 +4407,21 @@ __global__ __launch_bounds__(kExtendThreads) void connect_analytic_kernel(Connec
 // form takes its normal from the caller's rows and is connect_kernel's.
 template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
 __global__ __launch_bounds__(kExtendThreads) void connect_shading_kernel(ConnectArgs a, const float4 *sn) {
-    constexpr bool POWER = false, ANALYTIC = false, SHADING = true;
+    constexpr bool POWER = false, ANALYTIC = false, SHADING = true, NMAP = false;
+    const NmapScene nm{};
     const LightDist ld{};
     const LightTable lt{};
+#include "wfpt_connect_body.inc"
+}
+// NMAP (WFPT_FLAG_NORMAL_MAPS contexts that hold a binding; triangles; never with POWER or ANALYTIC): the receiver's normal n is the mapped
+// normal of the hit (mapped_normal_at with `nm`) -- what shade will scatter about -- in both the emitter and the map branch; nothing else
+// differs. The tables are a second argument, as the rows above.
+template <typename Trail, int PRIM, bool LDS_SCENE, bool EXACT, bool TEX, bool ENVS, bool MIS>
+__global__ __launch_bounds__(kExtendThreads) void connect_nmap_kernel(ConnectArgs a, NmapScene nm) {
+    constexpr bool POWER = false, ANALYTIC = false, SHADING = false, NMAP = true;
+    const LightDist ld{};
+    const LightTable lt{};
+    const float4 *const sn = nullptr;
 #include "wfpt_connect_body.inc"
 }
 
@@ -5103,6 +5222,24 @@ hipError_t launch_rough_glass_sample(const float *in16, float *out8, uint32_t n,
     return hipGetLastError();
 }
 
+hipError_t launch_nmap_record(const MicrofacetArgs &a, const NmapScene &nm, bool glass, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    if (!nm.prim_map || !nm.tex || !a.table || !a.rec_out || (glass && !a.mf_prim)) return hipErrorInvalidValue;
+    const dim3 g(grid, a.w.batch.n), b(kConsumerThreads);
+    if (!a.mf_prim) hipLaunchKernelGGL(shading_nmap_kernel, g, b, 0, s, a, nm);
+    else if (glass) hipLaunchKernelGGL(rough_glass_nmap_kernel, g, b, 0, s, a, nm);
+    else hipLaunchKernelGGL(microfacet_nmap_kernel, g, b, 0, s, a, nm);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmap_sample(const float4 *prim_geom, const float4 *shade_rec, const NmapScene &nm, uint32_t n_prims, const float *in4,
+                              float *out4, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!nm.prim_map || !nm.tex) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmap_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, prim_geom, shade_rec, nm, n_prims, in4, out4, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_emission(const EmissionArgs &a, EmissionKind kind, uint32_t grid, hipStream_t s, float q, const LightDist *ld) {
     if (grid == 0) return hipSuccess;
     if (kind == kEmitWeighedPower) {
@@ -5238,20 +5375,33 @@ struct AovShadingK {
     }
 };
 using AovShading = Family<AovShadingK, Bool, Bool>;
+using AovNmapFn = void (*)(AovArgs, EnvDev, TexScene, NmapScene);
+struct AovNmapK {
+    template <bool ENV, bool TEX, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static AovNmapFn get() {
+        if constexpr (PRIM == 1) return aov_nmap_kernel<Trail, PRIM, LDS_SCENE, EXACT, ENV, TEX>;
+        else return nullptr;
+    }
+};
+using AovNmap = Family<AovNmapK, Bool, Bool>;
 uint32_t aov_lds_bytes(const SceneDev &sc) { return sc.lds_scene ? scene_lds_bytes(sc.n_nodes, sc.n_spheres, sc.prim_kind) : kStackColumnBytes; }
 } // namespace
 
 hipError_t aov_prepare(const SceneDev &scene) {
     if (const hipError_t e = allow_dynamic_lds<Aov, AovEnv, AovTex>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)); e != hipSuccess) return e;
-    return scene.prim_kind == 1 ? allow_dynamic_lds<AovShading>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
+    return scene.prim_kind == 1 ? allow_dynamic_lds<AovShading, AovNmap>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
 }
 
-hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex, const float4 *shading) {
+hipError_t launch_aov(const AovArgs &a, uint32_t grid, hipStream_t s, const EnvDev *env, const TexScene *tex, const float4 *shading,
+                      const NmapScene *nmap) {
     if (grid == 0 || a.n == 0 || a.gx * a.gy == 0) return hipSuccess;
-    if (shading && a.scene.prim_kind != 1) return hipErrorInvalidValue;
+    if ((shading || nmap) && a.scene.prim_kind != 1) return hipErrorInvalidValue;
+    if (nmap && (!nmap->prim_map || !nmap->tex)) return hipErrorInvalidValue;
     const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
     const dim3 g(grid), b(kExtendThreads);
-    if (shading)
+    if (nmap)
+        hipLaunchKernelGGL(AovNmap::pick(a.scene, exact, lds, env != nullptr, tex != nullptr), g, b, aov_lds_bytes(a.scene), s, a,
+                           env ? *env : EnvDev{}, tex ? *tex : TexScene{}, *nmap);
+    else if (shading)
         hipLaunchKernelGGL(AovShading::pick(a.scene, exact, lds, env != nullptr, tex != nullptr), g, b, aov_lds_bytes(a.scene), s, a,
                            env ? *env : EnvDev{}, tex ? *tex : TexScene{}, shading);
     else if (tex) hipLaunchKernelGGL(AovTex::pick(a.scene, exact, lds, env != nullptr), g, b, aov_lds_bytes(a.scene), s, a, env ? *env : EnvDev{}, *tex);
@@ -5291,24 +5441,34 @@ struct ConnectShadingK {
     }
 };
 using ConnectShading = Family<ConnectShadingK, Bool, Bool, Bool>;
+using ConnectNmapFn = void (*)(ConnectArgs, NmapScene);
+struct ConnectNmapK {
+    template <bool TEX, bool ENVS, bool MIS, typename Trail, int PRIM, bool LDS_SCENE, bool EXACT> static ConnectNmapFn get() {
+        if constexpr (PRIM == 1) return connect_nmap_kernel<Trail, PRIM, LDS_SCENE, EXACT, TEX, ENVS, MIS>;
+        else return nullptr;
+    }
+};
+using ConnectNmap = Family<ConnectNmapK, Bool, Bool, Bool>;
 } // namespace
 
 hipError_t connect_prepare(const SceneDev &scene) {
     if (const hipError_t e = allow_dynamic_lds<Connect, ConnectPower, ConnectAnalytic>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)); e != hipSuccess)
         return e;
-    return scene.prim_kind == 1 ? allow_dynamic_lds<ConnectShading>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
+    return scene.prim_kind == 1 ? allow_dynamic_lds<ConnectShading, ConnectNmap>(scene, scene.lds_scene != 0, aov_lds_bytes(scene)) : hipSuccess;
 }
 
 hipError_t launch_connect(const ConnectArgs &a, uint32_t grid, hipStream_t s, bool textured, bool envs, bool mis, const LightDist *power,
-                          const LightTable *analytic, const float4 *shading) {
+                          const LightTable *analytic, const float4 *shading, const NmapScene *nmap) {
     if (grid == 0 || (a.n_lights == 0 && !envs && !analytic)) return hipSuccess;
     if (analytic && (envs || power || !analytic->rows || analytic->n == 0)) return hipErrorInvalidValue;
     if (mis && !a.origin && !a.sample_in) return hipErrorInvalidValue; // (the render form stores every diffuse hit's point)
     if (power && (envs || !power->cdf || power->total == 0)) return hipErrorInvalidValue;
-    if (shading && (power || analytic || a.scene.prim_kind != 1 || a.sample_in)) return hipErrorInvalidValue;
+    if ((shading || nmap) && (power || analytic || a.scene.prim_kind != 1 || a.sample_in)) return hipErrorInvalidValue;
+    if (nmap && (!nmap->prim_map || !nmap->tex)) return hipErrorInvalidValue;
     const bool exact = a.scene.exact != 0, lds = a.scene.lds_scene != 0;
     const dim3 g(grid), b(kExtendThreads);
-    if (shading) hipLaunchKernelGGL(ConnectShading::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a, shading);
+    if (nmap) hipLaunchKernelGGL(ConnectNmap::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a, *nmap);
+    else if (shading) hipLaunchKernelGGL(ConnectShading::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a, shading);
     else if (analytic) hipLaunchKernelGGL(ConnectAnalytic::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *analytic);
     else if (power) hipLaunchKernelGGL(ConnectPower::pick(a.scene, exact, lds, textured, mis), g, b, aov_lds_bytes(a.scene), s, a, *power);
     else hipLaunchKernelGGL(Connect::pick(a.scene, exact, lds, textured, envs, mis), g, b, aov_lds_bytes(a.scene), s, a);

@@ -383,6 +383,25 @@ class PathTracer {
         check(wfpt_sample_rough_dielectric(ctx_, in16.data(), in16.size() / 16, out.data()));
         return out;
     }
+    // Normal maps (WFPT_FLAG_NORMAL_MAPS, include/wfpt.h "Normal maps"): a material takes a texture slot as its tangent-space normal map
+    // (rgb = 0.5 + 0.5 n, green = +v); slot -1 unbinds.
+    void bind_normal_map(uint32_t material_idx, int32_t slot, float strength = 1.0f) { check(wfpt_bind_normal_map(ctx_, material_idx, slot, strength)); }
+    std::pair<int32_t, float> normal_map(uint32_t material_idx) { // (slot or -1, strength)
+        int32_t slot = -1;
+        float strength = 0.0f;
+        check(wfpt_get_normal_map(ctx_, material_idx, &slot, &strength));
+        return {slot, strength};
+    }
+    std::vector<float> sample_normal_map(const std::vector<float> &in4) { // (p.xyz | the triangle's bits) -> (n.xyz | code 0..5)
+        std::vector<float> out(in4.size() / 4 * 4);
+        check(wfpt_sample_normal_map(ctx_, in4.data(), in4.size() / 4, out.data()));
+        return out;
+    }
+    static std::vector<float> mapped_normal_host(const std::vector<float> &in22) { // steps B-F on the host: rows of 22 -> (n.xyz | code 0..3)
+        std::vector<float> out(in22.size() / 22 * 4);
+        if (wfpt_mapped_normal_host(in22.data(), in22.size() / 22, out.data()) != WFPT_OK) throw Error(WFPT_ERR_INVALID_ARGUMENT, "wfpt_mapped_normal_host");
+        return out;
+    }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
