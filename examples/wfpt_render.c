@@ -4,7 +4,7 @@
  *   gcc -std=c99 -O1 -Iinclude examples/wfpt_render.c -Lwavefront_path_tracer_amd -lwfpt \
  *       -Wl,-rpath,$PWD/wavefront_path_tracer_amd -lm -o wfpt_render
  *   ./wfpt_render out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha]
- *                 [--normal-map strength]] [--adaptive]
+ *                 [--roughness-map] [--normal-map strength]] [--adaptive]
  * --adaptive: a WFPT_FLAG_ADAPTIVE context rendered with wfpt_render_adaptive (at most spp passes, an update every 8) at the default
  * parameters; the image written is the mean (each pixel divided by its own sample count).
  * --obj-normals mesh.obj: instead of the book's scene, the triangles of a Wavefront OBJ file (grey Lambertian, about the origin, seen from
@@ -13,7 +13,10 @@
  * WFPT_FLAG_MICROFACET as well, and wfpt_set_roughness.
  * --rough-glass alpha (after --obj-normals mesh.obj): the mesh is a white dielectric of refraction index 1.5 with the GGX roughness alpha
  * in (0, 1] -- frosted glass: WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC, and wfpt_set_roughness on the dielectric material.
- * --normal-map strength (after --obj-normals mesh.obj and its roughness option): the mesh's material takes a procedural 64 x 64 map of
+ * --roughness-map (after --roughness alpha or --rough-glass alpha): the mesh's material takes the green channel of a procedural 64 x 64
+ * map of brushed bands (factors from 0.1 to 1, a polished stripe of exact zeros) as its roughness map, through the file's `vt` UVs:
+ * WFPT_FLAG_TEXTURES | WFPT_FLAG_ROUGHNESS_MAPS as well, wfpt_set_triangle_uvs, wfpt_set_texture and wfpt_bind_roughness_map.
+ * --normal-map strength (after --obj-normals mesh.obj and its roughness options): the mesh's material takes a procedural 64 x 64 map of
  * ripples as its tangent-space normal map at that strength (> 0), through the file's `vt` UVs: WFPT_FLAG_TEXTURES |
  * WFPT_FLAG_NORMAL_MAPS as well, wfpt_set_triangle_uvs, wfpt_set_texture and wfpt_bind_normal_map.
  */
@@ -42,10 +45,14 @@ int main(int argc, char **argv) {
         argc -= 1;
     }
     float roughness = 0.0f, map_strength = 0.0f;
-    int glass = 0;
+    int glass = 0, roughness_map = 0;
     if (argc > 5 && strcmp(argv[argc - 2], "--normal-map") == 0) {
         map_strength = (float)atof(argv[argc - 1]);
         argc -= 2;
+    }
+    if (argc > 6 && strcmp(argv[argc - 1], "--roughness-map") == 0) {
+        roughness_map = 1;
+        argc -= 1;
     }
     if (argc > 5 && (strcmp(argv[argc - 2], "--roughness") == 0 || strcmp(argv[argc - 2], "--rough-glass") == 0)) {
         glass = strcmp(argv[argc - 2], "--rough-glass") == 0;
@@ -56,8 +63,8 @@ int main(int argc, char **argv) {
         obj = argv[argc - 1];
         argc -= 2;
     }
-    if (argc < 2 || ((roughness != 0.0f || map_strength != 0.0f) && !obj) || (glass && !(roughness > 0.0f)) || map_strength < 0.0f) {
-        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha] [--normal-map strength]] [--adaptive]\n", argv[0]);
+    if (argc < 2 || ((roughness != 0.0f || map_strength != 0.0f) && !obj) || (glass && !(roughness > 0.0f)) || map_strength < 0.0f || (roughness_map && !(roughness > 0.0f))) {
+        fprintf(stderr, "usage: %s out.ppm [width height spp bounces [device_bvh]] [--obj-normals mesh.obj [--roughness alpha | --rough-glass alpha] [--roughness-map] [--normal-map strength]] [--adaptive]\n", argv[0]);
         return 2;
     }
     const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[2]) : 400, height = argc > 3 ? (uint32_t)atoi(argv[3]) : 225;
@@ -99,7 +106,7 @@ int main(int argc, char **argv) {
         params.max_wavefronts = bounces;
         params.miss_floor = 128;
         params.flags = WFPT_FLAG_SHADING_NORMALS | (roughness > 0.0f ? WFPT_FLAG_MICROFACET : 0u) | (glass ? WFPT_FLAG_ROUGH_DIELECTRIC : 0u) | (adaptive ? WFPT_FLAG_ADAPTIVE : 0u) |
-                       (map_strength > 0.0f ? WFPT_FLAG_TEXTURES | WFPT_FLAG_NORMAL_MAPS : 0u);
+                       (map_strength > 0.0f ? WFPT_FLAG_TEXTURES | WFPT_FLAG_NORMAL_MAPS : 0u) | (roughness_map ? WFPT_FLAG_TEXTURES | WFPT_FLAG_ROUGHNESS_MAPS : 0u);
         ctx = wfpt_create_mesh(&params, tris, n_tris, &grey, 1, mesh_nodes, n_mesh_nodes, &camera, inv_proj, view);
         if (!ctx) {
             fprintf(stderr, "wfpt_create_mesh: %s\n", wfpt_last_error(NULL));
@@ -107,6 +114,20 @@ int main(int argc, char **argv) {
         }
         CHECK(wfpt_set_triangle_normals(ctx, n9, n_tris));
         if (roughness > 0.0f) CHECK(wfpt_set_roughness(ctx, 0, roughness)); /* include/wfpt.h "Microfacet metals", "Rough dielectrics" */
+        if (roughness_map) { /* include/wfpt.h "Roughness maps": slot 1's green channel scales alpha per hit; 8 bands along u, every fourth polished */
+            enum { RMAP = 64 };
+            float *rgb = (float *)calloc(3u * RMAP * RMAP, sizeof *rgb);
+            for (int row = 0; row < RMAP; ++row)
+                for (int col = 0; col < RMAP; ++col) {
+                    const int band = col / (RMAP / 8);
+                    const float u = ((float)col + 0.5f) / RMAP;
+                    rgb[3 * (row * RMAP + col) + 1] = band % 4 == 3 ? 0.0f : 0.55f + 0.45f * sinf(8.0f * 6.2831853f * u);
+                }
+            CHECK(wfpt_set_triangle_uvs(ctx, uv6, n_tris));
+            CHECK(wfpt_set_texture(ctx, 1, rgb, RMAP, RMAP, NULL));
+            CHECK(wfpt_bind_roughness_map(ctx, 0, 1, 1, WFPT_ROUGHNESS_LINEAR));
+            free(rgb);
+        }
         if (map_strength > 0.0f) { /* include/wfpt.h "Normal maps": rgb = 0.5 + 0.5 n of the height field 0.02 sin(8 2pi u) sin(8 2pi v), green = +v, row 0 = the top */
             enum { MAP = 64 };
             float *rgb = (float *)calloc(3u * MAP * MAP, sizeof *rgb);

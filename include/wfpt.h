@@ -283,7 +283,12 @@ enum {
                                         texture slot as its normal map scatters, connects and reports its AOV normal about the texel's
                                         normal carried into the triangle's tangent frame. Needs WFPT_FLAG_TEXTURES and
                                         WFPT_FLAG_SHADING_NORMALS and inherits the latter's refusals. With nothing bound the context
-                                        launches the kernels it launches without the flag, same bits. */
+                                        launches the kernels it launches without the flag, same bits. */,
+    WFPT_FLAG_ROUGHNESS_MAPS = 1u << 28 /* roughness maps on triangle meshes, see "Roughness maps" below: a material bound to a texture
+                                        slot as its roughness map is sampled, per hit, with its alpha times one channel of the texel.
+                                        Needs WFPT_FLAG_TEXTURES and WFPT_FLAG_MICROFACET and goes with everything the latter goes with;
+                                        with WFPT_FLAG_ROUGH_DIELECTRIC it acts on rough glass as well. With nothing bound, or no alpha
+                                        above 0, the context launches the kernels it launches without the flag, same bits. */
 };
 
 #define WFPT_INACTIVE_PIXEL 0xffffffffu
@@ -705,8 +710,8 @@ int wfpt_sample_environment(wfpt_ctx *ctx, const float *dirs, size_t n, float *r
  * range, a binding to an empty slot, a bad size, texel or parameter, a UV that is not finite, and a triangle whose row is >= the rows of a set
  * UV table (checked by wfpt_set_triangle_uvs and wfpt_update_scene_mesh); WFPT_ERR_UNSUPPORTED for a call that would texture a
  * WFPT_LOOP_FUSED_BINNED context (a context with a binding never runs the class-binned loop). wfpt_render_chunked* masks the flag off.
- * Out of scope: mip-mapping, bump / roughness maps, .mtl files (per-vertex normals: "Shading normals" below; normal maps: "Normal maps"
- * below). */
+ * Out of scope: mip-mapping, bump maps, .mtl files (per-vertex normals: "Shading normals" below; normal maps: "Normal maps" below;
+ * roughness maps: "Roughness maps" below). */
 #define WFPT_MAX_TEXTURES 64u
 typedef enum wfpt_texture_filter { WFPT_TEXTURE_BILINEAR = 0, WFPT_TEXTURE_NEAREST = 1 } wfpt_texture_filter;
 typedef struct wfpt_texture_params {
@@ -835,7 +840,7 @@ int wfpt_shading_normal_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *laun
  * WFPT_FLAG_LIGHT_POWER and WFPT_FLAG_ANALYTIC_LIGHTS included.
  * Rough dielectrics are a flag of their own, WFPT_FLAG_ROUGH_DIELECTRIC: see "Rough dielectrics" below.
  * Out of scope: sphere contexts (the shade step and the traversal share one prim_kind, and a sphere's record holds a centre, not a
- * normal); roughness and bump maps (normal maps: "Normal maps" below); anisotropy; multiple-scattering energy compensation (single-scatter GGX
+ * normal); bump maps (normal maps: "Normal maps" below; roughness maps: "Roughness maps" below); anisotropy; multiple-scattering energy compensation (single-scatter GGX
  * loses energy at high alpha by construction); next-event estimation or MIS at rough hits (unbiased without, and noisier); scatter
  * directions below a shading normal's geometric surface; the stage API (wfpt_kernel_run ignores roughness); wfpt_render_chunked* (the
  * flag is masked off). */
@@ -895,7 +900,7 @@ int wfpt_microfacet_timing_ms(wfpt_ctx *ctx, float *ms_total, uint32_t *launches
  * WFPT_LOOP_FUSED_BINNED context (WFPT_ERR_UNSUPPORTED for the call that would put an alpha above 0 there); masked off in
  * wfpt_render_chunked*; ignored by the stage API; the setters restart the accumulation and drop history and graphs;
  * wfpt_update_scene_mesh keeps the alphas; wfpt_update_scene to spheres is refused while an alpha is above 0.
- * Out of scope: sphere contexts; roughness and bump maps (normal maps: "Normal maps" below); anisotropy; multiple-scattering energy compensation; next-event
+ * Out of scope: sphere contexts; bump maps (normal maps: "Normal maps" below; roughness maps: "Roughness maps" below); anisotropy; multiple-scattering energy compensation; next-event
  * estimation or MIS at rough hits; radiance scaling by eta^2; absorption inside the medium; thin-walled glass; directions below a
  * shading normal's geometric surface. */
 /* steps 1-12 on the device for n caller rows in16 of (d.xyz, n.xyz, u1, u2 | u3, alpha, ior, albedo.rgb, 0, 0): rows out8 of
@@ -943,7 +948,7 @@ int wfpt_sample_rough_dielectric(wfpt_ctx *ctx, const float *in16, size_t n, flo
  * WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS; from the calls below for a context without the flag, a sphere context, a material
  * out of range, an empty slot or one out of range, a strength that is NaN, infinite or negative; WFPT_ERR_UNSUPPORTED for a binding on a
  * WFPT_LOOP_FUSED_BINNED context (a mapped context never runs the class-binned loop).
- * Out of scope: sphere contexts; per-vertex or MikkTSpace tangents; bump (height) maps; roughness maps; mip-mapping; correction of
+ * Out of scope: sphere contexts; per-vertex or MikkTSpace tangents; bump (height) maps; mip-mapping; correction of
  * scatter directions that dip below the geometric surface; the flag with WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS; .mtl files;
  * the stage API and wfpt_render_chunked*. */
 /* material `material_idx` takes the texture of `slot` as its normal map at `strength` (finite, >= 0); slot = -1 unbinds. Blocking. */
@@ -958,6 +963,61 @@ int wfpt_sample_normal_map(wfpt_ctx *ctx, const float *in4, size_t n, float *out
 /* steps B-F on the host, no GPU and no context, compiled from the function the kernels call: n rows in22 of
  * (ng.xyz, ns.xyz, e1.xyz, e2.xyz, u0 v0 u1 v1 u2 v2, c.rgb, strength) -> rows out4 of (n.xyz | code 0..3) */
 int wfpt_mapped_normal_host(const float *in22, size_t n, float *out4);
+
+/* ------------------------------------------------------------------ Roughness maps (WFPT_FLAG_ROUGHNESS_MAPS): a GGX alpha per hit on meshes
+ * On a triangle context created with WFPT_FLAG_TEXTURES | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGHNESS_MAPS a material can be bound to a
+ * texture slot (wfpt_set_texture above) as its ROUGHNESS MAP: one channel of the linear texel scales the material's alpha
+ * (wfpt_set_roughness) at every hit. With WFPT_FLAG_ROUGH_DIELECTRIC the map acts on rough glass as well. A material may hold a colour
+ * binding, a normal-map binding and a roughness binding at once, and one slot may serve all three kinds. A context is ROUGHNESS-MAPPED
+ * while an alpha is above 0 and at least one material holds a roughness binding; a binding is inert while its material's alpha is 0. With
+ * the flag and nothing bound, or bound while no alpha is above 0, the context launches exactly the kernels it launches without the flag
+ * and renders the same bits.
+ * The alpha of a hit at p of a scattering wavefront, in the arithmetic of "Microfacet metals" (IEEE f32 in the order written, no fma,
+ * min as minNum); tests/roughness_map_ref.py restates it:
+ *  R1. alpha_m is the alpha the microfacet pass reads for the hit's primitive today (the material's where the primitive is a metal or,
+ *      with WFPT_FLAG_ROUGH_DIELECTRIC, a dielectric; +0 otherwise). If !(alpha_m > 0) the hit is not rough: no lookup, the record is
+ *      what the replaced kernel writes
+ *  R2. if the hit's material has no roughness binding, alpha_h = alpha_m: the record is bit for bit the replaced kernel's
+ *  R3. (u, v) = triangle_uv(p, ...) and c = tex_lookup(the slot's texture, u, v), exactly as "Textures" and "Normal maps" step A form
+ *      them (the slot's own scale, offset and filter apply; the UVs are all zero where no UV table is set); r = min(c[channel], 1); if
+ *      the remap is WFPT_ROUGHNESS_SQUARED (glTF's perceptual roughness, alpha = r^2), r <- r r
+ *  R4. alpha_h = alpha_m r. Texels are finite and >= 0 (wfpt_set_texture's own check), so alpha_h lies in [0, alpha_m]
+ *  R5. if !(alpha_h > 0) the hit is NOT rough: it gets the record of a non-rough hit -- the primitive's own, with the shading or mapped
+ *      normal where the context has one -- so a zero texel on a metal is Shirley's mirror with the material's fuzz, and on glass the
+ *      smooth dielectric. Otherwise the hit is sampled exactly as under "Microfacet metals" and "Rough dielectrics" with alpha_h in
+ *      alpha's place (the stretch, the unstretch and a2 in G); draws, streams, the normal's source and the slot rewrite are unchanged.
+ *      There is no floor on alpha_h: any positive value is sampled, as any positive wfpt_set_roughness value is.
+ * The per-hit alpha goes into the two samplers and nowhere else. Whether a context is rough, and whether its pass is the glass one, stays
+ * decided on the host by the materials' alphas; the connect pass, the emission pass, the AOV kernel, the cost class and split-shade's
+ * lists are untouched.
+ * Device side: on a roughness-mapped context microfacet_rmap_kernel takes the place of microfacet_kernel / microfacet_nmap_kernel and
+ * rough_glass_rmap_kernel that of rough_glass_kernel / rough_glass_nmap_kernel -- same slot, same walk, same table, booked in
+ * wfpt_microfacet_timing_ms; the hit's normal is the mapped one on a mapped context, else the shading or the stored one, with the bits
+ * of the kernel replaced. A hit with both a normal map and a roughness map forms its (u, v) once.
+ * A bind or unbind restarts the accumulation and the frame counter and drops the temporal history and the captured graphs; a refused call
+ * leaves the context as it was. wfpt_clear_texture on a slot also drops the roughness bindings to it; wfpt_set_texture on a bound slot
+ * keeps them; wfpt_set_roughness and wfpt_clear_roughness keep them. wfpt_update_scene_mesh keeps the bindings of material indices below
+ * the new count; wfpt_update_scene to spheres is refused while a roughness binding is held. wfpt_render_chunked* masks the flag off; the
+ * stage API ignores it.
+ * Errors: WFPT_ERR_INVALID_ARGUMENT at wfpt_create without WFPT_FLAG_TEXTURES or WFPT_FLAG_MICROFACET; from the calls below for a context
+ * without the flag, a sphere context, a material or slot out of range, an empty slot, a channel above 2 or a remap above 1;
+ * WFPT_ERR_UNSUPPORTED for a binding on a WFPT_LOOP_FUSED_BINNED context.
+ * Out of scope: metallic maps (a per-texel material type) and emission maps; anisotropy; mip-mapping; .mtl or glTF loading; sphere
+ * contexts; next-event estimation or MIS at rough hits; a lower bound on the per-hit alpha; the stage API and wfpt_render_chunked*. */
+typedef enum wfpt_roughness_remap { WFPT_ROUGHNESS_LINEAR = 0, WFPT_ROUGHNESS_SQUARED = 1 } wfpt_roughness_remap;
+/* material `material_idx` takes channel `channel` (0, 1, 2 = r, g, b; glTF keeps roughness in g) of the texture of `slot` as its
+ * roughness map under `remap` (a wfpt_roughness_remap); slot = -1 unbinds. Blocking. */
+int wfpt_bind_roughness_map(wfpt_ctx *ctx, uint32_t material_idx, int32_t slot, uint32_t channel, uint32_t remap);
+/* the binding of a material: its slot (-1 = none), channel and remap (0 where none) */
+int wfpt_get_roughness_map(wfpt_ctx *ctx, uint32_t material_idx, int32_t *slot, uint32_t *channel, uint32_t *remap);
+/* steps R1-R4 on the device for n caller rows in4 of (p.xyz | the triangle's index in the device's order as the BITS of the fourth
+ * float), as wfpt_sample_normal_map takes them: rows out4 of (alpha_h | r | code | 0) with code 0 mapped, 1 the material has no roughness
+ * binding (alpha_h = alpha_m, r = 1), 2 the material's alpha is not above 0 (no lookup, alpha_h = +0, r = 0), 3 mapped and alpha_h is
+ * not above 0, 5 with (0, 0, 5, 0) an index outside the scene. Needs a binding. Blocking. */
+int wfpt_sample_roughness_map(wfpt_ctx *ctx, const float *in4, size_t n, float *out4);
+/* steps R3-R4 on the host, no GPU and no context, compiled from the function the kernels call: n rows in4 of (alpha_m, c.r, c.g, c.b)
+ * with one channel and remap for all -> rows out2 of (alpha_h, r) */
+int wfpt_hit_roughness_host(const float *in4, uint32_t channel, uint32_t remap, size_t n, float *out2);
 
 /* ------------------------------------------------------------------ Emission (WFPT_FLAG_EMISSION): materials that light the scene
  * A context created with WFPT_FLAG_EMISSION holds one emission colour per material, all zero at creation. A material with a non-zero colour

@@ -24,7 +24,7 @@ from . import _build
 
 __all__ = ["SPP", "SPF", "Scene", "BVHTree", "Camera", "CameraController", "ProjectionMatrix", "GPUFrameBuffer",
            "RenderParameters", "RenderProgress", "Kernel", "PathTracer", "WfptError", "workgroup_size_64",
-           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "FLAG_ROUGH_DIELECTRIC", "FLAG_NORMAL_MAPS", "mapped_normal_host", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
+           "RNG_DISPATCH", "RNG_PIXEL", "FLAG_SPLIT_SHADE", "FLAG_NO_GRAPH", "FLAG_UNFUSED", "FLAG_BINARY_BVH", "FLAG_NO_REFILL", "FLAG_NO_LDS_SCENE", "FLAG_EXACT_TRAVERSAL", "FLAG_NO_BINNING", "FLAG_BINNING", "FLAG_AOV", "AOVS", "FLAG_DENOISE", "DENOISE_DEFAULTS", "FLAG_ENVIRONMENT", "load_environment", "FLAG_TEXTURES", "MAX_TEXTURES", "load_texture", "FLAG_EMISSION", "FLAG_NEE", "FLAG_ENV_NEE", "FLAG_MIS", "FLAG_ENV_MIS", "FLAG_LIGHT_POWER", "FLAG_ANALYTIC_LIGHTS", "FLAG_SHADING_NORMALS", "FLAG_MICROFACET", "FLAG_ROUGH_DIELECTRIC", "FLAG_NORMAL_MAPS", "mapped_normal_host", "FLAG_ROUGHNESS_MAPS", "ROUGHNESS_REMAPS", "hit_roughness_host", "LIGHT", "LIGHT_POINT", "LIGHT_SPOT", "LIGHT_DIRECTIONAL", "MAX_LIGHTS", "FLAG_NO_TILE_LISTS", "TILE_LIST_CAP", "TILE_NO_LIST", "tile_lists_host", "nodes_ch", "TEMPORAL_DEFAULTS", "TEMPORAL_OUTPUTS", "STAGES", "lib", "build",
            "tonemap_rgb8", "selftest_math", "device_count"]
 
 SPP = 10  # wavefront_common/src/parameters.rs:4
@@ -67,6 +67,8 @@ FLAG_MICROFACET = 1 << 25
 FLAG_ROUGH_DIELECTRIC = 1 << 26
 # tangent-space normal maps on triangle meshes (include/wfpt.h "Normal maps"); needs FLAG_TEXTURES and FLAG_SHADING_NORMALS
 FLAG_NORMAL_MAPS = 1 << 27
+FLAG_ROUGHNESS_MAPS = 1 << 28
+ROUGHNESS_REMAPS = ("linear", "squared")  # wfpt_roughness_remap, by value
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL = 0, 1, 2  # wfpt_light_type
 MAX_LIGHTS = 1024  # WFPT_MAX_LIGHTS
 ADAPTIVE_DEFAULTS = {"min_samples": 16, "max_samples": 0, "threshold": 0.05, "luminance_floor": 0.01, "dilate": 1}  # wfpt_adaptive_params_default
@@ -400,6 +402,10 @@ def lib():
         "wfpt_get_normal_map": (i32, [vp, u32, C.POINTER(C.c_int32), C.POINTER(f32)]),
         "wfpt_sample_normal_map": (i32, [vp, vp, sz, vp]),
         "wfpt_mapped_normal_host": (i32, [vp, sz, vp]),
+        "wfpt_bind_roughness_map": (i32, [vp, u32, C.c_int32, u32, u32]),
+        "wfpt_get_roughness_map": (i32, [vp, u32, C.POINTER(C.c_int32), C.POINTER(u32), C.POINTER(u32)]),
+        "wfpt_sample_roughness_map": (i32, [vp, vp, sz, vp]),
+        "wfpt_hit_roughness_host": (i32, [vp, u32, u32, sz, vp]),
         "wfpt_set_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_get_emission": (i32, [vp, u32, C.POINTER(f32)]),
         "wfpt_clear_emission": (i32, [vp]),
@@ -498,6 +504,27 @@ def mapped_normal_host(rows):
     st = lib().wfpt_mapped_normal_host(_p(a), a.shape[0], _p(out))
     if st != 0:
         raise WfptError(st, "wfpt_mapped_normal_host: invalid argument")
+    return out
+
+
+def _remap_value(remap):
+    if isinstance(remap, str):
+        if remap not in ROUGHNESS_REMAPS:
+            raise ValueError(f"remap must be one of {ROUGHNESS_REMAPS}, got {remap!r}")
+        return ROUGHNESS_REMAPS.index(remap)
+    return int(remap)
+
+
+def hit_roughness_host(rows, channel=1, remap="linear"):
+    """Steps R3-R4 of include/wfpt.h "Roughness maps" on the host (no GPU), from the function the kernels call. rows: (n, 4) float32 of
+    (alpha_m, c.r, c.g, c.b); channel 0, 1 or 2 and remap "linear" or "squared" for all rows; returns (n, 2) float32 of (alpha_h, r)."""
+    a = np.ascontiguousarray(rows, "<f4")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"hit_roughness_host: expected rows of 4 floats, got shape {a.shape}")
+    out = np.zeros((a.shape[0], 2), "<f4")
+    st = lib().wfpt_hit_roughness_host(_p(a), int(channel), _remap_value(remap), a.shape[0], _p(out))
+    if st != 0:
+        raise WfptError(st, "wfpt_hit_roughness_host: invalid argument")
     return out
 
 
@@ -1594,6 +1621,27 @@ class PathTracer:
         device's order as the BITS of the fourth float); returns (n, 4) float32 of (n.xyz, code): 0 mapped, 1 identity, 2 no tangent
         frame, 3 rejected, 4 the material has no map, 5 an index outside the scene."""
         return self._probe(lib().wfpt_sample_normal_map, "sample_normal_map", rows, 4, 4)
+
+    # ---- roughness maps (triangle contexts created with FLAG_ROUGHNESS_MAPS; include/wfpt.h "Roughness maps")
+    def bind_roughness_map(self, material_idx, slot, channel=1, remap="linear"):
+        """Material `material_idx` takes channel `channel` (0, 1, 2 = r, g, b) of the texture of slot `slot` as its roughness map: a hit
+        is sampled with set_roughness' alpha times min(texel, 1), squared first where remap is "squared" (glTF's perceptual roughness).
+        None or -1 unbinds it. Restarts the accumulation like a scene update."""
+        self._check(lib().wfpt_bind_roughness_map(self.handle, _material_index(material_idx), -1 if slot is None else slot, int(channel),
+                                                  _remap_value(remap)))
+        self.render_progress.reset()
+
+    def get_roughness_map(self, material_idx):
+        """(slot, channel, remap) of the material's roughness binding; (None, 0, "linear") where it has none."""
+        slot, channel, remap = C.c_int32(-1), C.c_uint32(0), C.c_uint32(0)
+        self._check(lib().wfpt_get_roughness_map(self.handle, _material_index(material_idx), C.byref(slot), C.byref(channel), C.byref(remap)))
+        return (None if slot.value < 0 else int(slot.value)), int(channel.value), ROUGHNESS_REMAPS[remap.value]
+
+    def sample_roughness_map(self, rows):
+        """The per-hit alpha for caller-supplied hits, computed on the device. rows: (n, 4) float32 of (p.xyz, the triangle's index in the
+        device's order as the BITS of the fourth float); returns (n, 4) float32 of (alpha_h, r, code, 0): 0 mapped, 1 the material has no
+        roughness binding, 2 its alpha is not above 0, 3 mapped and alpha_h is not above 0, 5 an index outside the scene."""
+        return self._probe(lib().wfpt_sample_roughness_map, "sample_roughness_map", rows, 4, 4)
 
     # ---- emission (contexts created with FLAG_EMISSION; include/wfpt.h "Emission")
     def set_emission(self, material_idx, rgb):

@@ -122,6 +122,12 @@ struct NmapTables {
     DeviceBuffer<uint4> prim;
 };
 
+// The roughness-map tables the kernels read (wfpt_ctx::rm_desc, rm_prim), built for a candidate state and then committed whole
+struct RmapTables {
+    DeviceBuffer<TexDev> desc;
+    DeviceBuffer<uint4> prim;
+};
+
 // The emission tables the kernels read (wfpt_ctx::em_prim, em_mat), built for a candidate state and then committed whole
 struct EmissionTables {
     DeviceBuffer<uint32_t> prim;
@@ -297,6 +303,14 @@ struct wfpt_ctx {
     std::vector<float> nm_strength;
     DeviceBuffer<TexDev> nm_desc;
     DeviceBuffer<uint4> nm_prim;
+    // WFPT_FLAG_ROUGHNESS_MAPS (include/wfpt.h "Roughness maps"): the binding per material (slot, -1 = none; channel | remap << 2) and
+    // what build_rmap_tables makes of them and of the roughnesses above for the kernels -- a copy of the slots' descriptors and the
+    // per-primitive {slot or kNoTexture, UV row, channel | remap << 2, alpha} table (both null while no material is bound; while no alpha
+    // is above 0 they are read by the probe only: the context then runs as one without the flag)
+    std::vector<int32_t> rm_bind;
+    std::vector<uint32_t> rm_mode;
+    DeviceBuffer<TexDev> rm_desc;
+    DeviceBuffer<uint4> rm_prim;
     // The per-hit shade records of the shading-normal and microfacet passes, 3 x float4 per ray-queue slot per sample in flight: one table
     // for the three features, allocated with the first of {table of normals, roughness above 0, normal map bound} and released with the last
     // (reserve_hit_table, commit_hit_table)
@@ -841,6 +855,13 @@ bool rough(const wfpt_ctx *c) { return c->mf_prim.get() != nullptr; }
 MicrofacetArgs microfacet_args(wfpt_ctx *c, uint32_t wavefront, const HitWalk &w, float4 *rec_out) {
     return MicrofacetArgs{w, c->scene.prim_geom, c->sn_rows.get(), c->mf_prim.get(), c->hit_table.get(), rec_out, wavefront};
 }
+// a WFPT_FLAG_ROUGHNESS_MAPS context is "roughness-mapped" while it is rough and a material holds a roughness binding: the record pass is
+// then the RMAP one of its kind; every other pass is the context's own
+bool roughness_bound(const wfpt_ctx *c) { return c->rm_prim.get() != nullptr; }
+bool roughness_mapped(const wfpt_ctx *c) { return roughness_bound(c) && c->mf_prim.get() != nullptr; }
+RmapScene rmap_scene(const wfpt_ctx *c) {
+    return RmapScene{c->rm_prim.get(), c->nm_prim.get(), c->rm_desc.get(), c->tex_uv.get(), c->sn_rows.get()};
+}
 // the shade steps that scatter read their shade records per hit (shaded_scene), from the table one of the two passes has just written
 bool per_hit(const wfpt_ctx *c) { return shading(c) || rough(c) || mapped(c); }
 // The per-hit table for a CANDIDATE state that needs one, into `out` unless the context already holds it; commit_hit_table(c, out, needed)
@@ -935,7 +956,11 @@ int enqueue_pre_shade(wfpt_ctx *c, Timed &timed, uint32_t b, uint32_t nb, const 
     if (textured(c)) WFPT_HIP(c, timed(pass_stage(kPassTexture), [&] { return launch_texture(texture_args(c, w), grid, c->stream.get()); }));
     if (emitting(c)) WFPT_HIP(c, timed(pass_stage(kPassEmission), [&] { return launch_emission_pass(c, emission_args(c, w), grid); }));
     if (connecting(c)) WFPT_HIP(c, timed(pass_stage(kPassConnect), [&] { return launch_connect_pass(c, connect_args(c, b, w), nb, shaded); }));
-    if (shade_rec_out && mapped(c)) // (booked where the pass it replaces is booked)
+    if (shade_rec_out && roughness_mapped(c)) // (roughness maps: rough, so booked as the microfacet pass; the normal is the context's kind)
+        WFPT_HIP(c, timed(pass_stage(kPassMicrofacet), [&] {
+            return launch_rmap_record(microfacet_args(c, b, w, shade_rec_out), rmap_scene(c), c->mf_glass, grid, c->stream.get());
+        }));
+    else if (shade_rec_out && mapped(c)) // (booked where the pass it replaces is booked)
         WFPT_HIP(c, timed(pass_stage(rough(c) ? kPassMicrofacet : kPassShading), [&] {
             return launch_nmap_record(microfacet_args(c, b, w, shade_rec_out), nmap_scene(c), c->mf_glass, grid, c->stream.get());
         }));
@@ -1753,6 +1778,12 @@ const FlagRule kFlagRules[] = {
      "(the pass slot, and the connect and AOV twins it stands in for)",
      "wfpt_create: WFPT_FLAG_NORMAL_MAPS does not go with WFPT_FLAG_LIGHT_POWER or WFPT_FLAG_ANALYTIC_LIGHTS "
      "(their connect kernels are twins of their own)"},
+    // WFPT_FLAG_ROUGHNESS_MAPS reads WFPT_FLAG_TEXTURES' slots and UV table and scales WFPT_FLAG_MICROFACET's alpha inside that flag's
+    // pass: it goes with everything that flag goes with
+    {WFPT_FLAG_ROUGHNESS_MAPS, WFPT_FLAG_TEXTURES | WFPT_FLAG_MICROFACET, 0,
+     "wfpt_create: WFPT_FLAG_ROUGHNESS_MAPS needs WFPT_FLAG_TEXTURES (the slots and the UV table) and WFPT_FLAG_MICROFACET "
+     "(the alpha per material it scales, and the pass)",
+     nullptr},
     // (WFPT_FLAG_ENV_MIS goes with no WFPT_FLAG_MIS either, since it weighs the emitters itself: the WFPT_FLAG_ENV_NEE it needs has
     // refused that at WFPT_FLAG_MIS's row)
     {WFPT_FLAG_ENV_MIS, WFPT_FLAG_ENVIRONMENT | kFlagsOfConnect | WFPT_FLAG_ENV_NEE, 0,
@@ -2026,7 +2057,7 @@ static int render_chunked_impl(const wfpt_params *params, const wfpt_sphere *sph
         p.tile_rank = k;
         p.tile_world = chunks;
         p.max_pixels = 0;
-        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC | WFPT_FLAG_NORMAL_MAPS); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
+        p.flags &= ~static_cast<uint32_t>(WFPT_FLAG_AOV | WFPT_FLAG_DENOISE | WFPT_FLAG_ENVIRONMENT | WFPT_FLAG_TEXTURES | WFPT_FLAG_EMISSION | WFPT_FLAG_NEE | WFPT_FLAG_ENV_NEE | WFPT_FLAG_MIS | WFPT_FLAG_ENV_MIS | WFPT_FLAG_RETIRE | WFPT_FLAG_LIGHT_POWER | WFPT_FLAG_ANALYTIC_LIGHTS | WFPT_FLAG_SHADING_NORMALS | WFPT_FLAG_MICROFACET | WFPT_FLAG_ROUGH_DIELECTRIC | WFPT_FLAG_NORMAL_MAPS | WFPT_FLAG_ROUGHNESS_MAPS); // path termination, AOVs / denoising / maps / textures / emitters (and connecting to them) / shading normals / roughness of chunked renders are out of scope (include/wfpt.h)
         p.flags |= WFPT_FLAG_NO_TILE_LISTS; // (a chunk's context is rendered once and destroyed: it would never use its lists)
         if (bands_of(h, k, chunks) == 0) continue; // more chunks than bands: nothing to render for this one
         g_last_status = WFPT_ERR_HIP;
@@ -2131,6 +2162,10 @@ static int build_nmap_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<i
 static void commit_nmap_tables(wfpt_ctx *c, NmapTables &&t);
 static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
                                  const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out, bool &glass);
+static int build_rmap_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mode,
+                             const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx, const std::vector<uint32_t> &mat_type,
+                             const std::vector<uint32_t> &row, RmapTables &out);
+static void commit_rmap_tables(wfpt_ctx *c, RmapTables &&t);
 static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *triangles, uint32_t n_prims, const wfpt_material *materials,
                              uint32_t n_materials, uint32_t n_bins) {
     if (!c || !(spheres || triangles) || !materials || n_prims == 0 || n_materials == 0)
@@ -2150,6 +2185,8 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     }
     if (spheres && mapped(c)) // WFPT_FLAG_NORMAL_MAPS with a binding: spheres take none
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a normal-map binding (unbind it first)");
+    if (spheres && roughness_bound(c)) // WFPT_FLAG_ROUGHNESS_MAPS with a binding (inert or not): spheres take none
+        return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a roughness-map binding (unbind it first)");
     if (spheres && rough(c)) // WFPT_FLAG_MICROFACET with a roughness above 0: spheres take none
         return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_update_scene: the context holds a roughness above 0 (clear it first)");
     WFPT_HIP(c, hipSetDevice(c->device));
@@ -2187,12 +2224,21 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
     DeviceBuffer<float> mf_prim; // likewise the roughness table; the alphas of materials the new scene no longer has are dropped
     std::vector<float> mf_alpha;
     bool mf_glass = false;
-    if (rough(c)) {
+    RmapTables rm_tables; // and the roughness-map tables with it; the bindings of such materials are dropped too (inert ones as well)
+    std::vector<int32_t> rm_bind = c->rm_bind;
+    std::vector<uint32_t> rm_mode = c->rm_mode;
+    if (rm_bind.size() > n_materials) {
+        rm_bind.resize(n_materials);
+        rm_mode.resize(n_materials);
+    }
+    if (rough(c) || roughness_bound(c)) { // (triangles: spheres were refused above)
         mf_alpha = c->mf_alpha;
         mf_alpha.resize(n_materials, 0.0f);
         std::vector<uint32_t> mat_type(n_prims);
         for (uint32_t i = 0; i < n_prims; ++i) mat_type[i] = triangles[i].material_type;
-        if (int r = build_roughness_table(c, mf_alpha, mat_idx, mat_type, mf_prim, mf_glass); r != WFPT_OK) return r;
+        if (rough(c))
+            if (int r = build_roughness_table(c, mf_alpha, mat_idx, mat_type, mf_prim, mf_glass); r != WFPT_OK) return r;
+        if (int r = build_rmap_tables(c, c->tex_dev, rm_bind, rm_mode, mf_alpha, mat_idx, mat_type, row, rm_tables); r != WFPT_OK) return r;
     }
     EmissionTables em_tables; // likewise; the colours of materials the new scene no longer has are dropped
     std::vector<float> em_rgb;
@@ -2224,6 +2270,9 @@ static int update_scene_impl(wfpt_ctx *c, wfpt_sphere *spheres, wfpt_triangle *t
         commit_nmap_tables(c, std::move(nm_tables));
         if (!rough(c)) commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
     }
+    c->rm_bind = std::move(rm_bind);
+    c->rm_mode = std::move(rm_mode);
+    commit_rmap_tables(c, std::move(rm_tables));
     if (rough(c)) { // (the dropped alphas may have been the last above 0: the per-hit records then go with them)
         c->mf_alpha = std::move(mf_alpha);
         c->mf_prim = std::move(mf_prim);
@@ -3427,11 +3476,15 @@ int wfpt_set_texture(wfpt_ctx *c, uint32_t slot, const float *rgb, uint32_t w, u
     if (int r = build_texture_tables(c, dev, c->tex_bind, c->h_prim_mat_idx, c->h_prim_row, tables); r != WFPT_OK) return r;
     NmapTables nm_tables; // (the normal-map bindings to the slot stay: their descriptors are the new texture's)
     if (int r = build_nmap_tables(c, dev, c->nm_bind, c->nm_strength, c->h_prim_mat_idx, c->h_prim_row, nm_tables); r != WFPT_OK) return r;
+    RmapTables rm_tables; // (and the roughness bindings)
+    if (int r = build_rmap_tables(c, dev, c->rm_bind, c->rm_mode, c->mf_alpha, c->h_prim_mat_idx, c->h_prim_mat_type, c->h_prim_row, rm_tables); r != WFPT_OK)
+        return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old texels
     c->tex_texels[slot] = std::move(tex);               // (frees the old texels: the old tables that named them go with them)
     std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
     commit_texture_tables(c, std::move(tables));
     commit_nmap_tables(c, std::move(nm_tables));
+    commit_rmap_tables(c, std::move(rm_tables));
     return scene_changed(c);
 }
 
@@ -3452,6 +3505,12 @@ int wfpt_clear_texture(wfpt_ctx *c, uint32_t slot) {
         if (b == static_cast<int32_t>(slot)) b = -1;
     NmapTables nm_tables;
     if (int r = build_nmap_tables(c, dev, nm_bind, c->nm_strength, c->h_prim_mat_idx, c->h_prim_row, nm_tables); r != WFPT_OK) return r;
+    std::vector<int32_t> rm_bind = c->rm_bind; // and the roughness bindings to it
+    for (int32_t &b : rm_bind)
+        if (b == static_cast<int32_t>(slot)) b = -1;
+    RmapTables rm_tables;
+    if (int r = build_rmap_tables(c, dev, rm_bind, c->rm_mode, c->mf_alpha, c->h_prim_mat_idx, c->h_prim_mat_type, c->h_prim_row, rm_tables); r != WFPT_OK)
+        return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get()));
     c->tex_texels[slot].release();
     std::copy(dev, dev + WFPT_MAX_TEXTURES, c->tex_dev);
@@ -3459,6 +3518,8 @@ int wfpt_clear_texture(wfpt_ctx *c, uint32_t slot) {
     commit_texture_tables(c, std::move(tables));
     c->nm_bind = std::move(nm_bind);
     commit_nmap_tables(c, std::move(nm_tables));
+    c->rm_bind = std::move(rm_bind);
+    commit_rmap_tables(c, std::move(rm_tables));
     commit_hit_table(c, DeviceBuffer<float4>(), per_hit(c));
     return scene_changed(c);
 }
@@ -3688,18 +3749,21 @@ int wfpt_mapped_normal_host(const float *in22, size_t n, float *out4) {
 // alpha is above 0. glass: a dielectric primitive's entry is above 0 (the pass is then rough_glass_kernel). Built for a CANDIDATE state -- alphas (one
 // per material, missing ones 0), and per primitive its material_idx and material_type -- without touching the context, like
 // build_emission_tables.
+// the alpha of a primitive of material m and material_type `type` under the candidate alphas: the entry of both tables below
+static float prim_alpha(const wfpt_ctx *c, const std::vector<float> &alpha, uint32_t m, uint32_t type) {
+    const bool counts = type == 1u || ((c->p.flags & WFPT_FLAG_ROUGH_DIELECTRIC) != 0 && type == 2u);
+    return counts && m < alpha.size() ? alpha[m] : 0.0f;
+}
 static int build_roughness_table(wfpt_ctx *c, const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx,
                                  const std::vector<uint32_t> &mat_type, DeviceBuffer<float> &out, bool &glass) {
     glass = false;
     bool any = false;
     for (float a : alpha) any = any || a > 0.0f;
     if (!any) return WFPT_OK;
-    const bool dielectrics = (c->p.flags & WFPT_FLAG_ROUGH_DIELECTRIC) != 0;
     const size_t n = mat_idx.size();
     std::vector<float> t(n);
     for (size_t i = 0; i < n; ++i) {
-        const bool counts = mat_type[i] == 1u || (dielectrics && mat_type[i] == 2u);
-        t[i] = counts && mat_idx[i] < alpha.size() ? alpha[mat_idx[i]] : 0.0f;
+        t[i] = prim_alpha(c, alpha, mat_idx[i], mat_type[i]);
         glass = glass || (mat_type[i] == 2u && t[i] > 0.0f);
     }
     WFPT_HIP(c, out.alloc(n));
@@ -3721,10 +3785,14 @@ static int apply_roughness(wfpt_ctx *c, const char *who, std::vector<float> &&al
     DeviceBuffer<float4> table;
     bool glass = false;
     if (int r = build_roughness_table(c, alpha, c->h_prim_mat_idx, c->h_prim_mat_type, prim, glass); r != WFPT_OK) return r;
+    RmapTables rm_tables; // (the roughness bindings stay: their rows hold the new alphas)
+    if (int r = build_rmap_tables(c, c->tex_dev, c->rm_bind, c->rm_mode, alpha, c->h_prim_mat_idx, c->h_prim_mat_type, c->h_prim_row, rm_tables); r != WFPT_OK)
+        return r;
     if (prim.get())
         if (int r = reserve_hit_table(c, table); r != WFPT_OK) return r;
     WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old table
     commit_hit_table(c, std::move(table), prim.get() != nullptr || shading(c) || mapped(c));
+    commit_rmap_tables(c, std::move(rm_tables));
     c->mf_prim = std::move(prim); // (the kernel takes it from the context at each launch; the graphs that hold the old one are dropped)
     c->mf_glass = glass;
     c->mf_alpha = std::move(alpha);
@@ -3773,6 +3841,100 @@ int wfpt_sample_rough_dielectric(wfpt_ctx *c, const float *in16, size_t n, float
 int wfpt_microfacet_timing_ms(wfpt_ctx *c, float *ms_total, uint32_t *launches) {
     if (int r = microfacet_check(c, "wfpt_microfacet_timing_ms"); r != WFPT_OK) return r;
     return pass_timing(c, kPassMicrofacet, ms_total, launches);
+}
+
+// ---------------------------------------------------------------- roughness maps (include/wfpt.h "Roughness maps")
+// The record kernels' view of the bindings, the roughnesses, the slots and the scene: a copy of the descriptor array and per primitive
+// {slot or kNoTexture, UV row, channel | remap << 2, the bits of build_roughness_table's entry}, in the order the device holds the
+// primitives (both null while no material is bound). Built whole for a CANDIDATE state without touching the context, like
+// build_nmap_tables.
+static int build_rmap_tables(wfpt_ctx *c, const TexDev *dev, const std::vector<int32_t> &bind, const std::vector<uint32_t> &mode,
+                             const std::vector<float> &alpha, const std::vector<uint32_t> &mat_idx, const std::vector<uint32_t> &mat_type,
+                             const std::vector<uint32_t> &row, RmapTables &out) {
+    bool bound = false;
+    for (int32_t b : bind) bound = bound || b >= 0;
+    if (!bound) return WFPT_OK;
+    const size_t n = mat_idx.size();
+    std::vector<uint4> t(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t slot = mat_idx[i] < bind.size() ? bind[mat_idx[i]] : -1;
+        const float a = prim_alpha(c, alpha, mat_idx[i], mat_type[i]);
+        uint32_t bits;
+        std::memcpy(&bits, &a, sizeof(bits));
+        t[i] = make_uint4(slot >= 0 ? static_cast<uint32_t>(slot) : kNoTexture, row[i], slot >= 0 ? mode[mat_idx[i]] : 0u, bits);
+    }
+    WFPT_HIP(c, out.desc.alloc(WFPT_MAX_TEXTURES));
+    WFPT_HIP(c, out.prim.alloc(n));
+    WFPT_HIP(c, hipMemcpy(out.desc.get(), dev, sizeof(TexDev) * WFPT_MAX_TEXTURES, hipMemcpyHostToDevice));
+    WFPT_HIP(c, hipMemcpy(out.prim.get(), t.data(), sizeof(uint4) * n, hipMemcpyHostToDevice));
+    return WFPT_OK;
+}
+// the new tables replace the old ones (the stream is idle: the caller synchronised it)
+static void commit_rmap_tables(wfpt_ctx *c, RmapTables &&t) {
+    c->rm_desc = std::move(t.desc);
+    c->rm_prim = std::move(t.prim);
+}
+
+static int rmap_check(wfpt_ctx *c, const char *who) { return flag_check(c, who, WFPT_FLAG_ROUGHNESS_MAPS, "WFPT_FLAG_ROUGHNESS_MAPS"); }
+
+int wfpt_bind_roughness_map(wfpt_ctx *c, uint32_t material_idx, int32_t slot, uint32_t channel, uint32_t remap) {
+    const char *who = "wfpt_bind_roughness_map";
+    if (int r = rmap_check(c, who); r != WFPT_OK) return r;
+    if (c->scene.prim_kind != 1) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": a sphere context takes no roughness maps");
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": material_idx out of range");
+    if (slot < -1 || slot >= static_cast<int32_t>(WFPT_MAX_TEXTURES)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": slot out of range");
+    // the class-binned refusal, of a call that binds only (unbinding is always allowed); ahead of the empty slot's, as wfpt_bind_normal_map's
+    if (int r = feature_check(c, who, WFPT_FLAG_ROUGHNESS_MAPS, "WFPT_FLAG_ROUGHNESS_MAPS", slot >= 0 ? "roughness maps" : nullptr); r != WFPT_OK) return r;
+    if (slot >= 0 && !c->tex_texels[slot].get()) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": the slot holds no texture");
+    if (slot >= 0 && channel > 2u) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": channel must be 0, 1 or 2");
+    if (slot >= 0 && remap > WFPT_ROUGHNESS_SQUARED) return fail(c, WFPT_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown remap");
+    WFPT_HIP(c, hipSetDevice(c->device));
+    std::vector<int32_t> bind = c->rm_bind;
+    std::vector<uint32_t> mode = c->rm_mode;
+    if (bind.size() <= material_idx) {
+        bind.resize(material_idx + 1u, -1);
+        mode.resize(material_idx + 1u, 0u);
+    }
+    bind[material_idx] = slot;
+    mode[material_idx] = slot >= 0 ? (channel | remap << 2) : 0u;
+    RmapTables tables; // (a roughness-mapped context is rough: it holds the per-hit records already)
+    if (int r = build_rmap_tables(c, c->tex_dev, bind, mode, c->mf_alpha, c->h_prim_mat_idx, c->h_prim_mat_type, c->h_prim_row, tables); r != WFPT_OK) return r;
+    WFPT_HIP(c, hipStreamSynchronize(c->stream.get())); // nothing in flight may still read the old tables
+    c->rm_bind = std::move(bind);
+    c->rm_mode = std::move(mode);
+    commit_rmap_tables(c, std::move(tables));
+    return scene_changed(c);
+}
+
+int wfpt_get_roughness_map(wfpt_ctx *c, uint32_t material_idx, int32_t *slot, uint32_t *channel, uint32_t *remap) {
+    if (int r = rmap_check(c, "wfpt_get_roughness_map"); r != WFPT_OK) return r;
+    if (material_idx >= c->scene.n_materials) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_get_roughness_map: material_idx out of range");
+    const bool bound = material_idx < c->rm_bind.size() && c->rm_bind[material_idx] >= 0;
+    if (slot) *slot = bound ? c->rm_bind[material_idx] : -1;
+    if (channel) *channel = bound ? c->rm_mode[material_idx] & 3u : 0u;
+    if (remap) *remap = bound ? c->rm_mode[material_idx] >> 2 : 0u;
+    return WFPT_OK;
+}
+
+int wfpt_sample_roughness_map(wfpt_ctx *c, const float *in4, size_t n, float *out4) {
+    if (int r = rmap_check(c, "wfpt_sample_roughness_map"); r != WFPT_OK) return r;
+    const bool null_argument = (!in4 || !out4) && n; // (reported by probe, ahead of a missing binding)
+    if (!null_argument && !roughness_bound(c)) return fail(c, WFPT_ERR_INVALID_ARGUMENT, "wfpt_sample_roughness_map: no roughness map is bound");
+    return probe(c, "wfpt_sample_roughness_map", in4, 4, out4, 4, n, true, [&](const float *d_in, float *d_out) {
+        return launch_rmap_sample(c->scene.prim_geom, rmap_scene(c), c->scene.n_spheres, d_in, d_out, static_cast<uint32_t>(n), c->stream.get());
+    });
+}
+
+// Steps R3-R4 on the host, from the function the kernels call (this file's host side is compiled without contraction, as the device side)
+int wfpt_hit_roughness_host(const float *in4, uint32_t channel, uint32_t remap, size_t n, float *out2) {
+    if (((!in4 || !out2) && n) || channel > 2u || remap > WFPT_ROUGHNESS_SQUARED) return WFPT_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = in4 + 4u * i;
+        float f;
+        out2[2u * i] = hit_roughness(r[0], {r[1], r[2], r[3]}, channel, remap, f);
+        out2[2u * i + 1u] = f;
+    }
+    return WFPT_OK;
 }
 
 // ---------------------------------------------------------------- emission (include/wfpt.h "Emission")

@@ -293,6 +293,16 @@ __host__ __device__ __forceinline__ uint32_t mapped_normal(float3_ ng, float3_ n
     return 0u;
 }
 
+// ---------------- roughness maps (WFPT_FLAG_ROUGHNESS_MAPS; include/wfpt.h "Roughness maps") ----------------
+// Steps R3-R4 of the header in its operation order, the same rules again (no fma, min as minNum); restated bit for bit by
+// tests/roughness_map_ref.py. The GGX alpha a mapped hit is sampled with: the material's alpha_m scaled by channel `channel` (0, 1, 2 = r,
+// g, b) of the texel c, clamped at 1 and, where remap is WFPT_ROUGHNESS_SQUARED (1), squared. r: the factor.
+__host__ __device__ __forceinline__ float hit_roughness(float alpha_m, float3_ c, uint32_t channel, uint32_t remap, float &r) {
+    r = __builtin_fminf(channel == 0u ? c.x : channel == 1u ? c.y : c.z, 1.0f);
+    if (remap == 1u) r = r * r;
+    return alpha_m * r;
+}
+
 // index of a texel coordinate c0 (floor of a float, expected in -1 .. n-1) and of c0 + 1, both wrapped into 0 .. n-1; NaN reads index n-1
 __host__ __device__ __forceinline__ void wrap_pair(float c0, float fn, uint32_t n, uint32_t &i0, uint32_t &i1) {
     const int k = static_cast<int>(__builtin_fminf(__builtin_fmaxf(c0, -1.0f), fn - 1.0f)); // -1 .. n-1

@@ -645,6 +645,20 @@ struct NmapScene {
     const float4 *normals;
 };
 
+// Roughness maps (WFPT_FLAG_ROUGHNESS_MAPS contexts that hold a roughness above 0 and a binding, include/wfpt.h "Roughness maps"), as the
+// record kernels of such a context read them: per PRIMITIVE, in the order the device holds them, {texture slot or kNoTexture, UV row,
+// channel | remap << 2, the bits of the material's alpha as MicrofacetArgs::mf_prim holds it} -- the bindings resolved through each
+// primitive's material_idx and _pad on the host (build_rmap_tables) --, the normal-map rows of NmapScene::prim_map (null = the context
+// is not mapped), the WFPT_MAX_TEXTURES descriptors, the UV rows (null = (0, 0) at every corner) and the shading-normal pass's rows of
+// corner normals (null = no table is set). Passed by value, as NmapScene.
+struct RmapScene {
+    const uint4 *prim_rough;
+    const uint4 *prim_map;
+    const TexDev *tex;
+    const float *uv6;
+    const float4 *normals;
+};
+
 struct AccumulateArgs {
     Batch batch;
     const float *image;
@@ -876,6 +890,15 @@ hipError_t launch_nmap_record(const MicrofacetArgs &a, const NmapScene &nm, bool
 // outside the scene answers (0, 0, 0, 5)
 hipError_t launch_nmap_sample(const float4 *prim_geom, const float4 *shade_rec, const NmapScene &nm, uint32_t n_prims, const float *in4,
                               float *out4, uint32_t n, hipStream_t s);
+// The record pass of a roughness-mapped context (include/wfpt.h "Roughness maps"), in the place of launch_microfacet or launch_nmap_record
+// (microfacet_rmap_kernel) or, with glass, launch_rough_glass (rough_glass_rmap_kernel): the same walk, table and slot rewrite; a rough
+// hit of a bound material is sampled with alpha_m * the map's factor, or gets a non-rough hit's record where that is not above 0. The
+// normal is the mapped one (rm.prim_map set), the shading one (rm.normals set) or the stored one. a.normals and a.mf_prim are ignored.
+hipError_t launch_rmap_record(const MicrofacetArgs &a, const RmapScene &rm, bool glass, uint32_t grid, hipStream_t s);
+// wfpt_sample_roughness_map: n rows of (p.xyz | the primitive's bits) -> (alpha_h | r | the header's probe code | 0), one thread per row;
+// a primitive outside the scene answers (0, 0, 5, 0)
+hipError_t launch_rmap_sample(const float4 *prim_geom, const RmapScene &rm, uint32_t n_prims, const float *in4, float *out4, uint32_t n,
+                              hipStream_t s);
 // The sampling distribution of a light list (include/wfpt.h "Light selection by power"), built on the device on `s`. lights: the n_l
 // primitives that emit, in list order; geom / prim_kind: the primitives they index (SceneDev::prim_geom's layout); prim_em / em: the
 // emission tables. First f = L * A per light into `f` and the bits of the largest f > 0 into *max_bits (zeroed by the caller); then, once the

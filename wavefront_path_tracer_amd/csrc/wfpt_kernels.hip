@@ -2514,6 +2514,116 @@ __global__ __launch_bounds__(256) void nmap_sample_kernel(const float4 *prim_geo
 }
 
 // ================================================================================================
+// roughness maps (WFPT_FLAG_ROUGHNESS_MAPS; include/wfpt.h "Roughness maps")
+// ================================================================================================
+// The normal a hit at point p of triangle `prim` with stored normal ng scatters about and the GGX alpha it is sampled with, on a
+// roughness-mapped context. n: what the replaced kernel has, bit for bit -- mapped_normal_at's answer where the context is mapped
+// (rm.prim_map), shading_normal_at's where it holds a table of corner normals only, ng otherwise (block-uniform pointer tests). alpha:
+// steps R1-R4 -- the entry's alpha_m where that is not above 0 or the material has no roughness binding, else alpha_m * hit_roughness'
+// factor of the binding's texel. One 16-byte gather (the entry) decides; the triangle's geometry is read only where a normal or a lookup
+// needs it, and a hit with both a normal map and a roughness map forms triangle_uv once (the UV row is the primitive's, whichever
+// binding names it). Returns the header's probe code (r: the factor, 1 without a binding, 0 without an alpha).
+__device__ __forceinline__ uint32_t hit_normal_alpha(const RmapScene &rm, const float4 *prim_geom, uint32_t prim, float3_ p, float3_ ng, float3_ &n,
+                                                     float &alpha, float &r) {
+    const uint4 e = rm.prim_rough[prim];
+    const float alpha_m = __uint_as_float(e.w);
+    const bool rough = alpha_m > 0.0f;              // R1.
+    const bool looks = rough && e.x != kNoTexture;  // R2.
+    alpha = rough ? alpha_m : 0.0f;
+    r = rough ? 1.0f : 0.0f;
+    n = ng;
+    const uint32_t code = !rough ? 2u : !looks ? 1u : 0u;
+    if (!rm.prim_map && !rm.normals && !looks) return code;
+    const float4 g0 = prim_geom[3u * prim], g1 = prim_geom[3u * prim + 1u], g2 = prim_geom[3u * prim + 2u];
+    const float3_ v0 = {g0.x, g0.y, g0.z}, e1 = {g1.x, g1.y, g1.z}, e2 = {g2.x, g2.y, g2.z};
+    float3_ ns = ng;
+    if (rm.normals) {
+        const float4 r0 = rm.normals[3u * prim], r1 = rm.normals[3u * prim + 1u], r2 = rm.normals[3u * prim + 2u];
+        shading_normal(p, v0, e1, e2, ng, {r0.x, r0.y, r0.z}, {r1.x, r1.y, r1.z}, {r2.x, r2.y, r2.z}, ns);
+    }
+    n = ns;
+    uint4 m = make_uint4(kNoTexture, 0u, 0u, 0u);
+    if (rm.prim_map) m = rm.prim_map[prim];
+    const bool bumps = m.x != kNoTexture;
+    if (!bumps && !looks) return code;
+    float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (rm.uv6) {
+        const float2 *row = reinterpret_cast<const float2 *>(rm.uv6 + 6u * static_cast<size_t>(e.y));
+        const float2 q0 = row[0], q1 = row[1], q2 = row[2];
+        uv[0] = q0.x; uv[1] = q0.y; uv[2] = q1.x; uv[3] = q1.y; uv[4] = q2.x; uv[5] = q2.y;
+    }
+    float u, v;
+    triangle_uv(p, v0, e1, e2, uv, u, v); // normal-map step A and R3's, once
+    if (bumps) mapped_normal(ng, ns, e1, e2, uv, tex_lookup(rm.tex[m.x], u, v), __uint_as_float(m.z), n);
+    if (!looks) return code;
+    alpha = hit_roughness(alpha_m, tex_lookup(rm.tex[e.x], u, v), e.z & 3u, e.z >> 2, r); // R3-R4.
+    return alpha > 0.0f ? 0u : 3u;
+}
+
+// The record pass of a roughness-mapped context, one text for the two kernels below. KIND 1: microfacet_kernel's (or
+// microfacet_nmap_kernel's) records; 2: rough_glass_kernel's (or rough_glass_nmap_kernel's) -- each with the per-hit alpha in alpha's
+// place (R5: a hit whose alpha_h is not above 0 gets the record of a non-rough hit), the same draws from the same streams, the same
+// normal and the same slot rewrite.
+template <int KIND>
+__device__ __forceinline__ void rmap_record_body(const MicrofacetArgs &a, const RmapScene &rm) {
+    const SampleHits s = sample_hits(a.w, blockIdx.y);
+    const uint32_t frame = uniform(a.w.ctl->frame.frame) + blockIdx.y; // (as microfacet_kernel takes it)
+    for_each_shaded_hit<true>(a.w, s, [&](size_t slot, const Hit &h) {
+        const float4 rec0 = a.w.shade_rec[3u * h.prim], rec1 = a.w.shade_rec[3u * h.prim + 1u], rec2 = a.w.shade_rec[3u * h.prim + 2u];
+        float3_ n;
+        float alpha, r;
+        hit_normal_alpha(rm, a.prim_geom, h.prim, h.p, {rec0.x, rec0.y, rec0.z}, n, alpha, r);
+        float4 o0 = make_float4(n.x, n.y, n.z, rec0.w), o1 = rec1, o2 = rec2;
+        if (alpha > 0.0f) { // R5.
+            const bool glass = KIND == 2 && __float_as_uint(rec2.x) == 2u;
+            uint32_t rng = jenkins_hash(h.pixel_idx ^ jenkins_hash(frame));
+            rng = jenkins_hash(rng ^ ((glass ? kRoughGlassStream : 0xC2B2AE35u) * (a.wavefront + 1u)));
+            const float u1 = rng_next_float(rng);
+            const float u2 = rng_next_float(rng);
+            if (glass) {
+                const float u3 = rng_next_float(rng);
+                const RoughGlassSample gs = rough_glass_sample(h.d, n, u1, u2, u3, alpha, rec1.w, {rec1.x, rec1.y, rec1.z});
+                if (!gs.fell) {
+                    o0 = make_float4(gs.h.x, gs.h.y, gs.h.z, 0.0f);
+                    o1 = make_float4(gs.weight.x, gs.weight.y, gs.weight.z, rec1.w);
+                    o2.x = __uint_as_float(1u);
+                }
+            } else {
+                const MicrofacetSample ms = microfacet_sample(h.d, n, u1, u2, alpha, {rec1.x, rec1.y, rec1.z});
+                if (!ms.fell) {
+                    o0 = make_float4(ms.m.x, ms.m.y, ms.m.z, 0.0f);
+                    o1 = make_float4(ms.weight.x, ms.weight.y, ms.weight.z, rec1.w);
+                }
+            }
+        }
+        float4 *out = a.table + 3u * slot;
+        out[0] = o0;
+        out[1] = o1;
+        out[2] = o2;
+        a.rec_out[2u * slot + 1u].w = __uint_as_float(static_cast<uint32_t>(slot)); // (3 * slot stays below 2^32: wfpt_create's size check)
+    });
+}
+__global__ __launch_bounds__(kConsumerThreads) void microfacet_rmap_kernel(MicrofacetArgs a, RmapScene rm) { rmap_record_body<1>(a, rm); }
+__global__ __launch_bounds__(kConsumerThreads) void rough_glass_rmap_kernel(MicrofacetArgs a, RmapScene rm) { rmap_record_body<2>(a, rm); }
+
+// wfpt_sample_roughness_map: hit_normal_alpha for caller rows of (p | the primitive's bits), one thread per row
+__global__ __launch_bounds__(256) void rmap_sample_kernel(const float4 *prim_geom, RmapScene rm, uint32_t n_prims, const float *in4, float *out4,
+                                                          uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *row = in4 + 4u * static_cast<size_t>(i);
+    const uint32_t prim = __float_as_uint(row[3]);
+    float alpha = 0.0f, r = 0.0f;
+    uint32_t code = 5u;
+    if (prim < n_prims) {
+        float3_ nn;
+        code = hit_normal_alpha(rm, prim_geom, prim, {row[0], row[1], row[2]}, {0.0f, 0.0f, 0.0f}, nn, alpha, r);
+    }
+    float *out = out4 + 4u * static_cast<size_t>(i);
+    out[0] = alpha; out[1] = r; out[2] = static_cast<float>(code); out[3] = 0.0f;
+}
+
+// ================================================================================================
 // emission pass (WFPT_FLAG_EMISSION; include/wfpt.h "Emission")
 // ================================================================================================
 // The normal nl of light primitive `prim` at its point q and the primitive's area (include/wfpt.h "Next-event estimation", step 3's
@@ -5237,6 +5347,23 @@ hipError_t launch_nmap_sample(const float4 *prim_geom, const float4 *shade_rec, 
     if (n == 0) return hipSuccess;
     if (!nm.prim_map || !nm.tex) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nmap_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, prim_geom, shade_rec, nm, n_prims, in4, out4, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_rmap_record(const MicrofacetArgs &a, const RmapScene &rm, bool glass, uint32_t grid, hipStream_t s) {
+    if (grid == 0) return hipSuccess;
+    if (!rm.prim_rough || !rm.tex || !a.table || !a.rec_out) return hipErrorInvalidValue;
+    const dim3 g(grid, a.w.batch.n), b(kConsumerThreads);
+    if (glass) hipLaunchKernelGGL(rough_glass_rmap_kernel, g, b, 0, s, a, rm);
+    else hipLaunchKernelGGL(microfacet_rmap_kernel, g, b, 0, s, a, rm);
+    return hipGetLastError();
+}
+
+hipError_t launch_rmap_sample(const float4 *prim_geom, const RmapScene &rm, uint32_t n_prims, const float *in4, float *out4, uint32_t n,
+                              hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (!rm.prim_rough || !rm.tex) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rmap_sample_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, prim_geom, rm, n_prims, in4, out4, n);
     return hipGetLastError();
 }
 

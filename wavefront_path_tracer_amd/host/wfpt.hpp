@@ -402,6 +402,30 @@ class PathTracer {
         if (wfpt_mapped_normal_host(in22.data(), in22.size() / 22, out.data()) != WFPT_OK) throw Error(WFPT_ERR_INVALID_ARGUMENT, "wfpt_mapped_normal_host");
         return out;
     }
+    // Roughness maps (WFPT_FLAG_ROUGHNESS_MAPS, include/wfpt.h "Roughness maps"): a material takes one channel of a texture slot as the
+    // per-hit factor of its GGX alpha (glTF keeps roughness in g, perceptual: WFPT_ROUGHNESS_SQUARED); slot -1 unbinds.
+    struct RoughnessMap {
+        int32_t slot; // -1 = none
+        uint32_t channel, remap;
+    };
+    void bind_roughness_map(uint32_t material_idx, int32_t slot, uint32_t channel = 1, uint32_t remap = WFPT_ROUGHNESS_LINEAR) {
+        check(wfpt_bind_roughness_map(ctx_, material_idx, slot, channel, remap));
+    }
+    RoughnessMap roughness_map(uint32_t material_idx) {
+        RoughnessMap m{-1, 0u, 0u};
+        check(wfpt_get_roughness_map(ctx_, material_idx, &m.slot, &m.channel, &m.remap));
+        return m;
+    }
+    std::vector<float> sample_roughness_map(const std::vector<float> &in4) { // (p.xyz | the triangle's bits) -> (alpha_h | r | code | 0)
+        std::vector<float> out(in4.size() / 4 * 4);
+        check(wfpt_sample_roughness_map(ctx_, in4.data(), in4.size() / 4, out.data()));
+        return out;
+    }
+    static std::vector<float> hit_roughness_host(const std::vector<float> &in4, uint32_t channel, uint32_t remap) { // (alpha_m, c.rgb) -> (alpha_h, r)
+        std::vector<float> out(in4.size() / 4 * 2);
+        if (wfpt_hit_roughness_host(in4.data(), channel, remap, in4.size() / 4, out.data()) != WFPT_OK) throw Error(WFPT_ERR_INVALID_ARGUMENT, "wfpt_hit_roughness_host");
+        return out;
+    }
     // Emission (WFPT_FLAG_EMISSION, include/wfpt.h "Emission"): a material with a non-zero colour lights the scene and ends the paths that hit it.
     void set_emission(uint32_t material_idx, std::array<float, 3> rgb) { check(wfpt_set_emission(ctx_, material_idx, rgb.data())); }
     std::array<float, 3> emission(uint32_t material_idx) {
